@@ -15,7 +15,8 @@ Unit: 1 frame = one NSNet2 STFT frame of one channel = 10 ms of audio (SURVEY.md
 BASELINE.json calls it a "20 ms frame" after its window length).  Streams shard across ranks with
 no data-path collective (weak scaling: every rank processes the same amount of audio); the only
 collective is the final all_gather of per-stream Evaluator statistics (RCCL), outside the steps.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  `--dump-outputs DIR` also writes
+what the last timed step computed as .npy files (dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import importlib.util
@@ -75,7 +76,15 @@ def parse():
     ap.add_argument("--cfg4-seconds", type=int, default=7200, help="seconds per stream (a multiple of 600)")
     ap.add_argument("--cfg4-one-call", action="store_true",
                     help="config 4: one device-resident call per step and the host VAD behind it (rounds 1-4) instead of time slices with the host VAD beside the GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed (rank 0's streams) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB in all (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "headline":
+        ap.error("--dump-outputs writes the headline's outputs; --config cfg4 does not run it")
+    return args
 
 
 def make_inputs(pkg, rank, lanes, seconds):
@@ -156,6 +165,43 @@ def check_against_oracle(ctx, weights, host_pcm, lanes, d_den, n_samp, band, seg
     out["ok"] = bool(out["max_err"]["denoised_of_peak"] <= 1e-4 and out["max_err"]["band_sum_rel"] <= 1e-4
                      and out["segments_identical"] and np.isfinite(out["max_err"]["denoised_of_peak"]))
     return out
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: everything it writes, .npy headers included
+DUMP_SEED = 20251015
+NPY_HEADER = 128            # bytes np.save puts in front of a 1-D or 2-D array
+
+
+def seeded_rows(n, row_bytes, budget, rng):
+    """row indices of an output to dump: all n rows if they fit in `budget` bytes, else a seeded sample of them, sorted"""
+    k = int(min(n, budget // row_bytes))
+    return np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, ctx, d_den, n_chunks, band, rms, segments):
+    """--dump-outputs: what fvad_engine_enqueue_device and the host VAD handed back for the last timed step, as
+    out_dir/<name>.npy.  The inputs and DUMP_SEED are fixed, so two builds run with the same arguments can be compared file
+    for file.
+      segments         [n, 5] float64: lane, sample_from, sample_to, avg_channel_vol_ratio, vad_met_sec, every lane
+      band_sum         [k, n_fft_frames] float32 and chunk_rms [k, n_chunks] float32 of the lanes in band_lanes [k] (float64):
+                       every lane unless they would take over a quarter of DUMP_BYTES
+      denoised         [m, CHUNK] float32: a seeded sample of (lane, chunk) blocks of the denoised audio (all of it is
+                       lanes x 12 MB at the default size), filling the rest of DUMP_BYTES; denoised_chunks [m, 2] float64
+                       holds each block's lane and chunk"""
+    rng = np.random.default_rng(DUMP_SEED)
+    lanes = band.shape[0]
+    out = {"segments": np.array([(lane, *s) for lane, segs in enumerate(segments) for s in segs], np.float64).reshape(-1, 5)}
+    rows = seeded_rows(lanes, band[0].nbytes + rms[0].nbytes, DUMP_BYTES // 4, rng)
+    out.update(band_sum=band[rows], chunk_rms=rms[rows], band_lanes=rows.astype(np.float64))
+    left = DUMP_BYTES - sum(a.nbytes + NPY_HEADER for a in out.values()) - 2 * NPY_HEADER
+    picks = seeded_rows(lanes * n_chunks, CHUNK * 4 + 16, left, rng)
+    den = np.empty((len(picks), CHUNK), np.float32)
+    for row, i in zip(den, picks):          # lane l's chunk c is block l * n_chunks + c of d_den
+        ctx.to_host(row, d_den + int(i) * CHUNK * 4)
+    out.update(denoised=den, denoised_chunks=np.stack([picks // n_chunks, picks % n_chunks], 1).astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def gather_all_stats(pkg, fv, ctx, dist, world, args, cdev, local_ids, local_stats, n_streams):
@@ -590,6 +636,9 @@ def main():
         ktimes = ctx.kernel_times()              # sums over the K timed steps, HIP events on ctx's stream
         ctx.enable_timing(False)
         path = ctx.last_nn_path()
+        if args.dump_outputs and tag == "timed" and rank == 0:     # before the device-only pass below rewrites the buffers
+            last = (args.steps - 1) & 1
+            dump_outputs(args.dump_outputs, ctx, d_den, n_chunks, h_band[last], h_rms[last], results[(tag, args.steps - 1)])
         # self-check of the configuration that was just timed: two lanes of the LAST timed step (the first and
         # the last of the batch) against the CPU oracle -- denoised audio, band sums, segment boundaries
         check = None

@@ -1461,6 +1461,32 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     assert bad.returncode == 2 and "rank" in bad.stderr
 
 
+def test_bench_dump_outputs_are_bounded_and_the_same_on_every_run(tmp_path):
+    # --dump-outputs: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most, from inputs that are the
+    # same on every run.  32 lanes x 128 s = 8192 chunks, one launch of the persistent GEMM path: the same bits every run.
+    import json
+    import subprocess
+    import sys
+    runs = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lanes", "32", "--seconds", "128", "--steps", "3",
+               "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-emulated", "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["self_check"]["ok"]
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert set(a) == {"segments", "band_sum", "chunk_rms", "band_lanes", "denoised", "denoised_chunks"}
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= 64_000_000
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["band_sum"].shape == (32, 128 * 48000 // 1024) and a["chunk_rms"].shape == (32, 256)
+    assert a["denoised"].shape == (a["denoised_chunks"].shape[0], 24000) and a["denoised"].shape[0] > 100
+    assert len(a["segments"]) >= 32 and set(a["segments"][:, 0]) == set(range(32))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 # ------------------------------------------------------------------ K1's own outputs (NSNet2.zig:239-287)
 def test_k1_spectrogram_and_features_taps_match_oracle(fv, gpu_ctx, weights7, pkg):
     # fvad_lane.spectrogram / .features expose what stft_kernel hands to the network and to K3 -- not the
