@@ -276,6 +276,8 @@ pub extern "c" fn fvad_engine_opts_default(o: *EngineOpts) void;
 pub extern "c" fn fvad_engine_run(ctx: *Ctx, lanes: [*]Lane, n_lanes: usize, opts: ?*const EngineOpts) c_int;
 pub extern "c" fn fvad_engine_enqueue_device(ctx: *Ctx, d_pcm: [*]const f32, n_lanes: usize, lane_stride: usize, n_samples: usize, d_denoised: ?[*]f32, d_band_sum: [*]f32, d_chunk_rms: ?[*]f32, opts: ?*const EngineOpts) c_int;
 pub extern "c" fn fvad_engine_enqueue_device_i16(ctx: *Ctx, d_pcm16: [*]const i16, n_lanes: usize, lane_stride: usize, n_samples: usize, d_denoised16: ?[*]i16, d_band_sum: [*]f32, d_chunk_rms: ?[*]f32, opts: ?*const EngineOpts) c_int;
+/// several speech bands' sums in one pass over device-resident denoised audio (see fvad.h)
+pub extern "c" fn fvad_engine_band_sums_device(ctx: *Ctx, d_denoised: [*]const f32, n_lanes: usize, lane_stride: usize, n_samples: usize, fft_size: usize, bins: [*]const i32, n_bands: usize, d_band_sum: [*]f32, band_stride: usize) c_int;
 pub extern "c" fn fvad_nsnet2_forward(ctx: *Ctx, features: [*]const f32, n_seq: usize, T: usize, gains: [*]f32) c_int;
 /// arithmetic of the NSNet2 matrix products at every batch size; returns the previous mode.  Default 0 = f32 (the ORT
 /// CPU arithmetic); 1 = f16x3 emulation (22-bit operands), 2 = bf16x3 (24-bit operands, dense layers) are opt-in
@@ -305,6 +307,14 @@ pub extern "c" fn fvad_vad_batch_run_part(b: *VadBatch, band: [*]const f32, band
 pub extern "c" fn fvad_vad_batch_total_segments(b: *const VadBatch) usize;
 pub extern "c" fn fvad_vad_batch_segments(b: *const VadBatch, out: [*]SpeechSegment, cap: usize, offsets: [*]usize) c_int;
 pub extern "c" fn fvad_vad_batch_audit(b: *const VadBatch, stream: usize, out: *VadAudit) c_int;
+/// parameter sweeps: one machine per (stream, config), each on its own speech band (see fvad.h)
+pub extern "c" fn fvad_vad_batch_create_sweep(cfgs: [*]const VadConfig, n_configs: usize, sample_rate: usize, n_channels: usize, fft_size: usize, n_streams: usize, out: *?*VadBatch) c_int;
+pub extern "c" fn fvad_vad_batch_n_configs(b: *const VadBatch) usize;
+pub extern "c" fn fvad_vad_batch_bands(b: *const VadBatch, bins: ?[*]i32, cap: usize, n_bands: *usize, band_of: ?[*]u32) c_int;
+pub extern "c" fn fvad_vad_batch_config_segments(b: *const VadBatch, config: usize, out: ?[*]SpeechSegment, cap: usize, offsets: [*]usize) c_int;
+pub extern "c" fn fvad_vad_batch_config_audit(b: *const VadBatch, stream: usize, config: usize, out: *VadAudit) c_int;
+pub extern "c" fn fvad_vad_batch_lazy_stats(b: *const VadBatch, stream: usize, config: usize, exact_evaluations: ?*u64, lazy_pushes: ?*u64) c_int;
+pub extern "c" fn fvad_vad_batch_run_device(ctx: *Ctx, b: *VadBatch, d_band: [*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: [*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize) c_int;
 pub extern "c" fn fvad_ra_create(count: usize, has_initial: c_int, initial_val: f64, out: *?*RollingAverage) c_int;
 pub extern "c" fn fvad_ra_destroy(ra: ?*RollingAverage) void;
 pub extern "c" fn fvad_ra_push(ra: *RollingAverage, sample: f32) f64;

@@ -19,6 +19,9 @@ sz = C.c_size_t
 FVAD_OK = 0
 FVAD_ERR_NO_DEVICE = -101
 FVAD_ERR_INVALID_ARGUMENT = -100
+FVAD_ERR_OUT_OF_RANGE = -6
+FVAD_ERR_NEGATIVE_FREQUENCY = -7
+FVAD_ERR_BUFFER_TOO_SMALL = -106
 
 
 class FvadError(RuntimeError):
@@ -190,6 +193,7 @@ SIGNATURES = {
     "fvad_engine_enqueue_device": (C.c_int, [vp, vp, sz, sz, sz, vp, vp, vp,
                                              C.POINTER(EngineOpts)]),
     "fvad_engine_enqueue_device_i16": (C.c_int, [vp, vp, sz, sz, sz, vp, vp, vp, C.POINTER(EngineOpts)]),
+    "fvad_engine_band_sums_device": (C.c_int, [vp, vp, sz, sz, sz, sz, C.POINTER(C.c_int32), sz, vp, sz]),
     "fvad_nsnet2_forward": (C.c_int, [vp, c_float_p, sz, sz, c_float_p]),
     "fvad_ctx_enable_timing": (C.c_int, [vp, C.c_int]),
     "fvad_ctx_set_nn_math": (C.c_int, [vp, C.c_int]),
@@ -224,6 +228,13 @@ SIGNATURES = {
     "fvad_vad_batch_total_segments": (sz, [vp]),
     "fvad_vad_batch_segments": (C.c_int, [vp, C.POINTER(SpeechSegment), sz, C.POINTER(sz)]),
     "fvad_vad_batch_audit": (C.c_int, [vp, sz, C.POINTER(VadAudit)]),
+    "fvad_vad_batch_create_sweep": (C.c_int, [C.POINTER(VadConfig), sz, sz, sz, sz, sz, C.POINTER(vp)]),
+    "fvad_vad_batch_n_configs": (sz, [vp]),
+    "fvad_vad_batch_bands": (C.c_int, [vp, C.POINTER(C.c_int32), sz, C.POINTER(sz), C.POINTER(C.c_uint32)]),
+    "fvad_vad_batch_config_segments": (C.c_int, [vp, sz, C.POINTER(SpeechSegment), sz, C.POINTER(sz)]),
+    "fvad_vad_batch_config_audit": (C.c_int, [vp, sz, sz, C.POINTER(VadAudit)]),
+    "fvad_vad_batch_lazy_stats": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_vad_batch_run_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
     "fvad_ra_push": (C.c_double, [vp, C.c_float]),
@@ -551,6 +562,14 @@ class Context:
                                                   vp(d_den) if d_den else None, vp(d_band), vp(d_rms) if d_rms else None,
                                                   C.byref(opts)), "fvad_engine_enqueue_device")
 
+    def band_sums_device(self, d_den, n_lanes, lane_stride, n_samples, bins, d_band, band_stride, fft_size=1024):
+        """fvad_engine_band_sums_device: bins = [(min_bin, max_bin), ...]; band j of lane l at d_band + (j * n_lanes + l) *
+        band_stride floats (device addresses as ints)"""
+        b = np.ascontiguousarray(np.asarray(bins, np.int32).reshape(-1, 2))
+        self._ck(lib().fvad_engine_band_sums_device(self.h, vp(d_den), n_lanes, lane_stride, n_samples, fft_size,
+                                                    b.ctypes.data_as(C.POINTER(C.c_int32)), b.shape[0], vp(d_band), band_stride),
+                 "fvad_engine_band_sums_device")
+
     def lane_state(self):
         s = vp()
         self._ck(lib().fvad_lane_state_create(self.h, C.byref(s)), "fvad_lane_state_create")
@@ -858,6 +877,82 @@ class VadBatch:
         if self.h:
             lib().fvad_vad_batch_destroy(self.h)
             self.h = vp()
+
+
+class VadSweep:
+    """fvad_vad_batch with several configs (fvad_vad_batch_create_sweep): one VAD machine per (stream, config), each on its
+    config's speech band.  configs: list of VadConfig overrides dicts (defaults for the fields a dict leaves out)."""
+
+    def __init__(self, n_streams, configs, n_channels=1, sample_rate=48000, fft_size=1024):
+        arr = (VadConfig * len(configs))()
+        for i, ov in enumerate(configs):
+            lib().fvad_vad_config_default(C.byref(arr[i]))
+            for k, v in (ov or {}).items():
+                setattr(arr[i], k, v)
+        self.h = vp()
+        check(lib().fvad_vad_batch_create_sweep(arr, len(configs), sample_rate, n_channels, fft_size, n_streams, C.byref(self.h)),
+              "fvad_vad_batch_create_sweep")
+        self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, len(configs)
+        assert lib().fvad_vad_batch_n_configs(self.h) == self.n_configs
+
+    def bands(self):
+        """-> (bins [(min_bin, max_bin)] of the distinct bands, band_of [config])"""
+        n = sz()
+        cap = 2 * self.n_configs
+        bins = (C.c_int32 * cap)()
+        band_of = (C.c_uint32 * self.n_configs)()
+        check(lib().fvad_vad_batch_bands(self.h, bins, self.n_configs, C.byref(n), band_of), "fvad_vad_batch_bands")
+        return [(bins[2 * j], bins[2 * j + 1]) for j in range(n.value)], list(band_of)
+
+    def run(self, band, chunk_rms, n_threads=1, chunk_size=24000):
+        """band [n_bands][n_streams * n_channels][n_frames] (bands() order), chunk_rms [n_streams * n_channels][n_chunks], float32"""
+        assert band.dtype == np.float32 and chunk_rms.dtype == np.float32 and band.flags["C_CONTIGUOUS"] and chunk_rms.flags["C_CONTIGUOUS"]
+        assert band.shape[1] == chunk_rms.shape[0] == self.n_streams * self.n_channels
+        check(lib().fvad_vad_batch_run(self.h, fptr(band), band.shape[2], band.shape[2], fptr(chunk_rms), chunk_rms.shape[1],
+                                       chunk_rms.shape[1], chunk_size, n_threads), "fvad_vad_batch_run")
+
+    def run_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, chunk_size=24000):
+        """fvad_vad_batch_run_device: d_band as Context.band_sums_device writes it (device address), n_frames / n_chunks per
+        stream, chunk_rms [n_streams * n_channels][>= max n_chunks] float32 on the host"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf = (sz * self.n_streams)(*[int(x) for x in n_frames])
+        nc = (sz * self.n_streams)(*[int(x) for x in n_chunks])
+        ctx._ck(lib().fvad_vad_batch_run_device(ctx.h, self.h, vp(d_band), band_stride, nf, fptr(chunk_rms), chunk_rms.shape[1], nc,
+                                                chunk_size), "fvad_vad_batch_run_device")
+
+    def segments(self, config):
+        """config's segments per stream: [[(from, to, avg_ratio, vad_met_sec)]]"""
+        offs = (sz * (self.n_streams + 1))()
+        st = lib().fvad_vad_batch_config_segments(self.h, config, None, 0, offs)
+        n = offs[self.n_streams]
+        if st != FVAD_OK and not (st == FVAD_ERR_BUFFER_TOO_SMALL and n > 0):
+            check(st, "fvad_vad_batch_config_segments")
+        arr = (SpeechSegment * max(n, 1))()
+        check(lib().fvad_vad_batch_config_segments(self.h, config, arr, max(n, 1), offs), "fvad_vad_batch_config_segments")
+        flat = [(a.sample_from, a.sample_to, a.avg_channel_vol_ratio, a.vad_met_sec) for a in arr[:n]]
+        return [flat[offs[s]:offs[s + 1]] for s in range(self.n_streams)]
+
+    def audit(self, stream, config):
+        a = VadAudit()
+        check(lib().fvad_vad_batch_config_audit(self.h, stream, config, C.byref(a)), "fvad_vad_batch_config_audit")
+        return a.min_rel_threshold_margin, a.min_abs_ratio_margin, a.n_frames
+
+    def lazy_stats(self, stream, config):
+        """(exact evaluations of the long-term chain, lazily absorbed pushes) of machine (stream, config) in the last run"""
+        e, p = C.c_uint64(), C.c_uint64()
+        check(lib().fvad_vad_batch_lazy_stats(self.h, stream, config, C.byref(e), C.byref(p)), "fvad_vad_batch_lazy_stats")
+        return e.value, p.value
+
+    def close(self):
+        if self.h:
+            lib().fvad_vad_batch_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_threads=1):

@@ -193,6 +193,16 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
     }
     else if (name == "trace_kernels") { if (!to_bool(tn.trace_kernels)) return FVAD_ERR_INVALID_ARGUMENT; }
     else if (name == "reproducible") { if (!to_bool(tn.reproducible)) return FVAD_ERR_INVALID_ARGUMENT; }
+    else if (name == "vad_lane_map") { // fvad_vad_batch_run_device's lanes: "stream" (a stream's configs per wavefront) or "config"; same bits
+        if (unset || v == "stream") tn.vad_lane_map = 0;
+        else if (v == "config") tn.vad_lane_map = 1;
+        else return FVAD_ERR_INVALID_ARGUMENT;
+    }
+    else if (name == "vad_seg_cap") { // fvad_vad_batch_run_device's first segment room per machine (tests: the overflow path); unset = 512 MB over all machines
+        long c = 0;
+        if (!unset && (!to_long(c) || c < 1 || c > (1L << 24))) return FVAD_ERR_INVALID_ARGUMENT;
+        tn.vad_seg_cap = unset ? def.vad_seg_cap : (int)c;
+    }
     else return FVAD_ERR_INVALID_ARGUMENT;
     ctx->ws.generation++; // a captured launch sequence holds the kernels of the old selection
     return FVAD_OK;

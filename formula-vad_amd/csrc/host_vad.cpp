@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -484,16 +486,6 @@ int fvad_ra_last_avg(const fvad_rolling_average* ra, double* out)
 // the two metadata hand-overs (BufferedVolumeAnalyzer.zig:33-45, BufferedDenoiser.zig:83-86,115) -> the
 // sample-weighted ratio of every FFT frame (BufferedFFT.zig:137-140,153) -> VADMachine.run per frame
 // (VADMachine.zig:138-239).  Streams are dealt to threads like simulator.zig:221-232 deals files.
-struct fvad_vad_batch {
-    fvad_vad_config cfg;
-    size_t sample_rate, n_channels, fft_size, n_streams;
-    std::vector<std::vector<fvad_speech_segment>> segs;
-    std::vector<fvad_vad_audit> audits;
-    // a run in parts (fvad_vad_batch_run_part): the streams' machines live on between the parts
-    std::vector<std::unique_ptr<fvad::VadMachine>> machines;
-    uint64_t next_frame = 0;
-};
-
 int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t n_channels, size_t fft_size, size_t n_streams,
                           fvad_vad_batch** out)
 {
@@ -501,64 +493,186 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
     if ((size_t)(((float)sample_rate / (float)fft_size) * cfg->channel_vol_ratio_avg_sec) == 0) return FVAD_ERR_INVALID_ARGUMENT;
     auto* b = new (std::nothrow) fvad_vad_batch();
     if (!b) return FVAD_ERR_ALLOC_FAILED;
-    b->cfg = *cfg; b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = fft_size; b->n_streams = n_streams;
+    b->cfgs.assign(1, *cfg); b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = fft_size; b->n_streams = n_streams;
+    // the band of a plain batch is whatever the caller summed: one block, whatever the config's edges say
+    const float bin_width = (float)sample_rate / (float)fft_size;
+    b->bins = {(int32_t)roundf(cfg->speech_min_freq / bin_width), (int32_t)roundf(cfg->speech_max_freq / bin_width)};
+    b->band_of.assign(1, 0);
     b->segs.resize(n_streams);
     b->audits.resize(n_streams);
+    b->exact_evals.assign(n_streams, 0);
+    b->lazy_pushes.assign(n_streams, 0);
     *out = b;
     return FVAD_OK;
 }
+
+// The checks fvad_vad_create and fvad_pipeline_create make of a VADMachine.Config, with their status codes: the speech band's
+// edges as FFT.freqToBin sees them (FFT.zig:156-167, then the pipeline's max < min), the channel-ratio ring's length
+// (RollingAverage.zig:36)
+static int check_sweep_config(const fvad_vad_config& c, size_t sample_rate, size_t fft_size, int32_t* lo, int32_t* hi)
+{
+    const float bin_width = (float)sample_rate / (float)fft_size;
+    const float nyq = (float)sample_rate / 2;
+    if (c.speech_min_freq > nyq || c.speech_max_freq > nyq) return FVAD_ERR_OUT_OF_RANGE;
+    if (c.speech_min_freq < 0 || c.speech_max_freq < 0) return FVAD_ERR_NEGATIVE_FREQUENCY;
+    *lo = (int32_t)roundf(c.speech_min_freq / bin_width);
+    *hi = (int32_t)roundf(c.speech_max_freq / bin_width);
+    if (*hi < *lo) return FVAD_ERR_INVALID_ARGUMENT;
+    if ((size_t)(((float)sample_rate / (float)fft_size) * c.channel_vol_ratio_avg_sec) == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_create_sweep(const fvad_vad_config* cfgs, size_t n_configs, size_t sample_rate, size_t n_channels, size_t fft_size,
+                                size_t n_streams, fvad_vad_batch** out)
+{
+    if (!cfgs || !out || n_configs == 0 || n_channels == 0 || fft_size == 0 || sample_rate == 0 || n_streams == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    std::vector<int32_t> bins;
+    std::vector<uint32_t> band_of(n_configs);
+    for (size_t c = 0; c < n_configs; ++c) {
+        int32_t lo = 0, hi = 0;
+        const int rc = check_sweep_config(cfgs[c], sample_rate, fft_size, &lo, &hi);
+        if (rc) return rc;
+        size_t j = 0; // distinct bands in first-seen order
+        while (j < bins.size() / 2 && !(bins[2 * j] == lo && bins[2 * j + 1] == hi)) ++j;
+        if (j == bins.size() / 2) { bins.push_back(lo); bins.push_back(hi); }
+        band_of[c] = (uint32_t)j;
+    }
+    auto* b = new (std::nothrow) fvad_vad_batch();
+    if (!b) return FVAD_ERR_ALLOC_FAILED;
+    b->cfgs.assign(cfgs, cfgs + n_configs); b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = fft_size;
+    b->n_streams = n_streams;
+    b->bins = std::move(bins);
+    b->band_of = std::move(band_of);
+    b->segs.resize(n_streams * n_configs);
+    b->audits.resize(n_streams * n_configs);
+    b->exact_evals.assign(n_streams * n_configs, 0);
+    b->lazy_pushes.assign(n_streams * n_configs, 0);
+    *out = b;
+    return FVAD_OK;
+}
+
 void fvad_vad_batch_destroy(fvad_vad_batch* b) { delete b; }
+
+size_t fvad_vad_batch_n_configs(const fvad_vad_batch* b) { return b ? b->cfgs.size() : 0; }
+
+int fvad_vad_batch_bands(const fvad_vad_batch* b, int32_t* bins, size_t cap, size_t* n_bands, uint32_t* band_of)
+{
+    if (!b || !n_bands) return FVAD_ERR_INVALID_ARGUMENT;
+    *n_bands = b->bins.size() / 2;
+    if (band_of) memcpy(band_of, b->band_of.data(), b->band_of.size() * sizeof(uint32_t));
+    if (cap < *n_bands) return FVAD_ERR_BUFFER_TOO_SMALL;
+    if (*n_bands && !bins) return FVAD_ERR_INVALID_ARGUMENT;
+    memcpy(bins, b->bins.data(), b->bins.size() * sizeof(int32_t));
+    return FVAD_OK;
+}
+
+} // extern "C"
+
+namespace fvad {
+// The volume ratio of every FFT frame of a stream (BufferedVolumeAnalyzer.zig:48-69 per chunk, the two metadata hand-overs
+// BufferedVolumeAnalyzer.zig:33-45 / BufferedDenoiser.zig:83-86,115, the sample-weighted frame ratio BufferedFFT.zig:137-140,153).
+// Frames [first_frame, first_frame + n_frames); chunk_rms(c, k) = channel c's RMS of chunk first_chunk + k.  Every frame
+// covers at least one chunk, so every frame has a ratio (has[f] = 1; the flag is still carried, not inferred from the value: a
+// NaN ratio from NaN audio is a ratio, pushed as it is).
+template <class Rms>
+static void frame_ratios(Rms chunk_rms, size_t C, size_t n_chunks, size_t n_frames, uint64_t first_frame, uint64_t first_chunk,
+                         size_t fft_size, size_t chunk_size, float* out, uint8_t* has)
+{
+    std::vector<float> ratio(n_chunks), ch(C);
+    for (size_t k = 0; k < n_chunks; ++k) {
+        for (size_t c = 0; c < C; ++c) ch[c] = chunk_rms(c, k);
+        const MetaResult va = analyse_volume(ch.data(), C);
+        Metadata m1; m1.push(va, (float)chunk_size);
+        const MetaResult r1 = m1.to_result();
+        Metadata m2; m2.push(r1, (float)chunk_size);
+        ratio[k] = m2.to_result().volume_ratio;
+    }
+    for (size_t f = 0; f < n_frames; ++f) {
+        Metadata md;
+        const uint64_t from = (first_frame + f) * fft_size, to = from + fft_size;
+        for (uint64_t c = from / chunk_size; c * chunk_size < to; ++c) {
+            const uint64_t lo = std::max<uint64_t>(from, c * chunk_size), hi = std::min<uint64_t>(to, (c + 1) * chunk_size);
+            MetaResult r;
+            r.has_ratio = true;
+            r.volume_ratio = ratio[(size_t)(c - first_chunk)];
+            md.push(r, (float)(hi - lo));
+        }
+        const MetaResult fr = md.to_result();
+        out[f] = fr.volume_ratio;
+        if (has) has[f] = fr.has_ratio ? 1 : 0;
+    }
+}
+
+void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t C, size_t n_chunks, size_t n_frames, size_t fft_size,
+                        size_t chunk_size, float* out)
+{
+    frame_ratios([&](size_t c, size_t k) { return chunk_rms[c * rms_stride + k]; }, C, n_chunks, n_frames, 0, 0, fft_size, chunk_size, out,
+                 nullptr);
+}
+
+// items 0 .. n - 1 dealt to up to n_threads host threads
+static void deal(size_t n, int n_threads, const std::function<void(size_t)>& fn)
+{
+    const int nt = (int)std::min<size_t>((size_t)std::max(n_threads, 1), n);
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
+    std::vector<std::thread> th;
+    std::atomic<size_t> next{0};
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= n) break; fn(i); } });
+    for (auto& t : th) t.join();
+}
+} // namespace fvad
+
+extern "C" {
 
 int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_stride, size_t n_frames, const float* chunk_rms,
                             size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_frame, int n_threads)
 {
     if (!b || (n_frames && !band) || (n_chunks && !chunk_rms) || chunk_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    const size_t NC = b->cfgs.size();
     // parts follow each other without gaps, and a part starts where a chunk starts (its first chunk is chunk_rms' first column)
-    if (first_frame != 0 && (first_frame != b->next_frame || b->machines.size() != b->n_streams)) return FVAD_ERR_INVALID_ARGUMENT;
+    if (first_frame != 0 && (first_frame != b->next_frame || b->machines.size() != b->n_streams * NC)) return FVAD_ERR_INVALID_ARGUMENT;
     if ((first_frame * b->fft_size) % chunk_size) return FVAD_ERR_INVALID_ARGUMENT;
     const uint64_t first_chunk = first_frame * b->fft_size / chunk_size;
     if ((first_frame + n_frames) * b->fft_size > (first_chunk + n_chunks) * chunk_size) return FVAD_ERR_INVALID_ARGUMENT; // a frame without its chunk's ratio
-    const size_t C = b->n_channels;
-    if (first_frame == 0) { // fresh machines (VADMachine.init per pipeline, VADPipeline.zig:60-75)
+    const size_t C = b->n_channels, n_lanes = b->n_streams * C;
+    if (first_frame == 0) { // fresh machines (VADMachine.init per pipeline, VADPipeline.zig:60-75); machine s * NC + c
         b->machines.clear();
-        for (size_t s = 0; s < b->n_streams; ++s) b->machines.emplace_back(new fvad::VadMachine(b->cfg, b->sample_rate, C, b->fft_size));
+        for (size_t s = 0; s < b->n_streams; ++s)
+            for (size_t c = 0; c < NC; ++c) b->machines.emplace_back(new fvad::VadMachine(b->cfgs[c], b->sample_rate, C, b->fft_size));
     }
-    auto run_stream = [&](size_t s) {
-        fvad::VadMachine& m = *b->machines[s];
-        std::vector<float> ratio(n_chunks), ch(C), vols(C);
-        for (size_t k = 0; k < n_chunks; ++k) {
-            for (size_t c = 0; c < C; ++c) ch[c] = chunk_rms[(s * C + c) * rms_stride + k];
-            const fvad::MetaResult va = fvad::analyse_volume(ch.data(), C);
-            fvad::Metadata m1; m1.push(va, (float)chunk_size);
-            const fvad::MetaResult r1 = m1.to_result();
-            fvad::Metadata m2; m2.push(r1, (float)chunk_size);
-            ratio[k] = m2.to_result().volume_ratio;
-        }
+    auto run_machine = [&](size_t s, size_t c, const float* ratio, const uint8_t* has) {
+        fvad::VadMachine& m = *b->machines[s * NC + c];
+        const float* bb = band + ((size_t)b->band_of[c] * n_lanes + s * C) * band_stride; // config c's band block, stream s's lanes
+        std::vector<float> vols(C);
         for (size_t f = 0; f < n_frames; ++f) {
-            fvad::Metadata md;
-            const uint64_t from = (first_frame + f) * b->fft_size, to = from + b->fft_size;
-            for (uint64_t c = from / chunk_size; c * chunk_size < to; ++c) {
-                const uint64_t lo = std::max<uint64_t>(from, c * chunk_size), hi = std::min<uint64_t>(to, (c + 1) * chunk_size);
-                fvad::MetaResult r;
-                r.has_ratio = true;
-                r.volume_ratio = ratio[(size_t)(c - first_chunk)];
-                md.push(r, (float)(hi - lo));
-            }
-            const fvad::MetaResult fr = md.to_result();
-            for (size_t c = 0; c < C; ++c) vols[c] = band[(s * C + c) * band_stride + f];
-            m.run(from, vols.data(), fr.has_ratio, fr.volume_ratio);
+            for (size_t ch = 0; ch < C; ++ch) vols[ch] = bb[ch * band_stride + f];
+            m.run((first_frame + f) * b->fft_size, vols.data(), has[f] != 0, ratio[f]);
         }
-        b->segs[s] = m.segments; // (everything so far: a segment is appended when it closes)
-        b->audits[s] = m.audit;
+        b->segs[s * NC + c] = m.segments; // (everything so far: a segment is appended when it closes)
+        b->audits[s * NC + c] = m.audit;
+        b->exact_evals[s * NC + c] = m.lt_exact_evals;
+        b->lazy_pushes[s * NC + c] = m.lt_lazy_pushes;
     };
-    const int nt = (int)std::min<size_t>((size_t)std::max(n_threads, 1), b->n_streams);
-    if (nt <= 1) { for (size_t s = 0; s < b->n_streams; ++s) run_stream(s); }
-    else {
-        std::vector<std::thread> th;
-        std::atomic<size_t> next{0};
-        for (int t = 0; t < nt; ++t)
-            th.emplace_back([&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= b->n_streams) break; run_stream(i); } });
-        for (auto& t : th) t.join();
+    auto stream_ratios = [&](size_t s, float* out, uint8_t* has) {
+        fvad::frame_ratios([&](size_t c, size_t k) { return chunk_rms[(s * C + c) * rms_stride + k]; }, C, n_chunks, n_frames, first_frame,
+                           first_chunk, b->fft_size, chunk_size, out, has);
+    };
+    if (NC == 1) {
+        // one machine per stream: a stream's frame ratios and its machine on the same thread
+        fvad::deal(b->n_streams, n_threads, [&](size_t s) {
+            std::vector<float> ratio(n_frames);
+            std::vector<uint8_t> has(n_frames);
+            stream_ratios(s, ratio.data(), has.data());
+            run_machine(s, 0, ratio.data(), has.data());
+        });
+    } else {
+        // a sweep: the frame ratios of every stream (they do not depend on the config), then every (stream, config) machine
+        std::vector<float> ratio(b->n_streams * n_frames);
+        std::vector<uint8_t> has(b->n_streams * n_frames);
+        fvad::deal(b->n_streams, n_threads, [&](size_t s) { stream_ratios(s, ratio.data() + s * n_frames, has.data() + s * n_frames); });
+        fvad::deal(b->n_streams * NC, n_threads,
+                   [&](size_t i) { run_machine(i / NC, i % NC, ratio.data() + (i / NC) * n_frames, has.data() + (i / NC) * n_frames); });
     }
     b->next_frame = first_frame + n_frames;
     return FVAD_OK;
@@ -570,30 +684,51 @@ int fvad_vad_batch_run(fvad_vad_batch* b, const float* band, size_t band_stride,
     return fvad_vad_batch_run_part(b, band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, 0, n_threads);
 }
 
-size_t fvad_vad_batch_total_segments(const fvad_vad_batch* b)
+size_t fvad_vad_batch_total_segments(const fvad_vad_batch* b) // (config 0's on a sweep batch)
 {
     size_t n = 0;
-    if (b) for (const auto& v : b->segs) n += v.size();
+    if (b) for (size_t s = 0; s < b->n_streams; ++s) n += b->segs[s * b->cfgs.size()].size();
     return n;
 }
 
 int fvad_vad_batch_segments(const fvad_vad_batch* b, fvad_speech_segment* out, size_t cap, size_t* offsets)
 {
-    if (!b || !offsets) return FVAD_ERR_INVALID_ARGUMENT;
+    return fvad_vad_batch_config_segments(b, 0, out, cap, offsets);
+}
+
+int fvad_vad_batch_config_segments(const fvad_vad_batch* b, size_t config, fvad_speech_segment* out, size_t cap, size_t* offsets)
+{
+    if (!b || !offsets || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    const size_t NC = b->cfgs.size();
     size_t n = 0;
-    for (size_t s = 0; s < b->n_streams; ++s) { offsets[s] = n; n += b->segs[s].size(); }
+    for (size_t s = 0; s < b->n_streams; ++s) { offsets[s] = n; n += b->segs[s * NC + config].size(); }
     offsets[b->n_streams] = n;
     if (cap < n) return FVAD_ERR_BUFFER_TOO_SMALL;
     if (n && !out) return FVAD_ERR_INVALID_ARGUMENT;
-    for (size_t s = 0; s < b->n_streams; ++s)
-        if (!b->segs[s].empty()) memcpy(out + offsets[s], b->segs[s].data(), b->segs[s].size() * sizeof(fvad_speech_segment));
+    for (size_t s = 0; s < b->n_streams; ++s) {
+        const auto& v = b->segs[s * NC + config];
+        if (!v.empty()) memcpy(out + offsets[s], v.data(), v.size() * sizeof(fvad_speech_segment));
+    }
     return FVAD_OK;
 }
 
 int fvad_vad_batch_audit(const fvad_vad_batch* b, size_t stream, fvad_vad_audit* out)
 {
-    if (!b || !out || stream >= b->n_streams) return FVAD_ERR_INVALID_ARGUMENT;
-    *out = b->audits[stream];
+    return fvad_vad_batch_config_audit(b, stream, 0, out);
+}
+
+int fvad_vad_batch_lazy_stats(const fvad_vad_batch* b, size_t stream, size_t config, uint64_t* exact_evaluations, uint64_t* lazy_pushes)
+{
+    if (!b || stream >= b->n_streams || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    if (exact_evaluations) *exact_evaluations = b->exact_evals[stream * b->cfgs.size() + config];
+    if (lazy_pushes) *lazy_pushes = b->lazy_pushes[stream * b->cfgs.size() + config];
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_config_audit(const fvad_vad_batch* b, size_t stream, size_t config, fvad_vad_audit* out)
+{
+    if (!b || !out || stream >= b->n_streams || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    *out = b->audits[stream * b->cfgs.size() + config];
     return FVAD_OK;
 }
 

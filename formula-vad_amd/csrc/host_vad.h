@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "../../include/fvad.h"
@@ -79,4 +80,24 @@ void run_many(VadMachine* const* vads, size_t n_streams, const float* const* ban
               const float* const* ratio, const size_t* n_frames, size_t n_channels,
               const uint64_t* first_index, size_t fft_size, int n_threads);
 
+// the volume ratio of each of a stream's first n_frames FFT frames from its channels' chunk RMS (channel c's chunk k at
+// chunk_rms[c * rms_stride + k]), as fvad_vad_batch_run hands it to the machines (every frame covers a chunk: each has a ratio)
+void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t n_channels, size_t n_chunks, size_t n_frames, size_t fft_size,
+                        size_t chunk_size, float* out);
+
 } // namespace fvad
+
+// fvad_vad_batch (include/fvad.h): n_configs machines per stream, machine s * n_configs + c; a batch from
+// fvad_vad_batch_create has one config.  Segments and audits of the last run, machine by machine.
+struct fvad_vad_batch {
+    std::vector<fvad_vad_config> cfgs;
+    std::vector<int32_t> bins;      // distinct speech bands (min, max bin), first-seen order
+    std::vector<uint32_t> band_of;  // band of each config
+    size_t sample_rate, n_channels, fft_size, n_streams;
+    std::vector<std::vector<fvad_speech_segment>> segs;
+    std::vector<fvad_vad_audit> audits;
+    std::vector<uint64_t> exact_evals, lazy_pushes; // exact evaluations of the long-term chain / lazily absorbed pushes per machine
+    // a run in parts (fvad_vad_batch_run_part): the streams' machines live on between the parts
+    std::vector<std::unique_ptr<fvad::VadMachine>> machines;
+    uint64_t next_frame = 0;
+};

@@ -184,6 +184,19 @@ void fvad_launch_vadfft(const float* den, long n_frames, VadFftPlan pl, int min_
 // (returns a hipError_t as int: a failed hipFuncSetAttribute must not leave the caller with stale band sums and FVAD_OK)
 int fvad_launch_vadfft_jobs(const VadFftJob* jobs, int n_jobs, long max_frames, VadFftPlan pl,
                             int min_bin, int max_bin, hipStream_t stream, int any_bins, int n_cu, int plain_loads = 0);
+// K4 with several bands per pass (fvad_engine_band_sums_device): band b of the set is bins lo[b]..hi[b], written for a job's frame f at
+// job.band_sum + idx[b] * step + f; per band the bits of fvad_launch_vadfft_jobs with that band.  pruned: every band of the set lies
+// inside bins 1..47 at 1024 points (vadfft1024_band_kernel's pass, where the single-band launch takes those bands' bits); else the
+// full-spectrum kernel of the size (512 / 1024 / 2048) or the generic one
+constexpr int kVadBandsPerLaunch = 256;
+struct VadBandSet {
+    long step;
+    int n;
+    int16_t lo[kVadBandsPerLaunch], hi[kVadBandsPerLaunch];
+    int32_t idx[kVadBandsPerLaunch];
+};
+int fvad_launch_vadfft_bands(const VadFftJob* jobs, int n_jobs, long max_frames, VadFftPlan pl, const VadBandSet& bs, int pruned,
+                             hipStream_t stream, int n_cu, int plain_loads = 0); // hipError_t as int
 // batched FFT.fft for B3 / BASELINE config 2: n_fft in {320, 512, 1024, 2048} (pl is used for n_fft != 320)
 int fvad_launch_rfft_batch(const float* frames, long n_frames, int n_fft, const float* window,
                            FftTables tb, VadFftPlan pl, float* bins_or_null, float* mag_or_null,
@@ -193,3 +206,44 @@ void fvad_launch_irfft_batch(const float* bins, long n_frames, FftTables tb, flo
 // FFT.invFft for any even size (pl.generic plans; tables of the FORWARD transform, conjugated in the kernel): bins
 // [n_frames][n/2 + 1][2] -> out [n_frames][n], unscaled like kiss_fftri
 int fvad_launch_irfft_generic(const float* bins, long n_frames, VadFftPlan pl, float* out, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ VAD machines of a parameter sweep (kernels_vad.hip)
+// per config: what host_vad.cpp's VadMachine derives from its VADMachine.Config, evaluated on the host with the host's expressions
+struct VadMachineCfg {
+    double lt_scalar, st_scalar, cr_scalar; // 1 / ring length (RollingAverage.zig:45-56 once full)
+    double lt_q_init;        // fl(initial_long_term_avg * lt_scalar): the term of a slot still holding the initial value
+    double initial;          // initial_long_term_avg
+    double factor;           // (double)speech_threshold_factor
+    double ratio_threshold;  // (double)channel_vol_ratio_threshold
+    double gamma;            // n u / (1 - n u), n = long_len (host_vad.cpp decide)
+    uint64_t min_open, max_gap, start_buffer, end_buffer; // VADMachine.zig:161,163,312-325 in samples
+    float input_len_sec, sample_rate_f, min_vad_duration_sec;
+    uint32_t long_len, short_len, ratio_len;
+    int32_t has_init;
+    uint32_t band;           // band block of d_band this config reads
+};
+struct VadSegmentDev { uint64_t sample_from, sample_to; float avg_channel_vol_ratio, vad_met_sec; }; // = fvad_speech_segment
+struct VadAuditDev { double min_rel_threshold_margin, min_abs_ratio_margin; uint64_t n_frames; };    // = fvad_vad_audit
+struct VadMachinesArgs {
+    const VadMachineCfg* cfgs; // [n_configs] (device)
+    int n_configs, n_channels;
+    long n_streams;
+    int by_config;             // lane mapping: 0 = a stream's configs side by side, 1 = a config's streams side by side
+    long n_machines;           // n_streams * n_configs, machine = stream * n_configs + config
+    long n_lanes;              // n_streams * n_channels
+    const float* band;         // band j of lane l at band + (j * n_lanes + l) * band_stride
+    long band_stride;
+    const float* ratio;        // stream s's frame ratios at ratio + s * ratio_stride (NaN: none)
+    long ratio_stride;
+    const long* n_frames;      // [n_streams] (device)
+    uint64_t fft_size;
+    float* lt_rings;           // [(max long_len rounded up to 64) / 4 + 16][n_machines][4]
+    float* rings;              // [st_max + cr_max][n_machines] when !rings_in_lds
+    int rings_in_lds, st_max, cr_max;
+    VadSegmentDev* segs;       // [n_machines][seg_cap]
+    uint32_t seg_cap;
+    uint32_t* seg_count;       // [n_machines]: segments the machine closed (may exceed seg_cap: then only seg_cap were written)
+    VadAuditDev* audits;       // [n_machines]
+    unsigned long long* stats; // [n_machines][2]: exact evaluations of the long-term chain, lazy pushes
+};
+int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int

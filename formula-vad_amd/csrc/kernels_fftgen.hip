@@ -131,6 +131,38 @@ __global__ __launch_bounds__(256) void rfft_generic_kernel(const float* __restri
     }
 }
 
+// K4 with several bands per pass (fvad_engine_band_sums_device): rfft_generic_kernel's magnitudes, then the threads take the
+// bands in turn, each summed in index order from 0.0f (per band the bits of the single-band pass)
+__global__ __launch_bounds__(256) void rfft_generic_bands_kernel(const VadFftJob* __restrict__ jobs, VadFftPlan pl, VadBandSet bs)
+{
+    extern __shared__ __attribute__((aligned(16))) float gsm[];
+    const int M = pl.n / 2, NB = M + 1;
+    cpx* bufA = reinterpret_cast<cpx*>(gsm);
+    cpx* bufB = bufA + NB;
+    const long frame = blockIdx.x;
+    const VadFftJob j = jobs[blockIdx.y];
+    if (frame >= j.n_frames) return;
+    cpx* X;
+    generic_rfft(j.den + frame * pl.n, pl.win, pl, bufA, bufB, X);
+    float* m = reinterpret_cast<float*>(X == bufA ? bufB : bufA);
+    for (int k = threadIdx.x; k < NB; k += 256) m[k] = sqrtf(X[k].r * X[k].r + X[k].i * X[k].i) * pl.norm;
+    __syncthreads();
+    for (int b = threadIdx.x; b < bs.n; b += 256) {
+        float acc = 0.0f;
+        for (int k = bs.lo[b]; k <= bs.hi[b]; ++k) acc += m[k];
+        j.band_sum[bs.idx[b] * bs.step + frame] = acc;
+    }
+}
+
+int fvad_launch_rfft_generic_bands(const VadFftJob* jobs, int n_jobs, long max_frames, VadFftPlan pl, const VadBandSet& bs, hipStream_t stream)
+{
+    const size_t lds = (size_t)(pl.n / 2 + 1) * 2 * sizeof(cpx);
+    const hipError_t e = hipFuncSetAttribute((const void*)rfft_generic_bands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(rfft_generic_bands_kernel, dim3((unsigned)max_frames, (unsigned)n_jobs), dim3(256), lds, stream, jobs, pl, bs);
+    return (int)hipGetLastError();
+}
+
 // FFT.invFft: kiss_fftri's pre-mixing, the inverse complex transform, unscaled
 __global__ __launch_bounds__(256) void irfft_generic_kernel(const float* __restrict__ bins, long n_frames, VadFftPlan pl, float* __restrict__ out)
 {

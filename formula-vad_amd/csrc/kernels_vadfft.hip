@@ -132,8 +132,11 @@ __device__ __forceinline__ void dft32_band(cpx (&u)[32], cpx (&y)[6])
 
 // MINB / MAXB: the band as compile-time constants (the reference's 11..43: the index-order sum is then 33 adds), or 0, 0: the
 // band is the run-time pair (a select per bin)
-template <int MINB, int MAXB>
-__global__ __launch_bounds__(256) void vadfft1024_band_kernel(const VadFftJob* __restrict__ jobs, VadFftPlan pl, int min_bin, int max_bin, int plain_loads)
+// MULTI: the band table `bs` instead (fvad_engine_band_sums_device): the 16 lanes of a frame take its bands in turn, each band
+// summed in index order from 0.0f like the single band (the same bits per band)
+template <int MINB, int MAXB, bool MULTI>
+__device__ __forceinline__ void vadfft1024_band_body(const VadFftJob* __restrict__ jobs, const VadFftPlan& pl, int min_bin, int max_bin,
+                                                     int plain_loads, const VadBandSet* bs)
 {
     // dynamic LDS (77 KB: over the static limit; two workgroups per CU): per wavefront a slab of 4 frames x 16 rows of 64 (+4)
     // floats; the window in the same padded rows; 48 magnitudes per frame
@@ -277,7 +280,16 @@ __global__ __launch_bounds__(256) void vadfft1024_band_kernel(const VadFftJob* _
             mg[k1 + 16 * j] = sqrtf(xk.r * xk.r + xk.i * xk.i) * norm; // FFT.zig:16-18 (bin 0's entry is never read)
         }
         __builtin_amdgcn_wave_barrier();
-        if (a == 0) {
+        if constexpr (MULTI) {
+            const long frame = 4 * grp + q;
+            if (frame < job.n_frames) {
+                for (int j = a; j < bs->n; j += 16) {
+                    float acc = 0.0f; // index order, BufferedFFT.zig:192-199
+                    for (int k = bs->lo[j]; k <= bs->hi[j]; ++k) acc += mg[k];
+                    job.band_sum[bs->idx[j] * bs->step + frame] = acc;
+                }
+            }
+        } else if (a == 0) {
             const f32x4* m4 = reinterpret_cast<const f32x4*>(mg);
             float m[48];
 #pragma unroll
@@ -298,6 +310,74 @@ __global__ __launch_bounds__(256) void vadfft1024_band_kernel(const VadFftJob* _
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+template <int MINB, int MAXB>
+__global__ __launch_bounds__(256) void vadfft1024_band_kernel(const VadFftJob* __restrict__ jobs, VadFftPlan pl, int min_bin, int max_bin, int plain_loads)
+{
+    vadfft1024_band_body<MINB, MAXB, false>(jobs, pl, min_bin, max_bin, plain_loads, nullptr);
+}
+
+__global__ __launch_bounds__(256) void vadfft1024_bands_kernel(const VadFftJob* __restrict__ jobs, VadFftPlan pl, VadBandSet bs, int plain_loads)
+{
+    vadfft1024_band_body<0, 0, true>(jobs, pl, 0, 0, plain_loads, &bs);
+}
+
+// ============================================================================ several bands per pass, every size of the wavefront kernels
+// vadfft_body's magnitudes (the same expression per bin) for the bins lo_all..hi_all the bands span, kept in LDS; then the lanes
+// take the bands in turn, each summed in index order from 0.0f: per band the bits of a single-band vadfft_jobs_kernel pass
+template <int R>
+__global__ __launch_bounds__(256) void vadfft_bands_kernel(const VadFftJob* __restrict__ jobs, VadFftPlan pl, VadBandSet bs, int lo_all, int hi_all)
+{
+    constexpr int N = 128 * R, NB = N / 2 + 1;
+    __shared__ __attribute__((aligned(16))) float zl[4][N];
+    __shared__ float mag[4][NB];
+    const VadFftJob j = jobs[blockIdx.y];
+    if ((long)blockIdx.x * 4 >= j.n_frames) return; // whole workgroup past this lane's frames
+    const long frame = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const bool active = frame < j.n_frames;
+    if (active) rfftN_wave<R>(j.den + frame * N, pl.win, pl, zl[wave], lane);
+    __syncthreads();
+    if (active) {
+        for (int k = lo_all + lane; k <= hi_all; k += 64) {
+            const cpx xk = rfftN_bin<R>(zl[wave], pl.st, k);
+            mag[wave][k] = sqrtf(xk.r * xk.r + xk.i * xk.i) * pl.norm; // FFT.zig:16-18
+        }
+    }
+    __syncthreads();
+    if (active) {
+        for (int b = lane; b < bs.n; b += 64) {
+            float acc = 0.0f; // BufferedFFT.zig:192-199
+            for (int k = bs.lo[b]; k <= bs.hi[b]; ++k) acc += mag[wave][k];
+            j.band_sum[bs.idx[b] * bs.step + frame] = acc;
+        }
+    }
+}
+
+int fvad_launch_vadfft_bands(const VadFftJob* jobs, int n_jobs, long max_frames, VadFftPlan pl, const VadBandSet& bs, int pruned,
+                             hipStream_t stream, int n_cu, int plain)
+{
+    if (n_jobs <= 0 || max_frames <= 0 || bs.n <= 0) return (int)hipSuccess;
+    if (pl.generic) return fvad_launch_rfft_generic_bands(jobs, n_jobs, max_frames, pl, bs, stream);
+    if (pruned) { // every band inside 1..47 at 1024 points: the launch geometry of fvad_launch_vadfft_jobs' band kernel
+        if (pl.n != 1024) return (int)hipErrorInvalidValue;
+        const long groups = (max_frames + 3) / 4, wg_all = (groups + 3) / 4;
+        long per_job = (2L * (n_cu > 0 ? n_cu : 256)) / n_jobs;
+        if (per_job < 1) per_job = 1;
+        if (per_job > wg_all) per_job = wg_all;
+        constexpr size_t lds = (size_t)(4 * 64 * V4_ROW + 16 * V4_ROW + 16 * 48) * sizeof(float);
+        const hipError_t e = hipFuncSetAttribute((const void*)vadfft1024_bands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(vadfft1024_bands_kernel, dim3((unsigned)per_job, (unsigned)n_jobs), dim3(256), lds, stream, jobs, pl, bs, plain);
+        return (int)hipGetLastError();
+    }
+    int lo_all = bs.lo[0], hi_all = bs.hi[0];
+    for (int b = 1; b < bs.n; ++b) { lo_all = bs.lo[b] < lo_all ? bs.lo[b] : lo_all; hi_all = bs.hi[b] > hi_all ? bs.hi[b] : hi_all; }
+    VADFFT_DISPATCH(pl.n, hipLaunchKernelGGL(vadfft_bands_kernel<R>, dim3((unsigned)((max_frames + 3) / 4), (unsigned)n_jobs), dim3(256), 0,
+                                              stream, jobs, pl, bs, lo_all, hi_all))
+    return (int)hipGetLastError();
 }
 
 void fvad_launch_vadfft(const float* den, long n_frames, VadFftPlan pl, int min_bin, int max_bin,

@@ -4,6 +4,7 @@ on top of the C ABI -- SURVEY.md section 8 f1/f3.  Plumbing only (JSON, paths, t
 the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
 
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
+    python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
 
 Plan schema = the reference's (simulator.zig:41-76, tmp/plan.example.json), unknown fields ignored
 (simulator.zig:152-154); audio/ref paths are relative to the plan file (simulator.zig:146,
@@ -202,6 +203,17 @@ def _run_instances(ctx, plan, audio):
         return list(pool.map(host_stage, range(len(audio))))
 
 
+def _read_instance(inst):
+    try:    # PCM16 files stay 16-bit all the way to the GPU (half the PCIe / HBM bytes; converted by the kernel
+        pcm, sr = fv.wav_read_i16(inst["audio_path"])   # that reads them, bit-identical to converting first)
+    except fv.FvadError:
+        pcm, sr = fv.wav_read(inst["audio_path"])
+    if sr != 48000:
+        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
+    with open(inst["ref_path"], "rb") as f:
+        return pcm, fv.parse_audacity(f.read())
+
+
 def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None):
     """Runs a whole plan; returns (report_text, per_instance_results).
 
@@ -217,15 +229,7 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
         ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])]
     else:
         ctxs = [ctx]
-    def read_instance(inst):
-        try:    # PCM16 files stay 16-bit all the way to the GPU (half the PCIe / HBM bytes; converted by the kernel
-            pcm, sr = fv.wav_read_i16(inst["audio_path"])   # that reads them, bit-identical to converting first)
-        except fv.FvadError:
-            pcm, sr = fv.wav_read(inst["audio_path"])
-        if sr != 48000:
-            raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
-        with open(inst["ref_path"], "rb") as f:
-            return pcm, fv.parse_audacity(f.read())
+    read_instance = _read_instance
 
     # the files side by side (the reference opens them on a thread each, SimulationInstance.zig:144-152): reading and
     # de-interleaving a two-hour file is most of a plan's wall time once the GPU does the rest
@@ -298,6 +302,170 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
     return text, results
 
 
+SWEEP_COLUMNS = ("P", "TP", "FP", "FN", "TPR", "PPV", "FNR", "FDR", "F", "FM")
+
+
+def _agg_row(agg):
+    return {"P": agg.total_positives_sec, "TP": agg.true_positives_sec, "FP": agg.false_positives_sec, "FN": agg.false_negatives_sec,
+            "TPR": agg.true_positive_rate.overall, "PPV": agg.precision.overall, "FNR": agg.false_negative_rate.overall,
+            "FDR": agg.false_discovery_rate.overall, "F": agg.f_score, "FM": agg.fm_index}
+
+
+# configs from which the VAD machines run on the GPU when run_sweep is left to choose: the measured crossover against 16 host threads
+# (tools/vad_sweep_time.py, 21 two-hour streams: the GPU machines are slower below 256 configs, about even at 256)
+SWEEP_DEVICE_MIN_CONFIGS = 256
+
+
+def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16):
+    """Scores many VADMachine configurations over one denoising pass of a plan's instances.
+
+    configs: list of VADMachine.Config override dicts (vad_overrides' form); default: the plan's vad_machine_config followed by its
+    alt_vad_machine_configs (VADPipeline.zig:110-122).  Flow: every channel of every instance is one lane of ONE device batch
+    (ragged lengths padded to the longest: chunks are causal, so padding changes no real chunk) -> fvad_engine_enqueue_device with
+    the denoised audio kept -> per channel-count group, fvad_engine_band_sums_device for the configs' distinct speech bands ->
+    the VAD machines -> per (instance, config) the Evaluator statistics against the labels, aggregated in plan order like
+    run_plan's report (statistics.zig:116-172).  vad_on: "device" (fvad_vad_batch_run_device, every (instance, config) machine on
+    the GPU), "host" (fvad_vad_batch_run on n_threads host threads over the band sums, one call per instance) or "auto" (the GPU
+    from SWEEP_DEVICE_MIN_CONFIGS configs on); both give the same bits.
+
+    Returns dict(configs, rows [one aggregate dict per config], aggregates [AggregateStats], segments [config][instance],
+    stats [config][instance]); prints one table row per config and writes the rows as JSON to json_path if given."""
+    plan = load_plan(plan_path)
+    if configs is None:
+        configs = [plan["vad_machine_config"]] + list(plan["alt_vad_machine_configs"])
+    configs = [dict(c) for c in configs]
+    if vad_on == "auto":
+        vad_on = "device" if len(configs) >= SWEEP_DEVICE_MIN_CONFIGS else "host"
+    if vad_on not in ("device", "host"):
+        raise ValueError(f"vad_on: {vad_on!r}")
+    F = plan["fft_size"]
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = _make_ctx(plan, 0, synth_seed)
+    loaded = [_read_instance(i) for i in plan["instances"]]
+    audio = [a for a, _ in loaded]
+    refs = [r for _, r in loaded]
+    t0 = time.perf_counter()
+    chunk = 24000
+    lens = [p.shape[1] for p in audio]
+    n_chunks = [n // chunk for n in lens]
+    L = max(lens)
+    stride = (L + 3) // 4 * 4                        # 16-byte aligned lanes
+    # instances grouped by channel count (a batch has one channel count), each group's lanes side by side
+    groups = {}
+    for i, p in enumerate(audio):
+        groups.setdefault(p.shape[0], []).append(i)
+    order = [i for members in groups.values() for i in members]
+    n_lanes = sum(audio[i].shape[0] for i in order)
+    n_ck = L // chunk
+    n_den = n_ck * chunk
+    nf_all = n_den // F
+    host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
+    l = 0
+    for i in order:
+        p = audio[i]
+        for c in range(p.shape[0]):
+            if p.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                np.multiply(p[c], np.float32(1.0 / 32768.0), out=host[l, :p.shape[1]], casting="unsafe")
+            else:
+                host[l, :p.shape[1]] = p[c]
+            l += 1
+    # the engine pass sums config 0's band (FFT.freqToBin as the library computes it); the sweep's bands come from their own pass
+    probe = fv.VadSweep(1, configs[:1], fft_size=F)
+    (min_bin, max_bin), = probe.bands()[0]
+    probe.close()
+    allocs = []
+
+    def dalloc(nbytes):
+        a = ctx.device_alloc(max(int(nbytes), 16))
+        allocs.append(a)
+        return a
+
+    segs = [[None] * len(audio) for _ in configs]
+    try:
+        d_pcm = dalloc(host.nbytes)
+        ctx.to_device(d_pcm, host)
+        del host
+        d_den = dalloc(n_lanes * n_den * 4)
+        d_band0 = dalloc(n_lanes * max(nf_all, 1) * 4)
+        d_rms = dalloc(n_lanes * max(n_ck, 1) * 4)
+        if n_ck:
+            opts = fv.EngineOpts()
+            fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
+            opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
+            ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d_pcm), n_lanes, stride, L, fv.vp(d_den), fv.vp(d_band0),
+                                                        fv.vp(d_rms), fv.C.byref(opts)), "fvad_engine_enqueue_device")
+        rms = np.zeros((n_lanes, max(n_ck, 1)), np.float32)
+        if n_ck:
+            ctx.to_host(rms, d_rms)
+        l0 = 0
+        for nch, members in groups.items():
+            sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+            try:
+                bins, _ = sweep.bands()
+                g_lanes = list(range(l0, l0 + len(members) * nch))
+                l0 += len(g_lanes)
+                d_gden = d_den + g_lanes[0] * n_den * 4
+                bstride = max(nf_all, 1)
+                d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                if nf_all:
+                    ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                g_rms = np.ascontiguousarray(rms[g_lanes])
+                if vad_on == "device":
+                    sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
+                                     [n_chunks[i] for i in members])
+                    for c in range(len(configs)):
+                        per = sweep.segments(c)
+                        for k, i in enumerate(members):
+                            segs[c][i] = per[k]
+                    continue
+                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
+                for k, i in enumerate(members):   # instances differ in length: one host batch each
+                    nf_i = n_chunks[i] * chunk // F
+                    one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
+                    try:
+                        one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
+                                np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
+                        for c in range(len(configs)):
+                            segs[c][i] = one.segments(c)[0]
+                    finally:
+                        one.close()
+            finally:
+                sweep.close()
+    finally:
+        for a in allocs:
+            ctx.device_free(a)
+        if own_ctx:
+            ctx.close()
+    elapsed = time.perf_counter() - t0
+    rows, aggs, all_stats = [], [], []
+    for c, cfg in enumerate(configs):
+        stat_cfg = {"ignore_shorter_than_sec": float(np.float32(cfg.get("min_vad_duration_sec", 0.7))),
+                    "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
+        stats = []
+        for i, ref in enumerate(refs):
+            secs = [(float(np.float32(x[0]) / np.float32(48000)), float(np.float32(x[1]) / np.float32(48000))) for x in segs[c][i]]
+            stats.append(fv.stats_from_segments(secs, ref, stat_cfg))
+        agg = fv.stats_aggregate(stats)
+        aggs.append(agg)
+        all_stats.append(stats)
+        rows.append(dict(config=c, **_agg_row(agg)))
+    result = {"configs": configs, "rows": rows, "aggregates": aggs, "segments": segs, "stats": all_stats}
+    if json_path:
+        with open(json_path, "w") as f:
+            json.dump({"configs": configs, "rows": rows,
+                       "segments": [[[list(map(float, x)) for x in inst] for inst in per] for per in segs]}, f, indent=1)
+    if out is not None:
+        out.write("| config |      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
+        for r in rows:
+            out.write("| {:>6} | {} | {} | {} | {} | {}% | {}% | {}% | {}% | {}% | {}% |\n".format(
+                r["config"], _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
+                *[_f(np.float32(r[k]) * np.float32(100), 5, 1) for k in ("TPR", "PPV", "FNR", "FDR")],
+                _f(np.float32(r["F"]) * np.float32(100), 6, 1), _f(np.float32(r["FM"]) * np.float32(100), 5, 1)))
+        out.write(f"[{len(configs)} configs x {len(audio)} instances in {elapsed:.2f} s]\n")
+    return result
+
+
 def frame_ratios(chunk_rms, n_frames, fft_size=1024, chunk=24000):
     """Per-frame volume_ratio exactly as the metadata flows through the three buffered stages
     (BufferedVolumeAnalyzer.zig:33-45 -> BufferedDenoiser.zig:83-86,115 -> BufferedFFT.zig:137-140,153):
@@ -331,7 +499,15 @@ def main(argv=None):
     ap.add_argument("--synth-seed", type=int, default=None, help="use random-init NSNet2 weights")
     ap.add_argument("--devices", default="0", help="comma-separated HIP devices: one context + one thread each, "
                                                    "instances dealt round-robin (e.g. 0,1,2,3,4,5,6,7)")
+    ap.add_argument("--sweep", action="store_true", help="score the plan's vad_machine_config and alt_vad_machine_configs over one "
+                                                         "denoising pass: one table row per config (device 0)")
+    ap.add_argument("--sweep-json", default=None, help="with --sweep: write the rows and segments to this JSON file")
+    ap.add_argument("--sweep-vad", default="auto", choices=("auto", "device", "host"),
+                    help="with --sweep: where the VAD machines run (auto: the GPU from %d configs on)" % SWEEP_DEVICE_MIN_CONFIGS)
     a = ap.parse_args(argv)
+    if a.sweep:
+        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)
+        return
     run_plan(a.input, synth_seed=a.synth_seed, devices=[int(d) for d in a.devices.split(",") if d != ""])
 
 

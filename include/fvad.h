@@ -272,6 +272,16 @@ int fvad_engine_enqueue_device_i16(fvad_ctx *ctx, const int16_t *d_pcm16, size_t
                                    size_t lane_stride, size_t n_samples, int16_t *d_denoised16,
                                    float *d_band_sum, float *d_chunk_rms,
                                    const fvad_engine_opts *opts);
+/* Band sums of several bands in one pass over device-resident denoised audio: n_bands bands (bins[2j], bins[2j+1]
+ * inclusive, a host array) of the fft_size-point periodic-Hann magnitude spectrum of every frame of every lane (lane l
+ * at d_denoised + l * lane_stride, frames at k * fft_size, k < n_samples / fft_size); band j of lane l at
+ * d_band_sum + (j * n_lanes + l) * band_stride.  Each band's sums have the bits an engine call with min_bin/max_bin =
+ * that band gives (FVAD_ERR_OUT_OF_RANGE for bins outside 0..fft_size/2 or max < min).  Frames are read as float pairs:
+ * d_denoised must be 8-byte aligned and lane_stride even (FVAD_ERR_INVALID_ARGUMENT otherwise); 16-byte alignment is not
+ * needed.  Returns when the work has completed. */
+int fvad_engine_band_sums_device(fvad_ctx *ctx, const float *d_denoised, size_t n_lanes, size_t lane_stride,
+                                 size_t n_samples, size_t fft_size, const int32_t *bins, size_t n_bands,
+                                 float *d_band_sum, size_t band_stride);
 /* NSNet2 graph only: features [n_seq][T][161] -> gains [n_seq][T][161] (host pointers).
  * Replaces onnx_instance.run() (NSNet2.zig:220) for n_seq independent sequences. */
 int fvad_nsnet2_forward(fvad_ctx *ctx, const float *features, size_t n_seq, size_t T,
@@ -432,6 +442,34 @@ size_t fvad_vad_batch_total_segments(const fvad_vad_batch *b);
 int fvad_vad_batch_segments(const fvad_vad_batch *b, fvad_speech_segment *out, size_t cap,
                             size_t *offsets);
 int fvad_vad_batch_audit(const fvad_vad_batch *b, size_t stream, fvad_vad_audit *out);
+
+/* Parameter sweeps: a batch of n_configs VADMachine.Configs over the same streams, one machine per (stream, config) --
+ * the reference's alt_vad_machine_configs (VADPipeline.zig:110-122,231-236) with every machine on its own speech band
+ * (VADMachine.zig:146-151).  Each config is checked like fvad_vad_create / fvad_pipeline_create do it (speech band above
+ * Nyquist: FVAD_ERR_OUT_OF_RANGE; a negative edge: FVAD_ERR_NEGATIVE_FREQUENCY; max bin < min bin or a channel-ratio ring
+ * of length 0: FVAD_ERR_INVALID_ARGUMENT).  fvad_vad_batch_run / _run_part take a sweep batch too: `band` then holds
+ * n_bands consecutive [n_lanes][band_stride] blocks (fvad_vad_batch_bands' order), config c reading block band_of[c].
+ * fvad_vad_batch_segments / _total_segments / _audit give config 0's results. */
+int fvad_vad_batch_create_sweep(const fvad_vad_config *cfgs, size_t n_configs, size_t sample_rate, size_t n_channels,
+                                size_t fft_size, size_t n_streams, fvad_vad_batch **out);
+size_t fvad_vad_batch_n_configs(const fvad_vad_batch *b); /* 1 for fvad_vad_batch_create */
+/* distinct speech bands of the configs (FFT.freqToBin of speech_min/max_freq, as fvad_pipeline_create computes them),
+ * bins[2j], bins[2j+1], in first-seen config order; band_of[c] = the band of config c (may be NULL) */
+int fvad_vad_batch_bands(const fvad_vad_batch *b, int32_t *bins, size_t cap, size_t *n_bands, uint32_t *band_of);
+/* config `config`'s segments, stream after stream, like fvad_vad_batch_segments */
+int fvad_vad_batch_config_segments(const fvad_vad_batch *b, size_t config, fvad_speech_segment *out, size_t cap,
+                                   size_t *offsets);
+int fvad_vad_batch_config_audit(const fvad_vad_batch *b, size_t stream, size_t config, fvad_vad_audit *out);
+/* fvad_vad_lazy_stats of machine (stream, config) in the last run, host or device */
+int fvad_vad_batch_lazy_stats(const fvad_vad_batch *b, size_t stream, size_t config, uint64_t *exact_evaluations,
+                              uint64_t *lazy_pushes);
+/* Every (stream, config) machine of b on the GPU (csrc/kernels_vad.hip); d_band as fvad_engine_band_sums_device writes it
+ * (band j of lane l at d_band + (j * n_lanes + l) * band_stride, lane = stream * n_channels + channel); stream s has
+ * n_frames[s] frames and n_chunks[s] chunks (host arrays; chunk_rms on the host: lane l's values at
+ * chunk_rms + l * rms_stride).  Returns when the segments and audits are in b; bit-identical to fvad_vad_batch_run. */
+int fvad_vad_batch_run_device(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                              const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
+                              const size_t *n_chunks, size_t chunk_size);
 
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;

@@ -1,0 +1,128 @@
+"""Cost of a VAD parameter sweep on config 4's corpus shape: S streams x H hours of synthetic denoised-like audio (seeded noise
+with speech-like bursts, generated on the device), N configs that vary threshold, windows and speech band.  Per N:
+  * K4: one multi-band pass (fvad_engine_band_sums_device with the sweep's distinct bands) against one single-band pass per
+    distinct band (and against one per config: each distinct band's pass counted for every config that uses it);
+  * the GPU VAD stage: device events around the machines' kernel inside fvad_vad_batch_run_device with both lane mappings
+    (context option vad_lane_map: a stream's configs per wavefront, the default, or a config's streams), and the call's host
+    part (frame ratios, uploads, read-back) separately;
+  * fvad_vad_batch_run with T host threads over the same band sums;
+  * device against host, bit for bit (segments and audits of every machine).
+python tools/vad_sweep_time.py [--streams 21] [--hours 2] [--configs 1,8,64,256] [--threads 16]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from conftest import load_package  # noqa: E402
+
+BANDS = [(500.0, 2000.0), (300.0, 3400.0), (1000.0, 4000.0), (200.0, 1200.0), (400.0, 2500.0), (600.0, 1800.0), (250.0, 4000.0),
+         (800.0, 3000.0)]
+
+
+def make_configs(n, seed):
+    rng = np.random.default_rng(seed)
+    out = [{}]
+    while len(out) < n:
+        lo, hi = BANDS[rng.integers(len(BANDS))]
+        out.append({"speech_min_freq": lo, "speech_max_freq": hi, "speech_threshold_factor": float(rng.uniform(3.0, 15.0)),
+                    "long_term_speech_avg_sec": float(rng.choice([60.0, 120.0, 180.0, 300.0])),
+                    "short_term_speech_avg_sec": float(rng.uniform(0.1, 0.5)),
+                    "channel_vol_ratio_avg_sec": float(rng.uniform(0.3, 1.0)),
+                    "max_speech_gap_sec": float(rng.uniform(1.0, 3.0)), "min_vad_duration_sec": float(rng.uniform(0.5, 1.0))})
+    return out[:n]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=21)
+    ap.add_argument("--hours", type=float, default=2.0)
+    ap.add_argument("--configs", default="1,8,64,256")
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--seed", type=int, default=4)
+    a = ap.parse_args()
+    import torch
+    pkg = load_package()
+    fv = pkg.binding
+    ctx = fv.Context(0)
+    chunk, F = 24000, 1024
+    n_chunks = int(a.hours * 3600 * 48000) // chunk
+    L = n_chunks * chunk
+    nf = L // F
+    S = a.streams
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(a.seed)
+    rng = np.random.default_rng(a.seed)
+    audio = torch.empty((S, L), dtype=torch.float32, device=dev)
+    for s in range(S):  # a noise floor with bursts of 0.5 .. 5 s every 1 .. 20 s, at frame resolution
+        edges = np.cumsum(rng.uniform(0.5, 20.0, int(L / 48000 / 5) + 8)) * 48000 / F
+        env = np.zeros(nf + 1, np.float32)
+        for x in edges:
+            i0 = int(x)
+            if i0 >= nf:
+                break
+            env[i0:min(nf, i0 + int(rng.uniform(0.5, 5.0) * 48000 / F))] = 1.0
+        e = torch.from_numpy(env[:nf]).to(dev).repeat_interleave(F)
+        audio[s] = torch.randn(L, generator=g, device=dev) * (0.01 + 0.2 * e)
+        del e
+    rms = torch.sqrt(torch.mean(audio.view(S, n_chunks, chunk) ** 2, dim=2)).cpu().numpy().astype(np.float32)
+    torch.cuda.synchronize()
+    d_den = audio.data_ptr()
+    print(f"{S} streams x {a.hours:g} h ({nf} frames each), mono, fft 1024", flush=True)
+    ctx.enable_timing(True)
+    for N in [int(x) for x in a.configs.split(",")]:
+        cfgs = make_configs(N, a.seed + N)
+        sw = fv.VadSweep(S, cfgs)
+        bins, band_of = sw.bands()
+        band = torch.empty((len(bins), S, nf), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        ctx.kernel_times()
+        ctx.band_sums_device(d_den, S, L, L, bins, band.data_ptr(), nf)
+        k4_multi = ctx.kernel_times().get("k4_bands", float("nan"))
+        one = torch.empty((S, nf), dtype=torch.float32, device=dev)
+        single = []
+        for b in bins:
+            ctx.band_sums_device(d_den, S, L, L, [b], one.data_ptr(), nf)
+            single.append(ctx.kernel_times().get("k4_bands", float("nan")))
+        k4_distinct = sum(single)
+        k4_singles = sum(single[j] for j in band_of)
+        torch.cuda.synchronize()
+        lane_ms = {}
+        for lane_map in ("config", "stream"):   # the device run kept below is the last one
+            ctx.set_option("vad_lane_map", lane_map)
+            t0 = time.perf_counter()
+            sw.run_device(ctx, band.data_ptr(), nf, [nf] * S, rms, [n_chunks] * S)
+            wall = time.perf_counter() - t0
+            kt = ctx.kernel_times()
+            lane_ms[lane_map] = kt.get("vad_machines", float("nan"))
+            if lane_map == "config":
+                segs_cfg = [sw.segments(c) for c in range(N)]
+        ctx.set_option("vad_lane_map", None)
+        vad_ms = lane_ms["stream"]
+        hb = band.cpu().numpy()
+        hs = fv.VadSweep(S, cfgs)
+        t0 = time.perf_counter()
+        hs.run(hb, rms, n_threads=a.threads)
+        host = time.perf_counter() - t0
+        same = all(sw.segments(c) == hs.segments(c) == segs_cfg[c] for c in range(N)) and \
+            all(sw.audit(s, c) == hs.audit(s, c) for s in range(S) for c in range(N))
+        n_segs = sum(len(x) for c in range(N) for x in sw.segments(c))
+        ex_d = sum(sw.lazy_stats(s, c)[0] for s in range(S) for c in range(N))
+        ex_h = sum(hs.lazy_stats(s, c)[0] for s in range(S) for c in range(N))
+        print(f"N={N:4d} ({len(bins)} bands): K4 multi-band {k4_multi:8.2f} ms vs {len(bins)} single-band passes {k4_distinct:8.2f} ms "
+              f"({N} per config: {k4_singles:9.2f} ms) | GPU VAD kernel {vad_ms:8.2f} ms (lanes by config: {lane_ms['config']:8.2f} ms) "
+              f"+ host part {wall * 1e3 - vad_ms:7.2f} ms | host {a.threads} threads {host * 1e3:9.1f} ms | "
+              f"speed-up {host * 1e3 / vad_ms:6.1f}x (kernel), {host / wall:6.1f}x (call) | {n_segs} segments, exact evals "
+              f"{ex_d} dev / {ex_h} host | bit-identical: {same}", flush=True)
+        sw.close()
+        hs.close()
+        del band, one
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
