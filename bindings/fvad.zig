@@ -338,6 +338,11 @@ pub extern "c" fn fvad_pipeline_trace(p: *const Pipeline, band_volumes: [*]f32, 
 pub extern "c" fn fvad_segment_to_sec(s: *const SpeechSegment, sample_rate: usize) SegmentSec;
 pub extern "c" fn fvad_stats_from_segments(vad: [*]const SegmentSec, n_vad: usize, ref: [*]const SegmentSec, n_ref: usize, cfg: *const StatConfig, out: *SingleStats) c_int;
 pub extern "c" fn fvad_stats_aggregate(stats: [*]const SingleStats, n: usize, out: *AggregateStats) c_int;
+/// scoring a VAD batch against reference labels, on the host or (fvad_vad_batch_run_device) on the device (see fvad.h)
+pub extern "c" fn fvad_vad_batch_set_references(b: *VadBatch, refs: ?[*]const SegmentSec, ref_offsets: [*]const usize, stat_cfgs: [*]const StatConfig) c_int;
+pub extern "c" fn fvad_vad_batch_set_keep_segments(b: *VadBatch, keep: c_int) c_int;
+pub extern "c" fn fvad_vad_batch_score(b: *VadBatch, n_threads: c_int) c_int;
+pub extern "c" fn fvad_vad_batch_config_stats(b: *const VadBatch, config: usize, out: [*]SingleStats) c_int;
 // one thread or process per GPU, stream i of the plan on rank i % world: the per-stream SingleStats of every rank,
 // all-gathered over RCCL in plan order, ready for statistics.aggregate (src/Evaluator/statistics.zig:116-172) --
 // replaces the join of simulator.zig:221-232's per-file threads

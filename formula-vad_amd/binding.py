@@ -258,6 +258,10 @@ SIGNATURES = {
     "fvad_stats_from_segments": (C.c_int, [C.POINTER(SegmentSec), sz, C.POINTER(SegmentSec), sz,
                                            C.POINTER(StatConfig), C.POINTER(SingleStats)]),
     "fvad_stats_aggregate": (C.c_int, [C.POINTER(SingleStats), sz, C.POINTER(AggregateStats)]),
+    "fvad_vad_batch_set_references": (C.c_int, [vp, C.POINTER(SegmentSec), C.POINTER(sz), C.POINTER(StatConfig)]),
+    "fvad_vad_batch_set_keep_segments": (C.c_int, [vp, C.c_int]),
+    "fvad_vad_batch_score": (C.c_int, [vp, C.c_int]),
+    "fvad_vad_batch_config_stats": (C.c_int, [vp, sz, C.POINTER(SingleStats)]),
     "fvad_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8), sz]),
     "fvad_comm_create": (C.c_int, [vp, C.POINTER(C.c_uint8), sz, C.c_int, C.c_int, C.POINTER(vp)]),
     "fvad_comm_destroy": (None, [vp]),
@@ -443,6 +447,12 @@ class Context:
 
     def enable_timing(self, on=True):
         self._ck(lib().fvad_ctx_enable_timing(self.h, 1 if on else 0), "fvad_ctx_enable_timing")
+        self._timing = bool(on)
+
+    @property
+    def timing(self):
+        """whether kernel timing is on (as set through enable_timing; off in a new context)"""
+        return getattr(self, "_timing", False)
 
     def kernel_times(self):
         cap = 64
@@ -943,6 +953,38 @@ class VadSweep:
         check(lib().fvad_vad_batch_lazy_stats(self.h, stream, config, C.byref(e), C.byref(p)), "fvad_vad_batch_lazy_stats")
         return e.value, p.value
 
+    def set_references(self, refs, stat_cfgs):
+        """fvad_vad_batch_set_references: refs[s] = stream s's labels, [(from_sec, to_sec)] or a float32 [n][2] array;
+        stat_cfgs: one StatConfig dict per config (stats_from_segments' keys), or one dict for every config"""
+        if isinstance(stat_cfgs, dict):
+            stat_cfgs = [stat_cfgs] * self.n_configs
+        assert len(refs) == self.n_streams and len(stat_cfgs) == self.n_configs
+        arrs = [np.asarray(r, np.float32).reshape(-1, 2) for r in refs]
+        flat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 2), np.float32))
+        offs = (sz * (self.n_streams + 1))(*np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(int).tolist())
+        sc = (StatConfig * self.n_configs)(*[StatConfig(c.get("ignore_shorter_than_sec", 0.0), c.get("extrude_start", 0.0),
+                                                        c.get("extrude_end", 0.0), c.get("fill_gaps", 0.0)) for c in stat_cfgs])
+        check(lib().fvad_vad_batch_set_references(self.h, flat.ctypes.data_as(C.POINTER(SegmentSec)), offs, sc),
+              "fvad_vad_batch_set_references")
+
+    def keep_segments(self, keep):
+        """fvad_vad_batch_set_keep_segments: keep=False leaves a device run's segments on the device (segments() then raises)"""
+        check(lib().fvad_vad_batch_set_keep_segments(self.h, 1 if keep else 0), "fvad_vad_batch_set_keep_segments")
+
+    def score(self, n_threads=16):
+        """fvad_vad_batch_score: every machine's segments against its stream's labels on n_threads host threads"""
+        check(lib().fvad_vad_batch_score(self.h, n_threads), "fvad_vad_batch_score")
+
+    def config_stats(self, config, out=None):
+        """config's SingleStats of every stream from the last scoring (host or device), as float32 [n_streams][11]; out: a
+        C-contiguous float32 [n_streams][11] array to fill instead"""
+        if out is None:
+            out = np.empty((self.n_streams, len(SingleStats._fields_)), np.float32)
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == (self.n_streams, len(SingleStats._fields_))
+        check(lib().fvad_vad_batch_config_stats(self.h, config, out.ctypes.data_as(C.POINTER(SingleStats))),
+              "fvad_vad_batch_config_stats")
+        return out
+
     def close(self):
         if self.h:
             lib().fvad_vad_batch_destroy(self.h)
@@ -1068,6 +1110,15 @@ def stats_aggregate(stats):
     arr = (SingleStats * max(len(stats), 1))(*stats)
     out = AggregateStats()
     check(lib().fvad_stats_aggregate(arr, len(stats), C.byref(out)), "statistics.aggregate")
+    return out
+
+
+def stats_aggregate_array(stats):
+    """statistics.aggregate over a C-contiguous float32 [n][11] array of SingleStats (VadSweep.config_stats' layout)"""
+    assert stats.dtype == np.float32 and stats.flags["C_CONTIGUOUS"] and stats.shape[-1] == len(SingleStats._fields_)
+    out = AggregateStats()
+    check(lib().fvad_stats_aggregate(stats.ctypes.data_as(C.POINTER(SingleStats)), stats.shape[0], C.byref(out)),
+          "statistics.aggregate")
     return out
 
 

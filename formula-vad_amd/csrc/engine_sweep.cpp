@@ -1,5 +1,6 @@
 // engine_sweep.cpp -- parameter sweeps on the GPU: several speech bands per K4 pass (fvad_engine_band_sums_device) and every
-// (stream, config) VAD machine of a sweep batch at once (fvad_vad_batch_run_device, kernels_vad.hip).
+// (stream, config) VAD machine of a sweep batch at once (fvad_vad_batch_run_device, kernels_vad.hip), scored against the
+// streams' labels on the device when the batch has them (kernels_eval.hip).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -15,6 +16,7 @@ using namespace fvad;
 static_assert(sizeof(VadSegmentDev) == sizeof(fvad_speech_segment) && offsetof(VadSegmentDev, avg_channel_vol_ratio) ==
               offsetof(fvad_speech_segment, avg_channel_vol_ratio), "VadSegmentDev mirrors fvad_speech_segment");
 static_assert(sizeof(VadAuditDev) == sizeof(fvad_vad_audit), "VadAuditDev mirrors fvad_vad_audit");
+static_assert(sizeof(fvad_single_stats) == 11 * sizeof(float), "fvad_single_stats is copied back as it is");
 
 namespace {
 
@@ -249,22 +251,71 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
         if (attempt == 1) return set_err(ctx, FVAD_ERR_HIP, "vad machines: segment count changed between two launches");
         cap = most;
     }
-    std::vector<VadSegmentDev> segs(cap * (size_t)M);
+    // ---- scoring (kernels_eval.hip): every machine against its stream's labels, on the segments of the final launch
+    std::vector<fvad_single_stats> scores;
+    if (b->has_refs) {
+        const size_t n_ref = b->ref_off[S];
+        fvad_segment_sec* d_refs = nullptr;
+        float* d_pmax = nullptr;
+        unsigned long long* d_roff = nullptr;
+        fvad_stat_config* d_scfg = nullptr;
+        fvad_single_stats* d_scores = nullptr;
+        const std::vector<unsigned long long> roff(b->ref_off.begin(), b->ref_off.end());
+        FVAD_HIP(ctx, scratch.alloc(&d_refs, n_ref));
+        FVAD_HIP(ctx, scratch.alloc(&d_pmax, n_ref));
+        FVAD_HIP(ctx, scratch.alloc(&d_roff, S + 1));
+        FVAD_HIP(ctx, scratch.alloc(&d_scfg, NC));
+        FVAD_HIP(ctx, scratch.alloc(&d_scores, (size_t)M));
+        if (n_ref) {
+            FVAD_HIP(ctx, hipMemcpyAsync(d_refs, b->refs.data(), n_ref * sizeof(fvad_segment_sec), hipMemcpyHostToDevice, st));
+            FVAD_HIP(ctx, hipMemcpyAsync(d_pmax, b->ref_pmax.data(), n_ref * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+        FVAD_HIP(ctx, hipMemcpyAsync(d_roff, roff.data(), (S + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_scfg, b->stat_cfgs.data(), NC * sizeof(fvad_stat_config), hipMemcpyHostToDevice, st));
+        VadScoreArgs sa{};
+        sa.segs = d_segs;
+        sa.seg_count = d_count;
+        sa.seg_cap = (uint32_t)cap;
+        sa.n_machines = M;
+        sa.n_configs = (int)NC;
+        sa.sample_rate_f = (float)b->sample_rate;
+        sa.refs = d_refs;
+        sa.ref_pmax = d_pmax;
+        sa.ref_off = d_roff;
+        sa.stat_cfgs = d_scfg;
+        sa.out = d_scores;
+        time_begin(ctx, "vad_score");
+        const int e = fvad_launch_vad_score(sa, st);
+        time_end(ctx);
+        if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_score");
+        scores.resize((size_t)M);
+        FVAD_HIP(ctx, hipMemcpyAsync(scores.data(), d_scores, (size_t)M * sizeof(fvad_single_stats), hipMemcpyDeviceToHost, st));
+    }
+    // the segments only when the caller keeps them (fvad_vad_batch_set_keep_segments)
+    std::vector<VadSegmentDev> segs(b->keep_segments ? cap * (size_t)M : 0);
     std::vector<VadAuditDev> audits((size_t)M);
     std::vector<unsigned long long> stats(2 * (size_t)M);
-    FVAD_HIP(ctx, hipMemcpyAsync(segs.data(), d_segs, segs.size() * sizeof(VadSegmentDev), hipMemcpyDeviceToHost, st));
+    if (b->keep_segments)
+        FVAD_HIP(ctx, hipMemcpyAsync(segs.data(), d_segs, segs.size() * sizeof(VadSegmentDev), hipMemcpyDeviceToHost, st));
     FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), d_audit, audits.size() * sizeof(VadAuditDev), hipMemcpyDeviceToHost, st));
     FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     FVAD_HIP(ctx, hipStreamSynchronize(st));
     FVAD_HIP(ctx, hipGetLastError());
     for (long m = 0; m < M; ++m) {
         auto& v = b->segs[(size_t)m];
-        v.resize(count[(size_t)m]);
-        if (count[(size_t)m]) memcpy(v.data(), segs.data() + (size_t)m * cap, count[(size_t)m] * sizeof(fvad_speech_segment));
+        if (b->keep_segments) {
+            v.resize(count[(size_t)m]);
+            if (count[(size_t)m]) memcpy(v.data(), segs.data() + (size_t)m * cap, count[(size_t)m] * sizeof(fvad_speech_segment));
+        } else {
+            std::vector<fvad_speech_segment>().swap(v);
+        }
         memcpy(&b->audits[(size_t)m], &audits[(size_t)m], sizeof(fvad_vad_audit));
         b->exact_evals[(size_t)m] = stats[2 * (size_t)m];
         b->lazy_pushes[(size_t)m] = stats[2 * (size_t)m + 1];
     }
+    b->segs_kept = b->keep_segments;
+    b->scored = b->has_refs;
+    if (b->has_refs) b->scores = std::move(scores);
     b->machines.clear(); // nothing to continue from: a later fvad_vad_batch_run_part must start at frame 0
     b->next_frame = 0;
     return FVAD_OK;

@@ -675,6 +675,8 @@ int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_st
                    [&](size_t i) { run_machine(i / NC, i % NC, ratio.data() + (i / NC) * n_frames, has.data() + (i / NC) * n_frames); });
     }
     b->next_frame = first_frame + n_frames;
+    b->segs_kept = true;
+    b->scored = false; // the scores were of the previous segments
     return FVAD_OK;
 }
 
@@ -686,6 +688,7 @@ int fvad_vad_batch_run(fvad_vad_batch* b, const float* band, size_t band_stride,
 
 size_t fvad_vad_batch_total_segments(const fvad_vad_batch* b) // (config 0's on a sweep batch)
 {
+    if (b && !b->segs_kept) return SIZE_MAX; // a device run without keeping its segments
     size_t n = 0;
     if (b) for (size_t s = 0; s < b->n_streams; ++s) n += b->segs[s * b->cfgs.size()].size();
     return n;
@@ -699,6 +702,7 @@ int fvad_vad_batch_segments(const fvad_vad_batch* b, fvad_speech_segment* out, s
 int fvad_vad_batch_config_segments(const fvad_vad_batch* b, size_t config, fvad_speech_segment* out, size_t cap, size_t* offsets)
 {
     if (!b || !offsets || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b->segs_kept) return FVAD_ERR_INVALID_ARGUMENT; // a device run without keeping its segments: none to give
     const size_t NC = b->cfgs.size();
     size_t n = 0;
     for (size_t s = 0; s < b->n_streams; ++s) { offsets[s] = n; n += b->segs[s * NC + config].size(); }

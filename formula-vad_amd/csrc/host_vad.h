@@ -100,4 +100,15 @@ struct fvad_vad_batch {
     // a run in parts (fvad_vad_batch_run_part): the streams' machines live on between the parts
     std::vector<std::unique_ptr<fvad::VadMachine>> machines;
     uint64_t next_frame = 0;
+    // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
+    // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
+    bool has_refs = false;
+    std::vector<fvad_segment_sec> refs;
+    std::vector<float> ref_pmax;
+    std::vector<size_t> ref_off;
+    std::vector<fvad_stat_config> stat_cfgs;
+    bool scored = false;
+    std::vector<fvad_single_stats> scores;
+    // fvad_vad_batch_set_keep_segments: 0 = a device run leaves the segments on the device (segs_kept is false until a run keeps them)
+    bool keep_segments = true, segs_kept = true;
 };

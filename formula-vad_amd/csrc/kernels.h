@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/fvad.h"
+
 enum { FVAD_ACT_NONE = 0, FVAD_ACT_RELU = 1, FVAD_ACT_SIGMOID = 2 };
 
 // ------------------------------------------------------------------ geometry (NSNet2.zig:12-16)
@@ -247,3 +249,20 @@ struct VadMachinesArgs {
     unsigned long long* stats; // [n_machines][2]: exact evaluations of the long-term chain, lazy pushes
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ scoring the machines of a VAD batch (kernels_eval.hip)
+// one lane per machine, machine = stream * n_configs + config: the Evaluator statistics of its segments (eval_walk.h)
+struct VadScoreArgs {
+    const VadSegmentDev* segs;            // [n_machines][seg_cap], as fvad_launch_vad_machines wrote them
+    const uint32_t* seg_count;            // [n_machines] (counts above seg_cap are read as seg_cap)
+    uint32_t seg_cap;
+    long n_machines;
+    int n_configs;
+    float sample_rate_f;                  // (float)sample_rate
+    const fvad_segment_sec* refs;         // every stream's labels, sorted by start
+    const float* ref_pmax;                // prefix max of their ends, per stream
+    const unsigned long long* ref_off;    // [n_streams + 1]
+    const fvad_stat_config* stat_cfgs;    // [n_configs]
+    fvad_single_stats* out;               // [n_machines]
+};
+int fvad_launch_vad_score(const VadScoreArgs& a, hipStream_t stream); // hipError_t as int

@@ -5,6 +5,8 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
 
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
+    python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K]   (or: run_grid(path, grid): a parameter grid,
+                                                      every machine scored on the GPU, the top K configs by F-score)
 
 Plan schema = the reference's (simulator.zig:41-76, tmp/plan.example.json), unknown fields ignored
 (simulator.zig:152-154); audio/ref paths are relative to the plan file (simulator.zig:146,
@@ -16,6 +18,7 @@ SimulationInstance.zig:101-104).  Differences, by design:
   * `preload_audio` only changes how samples are pushed in the reference, not the result.
 """
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -316,6 +319,57 @@ def _agg_row(agg):
 SWEEP_DEVICE_MIN_CONFIGS = 256
 
 
+def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
+    """The denoising pass of a sweep: every channel of every instance is one lane of ONE device batch (ragged lengths padded to
+    the longest: chunks are causal, so padding changes no real chunk), fvad_engine_enqueue_device with the denoised audio kept
+    (device memory from dalloc).  Instances are grouped by channel count (a VAD batch has one channel count), each group's lanes
+    side by side.  Returns (groups {n_channels: [instance]}, n_chunks [instance], n_den samples per lane, nf_all frames per
+    lane, d_den, chunk RMS [lane][chunk] on the host)."""
+    chunk = 24000
+    lens = [p.shape[1] for p in audio]
+    n_chunks = [n // chunk for n in lens]
+    L = max(lens)
+    stride = (L + 3) // 4 * 4                        # 16-byte aligned lanes
+    groups = {}
+    for i, p in enumerate(audio):
+        groups.setdefault(p.shape[0], []).append(i)
+    order = [i for members in groups.values() for i in members]
+    n_lanes = sum(audio[i].shape[0] for i in order)
+    n_ck = L // chunk
+    n_den = n_ck * chunk
+    nf_all = n_den // F
+    host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
+    l = 0
+    for i in order:
+        p = audio[i]
+        for c in range(p.shape[0]):
+            if p.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                np.multiply(p[c], np.float32(1.0 / 32768.0), out=host[l, :p.shape[1]], casting="unsafe")
+            else:
+                host[l, :p.shape[1]] = p[c]
+            l += 1
+    # the engine pass sums config 0's band (FFT.freqToBin as the library computes it); the sweep's bands come from their own pass
+    probe = fv.VadSweep(1, [config0], fft_size=F)
+    (min_bin, max_bin), = probe.bands()[0]
+    probe.close()
+    d_pcm = dalloc(host.nbytes)
+    ctx.to_device(d_pcm, host)
+    del host
+    d_den = dalloc(n_lanes * n_den * 4)
+    d_band0 = dalloc(n_lanes * max(nf_all, 1) * 4)
+    d_rms = dalloc(n_lanes * max(n_ck, 1) * 4)
+    if n_ck:
+        opts = fv.EngineOpts()
+        fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
+        opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
+        ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d_pcm), n_lanes, stride, L, fv.vp(d_den), fv.vp(d_band0),
+                                                    fv.vp(d_rms), fv.C.byref(opts)), "fvad_engine_enqueue_device")
+    rms = np.zeros((n_lanes, max(n_ck, 1)), np.float32)
+    if n_ck:
+        ctx.to_host(rms, d_rms)
+    return groups, n_chunks, n_den, nf_all, d_den, rms
+
+
 def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16):
     """Scores many VADMachine configurations over one denoising pass of a plan's instances.
 
@@ -347,33 +401,6 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     refs = [r for _, r in loaded]
     t0 = time.perf_counter()
     chunk = 24000
-    lens = [p.shape[1] for p in audio]
-    n_chunks = [n // chunk for n in lens]
-    L = max(lens)
-    stride = (L + 3) // 4 * 4                        # 16-byte aligned lanes
-    # instances grouped by channel count (a batch has one channel count), each group's lanes side by side
-    groups = {}
-    for i, p in enumerate(audio):
-        groups.setdefault(p.shape[0], []).append(i)
-    order = [i for members in groups.values() for i in members]
-    n_lanes = sum(audio[i].shape[0] for i in order)
-    n_ck = L // chunk
-    n_den = n_ck * chunk
-    nf_all = n_den // F
-    host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
-    l = 0
-    for i in order:
-        p = audio[i]
-        for c in range(p.shape[0]):
-            if p.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
-                np.multiply(p[c], np.float32(1.0 / 32768.0), out=host[l, :p.shape[1]], casting="unsafe")
-            else:
-                host[l, :p.shape[1]] = p[c]
-            l += 1
-    # the engine pass sums config 0's band (FFT.freqToBin as the library computes it); the sweep's bands come from their own pass
-    probe = fv.VadSweep(1, configs[:1], fft_size=F)
-    (min_bin, max_bin), = probe.bands()[0]
-    probe.close()
     allocs = []
 
     def dalloc(nbytes):
@@ -383,21 +410,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
 
     segs = [[None] * len(audio) for _ in configs]
     try:
-        d_pcm = dalloc(host.nbytes)
-        ctx.to_device(d_pcm, host)
-        del host
-        d_den = dalloc(n_lanes * n_den * 4)
-        d_band0 = dalloc(n_lanes * max(nf_all, 1) * 4)
-        d_rms = dalloc(n_lanes * max(n_ck, 1) * 4)
-        if n_ck:
-            opts = fv.EngineOpts()
-            fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
-            opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
-            ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d_pcm), n_lanes, stride, L, fv.vp(d_den), fv.vp(d_band0),
-                                                        fv.vp(d_rms), fv.C.byref(opts)), "fvad_engine_enqueue_device")
-        rms = np.zeros((n_lanes, max(n_ck, 1)), np.float32)
-        if n_ck:
-            ctx.to_host(rms, d_rms)
+        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
         l0 = 0
         for nch, members in groups.items():
             sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
@@ -466,6 +479,205 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     return result
 
 
+
+def _stat_cfg(cfg):
+    """the Evaluator's StatConfig of a config (simulator.zig:127-132): labels shorter than its min_vad_duration_sec are ignored"""
+    return {"ignore_shorter_than_sec": float(np.float32(cfg.get("min_vad_duration_sec", 0.7))),
+            "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
+
+
+# the largest grid run_grid accepts: every config is one VAD machine per instance, each with its own long-term ring on the device
+# (34 KB at the default 180 s: 4096 configs x 21 instances are 2.9 GB)
+GRID_MAX_CONFIGS = 16384
+
+
+def expand_grid(grid):
+    """Grid {"base": {overrides}, "axes": {field: [values]}} -> the configs (vad_overrides' form): the cartesian product of the
+    axes in file order, the last axis fastest, each on top of base (both in the plan's vad_machine_config form).  Raises
+    ValueError for an unknown field, an empty axis or more than GRID_MAX_CONFIGS configs."""
+    if not isinstance(grid, dict):
+        raise ValueError("a grid is a JSON object with \"base\" and \"axes\"")
+    extra = [k for k in grid if k not in ("base", "axes")]
+    if extra:
+        raise ValueError(f"unknown grid key(s) {extra}: a grid has \"base\" and \"axes\"")
+    base = grid.get("base") or {}
+    axes = grid.get("axes") or {}
+    if not isinstance(base, dict) or not isinstance(axes, dict):
+        raise ValueError("grid \"base\" and \"axes\" are JSON objects")
+    for k in list(base) + list(axes):
+        if k not in VAD_FIELDS:
+            raise ValueError(f"unknown VADMachine.Config field {k!r} in the grid; valid fields: {', '.join(VAD_FIELDS)}")
+    n = 1
+    for k, vals in axes.items():
+        if not isinstance(vals, list) or not vals:
+            raise ValueError(f"grid axis {k!r} is empty (an axis is a non-empty list of values)")
+        n *= len(vals)
+    if n > GRID_MAX_CONFIGS:
+        raise ValueError(f"the grid has {n} configs, more than GRID_MAX_CONFIGS = {GRID_MAX_CONFIGS}")
+    configs = []
+    for combo in itertools.product(*axes.values()):
+        c = dict(base)
+        c.update(zip(axes.keys(), combo))
+        try:
+            configs.append(vad_overrides(c))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"grid values must be numbers (initial_long_term_avg may be null): {c}") from e
+    return configs
+
+
+def _ranked(rows):
+    """rows by aggregate F-score, highest first (NaN last), ties by config index"""
+    return sorted(rows, key=lambda r: (0, -r["F"], r["config"]) if r["F"] == r["F"] else (1, 0.0, r["config"]))
+
+
+def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
+             n_threads=16):
+    """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
+    denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
+    denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
+    scored against the instance's labels -- score_on "device": on the GPU next to its segments (fvad_vad_batch_run_device with
+    references set and keep_segments 0: only counts, audits and the statistics come back), "host": fvad_vad_batch_score on
+    n_threads host threads; "auto": where the machines ran.  vad_on as in run_sweep.  Both scorers give run_sweep's bits.
+    Per config, fvad_stats_aggregate over the instances in plan order.  The grid is checked before any GPU work.  With device
+    scoring, the context's kernel timing is switched on around each fvad_vad_batch_run_device call (for the scoring kernel's
+    time) if it was off, and off again after it; a caller that has it on keeps its records, and the machines' time then
+    includes the scoring.  Labels must be numbers: the scorers walk them sorted, so a NaN label (fvad_parse_audacity reads
+    "nan") is refused (ValueError, before any GPU work), where run_sweep's per-pair fvad_stats_from_segments takes it.
+
+    Returns dict(configs, rows [one aggregate dict per config, config order], aggregates [AggregateStats], stats float32
+    [config][instance][11] (fvad_single_stats), times {stage: s}); prints the top rows by F-score and the stage times, and
+    writes the configs and all rows as JSON to json_path if given."""
+    if isinstance(grid, str):
+        with open(grid) as f:
+            grid = json.load(f)
+    configs = expand_grid(grid)
+    if vad_on == "auto":
+        vad_on = "device" if len(configs) >= SWEEP_DEVICE_MIN_CONFIGS else "host"
+    if vad_on not in ("device", "host"):
+        raise ValueError(f"vad_on: {vad_on!r}")
+    if score_on == "auto":
+        score_on = vad_on
+    if score_on not in ("device", "host"):
+        raise ValueError(f"score_on: {score_on!r}")
+    if score_on == "device" and vad_on != "device":
+        raise ValueError("score_on='device' scores next to the device machines: it needs vad_on='device'")
+    plan = load_plan(plan_path)
+    F = plan["fft_size"]
+    stat_cfgs = [_stat_cfg(c) for c in configs]
+    loaded = [_read_instance(i) for i in plan["instances"]]
+    for inst, (_, ref) in zip(plan["instances"], loaded):
+        if any(x != x for r in ref for x in r):
+            raise ValueError(f"{inst['ref_path']}: a NaN label; grid scoring walks the labels sorted by start and needs "
+                             "numbers (fvad_vad_batch_set_references refuses NaN)")
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = _make_ctx(plan, 0, synth_seed)
+    audio = [a for a, _ in loaded]
+    refs = [r for _, r in loaded]
+    NC, n_inst = len(configs), len(audio)
+    stats = np.empty((NC, n_inst, len(fv.SingleStats._fields_)), np.float32)
+    times = {"denoise": 0.0, "bands": 0.0, "machines": 0.0, "scoring": 0.0}
+    chunk = 24000
+    t_all = time.perf_counter()
+    allocs = []
+
+    def dalloc(nbytes):
+        a = ctx.device_alloc(max(int(nbytes), 16))
+        allocs.append(a)
+        return a
+
+    try:
+        t0 = time.perf_counter()
+        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
+        times["denoise"] = time.perf_counter() - t0
+        l0 = 0
+        for nch, members in groups.items():
+            sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+            try:
+                t0 = time.perf_counter()
+                bins, _ = sweep.bands()
+                g_lanes = list(range(l0, l0 + len(members) * nch))
+                l0 += len(g_lanes)
+                d_gden = d_den + g_lanes[0] * n_den * 4
+                bstride = max(nf_all, 1)
+                d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                if nf_all:
+                    ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                g_rms = np.ascontiguousarray(rms[g_lanes])
+                times["bands"] += time.perf_counter() - t0
+                if vad_on == "device":
+                    if score_on == "device":
+                        sweep.set_references([refs[i] for i in members], stat_cfgs)
+                        sweep.keep_segments(False)
+                    # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
+                    # caller's own timing records are left alone: the machines' time then includes the scoring)
+                    timed = score_on == "device" and not ctx.timing
+                    if timed:
+                        ctx.enable_timing(True)
+                    try:
+                        t0 = time.perf_counter()
+                        sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
+                                         [n_chunks[i] for i in members])
+                        wall = time.perf_counter() - t0
+                        score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
+                    finally:
+                        if timed:
+                            ctx.enable_timing(False)
+                    if score_on == "device":
+                        times["machines"] += wall - score_s
+                        times["scoring"] += score_s
+                    else:
+                        times["machines"] += wall
+                        t0 = time.perf_counter()
+                        sweep.set_references([refs[i] for i in members], stat_cfgs)
+                        sweep.score(n_threads)
+                        times["scoring"] += time.perf_counter() - t0
+                    for c in range(NC):
+                        stats[c, members] = sweep.config_stats(c)
+                    continue
+                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
+                for k, i in enumerate(members):   # instances differ in length: one host batch each
+                    nf_i = n_chunks[i] * chunk // F
+                    one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
+                    try:
+                        t0 = time.perf_counter()
+                        one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
+                                np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
+                        times["machines"] += time.perf_counter() - t0
+                        t0 = time.perf_counter()
+                        one.set_references([refs[i]], stat_cfgs)
+                        one.score(n_threads)
+                        for c in range(NC):
+                            stats[c, i] = one.config_stats(c)[0]
+                        times["scoring"] += time.perf_counter() - t0
+                    finally:
+                        one.close()
+            finally:
+                sweep.close()
+    finally:
+        for a in allocs:
+            ctx.device_free(a)
+        if own_ctx:
+            ctx.close()
+    aggs = [fv.stats_aggregate_array(stats[c]) for c in range(NC)]
+    rows = [dict(config=c, **_agg_row(agg)) for c, agg in enumerate(aggs)]
+    elapsed = time.perf_counter() - t_all
+    if json_path:
+        with open(json_path, "w") as f:
+            json.dump({"grid": grid, "configs": configs, "rows": rows}, f, indent=1)
+    if out is not None:
+        out.write(f"top {min(top, NC)} of {NC} configs by F-score (β = 0.7):\n")
+        out.write("| config |      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
+        for r in _ranked(rows)[:top]:
+            out.write("| {:>6} | {} | {} | {} | {} | {}% | {}% | {}% | {}% | {}% | {}% |\n".format(
+                r["config"], _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
+                *[_f(np.float32(r[k]) * np.float32(100), 5, 1) for k in ("TPR", "PPV", "FNR", "FDR")],
+                _f(np.float32(r["F"]) * np.float32(100), 6, 1), _f(np.float32(r["FM"]) * np.float32(100), 5, 1)))
+        out.write(f"[{NC} configs x {n_inst} instances in {elapsed:.2f} s: denoise {times['denoise']:.2f} s, bands "
+                  f"{times['bands']:.2f} s, machines ({vad_on}) {times['machines']:.2f} s, scoring ({score_on}) "
+                  f"{times['scoring']:.3f} s]\n")
+    return {"configs": configs, "rows": rows, "aggregates": aggs, "stats": stats, "times": times}
+
 def frame_ratios(chunk_rms, n_frames, fft_size=1024, chunk=24000):
     """Per-frame volume_ratio exactly as the metadata flows through the three buffered stages
     (BufferedVolumeAnalyzer.zig:33-45 -> BufferedDenoiser.zig:83-86,115 -> BufferedFFT.zig:137-140,153):
@@ -501,10 +713,17 @@ def main(argv=None):
                                                    "instances dealt round-robin (e.g. 0,1,2,3,4,5,6,7)")
     ap.add_argument("--sweep", action="store_true", help="score the plan's vad_machine_config and alt_vad_machine_configs over one "
                                                          "denoising pass: one table row per config (device 0)")
-    ap.add_argument("--sweep-json", default=None, help="with --sweep: write the rows and segments to this JSON file")
+    ap.add_argument("--sweep-json", default=None, help="with --sweep: write the rows and segments to this JSON file; "
+                                                       "with --sweep-grid: the configs and all rows")
     ap.add_argument("--sweep-vad", default="auto", choices=("auto", "device", "host"),
-                    help="with --sweep: where the VAD machines run (auto: the GPU from %d configs on)" % SWEEP_DEVICE_MIN_CONFIGS)
+                    help="with --sweep / --sweep-grid: where the VAD machines run (auto: the GPU from %d configs on)" % SWEEP_DEVICE_MIN_CONFIGS)
+    ap.add_argument("--sweep-grid", default=None, help="score every config of a grid file ({\"base\": {...}, \"axes\": {field: "
+                                                          "[values]}}) over one denoising pass; print the top configs (device 0)")
+    ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
     a = ap.parse_args(argv)
+    if a.sweep_grid:
+        run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed)
+        return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)
         return

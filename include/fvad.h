@@ -566,6 +566,26 @@ int fvad_stats_from_segments(const fvad_segment_sec *vad, size_t n_vad,
                              const fvad_stat_config *cfg, fvad_single_stats *out);
 /* statistics.aggregate(stats)  statistics.zig:116-172 -- in slice order */
 int fvad_stats_aggregate(const fvad_single_stats *stats, size_t n, fvad_aggregate_stats *out);
+
+/* ---- scoring a VAD batch (fvad_vad_batch_create or _create_sweep): the statistics of every (stream, config) machine against
+ * its stream's labels, fvad_single_stats machine by machine, each bit for bit fvad_stats_from_segments of the machine's
+ * fvad_segment_to_sec-converted segments and the stream's labels.
+ * fvad_vad_batch_set_references: stream s's labels are refs[ref_offsets[s] .. ref_offsets[s + 1]) (ref_offsets has
+ * n_streams + 1 entries, ref_offsets[0] == 0, non-decreasing); the batch keeps its own copy, stably sorted by start
+ * (Evaluator.initAndRun).  stat_cfgs has one fvad_stat_config per config.  NULL arguments, bad offsets or a NaN label:
+ * FVAD_ERR_INVALID_ARGUMENT.  Once references are set, fvad_vad_batch_run_device also scores every machine on the device
+ * (csrc/kernels_eval.hip) after its last launch; without references it does not score.
+ * fvad_vad_batch_score scores the segments in b on n_threads host threads (FVAD_ERR_INVALID_ARGUMENT without references
+ * or segments).  fvad_vad_batch_config_stats: config `config`'s stats of every stream (out has n_streams entries) from the
+ * last scoring, host or device; FVAD_ERR_INVALID_ARGUMENT if the segments in b have not been scored.
+ * fvad_vad_batch_set_keep_segments(b, 0): fvad_vad_batch_run_device leaves the segments on the device (counts, audits,
+ * lazy statistics and scores still come back); until a run keeps segments again, fvad_vad_batch_segments and
+ * _config_segments return FVAD_ERR_INVALID_ARGUMENT and fvad_vad_batch_total_segments returns SIZE_MAX.  Default 1. */
+int fvad_vad_batch_set_references(fvad_vad_batch *b, const fvad_segment_sec *refs, const size_t *ref_offsets,
+                                  const fvad_stat_config *stat_cfgs);
+int fvad_vad_batch_set_keep_segments(fvad_vad_batch *b, int keep);
+int fvad_vad_batch_score(fvad_vad_batch *b, int n_threads);
+int fvad_vad_batch_config_stats(const fvad_vad_batch *b, size_t config, fvad_single_stats *out);
 /* ---- multi-GPU: the plan's streams are dealt round-robin to one rank (process or thread) per GPU, nothing but
  * these per-stream statistics ever crosses GPUs.  Replaces the join of the reference's one-thread-per-file
  * instances (src/simulator.zig:221-232) in front of report_generator.zig:48-68: every rank hands in the
