@@ -2,10 +2,7 @@
 // (stream, config) VAD machine of a sweep batch at once (fvad_vad_batch_run_device, kernels_vad.hip), scored against the
 // streams' labels on the device when the batch has them (kernels_eval.hip).
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstring>
-#include <thread>
 #include <vector>
 
 #include "host_vad.h"
@@ -13,9 +10,6 @@
 
 using namespace fvad;
 
-static_assert(sizeof(VadSegmentDev) == sizeof(fvad_speech_segment) && offsetof(VadSegmentDev, avg_channel_vol_ratio) ==
-              offsetof(fvad_speech_segment, avg_channel_vol_ratio), "VadSegmentDev mirrors fvad_speech_segment");
-static_assert(sizeof(VadAuditDev) == sizeof(fvad_vad_audit), "VadAuditDev mirrors fvad_vad_audit");
 static_assert(sizeof(fvad_single_stats) == 11 * sizeof(float), "fvad_single_stats is copied back as it is");
 
 namespace {
@@ -120,58 +114,17 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     // ---- host: the frame ratios (one per stream: they do not depend on the config) and the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
     std::vector<float> ratio(S * ratio_stride, 0.0f);
-    {
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-            for (;;) {
-                const size_t s = next.fetch_add(1);
-                if (s >= S) break;
-                sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[s], F, chunk_size, ratio.data() + s * ratio_stride);
-            }
-        };
-        const int nt = (int)std::min<size_t>(S, 16);
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(work);
-        work();
-        for (auto& t : th) t.join();
-    }
-    constexpr double kU = 1.1102230246251565e-16;
+    deal(S, 16, [&](size_t s) {
+        sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[s], F, chunk_size, ratio.data() + s * ratio_stride);
+    });
     std::vector<VadMachineCfg> hc(NC);
     uint32_t lt_max = 1, st_max = 1, cr_max = 1;
-    for (size_t c = 0; c < NC; ++c) { // the expressions of VadMachine's constructor, finish_step, on_speech_end and decide (host_vad.cpp)
-        const fvad_vad_config& cf = b->cfgs[c];
-        const float sample_rate_f = (float)b->sample_rate, fft_size_f = (float)F;
-        const float eval_per_sec = sample_rate_f / fft_size_f;
-        const size_t long_len = std::max<size_t>(1, (size_t)(eval_per_sec * cf.long_term_speech_avg_sec));
-        const size_t short_len = std::max<size_t>(1, (size_t)(eval_per_sec * cf.short_term_speech_avg_sec));
-        const size_t ratio_len = (size_t)(eval_per_sec * cf.channel_vol_ratio_avg_sec);
-        if (ratio_len == 0 || long_len > 0xFFFFFFFFu || short_len > 0xFFFFFFFFu || ratio_len > 0xFFFFFFFFu)
-            return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
-        VadMachineCfg& k = hc[c];
-        k.lt_scalar = 1.0 / (double)long_len;
-        k.st_scalar = 1.0 / (double)short_len;
-        k.cr_scalar = 1.0 / (double)ratio_len;
-        k.lt_q_init = cf.initial_long_term_avg * k.lt_scalar;
-        k.initial = cf.initial_long_term_avg;
-        k.factor = (double)cf.speech_threshold_factor;
-        k.ratio_threshold = (double)cf.channel_vol_ratio_threshold;
-        const double n = (double)long_len;
-        k.gamma = n * kU / (1.0 - n * kU);
-        k.min_open = (uint64_t)(sample_rate_f * cf.min_consecutive_sec_to_open);
-        k.max_gap = (uint64_t)(sample_rate_f * cf.max_speech_gap_sec);
-        k.start_buffer = (uint64_t)((float)b->sample_rate * 2);
-        k.end_buffer = (uint64_t)((float)b->sample_rate * 2);
-        k.input_len_sec = fft_size_f / sample_rate_f;
-        k.sample_rate_f = sample_rate_f;
-        k.min_vad_duration_sec = cf.min_vad_duration_sec;
-        k.long_len = (uint32_t)long_len;
-        k.short_len = (uint32_t)short_len;
-        k.ratio_len = (uint32_t)ratio_len;
-        k.has_init = cf.has_initial_long_term_avg != 0;
-        k.band = b->band_of[c];
-        lt_max = std::max(lt_max, k.long_len);
-        st_max = std::max(st_max, k.short_len);
-        cr_max = std::max(cr_max, k.ratio_len);
+    for (size_t c = 0; c < NC; ++c) {
+        if (vad_machine_cfg(b->cfgs[c], b->sample_rate, F, &hc[c])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
+        hc[c].band = b->band_of[c];
+        lt_max = std::max(lt_max, hc[c].long_len);
+        st_max = std::max(st_max, hc[c].short_len);
+        cr_max = std::max(cr_max, hc[c].ratio_len);
     }
 
     // ---- device
@@ -183,7 +136,7 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     float* d_lt = nullptr;
     float* d_rings = nullptr;
     uint32_t* d_count = nullptr;
-    VadAuditDev* d_audit = nullptr;
+    fvad_vad_audit* d_audit = nullptr;
     unsigned long long* d_stats = nullptr;
     std::vector<long> nf_l(n_frames, n_frames + S);
     FVAD_HIP(ctx, scratch.alloc(&d_cfg, NC));
@@ -231,10 +184,10 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     // redoes the run (the machines start fresh in every launch: same results).
     const size_t bound = max_nf / 4 + 1;
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
-                                                  : std::max<size_t>(256, (512u << 20) / sizeof(VadSegmentDev) / (size_t)M);
+                                                  : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / (size_t)M);
     size_t cap = std::min(bound, room);
     std::vector<uint32_t> count((size_t)M);
-    VadSegmentDev* d_segs = nullptr;
+    fvad_speech_segment* d_segs = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (d_segs) { hipFree(d_segs); scratch.ptrs.pop_back(); d_segs = nullptr; }
         FVAD_HIP(ctx, scratch.alloc(&d_segs, cap * (size_t)M));
@@ -292,27 +245,27 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
         FVAD_HIP(ctx, hipMemcpyAsync(scores.data(), d_scores, (size_t)M * sizeof(fvad_single_stats), hipMemcpyDeviceToHost, st));
     }
     // the segments only when the caller keeps them (fvad_vad_batch_set_keep_segments)
-    std::vector<VadSegmentDev> segs(b->keep_segments ? cap * (size_t)M : 0);
-    std::vector<VadAuditDev> audits((size_t)M);
+    std::vector<fvad_speech_segment> segs(b->keep_segments ? cap * (size_t)M : 0);
+    std::vector<fvad_vad_audit> audits((size_t)M);
     std::vector<unsigned long long> stats(2 * (size_t)M);
     if (b->keep_segments)
-        FVAD_HIP(ctx, hipMemcpyAsync(segs.data(), d_segs, segs.size() * sizeof(VadSegmentDev), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), d_audit, audits.size() * sizeof(VadAuditDev), hipMemcpyDeviceToHost, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(segs.data(), d_segs, segs.size() * sizeof(fvad_speech_segment), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), d_audit, audits.size() * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
     FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), d_stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     FVAD_HIP(ctx, hipStreamSynchronize(st));
     FVAD_HIP(ctx, hipGetLastError());
     for (long m = 0; m < M; ++m) {
         auto& v = b->segs[(size_t)m];
         if (b->keep_segments) {
-            v.resize(count[(size_t)m]);
-            if (count[(size_t)m]) memcpy(v.data(), segs.data() + (size_t)m * cap, count[(size_t)m] * sizeof(fvad_speech_segment));
+            const fvad_speech_segment* sm = segs.data() + (size_t)m * cap;
+            v.assign(sm, sm + count[(size_t)m]);
         } else {
             std::vector<fvad_speech_segment>().swap(v);
         }
-        memcpy(&b->audits[(size_t)m], &audits[(size_t)m], sizeof(fvad_vad_audit));
         b->exact_evals[(size_t)m] = stats[2 * (size_t)m];
         b->lazy_pushes[(size_t)m] = stats[2 * (size_t)m + 1];
     }
+    b->audits = std::move(audits);
     b->segs_kept = b->keep_segments;
     b->scored = b->has_refs;
     if (b->has_refs) b->scores = std::move(scores);

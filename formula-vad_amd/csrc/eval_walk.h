@@ -19,12 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/fvad.h"
-
-#if defined(__HIPCC__) || defined(__HIP__)
-#define FVAD_HD __host__ __device__
-#else
-#define FVAD_HD
-#endif
+#include "vad_machine.h" // FVAD_HD
 
 namespace fvad_eval {
 

@@ -3,10 +3,7 @@
 // Evaluator.initAndRun (Evaluator.zig:90-111) per machine: the machine's segments converted to seconds as
 // SimulationInstance.storeResult does (fvad_segment_to_sec), the stream's labels sorted once, statistics.fromEvaluator.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstring>
-#include <thread>
 #include <vector>
 
 #include "eval_walk.h"
@@ -67,16 +64,7 @@ int fvad_vad_batch_score(fvad_vad_batch* b, int n_threads)
         out[m] = fvad_eval::score_walk(vad, (uint32_t)v.size(), b->refs.data() + r0, b->ref_pmax.data() + r0,
                                        (uint32_t)(b->ref_off[s + 1] - r0), b->stat_cfgs[c]);
     };
-    const int nt = (int)std::min<size_t>((size_t)std::max(n_threads, 1), M);
-    if (nt <= 1) {
-        for (size_t m = 0; m < M; ++m) score(m);
-    } else {
-        std::atomic<size_t> next{0};
-        std::vector<std::thread> th;
-        for (int t = 0; t < nt; ++t)
-            th.emplace_back([&]() { for (;;) { const size_t m = next.fetch_add(1); if (m >= M) break; score(m); } });
-        for (auto& t : th) t.join();
-    }
+    fvad::deal(M, n_threads, score);
     b->scores = std::move(out);
     b->scored = true;
     return FVAD_OK;

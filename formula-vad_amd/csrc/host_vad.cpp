@@ -5,12 +5,13 @@
 // order on every push (RollingAverage.zig:45-56), integer sample arithmetic, @intFromFloat
 // truncations.  Segment boundaries are integers decided by `short_term > threshold`
 // (VADMachine.zig:171), so this code keeps the reference's exact operation order; the GPU only
-// supplies the per-frame band sums and per-chunk RMS values that feed it.
+// supplies the per-frame band sums and per-chunk RMS values that feed it.  The machine's step past
+// its rolling averages is vad_machine.h's, which the sweep kernel (kernels_vad.hip) shares.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -122,107 +123,53 @@ MetaResult analyse_volume(const float* channel_rms, size_t n_channels)
 }
 
 // ------------------------------------------------------------------ VADMachine
-VadMachine::VadMachine(const fvad_vad_config& c, size_t sample_rate_, size_t n_channels_, size_t fft_size_)
-    : cfg(c), sample_rate(sample_rate_), n_channels(n_channels_), fft_size(fft_size_),
-      long_term(1, false, 0), short_term(1, false, 0), ch_ratio(1, false, 0)
+int vad_machine_cfg(const fvad_vad_config& c, size_t sample_rate, size_t fft_size, VadMachineCfg* out)
 {
     // VADMachine.zig:75-106
     const float sample_rate_f = (float)sample_rate;
     const float fft_size_f = (float)fft_size;
     const float eval_per_sec = sample_rate_f / fft_size_f;
-    size_t long_len = (size_t)(eval_per_sec * cfg.long_term_speech_avg_sec);
-    size_t short_len = (size_t)(eval_per_sec * cfg.short_term_speech_avg_sec);
-    const size_t ratio_len = (size_t)(eval_per_sec * cfg.channel_vol_ratio_avg_sec);
-    long_len = std::max<size_t>(1, long_len);
-    short_len = std::max<size_t>(1, short_len);
-    long_term = RollingAverage(long_len, cfg.has_initial_long_term_avg != 0, cfg.initial_long_term_avg);
-    short_term = RollingAverage(short_len, false, 0);
-    ch_ratio = RollingAverage(ratio_len, false, 0);
+    const size_t long_len = std::max<size_t>(1, (size_t)(eval_per_sec * c.long_term_speech_avg_sec));
+    const size_t short_len = std::max<size_t>(1, (size_t)(eval_per_sec * c.short_term_speech_avg_sec));
+    const size_t ratio_len = (size_t)(eval_per_sec * c.channel_vol_ratio_avg_sec);
+    VadMachineCfg& k = *out;
+    k.lt_scalar = 1.0 / (double)long_len;
+    k.st_scalar = 1.0 / (double)short_len;
+    k.cr_scalar = 1.0 / (double)ratio_len;
+    k.lt_q_init = c.initial_long_term_avg * k.lt_scalar;
+    k.initial = c.initial_long_term_avg;
+    k.factor = (double)c.speech_threshold_factor;
+    k.ratio_threshold = (double)c.channel_vol_ratio_threshold;
+    const double n = (double)long_len;
+    k.gamma = n * kU / (1.0 - n * kU);
+    k.min_open = (uint64_t)(sample_rate_f * c.min_consecutive_sec_to_open); // :161
+    k.max_gap = (uint64_t)(sample_rate_f * c.max_speech_gap_sec);           // :163
+    k.start_buffer = (uint64_t)(sample_rate_f * 2);                          // :312-325
+    k.end_buffer = (uint64_t)(sample_rate_f * 2);
+    k.input_len_sec = fft_size_f / sample_rate_f;
+    k.sample_rate_f = sample_rate_f;
+    k.min_vad_duration_sec = c.min_vad_duration_sec;
+    k.long_len = (uint32_t)long_len;
+    k.short_len = (uint32_t)short_len;
+    k.ratio_len = (uint32_t)ratio_len;
+    k.has_init = c.has_initial_long_term_avg != 0;
+    k.band = 0;
+    if (ratio_len == 0 || long_len > 0xFFFFFFFFu || short_len > 0xFFFFFFFFu || ratio_len > 0xFFFFFFFFu) return FVAD_ERR_INVALID_ARGUMENT;
+    return FVAD_OK;
+}
+
+VadMachine::VadMachine(const fvad_vad_config& c, size_t sample_rate, size_t n_channels_, size_t fft_size)
+    : n_channels(n_channels_), long_term(1, false, 0), short_term(1, false, 0), ch_ratio(1, false, 0)
+{
+    vad_machine_cfg(c, sample_rate, fft_size, &cf); // (every caller has checked c with it)
+    long_term = RollingAverage(cf.long_len, cf.has_init != 0, cf.initial);
+    short_term = RollingAverage(cf.short_len, false, 0);
+    ch_ratio = RollingAverage(cf.ratio_len, false, 0);
+    lt_last = long_term.last_avg; // (an initial value fills the ring and evaluates its average)
+    has_last = long_term.has_last_avg;
     segments.reserve(100); // :111
-    audit.min_rel_threshold_margin = INFINITY;
-    audit.min_abs_ratio_margin = INFINITY;
-    audit.n_frames = 0;
     const char* eager = getenv("FVAD_VAD_EAGER");
     lt_lazy = !(eager && eager[0] == '1');
-}
-
-uint64_t VadMachine::offset_start(uint64_t vad_from) const // :312-317
-{
-    const uint64_t start_buffer = (uint64_t)((float)sample_rate * 2);
-    return vad_from - std::min(start_buffer, vad_from);
-}
-uint64_t VadMachine::offset_end(uint64_t vad_to) const // :320-325
-{
-    const uint64_t end_buffer = (uint64_t)((float)sample_rate * 2);
-    return vad_to + end_buffer;
-}
-
-fvad_vad_result VadMachine::on_speech_end() // :265-309
-{
-    const float sample_rate_f = (float)sample_rate;
-    const uint64_t sample_from = speech_start_index, sample_to = speech_end_index;
-    const uint64_t length_samples = sample_to - sample_from;
-    const float length_sec = (float)length_samples / sample_rate_f;
-    const bool speech_duration_met = length_sec >= cfg.min_vad_duration_sec;
-    const float avg_ratio = channel_vol_ratio_sum / (float)channel_vol_ratio_count;
-    if (speech_duration_met) {
-        fvad_speech_segment s;
-        s.sample_from = offset_start(sample_from);
-        s.sample_to = offset_end(sample_to);
-        s.avg_channel_vol_ratio = avg_ratio;
-        s.vad_met_sec = vad_threshold_met_cumulative_sec;
-        segments.push_back(s);
-        return {FVAD_REC_COMPLETED, offset_end(sample_to)};
-    }
-    return {FVAD_REC_ABORTED, 0};
-}
-
-fvad_vad_result VadMachine::finish_step(uint64_t index, bool threshold_met, bool has_ratio, float ratio)
-{
-    const float sample_rate_f = (float)sample_rate;
-    const uint64_t min_consecutive_to_open = (uint64_t)(sample_rate_f * cfg.min_consecutive_sec_to_open); // :161
-    const uint64_t max_gap_samples = (uint64_t)(sample_rate_f * cfg.max_speech_gap_sec);                 // :163
-    fvad_vad_result result = {FVAD_REC_NONE, 0};
-    const State from_state = state;
-    switch (state) { // :189-233
-    case CLOSED:
-        if (threshold_met) { state = OPENING; speech_start_index = index; }
-        break;
-    case OPENING: {
-        const uint64_t since = index - speech_start_index;
-        const bool met = since >= min_consecutive_to_open;
-        if (threshold_met && met) {
-            state = OPEN;
-            result = {FVAD_REC_STARTED, offset_start(speech_start_index)};
-        } else if (!threshold_met) {
-            state = CLOSED;
-        }
-        break;
-    }
-    case OPEN:
-        if (!threshold_met) { state = CLOSING; speech_end_index = index; }
-        break;
-    case CLOSING: {
-        const uint64_t since = index - speech_end_index;
-        const bool met = since >= max_gap_samples;
-        if (threshold_met) state = OPEN;
-        else if (met) { state = CLOSED; result = on_speech_end(); }
-        break;
-    }
-    }
-    // trackSpeechStats, :241-263
-    const float input_length_sec = (float)fft_size / sample_rate_f;
-    const float r = has_ratio ? ratio : 0;
-    if (from_state == CLOSED && state == OPENING) {
-        channel_vol_ratio_sum = r;
-        channel_vol_ratio_count = 1;
-        vad_threshold_met_cumulative_sec = input_length_sec;
-    } else if (from_state == OPEN) {
-        channel_vol_ratio_sum += r;
-        channel_vol_ratio_count += 1;
-        if (threshold_met) vad_threshold_met_cumulative_sec += input_length_sec;
-    }
-    return result;
 }
 
 // ---- lazily exact long-term average
@@ -237,34 +184,20 @@ fvad_vad_result VadMachine::finish_step(uint64_t index, bool threshold_met, bool
 //   |lt_approx - chain| <= gamma_N sum|q_i|(anchor) + lt_err + gamma_N sum|q_i|(now)
 // (gamma_N = N u / (1 - N u), u = 2^-53: the chain's error against the real-number sum when lt_approx was
 // anchored on it, the updates' rounding, the chain's own error now).
-// decide() evaluates the comparison with the threshold interval this gives; only if `short_term` falls
+// decide() (vad_machine.h) evaluates the comparison with the threshold interval this gives; only if `short_term` falls
 // inside the interval, or the frame could lower the audit's minimum margin, is the chain run for real
 // (long_term_exact: the reference's additions in the reference's order).  Every decision and every
 // audited number is therefore the one the eager evaluation produces; the tests compare whole runs
 // bit for bit with the oracle.
-static constexpr double kU = 1.1102230246251565e-16; // 2^-53
-
 void VadMachine::long_term_exact()
 {
-    RollingAverage& a = long_term;
-    const double* qq = a.q.data();
-    double acc = 0.0, pref = 0.0, abs_sum = 0.0;
-    for (size_t i = 0; i < a.len; ++i) {
-        if (i == a.write_idx) pref = acc;
+    const double* qq = long_term.q.data();
+    double acc = 0.0, abs_sum = 0.0;
+    for (size_t i = 0; i < long_term.len; ++i) {
         acc += qq[i]; // == a += data[i] * scalar (RollingAverage.zig:50-53), products cached in q
         abs_sum += std::fabs(qq[i]);
     }
-    a.last_avg = acc;
-    a.has_last_avg = true;
-    a.pref = (a.write_idx == 0) ? 0.0 : pref;
-    lt_approx = acc;
-    lt_abs = abs_sum;
-    lt_abs_anchor = abs_sum;
-    lt_anchored = true;
-    lt_err = 0.0;
-    lt_stale = false;
-    lt_updates = 0;
-    ++lt_exact_evals;
+    anchor(acc, abs_sum);
 }
 
 void VadMachine::long_term_push(float mv) // RollingAverage.push for the long-term ring
@@ -272,7 +205,8 @@ void VadMachine::long_term_push(float mv) // RollingAverage.push for the long-te
     RollingAverage& a = long_term;
     if (!a.steady || !lt_lazy) { // ring not full yet (or eager mode): the reference's path as is
         const bool was_steady = a.steady;
-        a.push(mv);
+        lt_last = a.push(mv);
+        has_last = true;
         if (lt_lazy && !was_steady && a.steady) long_term_exact();
         return;
     }
@@ -282,61 +216,7 @@ void VadMachine::long_term_push(float mv) // RollingAverage.push for the long-te
     a.data[w] = (double)mv;
     a.q[w] = qn;
     a.write_idx = (w + 1) % a.len;
-    const double s1 = lt_approx + qn, s2 = s1 - qo;
-    lt_err += 2.0 * kU * (std::fabs(s1) + std::fabs(s2)); // each rounding <= u |result|; doubled
-    lt_abs += std::fabs(qn) - std::fabs(qo);
-    lt_approx = s2;
-    lt_stale = true;
-    a.has_last_avg = true;
-    ++lt_lazy_pushes;
-    if (++lt_updates >= 4096) long_term_exact(); // keep the bound tight
-}
-
-bool VadMachine::decide(double short_term_avg, double ratio_avg, double* threshold_out)
-{
-    const double f = (double)cfg.speech_threshold_factor;
-    if (long_term.steady && lt_stale && threshold_out) long_term_exact();
-    if (long_term.steady && lt_stale) {
-        const double n = (double)long_term.len;
-        const double gamma = n * kU / (1.0 - n * kU);
-        // lt_abs is itself updated in floating point: widen it by its own drift
-        const double abs_now = std::fabs(lt_abs) * (1.0 + 1e-9) + 8192.0 * 2.0 * kU * (std::fabs(lt_abs) + lt_abs_anchor);
-        const double delta = lt_err + 2.0 * gamma * (abs_now + lt_abs_anchor);
-        double t0 = (lt_approx - delta) * f, t1 = (lt_approx + delta) * f;
-        if (t0 > t1) std::swap(t0, t1);
-        const double lo = t0 - std::fabs(t0) * 4.0 * kU - 1e-300, hi = t1 + std::fabs(t1) * 4.0 * kU + 1e-300;
-        const bool sure_true = short_term_avg > hi, sure_false = short_term_avg <= lo;
-        bool need_exact = !(sure_true || sure_false);
-        if (!need_exact && hi > 0) {
-            // smallest relative margin |st - thr| / thr any threshold in [lo, hi] could give
-            const double gap = sure_true ? short_term_avg - hi : lo - short_term_avg;
-            const double m_lb = gap / (sure_true ? hi : std::max(lo, hi));
-            if (!(m_lb * (1.0 - 1e-9) > audit.min_rel_threshold_margin)) need_exact = true;
-        }
-        if (!need_exact) {
-            const double rm = std::fabs(ratio_avg - (double)cfg.channel_vol_ratio_threshold);
-            if (rm < audit.min_abs_ratio_margin) audit.min_abs_ratio_margin = rm;
-            audit.n_frames++;
-            return sure_true && ratio_avg > (double)cfg.channel_vol_ratio_threshold;
-        }
-        long_term_exact();
-    }
-    double base; // :169  last_avg orelse initial_long_term_avg orelse short_term
-    if (long_term.has_last_avg) base = long_term.last_avg;
-    else if (cfg.has_initial_long_term_avg) base = cfg.initial_long_term_avg;
-    else base = short_term_avg;
-    const double threshold = base * f; // :170
-    const bool met = short_term_avg > threshold && ratio_avg > (double)cfg.channel_vol_ratio_threshold; // :171
-    // margin audit: how close was this frame to flipping?
-    if (threshold > 0) {
-        const double m = std::fabs(short_term_avg - threshold) / threshold;
-        if (m < audit.min_rel_threshold_margin) audit.min_rel_threshold_margin = m;
-    }
-    const double rm = std::fabs(ratio_avg - (double)cfg.channel_vol_ratio_threshold);
-    if (rm < audit.min_abs_ratio_margin) audit.min_abs_ratio_margin = rm;
-    audit.n_frames++;
-    if (threshold_out) *threshold_out = threshold;
-    return met;
+    if (lazy_update(qn, qo)) long_term_exact();
 }
 
 float VadMachine::min_volume(const float* channel_volumes) const // :153-158
@@ -356,9 +236,21 @@ fvad_vad_result VadMachine::run(uint64_t index, const float* channel_volumes, bo
     const float mv = min_volume(channel_volumes);
     const double st = short_term.push(mv);                       // :166
     const double cr = ch_ratio.push(has_ratio ? ratio : 0);      // :167
-    const bool met = decide(st, cr, nullptr);
+    const bool met = decide(cf, st, cr, [&] { long_term_exact(); });
     if (!met) long_term_push(mv);                                // :176-178
-    return finish_step(index, met, has_ratio, ratio);
+    return finish_step(cf, index, met, has_ratio, ratio, [&](const fvad_speech_segment& s) { segments.push_back(s); });
+}
+
+// items 0 .. n - 1 dealt to up to n_threads host threads
+void deal(size_t n, int n_threads, const std::function<void(size_t)>& fn)
+{
+    const int nt = (int)std::min<size_t>((size_t)std::max(n_threads, 1), n);
+    if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
+    std::vector<std::thread> th;
+    std::atomic<size_t> next{0};
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= n) break; fn(i); } });
+    for (auto& t : th) t.join();
 }
 
 // ------------------------------------------------------------------ many streams
@@ -368,31 +260,14 @@ void run_many(VadMachine* const* vads, size_t n_streams, const float* const* ban
               const float* const* ratio, const size_t* n_frames, size_t n_channels,
               const uint64_t* first_index, size_t fft_size, int n_threads)
 {
-    if (n_threads < 1) n_threads = 1;
-    auto run_stream = [&](size_t s) {
+    deal(n_streams, n_threads, [&](size_t s) {
         VadMachine* m = vads[s];
         for (size_t k = 0; k < n_frames[s]; ++k) {
             const float r = ratio[s][k];
             const bool has_ratio = !std::isnan(r);
             m->run(first_index[s] + (uint64_t)k * fft_size, band[s] + k * n_channels, has_ratio, r);
         }
-    };
-    if (n_threads == 1 || n_streams <= 1) {
-        for (size_t s = 0; s < n_streams; ++s) run_stream(s);
-        return;
-    }
-    std::vector<std::thread> th;
-    std::atomic<size_t> next{0};
-    const int nt = (int)std::min<size_t>((size_t)n_threads, n_streams);
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&]() {
-            for (;;) {
-                const size_t i = next.fetch_add(1);
-                if (i >= n_streams) break;
-                run_stream(i);
-            }
-        });
-    for (auto& t : th) t.join();
+    });
 }
 
 } // namespace fvad
@@ -415,8 +290,8 @@ void fvad_vad_config_default(fvad_vad_config* c)
 int fvad_vad_create(const fvad_vad_config* cfg, size_t sample_rate, size_t n_channels, size_t fft_size, fvad_vad** out)
 {
     if (!cfg || !out || n_channels == 0 || fft_size == 0 || sample_rate == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    // a zero-length channel_vol_ratio ring would divide by zero in the reference (RollingAverage.zig:36)
-    if ((size_t)(((float)sample_rate / (float)fft_size) * cfg->channel_vol_ratio_avg_sec) == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    fvad::VadMachineCfg k;
+    if (const int rc = fvad::vad_machine_cfg(*cfg, sample_rate, fft_size, &k)) return rc;
     *out = new (std::nothrow) fvad_vad(*cfg, sample_rate, n_channels, fft_size);
     return *out ? FVAD_OK : FVAD_ERR_ALLOC_FAILED;
 }
@@ -441,8 +316,8 @@ int fvad_vad_segments(const fvad_vad* v, fvad_speech_segment* out, size_t cap, s
 int fvad_vad_lazy_stats(const fvad_vad* v, uint64_t* exact_evaluations, uint64_t* lazy_pushes)
 {
     if (!v) return FVAD_ERR_INVALID_ARGUMENT;
-    if (exact_evaluations) *exact_evaluations = v->m.lt_exact_evals;
-    if (lazy_pushes) *lazy_pushes = v->m.lt_lazy_pushes;
+    if (exact_evaluations) *exact_evaluations = v->m.exact_evals;
+    if (lazy_pushes) *lazy_pushes = v->m.lazy_pushes;
     return FVAD_OK;
 }
 
@@ -490,7 +365,8 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
                           fvad_vad_batch** out)
 {
     if (!cfg || !out || n_channels == 0 || fft_size == 0 || sample_rate == 0 || n_streams == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    if ((size_t)(((float)sample_rate / (float)fft_size) * cfg->channel_vol_ratio_avg_sec) == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    fvad::VadMachineCfg k;
+    if (const int rc = fvad::vad_machine_cfg(*cfg, sample_rate, fft_size, &k)) return rc;
     auto* b = new (std::nothrow) fvad_vad_batch();
     if (!b) return FVAD_ERR_ALLOC_FAILED;
     b->cfgs.assign(1, *cfg); b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = fft_size; b->n_streams = n_streams;
@@ -507,8 +383,7 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
 }
 
 // The checks fvad_vad_create and fvad_pipeline_create make of a VADMachine.Config, with their status codes: the speech band's
-// edges as FFT.freqToBin sees them (FFT.zig:156-167, then the pipeline's max < min), the channel-ratio ring's length
-// (RollingAverage.zig:36)
+// edges as FFT.freqToBin sees them (FFT.zig:156-167, then the pipeline's max < min), the ring lengths (vad_machine_cfg)
 static int check_sweep_config(const fvad_vad_config& c, size_t sample_rate, size_t fft_size, int32_t* lo, int32_t* hi)
 {
     const float bin_width = (float)sample_rate / (float)fft_size;
@@ -518,8 +393,8 @@ static int check_sweep_config(const fvad_vad_config& c, size_t sample_rate, size
     *lo = (int32_t)roundf(c.speech_min_freq / bin_width);
     *hi = (int32_t)roundf(c.speech_max_freq / bin_width);
     if (*hi < *lo) return FVAD_ERR_INVALID_ARGUMENT;
-    if ((size_t)(((float)sample_rate / (float)fft_size) * c.channel_vol_ratio_avg_sec) == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    return FVAD_OK;
+    fvad::VadMachineCfg k;
+    return fvad::vad_machine_cfg(c, sample_rate, fft_size, &k);
 }
 
 int fvad_vad_batch_create_sweep(const fvad_vad_config* cfgs, size_t n_configs, size_t sample_rate, size_t n_channels, size_t fft_size,
@@ -610,17 +485,6 @@ void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t C, siz
                  nullptr);
 }
 
-// items 0 .. n - 1 dealt to up to n_threads host threads
-static void deal(size_t n, int n_threads, const std::function<void(size_t)>& fn)
-{
-    const int nt = (int)std::min<size_t>((size_t)std::max(n_threads, 1), n);
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
-    std::vector<std::thread> th;
-    std::atomic<size_t> next{0};
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= n) break; fn(i); } });
-    for (auto& t : th) t.join();
-}
 } // namespace fvad
 
 extern "C" {
@@ -651,8 +515,8 @@ int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_st
         }
         b->segs[s * NC + c] = m.segments; // (everything so far: a segment is appended when it closes)
         b->audits[s * NC + c] = m.audit;
-        b->exact_evals[s * NC + c] = m.lt_exact_evals;
-        b->lazy_pushes[s * NC + c] = m.lt_lazy_pushes;
+        b->exact_evals[s * NC + c] = m.exact_evals;
+        b->lazy_pushes[s * NC + c] = m.lazy_pushes;
     };
     auto stream_ratios = [&](size_t s, float* out, uint8_t* has) {
         fvad::frame_ratios([&](size_t c, size_t k) { return chunk_rms[(s * C + c) * rms_stride + k]; }, C, n_chunks, n_frames, first_frame,

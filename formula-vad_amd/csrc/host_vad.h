@@ -1,12 +1,13 @@
 // host_vad.h -- host-side VAD state machine (mirrors the reference's VADMachine / RollingAverage)
 #pragma once
-#include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <vector>
 
 #include "../../include/fvad.h"
+#include "vad_machine.h"
 
 namespace fvad {
 
@@ -40,40 +41,28 @@ struct Metadata {                  // VADMetadata.zig:11-60
 };
 MetaResult analyse_volume(const float* channel_rms, size_t n_channels);
 
-struct VadMachine {                // src/AudioPipeline/VADMachine.zig
-    enum State { CLOSED, OPENING, OPEN, CLOSING };
-    fvad_vad_config cfg;
-    size_t sample_rate, n_channels, fft_size;
-    State state = CLOSED;
+struct VadMachine : VadMachineState { // src/AudioPipeline/VADMachine.zig; the step itself is vad_machine.h's
+    VadMachineCfg cf;
+    size_t n_channels;
     RollingAverage long_term, short_term, ch_ratio;
-    uint64_t speech_start_index = 0, speech_end_index = 0;
-    float channel_vol_ratio_sum = 0;
-    size_t channel_vol_ratio_count = 0;
-    float vad_threshold_met_cumulative_sec = 0;
     std::vector<fvad_speech_segment> segments;
-    fvad_vad_audit audit;
-
-    // Lazily exact long-term average (see host_vad.cpp): between exact evaluations of the reference's
-    // 8437-term chain the machine carries an incrementally updated value and a rigorous bound on its
-    // distance from what the chain would give; the chain is run only when that bound cannot settle a
-    // comparison.  long_term.last_avg is current only while !lt_stale.
-    double lt_approx = 0, lt_err = 0, lt_abs = 0, lt_abs_anchor = 0;
-    bool lt_stale = false, lt_anchored = false;
+    // the long-term average is lazily exact (see host_vad.cpp): pushes on the full ring update the bound of vad_machine.h, and
+    // the chain over the ring's cached products runs only when that bound cannot settle a comparison
     bool lt_lazy = true; // FVAD_VAD_EAGER=1 in the environment: run the chain on every push (testing aid)
-    unsigned lt_updates = 0;
-    uint64_t lt_exact_evals = 0, lt_lazy_pushes = 0; // statistics
     void long_term_push(float mv);
     void long_term_exact();
 
     VadMachine(const fvad_vad_config& c, size_t sample_rate, size_t n_channels, size_t fft_size);
     fvad_vad_result run(uint64_t index, const float* channel_volumes, bool has_ratio, float ratio);
     float min_volume(const float* channel_volumes) const;
-    bool decide(double short_term_avg, double ratio_avg, double* threshold_out);
-    fvad_vad_result finish_step(uint64_t index, bool threshold_met, bool has_ratio, float ratio);
-    fvad_vad_result on_speech_end();
-    uint64_t offset_start(uint64_t vad_from) const;
-    uint64_t offset_end(uint64_t vad_to) const;
 };
+
+// what a machine derives from (c, sample_rate, fft_size) -- *out is filled either way; FVAD_ERR_INVALID_ARGUMENT when a ring
+// length is zero (channel ratio: RollingAverage.zig:36 would divide by zero) or does not fit in 32 bits
+int vad_machine_cfg(const fvad_vad_config& c, size_t sample_rate, size_t fft_size, VadMachineCfg* out);
+
+// items 0 .. n - 1 dealt to up to n_threads host threads
+void deal(size_t n, int n_threads, const std::function<void(size_t)>& fn);
 
 // ratio[s][k] is NaN where the frame carries no volume_ratio (null in the reference)
 void run_many(VadMachine* const* vads, size_t n_streams, const float* const* band,

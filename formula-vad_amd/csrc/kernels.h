@@ -210,24 +210,9 @@ void fvad_launch_irfft_batch(const float* bins, long n_frames, FftTables tb, flo
 int fvad_launch_irfft_generic(const float* bins, long n_frames, VadFftPlan pl, float* out, hipStream_t stream); // hipError_t as int
 
 // ------------------------------------------------------------------ VAD machines of a parameter sweep (kernels_vad.hip)
-// per config: what host_vad.cpp's VadMachine derives from its VADMachine.Config, evaluated on the host with the host's expressions
-struct VadMachineCfg {
-    double lt_scalar, st_scalar, cr_scalar; // 1 / ring length (RollingAverage.zig:45-56 once full)
-    double lt_q_init;        // fl(initial_long_term_avg * lt_scalar): the term of a slot still holding the initial value
-    double initial;          // initial_long_term_avg
-    double factor;           // (double)speech_threshold_factor
-    double ratio_threshold;  // (double)channel_vol_ratio_threshold
-    double gamma;            // n u / (1 - n u), n = long_len (host_vad.cpp decide)
-    uint64_t min_open, max_gap, start_buffer, end_buffer; // VADMachine.zig:161,163,312-325 in samples
-    float input_len_sec, sample_rate_f, min_vad_duration_sec;
-    uint32_t long_len, short_len, ratio_len;
-    int32_t has_init;
-    uint32_t band;           // band block of d_band this config reads
-};
-struct VadSegmentDev { uint64_t sample_from, sample_to; float avg_channel_vol_ratio, vad_met_sec; }; // = fvad_speech_segment
-struct VadAuditDev { double min_rel_threshold_margin, min_abs_ratio_margin; uint64_t n_frames; };    // = fvad_vad_audit
+namespace fvad { struct VadMachineCfg; } // vad_machine.h
 struct VadMachinesArgs {
-    const VadMachineCfg* cfgs; // [n_configs] (device)
+    const fvad::VadMachineCfg* cfgs; // [n_configs] (device), with their bands
     int n_configs, n_channels;
     long n_streams;
     int by_config;             // lane mapping: 0 = a stream's configs side by side, 1 = a config's streams side by side
@@ -242,10 +227,10 @@ struct VadMachinesArgs {
     float* lt_rings;           // [(max long_len rounded up to 64) / 4 + 16][n_machines][4]
     float* rings;              // [st_max + cr_max][n_machines] when !rings_in_lds
     int rings_in_lds, st_max, cr_max;
-    VadSegmentDev* segs;       // [n_machines][seg_cap]
+    fvad_speech_segment* segs; // [n_machines][seg_cap]
     uint32_t seg_cap;
     uint32_t* seg_count;       // [n_machines]: segments the machine closed (may exceed seg_cap: then only seg_cap were written)
-    VadAuditDev* audits;       // [n_machines]
+    fvad_vad_audit* audits;    // [n_machines]
     unsigned long long* stats; // [n_machines][2]: exact evaluations of the long-term chain, lazy pushes
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
@@ -253,7 +238,7 @@ int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // h
 // ------------------------------------------------------------------ scoring the machines of a VAD batch (kernels_eval.hip)
 // one lane per machine, machine = stream * n_configs + config: the Evaluator statistics of its segments (eval_walk.h)
 struct VadScoreArgs {
-    const VadSegmentDev* segs;            // [n_machines][seg_cap], as fvad_launch_vad_machines wrote them
+    const fvad_speech_segment* segs;      // [n_machines][seg_cap], as fvad_launch_vad_machines wrote them
     const uint32_t* seg_count;            // [n_machines] (counts above seg_cap are read as seg_cap)
     uint32_t seg_cap;
     long n_machines;

@@ -17,7 +17,7 @@ __global__ __launch_bounds__(64) void vad_score_kernel(VadScoreArgs a)
     const long s = m / a.n_configs;
     const int c = (int)(m - s * a.n_configs);
     const uint32_t n = a.seg_count[m] < a.seg_cap ? a.seg_count[m] : a.seg_cap;
-    const VadSegmentDev* seg = a.segs + m * (long)a.seg_cap;
+    const fvad_speech_segment* seg = a.segs + m * (long)a.seg_cap;
     const float sr = a.sample_rate_f;
     auto vad = [&](uint32_t i) {
         fvad_segment_sec r;

@@ -1,10 +1,9 @@
 // kernels_vad.hip -- the VAD state machines of a parameter sweep on the GPU: one lane per (stream, config) machine.
 //
-// A port of host_vad.cpp's VadMachine::run (VADMachine.zig:138-239) that gives the same bits: f64 rolling averages summed in
-// index order (RollingAverage.zig:45-56), the lazily exact long-term average with host_vad.cpp's error bound and its exact
-// re-evaluations, the four-state machine, the segment statistics and the margin audit, every operation in the host's order
-// (the library is built with -ffp-contract=off: no fused multiply-adds; f32 division and u64 -> f32 conversion are correctly
-// rounded on both sides).  What only depends on the stream -- the volume ratio of each frame -- comes from the host.
+// host_vad.cpp's VadMachine::run (VADMachine.zig:138-239) with the same bits: f64 rolling averages summed in index order
+// (RollingAverage.zig:45-56) and the long-term chain in the host's order, around the step both share (vad_machine.h: the lazily
+// exact long-term bound, the four-state machine, the segment statistics and the margin audit).  The library is built with
+// -ffp-contract=off.  What only depends on the stream -- the volume ratio of each frame -- comes from the host.
 //
 // Storage per machine.  Pushed samples are f32, so every ring holds f32 and the f64 term fl(data[i] * scalar) is recomputed
 // inside the chain with the bits the host's cached product has (data[i] = (double)sample there).  The long-term ring also
@@ -26,10 +25,11 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "vad_machine.h"
 
 namespace {
 
-constexpr double kU = 1.1102230246251565e-16; // 2^-53, as host_vad.cpp
+using fvad::VadMachineCfg;
 
 template <class P> // float* (global) or an LDS float pointer: the address space is known, so LDS slots are ds_read / ds_write
 struct Ring { // a rolling average without initial value (RollingAverage.zig:11-56) over f32 slots base[i * stride]
@@ -65,27 +65,16 @@ struct Ring { // a rolling average without initial value (RollingAverage.zig:11-
 };
 
 template <class P>
-struct Machine {
+struct Machine : fvad::VadMachineState { // the step (decide, finish_step) and the long-term bound are vad_machine.h's
     VadMachineCfg cf; // in registers: read through a pointer, every field would be loaded again after each ring store (may alias)
-    // long-term ring and its lazily exact average (host_vad.cpp: long_term_push, long_term_exact, decide).  Slot i of this
-    // machine at lt[(i / 4) * lt_stride + i % 4]: four consecutive slots are one 16-byte load of the lane.
+    // long-term ring (host_vad.cpp: long_term_push, long_term_exact).  Slot i of this machine at lt[(i / 4) * lt_stride + i % 4]:
+    // four consecutive slots are one 16-byte load of the lane.
     float* lt;
     long lt_stride;
     float lt_next = 0; // slot lt_w, loaded one push ahead (the next lazy push overwrites it and needs its old value at once)
-    uint32_t lt_w = 0, lt_wc = 0, lt_filled = 0, lt_updates = 0;
-    bool lt_steady = false, lt_has_last = false, lt_stale = false, lt_anchored = false;
-    double lt_last = 0, lt_approx = 0, lt_err = 0, lt_abs = 0, lt_abs_anchor = 0;
-    uint64_t exact_evals = 0, lazy_pushes = 0;
+    uint32_t lt_w = 0, lt_wc = 0, lt_filled = 0;
+    bool lt_steady = false;
     Ring<P> st, cr;
-    // VADMachine state
-    int state = 0; // CLOSED, OPENING, OPEN, CLOSING
-    uint64_t speech_start = 0, speech_end = 0;
-    float ratio_sum = 0;
-    uint64_t ratio_count = 0;
-    float met_cum = 0;
-    double a_rel = __builtin_inf(), a_abs = __builtin_inf();
-    uint64_t a_frames = 0;
-    uint32_t n_segs = 0;
 
     __device__ float& slot(uint32_t i) const { return lt[(long)(i >> 2) * lt_stride + (i & 3)]; }
     __device__ double lt_q(uint32_t i, float x) const { return i < lt_filled ? (double)x * cf.lt_scalar : cf.lt_q_init; }
@@ -99,7 +88,7 @@ struct Machine {
 #pragma unroll
         for (int g = 0; g < kLtBlock / 4; ++g) x[g] = *reinterpret_cast<const float4*>(lt + (long)((i0 >> 2) + g) * lt_stride);
     }
-    __device__ void lt_exact()
+    __device__ __forceinline__ void lt_exact() // (inlined at each call: a call would put the machine on the stack)
     {
         double acc = 0.0, abs_sum = 0.0;
         const uint32_t n = cf.long_len;
@@ -119,16 +108,7 @@ struct Machine {
 #pragma unroll
             for (int g = 0; g < kLtBlock / 4; ++g) cur[g] = nxt[g];
         }
-        lt_last = acc;
-        lt_has_last = true;
-        lt_approx = acc;
-        lt_abs = abs_sum;
-        lt_abs_anchor = abs_sum;
-        lt_anchored = true;
-        lt_err = 0.0;
-        lt_stale = false;
-        lt_updates = 0;
-        ++exact_evals;
+        anchor(acc, abs_sum);
     }
 
     __device__ void lt_push(float mv)
@@ -144,7 +124,7 @@ struct Machine {
 #pragma unroll 8
             for (uint32_t i = 0; i < lt_wc; ++i) acc += (double)slot(i) * sc;
             lt_last = acc;
-            lt_has_last = true;
+            has_last = true;
             if (lt_wc == len) { lt_steady = true; lt_next = slot(0); lt_exact(); }
             return;
         }
@@ -155,105 +135,7 @@ struct Machine {
         if (lt_filled < len) lt_filled += 1; // (only with an initial value: slot w == lt_filled is the one written now)
         lt_w = (w + 1 == len) ? 0 : w + 1;
         lt_next = slot(lt_w); // (w + 1 == len == 1: the slot just written, read back after the store)
-        const double s1 = lt_approx + qn, s2 = s1 - qo;
-        lt_err += 2.0 * kU * (fabs(s1) + fabs(s2));
-        lt_abs += fabs(qn) - fabs(qo);
-        lt_approx = s2;
-        lt_stale = true;
-        lt_has_last = true;
-        ++lazy_pushes;
-        if (++lt_updates >= 4096) lt_exact();
-    }
-
-    __device__ bool decide(double st_avg, double cr_avg)
-    {
-        const double f = cf.factor;
-        const double thr_r = cf.ratio_threshold;
-        if (lt_steady && lt_stale) {
-            const double gamma = cf.gamma;
-            const double abs_now = fabs(lt_abs) * (1.0 + 1e-9) + 8192.0 * 2.0 * kU * (fabs(lt_abs) + lt_abs_anchor);
-            const double delta = lt_err + 2.0 * gamma * (abs_now + lt_abs_anchor);
-            double t0 = (lt_approx - delta) * f, t1 = (lt_approx + delta) * f;
-            if (t0 > t1) { const double t = t0; t0 = t1; t1 = t; }
-            const double lo = t0 - fabs(t0) * 4.0 * kU - 1e-300, hi = t1 + fabs(t1) * 4.0 * kU + 1e-300;
-            const bool sure_true = st_avg > hi, sure_false = st_avg <= lo;
-            bool need_exact = !(sure_true || sure_false);
-            if (!need_exact && hi > 0) {
-                const double gap = sure_true ? st_avg - hi : lo - st_avg;
-                const double m_lb = gap / (sure_true ? hi : (lo < hi ? hi : lo));
-                if (!(m_lb * (1.0 - 1e-9) > a_rel)) need_exact = true;
-            }
-            if (!need_exact) {
-                const double rm = fabs(cr_avg - thr_r);
-                if (rm < a_abs) a_abs = rm;
-                a_frames++;
-                return sure_true && cr_avg > thr_r;
-            }
-            lt_exact();
-        }
-        double base;
-        if (lt_has_last) base = lt_last;
-        else if (cf.has_init) base = cf.initial;
-        else base = st_avg;
-        const double threshold = base * f;
-        const bool met = st_avg > threshold && cr_avg > thr_r;
-        if (threshold > 0) {
-            const double m = fabs(st_avg - threshold) / threshold;
-            if (m < a_rel) a_rel = m;
-        }
-        const double rm = fabs(cr_avg - thr_r);
-        if (rm < a_abs) a_abs = rm;
-        a_frames++;
-        return met;
-    }
-
-    __device__ void speech_end_event(VadSegmentDev* seg, uint32_t cap)
-    {
-        const uint64_t length_samples = speech_end - speech_start;
-        const float length_sec = (float)length_samples / cf.sample_rate_f;
-        const float avg_ratio = ratio_sum / (float)ratio_count;
-        if (length_sec >= cf.min_vad_duration_sec) {
-            if (n_segs < cap) {
-                VadSegmentDev s;
-                s.sample_from = speech_start - (cf.start_buffer < speech_start ? cf.start_buffer : speech_start);
-                s.sample_to = speech_end + cf.end_buffer;
-                s.avg_channel_vol_ratio = avg_ratio;
-                s.vad_met_sec = met_cum;
-                seg[n_segs] = s;
-            }
-            ++n_segs; // counted past the capacity: the caller sees the overflow and runs again with room for all
-        }
-    }
-
-    __device__ void finish_step(uint64_t index, bool met, bool has_ratio, float ratio, VadSegmentDev* seg, uint32_t cap)
-    {
-        const int from_state = state;
-        switch (state) {
-        case 0:
-            if (met) { state = 1; speech_start = index; }
-            break;
-        case 1:
-            if (met && index - speech_start >= cf.min_open) state = 2;
-            else if (!met) state = 0;
-            break;
-        case 2:
-            if (!met) { state = 3; speech_end = index; }
-            break;
-        default:
-            if (met) state = 2;
-            else if (index - speech_end >= cf.max_gap) { state = 0; speech_end_event(seg, cap); }
-            break;
-        }
-        const float r = has_ratio ? ratio : 0;
-        if (from_state == 0 && state == 1) {
-            ratio_sum = r;
-            ratio_count = 1;
-            met_cum = cf.input_len_sec;
-        } else if (from_state == 2) {
-            ratio_sum += r;
-            ratio_count += 1;
-            if (met) met_cum += cf.input_len_sec;
-        }
+        if (lazy_update(qn, qo)) lt_exact();
     }
 };
 
@@ -293,7 +175,7 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         double acc = 0.0;
         for (uint32_t i = 0; i < cfg->long_len; ++i) acc += cfg->lt_q_init;
         mc.lt_last = acc;
-        mc.lt_has_last = true;
+        mc.has_last = true;
         mc.lt_steady = true;
         mc.lt_wc = cfg->long_len;
         mc.lt_next = mc.slot(0);
@@ -303,7 +185,8 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     const int C = a.n_channels;
     const float* band = a.band + ((long)cfg->band * a.n_lanes + s * C) * a.band_stride;
     const float* ratio = a.ratio + s * a.ratio_stride;
-    VadSegmentDev* seg = a.segs + id * (long)a.seg_cap;
+    fvad_speech_segment* seg = a.segs + id * (long)a.seg_cap;
+    uint32_t n_segs = 0;
     // the next frame's band values (up to kPre channels) and ratio are loaded while this frame runs; the minimum is taken when the
     // frame is run, so that the loads are waited for a frame later (more channels: loaded and reduced at once)
     constexpr int kPre = 4;
@@ -331,16 +214,15 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         // NaN ratio (from NaN audio) goes into the ring as it is, as on the host
         const double st = mc.st.push(mv);
         const double cr = mc.cr.push(rt);
-        const bool met = mc.decide(st, cr);
+        const bool met = mc.decide(mc.cf, st, cr, [&] { mc.lt_exact(); });
         if (!met) mc.lt_push(mv);
-        mc.finish_step((uint64_t)k * a.fft_size, met, true, rt, seg, a.seg_cap);
+        mc.finish_step(mc.cf, (uint64_t)k * a.fft_size, met, true, rt, [&](const fvad_speech_segment& sg) {
+            if (n_segs < a.seg_cap) seg[n_segs] = sg;
+            ++n_segs; // counted past the capacity: the caller sees the overflow and runs again with room for all
+        });
     }
-    a.seg_count[id] = mc.n_segs;
-    VadAuditDev au;
-    au.min_rel_threshold_margin = mc.a_rel;
-    au.min_abs_ratio_margin = mc.a_abs;
-    au.n_frames = mc.a_frames;
-    a.audits[id] = au;
+    a.seg_count[id] = n_segs;
+    a.audits[id] = mc.audit;
     a.stats[2 * id] = mc.exact_evals;
     a.stats[2 * id + 1] = mc.lazy_pushes;
 }

@@ -440,15 +440,17 @@ int fvad_pipeline_create(fvad_ctx* ctx, const fvad_pipeline_config* cfg, const f
         if (rc) { for (auto* t : p->states) fvad_lane_state_destroy(t); return rc; }
         p->states.push_back(s);
     }
-    // a zero-length channel_vol_ratio ring would divide by zero (RollingAverage.zig:36; same check as fvad_vad_create)
-    auto ratio_ring_ok = [&](const fvad_vad_config& vc) {
-        return (size_t)(((float)cfg->sample_rate / (float)cfg->fft_size) * vc.channel_vol_ratio_avg_sec) != 0;
+    // the machines' ring lengths, checked as fvad_vad_create checks them (a zero-length channel_vol_ratio ring would divide by
+    // zero, RollingAverage.zig:36)
+    auto rings_ok = [&](const fvad_vad_config& vc) {
+        VadMachineCfg k;
+        return vad_machine_cfg(vc, cfg->sample_rate, cfg->fft_size, &k) == FVAD_OK;
     };
-    bool rings_ok = ratio_ring_ok(cfg->vad_machine_config);
-    for (size_t i = 0; i < cfg->n_alt_vad_machine_configs; ++i) rings_ok = rings_ok && ratio_ring_ok(cfg->alt_vad_machine_configs[i]);
-    if (!rings_ok) {
+    bool ok = rings_ok(cfg->vad_machine_config);
+    for (size_t i = 0; i < cfg->n_alt_vad_machine_configs; ++i) ok = ok && rings_ok(cfg->alt_vad_machine_configs[i]);
+    if (!ok) {
         for (auto* t : p->states) fvad_lane_state_destroy(t);
-        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "channel_vol_ratio_avg_sec is shorter than one FFT frame");
+        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a VAD machine ring is shorter than one FFT frame or too long");
     }
     p->vad.reset(new VadMachine(cfg->vad_machine_config, cfg->sample_rate, cfg->n_channels, cfg->fft_size));
     for (size_t i = 0; i < cfg->n_alt_vad_machine_configs; ++i)
@@ -595,8 +597,8 @@ int fvad_pipeline_push_samples(fvad_pipeline* p, const float* const* channel_pcm
         // = speech start - 2 s (VADMachine.zig:309-315); the earliest speech start still to come is the one of
         // an opening in progress, else the next frame
         const uint64_t next_index = p->frames_done * (uint64_t)p->cfg.fft_size;
-        uint64_t earliest = p->vad->state != VadMachine::CLOSED ? std::min(next_index, p->vad->speech_start_index) : next_index;
-        uint64_t keep_from = p->vad->offset_start(earliest);
+        uint64_t earliest = p->vad->state != VadMachine::CLOSED ? std::min(next_index, p->vad->speech_start) : next_index;
+        uint64_t keep_from = offset_start(p->vad->cf, earliest);
         for (const auto& r : p->rec) if (r.recording) keep_from = std::min(keep_from, r.start);
         if (keep_from > p->hist_base) {
             const size_t drop = (size_t)(keep_from - p->hist_base);
