@@ -315,6 +315,11 @@ pub extern "c" fn fvad_vad_batch_config_segments(b: *const VadBatch, config: usi
 pub extern "c" fn fvad_vad_batch_config_audit(b: *const VadBatch, stream: usize, config: usize, out: *VadAudit) c_int;
 pub extern "c" fn fvad_vad_batch_lazy_stats(b: *const VadBatch, stream: usize, config: usize, exact_evaluations: ?*u64, lazy_pushes: ?*u64) c_int;
 pub extern "c" fn fvad_vad_batch_run_device(ctx: *Ctx, b: *VadBatch, d_band: [*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: [*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize) c_int;
+/// the same in parts: the machines' state stays in device memory between the parts; a batch holding part state is destroyed
+/// before its context (see fvad.h)
+pub extern "c" fn fvad_vad_batch_run_device_part(ctx: *Ctx, b: *VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_frame: u64) c_int;
+pub extern "c" fn fvad_vad_batch_score_device(ctx: *Ctx, b: *VadBatch) c_int;
+pub extern "c" fn fvad_vad_batch_device_bytes(b: *const VadBatch) usize;
 pub extern "c" fn fvad_ra_create(count: usize, has_initial: c_int, initial_val: f64, out: *?*RollingAverage) c_int;
 pub extern "c" fn fvad_ra_destroy(ra: ?*RollingAverage) void;
 pub extern "c" fn fvad_ra_push(ra: *RollingAverage, sample: f32) f64;

@@ -22,6 +22,7 @@ FVAD_ERR_INVALID_ARGUMENT = -100
 FVAD_ERR_OUT_OF_RANGE = -6
 FVAD_ERR_NEGATIVE_FREQUENCY = -7
 FVAD_ERR_BUFFER_TOO_SMALL = -106
+FVAD_ERR_MODEL_FORMAT = -104
 
 
 class FvadError(RuntimeError):
@@ -235,6 +236,9 @@ SIGNATURES = {
     "fvad_vad_batch_config_audit": (C.c_int, [vp, sz, sz, C.POINTER(VadAudit)]),
     "fvad_vad_batch_lazy_stats": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fvad_vad_batch_run_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz]),
+    "fvad_vad_batch_run_device_part": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
+    "fvad_vad_batch_score_device": (C.c_int, [vp, vp]),
+    "fvad_vad_batch_device_bytes": (sz, [vp]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
     "fvad_ra_push": (C.c_double, [vp, C.c_float]),
@@ -930,6 +934,27 @@ class VadSweep:
         ctx._ck(lib().fvad_vad_batch_run_device(ctx.h, self.h, vp(d_band), band_stride, nf, fptr(chunk_rms), chunk_rms.shape[1], nc,
                                                 chunk_size), "fvad_vad_batch_run_device")
 
+    def run_device_part(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_frame, chunk_size=24000):
+        """fvad_vad_batch_run_device_part: frames [first_frame, first_frame + n_frames[s]) of every stream, the machines' state
+        kept in device memory between the parts; d_band / chunk_rms hold the part's frames / chunks as run_device takes them.
+        first_frame = 0 starts fresh machines.  After each part, segments (keep_segments on), audits and lazy statistics cover
+        everything run so far."""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf = (sz * self.n_streams)(*[int(x) for x in n_frames])
+        nc = (sz * self.n_streams)(*[int(x) for x in n_chunks])
+        ctx._ck(lib().fvad_vad_batch_run_device_part(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf, fptr(chunk_rms),
+                                                     chunk_rms.shape[1], nc, chunk_size, int(first_frame)),
+                "fvad_vad_batch_run_device_part")
+
+    def score_device(self, ctx):
+        """fvad_vad_batch_score_device: score the segments the device parts left on the device (keep_segments off); read the
+        statistics with config_stats"""
+        ctx._ck(lib().fvad_vad_batch_score_device(ctx.h, self.h), "fvad_vad_batch_score_device")
+
+    def device_bytes(self):
+        """fvad_vad_batch_device_bytes: device memory the batch holds between device parts (0 when it holds none)"""
+        return lib().fvad_vad_batch_device_bytes(self.h)
+
     def segments(self, config):
         """config's segments per stream: [[(from, to, avg_ratio, vad_met_sec)]]"""
         offs = (sz * (self.n_streams + 1))()
@@ -1048,6 +1073,53 @@ def wav_read_i16(path):
     finally:
         lib().fvad_wav_free_i16(pp, nch.value)
     return out, sr.value
+
+
+def wav_map(path):
+    """A WAV file's samples without reading them: (samples, sample_rate), samples a read-only numpy memmap of the data chunk,
+    [n_frames][n_channels] int16 (PCM16) or float32 (IEEE float), interleaved as in the file.  The RIFF chunks are walked as
+    fvad_wav_read walks them (the first "fmt " and "data" chunks; WAVE_FORMAT_EXTENSIBLE takes its sub-format; a data length
+    past the end of the file is cut to the file); whatever fvad_wav_read refuses raises FvadError."""
+    import struct
+    def bad(why):
+        return FvadError(FVAD_ERR_MODEL_FORMAT, f"wav_map({path})", why)
+
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise bad("not a RIFF/WAVE file")
+        tag = channels = bits = rate = 0
+        data_off = data_bytes = None
+        pos = 12
+        while pos + 8 <= size:
+            f.seek(pos)
+            ck = f.read(8)
+            length = struct.unpack("<I", ck[4:8])[0]
+            body = pos + 8
+            if ck[:4] == b"fmt " and length >= 16 and body + 16 <= size:
+                fmt = f.read(min(length, 26))
+                tag, channels, rate = struct.unpack("<HHI", fmt[:8])
+                bits = struct.unpack("<H", fmt[14:16])[0]
+                if tag == 0xFFFE and length >= 26 and body + 26 <= size:
+                    tag = struct.unpack("<H", fmt[24:26])[0]
+            elif ck[:4] == b"data":
+                data_off = body
+                data_bytes = length if body + length <= size else size - body
+                break
+            pos = body + length + (length & 1)
+    if data_off is None or channels <= 0 or rate == 0:
+        raise bad("no data chunk or no format")
+    if tag == 1 and bits == 16:
+        dtype = np.dtype("<i2")
+    elif tag == 3 and bits == 32:
+        dtype = np.dtype("<f4")
+    else:
+        raise bad(f"format tag {tag} with {bits} bits (PCM16 or 32-bit float only)")
+    frames = data_bytes // (channels * dtype.itemsize)
+    if frames == 0:
+        return np.zeros((0, channels), dtype), rate
+    return np.memmap(path, dtype=dtype, mode="r", offset=data_off, shape=(frames, channels)), rate
 
 
 def parse_audacity(text):

@@ -1,8 +1,11 @@
 // engine_sweep.cpp -- parameter sweeps on the GPU: several speech bands per K4 pass (fvad_engine_band_sums_device) and every
 // (stream, config) VAD machine of a sweep batch at once (fvad_vad_batch_run_device, kernels_vad.hip), scored against the
-// streams' labels on the device when the batch has them (kernels_eval.hip).
+// streams' labels on the device when the batch has them (kernels_eval.hip); the same machines in parts, their state kept in
+// device memory between the parts (fvad_vad_batch_run_device_part, fvad_vad_batch_score_device).
 #include <algorithm>
 #include <cmath>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "host_vad.h"
@@ -35,6 +38,96 @@ struct DevScratch {
         return e;
     }
 };
+
+// The device state of a batch run in parts (fvad_vad_batch_run_device_part), held by the batch between the parts: the machines
+// (kernels_vad.hip's resume form: VadLaneState, the long-term rings, the short-term and channel-ratio rings), their outputs and
+// the segment buffer.  Freed with the batch (fvad_vad_batch_destroy) or when a run starts afresh.
+struct DevParts {
+    int device = 0;
+    const fvad_ctx* ctx = nullptr; // the context of the parts (every part runs on it)
+    std::vector<void*> ptrs;       // every allocation but the segment buffer
+    size_t bytes = 0;              // their size
+    VadMachineCfg* cfg = nullptr;
+    float* lt = nullptr;
+    float* rings = nullptr;
+    VadLaneState* state = nullptr;
+    uint32_t* count = nullptr;
+    fvad_vad_audit* audit = nullptr;
+    unsigned long long* stats = nullptr;
+    unsigned* paused = nullptr;
+    fvad_speech_segment* segs = nullptr; // [machine][seg_cap]
+    size_t seg_cap = 0;
+    bool rings_in_lds = false;
+    int by_config = 0;                   // the lane map of the first part (the rings are laid out by it)
+    uint32_t st_max = 1, cr_max = 1;
+    uint64_t next_frame = 0;             // where the next part starts
+    std::vector<uint8_t> ended;          // streams that got fewer frames than a part's longest
+    std::vector<uint32_t> count_h;       // every machine's segment count after the last part
+    bool segs_on_device = true;          // every part so far left its segments on the device: they are all in segs
+    ~DevParts()
+    {
+        hipSetDevice(device);
+        for (void* p : ptrs) hipFree(p);
+        hipFree(segs);
+    }
+    template <class T> hipError_t alloc(T** p, size_t n)
+    {
+        *p = nullptr;
+        const size_t nb = std::max<size_t>(n, 1) * sizeof(T);
+        const hipError_t e = hipMalloc((void**)p, nb);
+        if (e == hipSuccess) { ptrs.push_back(*p); bytes += nb; }
+        return e;
+    }
+};
+void free_dev_parts(void* p) { delete static_cast<DevParts*>(p); }
+
+// every machine of b against its stream's labels on the device (kernels_eval.hip): segment i of machine m at d_segs[m * cap + i],
+// d_count[m] of them (at most cap); the scores come back into *out
+int score_on_device(fvad_ctx* ctx, const fvad_vad_batch* b, const fvad_speech_segment* d_segs, const uint32_t* d_count, size_t cap,
+                    std::vector<fvad_single_stats>* out)
+{
+    const size_t S = b->n_streams, NC = b->cfgs.size(), M = S * NC;
+    hipStream_t st = ctx->stream;
+    DevScratch scratch;
+    const size_t n_ref = b->ref_off[S];
+    fvad_segment_sec* d_refs = nullptr;
+    float* d_pmax = nullptr;
+    unsigned long long* d_roff = nullptr;
+    fvad_stat_config* d_scfg = nullptr;
+    fvad_single_stats* d_scores = nullptr;
+    const std::vector<unsigned long long> roff(b->ref_off.begin(), b->ref_off.end());
+    FVAD_HIP(ctx, scratch.alloc(&d_refs, n_ref));
+    FVAD_HIP(ctx, scratch.alloc(&d_pmax, n_ref));
+    FVAD_HIP(ctx, scratch.alloc(&d_roff, S + 1));
+    FVAD_HIP(ctx, scratch.alloc(&d_scfg, NC));
+    FVAD_HIP(ctx, scratch.alloc(&d_scores, M));
+    if (n_ref) {
+        FVAD_HIP(ctx, hipMemcpyAsync(d_refs, b->refs.data(), n_ref * sizeof(fvad_segment_sec), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_pmax, b->ref_pmax.data(), n_ref * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    FVAD_HIP(ctx, hipMemcpyAsync(d_roff, roff.data(), (S + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_scfg, b->stat_cfgs.data(), NC * sizeof(fvad_stat_config), hipMemcpyHostToDevice, st));
+    VadScoreArgs sa{};
+    sa.segs = d_segs;
+    sa.seg_count = d_count;
+    sa.seg_cap = (uint32_t)cap;
+    sa.n_machines = (long)M;
+    sa.n_configs = (int)NC;
+    sa.sample_rate_f = (float)b->sample_rate;
+    sa.refs = d_refs;
+    sa.ref_pmax = d_pmax;
+    sa.ref_off = d_roff;
+    sa.stat_cfgs = d_scfg;
+    sa.out = d_scores;
+    time_begin(ctx, "vad_score");
+    const int e = fvad_launch_vad_score(sa, st);
+    time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_score");
+    out->resize(M);
+    FVAD_HIP(ctx, hipMemcpyAsync(out->data(), d_scores, M * sizeof(fvad_single_stats), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipStreamSynchronize(st)); // (before the scratch is freed)
+    return FVAD_OK;
+}
 
 } // namespace
 
@@ -110,6 +203,7 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     if (band_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
+    b->dev_parts.reset(); // a run in parts cannot go on after this one
 
     // ---- host: the frame ratios (one per stream: they do not depend on the config) and the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
@@ -207,42 +301,8 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     // ---- scoring (kernels_eval.hip): every machine against its stream's labels, on the segments of the final launch
     std::vector<fvad_single_stats> scores;
     if (b->has_refs) {
-        const size_t n_ref = b->ref_off[S];
-        fvad_segment_sec* d_refs = nullptr;
-        float* d_pmax = nullptr;
-        unsigned long long* d_roff = nullptr;
-        fvad_stat_config* d_scfg = nullptr;
-        fvad_single_stats* d_scores = nullptr;
-        const std::vector<unsigned long long> roff(b->ref_off.begin(), b->ref_off.end());
-        FVAD_HIP(ctx, scratch.alloc(&d_refs, n_ref));
-        FVAD_HIP(ctx, scratch.alloc(&d_pmax, n_ref));
-        FVAD_HIP(ctx, scratch.alloc(&d_roff, S + 1));
-        FVAD_HIP(ctx, scratch.alloc(&d_scfg, NC));
-        FVAD_HIP(ctx, scratch.alloc(&d_scores, (size_t)M));
-        if (n_ref) {
-            FVAD_HIP(ctx, hipMemcpyAsync(d_refs, b->refs.data(), n_ref * sizeof(fvad_segment_sec), hipMemcpyHostToDevice, st));
-            FVAD_HIP(ctx, hipMemcpyAsync(d_pmax, b->ref_pmax.data(), n_ref * sizeof(float), hipMemcpyHostToDevice, st));
-        }
-        FVAD_HIP(ctx, hipMemcpyAsync(d_roff, roff.data(), (S + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        FVAD_HIP(ctx, hipMemcpyAsync(d_scfg, b->stat_cfgs.data(), NC * sizeof(fvad_stat_config), hipMemcpyHostToDevice, st));
-        VadScoreArgs sa{};
-        sa.segs = d_segs;
-        sa.seg_count = d_count;
-        sa.seg_cap = (uint32_t)cap;
-        sa.n_machines = M;
-        sa.n_configs = (int)NC;
-        sa.sample_rate_f = (float)b->sample_rate;
-        sa.refs = d_refs;
-        sa.ref_pmax = d_pmax;
-        sa.ref_off = d_roff;
-        sa.stat_cfgs = d_scfg;
-        sa.out = d_scores;
-        time_begin(ctx, "vad_score");
-        const int e = fvad_launch_vad_score(sa, st);
-        time_end(ctx);
-        if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_score");
-        scores.resize((size_t)M);
-        FVAD_HIP(ctx, hipMemcpyAsync(scores.data(), d_scores, (size_t)M * sizeof(fvad_single_stats), hipMemcpyDeviceToHost, st));
+        const int rc = score_on_device(ctx, b, d_segs, d_count, cap, &scores);
+        if (rc) return rc;
     }
     // the segments only when the caller keeps them (fvad_vad_batch_set_keep_segments)
     std::vector<fvad_speech_segment> segs(b->keep_segments ? cap * (size_t)M : 0);
@@ -271,6 +331,236 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     if (b->has_refs) b->scores = std::move(scores);
     b->machines.clear(); // nothing to continue from: a later fvad_vad_batch_run_part must start at frame 0
     b->next_frame = 0;
+    return FVAD_OK;
+}
+
+size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)
+{
+    const DevParts* dp = b ? static_cast<const DevParts*>(b->dev_parts.get()) : nullptr;
+    if (!dp) return 0;
+    return dp->bytes + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
+}
+
+int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                   const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                                   uint64_t first_frame)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, F = b->fft_size;
+    const size_t M = S * NC;
+    size_t P = 0; // the part's longest stream: a stream with fewer frames has ended
+    for (size_t s = 0; s < S; ++s) {
+        if (n_frames[s] * F > n_chunks[s] * chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a frame without its chunk's ratio");
+        P = std::max(P, n_frames[s]);
+    }
+    if (P && (!d_band || !chunk_rms)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (band_stride < P) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
+    if ((first_frame * F) % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
+    DevParts* dp = static_cast<DevParts*>(b->dev_parts.get());
+    if (first_frame != 0) {
+        if (!dp) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no device part to continue (a host run or a one-shot device run came between)");
+        if (dp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the parts of a run are on one context");
+        if (first_frame != dp->next_frame) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts where the previous one ended");
+        for (size_t s = 0; s < S; ++s)
+            if (dp->ended[s] && (n_frames[s] || n_chunks[s])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "frames for a stream that has ended");
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+
+    // ---- host: the part's frame ratios and, for a fresh run, the configs' derived constants
+    const size_t ratio_stride = std::max<size_t>(P, 1);
+    std::vector<float> ratio(S * ratio_stride, 0.0f);
+    deal(S, 16, [&](size_t s) {
+        sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[s], F, chunk_size, ratio.data() + s * ratio_stride,
+                           first_frame);
+    });
+    if (first_frame == 0) { // fresh machines: the state of an earlier run is dropped
+        b->dev_parts.reset();
+        std::vector<VadMachineCfg> hc(NC);
+        uint32_t lt_max = 1, st_max = 1, cr_max = 1;
+        for (size_t c = 0; c < NC; ++c) {
+            if (vad_machine_cfg(b->cfgs[c], b->sample_rate, F, &hc[c])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
+            hc[c].band = b->band_of[c];
+            lt_max = std::max(lt_max, hc[c].long_len);
+            st_max = std::max(st_max, hc[c].short_len);
+            cr_max = std::max(cr_max, hc[c].ratio_len);
+        }
+        std::unique_ptr<DevParts> fresh(new (std::nothrow) DevParts());
+        if (!fresh) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
+        dp = fresh.get();
+        dp->device = ctx->device;
+        dp->ctx = ctx;
+        dp->st_max = st_max;
+        dp->cr_max = cr_max;
+        dp->by_config = ctx->tune.vad_lane_map;
+        // as fvad_vad_batch_run_device: the long-term rings in whole blocks of 64 slots plus one; the short-term and
+        // channel-ratio rings in LDS when a workgroup's fit in 48 KB (their home between launches is `rings` either way)
+        dp->rings_in_lds = (size_t)(st_max + cr_max) * 64 * sizeof(float) <= 48 * 1024;
+        FVAD_HIP(ctx, dp->alloc(&dp->cfg, NC));
+        FVAD_HIP(ctx, dp->alloc(&dp->lt, (((size_t)lt_max + 63) / 64 + 1) * 64 * M));
+        FVAD_HIP(ctx, dp->alloc(&dp->rings, (size_t)(st_max + cr_max) * M));
+        FVAD_HIP(ctx, dp->alloc(&dp->state, M));
+        FVAD_HIP(ctx, dp->alloc(&dp->count, M));
+        FVAD_HIP(ctx, dp->alloc(&dp->audit, M));
+        FVAD_HIP(ctx, dp->alloc(&dp->stats, 2 * M));
+        FVAD_HIP(ctx, dp->alloc(&dp->paused, 1));
+        FVAD_HIP(ctx, hipMemcpyAsync(dp->cfg, hc.data(), NC * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
+        dp->ended.assign(S, 0);
+        dp->count_h.assign(M, 0);
+        b->dev_parts = std::unique_ptr<void, DevPartsDeleter>(fresh.release(), DevPartsDeleter{free_dev_parts});
+        for (auto& v : b->segs) std::vector<fvad_speech_segment>().swap(v);
+    }
+    b->machines.clear(); // a host part cannot go on from a device part
+    const bool keep = b->keep_segments;
+    dp->segs_on_device = dp->segs_on_device && !keep;
+    dp->next_frame = UINT64_MAX; // (until this part has run: after an error the run starts again at frame 0)
+
+    // ---- device: the part's per-call inputs
+    DevScratch scratch;
+    float* d_ratio = nullptr;
+    long* d_nf = nullptr;
+    std::vector<long> nf_l(n_frames, n_frames + S);
+    FVAD_HIP(ctx, scratch.alloc(&d_ratio, ratio.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_nf, S));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), S * sizeof(long), hipMemcpyHostToDevice, st));
+
+    // Segment room: at most one segment per 4 frames (fvad_vad_batch_run_device).  A part that keeps its segments writes them
+    // from the start of the buffer (the earlier ones are on the host); otherwise the buffer holds every segment since the first
+    // part.  The buffer has room for at least the part's bound or the one-shot's first room (context option vad_seg_cap, else
+    // 512 MB over all machines), whichever is less; a machine that fills it stops before its next frame, the room doubles (the
+    // contents kept, never past what the frames allow) and the part goes on from there.  So the room follows the segments,
+    // not the length of the run.
+    const size_t most = keep ? P / 4 + 1 : (size_t)((first_frame + P) / 4 + 1);
+    const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
+                                                  : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / M);
+    const size_t first_room = std::min(P / 4 + 1, room);
+    auto grow = [&](size_t cap) -> int { // the buffer with room for cap segments per machine, the old contents kept
+        fvad_speech_segment* d = nullptr;
+        FVAD_HIP(ctx, hipMalloc((void**)&d, std::max<size_t>(cap * M, 1) * sizeof(fvad_speech_segment)));
+        if (dp->segs && dp->seg_cap) {
+            const size_t w = dp->seg_cap * sizeof(fvad_speech_segment);
+            const hipError_t e = hipMemcpy2DAsync(d, cap * sizeof(fvad_speech_segment), dp->segs, w, w, M, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) hipStreamSynchronize(st);
+            if (e != hipSuccess) { hipFree(d); return hip_fail(ctx, e, "hipMemcpy2DAsync"); }
+        }
+        hipFree(dp->segs);
+        dp->segs = d;
+        dp->seg_cap = cap;
+        return FVAD_OK;
+    };
+    if (dp->seg_cap < first_room) {
+        const int rc = grow(first_room);
+        if (rc) return rc;
+    }
+
+    VadMachinesArgs a{};
+    a.cfgs = dp->cfg;
+    a.n_configs = (int)NC;
+    a.n_streams = (long)S;
+    a.by_config = dp->by_config;
+    a.n_channels = (int)C;
+    a.n_machines = (long)M;
+    a.n_lanes = (long)(S * C);
+    a.band = d_band;
+    a.band_stride = (long)band_stride;
+    a.ratio = d_ratio;
+    a.ratio_stride = (long)ratio_stride;
+    a.n_frames = d_nf;
+    a.fft_size = F;
+    a.lt_rings = dp->lt;
+    a.rings = dp->rings;
+    a.rings_in_lds = dp->rings_in_lds ? 1 : 0;
+    a.st_max = (int)dp->st_max;
+    a.cr_max = (int)dp->cr_max;
+    a.seg_count = dp->count;
+    a.audits = dp->audit;
+    a.stats = dp->stats;
+    a.resume = 1;
+    a.fresh = first_frame == 0;
+    a.rebase = keep;
+    a.first_frame = first_frame;
+    a.state = dp->state;
+    a.paused = dp->paused;
+    for (;;) {
+        unsigned paused = 0;
+        a.segs = dp->segs;
+        a.seg_cap = (uint32_t)dp->seg_cap;
+        FVAD_HIP(ctx, hipMemsetAsync(dp->paused, 0, sizeof(unsigned), st));
+        time_begin(ctx, "vad_machines");
+        const int e = fvad_launch_vad_machines(a, st);
+        time_end(ctx);
+        if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
+        FVAD_HIP(ctx, hipMemcpyAsync(&paused, dp->paused, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        FVAD_HIP(ctx, hipStreamSynchronize(st));
+        if (!paused) break;
+        // a machine ran out of room: go on from where each machine stopped, with twice the room (no machine needs more than most)
+        const size_t cap = std::min(2 * dp->seg_cap, most);
+        if (cap <= dp->seg_cap) return set_err(ctx, FVAD_ERR_HIP, "vad machines: more segments than frames allow");
+        const int rc = grow(cap);
+        if (rc) return rc;
+        a.fresh = 0;
+        a.rebase = 0;
+    }
+
+    // ---- results: everything run so far
+    std::vector<uint32_t> count(M);
+    std::vector<fvad_vad_audit> audits(M);
+    std::vector<unsigned long long> stats(2 * M);
+    FVAD_HIP(ctx, hipMemcpyAsync(count.data(), dp->count, M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), dp->audit, M * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), dp->stats, 2 * M * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<fvad_speech_segment> segs;
+    size_t used = 0; // the part's segments: machine m's new ones at the start of its row
+    if (keep) {
+        for (size_t m = 0; m < M; ++m) used = std::max<size_t>(used, count[m] - dp->count_h[m]);
+        segs.resize(used * M);
+        if (used) {
+            const size_t w = used * sizeof(fvad_speech_segment);
+            FVAD_HIP(ctx, hipMemcpy2DAsync(segs.data(), w, dp->segs, dp->seg_cap * sizeof(fvad_speech_segment), w, M, hipMemcpyDeviceToHost, st));
+            FVAD_HIP(ctx, hipStreamSynchronize(st));
+        }
+    }
+    FVAD_HIP(ctx, hipGetLastError());
+    const bool all_kept = keep && (first_frame == 0 || b->segs_kept);
+    for (size_t m = 0; m < M; ++m) {
+        auto& v = b->segs[m];
+        if (all_kept) {
+            const fvad_speech_segment* sm = segs.data() + m * used;
+            v.insert(v.end(), sm, sm + (count[m] - dp->count_h[m]));
+        } else {
+            std::vector<fvad_speech_segment>().swap(v);
+        }
+        b->exact_evals[m] = stats[2 * m];
+        b->lazy_pushes[m] = stats[2 * m + 1];
+    }
+    b->audits = std::move(audits);
+    dp->count_h = std::move(count);
+    for (size_t s = 0; s < S; ++s)
+        if (n_frames[s] < P) dp->ended[s] = 1;
+    dp->next_frame = first_frame + P;
+    b->segs_kept = all_kept;
+    b->scored = false; // the scores were of the previous segments
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_score_device(fvad_ctx* ctx, fvad_vad_batch* b)
+{
+    if (!ctx) return no_ctx();
+    if (!b) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null batch");
+    const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+    if (!b->has_refs) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no references to score against");
+    if (!dp) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no device parts run");
+    if (dp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the parts ran on another context");
+    if (!dp->segs_on_device) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the segments are on the host (a part kept them): fvad_vad_batch_score");
+    hipSetDevice(ctx->device);
+    std::vector<fvad_single_stats> scores;
+    const int rc = score_on_device(ctx, b, dp->segs, dp->count, dp->seg_cap, &scores);
+    if (rc) return rc;
+    b->scores = std::move(scores);
+    b->scored = true;
     return FVAD_OK;
 }
 

@@ -479,10 +479,10 @@ static void frame_ratios(Rms chunk_rms, size_t C, size_t n_chunks, size_t n_fram
 }
 
 void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t C, size_t n_chunks, size_t n_frames, size_t fft_size,
-                        size_t chunk_size, float* out)
+                        size_t chunk_size, float* out, uint64_t first_frame)
 {
-    frame_ratios([&](size_t c, size_t k) { return chunk_rms[c * rms_stride + k]; }, C, n_chunks, n_frames, 0, 0, fft_size, chunk_size, out,
-                 nullptr);
+    frame_ratios([&](size_t c, size_t k) { return chunk_rms[c * rms_stride + k]; }, C, n_chunks, n_frames, first_frame,
+                 first_frame * fft_size / chunk_size, fft_size, chunk_size, out, nullptr);
 }
 
 } // namespace fvad
@@ -501,6 +501,7 @@ int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_st
     if ((first_frame + n_frames) * b->fft_size > (first_chunk + n_chunks) * chunk_size) return FVAD_ERR_INVALID_ARGUMENT; // a frame without its chunk's ratio
     const size_t C = b->n_channels, n_lanes = b->n_streams * C;
     if (first_frame == 0) { // fresh machines (VADMachine.init per pipeline, VADPipeline.zig:60-75); machine s * NC + c
+        b->dev_parts.reset(); // (a device run in parts cannot go on after a host run)
         b->machines.clear();
         for (size_t s = 0; s < b->n_streams; ++s)
             for (size_t c = 0; c < NC; ++c) b->machines.emplace_back(new fvad::VadMachine(b->cfgs[c], b->sample_rate, C, b->fft_size));

@@ -71,8 +71,15 @@ void run_many(VadMachine* const* vads, size_t n_streams, const float* const* ban
 
 // the volume ratio of each of a stream's first n_frames FFT frames from its channels' chunk RMS (channel c's chunk k at
 // chunk_rms[c * rms_stride + k]), as fvad_vad_batch_run hands it to the machines (every frame covers a chunk: each has a ratio)
+// (frames from first_frame on, first_frame * fft_size a multiple of chunk_size: chunk_rms starts at the part's first chunk)
 void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t n_channels, size_t n_chunks, size_t n_frames, size_t fft_size,
-                        size_t chunk_size, float* out);
+                        size_t chunk_size, float* out, uint64_t first_frame = 0);
+
+// the device state of a batch run in parts on the GPU (engine_sweep.cpp owns it; this file only releases it)
+struct DevPartsDeleter {
+    void (*fn)(void*) = nullptr;
+    void operator()(void* p) const { if (fn) fn(p); }
+};
 
 } // namespace fvad
 
@@ -89,6 +96,8 @@ struct fvad_vad_batch {
     // a run in parts (fvad_vad_batch_run_part): the streams' machines live on between the parts
     std::vector<std::unique_ptr<fvad::VadMachine>> machines;
     uint64_t next_frame = 0;
+    // a run in parts on the GPU (fvad_vad_batch_run_device_part): the machines' state in device memory between the parts
+    std::unique_ptr<void, fvad::DevPartsDeleter> dev_parts;
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
     // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
     bool has_refs = false;

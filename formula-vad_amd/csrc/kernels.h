@@ -210,7 +210,7 @@ void fvad_launch_irfft_batch(const float* bins, long n_frames, FftTables tb, flo
 int fvad_launch_irfft_generic(const float* bins, long n_frames, VadFftPlan pl, float* out, hipStream_t stream); // hipError_t as int
 
 // ------------------------------------------------------------------ VAD machines of a parameter sweep (kernels_vad.hip)
-namespace fvad { struct VadMachineCfg; } // vad_machine.h
+namespace fvad { struct VadMachineCfg; struct VadLaneState; } // vad_machine.h
 struct VadMachinesArgs {
     const fvad::VadMachineCfg* cfgs; // [n_configs] (device), with their bands
     int n_configs, n_channels;
@@ -232,6 +232,16 @@ struct VadMachinesArgs {
     uint32_t* seg_count;       // [n_machines]: segments the machine closed (may exceed seg_cap: then only seg_cap were written)
     fvad_vad_audit* audits;    // [n_machines]
     unsigned long long* stats; // [n_machines][2]: exact evaluations of the long-term chain, lazy pushes
+    // ---- the resume form (resume = 1, fvad_vad_batch_run_device_part): every machine's state lives on between launches in
+    // state[machine]; the short-term and channel-ratio rings in `rings` (copied into LDS and back when rings_in_lds); frames
+    // [first_frame, first_frame + n_frames[s]) of the stream, band / ratio from the part's first frame.  A machine whose
+    // segment room (seg_cap past its seg_base) is full before its last frame stops there and sets *paused: the next launch
+    // with fresh = 0 goes on from that frame.  rebase: seg_base = the machine's segment count on entry (segments are written
+    // at seg[count - seg_base]); else seg_base is kept.
+    int resume, fresh, rebase;
+    uint64_t first_frame;
+    fvad::VadLaneState* state;  // [n_machines], machine = stream * n_configs + config
+    unsigned* paused;
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
 

@@ -139,12 +139,39 @@ struct Machine : fvad::VadMachineState { // the step (decide, finish_step) and t
     }
 };
 
+// the step's state field by field (a copy of the whole struct takes it through the stack or LDS)
+__device__ __forceinline__ void copy_state(fvad::VadMachineState& d, const fvad::VadMachineState& s)
+{
+    d.state = s.state;
+    d.speech_start = s.speech_start;
+    d.speech_end = s.speech_end;
+    d.ratio_sum = s.ratio_sum;
+    d.ratio_count = s.ratio_count;
+    d.met_cum = s.met_cum;
+    d.audit.min_rel_threshold_margin = s.audit.min_rel_threshold_margin;
+    d.audit.min_abs_ratio_margin = s.audit.min_abs_ratio_margin;
+    d.audit.n_frames = s.audit.n_frames;
+    d.lt_last = s.lt_last;
+    d.has_last = s.has_last;
+    d.lt_approx = s.lt_approx;
+    d.lt_err = s.lt_err;
+    d.lt_abs = s.lt_abs;
+    d.lt_abs_anchor = s.lt_abs_anchor;
+    d.lt_stale = s.lt_stale;
+    d.lt_anchored = s.lt_anchored;
+    d.lt_updates = s.lt_updates;
+    d.exact_evals = s.exact_evals;
+    d.lazy_pushes = s.lazy_pushes;
+}
+
 } // namespace
 
 typedef __attribute__((address_space(3))) float lds_float;
 
-// RINGS_LDS: the short-term and channel-ratio rings in LDS ([st_max + cr_max][64]), else in global memory
-template <bool RINGS_LDS>
+// RINGS_LDS: the short-term and channel-ratio rings in LDS ([st_max + cr_max][64]), else in global memory.
+// RESUME: the machine lives on between launches (a.state, a.rings, a.lt_rings: fvad_vad_batch_run_device_part): it is loaded
+// before the frame loop and stored after it, so that the loop itself is the one-shot form's
+template <bool RINGS_LDS, bool RESUME>
 __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
 {
     extern __shared__ float vad_rings[];
@@ -171,7 +198,24 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     else { rb = a.rings + m; rs = a.n_machines; }
     mc.st = Ring<P>{rb, rs, cfg->short_len, 0, 0, cfg->st_scalar, 0.0};
     mc.cr = Ring<P>{rb + (long)a.st_max * rs, rs, cfg->ratio_len, 0, 0, cfg->cr_scalar, 0.0};
-    if (cfg->has_init) { // RollingAverage.init with an initial value (RollingAverage.zig:20-26): full, steady, its average evaluated
+    uint32_t n_segs = 0, seg_base = 0; // (seg_base: the machine's first segment in the buffer)
+    long k0 = 0;                       // the part's first frame this launch runs
+    if (RESUME && !a.fresh) {          // the machine where the previous launch left it
+        const fvad::VadLaneState& ls = a.state[id];
+        copy_state(mc, ls.m);
+        mc.st.w = ls.st_w; mc.st.wc = ls.st_wc; mc.st.pref = ls.st_pref;
+        mc.cr.w = ls.cr_w; mc.cr.wc = ls.cr_wc; mc.cr.pref = ls.cr_pref;
+        mc.lt_w = ls.lt_w; mc.lt_wc = ls.lt_wc; mc.lt_filled = ls.lt_filled; mc.lt_steady = ls.lt_steady != 0;
+        mc.lt_next = mc.slot(mc.lt_w);
+        n_segs = ls.n_segs;
+        seg_base = a.rebase ? n_segs : ls.seg_base;
+        k0 = ls.next_frame > a.first_frame ? (long)(ls.next_frame - a.first_frame) : 0;
+        if constexpr (RINGS_LDS) { // the rings' home between launches is a.rings, laid out as the global form has them
+            for (uint32_t i = 0; i < cfg->short_len; ++i) rb[(long)i * 64] = a.rings[(long)i * a.n_machines + m];
+            for (uint32_t i = 0; i < cfg->ratio_len; ++i)
+                rb[(long)(a.st_max + i) * 64] = a.rings[(long)(a.st_max + i) * a.n_machines + m];
+        }
+    } else if (cfg->has_init) { // RollingAverage.init with an initial value (RollingAverage.zig:20-26): full, steady, its average evaluated
         double acc = 0.0;
         for (uint32_t i = 0; i < cfg->long_len; ++i) acc += cfg->lt_q_init;
         mc.lt_last = acc;
@@ -186,7 +230,6 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     const float* band = a.band + ((long)cfg->band * a.n_lanes + s * C) * a.band_stride;
     const float* ratio = a.ratio + s * a.ratio_stride;
     fvad_speech_segment* seg = a.segs + id * (long)a.seg_cap;
-    uint32_t n_segs = 0;
     // the next frame's band values (up to kPre channels) and ratio are loaded while this frame runs; the minimum is taken when the
     // frame is run, so that the loads are waited for a frame later (more channels: loaded and reduced at once)
     constexpr int kPre = 4;
@@ -206,8 +249,10 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         }
         return mn;
     };
-    if (nf > 0) fetch(0);
-    for (long k = 0; k < nf; ++k) {
+    long k_end = nf;
+    if (nf > k0) fetch(k0);
+    for (long k = k0; k < nf; ++k) {
+        if (RESUME && n_segs - seg_base >= a.seg_cap) { k_end = k; *a.paused = 1; break; } // no room for a segment of this frame
         const float mv = min_vol(k), rt = nr;
         if (k + 1 < nf) fetch(k + 1);
         // every frame overlaps a chunk, so its metadata always has a ratio (BufferedFFT.zig:137-140): has_ratio is true, and a
@@ -216,10 +261,26 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         const double cr = mc.cr.push(rt);
         const bool met = mc.decide(mc.cf, st, cr, [&] { mc.lt_exact(); });
         if (!met) mc.lt_push(mv);
-        mc.finish_step(mc.cf, (uint64_t)k * a.fft_size, met, true, rt, [&](const fvad_speech_segment& sg) {
-            if (n_segs < a.seg_cap) seg[n_segs] = sg;
+        const uint64_t frame = RESUME ? a.first_frame + (uint64_t)k : (uint64_t)k;
+        mc.finish_step(mc.cf, frame * a.fft_size, met, true, rt, [&](const fvad_speech_segment& sg) {
+            if (n_segs - seg_base < a.seg_cap) seg[n_segs - seg_base] = sg;
             ++n_segs; // counted past the capacity: the caller sees the overflow and runs again with room for all
         });
+    }
+    if (RESUME) {
+        fvad::VadLaneState& ls = a.state[id];
+        copy_state(ls.m, mc);
+        ls.st_w = mc.st.w; ls.st_wc = mc.st.wc; ls.st_pref = mc.st.pref;
+        ls.cr_w = mc.cr.w; ls.cr_wc = mc.cr.wc; ls.cr_pref = mc.cr.pref;
+        ls.lt_w = mc.lt_w; ls.lt_wc = mc.lt_wc; ls.lt_filled = mc.lt_filled; ls.lt_steady = mc.lt_steady ? 1u : 0u;
+        ls.n_segs = n_segs;
+        ls.seg_base = seg_base;
+        ls.next_frame = a.first_frame + (uint64_t)k_end;
+        if constexpr (RINGS_LDS) {
+            for (uint32_t i = 0; i < cfg->short_len; ++i) a.rings[(long)i * a.n_machines + m] = rb[(long)i * 64];
+            for (uint32_t i = 0; i < cfg->ratio_len; ++i)
+                a.rings[(long)(a.st_max + i) * a.n_machines + m] = rb[(long)(a.st_max + i) * 64];
+        }
     }
     a.seg_count[id] = n_segs;
     a.audits[id] = mc.audit;
@@ -232,7 +293,10 @@ int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream)
     if (a.n_machines <= 0) return (int)hipSuccess;
     const size_t lds = a.rings_in_lds ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0;
     const dim3 grid((unsigned)((a.n_machines + 63) / 64));
-    if (a.rings_in_lds) hipLaunchKernelGGL(vad_machines_kernel<true>, grid, dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL(vad_machines_kernel<false>, grid, dim3(64), 0, stream, a);
+    if (a.resume) {
+        if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, true>), grid, dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((vad_machines_kernel<false, true>), grid, dim3(64), 0, stream, a);
+    } else if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, false>), grid, dim3(64), lds, stream, a);
+    else hipLaunchKernelGGL((vad_machines_kernel<false, false>), grid, dim3(64), 0, stream, a);
     return (int)hipGetLastError();
 }

@@ -185,4 +185,15 @@ struct VadMachineState {
     }
 };
 
+// A sweep machine between two launches of the kernel's resume form (kernels_vad.hip): the step's state, the cursors of its rings
+// (the rings themselves stay in device memory), its segment count and where its current part has got to
+struct VadLaneState {
+    VadMachineState m;
+    double st_pref, cr_pref;
+    uint32_t st_w, st_wc, cr_w, cr_wc;
+    uint32_t lt_w, lt_wc, lt_filled, lt_steady;
+    uint32_t n_segs, seg_base; // segments closed so far; the first of them in the segment buffer
+    uint64_t next_frame;       // the next frame the machine runs
+};
+
 } // namespace fvad

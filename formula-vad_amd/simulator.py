@@ -20,6 +20,7 @@ SimulationInstance.zig:101-104).  Differences, by design:
 import argparse
 import itertools
 import json
+import math
 import os
 import sys
 import time
@@ -215,6 +216,19 @@ def _read_instance(inst):
         raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
     with open(inst["ref_path"], "rb") as f:
         return pcm, fv.parse_audacity(f.read())
+
+
+def _read_labels(inst):
+    with open(inst["ref_path"], "rb") as f:
+        return fv.parse_audacity(f.read())
+
+
+def _map_audio(inst):
+    """an instance's audio mapped, not read (fv.wav_map): [n_frames][n_channels] int16 or float32"""
+    pcm, sr = fv.wav_map(inst["audio_path"])
+    if sr != 48000:
+        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
+    return pcm
 
 
 def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None):
@@ -530,8 +544,22 @@ def _ranked(rows):
     return sorted(rows, key=lambda r: (0, -r["F"], r["config"]) if r["F"] == r["F"] else (1, 0.0, r["config"]))
 
 
+def slice_align(fft_size, chunk=24000):
+    """the chunks a time slice of a sliced grid is a multiple of: lcm(chunk, fft_size) / chunk, so that every slice starts on a
+    frame (16 at fft_size 1024)"""
+    return math.lcm(chunk, int(fft_size)) // chunk
+
+
+def check_slice_chunks(slice_chunks, fft_size):
+    """ValueError unless slice_chunks is a positive multiple of slice_align(fft_size)"""
+    a = slice_align(fft_size)
+    if isinstance(slice_chunks, bool) or not isinstance(slice_chunks, (int, np.integer)) or slice_chunks <= 0 or slice_chunks % a:
+        raise ValueError(f"slice_chunks = {slice_chunks!r}: a time slice is a positive multiple of {a} chunks at fft_size {fft_size} "
+                         f"(lcm(24000, fft_size) / 24000: slices start on a frame)")
+
+
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16):
+             n_threads=16, slice_chunks=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -544,9 +572,21 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     includes the scoring.  Labels must be numbers: the scorers walk them sorted, so a NaN label (fvad_parse_audacity reads
     "nan") is refused (ValueError, before any GPU work), where run_sweep's per-pair fvad_stats_from_segments takes it.
 
+    slice_chunks = N runs the whole pipeline in time slices of N chunks (a positive multiple of slice_align(fft_size), 16 at
+    fft_size 1024; ValueError before any GPU work otherwise), so that device and host memory are bounded by the slice, not the
+    corpus (_run_grid_sliced): the audio is read slice by slice from the mapped files (wav_map), each slice denoised from zero
+    history with its SLICE_HALO_CHUNKS-chunk halo, its band sums computed, and the machines run on in parts
+    (fvad_vad_batch_run_device_part, or fvad_vad_batch_run_part with vad_on "host").  On a context with the option
+    reproducible = 1 the statistics are the unsliced run's bit for bit; by default the NN kernels the engine selects depend on
+    the launch size, which can move the gains by about 1e-6 and flip a decision.  None: everything in one pass, as above.
+
     Returns dict(configs, rows [one aggregate dict per config, config order], aggregates [AggregateStats], stats float32
-    [config][instance][11] (fvad_single_stats), times {stage: s}); prints the top rows by F-score and the stage times, and
-    writes the configs and all rows as JSON to json_path if given."""
+    [config][instance][11] (fvad_single_stats), times {stage: s}, slices [number of time slices; 1 unsliced], device_bytes);
+    prints the top rows by F-score and the stage times, and writes the configs and all rows as JSON to json_path if given.
+    device_bytes is set when sliced (else None): the peak of the slice buffers run_grid allocates, plus the largest
+    VadSweep.device_bytes() of a batch, plus the engine's launch workspace for a slice's chunks computed from shapes
+    (ENGINE_WS_BYTES_PER_CHUNK).  It excludes the context's own buffers (weights, FFT plans, the K4 pass's job
+    list), each part's frame ratios and the HIP runtime's overhead."""
     if isinstance(grid, str):
         with open(grid) as f:
             grid = json.load(f)
@@ -563,8 +603,13 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         raise ValueError("score_on='device' scores next to the device machines: it needs vad_on='device'")
     plan = load_plan(plan_path)
     F = plan["fft_size"]
+    if slice_chunks is not None:
+        check_slice_chunks(slice_chunks, F)
     stat_cfgs = [_stat_cfg(c) for c in configs]
-    loaded = [_read_instance(i) for i in plan["instances"]]
+    if slice_chunks is not None:   # the audio stays in its files: mapped, read slice by slice
+        loaded = [(_map_audio(i), _read_labels(i)) for i in plan["instances"]]
+    else:
+        loaded = [_read_instance(i) for i in plan["instances"]]
     for inst, (_, ref) in zip(plan["instances"], loaded):
         if any(x != x for r in ref for x in r):
             raise ValueError(f"{inst['ref_path']}: a NaN label; grid scoring walks the labels sorted by start and needs "
@@ -586,79 +631,88 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         allocs.append(a)
         return a
 
-    try:
-        t0 = time.perf_counter()
-        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
-        times["denoise"] = time.perf_counter() - t0
-        l0 = 0
-        for nch, members in groups.items():
-            sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
-            try:
-                t0 = time.perf_counter()
-                bins, _ = sweep.bands()
-                g_lanes = list(range(l0, l0 + len(members) * nch))
-                l0 += len(g_lanes)
-                d_gden = d_den + g_lanes[0] * n_den * 4
-                bstride = max(nf_all, 1)
-                d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                if nf_all:
-                    ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
-                g_rms = np.ascontiguousarray(rms[g_lanes])
-                times["bands"] += time.perf_counter() - t0
-                if vad_on == "device":
-                    if score_on == "device":
-                        sweep.set_references([refs[i] for i in members], stat_cfgs)
-                        sweep.keep_segments(False)
-                    # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
-                    # caller's own timing records are left alone: the machines' time then includes the scoring)
-                    timed = score_on == "device" and not ctx.timing
-                    if timed:
-                        ctx.enable_timing(True)
-                    try:
-                        t0 = time.perf_counter()
-                        sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
-                                         [n_chunks[i] for i in members])
-                        wall = time.perf_counter() - t0
-                        score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
-                    finally:
+    n_slices, dev_bytes = 1, None
+    if slice_chunks is not None:
+        try:
+            n_slices, dev_bytes = _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on,
+                                                   n_threads, stats, times)
+        finally:
+            if own_ctx:
+                ctx.close()
+    else:
+        try:
+            t0 = time.perf_counter()
+            groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
+            times["denoise"] = time.perf_counter() - t0
+            l0 = 0
+            for nch, members in groups.items():
+                sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+                try:
+                    t0 = time.perf_counter()
+                    bins, _ = sweep.bands()
+                    g_lanes = list(range(l0, l0 + len(members) * nch))
+                    l0 += len(g_lanes)
+                    d_gden = d_den + g_lanes[0] * n_den * 4
+                    bstride = max(nf_all, 1)
+                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                    if nf_all:
+                        ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                    g_rms = np.ascontiguousarray(rms[g_lanes])
+                    times["bands"] += time.perf_counter() - t0
+                    if vad_on == "device":
+                        if score_on == "device":
+                            sweep.set_references([refs[i] for i in members], stat_cfgs)
+                            sweep.keep_segments(False)
+                        # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
+                        # caller's own timing records are left alone: the machines' time then includes the scoring)
+                        timed = score_on == "device" and not ctx.timing
                         if timed:
-                            ctx.enable_timing(False)
-                    if score_on == "device":
-                        times["machines"] += wall - score_s
-                        times["scoring"] += score_s
-                    else:
-                        times["machines"] += wall
-                        t0 = time.perf_counter()
-                        sweep.set_references([refs[i] for i in members], stat_cfgs)
-                        sweep.score(n_threads)
-                        times["scoring"] += time.perf_counter() - t0
-                    for c in range(NC):
-                        stats[c, members] = sweep.config_stats(c)
-                    continue
-                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
-                for k, i in enumerate(members):   # instances differ in length: one host batch each
-                    nf_i = n_chunks[i] * chunk // F
-                    one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
-                    try:
-                        t0 = time.perf_counter()
-                        one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
-                                np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
-                        times["machines"] += time.perf_counter() - t0
-                        t0 = time.perf_counter()
-                        one.set_references([refs[i]], stat_cfgs)
-                        one.score(n_threads)
+                            ctx.enable_timing(True)
+                        try:
+                            t0 = time.perf_counter()
+                            sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
+                                             [n_chunks[i] for i in members])
+                            wall = time.perf_counter() - t0
+                            score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
+                        finally:
+                            if timed:
+                                ctx.enable_timing(False)
+                        if score_on == "device":
+                            times["machines"] += wall - score_s
+                            times["scoring"] += score_s
+                        else:
+                            times["machines"] += wall
+                            t0 = time.perf_counter()
+                            sweep.set_references([refs[i] for i in members], stat_cfgs)
+                            sweep.score(n_threads)
+                            times["scoring"] += time.perf_counter() - t0
                         for c in range(NC):
-                            stats[c, i] = one.config_stats(c)[0]
-                        times["scoring"] += time.perf_counter() - t0
-                    finally:
-                        one.close()
-            finally:
-                sweep.close()
-    finally:
-        for a in allocs:
-            ctx.device_free(a)
-        if own_ctx:
-            ctx.close()
+                            stats[c, members] = sweep.config_stats(c)
+                        continue
+                    gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
+                    for k, i in enumerate(members):   # instances differ in length: one host batch each
+                        nf_i = n_chunks[i] * chunk // F
+                        one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
+                        try:
+                            t0 = time.perf_counter()
+                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
+                                    np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
+                            times["machines"] += time.perf_counter() - t0
+                            t0 = time.perf_counter()
+                            one.set_references([refs[i]], stat_cfgs)
+                            one.score(n_threads)
+                            for c in range(NC):
+                                stats[c, i] = one.config_stats(c)[0]
+                            times["scoring"] += time.perf_counter() - t0
+                        finally:
+                            one.close()
+                finally:
+                    sweep.close()
+        finally:
+            for a in allocs:
+                ctx.device_free(a)
+            if own_ctx:
+                ctx.close()
     aggs = [fv.stats_aggregate_array(stats[c]) for c in range(NC)]
     rows = [dict(config=c, **_agg_row(agg)) for c, agg in enumerate(aggs)]
     elapsed = time.perf_counter() - t_all
@@ -676,7 +730,151 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         out.write(f"[{NC} configs x {n_inst} instances in {elapsed:.2f} s: denoise {times['denoise']:.2f} s, bands "
                   f"{times['bands']:.2f} s, machines ({vad_on}) {times['machines']:.2f} s, scoring ({score_on}) "
                   f"{times['scoring']:.3f} s]\n")
-    return {"configs": configs, "rows": rows, "aggregates": aggs, "stats": stats, "times": times}
+    return {"configs": configs, "rows": rows, "aggregates": aggs, "stats": stats, "times": times, "slices": n_slices,
+            "device_bytes": dev_bytes}
+
+# the halo of a time slice: a slice is denoised from zero history this many chunks early (two are what NSNet2's cross-chunk state
+# needs; shard.ALIGN_CHUNKS), and the halo's chunks are dropped
+SLICE_HALO_CHUNKS = 16
+# the engine's device intermediates per chunk of a launch (computed from shapes, not measured): features [54][176],
+# spectrogram [50][161][2], gi [54][25][3][16], h1 and h2 [54][400], fc2 / fc3 outputs [50][608], gains [50][176], f32
+ENGINE_WS_BYTES_PER_CHUNK = 4 * (54 * 176 + 50 * 161 * 2 + 54 * 25 * 3 * 16 + 2 * 54 * 400 + 50 * 608 + 50 * 176)
+ENGINE_MAX_LAUNCH_CHUNKS = 49152
+
+
+def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times):
+    """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
+    SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
+    (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
+    computed from the denoised audio at chunk s0 (fvad_engine_band_sums_device), and the machines run on: one device batch
+    per group in parts (fvad_vad_batch_run_device_part), or with vad_on "host" one host batch per instance
+    (fvad_vad_batch_run_part).  An instance gets 0 frames once it has ended.  The device buffers are allocated once, for the
+    largest group, and reused slice after slice.  Fills stats [config][instance][11] and times; returns (slices run,
+    device_bytes as run_grid describes it)."""
+    chunk, H = 24000, SLICE_HALO_CHUNKS
+    n_chunks = [a.shape[0] // chunk for a in audio]
+    groups = {}
+    for i, a in enumerate(audio):
+        groups.setdefault(a.shape[1], []).append(i)
+    probe = fv.VadSweep(1, configs, fft_size=F)
+    bins, _ = probe.bands()
+    probe.close()
+    probe = fv.VadSweep(1, [configs[0]], fft_size=F)   # the engine pass sums config 0's band (unused: the bands come from K4)
+    (min_bin, max_bin), = probe.bands()[0]
+    probe.close()
+    n_max = N + H                                      # chunks of a slice with its halo
+    lanes_max = max([len(m) * nch for nch, m in groups.items()] + [1])
+    fr_slice = N * chunk // F                          # frames of a full slice (N * chunk is a multiple of F)
+    own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4,
+           "band0": lanes_max * (n_max * chunk // F + 1) * 4, "rms": lanes_max * n_max * 4,
+           "bands": len(bins) * lanes_max * fr_slice * 4}
+    opts = fv.EngineOpts()
+    fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
+    opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
+    d = {}
+    host = None
+    batch_peak = 0
+    n_slices = 0
+    try:
+        for k, nb in own.items():
+            d[k] = ctx.device_alloc(max(nb, 16))
+        host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
+        for nch, members in groups.items():
+            L = len(members) * nch
+            K = max(n_chunks[i] for i in members)
+            nf_end = [n_chunks[i] * chunk // F for i in members]
+            dev = None
+            hosts = []
+            if vad_on == "device":
+                dev = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+                if score_on == "device":
+                    dev.set_references([refs[i] for i in members], stat_cfgs)
+                    dev.keep_segments(False)
+            else:
+                hosts = [fv.VadSweep(1, configs, n_channels=nch, fft_size=F) for _ in members]
+            try:
+                for s0 in range(0, K, N):
+                    s1 = min(s0 + N, K)
+                    start = max(s0 - H, 0)
+                    n = s1 - start
+                    n_slices += 1
+                    # ---- read and denoise [start, s1): lane l of the group at host[l * n * chunk]
+                    t0 = time.perf_counter()
+                    pcm = host[:L * n * chunk].reshape(L, n * chunk)
+                    for k, i in enumerate(members):
+                        a = audio[i]
+                        lo, hi = start * chunk, min(s1 * chunk, a.shape[0])
+                        for c in range(nch):
+                            row = pcm[k * nch + c]
+                            if hi > lo:
+                                if a.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                                    np.multiply(a[lo:hi, c], np.float32(1.0 / 32768.0), out=row[:hi - lo], casting="unsafe")
+                                else:
+                                    row[:hi - lo] = a[lo:hi, c]
+                            row[max(hi - lo, 0):] = 0.0
+                    ctx.to_device(d["pcm"], pcm)
+                    ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d["pcm"]), L, n * chunk, n * chunk, fv.vp(d["den"]),
+                                                                fv.vp(d["band0"]), fv.vp(d["rms"]), fv.C.byref(opts)),
+                            "fvad_engine_enqueue_device")
+                    rms = ctx.to_host(np.empty((L, n), np.float32), d["rms"])
+                    rms = np.ascontiguousarray(rms[:, s0 - start:])
+                    times["denoise"] += time.perf_counter() - t0
+                    # ---- band sums of the slice's frames: the denoised audio from chunk s0 on (frame-aligned: s0 is a
+                    # multiple of slice_align(F))
+                    t0 = time.perf_counter()
+                    f0 = s0 * chunk // F
+                    f1 = s1 * chunk // F
+                    ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins, d["bands"],
+                                         fr_slice, fft_size=F)
+                    times["bands"] += time.perf_counter() - t0
+                    nf = [max(0, min(e, f1) - f0) for e in nf_end]
+                    nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
+                    # ---- the machines
+                    t0 = time.perf_counter()
+                    if dev is not None:
+                        dev.run_device_part(ctx, d["bands"], fr_slice, nf, rms, nc, f0)
+                        batch_peak = max(batch_peak, dev.device_bytes())
+                    else:
+                        band = ctx.to_host(np.empty((len(bins), L, fr_slice), np.float32), d["bands"])
+                        for k, h in enumerate(hosts):
+                            if nf[k] == 0 and f0 > 0:
+                                continue   # ended (its machines keep their results)
+                            b = np.ascontiguousarray(band[:, k * nch:(k + 1) * nch, :nf[k]])
+                            r = np.ascontiguousarray(rms[k * nch:(k + 1) * nch, :max(nc[k], 1)])
+                            fv.check(fv.lib().fvad_vad_batch_run_part(h.h, b.ctypes.data_as(fv.c_float_p), max(nf[k], 1), nf[k],
+                                                                      r.ctypes.data_as(fv.c_float_p), r.shape[1], nc[k], chunk, f0,
+                                                                      n_threads), "fvad_vad_batch_run_part")
+                    times["machines"] += time.perf_counter() - t0
+                # ---- scoring
+                t0 = time.perf_counter()
+                if dev is not None:
+                    if score_on == "device":
+                        dev.score_device(ctx)
+                    else:
+                        dev.set_references([refs[i] for i in members], stat_cfgs)
+                        dev.score(n_threads)
+                    for c in range(len(configs)):
+                        stats[c, members] = dev.config_stats(c)
+                else:
+                    for k, (i, h) in enumerate(zip(members, hosts)):
+                        h.set_references([refs[i]], stat_cfgs)
+                        h.score(n_threads)
+                        for c in range(len(configs)):
+                            stats[c, i] = h.config_stats(c)[0]
+                times["scoring"] += time.perf_counter() - t0
+            finally:
+                if dev is not None:
+                    dev.close()
+                for h in hosts:
+                    h.close()
+    finally:
+        for a in d.values():
+            ctx.device_free(a)
+        if host is not None:
+            ctx.host_free(host)
+    ws = ENGINE_WS_BYTES_PER_CHUNK * min(lanes_max * n_max, ENGINE_MAX_LAUNCH_CHUNKS)
+    return n_slices, sum(own.values()) + batch_peak + ws
+
 
 def frame_ratios(chunk_rms, n_frames, fft_size=1024, chunk=24000):
     """Per-frame volume_ratio exactly as the metadata flows through the three buffered stages
@@ -720,9 +918,13 @@ def main(argv=None):
     ap.add_argument("--sweep-grid", default=None, help="score every config of a grid file ({\"base\": {...}, \"axes\": {field: "
                                                           "[values]}}) over one denoising pass; print the top configs (device 0)")
     ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
+    ap.add_argument("--slice-chunks", type=int, default=None,
+                    help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024), device and host "
+                         "memory bounded by the slice instead of the corpus")
     a = ap.parse_args(argv)
     if a.sweep_grid:
-        run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed)
+        run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
+                 slice_chunks=a.slice_chunks)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)

@@ -470,6 +470,29 @@ int fvad_vad_batch_lazy_stats(const fvad_vad_batch *b, size_t stream, size_t con
 int fvad_vad_batch_run_device(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
                               const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
                               const size_t *n_chunks, size_t chunk_size);
+/* The same in parts, for streams longer than device memory holds: frames [first_frame, first_frame + n_frames[s]) of stream
+ * s, d_band and chunk_rms pointing at the part's first frame and first chunk (as fvad_vad_batch_run_part takes them); the
+ * machines' state stays in device memory between the parts (csrc/kernels_vad.hip's resume form).  first_frame = 0 starts
+ * fresh machines and drops any earlier part state.  A later part must start where the previous device part ended, on a chunk
+ * boundary (first_frame * fft_size a multiple of chunk_size), on the same context; a stream given fewer frames than the
+ * part's longest has ended, and every later part must give it 0 frames and 0 chunks.  Host and device parts do not mix: a
+ * device part with first_frame > 0 after a host run, a one-shot device run or a failed part, and a host fvad_vad_batch_run_part
+ * with first_frame > 0 after a device part, return FVAD_ERR_INVALID_ARGUMENT (as does every other broken rule).  After each
+ * part the segments, audits and lazy statistics in b cover everything run so far, bit-identical to one
+ * fvad_vad_batch_run_device (and fvad_vad_batch_run) over all the frames, for every partition.  With keep_segments 1 each part's
+ * new segments are appended to b's; with 0 they stay in device memory (only counts, audits and statistics come back) for
+ * fvad_vad_batch_score_device.  A part never scores.  Segments are never truncated: a machine that fills its room (context
+ * option vad_seg_cap, as for the one-shot run) pauses, the room grows and the part goes on.
+ * fvad_vad_batch_score_device: the statistics of the device-held segments of the parts run so far (read them with
+ * fvad_vad_batch_config_stats), bit-identical to fvad_vad_batch_score on the same segments; FVAD_ERR_INVALID_ARGUMENT without
+ * references, without device part state, or when a part kept its segments on the host (score those with fvad_vad_batch_score).
+ * fvad_vad_batch_device_bytes: the device memory b holds between parts (0 without part state).
+ * A batch holding part state owns device memory of its context: destroy the batch before the context. */
+int fvad_vad_batch_run_device_part(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                                   const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
+                                   const size_t *n_chunks, size_t chunk_size, uint64_t first_frame);
+int fvad_vad_batch_score_device(fvad_ctx *ctx, fvad_vad_batch *b);
+size_t fvad_vad_batch_device_bytes(const fvad_vad_batch *b);
 
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;

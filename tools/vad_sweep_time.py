@@ -36,6 +36,35 @@ def make_configs(n, seed):
     return out[:n]
 
 
+def device_corpus(S, hours, seed, chunk=24000, F=1024):
+    """S streams x hours of synthetic denoised-like mono audio on the device (a noise floor with bursts of 0.5 .. 5 s every
+    1 .. 20 s, at frame resolution): (audio [S][n_chunks * chunk] f32 torch tensor on cuda:0, chunk RMS [S][n_chunks] numpy
+    f32, n_chunks)"""
+    import torch
+    n_chunks = int(hours * 3600 * 48000) // chunk
+    L = n_chunks * chunk
+    nf = L // F
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    audio = torch.empty((S, L), dtype=torch.float32, device=dev)
+    for s in range(S):
+        edges = np.cumsum(rng.uniform(0.5, 20.0, int(L / 48000 / 5) + 8)) * 48000 / F
+        env = np.zeros(nf + 1, np.float32)
+        for x in edges:
+            i0 = int(x)
+            if i0 >= nf:
+                break
+            env[i0:min(nf, i0 + int(rng.uniform(0.5, 5.0) * 48000 / F))] = 1.0
+        e = torch.from_numpy(env[:nf]).to(dev).repeat_interleave(F)
+        audio[s] = torch.randn(L, generator=g, device=dev) * (0.01 + 0.2 * e)
+        del e
+    rms = torch.sqrt(torch.mean(audio.view(S, n_chunks, chunk) ** 2, dim=2)).cpu().numpy().astype(np.float32)
+    torch.cuda.synchronize()
+    return audio, rms, n_chunks
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=21)
@@ -49,28 +78,11 @@ def main():
     fv = pkg.binding
     ctx = fv.Context(0)
     chunk, F = 24000, 1024
-    n_chunks = int(a.hours * 3600 * 48000) // chunk
+    S = a.streams
+    audio, rms, n_chunks = device_corpus(S, a.hours, a.seed)
     L = n_chunks * chunk
     nf = L // F
-    S = a.streams
-    dev = torch.device("cuda:0")
-    g = torch.Generator(device=dev)
-    g.manual_seed(a.seed)
-    rng = np.random.default_rng(a.seed)
-    audio = torch.empty((S, L), dtype=torch.float32, device=dev)
-    for s in range(S):  # a noise floor with bursts of 0.5 .. 5 s every 1 .. 20 s, at frame resolution
-        edges = np.cumsum(rng.uniform(0.5, 20.0, int(L / 48000 / 5) + 8)) * 48000 / F
-        env = np.zeros(nf + 1, np.float32)
-        for x in edges:
-            i0 = int(x)
-            if i0 >= nf:
-                break
-            env[i0:min(nf, i0 + int(rng.uniform(0.5, 5.0) * 48000 / F))] = 1.0
-        e = torch.from_numpy(env[:nf]).to(dev).repeat_interleave(F)
-        audio[s] = torch.randn(L, generator=g, device=dev) * (0.01 + 0.2 * e)
-        del e
-    rms = torch.sqrt(torch.mean(audio.view(S, n_chunks, chunk) ** 2, dim=2)).cpu().numpy().astype(np.float32)
-    torch.cuda.synchronize()
+    dev = audio.device
     d_den = audio.data_ptr()
     print(f"{S} streams x {a.hours:g} h ({nf} frames each), mono, fft 1024", flush=True)
     ctx.enable_timing(True)
