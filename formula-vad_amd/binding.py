@@ -239,6 +239,11 @@ SIGNATURES = {
     "fvad_vad_batch_run_device_part": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
     "fvad_vad_batch_score_device": (C.c_int, [vp, vp]),
     "fvad_vad_batch_device_bytes": (sz, [vp]),
+    "fvad_vad_batch_create_sweep_sized": (C.c_int, [C.POINTER(VadConfig), C.POINTER(sz), sz, sz, sz, sz, C.POINTER(vp)]),
+    "fvad_vad_batch_frame_sizes": (C.c_int, [vp, C.POINTER(sz), sz, C.POINTER(sz), C.POINTER(C.c_uint32)]),
+    "fvad_vad_batch_run_sized": (C.c_int, [vp, c_float_p, sz, C.POINTER(sz), c_float_p, sz, sz, sz, C.c_uint64, C.c_int]),
+    "fvad_vad_batch_run_device_sized": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz]),
+    "fvad_vad_batch_run_device_part_sized": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
     "fvad_ra_push": (C.c_double, [vp, C.c_float]),
@@ -1020,6 +1025,83 @@ class VadSweep:
             self.close()
         except Exception:
             pass
+
+
+class VadSweepSized(VadSweep):
+    """fvad_vad_batch_create_sweep_sized: a sweep whose configs run on frames of their own sizes (fft_sizes[c] for configs[c]),
+    several frame clocks in one batch.  The query calls (segments, audit, lazy_stats, references, scoring, config_stats,
+    device_bytes) are VadSweep's; bands() names each band's size."""
+
+    def __init__(self, n_streams, configs, fft_sizes, n_channels=1, sample_rate=48000):
+        assert len(fft_sizes) == len(configs)
+        arr = (VadConfig * len(configs))()
+        for i, ov in enumerate(configs):
+            lib().fvad_vad_config_default(C.byref(arr[i]))
+            for k, v in (ov or {}).items():
+                setattr(arr[i], k, v)
+        sizes = (sz * len(configs))(*[int(f) for f in fft_sizes])
+        self.h = vp()
+        check(lib().fvad_vad_batch_create_sweep_sized(arr, sizes, len(configs), sample_rate, n_channels, n_streams, C.byref(self.h)),
+              "fvad_vad_batch_create_sweep_sized")
+        self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, len(configs)
+        self.sizes, self.size_of_band = self.frame_sizes()
+
+    def frame_sizes(self):
+        """-> (the distinct sizes in first-seen config order, the size index of each band)"""
+        n = sz()
+        sizes = (sz * self.n_configs)()
+        sob = (C.c_uint32 * self.n_configs)()
+        check(lib().fvad_vad_batch_frame_sizes(self.h, sizes, self.n_configs, C.byref(n), sob), "fvad_vad_batch_frame_sizes")
+        n_bands = sz()
+        lib().fvad_vad_batch_bands(self.h, None, 0, C.byref(n_bands), None)
+        return [sizes[g] for g in range(n.value)], [sob[j] for j in range(n_bands.value)]
+
+    def bands(self):
+        """-> ([(fft_size, min_bin, max_bin)] of the distinct bands, size-major, band_of [config])"""
+        bins, band_of = VadSweep.bands(self)
+        return [(self.sizes[self.size_of_band[j]], lo, hi) for j, (lo, hi) in enumerate(bins)], band_of
+
+    def size_blocks(self):
+        """-> [(fft_size, first band, [(min_bin, max_bin)])] per size: the run of band blocks of each size"""
+        bands, _ = self.bands()
+        out = []
+        for g, F in enumerate(self.sizes):
+            js = [j for j in range(len(bands)) if self.size_of_band[j] == g]
+            out.append((F, js[0], [bands[j][1:] for j in js]))
+        return out
+
+    def run(self, band, chunk_rms, n_frames, first_sample=0, n_threads=1, chunk_size=24000):
+        """fvad_vad_batch_run_sized: band [n_bands][n_streams * n_channels][stride] (bands() order; a contiguous last axis),
+        n_frames[g] frames of size g from sample first_sample on, chunk_rms [lanes][n_chunks] from the part's first chunk"""
+        assert band.dtype == np.float32 and chunk_rms.dtype == np.float32
+        assert (band.shape[2] <= 1 or band.strides[2] == 4) and band.strides[1] == band.shape[2] * 4 and band.strides[0] == band.shape[1] * band.strides[1]
+        assert chunk_rms.shape[1] <= 1 or chunk_rms.strides[1] == 4
+        assert band.shape[1] == chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf = (sz * len(self.sizes))(*[int(x) for x in n_frames])
+        check(lib().fvad_vad_batch_run_sized(self.h, C.cast(band.ctypes.data, c_float_p), band.shape[2], nf,
+                                             C.cast(chunk_rms.ctypes.data, c_float_p), chunk_rms.strides[0] // 4, chunk_rms.shape[1],
+                                             chunk_size, int(first_sample), n_threads), "fvad_vad_batch_run_sized")
+
+    def _counts(self, n_frames, n_chunks):
+        G, S = len(self.sizes), self.n_streams
+        flat = [int(x) for row in n_frames for x in row]
+        assert len(flat) == G * S and len(n_chunks) == S
+        return (sz * (G * S))(*flat), (sz * S)(*[int(x) for x in n_chunks])
+
+    def run_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, chunk_size=24000):
+        """fvad_vad_batch_run_device_sized: n_frames [size][stream], n_chunks [stream]; d_band as bands() orders the blocks"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_run_device_sized(ctx.h, self.h, vp(d_band), band_stride, nf, fptr(chunk_rms), chunk_rms.shape[1], nc,
+                                                      chunk_size), "fvad_vad_batch_run_device_sized")
+
+    def run_device_part(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_sample, chunk_size=24000):
+        """fvad_vad_batch_run_device_part_sized: frames of every size from sample first_sample on, n_frames [size][stream]"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_run_device_part_sized(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf,
+                                                           fptr(chunk_rms), chunk_rms.shape[1], nc, chunk_size, int(first_sample)),
+                "fvad_vad_batch_run_device_part_sized")
 
 
 def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_threads=1):

@@ -198,6 +198,11 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
         else if (v == "config") tn.vad_lane_map = 1;
         else return FVAD_ERR_INVALID_ARGUMENT;
     }
+    else if (name == "vad_size_order") { // sized VAD batches, vad_lane_map "stream": a stream's lanes "size"-major (default) or in "caller" order; same bits
+        if (unset || v == "size") tn.vad_size_order = 0;
+        else if (v == "caller") tn.vad_size_order = 1;
+        else return FVAD_ERR_INVALID_ARGUMENT;
+    }
     else if (name == "vad_seg_cap") { // fvad_vad_batch_run_device's first segment room per machine (tests: the overflow path); unset = 512 MB over all machines
         long c = 0;
         if (!unset && (!to_long(c) || c < 1 || c > (1L << 24))) return FVAD_ERR_INVALID_ARGUMENT;

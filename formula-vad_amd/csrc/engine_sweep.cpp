@@ -60,7 +60,10 @@ struct DevParts {
     bool rings_in_lds = false;
     int by_config = 0;                   // the lane map of the first part (the rings are laid out by it)
     uint32_t st_max = 1, cr_max = 1;
-    uint64_t next_frame = 0;             // where the next part starts
+    uint64_t next_sample = 0;            // where the next part starts (UINT64_MAX: none can follow)
+    uint64_t* sizes = nullptr;           // several frame sizes (VadMachinesArgs.sized): the sizes, each config's, the lane order
+    uint32_t* size_of = nullptr;
+    int* lane_config = nullptr;
     std::vector<uint8_t> ended;          // streams that got fewer frames than a part's longest
     std::vector<uint32_t> count_h;       // every machine's segment count after the last part
     bool segs_on_device = true;          // every part so far left its segments on the device: they are all in segs
@@ -80,6 +83,32 @@ struct DevParts {
     }
 };
 void free_dev_parts(void* p) { delete static_cast<DevParts*>(p); }
+
+// The lane order of a sized launch by stream (VadMachinesArgs.lane_config): a stream's configs size-major (first-seen order within
+// a size), so that a wavefront mostly runs one frame clock; the caller's order with the context option vad_size_order "caller"
+std::vector<int> lane_order(const fvad_vad_batch* b, const fvad_ctx* ctx)
+{
+    std::vector<int> o(b->cfgs.size());
+    for (size_t c = 0; c < o.size(); ++c) o[c] = (int)c;
+    if (ctx->tune.vad_size_order == 0)
+        std::stable_sort(o.begin(), o.end(), [&](int x, int y) { return b->size_of[(size_t)x] < b->size_of[(size_t)y]; });
+    return o;
+}
+
+// the per-size inputs a launch checks: every (size g, stream s) has n_frames[g * S + s] frames, inside its n_chunks[s] chunks;
+// P[g] = the longest of size g.  FVAD_OK or the message of the broken rule.
+const char* frame_counts(const fvad_vad_batch* b, const size_t* n_frames, const size_t* n_chunks, size_t chunk_size, std::vector<size_t>* P)
+{
+    const size_t S = b->n_streams, G = b->sizes.size();
+    P->assign(G, 0);
+    for (size_t g = 0; g < G; ++g)
+        for (size_t s = 0; s < S; ++s) {
+            const size_t nf = n_frames[g * S + s];
+            if (nf > (n_chunks[s] * chunk_size) / b->sizes[g]) return "a frame without its chunk's ratio";
+            (*P)[g] = std::max((*P)[g], nf);
+        }
+    return nullptr;
+}
 
 // every machine of b against its stream's labels on the device (kernels_eval.hip): segment i of machine m at d_segs[m * cap + i],
 // d_count[m] of them (at most cap); the scores come back into *out
@@ -189,37 +218,61 @@ int fvad_engine_band_sums_device(fvad_ctx* ctx, const float* d_denoised, size_t 
     return FVAD_OK;
 }
 
-int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
-                              const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size)
+} // extern "C"
+
+namespace {
+
+// the configs' derived constants at their own frame sizes, with their bands; the rings' largest lengths
+int derive_cfgs(fvad_ctx* ctx, const fvad_vad_batch* b, std::vector<VadMachineCfg>* hc, uint32_t* lt_max, uint32_t* st_max, uint32_t* cr_max)
 {
-    if (!ctx) return no_ctx();
-    if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
-    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, F = b->fft_size;
-    size_t max_nf = 0;
-    for (size_t s = 0; s < S; ++s) {
-        if (n_frames[s] * F > n_chunks[s] * chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a frame without its chunk's ratio");
-        max_nf = std::max(max_nf, n_frames[s]);
+    const size_t NC = b->cfgs.size();
+    hc->resize(NC);
+    *lt_max = *st_max = *cr_max = 1;
+    for (size_t c = 0; c < NC; ++c) {
+        VadMachineCfg& k = (*hc)[c];
+        if (vad_machine_cfg(b->cfgs[c], b->sample_rate, b->sizes[b->size_of[c]], &k)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
+        k.band = b->band_of[c];
+        *lt_max = std::max(*lt_max, k.long_len);
+        *st_max = std::max(*st_max, k.short_len);
+        *cr_max = std::max(*cr_max, k.ratio_len);
     }
+    return FVAD_OK;
+}
+
+// the frame ratios of every (size g, stream s) row, ratio_stride apart (they do not depend on the config), from frame
+// first_sample / F of the size on
+std::vector<float> sized_ratios(const fvad_vad_batch* b, const size_t* n_frames, const float* chunk_rms, size_t rms_stride,
+                                const size_t* n_chunks, size_t chunk_size, uint64_t first_sample, size_t ratio_stride)
+{
+    const size_t S = b->n_streams, C = b->n_channels;
+    std::vector<float> ratio(b->sizes.size() * S * ratio_stride, 0.0f);
+    deal(b->sizes.size() * S, 16, [&](size_t i) {
+        const size_t s = i % S, F = b->sizes[i / S];
+        sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[i], F, chunk_size, ratio.data() + i * ratio_stride,
+                           first_sample / F);
+    });
+    return ratio;
+}
+
+// one launch of every machine of b (fvad_vad_batch_run_device and _run_device_sized); n_frames [n_sizes][n_streams]
+int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+               const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size)
+{
+    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, G = b->sizes.size();
+    std::vector<size_t> P;
+    if (const char* msg = frame_counts(b, n_frames, n_chunks, chunk_size, &P)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, msg);
+    const size_t max_nf = *std::max_element(P.begin(), P.end());
     if (band_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     b->dev_parts.reset(); // a run in parts cannot go on after this one
 
-    // ---- host: the frame ratios (one per stream: they do not depend on the config) and the configs' derived constants
+    // ---- host: the frame ratios (one row per (size, stream)) and the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
-    std::vector<float> ratio(S * ratio_stride, 0.0f);
-    deal(S, 16, [&](size_t s) {
-        sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[s], F, chunk_size, ratio.data() + s * ratio_stride);
-    });
-    std::vector<VadMachineCfg> hc(NC);
-    uint32_t lt_max = 1, st_max = 1, cr_max = 1;
-    for (size_t c = 0; c < NC; ++c) {
-        if (vad_machine_cfg(b->cfgs[c], b->sample_rate, F, &hc[c])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
-        hc[c].band = b->band_of[c];
-        lt_max = std::max(lt_max, hc[c].long_len);
-        st_max = std::max(st_max, hc[c].short_len);
-        cr_max = std::max(cr_max, hc[c].ratio_len);
-    }
+    const std::vector<float> ratio = sized_ratios(b, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, 0, ratio_stride);
+    std::vector<VadMachineCfg> hc;
+    uint32_t lt_max, st_max, cr_max;
+    if (const int rc = derive_cfgs(ctx, b, &hc, &lt_max, &st_max, &cr_max)) return rc;
 
     // ---- device
     const long M = (long)(S * NC);
@@ -232,10 +285,10 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     uint32_t* d_count = nullptr;
     fvad_vad_audit* d_audit = nullptr;
     unsigned long long* d_stats = nullptr;
-    std::vector<long> nf_l(n_frames, n_frames + S);
+    std::vector<long> nf_l(n_frames, n_frames + G * S);
     FVAD_HIP(ctx, scratch.alloc(&d_cfg, NC));
     FVAD_HIP(ctx, scratch.alloc(&d_ratio, ratio.size()));
-    FVAD_HIP(ctx, scratch.alloc(&d_nf, S));
+    FVAD_HIP(ctx, scratch.alloc(&d_nf, G * S));
     // long-term rings in whole blocks of 64 slots plus one block (the exact chain loads one block ahead, past long_len)
     FVAD_HIP(ctx, scratch.alloc(&d_lt, (((size_t)lt_max + 63) / 64 + 1) * 64 * (size_t)M));
     // the short-term and channel-ratio rings of a workgroup's 64 machines in LDS when they fit in 48 KB, else in global memory
@@ -246,7 +299,7 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     FVAD_HIP(ctx, scratch.alloc(&d_stats, 2 * (size_t)M));
     FVAD_HIP(ctx, hipMemcpyAsync(d_cfg, hc.data(), NC * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
     FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), S * sizeof(long), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), G * S * sizeof(long), hipMemcpyHostToDevice, st));
 
     VadMachinesArgs a{};
     a.cfgs = d_cfg;
@@ -261,7 +314,7 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     a.ratio = d_ratio;
     a.ratio_stride = (long)ratio_stride;
     a.n_frames = d_nf;
-    a.fft_size = F;
+    a.fft_size = b->fft_size;
     a.lt_rings = d_lt;
     a.rings = d_rings;
     a.rings_in_lds = rings_in_lds ? 1 : 0;
@@ -270,12 +323,30 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     a.seg_count = d_count;
     a.audits = d_audit;
     a.stats = d_stats;
+    if (G > 1) { // several frame clocks: the sized form of the kernel (one size runs the single-size form, as a create_sweep batch)
+        uint64_t* d_sizes = nullptr;
+        uint32_t* d_size_of = nullptr;
+        int* d_order = nullptr;
+        const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
+        const std::vector<int> order = lane_order(b, ctx);
+        FVAD_HIP(ctx, scratch.alloc(&d_sizes, G));
+        FVAD_HIP(ctx, scratch.alloc(&d_size_of, NC));
+        FVAD_HIP(ctx, scratch.alloc(&d_order, NC));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_size_of, b->size_of.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_order, order.data(), NC * sizeof(int), hipMemcpyHostToDevice, st));
+        a.sized = 1;
+        a.sizes = d_sizes;
+        a.size_of = d_size_of;
+        a.lane_config = d_order;
+        a.first_sample = 0;
+    }
     // Segment room.  A machine closes a segment only in a CLOSING -> CLOSED step, and the steps since the previous one include a
     // CLOSED -> OPENING, an OPENING -> OPEN and an OPEN -> CLOSING step, one transition per frame (VADMachine.zig:189-233): at most
-    // one segment per 4 frames, n_frames / 4 + 1 bounds every machine.  That bound is the room of the first launch when it is
-    // small; otherwise the first launch has room for 512 MB of segments over all machines (context option vad_seg_cap: that many
-    // per machine instead) and counts past it, and if any machine closed more, a second launch with room for the largest count
-    // redoes the run (the machines start fresh in every launch: same results).
+    // one segment per 4 frames, n_frames / 4 + 1 bounds every machine (the largest over the sizes).  That bound is the room of the
+    // first launch when it is small; otherwise the first launch has room for 512 MB of segments over all machines (context option
+    // vad_seg_cap: that many per machine instead) and counts past it, and if any machine closed more, a second launch with room for
+    // the largest count redoes the run (the machines start fresh in every launch: same results).
     const size_t bound = max_nf / 4 + 1;
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
                                                   : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / (size_t)M);
@@ -330,62 +401,47 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
     b->scored = b->has_refs;
     if (b->has_refs) b->scores = std::move(scores);
     b->machines.clear(); // nothing to continue from: a later fvad_vad_batch_run_part must start at frame 0
-    b->next_frame = 0;
+    b->next_sample = 0;
     return FVAD_OK;
 }
 
-size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)
+// one part of every machine of b (fvad_vad_batch_run_device_part and _run_device_part_sized); n_frames [n_sizes][n_streams],
+// frames from sample first_sample on
+int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                    const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size, uint64_t first_sample)
 {
-    const DevParts* dp = b ? static_cast<const DevParts*>(b->dev_parts.get()) : nullptr;
-    if (!dp) return 0;
-    return dp->bytes + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
-}
-
-int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
-                                   const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
-                                   uint64_t first_frame)
-{
-    if (!ctx) return no_ctx();
-    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
-    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, F = b->fft_size;
+    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, G = b->sizes.size();
     const size_t M = S * NC;
-    size_t P = 0; // the part's longest stream: a stream with fewer frames has ended
-    for (size_t s = 0; s < S; ++s) {
-        if (n_frames[s] * F > n_chunks[s] * chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a frame without its chunk's ratio");
-        P = std::max(P, n_frames[s]);
-    }
-    if (P && (!d_band || !chunk_rms)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
-    if (band_stride < P) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
-    if ((first_frame * F) % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
+    std::vector<size_t> P; // each size's longest stream in the part: a stream with fewer frames of some size has ended
+    if (const char* msg = frame_counts(b, n_frames, n_chunks, chunk_size, &P)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, msg);
+    const size_t max_nf = *std::max_element(P.begin(), P.end());
+    if (max_nf && (!d_band || !chunk_rms)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (band_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
+    if (first_sample % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
+    for (size_t g = 0; g < G; ++g)
+        if (first_sample % b->sizes[g]) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a frame of every size");
     DevParts* dp = static_cast<DevParts*>(b->dev_parts.get());
-    if (first_frame != 0) {
+    if (first_sample != 0) {
         if (!dp) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no device part to continue (a host run or a one-shot device run came between)");
         if (dp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the parts of a run are on one context");
-        if (first_frame != dp->next_frame) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts where the previous one ended");
-        for (size_t s = 0; s < S; ++s)
-            if (dp->ended[s] && (n_frames[s] || n_chunks[s])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "frames for a stream that has ended");
+        if (first_sample != dp->next_sample) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts where the previous one ended");
+        for (size_t s = 0; s < S; ++s) {
+            bool any = n_chunks[s] != 0;
+            for (size_t g = 0; g < G; ++g) any = any || n_frames[g * S + s] != 0;
+            if (dp->ended[s] && any) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "frames for a stream that has ended");
+        }
     }
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
 
     // ---- host: the part's frame ratios and, for a fresh run, the configs' derived constants
-    const size_t ratio_stride = std::max<size_t>(P, 1);
-    std::vector<float> ratio(S * ratio_stride, 0.0f);
-    deal(S, 16, [&](size_t s) {
-        sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[s], F, chunk_size, ratio.data() + s * ratio_stride,
-                           first_frame);
-    });
-    if (first_frame == 0) { // fresh machines: the state of an earlier run is dropped
+    const size_t ratio_stride = std::max<size_t>(max_nf, 1);
+    const std::vector<float> ratio = sized_ratios(b, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, ratio_stride);
+    if (first_sample == 0) { // fresh machines: the state of an earlier run is dropped
         b->dev_parts.reset();
-        std::vector<VadMachineCfg> hc(NC);
-        uint32_t lt_max = 1, st_max = 1, cr_max = 1;
-        for (size_t c = 0; c < NC; ++c) {
-            if (vad_machine_cfg(b->cfgs[c], b->sample_rate, F, &hc[c])) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
-            hc[c].band = b->band_of[c];
-            lt_max = std::max(lt_max, hc[c].long_len);
-            st_max = std::max(st_max, hc[c].short_len);
-            cr_max = std::max(cr_max, hc[c].ratio_len);
-        }
+        std::vector<VadMachineCfg> hc;
+        uint32_t lt_max, st_max, cr_max;
+        if (const int rc = derive_cfgs(ctx, b, &hc, &lt_max, &st_max, &cr_max)) return rc;
         std::unique_ptr<DevParts> fresh(new (std::nothrow) DevParts());
         if (!fresh) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
         dp = fresh.get();
@@ -406,6 +462,16 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
         FVAD_HIP(ctx, dp->alloc(&dp->stats, 2 * M));
         FVAD_HIP(ctx, dp->alloc(&dp->paused, 1));
         FVAD_HIP(ctx, hipMemcpyAsync(dp->cfg, hc.data(), NC * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
+        if (G > 1) { // the sized form's tables; the lane order is the first part's (the rings are laid out by it)
+            const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
+            const std::vector<int> order = lane_order(b, ctx);
+            FVAD_HIP(ctx, dp->alloc(&dp->sizes, G));
+            FVAD_HIP(ctx, dp->alloc(&dp->size_of, NC));
+            FVAD_HIP(ctx, dp->alloc(&dp->lane_config, NC));
+            FVAD_HIP(ctx, hipMemcpyAsync(dp->sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            FVAD_HIP(ctx, hipMemcpyAsync(dp->size_of, b->size_of.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            FVAD_HIP(ctx, hipMemcpyAsync(dp->lane_config, order.data(), NC * sizeof(int), hipMemcpyHostToDevice, st));
+        }
         dp->ended.assign(S, 0);
         dp->count_h.assign(M, 0);
         b->dev_parts = std::unique_ptr<void, DevPartsDeleter>(fresh.release(), DevPartsDeleter{free_dev_parts});
@@ -414,28 +480,30 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
     b->machines.clear(); // a host part cannot go on from a device part
     const bool keep = b->keep_segments;
     dp->segs_on_device = dp->segs_on_device && !keep;
-    dp->next_frame = UINT64_MAX; // (until this part has run: after an error the run starts again at frame 0)
+    dp->next_sample = UINT64_MAX; // (until this part has run: after an error the run starts again at sample 0)
 
     // ---- device: the part's per-call inputs
     DevScratch scratch;
     float* d_ratio = nullptr;
     long* d_nf = nullptr;
-    std::vector<long> nf_l(n_frames, n_frames + S);
+    std::vector<long> nf_l(n_frames, n_frames + G * S);
     FVAD_HIP(ctx, scratch.alloc(&d_ratio, ratio.size()));
-    FVAD_HIP(ctx, scratch.alloc(&d_nf, S));
+    FVAD_HIP(ctx, scratch.alloc(&d_nf, G * S));
     FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), S * sizeof(long), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), G * S * sizeof(long), hipMemcpyHostToDevice, st));
 
-    // Segment room: at most one segment per 4 frames (fvad_vad_batch_run_device).  A part that keeps its segments writes them
-    // from the start of the buffer (the earlier ones are on the host); otherwise the buffer holds every segment since the first
-    // part.  The buffer has room for at least the part's bound or the one-shot's first room (context option vad_seg_cap, else
-    // 512 MB over all machines), whichever is less; a machine that fills it stops before its next frame, the room doubles (the
-    // contents kept, never past what the frames allow) and the part goes on from there.  So the room follows the segments,
-    // not the length of the run.
-    const size_t most = keep ? P / 4 + 1 : (size_t)((first_frame + P) / 4 + 1);
+    // Segment room: at most one segment per 4 frames (fvad_vad_batch_run_device), the largest bound over the sizes.  A part that
+    // keeps its segments writes them from the start of the buffer (the earlier ones are on the host); otherwise the buffer holds
+    // every segment since the first part.  The buffer has room for at least the part's bound or the one-shot's first room
+    // (context option vad_seg_cap, else 512 MB over all machines), whichever is less; a machine that fills it stops before its
+    // next frame, the room doubles (the contents kept, never past what the frames allow) and the part goes on from there.  So the
+    // room follows the segments, not the length of the run.
+    size_t most = 0;
+    for (size_t g = 0; g < G; ++g)
+        most = std::max(most, keep ? P[g] / 4 + 1 : (size_t)((first_sample / b->sizes[g] + P[g]) / 4 + 1));
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
                                                   : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / M);
-    const size_t first_room = std::min(P / 4 + 1, room);
+    const size_t first_room = std::min(max_nf / 4 + 1, room);
     auto grow = [&](size_t cap) -> int { // the buffer with room for cap segments per machine, the old contents kept
         fvad_speech_segment* d = nullptr;
         FVAD_HIP(ctx, hipMalloc((void**)&d, std::max<size_t>(cap * M, 1) * sizeof(fvad_speech_segment)));
@@ -468,7 +536,7 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
     a.ratio = d_ratio;
     a.ratio_stride = (long)ratio_stride;
     a.n_frames = d_nf;
-    a.fft_size = F;
+    a.fft_size = b->fft_size;
     a.lt_rings = dp->lt;
     a.rings = dp->rings;
     a.rings_in_lds = dp->rings_in_lds ? 1 : 0;
@@ -478,11 +546,18 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
     a.audits = dp->audit;
     a.stats = dp->stats;
     a.resume = 1;
-    a.fresh = first_frame == 0;
+    a.fresh = first_sample == 0;
     a.rebase = keep;
-    a.first_frame = first_frame;
+    a.first_frame = first_sample / b->fft_size;
     a.state = dp->state;
     a.paused = dp->paused;
+    if (G > 1) {
+        a.sized = 1;
+        a.sizes = dp->sizes;
+        a.size_of = dp->size_of;
+        a.lane_config = dp->lane_config;
+        a.first_sample = first_sample;
+    }
     for (;;) {
         unsigned paused = 0;
         a.segs = dp->segs;
@@ -524,7 +599,7 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
         }
     }
     FVAD_HIP(ctx, hipGetLastError());
-    const bool all_kept = keep && (first_frame == 0 || b->segs_kept);
+    const bool all_kept = keep && (first_sample == 0 || b->segs_kept);
     for (size_t m = 0; m < M; ++m) {
         auto& v = b->segs[m];
         if (all_kept) {
@@ -538,12 +613,64 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
     }
     b->audits = std::move(audits);
     dp->count_h = std::move(count);
-    for (size_t s = 0; s < S; ++s)
-        if (n_frames[s] < P) dp->ended[s] = 1;
-    dp->next_frame = first_frame + P;
+    for (size_t g = 0; g < G; ++g)
+        for (size_t s = 0; s < S; ++s)
+            if (n_frames[g * S + s] < P[g]) dp->ended[s] = 1;
+    uint64_t next = first_sample + P[0] * b->sizes[0];
+    for (size_t g = 1; g < G; ++g)
+        if (first_sample + P[g] * b->sizes[g] != next) next = UINT64_MAX; // (the sizes ended apart: no part can follow)
+    dp->next_sample = next;
     b->segs_kept = all_kept;
     b->scored = false; // the scores were of the previous segments
     return FVAD_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                              const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->sizes.size() != 1) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "several frame sizes: fvad_vad_batch_run_device_sized");
+    return run_device(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size);
+}
+
+int fvad_vad_batch_run_device_sized(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                    const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    return run_device(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size);
+}
+
+size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)
+{
+    const DevParts* dp = b ? static_cast<const DevParts*>(b->dev_parts.get()) : nullptr;
+    if (!dp) return 0;
+    return dp->bytes + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
+}
+
+int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                   const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                                   uint64_t first_frame)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->sizes.size() != 1) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "several frame sizes: fvad_vad_batch_run_device_part_sized");
+    if (first_frame > UINT64_MAX / b->fft_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "first_frame out of range");
+    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_frame * b->fft_size);
+}
+
+int fvad_vad_batch_run_device_part_sized(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                         const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                                         uint64_t first_sample)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample);
 }
 
 int fvad_vad_batch_score_device(fvad_ctx* ctx, fvad_vad_batch* b)

@@ -374,6 +374,7 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
     const float bin_width = (float)sample_rate / (float)fft_size;
     b->bins = {(int32_t)roundf(cfg->speech_min_freq / bin_width), (int32_t)roundf(cfg->speech_max_freq / bin_width)};
     b->band_of.assign(1, 0);
+    b->sizes.assign(1, fft_size); b->size_of.assign(1, 0); b->size_of_band.assign(1, 0);
     b->segs.resize(n_streams);
     b->audits.resize(n_streams);
     b->exact_evals.assign(n_streams, 0);
@@ -397,32 +398,77 @@ static int check_sweep_config(const fvad_vad_config& c, size_t sample_rate, size
     return fvad::vad_machine_cfg(c, sample_rate, fft_size, &k);
 }
 
-int fvad_vad_batch_create_sweep(const fvad_vad_config* cfgs, size_t n_configs, size_t sample_rate, size_t n_channels, size_t fft_size,
-                                size_t n_streams, fvad_vad_batch** out)
+// The bands of configs cfgs[c] at frame sizes sizes[size_of[c]]: a band is (size, min bin, max bin); bands size-major, first-seen
+// config order within a size.  The configs are checked at their own sizes.
+static int make_sweep(const fvad_vad_config* cfgs, size_t n_configs, const std::vector<size_t>& sizes, const std::vector<uint32_t>& size_of,
+                      size_t sample_rate, size_t n_channels, size_t n_streams, fvad_vad_batch** out)
 {
-    if (!cfgs || !out || n_configs == 0 || n_channels == 0 || fft_size == 0 || sample_rate == 0 || n_streams == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    std::vector<int32_t> bins;
-    std::vector<uint32_t> band_of(n_configs);
+    std::vector<std::vector<int32_t>> bins(sizes.size()); // per size, first-seen order
+    std::vector<uint32_t> local(n_configs);
     for (size_t c = 0; c < n_configs; ++c) {
         int32_t lo = 0, hi = 0;
-        const int rc = check_sweep_config(cfgs[c], sample_rate, fft_size, &lo, &hi);
+        const int rc = check_sweep_config(cfgs[c], sample_rate, sizes[size_of[c]], &lo, &hi);
         if (rc) return rc;
-        size_t j = 0; // distinct bands in first-seen order
-        while (j < bins.size() / 2 && !(bins[2 * j] == lo && bins[2 * j + 1] == hi)) ++j;
-        if (j == bins.size() / 2) { bins.push_back(lo); bins.push_back(hi); }
-        band_of[c] = (uint32_t)j;
+        std::vector<int32_t>& bg = bins[size_of[c]];
+        size_t j = 0;
+        while (j < bg.size() / 2 && !(bg[2 * j] == lo && bg[2 * j + 1] == hi)) ++j;
+        if (j == bg.size() / 2) { bg.push_back(lo); bg.push_back(hi); }
+        local[c] = (uint32_t)j;
     }
     auto* b = new (std::nothrow) fvad_vad_batch();
     if (!b) return FVAD_ERR_ALLOC_FAILED;
-    b->cfgs.assign(cfgs, cfgs + n_configs); b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = fft_size;
+    std::vector<uint32_t> first(sizes.size()); // each size's first band
+    for (size_t g = 0; g < sizes.size(); ++g) {
+        first[g] = (uint32_t)(b->bins.size() / 2);
+        b->bins.insert(b->bins.end(), bins[g].begin(), bins[g].end());
+        b->size_of_band.insert(b->size_of_band.end(), bins[g].size() / 2, (uint32_t)g);
+    }
+    b->band_of.resize(n_configs);
+    for (size_t c = 0; c < n_configs; ++c) b->band_of[c] = first[size_of[c]] + local[c];
+    b->cfgs.assign(cfgs, cfgs + n_configs); b->sample_rate = sample_rate; b->n_channels = n_channels; b->fft_size = sizes[0];
     b->n_streams = n_streams;
-    b->bins = std::move(bins);
-    b->band_of = std::move(band_of);
+    b->sizes = sizes;
+    b->size_of = size_of;
     b->segs.resize(n_streams * n_configs);
     b->audits.resize(n_streams * n_configs);
     b->exact_evals.assign(n_streams * n_configs, 0);
     b->lazy_pushes.assign(n_streams * n_configs, 0);
     *out = b;
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_create_sweep(const fvad_vad_config* cfgs, size_t n_configs, size_t sample_rate, size_t n_channels, size_t fft_size,
+                                size_t n_streams, fvad_vad_batch** out)
+{
+    if (!cfgs || !out || n_configs == 0 || n_channels == 0 || fft_size == 0 || sample_rate == 0 || n_streams == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    return make_sweep(cfgs, n_configs, {fft_size}, std::vector<uint32_t>(n_configs, 0), sample_rate, n_channels, n_streams, out);
+}
+
+int fvad_vad_batch_create_sweep_sized(const fvad_vad_config* cfgs, const size_t* fft_sizes, size_t n_configs, size_t sample_rate,
+                                      size_t n_channels, size_t n_streams, fvad_vad_batch** out)
+{
+    if (!cfgs || !fft_sizes || !out || n_configs == 0 || n_channels == 0 || sample_rate == 0 || n_streams == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    std::vector<size_t> sizes; // distinct, first-seen order
+    std::vector<uint32_t> size_of(n_configs);
+    for (size_t c = 0; c < n_configs; ++c) {
+        const size_t F = fft_sizes[c];
+        if (F < 4 || F > 16384 || F % 2) return FVAD_ERR_INVALID_ARGUMENT; // (fvad_engine_band_sums_device's sizes)
+        size_t g = 0;
+        while (g < sizes.size() && sizes[g] != F) ++g;
+        if (g == sizes.size()) sizes.push_back(F);
+        size_of[c] = (uint32_t)g;
+    }
+    return make_sweep(cfgs, n_configs, sizes, size_of, sample_rate, n_channels, n_streams, out);
+}
+
+int fvad_vad_batch_frame_sizes(const fvad_vad_batch* b, size_t* sizes, size_t cap, size_t* n_sizes, uint32_t* size_of_band)
+{
+    if (!b || !n_sizes) return FVAD_ERR_INVALID_ARGUMENT;
+    *n_sizes = b->sizes.size();
+    if (size_of_band) memcpy(size_of_band, b->size_of_band.data(), b->size_of_band.size() * sizeof(uint32_t));
+    if (cap < *n_sizes) return FVAD_ERR_BUFFER_TOO_SMALL;
+    if (!sizes) return FVAD_ERR_INVALID_ARGUMENT;
+    memcpy(sizes, b->sizes.data(), b->sizes.size() * sizeof(size_t));
     return FVAD_OK;
 }
 
@@ -489,66 +535,104 @@ void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t C, siz
 
 extern "C" {
 
-int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_stride, size_t n_frames, const float* chunk_rms,
-                            size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_frame, int n_threads)
+} // extern "C"
+
+// Every machine of b over frames of its own size: n_frames[g] frames of size g from sample first_sample on (every stream the same
+// length), band blocks as fvad_vad_batch_bands lists them.  The part rules are fvad_vad_batch_run_part's, in samples.
+static int run_host(fvad_vad_batch* b, const float* band, size_t band_stride, const size_t* n_frames, const float* chunk_rms,
+                    size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_sample, int n_threads)
 {
-    if (!b || (n_frames && !band) || (n_chunks && !chunk_rms) || chunk_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    const size_t NC = b->cfgs.size();
-    // parts follow each other without gaps, and a part starts where a chunk starts (its first chunk is chunk_rms' first column)
-    if (first_frame != 0 && (first_frame != b->next_frame || b->machines.size() != b->n_streams * NC)) return FVAD_ERR_INVALID_ARGUMENT;
-    if ((first_frame * b->fft_size) % chunk_size) return FVAD_ERR_INVALID_ARGUMENT;
-    const uint64_t first_chunk = first_frame * b->fft_size / chunk_size;
-    if ((first_frame + n_frames) * b->fft_size > (first_chunk + n_chunks) * chunk_size) return FVAD_ERR_INVALID_ARGUMENT; // a frame without its chunk's ratio
+    const size_t NC = b->cfgs.size(), G = b->sizes.size();
+    // parts follow each other without gaps, and a part starts where a chunk and a frame of every size start (its first chunk is
+    // chunk_rms' first column)
+    if (first_sample != 0 && (first_sample != b->next_sample || b->machines.size() != b->n_streams * NC)) return FVAD_ERR_INVALID_ARGUMENT;
+    if (first_sample % chunk_size) return FVAD_ERR_INVALID_ARGUMENT;
+    for (size_t g = 0; g < G; ++g) {
+        if (first_sample % b->sizes[g]) return FVAD_ERR_INVALID_ARGUMENT;
+        if (n_frames[g] * b->sizes[g] > n_chunks * chunk_size) return FVAD_ERR_INVALID_ARGUMENT; // a frame without its chunk's ratio
+    }
+    const uint64_t first_chunk = first_sample / chunk_size;
     const size_t C = b->n_channels, n_lanes = b->n_streams * C;
-    if (first_frame == 0) { // fresh machines (VADMachine.init per pipeline, VADPipeline.zig:60-75); machine s * NC + c
+    if (first_sample == 0) { // fresh machines (VADMachine.init per pipeline, VADPipeline.zig:60-75); machine s * NC + c
         b->dev_parts.reset(); // (a device run in parts cannot go on after a host run)
         b->machines.clear();
         for (size_t s = 0; s < b->n_streams; ++s)
-            for (size_t c = 0; c < NC; ++c) b->machines.emplace_back(new fvad::VadMachine(b->cfgs[c], b->sample_rate, C, b->fft_size));
+            for (size_t c = 0; c < NC; ++c)
+                b->machines.emplace_back(new fvad::VadMachine(b->cfgs[c], b->sample_rate, C, b->sizes[b->size_of[c]]));
     }
     auto run_machine = [&](size_t s, size_t c, const float* ratio, const uint8_t* has) {
         fvad::VadMachine& m = *b->machines[s * NC + c];
+        const size_t F = b->sizes[b->size_of[c]], nf = n_frames[b->size_of[c]];
+        const uint64_t first_frame = first_sample / F;
         const float* bb = band + ((size_t)b->band_of[c] * n_lanes + s * C) * band_stride; // config c's band block, stream s's lanes
         std::vector<float> vols(C);
-        for (size_t f = 0; f < n_frames; ++f) {
+        for (size_t f = 0; f < nf; ++f) {
             for (size_t ch = 0; ch < C; ++ch) vols[ch] = bb[ch * band_stride + f];
-            m.run((first_frame + f) * b->fft_size, vols.data(), has[f] != 0, ratio[f]);
+            m.run((first_frame + f) * F, vols.data(), has[f] != 0, ratio[f]);
         }
         b->segs[s * NC + c] = m.segments; // (everything so far: a segment is appended when it closes)
         b->audits[s * NC + c] = m.audit;
         b->exact_evals[s * NC + c] = m.exact_evals;
         b->lazy_pushes[s * NC + c] = m.lazy_pushes;
     };
-    auto stream_ratios = [&](size_t s, float* out, uint8_t* has) {
-        fvad::frame_ratios([&](size_t c, size_t k) { return chunk_rms[(s * C + c) * rms_stride + k]; }, C, n_chunks, n_frames, first_frame,
-                           first_chunk, b->fft_size, chunk_size, out, has);
+    auto stream_ratios = [&](size_t g, size_t s, float* out, uint8_t* has) {
+        const size_t F = b->sizes[g];
+        fvad::frame_ratios([&](size_t c, size_t k) { return chunk_rms[(s * C + c) * rms_stride + k]; }, C, n_chunks, n_frames[g],
+                           first_sample / F, first_chunk, F, chunk_size, out, has);
     };
     if (NC == 1) {
         // one machine per stream: a stream's frame ratios and its machine on the same thread
         fvad::deal(b->n_streams, n_threads, [&](size_t s) {
-            std::vector<float> ratio(n_frames);
-            std::vector<uint8_t> has(n_frames);
-            stream_ratios(s, ratio.data(), has.data());
+            std::vector<float> ratio(n_frames[0]);
+            std::vector<uint8_t> has(n_frames[0]);
+            stream_ratios(0, s, ratio.data(), has.data());
             run_machine(s, 0, ratio.data(), has.data());
         });
     } else {
-        // a sweep: the frame ratios of every stream (they do not depend on the config), then every (stream, config) machine
-        std::vector<float> ratio(b->n_streams * n_frames);
-        std::vector<uint8_t> has(b->n_streams * n_frames);
-        fvad::deal(b->n_streams, n_threads, [&](size_t s) { stream_ratios(s, ratio.data() + s * n_frames, has.data() + s * n_frames); });
-        fvad::deal(b->n_streams * NC, n_threads,
-                   [&](size_t i) { run_machine(i / NC, i % NC, ratio.data() + (i / NC) * n_frames, has.data() + (i / NC) * n_frames); });
+        // a sweep: the frame ratios of every (size, stream) (they do not depend on the config), then every (stream, config) machine
+        size_t rs = 0;
+        for (size_t g = 0; g < G; ++g) rs = std::max(rs, n_frames[g]);
+        const size_t S = b->n_streams;
+        std::vector<float> ratio(G * S * rs);
+        std::vector<uint8_t> has(G * S * rs);
+        fvad::deal(G * S, n_threads, [&](size_t i) { stream_ratios(i / S, i % S, ratio.data() + i * rs, has.data() + i * rs); });
+        fvad::deal(S * NC, n_threads, [&](size_t i) {
+            const size_t row = ((size_t)b->size_of[i % NC] * S + i / NC) * rs;
+            run_machine(i / NC, i % NC, ratio.data() + row, has.data() + row);
+        });
     }
-    b->next_frame = first_frame + n_frames;
+    b->next_sample = first_sample + n_frames[0] * b->sizes[0];
+    for (size_t g = 1; g < G; ++g)
+        if (first_sample + n_frames[g] * b->sizes[g] != b->next_sample) b->next_sample = UINT64_MAX; // (the sizes ended apart)
     b->segs_kept = true;
     b->scored = false; // the scores were of the previous segments
     return FVAD_OK;
+}
+
+extern "C" {
+
+int fvad_vad_batch_run_part(fvad_vad_batch* b, const float* band, size_t band_stride, size_t n_frames, const float* chunk_rms,
+                            size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_frame, int n_threads)
+{
+    if (!b || (n_frames && !band) || (n_chunks && !chunk_rms) || chunk_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    if (b->sizes.size() != 1) return FVAD_ERR_INVALID_ARGUMENT; // (several frame sizes: fvad_vad_batch_run_sized)
+    if (first_frame > UINT64_MAX / b->fft_size) return FVAD_ERR_INVALID_ARGUMENT;
+    return run_host(b, band, band_stride, &n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_frame * b->fft_size, n_threads);
 }
 
 int fvad_vad_batch_run(fvad_vad_batch* b, const float* band, size_t band_stride, size_t n_frames, const float* chunk_rms,
                        size_t rms_stride, size_t n_chunks, size_t chunk_size, int n_threads)
 {
     return fvad_vad_batch_run_part(b, band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, 0, n_threads);
+}
+
+int fvad_vad_batch_run_sized(fvad_vad_batch* b, const float* band, size_t band_stride, const size_t* n_frames, const float* chunk_rms,
+                             size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_sample, int n_threads)
+{
+    if (!b || !n_frames || (n_chunks && !chunk_rms) || chunk_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    for (size_t g = 0; g < b->sizes.size(); ++g)
+        if ((n_frames[g] && !band) || band_stride < n_frames[g]) return FVAD_ERR_INVALID_ARGUMENT;
+    return run_host(b, band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, n_threads);
 }
 
 size_t fvad_vad_batch_total_segments(const fvad_vad_batch* b) // (config 0's on a sweep batch)

@@ -87,15 +87,19 @@ struct DevPartsDeleter {
 // fvad_vad_batch_create has one config.  Segments and audits of the last run, machine by machine.
 struct fvad_vad_batch {
     std::vector<fvad_vad_config> cfgs;
-    std::vector<int32_t> bins;      // distinct speech bands (min, max bin), first-seen order
+    std::vector<int32_t> bins;      // distinct speech bands (min, max bin): size-major, first-seen order within a size
     std::vector<uint32_t> band_of;  // band of each config
-    size_t sample_rate, n_channels, fft_size, n_streams;
+    size_t sample_rate, n_channels, fft_size, n_streams; // (fft_size: sizes[0])
+    // frame sizes (fvad_vad_batch_create_sweep_sized): the distinct sizes in first-seen config order, the size index of each
+    // config and of each band; one size, all indices 0, for the other batches
+    std::vector<size_t> sizes;
+    std::vector<uint32_t> size_of, size_of_band;
     std::vector<std::vector<fvad_speech_segment>> segs;
     std::vector<fvad_vad_audit> audits;
     std::vector<uint64_t> exact_evals, lazy_pushes; // exact evaluations of the long-term chain / lazily absorbed pushes per machine
     // a run in parts (fvad_vad_batch_run_part): the streams' machines live on between the parts
     std::vector<std::unique_ptr<fvad::VadMachine>> machines;
-    uint64_t next_frame = 0;
+    uint64_t next_sample = 0; // where the next host part starts, in samples (UINT64_MAX: the sizes' parts ended apart, none can follow)
     // a run in parts on the GPU (fvad_vad_batch_run_device_part): the machines' state in device memory between the parts
     std::unique_ptr<void, fvad::DevPartsDeleter> dev_parts;
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends

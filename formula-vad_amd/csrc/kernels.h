@@ -242,6 +242,16 @@ struct VadMachinesArgs {
     uint64_t first_frame;
     fvad::VadLaneState* state;  // [n_machines], machine = stream * n_configs + config
     unsigned* paused;
+    // ---- several frame sizes in one launch (sized = 1, fvad_vad_batch_create_sweep_sized): config c runs on frames of
+    // sizes[size_of[c]] samples; then n_frames is [n_sizes][n_streams] (size g, stream s at g * n_streams + s), the frame
+    // ratios of (g, s) at ratio + (g * n_streams + s) * ratio_stride, and frame k of a machine is at sample
+    // first_sample + k * F (fft_size and first_frame unused; a machine's next_frame counts frames of its own size).
+    // lane_config (by stream, may be null): lane j of a stream's n_configs runs config lane_config[j]
+    int sized;
+    const uint64_t* sizes;      // [n_sizes] (device)
+    const uint32_t* size_of;    // [n_configs] (device)
+    const int* lane_config;     // [n_configs] (device)
+    uint64_t first_sample;
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
 

@@ -171,7 +171,9 @@ typedef __attribute__((address_space(3))) float lds_float;
 // RINGS_LDS: the short-term and channel-ratio rings in LDS ([st_max + cr_max][64]), else in global memory.
 // RESUME: the machine lives on between launches (a.state, a.rings, a.lt_rings: fvad_vad_batch_run_device_part): it is loaded
 // before the frame loop and stored after it, so that the loop itself is the one-shot form's
-template <bool RINGS_LDS, bool RESUME>
+// SIZED: the machines run on frames of several sizes (a.sized): each lane takes its config's frame size, frame count and ratio
+// row, and by stream a stream's lanes take their configs in a.lane_config's order; the frame loop is the other forms'
+template <bool RINGS_LDS, bool RESUME, bool SIZED = false>
 __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
 {
     extern __shared__ float vad_rings[];
@@ -184,7 +186,11 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     long s;
     int c;
     if (a.by_config) { c = (int)(m / a.n_streams); s = m - (long)c * a.n_streams; }
-    else { s = m / a.n_configs; c = (int)(m - s * a.n_configs); }
+    else {
+        s = m / a.n_configs;
+        c = (int)(m - s * a.n_configs);
+        if constexpr (SIZED) { if (a.lane_config) c = a.lane_config[c]; }
+    }
     const long id = s * a.n_configs + c; // machine index of the outputs
     const VadMachineCfg* cfg = a.cfgs + c;
 
@@ -198,6 +204,16 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     else { rb = a.rings + m; rs = a.n_machines; }
     mc.st = Ring<P>{rb, rs, cfg->short_len, 0, 0, cfg->st_scalar, 0.0};
     mc.cr = Ring<P>{rb + (long)a.st_max * rs, rs, cfg->ratio_len, 0, 0, cfg->cr_scalar, 0.0};
+    // the machine's frame clock: its frame size and the part's first frame in its frames; its (size, stream) row of n_frames
+    // and the frame ratios
+    uint64_t F = a.fft_size, first_frame = a.first_frame;
+    long row = s;
+    if constexpr (SIZED) {
+        const uint32_t g = a.size_of[c];
+        F = a.sizes[g];
+        first_frame = a.first_sample / F;
+        row = (long)g * a.n_streams + s;
+    }
     uint32_t n_segs = 0, seg_base = 0; // (seg_base: the machine's first segment in the buffer)
     long k0 = 0;                       // the part's first frame this launch runs
     if (RESUME && !a.fresh) {          // the machine where the previous launch left it
@@ -209,7 +225,7 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         mc.lt_next = mc.slot(mc.lt_w);
         n_segs = ls.n_segs;
         seg_base = a.rebase ? n_segs : ls.seg_base;
-        k0 = ls.next_frame > a.first_frame ? (long)(ls.next_frame - a.first_frame) : 0;
+        k0 = ls.next_frame > first_frame ? (long)(ls.next_frame - first_frame) : 0;
         if constexpr (RINGS_LDS) { // the rings' home between launches is a.rings, laid out as the global form has them
             for (uint32_t i = 0; i < cfg->short_len; ++i) rb[(long)i * 64] = a.rings[(long)i * a.n_machines + m];
             for (uint32_t i = 0; i < cfg->ratio_len; ++i)
@@ -225,10 +241,10 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         mc.lt_next = mc.slot(0);
     }
 
-    const long nf = a.n_frames[s];
+    const long nf = a.n_frames[row];
     const int C = a.n_channels;
     const float* band = a.band + ((long)cfg->band * a.n_lanes + s * C) * a.band_stride;
-    const float* ratio = a.ratio + s * a.ratio_stride;
+    const float* ratio = a.ratio + row * a.ratio_stride;
     fvad_speech_segment* seg = a.segs + id * (long)a.seg_cap;
     // the next frame's band values (up to kPre channels) and ratio are loaded while this frame runs; the minimum is taken when the
     // frame is run, so that the loads are waited for a frame later (more channels: loaded and reduced at once)
@@ -261,8 +277,9 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         const double cr = mc.cr.push(rt);
         const bool met = mc.decide(mc.cf, st, cr, [&] { mc.lt_exact(); });
         if (!met) mc.lt_push(mv);
-        const uint64_t frame = RESUME ? a.first_frame + (uint64_t)k : (uint64_t)k;
-        mc.finish_step(mc.cf, frame * a.fft_size, met, true, rt, [&](const fvad_speech_segment& sg) {
+        const uint64_t frame = RESUME ? first_frame + (uint64_t)k : (uint64_t)k;
+        const uint64_t sample = SIZED ? a.first_sample + (uint64_t)k * F : frame * F;
+        mc.finish_step(mc.cf, sample, met, true, rt, [&](const fvad_speech_segment& sg) {
             if (n_segs - seg_base < a.seg_cap) seg[n_segs - seg_base] = sg;
             ++n_segs; // counted past the capacity: the caller sees the overflow and runs again with room for all
         });
@@ -275,7 +292,7 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
         ls.lt_w = mc.lt_w; ls.lt_wc = mc.lt_wc; ls.lt_filled = mc.lt_filled; ls.lt_steady = mc.lt_steady ? 1u : 0u;
         ls.n_segs = n_segs;
         ls.seg_base = seg_base;
-        ls.next_frame = a.first_frame + (uint64_t)k_end;
+        ls.next_frame = first_frame + (uint64_t)k_end;
         if constexpr (RINGS_LDS) {
             for (uint32_t i = 0; i < cfg->short_len; ++i) a.rings[(long)i * a.n_machines + m] = rb[(long)i * 64];
             for (uint32_t i = 0; i < cfg->ratio_len; ++i)
@@ -293,7 +310,13 @@ int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream)
     if (a.n_machines <= 0) return (int)hipSuccess;
     const size_t lds = a.rings_in_lds ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0;
     const dim3 grid((unsigned)((a.n_machines + 63) / 64));
-    if (a.resume) {
+    if (a.sized) {
+        if (a.resume) {
+            if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, true, true>), grid, dim3(64), lds, stream, a);
+            else hipLaunchKernelGGL((vad_machines_kernel<false, true, true>), grid, dim3(64), 0, stream, a);
+        } else if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, false, true>), grid, dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((vad_machines_kernel<false, false, true>), grid, dim3(64), 0, stream, a);
+    } else if (a.resume) {
         if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, true>), grid, dim3(64), lds, stream, a);
         else hipLaunchKernelGGL((vad_machines_kernel<false, true>), grid, dim3(64), 0, stream, a);
     } else if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_kernel<true, false>), grid, dim3(64), lds, stream, a);

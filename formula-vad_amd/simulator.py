@@ -539,6 +539,34 @@ def expand_grid(grid):
     return configs
 
 
+FFT_SIZE_MIN, FFT_SIZE_MAX = 4, 16384
+
+
+def expand_grid_sized(grid, plan_fft_size):
+    """A grid that may also carry a top-level "fft_size": [sizes] next to "base" and "axes" (VADPipeline.Config.fft_size beside
+    its vad_machine_config) -> (sizes, configs): sizes[c] is config c's frame size.  The size is the slowest axis: every config
+    of expand_grid(grid without the key) at the first size, then at the second, ...; the product counts against
+    GRID_MAX_CONFIGS.  Sizes are even integers in 4..16384 without duplicates.  Without the key every config runs at
+    plan_fft_size (None: the caller fills it in) and the configs are expand_grid's.  Raises ValueError (before any GPU work)."""
+    if not isinstance(grid, dict) or "fft_size" not in grid:
+        configs = expand_grid(grid)
+        return [plan_fft_size] * len(configs), configs
+    sizes = grid["fft_size"]
+    if not isinstance(sizes, list) or not sizes:
+        raise ValueError(f"grid \"fft_size\" = {sizes!r}: a non-empty list of frame sizes")
+    for f in sizes:
+        if isinstance(f, bool) or not isinstance(f, int) or f < FFT_SIZE_MIN or f > FFT_SIZE_MAX or f % 2:
+            raise ValueError(f"grid \"fft_size\" value {f!r}: a frame size is an even integer in {FFT_SIZE_MIN}..{FFT_SIZE_MAX}")
+    if len(set(sizes)) != len(sizes):
+        raise ValueError(f"grid \"fft_size\" = {sizes}: a size appears twice")
+    base = expand_grid({k: v for k, v in grid.items() if k != "fft_size"})
+    n = len(sizes) * len(base)
+    if n > GRID_MAX_CONFIGS:
+        raise ValueError(f"the grid has {n} configs ({len(sizes)} fft_size values x {len(base)}), more than "
+                         f"GRID_MAX_CONFIGS = {GRID_MAX_CONFIGS}")
+    return [f for f in sizes for _ in base], [dict(c) for _ in sizes for c in base]
+
+
 def _ranked(rows):
     """rows by aggregate F-score, highest first (NaN last), ties by config index"""
     return sorted(rows, key=lambda r: (0, -r["F"], r["config"]) if r["F"] == r["F"] else (1, 0.0, r["config"]))
@@ -556,6 +584,17 @@ def check_slice_chunks(slice_chunks, fft_size):
     if isinstance(slice_chunks, bool) or not isinstance(slice_chunks, (int, np.integer)) or slice_chunks <= 0 or slice_chunks % a:
         raise ValueError(f"slice_chunks = {slice_chunks!r}: a time slice is a positive multiple of {a} chunks at fft_size {fft_size} "
                          f"(lcm(24000, fft_size) / 24000: slices start on a frame)")
+
+
+def check_slice_chunks_sized(slice_chunks, sizes):
+    """ValueError unless slice_chunks is a positive multiple of the lcm of slice_align over the frame sizes"""
+    sizes = sorted(set(int(f) for f in sizes))
+    if len(sizes) == 1:
+        return check_slice_chunks(slice_chunks, sizes[0])
+    a = math.lcm(*[slice_align(f) for f in sizes])
+    if isinstance(slice_chunks, bool) or not isinstance(slice_chunks, (int, np.integer)) or slice_chunks <= 0 or slice_chunks % a:
+        raise ValueError(f"slice_chunks = {slice_chunks!r}: a time slice is a positive multiple of {a} chunks at fft_size {sizes} "
+                         f"(the lcm of lcm(24000, fft_size) / 24000 over the sizes: slices start on a frame of every size)")
 
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
@@ -590,7 +629,8 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if isinstance(grid, str):
         with open(grid) as f:
             grid = json.load(f)
-    configs = expand_grid(grid)
+    sizes_of, configs = expand_grid_sized(grid, None)
+    sized = "fft_size" in grid   # (a grid without the key runs every config at the plan's fft_size: expand_grid's configs)
     if vad_on == "auto":
         vad_on = "device" if len(configs) >= SWEEP_DEVICE_MIN_CONFIGS else "host"
     if vad_on not in ("device", "host"):
@@ -604,7 +644,11 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     plan = load_plan(plan_path)
     F = plan["fft_size"]
     if slice_chunks is not None:
-        check_slice_chunks(slice_chunks, F)
+        if sized:
+            check_slice_chunks_sized(slice_chunks, grid["fft_size"])
+        else:
+            check_slice_chunks(slice_chunks, F)
+    sizes_of = [F if f is None else f for f in sizes_of]
     stat_cfgs = [_stat_cfg(c) for c in configs]
     if slice_chunks is not None:   # the audio stays in its files: mapped, read slice by slice
         loaded = [(_map_audio(i), _read_labels(i)) for i in plan["instances"]]
@@ -635,7 +679,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if slice_chunks is not None:
         try:
             n_slices, dev_bytes = _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on,
-                                                   n_threads, stats, times)
+                                                   n_threads, stats, times, sizes_of if sized else None)
         finally:
             if own_ctx:
                 ctx.close()
@@ -646,17 +690,30 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
             times["denoise"] = time.perf_counter() - t0
             l0 = 0
             for nch, members in groups.items():
-                sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+                if sized:   # several frame sizes in one batch: one band-sum pass per size into its run of band blocks
+                    sweep = fv.VadSweepSized(len(members), configs, sizes_of, n_channels=nch)
+                else:
+                    sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
                 try:
                     t0 = time.perf_counter()
                     bins, _ = sweep.bands()
                     g_lanes = list(range(l0, l0 + len(members) * nch))
                     l0 += len(g_lanes)
                     d_gden = d_den + g_lanes[0] * n_den * 4
-                    bstride = max(nf_all, 1)
-                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                    if nf_all:
-                        ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                    if sized:
+                        bstride = max(n_den // min(sweep.sizes), 1)
+                        d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                        for Fg, j0, bins_g in sweep.size_blocks():
+                            if n_den // Fg:
+                                ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins_g,
+                                                     d_gband + j0 * len(g_lanes) * bstride * 4, bstride, fft_size=Fg)
+                        nf_run = [[n_chunks[i] * chunk // Fg for i in members] for Fg in sweep.sizes]
+                    else:
+                        bstride = max(nf_all, 1)
+                        d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                        if nf_all:
+                            ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                        nf_run = [n_chunks[i] * chunk // F for i in members]
                     g_rms = np.ascontiguousarray(rms[g_lanes])
                     times["bands"] += time.perf_counter() - t0
                     if vad_on == "device":
@@ -670,8 +727,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
                             ctx.enable_timing(True)
                         try:
                             t0 = time.perf_counter()
-                            sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
-                                             [n_chunks[i] for i in members])
+                            sweep.run_device(ctx, d_gband, bstride, nf_run, g_rms, [n_chunks[i] for i in members])
                             wall = time.perf_counter() - t0
                             score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
                         finally:
@@ -691,12 +747,20 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
                         continue
                     gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
                     for k, i in enumerate(members):   # instances differ in length: one host batch each
-                        nf_i = n_chunks[i] * chunk // F
-                        one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
+                        if sized:
+                            one = fv.VadSweepSized(1, configs, sizes_of, n_channels=nch)
+                        else:
+                            nf_i = n_chunks[i] * chunk // F
+                            one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
                         try:
                             t0 = time.perf_counter()
-                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
-                                    np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
+                            i_rms = np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)])
+                            if sized:
+                                nf_i = [n_chunks[i] * chunk // Fg for Fg in one.sizes]
+                                one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :max(max(nf_i), 1)]), i_rms, nf_i,
+                                        n_threads=n_threads)
+                            else:
+                                one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]), i_rms, n_threads=n_threads)
                             times["machines"] += time.perf_counter() - t0
                             t0 = time.perf_counter()
                             one.set_references([refs[i]], stat_cfgs)
@@ -715,16 +779,21 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
                 ctx.close()
     aggs = [fv.stats_aggregate_array(stats[c]) for c in range(NC)]
     rows = [dict(config=c, **_agg_row(agg)) for c, agg in enumerate(aggs)]
+    if sized:
+        for r in rows:
+            r["fft_size"] = sizes_of[r["config"]]
     elapsed = time.perf_counter() - t_all
     if json_path:
         with open(json_path, "w") as f:
             json.dump({"grid": grid, "configs": configs, "rows": rows}, f, indent=1)
     if out is not None:
         out.write(f"top {min(top, NC)} of {NC} configs by F-score (β = 0.7):\n")
-        out.write("| config |      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
+        out.write("| config |" + (" fft_size |" if sized else "") +
+                  "      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
         for r in _ranked(rows)[:top]:
-            out.write("| {:>6} | {} | {} | {} | {} | {}% | {}% | {}% | {}% | {}% | {}% |\n".format(
-                r["config"], _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
+            out.write("| {:>6} |".format(r["config"]) + (" {:>8} |".format(r["fft_size"]) if sized else "") +
+                      " {} | {} | {} | {} | {}% | {}% | {}% | {}% | {}% | {}% |\n".format(
+                _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
                 *[_f(np.float32(r[k]) * np.float32(100), 5, 1) for k in ("TPR", "PPV", "FNR", "FDR")],
                 _f(np.float32(r["F"]) * np.float32(100), 6, 1), _f(np.float32(r["FM"]) * np.float32(100), 5, 1)))
         out.write(f"[{NC} configs x {n_inst} instances in {elapsed:.2f} s: denoise {times['denoise']:.2f} s, bands "
@@ -742,7 +811,7 @@ ENGINE_WS_BYTES_PER_CHUNK = 4 * (54 * 176 + 50 * 161 * 2 + 54 * 25 * 3 * 16 + 2 
 ENGINE_MAX_LAUNCH_CHUNKS = 49152
 
 
-def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times):
+def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of=None):
     """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
     SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
     (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
@@ -750,21 +819,33 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
     per group in parts (fvad_vad_batch_run_device_part), or with vad_on "host" one host batch per instance
     (fvad_vad_batch_run_part).  An instance gets 0 frames once it has ended.  The device buffers are allocated once, for the
     largest group, and reused slice after slice.  Fills stats [config][instance][11] and times; returns (slices run,
-    device_bytes as run_grid describes it)."""
+    device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
+    batch, one band-sum pass per size and slice, and parts from sample s0 * chunk (fvad_vad_batch_run_device_part_sized /
+    fvad_vad_batch_run_sized)."""
     chunk, H = 24000, SLICE_HALO_CHUNKS
     n_chunks = [a.shape[0] // chunk for a in audio]
     groups = {}
     for i, a in enumerate(audio):
         groups.setdefault(a.shape[1], []).append(i)
-    probe = fv.VadSweep(1, configs, fft_size=F)
+    sized = sizes_of is not None
+
+    def new_batch(n_streams, nch):
+        if sized:
+            return fv.VadSweepSized(n_streams, configs, sizes_of, n_channels=nch)
+        return fv.VadSweep(n_streams, configs, n_channels=nch, fft_size=F)
+
+    probe = new_batch(1, 1)
     bins, _ = probe.bands()
+    # the frame sizes and each size's run of band blocks
+    blocks = probe.size_blocks() if sized else [(F, 0, bins)]
     probe.close()
+    f_min = min(Fg for Fg, _, _ in blocks)
     probe = fv.VadSweep(1, [configs[0]], fft_size=F)   # the engine pass sums config 0's band (unused: the bands come from K4)
     (min_bin, max_bin), = probe.bands()[0]
     probe.close()
     n_max = N + H                                      # chunks of a slice with its halo
     lanes_max = max([len(m) * nch for nch, m in groups.items()] + [1])
-    fr_slice = N * chunk // F                          # frames of a full slice (N * chunk is a multiple of F)
+    fr_slice = N * chunk // f_min                      # frames of a full slice at the smallest size (N * chunk is a multiple of each)
     own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4,
            "band0": lanes_max * (n_max * chunk // F + 1) * 4, "rms": lanes_max * n_max * 4,
            "bands": len(bins) * lanes_max * fr_slice * 4}
@@ -782,16 +863,16 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
         for nch, members in groups.items():
             L = len(members) * nch
             K = max(n_chunks[i] for i in members)
-            nf_end = [n_chunks[i] * chunk // F for i in members]
+            nf_end = [[n_chunks[i] * chunk // Fg for i in members] for Fg, _, _ in blocks]
             dev = None
             hosts = []
             if vad_on == "device":
-                dev = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+                dev = new_batch(len(members), nch)
                 if score_on == "device":
                     dev.set_references([refs[i] for i in members], stat_cfgs)
                     dev.keep_segments(False)
             else:
-                hosts = [fv.VadSweep(1, configs, n_channels=nch, fft_size=F) for _ in members]
+                hosts = [new_batch(1, nch) for _ in members]
             try:
                 for s0 in range(0, K, N):
                     s1 = min(s0 + N, K)
@@ -822,18 +903,32 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
                     # ---- band sums of the slice's frames: the denoised audio from chunk s0 on (frame-aligned: s0 is a
                     # multiple of slice_align(F))
                     t0 = time.perf_counter()
-                    f0 = s0 * chunk // F
-                    f1 = s1 * chunk // F
-                    ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins, d["bands"],
-                                         fr_slice, fft_size=F)
+                    for Fg, j0, bins_g in blocks:
+                        ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins_g,
+                                             d["bands"] + j0 * L * fr_slice * 4, fr_slice, fft_size=Fg)
                     times["bands"] += time.perf_counter() - t0
-                    nf = [max(0, min(e, f1) - f0) for e in nf_end]
+                    # each size's frames of the slice, per instance
+                    nf_g = [[max(0, min(e, s1 * chunk // Fg) - s0 * chunk // Fg) for e in ends] for (Fg, _, _), ends in zip(blocks, nf_end)]
+                    nf = nf_g[0]
+                    f0 = s0 * chunk // F
                     nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
                     # ---- the machines
                     t0 = time.perf_counter()
-                    if dev is not None:
+                    if dev is not None and sized:
+                        dev.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
+                        batch_peak = max(batch_peak, dev.device_bytes())
+                    elif dev is not None:
                         dev.run_device_part(ctx, d["bands"], fr_slice, nf, rms, nc, f0)
                         batch_peak = max(batch_peak, dev.device_bytes())
+                    elif sized:
+                        band = ctx.to_host(np.empty((len(bins), L, fr_slice), np.float32), d["bands"])
+                        for k, h in enumerate(hosts):
+                            nf_k = [row[k] for row in nf_g]
+                            if max(nf_k) == 0 and s0 > 0:
+                                continue   # ended (its machines keep their results)
+                            h.run(np.ascontiguousarray(band[:, k * nch:(k + 1) * nch, :max(max(nf_k), 1)]),
+                                  np.ascontiguousarray(rms[k * nch:(k + 1) * nch, :max(nc[k], 1)]), nf_k, first_sample=s0 * chunk,
+                                  n_threads=n_threads)
                     else:
                         band = ctx.to_host(np.empty((len(bins), L, fr_slice), np.float32), d["bands"])
                         for k, h in enumerate(hosts):
@@ -916,10 +1011,12 @@ def main(argv=None):
     ap.add_argument("--sweep-vad", default="auto", choices=("auto", "device", "host"),
                     help="with --sweep / --sweep-grid: where the VAD machines run (auto: the GPU from %d configs on)" % SWEEP_DEVICE_MIN_CONFIGS)
     ap.add_argument("--sweep-grid", default=None, help="score every config of a grid file ({\"base\": {...}, \"axes\": {field: "
-                                                          "[values]}}) over one denoising pass; print the top configs (device 0)")
+                                                          "[values]}}, optionally \"fft_size\": [sizes]) over one denoising pass; "
+                                                          "print the top configs (device 0)")
     ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
     ap.add_argument("--slice-chunks", type=int, default=None,
-                    help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024), device and host "
+                    help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
+                         "sizes, of the lcm over them), device and host "
                          "memory bounded by the slice instead of the corpus")
     a = ap.parse_args(argv)
     if a.sweep_grid:

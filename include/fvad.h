@@ -494,6 +494,44 @@ int fvad_vad_batch_run_device_part(fvad_ctx *ctx, fvad_vad_batch *b, const float
 int fvad_vad_batch_score_device(fvad_ctx *ctx, fvad_vad_batch *b);
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch *b);
 
+/* Sweeps over the FFT size (VADPipeline.Config.fft_size): config c's machines run on frames of fft_sizes[c] samples (each even,
+ * 4 .. 16384, else FVAD_ERR_INVALID_ARGUMENT; each config checked as fvad_vad_batch_create_sweep checks it, at its own size).
+ * - A band is the triple (size, min bin, max bin): the same Hz edges at two sizes are two bands, their bins from FFT.freqToBin
+ *   at each size.  fvad_vad_batch_bands lists them size-major -- every band of size 0, then of size 1, ... -- in first-seen
+ *   config order within a size, so that each size's bands are one run of blocks (one fvad_engine_band_sums_device call per
+ *   size on the same denoised audio fills them).  With one size the order is fvad_vad_batch_create_sweep's.
+ * - `band` / `d_band` hold the blocks with one band_stride for every size, at least the largest frame count of any size.
+ * - The distinct sizes are in first-seen config order (size g); fvad_vad_batch_frame_sizes lists them and size_of_band[j],
+ *   the size of band j (may be NULL).  Every batch has frame sizes: one for fvad_vad_batch_create / _create_sweep.
+ * - fvad_vad_batch_run_sized: the host machines (the yardstick), every stream the same length as in fvad_vad_batch_run_part;
+ *   n_frames[g] frames of size g from sample first_sample on.  fvad_vad_batch_run_device_sized: the device, one shot, as
+ *   fvad_vad_batch_run_device (segment room and device scoring alike), with n_frames[g * n_streams + s] frames of size g of
+ *   stream s.  fvad_vad_batch_run_device_part_sized: the same in parts, as fvad_vad_batch_run_device_part.  Frame k of a
+ *   machine of size F in a part is at sample first_sample + k * F.
+ * - Parts: first_sample = 0 starts fresh machines; a later part starts where the previous one ended, and must be a multiple of
+ *   chunk_size and of every size (FVAD_ERR_INVALID_ARGUMENT otherwise, as for every other broken part rule).  A part after
+ *   which the sizes' frames end at different samples is the last.  A stream given fewer frames of some size than the part's
+ *   longest of that size has ended.
+ * - The other run calls (_run, _run_part, _run_device, _run_device_part) take a sized batch of exactly one size and then behave
+ *   as for a fvad_vad_batch_create_sweep batch; with several sizes they return FVAD_ERR_INVALID_ARGUMENT.  The sized run calls
+ *   take every batch.  Segments, audits, lazy statistics, references, keep_segments, scoring (host and device), config_stats
+ *   and device_bytes work on sized batches unchanged: segments are in samples, so scoring does not depend on the size.
+ * - Context option vad_size_order (vad_lane_map "stream", several sizes): a stream's lanes take its configs "size"-major (the
+ *   default: a wavefront mostly runs one frame clock) or in the "caller"'s order; the results are the same bits. */
+int fvad_vad_batch_create_sweep_sized(const fvad_vad_config *cfgs, const size_t *fft_sizes, size_t n_configs,
+                                      size_t sample_rate, size_t n_channels, size_t n_streams, fvad_vad_batch **out);
+int fvad_vad_batch_frame_sizes(const fvad_vad_batch *b, size_t *sizes, size_t cap, size_t *n_sizes,
+                               uint32_t *size_of_band);
+int fvad_vad_batch_run_sized(fvad_vad_batch *b, const float *band, size_t band_stride, const size_t *n_frames,
+                             const float *chunk_rms, size_t rms_stride, size_t n_chunks, size_t chunk_size,
+                             uint64_t first_sample, int n_threads);
+int fvad_vad_batch_run_device_sized(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                                    const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
+                                    const size_t *n_chunks, size_t chunk_size);
+int fvad_vad_batch_run_device_part_sized(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                                         const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
+                                         const size_t *n_chunks, size_t chunk_size, uint64_t first_sample);
+
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;
 int fvad_ra_create(size_t count, int has_initial, double initial_val, fvad_rolling_average **out);
