@@ -984,17 +984,15 @@ def frame_ratios(chunk_rms, n_frames, fft_size=1024, chunk=24000):
     r2 = ((r2 * w) / w).astype(np.float32)        # denoiser stage
     out = np.empty(n_frames, np.float32)
     for k in range(n_frames):
+        # every chunk the frame overlaps, in order, weighted by the samples it gives the frame (a frame longer than a chunk
+        # spans three or more)
         lo, hi = k * fft_size, (k + 1) * fft_size
-        c0, c1 = lo // chunk, (hi - 1) // chunk
-        if c0 == c1:
-            n = np.float32(fft_size)
-            out[k] = (np.float32(0) + r2[c0] * n) / n
-        else:
-            n0 = np.float32((c0 + 1) * chunk - lo)
-            n1 = np.float32(hi - c1 * chunk)
-            s = np.float32(0) + r2[c0] * n0
-            s = s + r2[c1] * n1
-            out[k] = s / (n0 + n1)
+        s, n = np.float32(0), np.float32(0)
+        for c in range(lo // chunk, (hi - 1) // chunk + 1):
+            w = np.float32(min(hi, (c + 1) * chunk) - max(lo, c * chunk))
+            s = np.float32(s + r2[c] * w)
+            n = np.float32(n + w)
+        out[k] = s / n
     return out
 
 

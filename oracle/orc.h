@@ -185,6 +185,9 @@ void orc_vad_destroy(orc_vad *v);
  * (averageVolumeInBand) and the frame's vad_metadata.volume_ratio (has_ratio=0 -> null). */
 orc_vad_result orc_vad_run(orc_vad *v, uint64_t index, const float *channel_volumes,
                            int has_ratio, float volume_ratio);
+/* orc_vad_run frame by frame: channel_volumes [n_frames][n_channels], volume_ratio [n_frames] (NaN -> has_ratio = 0) */
+void orc_vad_run_frames(orc_vad *v, uint64_t first_index, size_t n_frames, const float *channel_volumes,
+                        const float *volume_ratio);
 size_t orc_vad_n_segments(const orc_vad *v);
 const orc_speech_segment *orc_vad_segments(const orc_vad *v);
 size_t orc_vad_n_trace(const orc_vad *v);

@@ -349,3 +349,15 @@ size_t orc_vad_n_segments(const orc_vad *v) { return v->n_segments; }
 const orc_speech_segment *orc_vad_segments(const orc_vad *v) { return v->segments; }
 size_t orc_vad_n_trace(const orc_vad *v) { return v->n_trace; }
 const orc_vad_trace *orc_vad_traces(const orc_vad *v) { return v->trace; }
+
+/* orc_vad_run over n_frames frames at samples first_index + k * fft_size: channel_volumes [n_frames][n_channels], volume_ratio
+ * [n_frames] (NaN = null).  A loop over orc_vad_run, nothing more: one foreign call per stream for the tests. */
+void orc_vad_run_frames(orc_vad *v, uint64_t first_index, size_t n_frames, const float *channel_volumes,
+                        const float *volume_ratio)
+{
+    for (size_t k = 0; k < n_frames; ++k) {
+        const float r = volume_ratio[k];
+        orc_vad_run(v, first_index + (uint64_t)k * (uint64_t)v->fft_size, channel_volumes + k * (size_t)v->n_channels,
+                    !isnan(r), r);
+    }
+}

@@ -174,6 +174,7 @@ def lib(native=False):
         "orc_vad_create": (vp, [C.POINTER(VadConfig), C.c_int, C.c_int, C.c_int]),
         "orc_vad_destroy": (None, [vp]),
         "orc_vad_run": (VadResult, [vp, C.c_uint64, c_float_p, C.c_int, C.c_float]),
+        "orc_vad_run_frames": (None, [vp, C.c_uint64, sz, c_float_p, c_float_p]),
         "orc_vad_n_segments": (sz, [vp]),
         "orc_vad_segments": (C.POINTER(SpeechSegment), [vp]),
         "orc_vad_n_trace": (sz, [vp]),
