@@ -17,6 +17,9 @@ no data-path collective (weak scaling: every rank processes the same amount of a
 collective is the final all_gather of per-stream Evaluator statistics (RCCL), outside the steps.
 Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  `--dump-outputs DIR` also writes
 what the last timed step computed as .npy files (dump_outputs), so that two builds can be compared output for output.
+A plain run does only that: set up, warm up, time the steps, dump, print.  `--full` adds everything else the line can
+carry (the oracle self-checks, the device-only passes, the f16x3 / bf16x3 blocks, the stereo reading, the Evaluator
+aggregate, cfg4_strong, the CPU baseline, the side measurements) and exits 1 when a self-check fails.
 """
 import argparse
 import importlib.util
@@ -56,6 +59,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--lanes", type=int, default=384, help="streams per GPU per step")
     ap.add_argument("--seconds", type=int, default=64, help="audio seconds per stream per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks: the oracle self-check and the "
+                         "device-only pass of each timed configuration, the f16x3 / bf16x3 blocks, the stereo reading, the "
+                         "Evaluator aggregate, cfg4_strong (N > 1), the CPU baseline and the side measurements (`extra`); the "
+                         "--no-* options below trim such a run.  Without it a run sets up, warms up, times the steps, dumps "
+                         "(--dump-outputs) and prints the headline line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cfg4-strong", action="store_true", help="N > 1: skip the strong-scaling block (config 4's plan on the same ranks)")
     ap.add_argument("--no-extra", action="store_true", help="skip the config-2 / config-3 side measurements")
@@ -90,20 +99,27 @@ def parse():
 def make_inputs(pkg, rank, lanes, seconds):
     """lanes x seconds of synthetic 48 kHz mono, every lane different: 32 seeded 64 s patterns per rank, lane l =
     pattern l % 32 rotated by (l // 32) * 4801 samples (a rotation is a different stream: other chunk phases,
-    other burst times) and tiled to the requested length"""
+    other burst times) and tiled to the requested length.  Patterns and lanes are made by a pool of threads: every
+    pattern has its own seeded generator and every lane its own row, so the arrays do not depend on the order."""
+    from concurrent.futures import ThreadPoolExecutor
     base_sec = min(64, seconds)
-    out = np.empty((lanes, seconds * 48000), np.float32)
-    labels = []
-    cache = {}
+    n = seconds * 48000
+    out = np.empty((lanes, n), np.float32)
     reps = (seconds + base_sec - 1) // base_sec
+    keys = range(min(lanes, 32))
+
+    def fill(lane):                          # np.tile(np.roll(pattern, shift), reps)[:n], written in place
+        row = np.roll(pats[lane % 32][0][0], 4801 * (lane // 32))
+        for at in range(0, n, row.size):
+            out[lane, at: at + row.size] = row[: n - at]
+
+    with ThreadPoolExecutor(min(os.cpu_count() or 1, 16)) as pool:
+        pats = dict(zip(keys, pool.map(lambda key: pkg.synth.make_stream(float(base_sec), seed=1000 * rank + key), keys)))
+        list(pool.map(fill, range(lanes)))
+    labels = []
     for lane in range(lanes):
-        key = lane % 32
-        if key not in cache:
-            cache[key] = pkg.synth.make_stream(float(base_sec), seed=1000 * rank + key)
-        pcm, lab = cache[key]
         shift = 4801 * (lane // 32)
-        out[lane] = np.tile(np.roll(pcm[0], shift), reps)[: seconds * 48000]
-        labels.append([(a, b) for a, b in roll_labels(lab, shift / 48000.0, float(base_sec), reps) if b <= seconds])
+        labels.append([(a, b) for a, b in roll_labels(pats[lane % 32][1], shift / 48000.0, float(base_sec), reps) if b <= seconds])
     return out, labels
 
 
@@ -621,8 +637,8 @@ def main():
 
     def measure(math, tag):
         """W warm-up steps, then EXACTLY K timed steps (barrier + synchronize on both sides) of the whole path with the
-        context's arithmetic set to `math`; HIP-event kernel times over the timed steps; the self-check of the last
-        timed step; then the device-only rate of the same work (no host stage), for the record."""
+        context's arithmetic set to `math`; HIP-event kernel times over the timed steps; with --full, the self-check of
+        the last timed step and then the device-only rate of the same work (no host stage), for the record."""
         ctx.set_nn_math(math)
         eff = ctx.nn_math_effective()
         del gpu_wall_ms[:], join_ms[:], host_ms[:]
@@ -642,15 +658,17 @@ def main():
         # self-check of the configuration that was just timed: two lanes of the LAST timed step (the first and
         # the last of the batch) against the CPU oracle -- denoised audio, band sums, segment boundaries
         check = None
-        if rank == 0:
-            check = check_against_oracle(ctx, weights, host_pcm, [0, lanes - 1], d_den, n_samp,
-                                         h_band[(args.steps - 1) & 1], results[(tag, args.steps - 1)])
-        barrier()
-        t1 = time.perf_counter()
-        for i in range(args.steps):
-            gpu_stage(i & 1)
-        barrier()
-        dev_elapsed = time.perf_counter() - t1
+        dev_elapsed = 0.0
+        if args.full:
+            if rank == 0:
+                check = check_against_oracle(ctx, weights, host_pcm, [0, lanes - 1], d_den, n_samp,
+                                             h_band[(args.steps - 1) & 1], results[(tag, args.steps - 1)])
+            barrier()
+            t1 = time.perf_counter()
+            for i in range(args.steps):
+                gpu_stage(i & 1)
+            barrier()
+            dev_elapsed = time.perf_counter() - t1
         t = torch.tensor([elapsed, dev_elapsed], dtype=torch.float64, device=cdev)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -720,7 +738,7 @@ def main():
     # ---- the emulated arithmetic on the same batch, first-class: the same W + K steps end to end, its own roofline
     # and self-check.  It is NOT the headline: f16x3 carries 22 significand bits per operand, the reference's f32 24.
     emulated = emulated24 = None
-    if nn_math == "f32" and not args.no_emulated:
+    if args.full and nn_math == "f32" and not args.no_emulated:
         em = measure("f16x3", "emulated")
         if em["nn_math"] == "f16x3":
             emulated = {"nn_math": "f16x3", "note": "three v_mfma_f32_16x16x32_f16 per product on (hi, lo) f16 pieces of power-of-two "
@@ -753,7 +771,7 @@ def main():
     # the GPU work is identical (a lane is a channel), the host stage runs 2-channel state machines on
     # min-over-channels band sums and the per-chunk RMS ratio (BufferedVolumeAnalyzer.zig:48-69)
     stereo = None
-    if rank == 0 and lanes % 2 == 0:
+    if args.full and rank == 0 and lanes % 2 == 0:
         t_s0 = time.perf_counter()
         gpu_stage(0)
         ctx.synchronize()
@@ -767,17 +785,21 @@ def main():
                   "note": "one step, host stage after the GPU stage (in the timed loop they overlap); frames = channel-frames"}
 
     # ---- final Evaluator aggregate: per-stream SingleStats -> all_gather (RCCL) -> ordered aggregate
-    stat_cfg = {"ignore_shorter_than_sec": 0.7, "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
-    last = results[("timed", args.steps - 1)]
-    local_ids = [rank + world * lane for lane in range(lanes)]   # round-robin plan order
-    local_stats = []
-    for lane in range(lanes):
-        segs = [(np.float32(s[0]) / np.float32(48000), np.float32(s[1]) / np.float32(48000)) for s in last[lane]]
-        local_stats.append(fv.stats_from_segments(segs, labels[lane], stat_cfg))
-    ta = time.perf_counter()
-    allst, collective, rccl_ranks = gather_all_stats(pkg, fv, ctx, dist, world, args, cdev, local_ids, local_stats, lanes * world)
-    agg = fv.stats_aggregate([fv.array_to_single_stats(a) for a in allst])
-    agg_ms = (time.perf_counter() - ta) * 1e3
+    aggregate = rccl_ranks = None
+    if args.full:
+        stat_cfg = {"ignore_shorter_than_sec": 0.7, "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
+        last = results[("timed", args.steps - 1)]
+        local_ids = [rank + world * lane for lane in range(lanes)]   # round-robin plan order
+        local_stats = []
+        for lane in range(lanes):
+            segs = [(np.float32(s[0]) / np.float32(48000), np.float32(s[1]) / np.float32(48000)) for s in last[lane]]
+            local_stats.append(fv.stats_from_segments(segs, labels[lane], stat_cfg))
+        ta = time.perf_counter()
+        allst, collective, rccl_ranks = gather_all_stats(pkg, fv, ctx, dist, world, args, cdev, local_ids, local_stats, lanes * world)
+        agg = fv.stats_aggregate([fv.array_to_single_stats(a) for a in allst])
+        agg_ms = (time.perf_counter() - ta) * 1e3
+        aggregate = {"ms": agg_ms, "n_streams": lanes * world, "tpr": agg.true_positive_rate.overall,
+                     "ppv": agg.precision.overall, "collective": collective, "stats_sha256": stats_digest(allst, agg)}
 
     # per-rank step times and the communicator's size, for the record of an N-rank run
     rank_ms = [None] * world
@@ -790,7 +812,7 @@ def main():
     # statistics gather, the plan-order aggregate) -- a FIXED amount of work, so one driver invocation per N records weak
     # scaling (the headline: every rank the same batch) and strong scaling (`cfg4_strong`) side by side
     cfg4_strong = None
-    if world > 1 and not args.no_cfg4_strong:
+    if args.full and world > 1 and not args.no_cfg4_strong:
         try:
             cfg4_strong = run_cfg4(args, pkg, fv, ctx, torch, dist, rank, world, cdev, steps=2, warmup=1, emit=False)
         except Exception as e:  # every rank takes the same path: an exception here is an allocation or a library error
@@ -818,41 +840,49 @@ def main():
             "config": {"workload": f"full pipeline (window->STFT->NSNet2->iSTFT->FFT1024 band->VAD decision), "
                                    f"{lanes} streams x {seconds} s per GPU per step = {lanes * n_chunks} chunks = "
                                    f"{frames_per_step} frames; BASELINE config 3 pipeline at a saturating batch "
-                                   f"(config 3's own 82-chunk batch is in extra.cfg3)",
+                                   f"(config 3's own 82-chunk batch is in extra.cfg3 of a --full run)",
                        "streams_per_gpu": lanes, "seconds_per_stream": seconds,
                        "frame": "10 ms hop / 20 ms window @16 kHz (NSNet2.zig:12-13)",
                        "parallelism": f"streams sharded over {world} GPU(s), no data-path collective"},
             "ranks": {"launched": world, "backend": args.dist_backend if world > 1 else "none", "rccl_ranks": rccl_ranks,
                       "ms_per_step_per_rank": rank_ms},
             "audio_seconds_per_s": value / 100.0,
-            "device_only_frames_per_s": total_frames / dev_elapsed,
+        }
+        # (the keys of a --full run stay in the order of the one line that carried them all)
+        if args.full:
+            out["device_only_frames_per_s"] = total_frames / dev_elapsed
+        out.update({
             "roofline": roofline_of(head),
             "roofline_pipeline": pipeline_of(head),
             "kernel_ms_per_step": {k: v / args.steps for k, v in ktimes.items()},
-            "aggregate": {"ms": agg_ms, "n_streams": lanes * world, "tpr": agg.true_positive_rate.overall,
-                          "ppv": agg.precision.overall, "collective": collective, "stats_sha256": stats_digest(allst, agg)},
-            "self_check": self_check,
-            "parity_note": "parity unpinned: the checker is oracle/, a CPU restatement of the reference; the reference holds no "
-                           "golden vector for FFT / NSNet2 / band sums / segments and cannot be built here (DESIGN.md section 4)",
-            "emulated": emulated,
-            "emulated24": emulated24,
-            "headline_as_stereo": stereo,
+        })
+        if args.full:
+            out.update({
+                "aggregate": aggregate,
+                "self_check": self_check,
+                "parity_note": "parity unpinned: the checker is oracle/, a CPU restatement of the reference; the reference holds no "
+                               "golden vector for FFT / NSNet2 / band sums / segments and cannot be built here (DESIGN.md section 4)",
+                "emulated": emulated,
+                "emulated24": emulated24,
+                "headline_as_stereo": stereo,
+            })
+        out.update({
             "host_vad_threads": vad_threads,
             "gpu_stage_wall_ms": head["gpu_wall_ms"],
             "kernel_ms_sum": float(sum(ktimes.values()) / args.steps),
             "join_wait_ms": head["join_ms"],
             "host_stage_ms": head["host_ms"],
-        }
+        })
         if cfg4_strong is not None:
             out["cfg4_strong"] = cfg4_strong
         # the CPU baseline and the side measurements belong to the single-GPU run only
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pkg, fv, weights, min(os.cpu_count() or 1, 16))
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             out["extra"] = side_measurements(pkg, fv, ctx, torch, dev)
         print(json.dumps(out))
-        if not self_check or not self_check["ok"] or (emulated and not emulated["self_check"]["ok"]) or \
-                (emulated24 and not emulated24["self_check"]["ok"]):
+        if args.full and (not self_check or not self_check["ok"] or (emulated and not emulated["self_check"]["ok"]) or
+                          (emulated24 and not emulated24["self_check"]["ok"])):
             print("bench.py: SELF-CHECK FAILED: the timed configuration does not match the oracle", file=sys.stderr)
             sys.exit(1)
     if world > 1:

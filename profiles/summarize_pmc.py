@@ -1,5 +1,5 @@
 """Per-kernel HBM traffic from the rocprofv3 PMC passes (separate --pmc FETCH_SIZE / WRITE_SIZE
-runs of `bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra`; usage:
+runs of `bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra`; usage:
 summarize_pmc.py <tag> <chunks_per_launch>, e.g. `r01b 49152`).
 Counter units are KiB.  Correction per /opt/skills/guides/MI355X_MICROARCH.md (HBM section): on
 gfx950 FETCH_SIZE reports half the bytes of wide (16 B/lane) coalesced reads, WRITE_SIZE is exact

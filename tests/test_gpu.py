@@ -1424,7 +1424,7 @@ def test_two_ranks_on_real_rccl_give_the_one_rank_report():
     assert two["aggregate"]["rccl_ranks"] == 2 and "ncclAllGather" in two["aggregate"]["collective"], two["aggregate"]
     assert two["aggregate"]["stats_sha256"] == one["aggregate"]["stats_sha256"]
     assert two["aggregate"]["tpr"] == one["aggregate"]["tpr"] and two["aggregate"]["ppv"] == one["aggregate"]["ppv"]
-    d = run(["--gpus", "2", "--lanes", "16", "--seconds", "64", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline",
+    d = run(["--gpus", "2", "--lanes", "16", "--seconds", "64", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline",
              "--cfg4-streams", "5", "--cfg4-seconds", "600"])
     assert d["n_gpus"] == 2 and d["ranks"]["launched"] == 2 and d["ranks"]["backend"] == "nccl" and d["ranks"]["rccl_ranks"] == 2, d["ranks"]
     assert d["self_check"]["ok"] and d["aggregate"]["n_streams"] == 32
@@ -1435,12 +1435,12 @@ def test_two_ranks_on_real_rccl_give_the_one_rank_report():
 def test_bench_gpus_2_launches_two_ranks_itself():
     # `python bench.py --gpus 2` with no launcher around it starts the two ranks itself (children of a process that
     # never touches the GPU) and prints ONE line with n_gpus = 2; here as a gloo rehearsal on the one GPU of the box.
-    # The headline is on the reference's f32 arithmetic, the f16x3 emulation sits in its own block.
+    # The headline is on the reference's f32 arithmetic, the f16x3 emulation sits in its own block (--full).
     import json
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--lanes", "16", "--seconds", "64",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--cfg4-streams", "5", "--cfg4-seconds", "600"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--cfg4-streams", "5", "--cfg4-seconds", "600"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1464,17 +1464,23 @@ def test_bench_gpus_2_launches_two_ranks_itself():
 def test_bench_dump_outputs_are_bounded_and_the_same_on_every_run(tmp_path):
     # --dump-outputs: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most, from inputs that are the
     # same on every run.  32 lanes x 128 s = 8192 chunks, one launch of the persistent GEMM path: the same bits every run.
+    # Run a is a plain run (the headline alone), run b a --full one whose self-check compares that last step with the oracle:
+    # both dump the same bits, and only b's line carries what --full adds.
     import json
     import subprocess
     import sys
     runs = []
-    for name in ("a", "b"):
+    for name, full in (("a", []), ("b", ["--full"])):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lanes", "32", "--seconds", "128", "--steps", "3",
-               "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-emulated", "--dump-outputs", str(tmp_path / name)]
+               "--warmup", "1"] + full + ["--no-cpu-baseline", "--no-extra", "--no-emulated", "--dump-outputs", str(tmp_path / name)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
-        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["self_check"]["ok"]
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        if full:
+            assert d["self_check"]["ok"] and d["device_only_frames_per_s"] > 0 and d["aggregate"]["n_streams"] == 32
+        else:
+            assert not {"self_check", "device_only_frames_per_s", "aggregate", "emulated", "headline_as_stereo"} & set(d), sorted(d)
         runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
     a, b = runs
     assert set(a) == {"segments", "band_sum", "chunk_rms", "band_lanes", "denoised", "denoised_chunks"}

@@ -54,6 +54,33 @@ def test_bench_gpus_n_without_enough_gpus_is_refused_before_any_rank_starts():
     assert r.returncode == 2 and "rank" in r.stderr
 
 
+def test_bench_runs_the_headline_alone_unless_full_is_given(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+
+
+@pytest.mark.parametrize("lanes,seconds", [(3, 150), (35, 20)])
+def test_bench_inputs_are_the_lanes_built_one_by_one(pkg, lanes, seconds):
+    # make_inputs builds its patterns and lanes on a pool of threads; here lane l is built alone: pattern l % 32 rotated by
+    # (l // 32) * 4801 samples, tiled and cut to the length (150 s: three 64 s periods, the last cut; 35 lanes: rotations)
+    import bench
+    pcm, labels = bench.make_inputs(pkg, 1, lanes, seconds)
+    base_sec = min(64, seconds)
+    reps = (seconds + base_sec - 1) // base_sec
+    assert pcm.shape == (lanes, seconds * 48000) and pcm.dtype == np.float32 and len(labels) == lanes
+    pats = {}
+    for lane in range(lanes):
+        if lane % 32 not in pats:
+            pats[lane % 32] = pkg.synth.make_stream(float(base_sec), seed=1000 + lane % 32)
+        x, lab = pats[lane % 32]
+        shift = 4801 * (lane // 32)
+        assert np.array_equal(pcm[lane], np.tile(np.roll(x[0], shift), reps)[: seconds * 48000]), lane
+        assert labels[lane] == [(a, b) for a, b in bench.roll_labels(lab, shift / 48000.0, float(base_sec), reps) if b <= seconds]
+
+
 @pytest.mark.parametrize("unit", ["kernels_b3.hip", "kernels_h3.hip", "kernels_nn.hip", "kernels_ws.hip"])
 def test_kernels_with_inline_lds_reads_compile_without_spills(unit):
     # The persistent GEMMs and the LDS-DMA recurrences read weight fragments with inline ds_read_b128 / global_load_lds

@@ -2,7 +2,7 @@
 # Profiles of one round, run on the GPU box from the repository root:
 #     bash tools/profile_round.sh r05 [bench] [cfg2] [cfg3] [calib]        (no target = all four)
 # Targets (the program always directly behind `--`, never a shell or env hop):
-#   bench  python3 bench.py ...               the headline launch shape (49152 chunks) -> <tag>_kernel_stats.csv, <tag>_pmc_*.csv
+#   bench  python3 bench.py --full ...        the headline launch shape (49152 chunks) -> <tag>_kernel_stats.csv, <tag>_pmc_*.csv
 #   cfg2   python3 tools/fft_batch_rate.py    BASELINE config 2: window + rFFT-320 + |X| at 1024 and 2^20 frames
 #   cfg3   python3 tools/cfg3_loop.py         BASELINE config 3's literal 82-chunk batch, 204 calls back to back
 #   calib  tools/fetch_calib                  known byte counts in this library's read shapes (what the counters mean)
@@ -59,7 +59,7 @@ run_target() {
 for t in $TARGETS; do
     case $t in
     bench)
-        run_target $TAG python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extra -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra
+        run_target $TAG python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-extra -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra
         cp $OUT/${TAG}_under_rocprof.out $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null ;;
     cfg2)
         run_target ${TAG}_cfg2 python3 tools/fft_batch_rate.py -- python3 tools/fft_batch_rate.py ;;
