@@ -239,6 +239,7 @@ SIGNATURES = {
     "fvad_vad_batch_run_device_part": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
     "fvad_vad_batch_score_device": (C.c_int, [vp, vp]),
     "fvad_vad_batch_device_bytes": (sz, [vp]),
+    "fvad_vad_batch_retain_configs": (C.c_int, [vp, vp, C.POINTER(C.c_uint32), sz]),
     "fvad_vad_batch_create_sweep_sized": (C.c_int, [C.POINTER(VadConfig), C.POINTER(sz), sz, sz, sz, sz, C.POINTER(vp)]),
     "fvad_vad_batch_frame_sizes": (C.c_int, [vp, C.POINTER(sz), sz, C.POINTER(sz), C.POINTER(C.c_uint32)]),
     "fvad_vad_batch_run_sized": (C.c_int, [vp, c_float_p, sz, C.POINTER(sz), c_float_p, sz, sz, sz, C.c_uint64, C.c_int]),
@@ -960,6 +961,18 @@ class VadSweep:
         """fvad_vad_batch_device_bytes: device memory the batch holds between device parts (0 when it holds none)"""
         return lib().fvad_vad_batch_device_bytes(self.h)
 
+    def retain(self, ctx, keep):
+        """fvad_vad_batch_retain_configs: keep configs keep (strictly increasing indices) and drop the rest, between runs or
+        device parts; new config c is old config keep[c].  ctx: the parts' Context when the batch holds device part state,
+        else None or any Context"""
+        keep = [int(k) for k in keep]
+        arr = (C.c_uint32 * max(len(keep), 1))(*keep)
+        if ctx is None:
+            check(lib().fvad_vad_batch_retain_configs(None, self.h, arr, len(keep)), "fvad_vad_batch_retain_configs")
+        else:
+            ctx._ck(lib().fvad_vad_batch_retain_configs(ctx.h, self.h, arr, len(keep)), "fvad_vad_batch_retain_configs")
+        self.n_configs = len(keep)
+
     def segments(self, config):
         """config's segments per stream: [[(from, to, avg_ratio, vad_met_sec)]]"""
         offs = (sz * (self.n_streams + 1))()
@@ -1044,6 +1057,11 @@ class VadSweepSized(VadSweep):
         check(lib().fvad_vad_batch_create_sweep_sized(arr, sizes, len(configs), sample_rate, n_channels, n_streams, C.byref(self.h)),
               "fvad_vad_batch_create_sweep_sized")
         self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, len(configs)
+        self.sizes, self.size_of_band = self.frame_sizes()
+
+    def retain(self, ctx, keep):
+        """VadSweep.retain; the frame sizes and bands are the kept configs' afterwards"""
+        VadSweep.retain(self, ctx, keep)
         self.sizes, self.size_of_band = self.frame_sizes()
 
     def frame_sizes(self):

@@ -59,11 +59,13 @@ struct DevParts {
     size_t seg_cap = 0;
     bool rings_in_lds = false;
     int by_config = 0;                   // the lane map of the first part (the rings are laid out by it)
-    uint32_t st_max = 1, cr_max = 1;
+    int size_order = 0;                  // the context's vad_size_order at the first part (a sized batch's lane order)
+    uint32_t lt_max = 1, st_max = 1, cr_max = 1;
     uint64_t next_sample = 0;            // where the next part starts (UINT64_MAX: none can follow)
     uint64_t* sizes = nullptr;           // several frame sizes (VadMachinesArgs.sized): the sizes, each config's, the lane order
     uint32_t* size_of = nullptr;
     int* lane_config = nullptr;
+    std::vector<int> order;              // lane_config's host copy (empty with one size: lane j of a stream runs config j)
     std::vector<uint8_t> ended;          // streams that got fewer frames than a part's longest
     std::vector<uint32_t> count_h;       // every machine's segment count after the last part
     bool segs_on_device = true;          // every part so far left its segments on the device: they are all in segs
@@ -86,11 +88,11 @@ void free_dev_parts(void* p) { delete static_cast<DevParts*>(p); }
 
 // The lane order of a sized launch by stream (VadMachinesArgs.lane_config): a stream's configs size-major (first-seen order within
 // a size), so that a wavefront mostly runs one frame clock; the caller's order with the context option vad_size_order "caller"
-std::vector<int> lane_order(const fvad_vad_batch* b, const fvad_ctx* ctx)
+std::vector<int> lane_order(const fvad_vad_batch* b, int size_order)
 {
     std::vector<int> o(b->cfgs.size());
     for (size_t c = 0; c < o.size(); ++c) o[c] = (int)c;
-    if (ctx->tune.vad_size_order == 0)
+    if (size_order == 0)
         std::stable_sort(o.begin(), o.end(), [&](int x, int y) { return b->size_of[(size_t)x] < b->size_of[(size_t)y]; });
     return o;
 }
@@ -328,7 +330,7 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
         uint32_t* d_size_of = nullptr;
         int* d_order = nullptr;
         const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
-        const std::vector<int> order = lane_order(b, ctx);
+        const std::vector<int> order = lane_order(b, ctx->tune.vad_size_order);
         FVAD_HIP(ctx, scratch.alloc(&d_sizes, G));
         FVAD_HIP(ctx, scratch.alloc(&d_size_of, NC));
         FVAD_HIP(ctx, scratch.alloc(&d_order, NC));
@@ -447,9 +449,11 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         dp = fresh.get();
         dp->device = ctx->device;
         dp->ctx = ctx;
+        dp->lt_max = lt_max;
         dp->st_max = st_max;
         dp->cr_max = cr_max;
         dp->by_config = ctx->tune.vad_lane_map;
+        dp->size_order = ctx->tune.vad_size_order;
         // as fvad_vad_batch_run_device: the long-term rings in whole blocks of 64 slots plus one; the short-term and
         // channel-ratio rings in LDS when a workgroup's fit in 48 KB (their home between launches is `rings` either way)
         dp->rings_in_lds = (size_t)(st_max + cr_max) * 64 * sizeof(float) <= 48 * 1024;
@@ -464,7 +468,8 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         FVAD_HIP(ctx, hipMemcpyAsync(dp->cfg, hc.data(), NC * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
         if (G > 1) { // the sized form's tables; the lane order is the first part's (the rings are laid out by it)
             const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
-            const std::vector<int> order = lane_order(b, ctx);
+            dp->order = lane_order(b, dp->size_order);
+            const std::vector<int>& order = dp->order;
             FVAD_HIP(ctx, dp->alloc(&dp->sizes, G));
             FVAD_HIP(ctx, dp->alloc(&dp->size_of, NC));
             FVAD_HIP(ctx, dp->alloc(&dp->lane_config, NC));
@@ -625,6 +630,119 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     return FVAD_OK;
 }
 
+// The place (kernels_vad.hip: a lane's rings) of machine (s, c) in a batch of S streams and NC configs run with lane map by_config
+// and lane order `order` (empty: lane j of a stream runs config j)
+long place_of(size_t s, size_t c, size_t S, size_t NC, int by_config, const std::vector<int>& order)
+{
+    if (by_config) return (long)(c * S + s);
+    if (order.empty()) return (long)(s * NC + c);
+    const size_t j = (size_t)(std::find(order.begin(), order.end(), (int)c) - order.begin());
+    return (long)(s * NC + j);
+}
+
+// fvad_vad_batch_retain_configs on a batch with device part state: nb (retain_stage's) gets the kept machines' state in buffers of
+// its own size, gathered on the device (kernels_vadretain.hip); b's state is left as it is (retain_commit frees it)
+int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, const uint32_t* keep, size_t n_keep)
+{
+    const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+    const size_t S = b->n_streams, NC = b->cfgs.size(), G = nb->sizes.size();
+    const size_t M = S * n_keep, M_old = S * NC;
+    std::vector<VadMachineCfg> hc;
+    uint32_t lt_max, st_max, cr_max;
+    if (const int rc = derive_cfgs(ctx, nb, &hc, &lt_max, &st_max, &cr_max)) return rc;
+    // (the survivors' rings are never longer than the batch's were: the new rows are a prefix of the old)
+    if (lt_max > dp->lt_max || st_max > dp->st_max || cr_max > dp->cr_max) return set_err(ctx, FVAD_ERR_HIP, "retain: rings grew");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    std::unique_ptr<DevParts> fresh(new (std::nothrow) DevParts());
+    if (!fresh) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
+    DevParts* np = fresh.get();
+    try {
+        np->ended = dp->ended;
+        np->count_h.resize(M);
+        for (size_t s = 0; s < S; ++s)
+            for (size_t c = 0; c < n_keep; ++c) np->count_h[s * n_keep + c] = dp->count_h[s * NC + keep[c]];
+        if (G > 1) np->order = lane_order(nb, dp->size_order);
+    } catch (const std::bad_alloc&) {
+        return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
+    }
+    np->device = dp->device;
+    np->ctx = dp->ctx;
+    np->by_config = dp->by_config;
+    np->size_order = dp->size_order;
+    np->lt_max = lt_max;
+    np->st_max = st_max;
+    np->cr_max = cr_max;
+    np->rings_in_lds = (size_t)(st_max + cr_max) * 64 * sizeof(float) <= 48 * 1024; // (as run_device_part decides it)
+    np->next_sample = dp->next_sample;
+    np->segs_on_device = dp->segs_on_device;
+    const size_t lt_rows = ((size_t)lt_max + 63) / 64 * 16 + 16, old_lt_rows = ((size_t)dp->lt_max + 63) / 64 * 16 + 16;
+    FVAD_HIP(ctx, np->alloc(&np->cfg, n_keep));
+    FVAD_HIP(ctx, np->alloc(&np->lt, lt_rows * 4 * M));
+    FVAD_HIP(ctx, np->alloc(&np->rings, (size_t)(st_max + cr_max) * M));
+    FVAD_HIP(ctx, np->alloc(&np->state, M));
+    FVAD_HIP(ctx, np->alloc(&np->count, M));
+    FVAD_HIP(ctx, np->alloc(&np->audit, M));
+    FVAD_HIP(ctx, np->alloc(&np->stats, 2 * M));
+    FVAD_HIP(ctx, np->alloc(&np->paused, 1));
+    FVAD_HIP(ctx, hipMalloc((void**)&np->segs, std::max<size_t>(dp->seg_cap * M, 1) * sizeof(fvad_speech_segment)));
+    np->seg_cap = dp->seg_cap;
+    FVAD_HIP(ctx, hipMemcpyAsync(np->cfg, hc.data(), n_keep * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
+    if (G > 1) {
+        const std::vector<uint64_t> sizes(nb->sizes.begin(), nb->sizes.end());
+        FVAD_HIP(ctx, np->alloc(&np->sizes, G));
+        FVAD_HIP(ctx, np->alloc(&np->size_of, n_keep));
+        FVAD_HIP(ctx, np->alloc(&np->lane_config, n_keep));
+        FVAD_HIP(ctx, hipMemcpyAsync(np->sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(np->size_of, nb->size_of.data(), n_keep * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(np->lane_config, np->order.data(), n_keep * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    // new place -> old place, new machine -> old machine (the lane map is the first part's; the lane orders are each batch's own)
+    std::vector<long> place_src(M), machine_src(M);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t c = 0; c < n_keep; ++c) {
+            machine_src[s * n_keep + c] = (long)(s * NC + keep[c]);
+            place_src[(size_t)place_of(s, c, S, n_keep, dp->by_config, np->order)] = place_of(s, keep[c], S, NC, dp->by_config, dp->order);
+        }
+    DevScratch scratch;
+    long *d_place = nullptr, *d_machine = nullptr;
+    FVAD_HIP(ctx, scratch.alloc(&d_place, M));
+    FVAD_HIP(ctx, scratch.alloc(&d_machine, M));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_place, place_src.data(), M * sizeof(long), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_machine, machine_src.data(), M * sizeof(long), hipMemcpyHostToDevice, st));
+    VadRetainArgs a{};
+    a.n_places = (long)M;
+    a.old_places = (long)M_old;
+    a.place_src = d_place;
+    a.machine_src = d_machine;
+    a.lt_src = reinterpret_cast<const float4*>(dp->lt);
+    a.lt_dst = reinterpret_cast<float4*>(np->lt);
+    a.lt_rows = (long)std::min(lt_rows, old_lt_rows);
+    a.rings_src = dp->rings;
+    a.rings_dst = np->rings;
+    a.st = (int)st_max;
+    a.cr = (int)cr_max;
+    a.old_st = (int)dp->st_max;
+    a.state_src = dp->state;
+    a.state_dst = np->state;
+    a.count_src = dp->count;
+    a.count_dst = np->count;
+    a.audit_src = dp->audit;
+    a.audit_dst = np->audit;
+    a.stats_src = dp->stats;
+    a.stats_dst = np->stats;
+    a.segs_src = dp->segs;
+    a.segs_dst = np->segs;
+    a.seg_cap = (uint32_t)dp->seg_cap;
+    time_begin(ctx, "vad_retain");
+    const int e = fvad_launch_vad_retain(a, st);
+    time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_retain");
+    FVAD_HIP(ctx, hipStreamSynchronize(st)); // (before the old state and the maps are freed)
+    nb->dev_parts = std::unique_ptr<void, DevPartsDeleter>(fresh.release(), DevPartsDeleter{free_dev_parts});
+    return FVAD_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -688,6 +806,22 @@ int fvad_vad_batch_score_device(fvad_ctx* ctx, fvad_vad_batch* b)
     if (rc) return rc;
     b->scores = std::move(scores);
     b->scored = true;
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_retain_configs(fvad_ctx* ctx, fvad_vad_batch* b, const uint32_t* keep, size_t n_keep)
+{
+    auto fail = [&](int rc, const char* msg) { return ctx ? set_err(ctx, rc, msg) : rc; };
+    if (!b || !keep) return fail(FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+    if (dp && dp->ctx != ctx) return fail(FVAD_ERR_INVALID_ARGUMENT, "the batch's device parts ran on another context");
+    std::unique_ptr<fvad_vad_batch> nb(new (std::nothrow) fvad_vad_batch());
+    if (!nb) return fail(FVAD_ERR_ALLOC_FAILED, "retain");
+    if (const int rc = retain_stage(b, keep, n_keep, nb.get()))
+        return fail(rc, rc == FVAD_ERR_ALLOC_FAILED ? "retain" : "keep: a strictly increasing list of config indices, not empty");
+    if (dp)
+        if (const int rc = retain_device(ctx, b, nb.get(), keep, n_keep)) return rc;
+    retain_commit(b, keep, n_keep, nb.get());
     return FVAD_OK;
 }
 

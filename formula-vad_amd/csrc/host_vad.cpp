@@ -490,6 +490,97 @@ int fvad_vad_batch_bands(const fvad_vad_batch* b, int32_t* bins, size_t cap, siz
 } // extern "C"
 
 namespace fvad {
+
+int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb)
+{
+    const size_t NC = b->cfgs.size(), S = b->n_streams;
+    if (n_keep == 0 || !keep) return FVAD_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n_keep; ++i)
+        if (keep[i] >= NC || (i && keep[i] <= keep[i - 1])) return FVAD_ERR_INVALID_ARGUMENT;
+    try {
+        // the sizes and bands of the kept configs as make_sweep finds them: sizes in first-seen order, bands size-major and
+        // first-seen within a size (a band's bins are the old band's: the same config at the same size)
+        std::vector<uint32_t> size_of(n_keep);
+        for (size_t c = 0; c < n_keep; ++c) {
+            const size_t F = b->sizes[b->size_of[keep[c]]];
+            size_t g = 0;
+            while (g < nb->sizes.size() && nb->sizes[g] != F) ++g;
+            if (g == nb->sizes.size()) nb->sizes.push_back(F);
+            size_of[c] = (uint32_t)g;
+        }
+        const size_t G = nb->sizes.size();
+        std::vector<std::vector<int32_t>> bins(G);
+        std::vector<uint32_t> local(n_keep);
+        for (size_t c = 0; c < n_keep; ++c) {
+            const uint32_t ob = b->band_of[keep[c]];
+            const int32_t lo = b->bins[2 * ob], hi = b->bins[2 * ob + 1];
+            std::vector<int32_t>& bg = bins[size_of[c]];
+            size_t j = 0;
+            while (j < bg.size() / 2 && !(bg[2 * j] == lo && bg[2 * j + 1] == hi)) ++j;
+            if (j == bg.size() / 2) { bg.push_back(lo); bg.push_back(hi); }
+            local[c] = (uint32_t)j;
+        }
+        std::vector<uint32_t> first(G);
+        for (size_t g = 0; g < G; ++g) {
+            first[g] = (uint32_t)(nb->bins.size() / 2);
+            nb->bins.insert(nb->bins.end(), bins[g].begin(), bins[g].end());
+            nb->size_of_band.insert(nb->size_of_band.end(), bins[g].size() / 2, (uint32_t)g);
+        }
+        nb->band_of.resize(n_keep);
+        for (size_t c = 0; c < n_keep; ++c) nb->band_of[c] = first[size_of[c]] + local[c];
+        nb->size_of = std::move(size_of);
+        nb->sample_rate = b->sample_rate; nb->n_channels = b->n_channels; nb->fft_size = nb->sizes[0]; nb->n_streams = S;
+        nb->cfgs.resize(n_keep);
+        for (size_t c = 0; c < n_keep; ++c) nb->cfgs[c] = b->cfgs[keep[c]];
+        // per machine (stream s, config c) -> (s, keep[c])
+        const size_t M = S * n_keep;
+        nb->segs.resize(M);
+        nb->audits.resize(M);
+        nb->exact_evals.resize(M);
+        nb->lazy_pushes.resize(M);
+        if (b->scored) nb->scores.resize(M);
+        for (size_t s = 0; s < S; ++s)
+            for (size_t c = 0; c < n_keep; ++c) {
+                const size_t m = s * n_keep + c, o = s * NC + keep[c];
+                nb->audits[m] = b->audits[o];
+                nb->exact_evals[m] = b->exact_evals[o];
+                nb->lazy_pushes[m] = b->lazy_pushes[o];
+                if (b->scored) nb->scores[m] = b->scores[o];
+            }
+        if (!b->machines.empty()) nb->machines.resize(M);
+        if (b->has_refs) {
+            nb->refs = b->refs;
+            nb->ref_pmax = b->ref_pmax;
+            nb->ref_off = b->ref_off;
+            nb->stat_cfgs.resize(n_keep);
+            for (size_t c = 0; c < n_keep; ++c) nb->stat_cfgs[c] = b->stat_cfgs[keep[c]];
+        }
+    } catch (const std::bad_alloc&) {
+        return FVAD_ERR_ALLOC_FAILED;
+    }
+    nb->has_refs = b->has_refs;
+    nb->scored = b->scored;
+    nb->keep_segments = b->keep_segments;
+    nb->segs_kept = b->segs_kept;
+    nb->next_sample = b->next_sample;
+    return FVAD_OK;
+}
+
+void retain_commit(fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb)
+{
+    const size_t NC = b->cfgs.size();
+    for (size_t s = 0; s < b->n_streams; ++s)
+        for (size_t c = 0; c < n_keep; ++c) {
+            nb->segs[s * n_keep + c] = std::move(b->segs[s * NC + keep[c]]);
+            if (!nb->machines.empty()) nb->machines[s * n_keep + c] = std::move(b->machines[s * NC + keep[c]]);
+        }
+    if (!nb->dev_parts) nb->dev_parts = std::move(b->dev_parts); // (else nb holds the compacted device state: b's is freed here)
+    *b = std::move(*nb);
+}
+
+} // namespace fvad
+
+namespace fvad {
 // The volume ratio of every FFT frame of a stream (BufferedVolumeAnalyzer.zig:48-69 per chunk, the two metadata hand-overs
 // BufferedVolumeAnalyzer.zig:33-45 / BufferedDenoiser.zig:83-86,115, the sample-weighted frame ratio BufferedFFT.zig:137-140,153).
 // Frames [first_frame, first_frame + n_frames); chunk_rms(c, k) = channel c's RMS of chunk first_chunk + k.  Every frame

@@ -83,6 +83,17 @@ struct DevPartsDeleter {
 
 } // namespace fvad
 
+struct fvad_vad_batch;
+namespace fvad {
+// fvad_vad_batch_retain_configs in two steps, so that a failure leaves b as it was.  retain_stage: check keep (strictly
+// increasing, < n_configs, n_keep > 0) and build in *nb what b becomes -- the kept configs with their sizes and bands
+// recomputed in first-seen order, audits, lazy statistics, stat configs and scores compacted; nb->machines and nb->segs sized but
+// empty (b is not touched).  retain_commit (cannot fail): move b's kept machines and segments into nb, then nb's fields into b
+// (b's device part state too, unless nb already holds the compacted one).
+int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
+void retain_commit(fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
+} // namespace fvad
+
 // fvad_vad_batch (include/fvad.h): n_configs machines per stream, machine s * n_configs + c; a batch from
 // fvad_vad_batch_create has one config.  Segments and audits of the last run, machine by machine.
 struct fvad_vad_batch {

@@ -271,3 +271,31 @@ struct VadScoreArgs {
     fvad_single_stats* out;               // [n_machines]
 };
 int fvad_launch_vad_score(const VadScoreArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ dropping configs from a batch between device parts (kernels_vadretain.hip)
+// fvad_vad_batch_retain_configs: the resume-form state of the kept machines gathered into freshly allocated buffers of the smaller
+// batch.  Places (a lane's rings, VadMachinesArgs' lane map) and machines (the outputs, stream * n_configs + config) are gathered
+// through host-built maps new -> old; every index of the maps is < the old count.
+struct VadRetainArgs {
+    long n_places, old_places;        // new / old machine counts (places and machines are the same number)
+    const long* place_src;            // [n_places]: the old place of new place p
+    const long* machine_src;          // [n_places]: the old machine of new machine m
+    const float4* lt_src;             // old long-term rings [old lt_rows][old_places] float4
+    float4* lt_dst;                   // new [lt_rows][n_places] float4
+    long lt_rows;                     // rows of the new allocation (<= the old one's)
+    const float* rings_src;           // old [old_st + old_cr][old_places]
+    float* rings_dst;                 // new [st + cr][n_places]
+    int st, cr, old_st;               // new short-term / channel-ratio rows, the old short-term rows (the old cr rows follow them)
+    const fvad::VadLaneState* state_src;
+    fvad::VadLaneState* state_dst;
+    const uint32_t* count_src;
+    uint32_t* count_dst;
+    const fvad_vad_audit* audit_src;
+    fvad_vad_audit* audit_dst;
+    const unsigned long long* stats_src; // [machine][2]
+    unsigned long long* stats_dst;
+    const fvad_speech_segment* segs_src; // [old machine][seg_cap]
+    fvad_speech_segment* segs_dst;       // [machine][seg_cap]: min(count, seg_cap) of each
+    uint32_t seg_cap;
+};
+int fvad_launch_vad_retain(const VadRetainArgs& a, hipStream_t stream); // hipError_t as int

@@ -598,7 +598,7 @@ def check_slice_chunks_sized(slice_chunks, sizes):
 
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16, slice_chunks=None):
+             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -625,7 +625,19 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     device_bytes is set when sliced (else None): the peak of the slice buffers run_grid allocates, plus the largest
     VadSweep.device_bytes() of a batch, plus the engine's launch workspace for a slice's chunks computed from shapes
     (ENGINE_WS_BYTES_PER_CHUNK).  It excludes the context's own buffers (weights, FFT plans, the K4 pass's job
-    list), each part's frame ratios and the HIP runtime's overhead."""
+    list), each part's frame ratios and the HIP runtime's overhead.
+
+    halving_eta = eta, halving_rungs = R: successive halving over the time slices (both or neither; slice_chunks, vad_on "device"
+    and score_on "device" required, eta >= 2, R >= 1; ValueError before any GPU work otherwise).  The slices run one after the
+    other across the channel-count groups, every group's batch alive; at each rung of halving_schedule(longest instance in
+    chunks, slice_chunks, eta, R) every config is scored on the prefix run so far against the labels cut to it, the
+    ceil(n / eta) best by aggregate F-score (ties to the lower config index) are kept and the other configs' machines are
+    dropped from the batches (VadSweep.retain), so that later slices run fewer machines in less memory.  The result then also
+    has survivors (config indices), rung (per config: the rung it was dropped at, 1-based, None for survivors),
+    evaluated_seconds (per config: the seconds of audio its machines ran over all instances) and rung_times (per rung: end
+    chunk, configs in, configs kept, seconds; a last entry with rung None for the survivors' run to the end); stats holds the
+    whole corpus's statistics for survivors and the last prefix's for dropped configs, and the rows carry rung and
+    evaluated_seconds.  The table ranks the survivors, then prints one line per rung."""
     if isinstance(grid, str):
         with open(grid) as f:
             grid = json.load(f)
@@ -641,6 +653,18 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         raise ValueError(f"score_on: {score_on!r}")
     if score_on == "device" and vad_on != "device":
         raise ValueError("score_on='device' scores next to the device machines: it needs vad_on='device'")
+    halving = None
+    if halving_eta is not None or halving_rungs is not None:
+        if halving_eta is None or halving_rungs is None:
+            raise ValueError("halving_eta and halving_rungs go together")
+        if slice_chunks is None:
+            raise ValueError("successive halving drops configs between time slices: it needs slice_chunks")
+        if vad_on != "device":
+            raise ValueError(f"successive halving drops device machines: it needs vad_on='device' (got {vad_on!r})")
+        if score_on != "device":
+            raise ValueError(f"successive halving scores its rungs on the device: it needs score_on='device' (got {score_on!r})")
+        halving_schedule(1, 1, halving_eta, halving_rungs)   # (eta and rungs checked)
+        halving = {"eta": int(halving_eta), "rungs": int(halving_rungs)}
     plan = load_plan(plan_path)
     F = plan["fft_size"]
     if slice_chunks is not None:
@@ -679,7 +703,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if slice_chunks is not None:
         try:
             n_slices, dev_bytes = _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on,
-                                                   n_threads, stats, times, sizes_of if sized else None)
+                                                   n_threads, stats, times, sizes_of if sized else None, halving)
         finally:
             if own_ctx:
                 ctx.close()
@@ -782,15 +806,27 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if sized:
         for r in rows:
             r["fft_size"] = sizes_of[r["config"]]
+    if halving is not None:
+        for r in rows:
+            r["rung"] = halving["rung"][r["config"]]
+            r["evaluated_seconds"] = halving["evaluated_seconds"][r["config"]]
     elapsed = time.perf_counter() - t_all
     if json_path:
         with open(json_path, "w") as f:
-            json.dump({"grid": grid, "configs": configs, "rows": rows}, f, indent=1)
+            doc = {"grid": grid, "configs": configs, "rows": rows}
+            if halving is not None:
+                doc.update(survivors=halving["survivors"], rung_times=halving["rungs_run"])
+            json.dump(doc, f, indent=1)
     if out is not None:
-        out.write(f"top {min(top, NC)} of {NC} configs by F-score (β = 0.7):\n")
+        ranked = _ranked(rows) if halving is None else _ranked([r for r in rows if r["rung"] is None])
+        if halving is None:
+            out.write(f"top {min(top, NC)} of {NC} configs by F-score (β = 0.7):\n")
+        else:
+            out.write(f"top {min(top, len(ranked))} of {len(ranked)} surviving configs ({NC} in all, successive halving with "
+                      f"eta {halving['eta']}) by F-score (β = 0.7):\n")
         out.write("| config |" + (" fft_size |" if sized else "") +
                   "      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
-        for r in _ranked(rows)[:top]:
+        for r in ranked[:top]:
             out.write("| {:>6} |".format(r["config"]) + (" {:>8} |".format(r["fft_size"]) if sized else "") +
                       " {} | {} | {} | {} | {}% | {}% | {}% | {}% | {}% | {}% |\n".format(
                 _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
@@ -799,8 +835,17 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         out.write(f"[{NC} configs x {n_inst} instances in {elapsed:.2f} s: denoise {times['denoise']:.2f} s, bands "
                   f"{times['bands']:.2f} s, machines ({vad_on}) {times['machines']:.2f} s, scoring ({score_on}) "
                   f"{times['scoring']:.3f} s]\n")
-    return {"configs": configs, "rows": rows, "aggregates": aggs, "stats": stats, "times": times, "slices": n_slices,
-            "device_bytes": dev_bytes}
+        if halving is not None:
+            for g in halving["rungs_run"]:
+                name = f"rung {g['rung']}" if g["rung"] is not None else "to the end"
+                out.write(f"[{name} (chunk {g['end_chunk']}): {g['configs_in']} configs in, {g['configs_kept']} kept, "
+                          f"{g['seconds']:.2f} s]\n")
+    res = {"configs": configs, "rows": rows, "aggregates": aggs, "stats": stats, "times": times, "slices": n_slices,
+           "device_bytes": dev_bytes}
+    if halving is not None:
+        res.update(survivors=halving["survivors"], rung=halving["rung"], evaluated_seconds=halving["evaluated_seconds"],
+                   rung_times=halving["rungs_run"])
+    return res
 
 # the halo of a time slice: a slice is denoised from zero history this many chunks early (two are what NSNet2's cross-chunk state
 # needs; shard.ALIGN_CHUNKS), and the halo's chunks are dropped
@@ -811,7 +856,172 @@ ENGINE_WS_BYTES_PER_CHUNK = 4 * (54 * 176 + 50 * 161 * 2 + 54 * 25 * 3 * 16 + 2 
 ENGINE_MAX_LAUNCH_CHUNKS = 49152
 
 
-def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of=None):
+def halving_schedule(K, slice_chunks, eta, rungs):
+    """The rungs of successive halving over a corpus whose longest instance is K chunks, run in slices of slice_chunks: rung k
+    (k = 1 .. rungs) ends at the first slice boundary at or after K * eta^(k - 1 - rungs) chunks.  Rungs that land on the same
+    boundary are merged and rungs at or past the end are skipped -> the rungs' ends in chunks, increasing.  ValueError unless
+    eta >= 2 and rungs >= 1 (integers)."""
+    for name, v, lo in (("eta", eta, 2), ("rungs", rungs, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"halving {name} = {v!r}: an integer >= {lo}")
+    ends = []
+    for k in range(1, rungs + 1):
+        div = int(slice_chunks) * int(eta) ** (rungs + 1 - k)
+        end = -(-int(K) // div) * int(slice_chunks)   # ceil(K / eta^(rungs + 1 - k) / slice_chunks) slices
+        if end < K and (not ends or end > ends[-1]):
+            ends.append(end)
+    return ends
+
+
+def _clip_labels(ref, t):
+    """labels [(from, to)] cut to [0, t) seconds: a label starting at or after t goes, one running past t ends at t"""
+    a = np.asarray(ref, np.float32).reshape(-1, 2)
+    a = a[a[:, 0] < np.float32(t)].copy()
+    a[:, 1] = np.minimum(a[:, 1], np.float32(t))
+    return a
+
+
+def _halving_slices(ctx, audio, refs, groups, n_chunks, new_batch, stat_cfgs, F, N, halving, d, host, opts, fr_slice, stats, times):
+    """_run_grid_sliced with successive halving (run_grid's halving_eta / halving_rungs): every group's device batch alive at
+    once, the slices run one after the other across the groups, so that every rung sees every instance at the same point in
+    time.  At a rung's end: each group's machines scored on the device against its labels cut to the rung (or the instance's
+    end), aggregated per config over the instances in plan order, the ceil(n / eta) best by F-score kept (ties to the lower
+    config index) and every batch cut to them (VadSweep.retain); the full labels go back for the final scoring.  Fills stats
+    (survivors: the whole corpus; dropped configs: the last prefix they were scored on) and halving["survivors"], ["rung"]
+    (per config: the rung it was dropped at, None for survivors), ["evaluated_seconds"] (per config: seconds of audio its
+    machines ran, over all instances), ["rungs"] (per rung: end chunk, configs in, kept, seconds).  Returns (slices run, the
+    largest device memory the batches held together)."""
+    chunk = 24000
+    eta = int(halving["eta"])
+    K = max(n_chunks)
+    ends = halving_schedule(K, N, eta, int(halving["rungs"]))
+    NC = len(stat_cfgs)
+    alive = list(range(NC))                 # the original index of each config the batches hold
+    rung_of = [None] * NC
+    evaluated = np.zeros(NC)
+    log = []
+    batches = {}
+    peak, n_slices = 0, 0
+    t_rung = time.perf_counter()
+    try:
+        for nch, members in groups.items():
+            b = new_batch(len(members), nch)
+            batches[nch] = b
+            b.set_references([refs[i] for i in members], stat_cfgs)
+            b.keep_segments(False)
+        for s0 in range(0, K, N):
+            s1 = min(s0 + N, K)
+            for nch, members in groups.items():
+                b = batches[nch]
+                if s0 >= max(n_chunks[i] for i in members):
+                    continue   # every instance of the group has ended
+                n_slices += 1
+                sized = isinstance(b, fv.VadSweepSized)
+                blocks = b.size_blocks() if sized else [(F, 0, b.bands()[0])]
+                sizes = [Fg for Fg, _, _ in blocks] if not sized else b.sizes
+                rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times)
+                nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
+                nf_g = [[max(0, min(n_chunks[i] * chunk // Fg, s1 * chunk // Fg) - s0 * chunk // Fg) for i in members] for Fg in sizes]
+                t0 = time.perf_counter()
+                if sized:
+                    b.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
+                else:
+                    b.run_device_part(ctx, d["bands"], fr_slice, nf_g[0], rms, nc, s0 * chunk // F)
+                times["machines"] += time.perf_counter() - t0
+            peak = max(peak, sum(b.device_bytes() for b in batches.values()))
+            for i in range(len(n_chunks)):
+                evaluated[alive] += (min(n_chunks[i], s1) - min(n_chunks[i], s0)) * chunk / 48000.0
+            if s1 not in ends:
+                continue
+            # ---- a rung: score the prefix [0, s1) against the labels cut to it, keep the best 1 / eta
+            t0 = time.perf_counter()
+            t_end = s1 * chunk / 48000.0
+            cur_cfgs = [stat_cfgs[o] for o in alive]
+            for nch, members in groups.items():
+                b = batches[nch]
+                b.set_references([_clip_labels(refs[i], min(t_end, n_chunks[i] * chunk / 48000.0)) for i in members], cur_cfgs)
+                b.score_device(ctx)
+                for c, o in enumerate(alive):
+                    stats[o, members] = b.config_stats(c)
+            times["scoring"] += time.perf_counter() - t0
+            rows = [dict(config=c, F=_agg_row(fv.stats_aggregate_array(np.ascontiguousarray(stats[o])))["F"])
+                    for c, o in enumerate(alive)]
+            n_keep = -(-len(alive) // eta)
+            keep = sorted(r["config"] for r in _ranked(rows)[:n_keep])
+            t0 = time.perf_counter()
+            for b in batches.values():
+                b.retain(ctx, keep)
+            times["retain"] = times.get("retain", 0.0) + time.perf_counter() - t0
+            kept = set(keep)
+            for c, o in enumerate(alive):
+                if c not in kept:
+                    rung_of[o] = len(log) + 1
+            n_in = len(alive)
+            alive = [alive[c] for c in keep]
+            for nch, members in groups.items():   # the full labels for what follows
+                batches[nch].set_references([refs[i] for i in members], [stat_cfgs[o] for o in alive])
+            now = time.perf_counter()
+            log.append({"rung": len(log) + 1, "end_chunk": s1, "configs_in": n_in, "configs_kept": len(alive),
+                        "seconds": now - t_rung})
+            t_rung = now
+        # ---- the survivors over the whole corpus
+        t0 = time.perf_counter()
+        for nch, members in groups.items():
+            b = batches[nch]
+            b.score_device(ctx)
+            for c, o in enumerate(alive):
+                stats[o, members] = b.config_stats(c)
+        times["scoring"] += time.perf_counter() - t0
+        log.append({"rung": None, "end_chunk": K, "configs_in": len(alive), "configs_kept": len(alive),
+                    "seconds": time.perf_counter() - t_rung})
+    finally:
+        for b in batches.values():
+            b.close()
+    halving.update(survivors=alive, rung=rung_of, evaluated_seconds=evaluated.tolist(), rungs_run=log)
+    return n_slices, peak
+
+
+def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times):
+    """one time slice [s0, s1) of a channel-count group (_run_grid_sliced): the slice and its SLICE_HALO_CHUNKS-chunk halo read
+    from the mapped files into the pinned host buffer, denoised from zero history, the band sums of the slice's frames for
+    blocks [(F, first band, bins)] written to d["bands"] (stride fr_slice); returns the slice's chunk RMS [lanes][s1 - s0]"""
+    chunk = 24000
+    start = max(s0 - SLICE_HALO_CHUNKS, 0)
+    n = s1 - start
+    L = len(members) * nch
+    # ---- read and denoise [start, s1): lane l of the group at host[l * n * chunk]
+    t0 = time.perf_counter()
+    pcm = host[:L * n * chunk].reshape(L, n * chunk)
+    for k, i in enumerate(members):
+        a = audio[i]
+        lo, hi = start * chunk, min(s1 * chunk, a.shape[0])
+        for c in range(nch):
+            row = pcm[k * nch + c]
+            if hi > lo:
+                if a.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                    np.multiply(a[lo:hi, c], np.float32(1.0 / 32768.0), out=row[:hi - lo], casting="unsafe")
+                else:
+                    row[:hi - lo] = a[lo:hi, c]
+            row[max(hi - lo, 0):] = 0.0
+    ctx.to_device(d["pcm"], pcm)
+    ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d["pcm"]), L, n * chunk, n * chunk, fv.vp(d["den"]),
+                                                fv.vp(d["band0"]), fv.vp(d["rms"]), fv.C.byref(opts)),
+            "fvad_engine_enqueue_device")
+    rms = ctx.to_host(np.empty((L, n), np.float32), d["rms"])
+    rms = np.ascontiguousarray(rms[:, s0 - start:])
+    times["denoise"] += time.perf_counter() - t0
+    # ---- band sums of the slice's frames: the denoised audio from chunk s0 on (frame-aligned: s0 is a
+    # multiple of slice_align(F))
+    t0 = time.perf_counter()
+    for Fg, j0, bins_g in blocks:
+        ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins_g,
+                             d["bands"] + j0 * L * fr_slice * 4, fr_slice, fft_size=Fg)
+    times["bands"] += time.perf_counter() - t0
+    return rms
+
+
+def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of=None,
+                     halving=None):
     """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
     SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
     (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
@@ -821,7 +1031,8 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
     largest group, and reused slice after slice.  Fills stats [config][instance][11] and times; returns (slices run,
     device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
     batch, one band-sum pass per size and slice, and parts from sample s0 * chunk (fvad_vad_batch_run_device_part_sized /
-    fvad_vad_batch_run_sized)."""
+    fvad_vad_batch_run_sized).  halving: a dict {"eta", "rungs"} for successive halving -- _halving_slices' loop instead of
+    the one below, which adds its results to the dict."""
     chunk, H = 24000, SLICE_HALO_CHUNKS
     n_chunks = [a.shape[0] // chunk for a in audio]
     groups = {}
@@ -856,10 +1067,15 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
     host = None
     batch_peak = 0
     n_slices = 0
+    ws = ENGINE_WS_BYTES_PER_CHUNK * min(lanes_max * n_max, ENGINE_MAX_LAUNCH_CHUNKS)
     try:
         for k, nb in own.items():
             d[k] = ctx.device_alloc(max(nb, 16))
         host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
+        if halving is not None:
+            n_slices, batch_peak = _halving_slices(ctx, audio, refs, groups, n_chunks, new_batch, stat_cfgs, F, N, halving, d, host,
+                                                   opts, fr_slice, stats, times)
+            return n_slices, sum(own.values()) + batch_peak + ws
         for nch, members in groups.items():
             L = len(members) * nch
             K = max(n_chunks[i] for i in members)
@@ -876,37 +1092,8 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
             try:
                 for s0 in range(0, K, N):
                     s1 = min(s0 + N, K)
-                    start = max(s0 - H, 0)
-                    n = s1 - start
                     n_slices += 1
-                    # ---- read and denoise [start, s1): lane l of the group at host[l * n * chunk]
-                    t0 = time.perf_counter()
-                    pcm = host[:L * n * chunk].reshape(L, n * chunk)
-                    for k, i in enumerate(members):
-                        a = audio[i]
-                        lo, hi = start * chunk, min(s1 * chunk, a.shape[0])
-                        for c in range(nch):
-                            row = pcm[k * nch + c]
-                            if hi > lo:
-                                if a.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
-                                    np.multiply(a[lo:hi, c], np.float32(1.0 / 32768.0), out=row[:hi - lo], casting="unsafe")
-                                else:
-                                    row[:hi - lo] = a[lo:hi, c]
-                            row[max(hi - lo, 0):] = 0.0
-                    ctx.to_device(d["pcm"], pcm)
-                    ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d["pcm"]), L, n * chunk, n * chunk, fv.vp(d["den"]),
-                                                                fv.vp(d["band0"]), fv.vp(d["rms"]), fv.C.byref(opts)),
-                            "fvad_engine_enqueue_device")
-                    rms = ctx.to_host(np.empty((L, n), np.float32), d["rms"])
-                    rms = np.ascontiguousarray(rms[:, s0 - start:])
-                    times["denoise"] += time.perf_counter() - t0
-                    # ---- band sums of the slice's frames: the denoised audio from chunk s0 on (frame-aligned: s0 is a
-                    # multiple of slice_align(F))
-                    t0 = time.perf_counter()
-                    for Fg, j0, bins_g in blocks:
-                        ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins_g,
-                                             d["bands"] + j0 * L * fr_slice * 4, fr_slice, fft_size=Fg)
-                    times["bands"] += time.perf_counter() - t0
+                    rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times)
                     # each size's frames of the slice, per instance
                     nf_g = [[max(0, min(e, s1 * chunk // Fg) - s0 * chunk // Fg) for e in ends] for (Fg, _, _), ends in zip(blocks, nf_end)]
                     nf = nf_g[0]
@@ -967,7 +1154,6 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
             ctx.device_free(a)
         if host is not None:
             ctx.host_free(host)
-    ws = ENGINE_WS_BYTES_PER_CHUNK * min(lanes_max * n_max, ENGINE_MAX_LAUNCH_CHUNKS)
     return n_slices, sum(own.values()) + batch_peak + ws
 
 
@@ -1016,10 +1202,15 @@ def main(argv=None):
                     help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
                          "sizes, of the lcm over them), device and host "
                          "memory bounded by the slice instead of the corpus")
+    ap.add_argument("--halving-eta", type=int, default=None,
+                    help="with --sweep-grid and --slice-chunks: successive halving, keeping the best 1/ETA of the configs at each "
+                         "rung (the machines and scoring on the GPU)")
+    ap.add_argument("--halving-rungs", type=int, default=None,
+                    help="with --halving-eta: the number of rungs R (rung k ends at ETA^(k-1-R) of the corpus)")
     a = ap.parse_args(argv)
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
-                 slice_chunks=a.slice_chunks)
+                 slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)

@@ -493,6 +493,23 @@ int fvad_vad_batch_run_device_part(fvad_ctx *ctx, fvad_vad_batch *b, const float
                                    const size_t *n_chunks, size_t chunk_size, uint64_t first_frame);
 int fvad_vad_batch_score_device(fvad_ctx *ctx, fvad_vad_batch *b);
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch *b);
+/* Keep configs keep[0] < keep[1] < ... < keep[n_keep - 1] of b and drop the rest, between runs or between the parts of a run
+ * (successive halving: drop the configs that lose on a prefix, run the survivors on).  Afterwards b is in every observable way
+ * the batch fvad_vad_batch_create_sweep (or _create_sweep_sized) would make from cfgs[keep[0..n_keep)] (and their sizes) after
+ * the same runs or parts; new config c is old config keep[c].
+ * - n_configs, the bands and band_of, the frame sizes and size_of_band are the kept configs', recomputed in first-seen order (a
+ *   band or a size no kept config uses disappears); segments (host or device), audits, lazy statistics, held scores, stat configs
+ *   and segment counts are restricted to the kept configs; references stay as set.
+ * - Allowed on a batch that has not run, after host runs and parts, after a one-shot device run (its results in b are compacted)
+ *   and between device parts: every later part, host or device, sized or not, gives the bits a fresh batch of the kept configs
+ *   would give over all the parts.
+ * - Between device parts the machines' state is gathered on the device (csrc/kernels_vadretain.hip) into new buffers of the kept
+ *   machines' size -- the rings as long as the longest kept config needs, in LDS or global memory as the kept configs allow --
+ *   and then the old state is freed: for the call, device memory peaks at the old plus the new fvad_vad_batch_device_bytes.
+ * - ctx may be NULL unless b holds device part state; then it must be the parts' context.
+ * FVAD_ERR_INVALID_ARGUMENT for n_keep == 0, a list not strictly increasing, an index >= n_configs, NULL arguments or the wrong
+ * context.  On any error (allocation failures included) b is unchanged and still usable. */
+int fvad_vad_batch_retain_configs(fvad_ctx *ctx, fvad_vad_batch *b, const uint32_t *keep, size_t n_keep);
 
 /* Sweeps over the FFT size (VADPipeline.Config.fft_size): config c's machines run on frames of fft_sizes[c] samples (each even,
  * 4 .. 16384, else FVAD_ERR_INVALID_ARGUMENT; each config checked as fvad_vad_batch_create_sweep checks it, at its own size).
