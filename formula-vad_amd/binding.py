@@ -369,6 +369,7 @@ class Context:
     def __init__(self, device=0):
         self.h = vp()
         check(lib().fvad_ctx_create(device, C.byref(self.h)), "fvad_ctx_create")
+        self.device = int(device)
 
     def close(self):
         if self.h:

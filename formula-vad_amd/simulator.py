@@ -5,8 +5,9 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
 
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
-    python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K]   (or: run_grid(path, grid): a parameter grid,
-                                                      every machine scored on the GPU, the top K configs by F-score)
+    python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
+                                                      parameter grid, every machine scored on the GPU, the top K configs by
+                                                      F-score; with --devices the instances dealt round-robin to the GPUs)
 
 Plan schema = the reference's (simulator.zig:41-76, tmp/plan.example.json), unknown fields ignored
 (simulator.zig:152-154); audio/ref paths are relative to the plan file (simulator.zig:146,
@@ -23,12 +24,23 @@ import json
 import math
 import os
 import sys
+import threading
 import time
 from decimal import ROUND_HALF_UP, Decimal
 
 import numpy as np
 
-from . import binding as fv
+if __package__:
+    from . import binding as fv
+else:   # run as a file (python formula-vad_amd/simulator.py): the directory's name is not an identifier, load it as the package
+    import importlib.util
+    _dir = os.path.dirname(os.path.abspath(__file__))
+    _spec = importlib.util.spec_from_file_location("formula_vad_amd", os.path.join(_dir, "__init__.py"),
+                                                   submodule_search_locations=[_dir])
+    _pkg = importlib.util.module_from_spec(_spec)
+    sys.modules["formula_vad_amd"] = _pkg
+    _spec.loader.exec_module(_pkg)
+    fv = _pkg.binding
 
 VAD_FIELDS = ("speech_min_freq", "speech_max_freq", "long_term_speech_avg_sec", "initial_long_term_avg",
               "short_term_speech_avg_sec", "speech_threshold_factor", "channel_vol_ratio_avg_sec",
@@ -231,6 +243,12 @@ def _map_audio(inst):
     return pcm
 
 
+def instance_shares(n_instances, n_devices):
+    """How run_plan and run_grid deal a plan's instances to n_devices contexts: instance i to share i % n_devices, each share
+    in plan order -> [[instance]] per share (a share may be empty)"""
+    return [[i for i in range(n_instances) if i % n_devices == d] for d in range(n_devices)]
+
+
 def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None):
     """Runs a whole plan; returns (report_text, per_instance_results).
 
@@ -261,7 +279,7 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
     refs = [r for _, r in loaded]
     t0 = time.perf_counter()
     n_ctx = len(ctxs)
-    parts = [[i for i in range(len(audio)) if i % n_ctx == d] for d in range(n_ctx)]
+    parts = instance_shares(len(audio), n_ctx)
     done = [None] * n_ctx
     errs = []
 
@@ -597,8 +615,36 @@ def check_slice_chunks_sized(slice_chunks, sizes):
                          f"(the lcm of lcm(24000, fft_size) / 24000 over the sizes: slices start on a frame of every size)")
 
 
+_Context = fv.Context   # the class, for run_grid's argument check
+
+
+def _check_grid_contexts(ctx, devices):
+    """run_grid's rules for ctx and devices (ValueError, before any context is made or GPU work done) -> the number of shares,
+    or None for one context (ctx a Context or None and devices None)"""
+    if ctx is not None and devices is not None:
+        raise ValueError("run_grid takes ctx or devices, not both")
+    if devices is not None:
+        if not isinstance(devices, (list, tuple)) or not devices:
+            raise ValueError(f"devices = {devices!r}: a non-empty list of HIP device indices")
+        for d in devices:
+            if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0:
+                raise ValueError(f"devices: {d!r} is not a HIP device index (an integer >= 0)")
+        return len(devices)
+    if isinstance(ctx, (list, tuple)):
+        if not ctx:
+            raise ValueError("ctx = []: a list of contexts is not empty")
+        for c in ctx:
+            if not isinstance(c, _Context):
+                raise ValueError(f"ctx: {c!r} is not a Context")
+        if len({id(c) for c in ctx}) != len(ctx):
+            raise ValueError("ctx: a context appears twice (each share runs on a context of its own; two contexts may share "
+                             "a device)")
+        return len(ctx)
+    return None
+
+
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None):
+             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -637,7 +683,28 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     evaluated_seconds (per config: the seconds of audio its machines ran over all instances) and rung_times (per rung: end
     chunk, configs in, configs kept, seconds; a last entry with rung None for the survivors' run to the end); stats holds the
     whole corpus's statistics for survivors and the last prefix's for dropped configs, and the rows carry rung and
-    evaluated_seconds.  The table ranks the survivors, then prints one line per rung."""
+    evaluated_seconds.  The table ranks the survivors, then prints one line per rung.
+
+    Several devices: devices = [HIP device indices] (one context made and closed per entry, as run_plan makes them; an index
+    may repeat) or ctx = [Context, ...] (the caller's, with the caller's options, left open) deals the instances to shares:
+    instance i to share i % n in plan order (instance_shares, as run_plan).  One host thread per share runs the flow above
+    on its own context over its own instances -- the denoising batch padded to the share's longest instance, its own
+    channel-count groups, slice buffers sized for its own largest group -- and writes its instances' columns of stats; a
+    share without instances makes no context and does no work.  Host machines and host scoring get max(1, n_threads //
+    shares at work) threads each.  With halving, the rungs are those of the whole plan's longest instance: at each rung
+    every share scores its batches, one thread aggregates stats over all instances in plan order and picks the configs to
+    keep, and every share retains them, so survivors, rung, evaluated_seconds and the rung ends and counts are one
+    context's.  The aggregates, ranking, table and JSON are built over all instances in plan order as above.  If a share
+    fails, the others stop at their next slice or rung, everything is freed (the contexts run_grid made closed) and the
+    first exception is raised here.  ValueError (before any context or GPU work) for both ctx and devices, an empty list,
+    a device index that is not an integer >= 0, or a ctx list holding something other than a Context, or one twice.  On
+    contexts with the option reproducible = 1 the statistics are the single context's bit for bit, sliced or not; by
+    default the NN kernels the engine selects depend on the launch size, which can move the gains by about 1e-6 and flip
+    a decision.  The result then also has share_times (per share: device, instances, wall seconds, stage times) and
+    device_bytes_per_share (each share's device_bytes); times and slices are sums over the shares (times in GPU-seconds),
+    device_bytes the largest share's, and with more than one share the summary line adds each share's wall time.  With one
+    context (ctx a Context or None, devices None) no thread is started and the result is as described above."""
+    n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
             grid = json.load(f)
@@ -682,125 +749,79 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         if any(x != x for r in ref for x in r):
             raise ValueError(f"{inst['ref_path']}: a NaN label; grid scoring walks the labels sorted by start and needs "
                              "numbers (fvad_vad_batch_set_references refuses NaN)")
-    own_ctx = ctx is None
-    if own_ctx:
-        ctx = _make_ctx(plan, 0, synth_seed)
     audio = [a for a, _ in loaded]
     refs = [r for _, r in loaded]
     NC, n_inst = len(configs), len(audio)
     stats = np.empty((NC, n_inst, len(fv.SingleStats._fields_)), np.float32)
-    times = {"denoise": 0.0, "bands": 0.0, "machines": 0.0, "scoring": 0.0}
-    chunk = 24000
-    t_all = time.perf_counter()
-    allocs = []
-
-    def dalloc(nbytes):
-        a = ctx.device_alloc(max(int(nbytes), 16))
-        allocs.append(a)
-        return a
-
-    n_slices, dev_bytes = 1, None
-    if slice_chunks is not None:
+    shares = instance_shares(n_inst, n_shares or 1)
+    workers = [s for s, share in enumerate(shares) if share]   # an empty share makes no context and does no work
+    if n_shares is None:   # one context: no thread
+        ctxs, owned = [ctx if ctx is not None else _make_ctx(plan, 0, synth_seed)], [ctx is None]
+    elif devices is not None:
+        ctxs, owned = [None] * n_shares, [True] * n_shares
         try:
-            n_slices, dev_bytes = _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on,
-                                                   n_threads, stats, times, sizes_of if sized else None, halving)
-        finally:
-            if own_ctx:
-                ctx.close()
+            for s in workers:
+                ctxs[s] = _make_ctx(plan, int(devices[s]), synth_seed)
+        except BaseException:
+            for c in ctxs:
+                if c is not None:
+                    c.close()
+            raise
     else:
+        ctxs, owned = list(ctx), [False] * n_shares
+    rungs = None
+    if halving is not None:   # the schedule over the longest instance of the whole plan, whatever the shares
+        rungs = _Rungs(len(workers), halving, [a.shape[0] // 24000 for a in audio], int(slice_chunks), stats, stat_cfgs)
+    share_times = [{"device": int(devices[s]) if devices is not None else getattr(ctxs[s], "device", None), "instances": shares[s],
+                    "wall": 0.0, "times": {}} for s in range(len(shares))]
+    share_out = [(0, None)] * len(shares)
+    stop = threading.Event()   # set when a worker fails: the others stop at their next slice or rung
+    errs, breaks = [], []
+    t_all = time.perf_counter()
+
+    def work(s):
+        t0 = time.perf_counter()
+        st = share_times[s]["times"]
+        st.update(denoise=0.0, bands=0.0, machines=0.0, scoring=0.0)
+        ids = np.asarray(shares[s], np.intp)
         try:
-            t0 = time.perf_counter()
-            groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
-            times["denoise"] = time.perf_counter() - t0
-            l0 = 0
-            for nch, members in groups.items():
-                if sized:   # several frame sizes in one batch: one band-sum pass per size into its run of band blocks
-                    sweep = fv.VadSweepSized(len(members), configs, sizes_of, n_channels=nch)
-                else:
-                    sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
-                try:
-                    t0 = time.perf_counter()
-                    bins, _ = sweep.bands()
-                    g_lanes = list(range(l0, l0 + len(members) * nch))
-                    l0 += len(g_lanes)
-                    d_gden = d_den + g_lanes[0] * n_den * 4
-                    if sized:
-                        bstride = max(n_den // min(sweep.sizes), 1)
-                        d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                        for Fg, j0, bins_g in sweep.size_blocks():
-                            if n_den // Fg:
-                                ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins_g,
-                                                     d_gband + j0 * len(g_lanes) * bstride * 4, bstride, fft_size=Fg)
-                        nf_run = [[n_chunks[i] * chunk // Fg for i in members] for Fg in sweep.sizes]
-                    else:
-                        bstride = max(nf_all, 1)
-                        d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                        if nf_all:
-                            ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
-                        nf_run = [n_chunks[i] * chunk // F for i in members]
-                    g_rms = np.ascontiguousarray(rms[g_lanes])
-                    times["bands"] += time.perf_counter() - t0
-                    if vad_on == "device":
-                        if score_on == "device":
-                            sweep.set_references([refs[i] for i in members], stat_cfgs)
-                            sweep.keep_segments(False)
-                        # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
-                        # caller's own timing records are left alone: the machines' time then includes the scoring)
-                        timed = score_on == "device" and not ctx.timing
-                        if timed:
-                            ctx.enable_timing(True)
-                        try:
-                            t0 = time.perf_counter()
-                            sweep.run_device(ctx, d_gband, bstride, nf_run, g_rms, [n_chunks[i] for i in members])
-                            wall = time.perf_counter() - t0
-                            score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
-                        finally:
-                            if timed:
-                                ctx.enable_timing(False)
-                        if score_on == "device":
-                            times["machines"] += wall - score_s
-                            times["scoring"] += score_s
-                        else:
-                            times["machines"] += wall
-                            t0 = time.perf_counter()
-                            sweep.set_references([refs[i] for i in members], stat_cfgs)
-                            sweep.score(n_threads)
-                            times["scoring"] += time.perf_counter() - t0
-                        for c in range(NC):
-                            stats[c, members] = sweep.config_stats(c)
-                        continue
-                    gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
-                    for k, i in enumerate(members):   # instances differ in length: one host batch each
-                        if sized:
-                            one = fv.VadSweepSized(1, configs, sizes_of, n_channels=nch)
-                        else:
-                            nf_i = n_chunks[i] * chunk // F
-                            one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
-                        try:
-                            t0 = time.perf_counter()
-                            i_rms = np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)])
-                            if sized:
-                                nf_i = [n_chunks[i] * chunk // Fg for Fg in one.sizes]
-                                one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :max(max(nf_i), 1)]), i_rms, nf_i,
-                                        n_threads=n_threads)
-                            else:
-                                one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]), i_rms, n_threads=n_threads)
-                            times["machines"] += time.perf_counter() - t0
-                            t0 = time.perf_counter()
-                            one.set_references([refs[i]], stat_cfgs)
-                            one.score(n_threads)
-                            for c in range(NC):
-                                stats[c, i] = one.config_stats(c)[0]
-                            times["scoring"] += time.perf_counter() - t0
-                        finally:
-                            one.close()
-                finally:
-                    sweep.close()
+            share_out[s] = _grid_share(ctxs[s], [audio[i] for i in shares[s]], [refs[i] for i in shares[s]], ids, configs,
+                                       stat_cfgs, sizes_of if sized else None, F, slice_chunks, vad_on, score_on,
+                                       max(1, n_threads // len(workers)), stats, st, rungs, stop)
+        except (threading.BrokenBarrierError, _Stopped) as e:   # another worker failed
+            breaks.append(e)
+        except BaseException as e:  # re-raised below, in the caller's thread
+            errs.append(e)
+            stop.set()
+            if rungs is not None:
+                rungs.barrier.abort()
         finally:
-            for a in allocs:
-                ctx.device_free(a)
-            if own_ctx:
-                ctx.close()
+            share_times[s]["wall"] = time.perf_counter() - t0
+
+    try:
+        if len(workers) == 1:
+            work(workers[0])
+        else:
+            th = [threading.Thread(target=work, args=(s,), name=f"run_grid share {s}") for s in workers]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+    finally:
+        for c, own in zip(ctxs, owned):
+            if own and c is not None:
+                c.close()
+    if errs or breaks:
+        raise (errs or breaks)[0]
+    times = {}
+    for s in workers:
+        for k, v in share_times[s]["times"].items():
+            times[k] = times.get(k, 0.0) + v
+    n_slices = sum(share_out[s][0] for s in workers)
+    bytes_per_share = [share_out[s][1] for s in range(len(shares))]
+    dev_bytes = max((b for b in bytes_per_share if b is not None), default=None)
+    if halving is not None:
+        halving.update(survivors=rungs.alive, rung=rungs.rung_of, evaluated_seconds=rungs.evaluated.tolist(), rungs_run=rungs.log)
     aggs = [fv.stats_aggregate_array(stats[c]) for c in range(NC)]
     rows = [dict(config=c, **_agg_row(agg)) for c, agg in enumerate(aggs)]
     if sized:
@@ -832,9 +853,12 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
                 _f(r["P"], 6, 1), _f(r["TP"], 6, 1), _f(r["FP"], 6, 1), _f(r["FN"], 6, 1),
                 *[_f(np.float32(r[k]) * np.float32(100), 5, 1) for k in ("TPR", "PPV", "FNR", "FDR")],
                 _f(np.float32(r["F"]) * np.float32(100), 6, 1), _f(np.float32(r["FM"]) * np.float32(100), 5, 1)))
+        per_share = ""
+        if len(shares) > 1:   # the stage times are sums over the shares; each share's own wall time
+            per_share = "; shares' wall times " + ", ".join(f"{t['wall']:.2f}" for t in share_times) + " s"
         out.write(f"[{NC} configs x {n_inst} instances in {elapsed:.2f} s: denoise {times['denoise']:.2f} s, bands "
                   f"{times['bands']:.2f} s, machines ({vad_on}) {times['machines']:.2f} s, scoring ({score_on}) "
-                  f"{times['scoring']:.3f} s]\n")
+                  f"{times['scoring']:.3f} s{per_share}]\n")
         if halving is not None:
             for g in halving["rungs_run"]:
                 name = f"rung {g['rung']}" if g["rung"] is not None else "to the end"
@@ -845,7 +869,198 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if halving is not None:
         res.update(survivors=halving["survivors"], rung=halving["rung"], evaluated_seconds=halving["evaluated_seconds"],
                    rung_times=halving["rungs_run"])
+    if n_shares is not None:
+        res.update(share_times=share_times, device_bytes_per_share=bytes_per_share)
     return res
+
+class _Stopped(Exception):
+    """a run_grid worker stopping because another one failed"""
+
+
+def _check_stop(stop):
+    if stop.is_set():
+        raise _Stopped()
+
+
+class _Rungs:
+    """Successive halving's decisions, shared by the workers of one run_grid call (one per share of the instances, each with its
+    own context and batches; a single worker on a single context).  The rungs are halving_schedule's over the longest instance
+    of the whole plan.  At a rung every worker scores its own batches into the shared stats and waits at the barrier; the
+    barrier's action, run by one thread once all have arrived, aggregates stats over all instances in plan order and picks the
+    configs to keep.  A failing worker aborts the barrier, so that none is left waiting."""
+
+    def __init__(self, n_workers, halving, n_chunks, slice_chunks, stats, stat_cfgs):
+        self.eta = int(halving["eta"])
+        self.n_chunks = n_chunks                 # every instance's, plan order
+        self.K = max(n_chunks)
+        self.ends = halving_schedule(self.K, slice_chunks, self.eta, int(halving["rungs"]))
+        self.stats, self.stat_cfgs = stats, stat_cfgs
+        NC = len(stat_cfgs)
+        self.alive = list(range(NC))             # the original index of each config the batches hold
+        self.rung_of = [None] * NC
+        self.evaluated = np.zeros(NC)
+        self.log = []
+        self.keep, self.n_in = None, None        # the last rung's keep list (indices into alive as it was) and its length
+        self.t_rung = time.perf_counter()
+        self._step = None
+        self.lock = threading.Lock()
+        self.barrier = threading.Barrier(n_workers, action=lambda: self._step())
+
+    def wait(self, step):
+        """every worker passes the same step; it runs once, when the last worker arrives"""
+        self._step = step
+        self.barrier.wait()
+
+    def count(self, ids, s0, s1):
+        """add the seconds of audio the alive configs' machines ran over instances ids (plan indices) in slice [s0, s1)"""
+        with self.lock:
+            for i in ids:
+                n = self.n_chunks[i]
+                self.evaluated[self.alive] += (min(n, s1) - min(n, s0)) * 24000 / 48000.0
+
+    def choose(self):
+        """the ceil(n / eta) best alive configs by aggregate F-score over the prefix (ties to the lower config index)"""
+        rows = [dict(config=c, F=_agg_row(fv.stats_aggregate_array(np.ascontiguousarray(self.stats[o])))["F"])
+                for c, o in enumerate(self.alive)]
+        n_keep = -(-len(self.alive) // self.eta)
+        self.keep = sorted(r["config"] for r in _ranked(rows)[:n_keep])
+        kept = set(self.keep)
+        for c, o in enumerate(self.alive):
+            if c not in kept:
+                self.rung_of[o] = len(self.log) + 1
+        self.n_in = len(self.alive)
+        self.alive = [self.alive[c] for c in self.keep]
+
+    def logged(self):
+        now = time.perf_counter()
+        self.log.append({"rung": len(self.log) + 1, "end_chunk": self.ends[len(self.log)], "configs_in": self.n_in,
+                         "configs_kept": len(self.alive), "seconds": now - self.t_rung})
+        self.t_rung = now
+
+    def ended(self):
+        self.log.append({"rung": None, "end_chunk": self.K, "configs_in": len(self.alive), "configs_kept": len(self.alive),
+                         "seconds": time.perf_counter() - self.t_rung})
+
+
+def _grid_share(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, slice_chunks, vad_on, score_on, n_threads, stats, times,
+                rungs, stop):
+    """run_grid's flow for one share of the instances on its own context: audio / refs the share's instances, ids their plan
+    indices (the columns of stats it fills); sizes_of None unless the grid is sized; rungs a _Rungs for successive halving;
+    stop an Event another worker sets when it fails.  Returns (slices run, device_bytes: None unsliced)."""
+    if slice_chunks is not None:
+        return _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on, n_threads, stats,
+                                times, sizes_of, rungs, stop)
+    _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_on, score_on, n_threads, stats, times, stop)
+    return 1, None
+
+
+def _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_on, score_on, n_threads, stats, times, stop):
+    """run_grid without slices over a share: one denoising batch of the share's instances (padded to its longest), then per
+    channel-count group the band sums, the machines and the scoring (run_grid's docstring)"""
+    sized = sizes_of is not None
+    NC = len(configs)
+    chunk = 24000
+    allocs = []
+
+    def dalloc(nbytes):
+        a = ctx.device_alloc(max(int(nbytes), 16))
+        allocs.append(a)
+        return a
+
+    try:
+        t0 = time.perf_counter()
+        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
+        times["denoise"] = time.perf_counter() - t0
+        l0 = 0
+        for nch, members in groups.items():
+            _check_stop(stop)
+            if sized:   # several frame sizes in one batch: one band-sum pass per size into its run of band blocks
+                sweep = fv.VadSweepSized(len(members), configs, sizes_of, n_channels=nch)
+            else:
+                sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+            try:
+                t0 = time.perf_counter()
+                bins, _ = sweep.bands()
+                g_lanes = list(range(l0, l0 + len(members) * nch))
+                l0 += len(g_lanes)
+                d_gden = d_den + g_lanes[0] * n_den * 4
+                if sized:
+                    bstride = max(n_den // min(sweep.sizes), 1)
+                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                    for Fg, j0, bins_g in sweep.size_blocks():
+                        if n_den // Fg:
+                            ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins_g,
+                                                 d_gband + j0 * len(g_lanes) * bstride * 4, bstride, fft_size=Fg)
+                    nf_run = [[n_chunks[i] * chunk // Fg for i in members] for Fg in sweep.sizes]
+                else:
+                    bstride = max(nf_all, 1)
+                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
+                    if nf_all:
+                        ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
+                    nf_run = [n_chunks[i] * chunk // F for i in members]
+                g_rms = np.ascontiguousarray(rms[g_lanes])
+                times["bands"] += time.perf_counter() - t0
+                if vad_on == "device":
+                    if score_on == "device":
+                        sweep.set_references([refs[i] for i in members], stat_cfgs)
+                        sweep.keep_segments(False)
+                    # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
+                    # caller's own timing records are left alone: the machines' time then includes the scoring)
+                    timed = score_on == "device" and not ctx.timing
+                    if timed:
+                        ctx.enable_timing(True)
+                    try:
+                        t0 = time.perf_counter()
+                        sweep.run_device(ctx, d_gband, bstride, nf_run, g_rms, [n_chunks[i] for i in members])
+                        wall = time.perf_counter() - t0
+                        score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
+                    finally:
+                        if timed:
+                            ctx.enable_timing(False)
+                    if score_on == "device":
+                        times["machines"] += wall - score_s
+                        times["scoring"] += score_s
+                    else:
+                        times["machines"] += wall
+                        t0 = time.perf_counter()
+                        sweep.set_references([refs[i] for i in members], stat_cfgs)
+                        sweep.score(n_threads)
+                        times["scoring"] += time.perf_counter() - t0
+                    for c in range(NC):
+                        stats[c, ids[members]] = sweep.config_stats(c)
+                    continue
+                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
+                for k, i in enumerate(members):   # instances differ in length: one host batch each
+                    _check_stop(stop)
+                    if sized:
+                        one = fv.VadSweepSized(1, configs, sizes_of, n_channels=nch)
+                    else:
+                        nf_i = n_chunks[i] * chunk // F
+                        one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
+                    try:
+                        t0 = time.perf_counter()
+                        i_rms = np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)])
+                        if sized:
+                            nf_i = [n_chunks[i] * chunk // Fg for Fg in one.sizes]
+                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :max(max(nf_i), 1)]), i_rms, nf_i,
+                                    n_threads=n_threads)
+                        else:
+                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]), i_rms, n_threads=n_threads)
+                        times["machines"] += time.perf_counter() - t0
+                        t0 = time.perf_counter()
+                        one.set_references([refs[i]], stat_cfgs)
+                        one.score(n_threads)
+                        for c in range(NC):
+                            stats[c, ids[i]] = one.config_stats(c)[0]
+                        times["scoring"] += time.perf_counter() - t0
+                    finally:
+                        one.close()
+            finally:
+                sweep.close()
+    finally:
+        for a in allocs:
+            ctx.device_free(a)
+
 
 # the halo of a time slice: a slice is denoised from zero history this many chunks early (two are what NSNet2's cross-chunk state
 # needs; shard.ALIGN_CHUNKS), and the halo's chunks are dropped
@@ -881,36 +1096,29 @@ def _clip_labels(ref, t):
     return a
 
 
-def _halving_slices(ctx, audio, refs, groups, n_chunks, new_batch, stat_cfgs, F, N, halving, d, host, opts, fr_slice, stats, times):
-    """_run_grid_sliced with successive halving (run_grid's halving_eta / halving_rungs): every group's device batch alive at
-    once, the slices run one after the other across the groups, so that every rung sees every instance at the same point in
-    time.  At a rung's end: each group's machines scored on the device against its labels cut to the rung (or the instance's
-    end), aggregated per config over the instances in plan order, the ceil(n / eta) best by F-score kept (ties to the lower
-    config index) and every batch cut to them (VadSweep.retain); the full labels go back for the final scoring.  Fills stats
-    (survivors: the whole corpus; dropped configs: the last prefix they were scored on) and halving["survivors"], ["rung"]
-    (per config: the rung it was dropped at, None for survivors), ["evaluated_seconds"] (per config: seconds of audio its
-    machines ran, over all instances), ["rungs"] (per rung: end chunk, configs in, kept, seconds).  Returns (slices run, the
-    largest device memory the batches held together)."""
+def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts, fr_slice, stats, times, stop):
+    """_run_grid_sliced with successive halving (run_grid's halving_eta / halving_rungs) over one share: every group's device
+    batch alive at once, the slices run one after the other across the groups, so that every rung sees every instance at the
+    same point in time.  At a rung's end (rungs.ends: the whole plan's): each group's machines scored on the device against
+    its labels cut to the rung (or the instance's end) into stats' columns ids[members]; then, with every share's workers
+    at the barrier, rungs.choose aggregates per config over all instances in plan order and keeps the ceil(n / eta) best by
+    F-score (ties to the lower config index); every batch is cut to them (VadSweep.retain) and the full labels go back.  A
+    share whose instances have all ended still scores and retains at every rung.  Fills stats (survivors: the whole corpus;
+    dropped configs: the last prefix they were scored on) and rungs' survivors, rung, evaluated seconds and log.  Returns
+    (slices run, the largest device memory the share's batches held together)."""
     chunk = 24000
-    eta = int(halving["eta"])
-    K = max(n_chunks)
-    ends = halving_schedule(K, N, eta, int(halving["rungs"]))
-    NC = len(stat_cfgs)
-    alive = list(range(NC))                 # the original index of each config the batches hold
-    rung_of = [None] * NC
-    evaluated = np.zeros(NC)
-    log = []
+    stat_cfgs = rungs.stat_cfgs
     batches = {}
     peak, n_slices = 0, 0
-    t_rung = time.perf_counter()
     try:
         for nch, members in groups.items():
             b = new_batch(len(members), nch)
             batches[nch] = b
             b.set_references([refs[i] for i in members], stat_cfgs)
             b.keep_segments(False)
-        for s0 in range(0, K, N):
-            s1 = min(s0 + N, K)
+        for s0 in range(0, rungs.K, N):
+            _check_stop(stop)
+            s1 = min(s0 + N, rungs.K)
             for nch, members in groups.items():
                 b = batches[nch]
                 if s0 >= max(n_chunks[i] for i in members):
@@ -929,55 +1137,40 @@ def _halving_slices(ctx, audio, refs, groups, n_chunks, new_batch, stat_cfgs, F,
                     b.run_device_part(ctx, d["bands"], fr_slice, nf_g[0], rms, nc, s0 * chunk // F)
                 times["machines"] += time.perf_counter() - t0
             peak = max(peak, sum(b.device_bytes() for b in batches.values()))
-            for i in range(len(n_chunks)):
-                evaluated[alive] += (min(n_chunks[i], s1) - min(n_chunks[i], s0)) * chunk / 48000.0
-            if s1 not in ends:
+            rungs.count(ids, s0, s1)
+            if s1 not in rungs.ends:
                 continue
             # ---- a rung: score the prefix [0, s1) against the labels cut to it, keep the best 1 / eta
             t0 = time.perf_counter()
             t_end = s1 * chunk / 48000.0
-            cur_cfgs = [stat_cfgs[o] for o in alive]
+            cur_cfgs = [stat_cfgs[o] for o in rungs.alive]
             for nch, members in groups.items():
                 b = batches[nch]
                 b.set_references([_clip_labels(refs[i], min(t_end, n_chunks[i] * chunk / 48000.0)) for i in members], cur_cfgs)
                 b.score_device(ctx)
-                for c, o in enumerate(alive):
-                    stats[o, members] = b.config_stats(c)
+                for c, o in enumerate(rungs.alive):
+                    stats[o, ids[members]] = b.config_stats(c)
             times["scoring"] += time.perf_counter() - t0
-            rows = [dict(config=c, F=_agg_row(fv.stats_aggregate_array(np.ascontiguousarray(stats[o])))["F"])
-                    for c, o in enumerate(alive)]
-            n_keep = -(-len(alive) // eta)
-            keep = sorted(r["config"] for r in _ranked(rows)[:n_keep])
+            rungs.wait(rungs.choose)
             t0 = time.perf_counter()
             for b in batches.values():
-                b.retain(ctx, keep)
+                b.retain(ctx, rungs.keep)
             times["retain"] = times.get("retain", 0.0) + time.perf_counter() - t0
-            kept = set(keep)
-            for c, o in enumerate(alive):
-                if c not in kept:
-                    rung_of[o] = len(log) + 1
-            n_in = len(alive)
-            alive = [alive[c] for c in keep]
             for nch, members in groups.items():   # the full labels for what follows
-                batches[nch].set_references([refs[i] for i in members], [stat_cfgs[o] for o in alive])
-            now = time.perf_counter()
-            log.append({"rung": len(log) + 1, "end_chunk": s1, "configs_in": n_in, "configs_kept": len(alive),
-                        "seconds": now - t_rung})
-            t_rung = now
+                batches[nch].set_references([refs[i] for i in members], [stat_cfgs[o] for o in rungs.alive])
+            rungs.wait(rungs.logged)
         # ---- the survivors over the whole corpus
         t0 = time.perf_counter()
         for nch, members in groups.items():
             b = batches[nch]
             b.score_device(ctx)
-            for c, o in enumerate(alive):
-                stats[o, members] = b.config_stats(c)
+            for c, o in enumerate(rungs.alive):
+                stats[o, ids[members]] = b.config_stats(c)
         times["scoring"] += time.perf_counter() - t0
-        log.append({"rung": None, "end_chunk": K, "configs_in": len(alive), "configs_kept": len(alive),
-                    "seconds": time.perf_counter() - t_rung})
+        rungs.wait(rungs.ended)
     finally:
         for b in batches.values():
             b.close()
-    halving.update(survivors=alive, rung=rung_of, evaluated_seconds=evaluated.tolist(), rungs_run=log)
     return n_slices, peak
 
 
@@ -1020,19 +1213,19 @@ def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, bl
     return rms
 
 
-def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of=None,
-                     halving=None):
+def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of, rungs,
+                     stop):
     """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
     SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
     (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
     computed from the denoised audio at chunk s0 (fvad_engine_band_sums_device), and the machines run on: one device batch
     per group in parts (fvad_vad_batch_run_device_part), or with vad_on "host" one host batch per instance
     (fvad_vad_batch_run_part).  An instance gets 0 frames once it has ended.  The device buffers are allocated once, for the
-    largest group, and reused slice after slice.  Fills stats [config][instance][11] and times; returns (slices run,
-    device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
+    largest group, and reused slice after slice.  Fills stats [config][instance][11] (the columns ids: the instances' plan
+    indices) and times; returns (slices run, device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
     batch, one band-sum pass per size and slice, and parts from sample s0 * chunk (fvad_vad_batch_run_device_part_sized /
-    fvad_vad_batch_run_sized).  halving: a dict {"eta", "rungs"} for successive halving -- _halving_slices' loop instead of
-    the one below, which adds its results to the dict."""
+    fvad_vad_batch_run_sized).  rungs: a _Rungs for successive halving -- _halving_slices' loop instead of the one below.
+    stop: checked before every slice (_Stopped once another worker has failed)."""
     chunk, H = 24000, SLICE_HALO_CHUNKS
     n_chunks = [a.shape[0] // chunk for a in audio]
     groups = {}
@@ -1072,9 +1265,9 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
         for k, nb in own.items():
             d[k] = ctx.device_alloc(max(nb, 16))
         host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
-        if halving is not None:
-            n_slices, batch_peak = _halving_slices(ctx, audio, refs, groups, n_chunks, new_batch, stat_cfgs, F, N, halving, d, host,
-                                                   opts, fr_slice, stats, times)
+        if rungs is not None:
+            n_slices, batch_peak = _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts,
+                                                   fr_slice, stats, times, stop)
             return n_slices, sum(own.values()) + batch_peak + ws
         for nch, members in groups.items():
             L = len(members) * nch
@@ -1091,6 +1284,7 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
                 hosts = [new_batch(1, nch) for _ in members]
             try:
                 for s0 in range(0, K, N):
+                    _check_stop(stop)
                     s1 = min(s0 + N, K)
                     n_slices += 1
                     rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times)
@@ -1136,13 +1330,13 @@ def _run_grid_sliced(ctx, audio, refs, configs, stat_cfgs, F, N, vad_on, score_o
                         dev.set_references([refs[i] for i in members], stat_cfgs)
                         dev.score(n_threads)
                     for c in range(len(configs)):
-                        stats[c, members] = dev.config_stats(c)
+                        stats[c, ids[members]] = dev.config_stats(c)
                 else:
                     for k, (i, h) in enumerate(zip(members, hosts)):
                         h.set_references([refs[i]], stat_cfgs)
                         h.score(n_threads)
                         for c in range(len(configs)):
-                            stats[c, i] = h.config_stats(c)[0]
+                            stats[c, ids[i]] = h.config_stats(c)[0]
                 times["scoring"] += time.perf_counter() - t0
             finally:
                 if dev is not None:
@@ -1186,8 +1380,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="Formula-VAD simulator harness on MI355X")
     ap.add_argument("-i", "--input", required=True, help="Simulation plan (path to JSON)")  # simulator.zig:78-82
     ap.add_argument("--synth-seed", type=int, default=None, help="use random-init NSNet2 weights")
-    ap.add_argument("--devices", default="0", help="comma-separated HIP devices: one context + one thread each, "
-                                                   "instances dealt round-robin (e.g. 0,1,2,3,4,5,6,7)")
+    ap.add_argument("--devices", default=None, help="comma-separated HIP devices (default 0): one context + one thread each, "
+                                                    "instances dealt round-robin (e.g. 0,1,2,3,4,5,6,7); for a plan run and "
+                                                    "--sweep-grid")
     ap.add_argument("--sweep", action="store_true", help="score the plan's vad_machine_config and alt_vad_machine_configs over one "
                                                          "denoising pass: one table row per config (device 0)")
     ap.add_argument("--sweep-json", default=None, help="with --sweep: write the rows and segments to this JSON file; "
@@ -1196,7 +1391,7 @@ def main(argv=None):
                     help="with --sweep / --sweep-grid: where the VAD machines run (auto: the GPU from %d configs on)" % SWEEP_DEVICE_MIN_CONFIGS)
     ap.add_argument("--sweep-grid", default=None, help="score every config of a grid file ({\"base\": {...}, \"axes\": {field: "
                                                           "[values]}}, optionally \"fft_size\": [sizes]) over one denoising pass; "
-                                                          "print the top configs (device 0)")
+                                                          "print the top configs (on --devices, default device 0)")
     ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
     ap.add_argument("--slice-chunks", type=int, default=None,
                     help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
@@ -1208,14 +1403,15 @@ def main(argv=None):
     ap.add_argument("--halving-rungs", type=int, default=None,
                     help="with --halving-eta: the number of rungs R (rung k ends at ETA^(k-1-R) of the corpus)")
     a = ap.parse_args(argv)
+    devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
-                 slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs)
+                 slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)
         return
-    run_plan(a.input, synth_seed=a.synth_seed, devices=[int(d) for d in a.devices.split(",") if d != ""])
+    run_plan(a.input, synth_seed=a.synth_seed, devices=devices or [0])
 
 
 if __name__ == "__main__":
