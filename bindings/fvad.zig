@@ -328,6 +328,10 @@ pub extern "c" fn fvad_vad_batch_frame_sizes(b: *const VadBatch, sizes: ?[*]usiz
 pub extern "c" fn fvad_vad_batch_run_sized(b: *VadBatch, band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: usize, chunk_size: usize, first_sample: u64, n_threads: c_int) c_int;
 pub extern "c" fn fvad_vad_batch_run_device_sized(ctx: *Ctx, b: *VadBatch, d_band: [*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: [*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize) c_int;
 pub extern "c" fn fvad_vad_batch_run_device_part_sized(ctx: *Ctx, b: *VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64) c_int;
+pub extern "c" fn fvad_vad_batch_run_device_part_async(ctx: *Ctx, b: *VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, d_chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64) c_int;
+pub extern "c" fn fvad_vad_batch_part_wait(ctx: *Ctx, b: *VadBatch) c_int;
+pub extern "c" fn fvad_vad_batch_frame_ratios_device(ctx: *Ctx, b: *const VadBatch, d_chunk_rms: ?[*]const f32, rms_stride: usize, n_frames: [*]const usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, d_ratio: ?[*]f32, ratio_stride: usize) c_int;
+pub extern "c" fn fvad_vad_batch_frame_ratios(b: *const VadBatch, chunk_rms: ?[*]const f32, rms_stride: usize, n_frames: [*]const usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, ratio: ?[*]f32, ratio_stride: usize) c_int;
 pub extern "c" fn fvad_ra_create(count: usize, has_initial: c_int, initial_val: f64, out: *?*RollingAverage) c_int;
 pub extern "c" fn fvad_ra_destroy(ra: ?*RollingAverage) void;
 pub extern "c" fn fvad_ra_push(ra: *RollingAverage, sample: f32) f64;

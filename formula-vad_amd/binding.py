@@ -245,6 +245,10 @@ SIGNATURES = {
     "fvad_vad_batch_run_sized": (C.c_int, [vp, c_float_p, sz, C.POINTER(sz), c_float_p, sz, sz, sz, C.c_uint64, C.c_int]),
     "fvad_vad_batch_run_device_sized": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz]),
     "fvad_vad_batch_run_device_part_sized": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
+    "fvad_vad_batch_run_device_part_async": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), sz, C.c_uint64]),
+    "fvad_vad_batch_part_wait": (C.c_int, [vp, vp]),
+    "fvad_vad_batch_frame_ratios_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), sz, C.c_uint64, vp, sz]),
+    "fvad_vad_batch_frame_ratios": (C.c_int, [vp, c_float_p, sz, C.POINTER(sz), C.POINTER(sz), sz, C.c_uint64, c_float_p, sz]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
     "fvad_ra_push": (C.c_double, [vp, C.c_float]),
@@ -952,6 +956,41 @@ class VadSweep:
         ctx._ck(lib().fvad_vad_batch_run_device_part(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf, fptr(chunk_rms),
                                                      chunk_rms.shape[1], nc, chunk_size, int(first_frame)),
                 "fvad_vad_batch_run_device_part")
+
+    def _sized_counts(self, n_frames, n_chunks):
+        """n_frames [stream] or [size][stream], n_chunks [stream] as the sized calls take them"""
+        flat = [int(x) for row in n_frames for x in (row if hasattr(row, "__len__") else [row])]
+        assert len(flat) % self.n_streams == 0 and len(n_chunks) == self.n_streams
+        return (sz * len(flat))(*flat), (sz * self.n_streams)(*[int(x) for x in n_chunks])
+
+    def run_device_part_async(self, ctx, d_band, band_stride, n_frames, d_chunk_rms, rms_stride, n_chunks, first_sample, chunk_size=24000):
+        """fvad_vad_batch_run_device_part_async: the sized part call (n_frames [stream] with one size, else [size][stream]) with
+        the chunk RMS on the device (lane l's chunks at d_chunk_rms + 4 * l * rms_stride); returns once the part is queued on the
+        context's second stream.  d_band and d_chunk_rms stay untouched, and the batch is not to be used, until part_wait."""
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_run_device_part_async(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf,
+                                                           vp(d_chunk_rms) if d_chunk_rms else None, rms_stride, nc, chunk_size,
+                                                           int(first_sample)), "fvad_vad_batch_run_device_part_async")
+
+    def part_wait(self, ctx):
+        """fvad_vad_batch_part_wait: finish the part run_device_part_async started (nothing in flight: nothing to do)"""
+        ctx._ck(lib().fvad_vad_batch_part_wait(ctx.h, self.h), "fvad_vad_batch_part_wait")
+
+    def frame_ratios_device(self, ctx, d_chunk_rms, rms_stride, n_frames, n_chunks, first_sample, d_ratio, ratio_stride, chunk_size=24000):
+        """fvad_vad_batch_frame_ratios_device: the frame ratios a device part computes, row (size, stream) at
+        d_ratio + 4 * row * ratio_stride"""
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_frame_ratios_device(ctx.h, self.h, vp(d_chunk_rms), rms_stride, nf, nc, chunk_size, int(first_sample),
+                                                         vp(d_ratio), ratio_stride), "fvad_vad_batch_frame_ratios_device")
+
+    def frame_ratios(self, chunk_rms, n_frames, n_chunks, first_sample=0, chunk_size=24000):
+        """fvad_vad_batch_frame_ratios: the same rows on the host from chunk_rms [lanes][chunks] -> float32 [rows][max frames]"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        out = np.zeros((len(nf), max(1, max(nf))), np.float32)
+        check(lib().fvad_vad_batch_frame_ratios(self.h, fptr(chunk_rms), chunk_rms.shape[1], nf, nc, chunk_size, int(first_sample),
+                                                fptr(out), out.shape[1]), "fvad_vad_batch_frame_ratios")
+        return out
 
     def score_device(self, ctx):
         """fvad_vad_batch_score_device: score the segments the device parts left on the device (keep_segments off); read the

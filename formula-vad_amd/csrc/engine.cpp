@@ -321,6 +321,7 @@ void fvad_ctx_destroy(fvad_ctx* ctx)
 {
     if (!ctx) return;
     hipSetDevice(ctx->device);
+    if (ctx->part_stream) hipStreamSynchronize(ctx->part_stream);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     for (auto& kv : ctx->vad_plans) if (kv.second.d) hipFree(kv.second.d);
     free_workspace_nn(ctx->ws);
@@ -369,6 +370,8 @@ void fvad_ctx_destroy(fvad_ctx* ctx)
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     if (ctx->d_tables) hipFree(ctx->d_tables);
     for (auto& kt : ctx->times) { hipEventDestroy(kt.e0); hipEventDestroy(kt.e1); }
+    if (ctx->part_ev) hipEventDestroy(ctx->part_ev);
+    if (ctx->part_stream) hipStreamDestroy(ctx->part_stream);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -378,6 +381,7 @@ const char* fvad_last_error(const fvad_ctx* ctx) { return ctx ? ctx->err.c_str()
 int fvad_ctx_synchronize(fvad_ctx* ctx)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (ctx->part_stream) FVAD_HIP(ctx, hipStreamSynchronize(ctx->part_stream)); // (a device part in flight: what it has queued)
     FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FVAD_OK;
 }

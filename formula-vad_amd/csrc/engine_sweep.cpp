@@ -1,7 +1,8 @@
 // engine_sweep.cpp -- parameter sweeps on the GPU: several speech bands per K4 pass (fvad_engine_band_sums_device) and every
 // (stream, config) VAD machine of a sweep batch at once (fvad_vad_batch_run_device, kernels_vad.hip), scored against the
 // streams' labels on the device when the batch has them (kernels_eval.hip); the same machines in parts, their state kept in
-// device memory between the parts (fvad_vad_batch_run_device_part, fvad_vad_batch_score_device).
+// device memory between the parts (fvad_vad_batch_run_device_part, fvad_vad_batch_score_device); parts that do not wait, on the
+// context's second stream, their frame ratios from the device's chunk RMS (fvad_vad_batch_run_device_part_async, _part_wait).
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -39,6 +40,20 @@ struct DevScratch {
     }
 };
 
+struct DevParts;
+// One part between its launch and its results: run_device_part launches it and finish_part brings the results back.  The blocking
+// part calls do both in one call; fvad_vad_batch_run_device_part_async leaves it in DevParts::flight for fvad_vad_batch_part_wait.
+struct PartFlight {
+    DevScratch scratch;            // the part's per-call inputs (frame ratios, frame and chunk counts)
+    VadMachinesArgs a{};           // the launch (segs / seg_cap follow the segment buffer)
+    hipStream_t st = nullptr;      // the stream it runs on
+    std::vector<size_t> n_frames;  // [n_sizes][n_streams]
+    std::vector<size_t> P;         // each size's longest stream in the part
+    size_t most = 0;               // segments no machine can exceed
+    bool keep = false;
+    uint64_t first_sample = 0;
+};
+
 // The device state of a batch run in parts (fvad_vad_batch_run_device_part), held by the batch between the parts: the machines
 // (kernels_vad.hip's resume form: VadLaneState, the long-term rings, the short-term and channel-ratio rings), their outputs and
 // the segment buffer.  Freed with the batch (fvad_vad_batch_destroy) or when a run starts afresh.
@@ -69,9 +84,11 @@ struct DevParts {
     std::vector<uint8_t> ended;          // streams that got fewer frames than a part's longest
     std::vector<uint32_t> count_h;       // every machine's segment count after the last part
     bool segs_on_device = true;          // every part so far left its segments on the device: they are all in segs
+    std::unique_ptr<PartFlight> flight;  // a part launched and not yet waited for (fvad_vad_batch_run_device_part_async)
     ~DevParts()
     {
         hipSetDevice(device);
+        if (flight) hipDeviceSynchronize(); // (a batch destroyed with its part in flight: the kernels read what is freed below)
         for (void* p : ptrs) hipFree(p);
         hipFree(segs);
     }
@@ -407,17 +424,158 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
     return FVAD_OK;
 }
 
-// one part of every machine of b (fvad_vad_batch_run_device_part and _run_device_part_sized); n_frames [n_sizes][n_streams],
-// frames from sample first_sample on
+// the segment buffer of dp with room for cap segments per machine (M machines), the old contents kept
+int grow_segs(fvad_ctx* ctx, DevParts* dp, size_t M, size_t cap, hipStream_t st)
+{
+    fvad_speech_segment* d = nullptr;
+    FVAD_HIP(ctx, hipMalloc((void**)&d, std::max<size_t>(cap * M, 1) * sizeof(fvad_speech_segment)));
+    if (dp->segs && dp->seg_cap) {
+        const size_t w = dp->seg_cap * sizeof(fvad_speech_segment);
+        const hipError_t e = hipMemcpy2DAsync(d, cap * sizeof(fvad_speech_segment), dp->segs, w, w, M, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) hipStreamSynchronize(st);
+        if (e != hipSuccess) { hipFree(d); return hip_fail(ctx, e, "hipMemcpy2DAsync"); }
+    }
+    hipFree(dp->segs);
+    dp->segs = d;
+    dp->seg_cap = cap;
+    return FVAD_OK;
+}
+
+// the machines of a part on its stream (the first launch, and again after a pause); the kernel-time table is the main stream's
+int launch_part(fvad_ctx* ctx, DevParts* dp, PartFlight& pf)
+{
+    pf.a.segs = dp->segs;
+    pf.a.seg_cap = (uint32_t)dp->seg_cap;
+    FVAD_HIP(ctx, hipMemsetAsync(dp->paused, 0, sizeof(unsigned), pf.st));
+    const bool timed = pf.st == ctx->stream;
+    if (timed) time_begin(ctx, "vad_machines");
+    const int e = fvad_launch_vad_machines(pf.a, pf.st);
+    if (timed) time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
+    return FVAD_OK;
+}
+
+// the rest of a launched part: wait, go on with more segment room while machines paused, bring the results into b
+int finish_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
+{
+    const size_t S = b->n_streams, NC = b->cfgs.size(), G = b->sizes.size();
+    const size_t M = S * NC;
+    hipStream_t st = pf.st;
+    const bool keep = pf.keep;
+    const uint64_t first_sample = pf.first_sample;
+    const std::vector<size_t>& P = pf.P;
+    for (;;) {
+        unsigned paused = 0;
+        FVAD_HIP(ctx, hipMemcpyAsync(&paused, dp->paused, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        FVAD_HIP(ctx, hipStreamSynchronize(st));
+        if (!paused) break;
+        // a machine ran out of room: go on from where each machine stopped, with twice the room (no machine needs more than most)
+        const size_t cap = std::min(2 * dp->seg_cap, pf.most);
+        if (cap <= dp->seg_cap) return set_err(ctx, FVAD_ERR_HIP, "vad machines: more segments than frames allow");
+        if (const int rc = grow_segs(ctx, dp, M, cap, st)) return rc;
+        pf.a.fresh = 0;
+        pf.a.rebase = 0;
+        if (const int rc = launch_part(ctx, dp, pf)) return rc;
+    }
+
+    // ---- results: everything run so far
+    std::vector<uint32_t> count(M);
+    std::vector<fvad_vad_audit> audits(M);
+    std::vector<unsigned long long> stats(2 * M);
+    FVAD_HIP(ctx, hipMemcpyAsync(count.data(), dp->count, M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), dp->audit, M * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), dp->stats, 2 * M * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<fvad_speech_segment> segs;
+    size_t used = 0; // the part's segments: machine m's new ones at the start of its row
+    if (keep) {
+        for (size_t m = 0; m < M; ++m) used = std::max<size_t>(used, count[m] - dp->count_h[m]);
+        segs.resize(used * M);
+        if (used) {
+            const size_t w = used * sizeof(fvad_speech_segment);
+            FVAD_HIP(ctx, hipMemcpy2DAsync(segs.data(), w, dp->segs, dp->seg_cap * sizeof(fvad_speech_segment), w, M, hipMemcpyDeviceToHost, st));
+            FVAD_HIP(ctx, hipStreamSynchronize(st));
+        }
+    }
+    FVAD_HIP(ctx, hipGetLastError());
+    const bool all_kept = keep && (first_sample == 0 || b->segs_kept);
+    for (size_t m = 0; m < M; ++m) {
+        auto& v = b->segs[m];
+        if (all_kept) {
+            const fvad_speech_segment* sm = segs.data() + m * used;
+            v.insert(v.end(), sm, sm + (count[m] - dp->count_h[m]));
+        } else {
+            std::vector<fvad_speech_segment>().swap(v);
+        }
+        b->exact_evals[m] = stats[2 * m];
+        b->lazy_pushes[m] = stats[2 * m + 1];
+    }
+    b->audits = std::move(audits);
+    dp->count_h = std::move(count);
+    for (size_t g = 0; g < G; ++g)
+        for (size_t s = 0; s < S; ++s)
+            if (pf.n_frames[g * S + s] < P[g]) dp->ended[s] = 1;
+    uint64_t next = first_sample + P[0] * b->sizes[0];
+    for (size_t g = 1; g < G; ++g)
+        if (first_sample + P[g] * b->sizes[g] != next) next = UINT64_MAX; // (the sizes ended apart: no part can follow)
+    dp->next_sample = next;
+    b->segs_kept = all_kept;
+    b->scored = false; // the scores were of the previous segments
+    return FVAD_OK;
+}
+
+// the context's second stream and the event that orders it behind the main one (fvad_vad_batch_run_device_part_async)
+int part_stream(fvad_ctx* ctx, hipStream_t* out)
+{
+    if (!ctx->part_stream) FVAD_HIP(ctx, hipStreamCreateWithFlags(&ctx->part_stream, hipStreamNonBlocking));
+    if (!ctx->part_ev) FVAD_HIP(ctx, hipEventCreateWithFlags(&ctx->part_ev, hipEventDisableTiming));
+    *out = ctx->part_stream;
+    return FVAD_OK;
+}
+
+// the frame ratios of a part on the device (kernels_vadratio.hip): rows (size, stream) ratio_stride apart, from the device's chunk
+// RMS; d_counts holds n_frames [n_sizes][n_streams] and then n_chunks [n_streams]; d_sizes null with one size
+int device_ratios(fvad_ctx* ctx, const fvad_vad_batch* b, const uint64_t* d_sizes, const long* d_counts, const float* d_chunk_rms,
+                  size_t rms_stride, size_t chunk_size, uint64_t first_sample, float* d_ratio, size_t ratio_stride, size_t max_nf, hipStream_t st)
+{
+    const size_t S = b->n_streams, G = b->sizes.size();
+    VadRatioArgs ra{};
+    ra.chunk_rms = d_chunk_rms;
+    ra.rms_stride = (long)rms_stride;
+    ra.n_channels = (int)b->n_channels;
+    ra.n_sizes = (int)G;
+    ra.n_streams = (long)S;
+    ra.sizes = d_sizes;
+    ra.fft_size = b->fft_size;
+    ra.n_frames = d_counts;
+    ra.n_chunks = d_counts + G * S;
+    ra.chunk_size = chunk_size;
+    ra.first_sample = first_sample;
+    ra.ratio = d_ratio;
+    ra.ratio_stride = (long)ratio_stride;
+    ra.max_frames = (long)max_nf;
+    const bool timed = st == ctx->stream;
+    if (timed) time_begin(ctx, "vad_ratios");
+    const int e = fvad_launch_vad_frame_ratios(ra, st);
+    if (timed) time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_frame_ratios");
+    return FVAD_OK;
+}
+
+// one part of every machine of b (fvad_vad_batch_run_device_part, _run_device_part_sized and _run_device_part_async); n_frames
+// [n_sizes][n_streams], frames from sample first_sample on.  The blocking calls give the chunk RMS on the host (chunk_rms) and
+// return with the results; the async call gives it on the device (d_chunk_rms) and returns once the part is queued on the
+// context's second stream, behind everything the main stream holds at that moment.
 int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
-                    const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size, uint64_t first_sample)
+                    const float* chunk_rms, const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                    uint64_t first_sample, bool async)
 {
     const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, G = b->sizes.size();
     const size_t M = S * NC;
     std::vector<size_t> P; // each size's longest stream in the part: a stream with fewer frames of some size has ended
     if (const char* msg = frame_counts(b, n_frames, n_chunks, chunk_size, &P)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, msg);
     const size_t max_nf = *std::max_element(P.begin(), P.end());
-    if (max_nf && (!d_band || !chunk_rms)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (max_nf && (!d_band || !(async ? d_chunk_rms : chunk_rms))) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
     if (band_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
     if (first_sample % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
     for (size_t g = 0; g < G; ++g)
@@ -435,10 +593,13 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     }
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
+    if (async)
+        if (const int rc = part_stream(ctx, &st)) return rc;
 
-    // ---- host: the part's frame ratios and, for a fresh run, the configs' derived constants
+    // ---- host: the part's frame ratios (the blocking calls) and, for a fresh run, the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
-    const std::vector<float> ratio = sized_ratios(b, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, ratio_stride);
+    std::vector<float> ratio;
+    if (!async) ratio = sized_ratios(b, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, ratio_stride);
     if (first_sample == 0) { // fresh machines: the state of an earlier run is dropped
         b->dev_parts.reset();
         std::vector<VadMachineCfg> hc;
@@ -488,14 +649,29 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     dp->next_sample = UINT64_MAX; // (until this part has run: after an error the run starts again at sample 0)
 
     // ---- device: the part's per-call inputs
-    DevScratch scratch;
+    std::unique_ptr<PartFlight> flight(new (std::nothrow) PartFlight());
+    if (!flight) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part");
+    PartFlight& pf = *flight;
+    pf.st = st;
+    pf.keep = keep;
+    pf.first_sample = first_sample;
+    pf.P = P;
+    pf.n_frames.assign(n_frames, n_frames + G * S);
     float* d_ratio = nullptr;
-    long* d_nf = nullptr;
+    long* d_nf = nullptr; // the frame counts, and behind them the chunk counts (the ratio kernel's)
     std::vector<long> nf_l(n_frames, n_frames + G * S);
-    FVAD_HIP(ctx, scratch.alloc(&d_ratio, ratio.size()));
-    FVAD_HIP(ctx, scratch.alloc(&d_nf, G * S));
-    FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), G * S * sizeof(long), hipMemcpyHostToDevice, st));
+    if (async) nf_l.insert(nf_l.end(), n_chunks, n_chunks + S);
+    FVAD_HIP(ctx, pf.scratch.alloc(&d_ratio, G * S * ratio_stride));
+    FVAD_HIP(ctx, pf.scratch.alloc(&d_nf, nf_l.size()));
+    if (!async) FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), nf_l.size() * sizeof(long), hipMemcpyHostToDevice, st));
+    if (async) {
+        // behind what the main stream holds now (the band sums and the RMS the part reads); nothing there waits for the part
+        FVAD_HIP(ctx, hipEventRecord(ctx->part_ev, ctx->stream));
+        FVAD_HIP(ctx, hipStreamWaitEvent(st, ctx->part_ev, 0));
+        if (const int rc = device_ratios(ctx, b, dp->sizes, d_nf, d_chunk_rms, rms_stride, chunk_size, first_sample, d_ratio, ratio_stride, max_nf, st))
+            return rc;
+    }
 
     // Segment room: at most one segment per 4 frames (fvad_vad_batch_run_device), the largest bound over the sizes.  A part that
     // keeps its segments writes them from the start of the buffer (the earlier ones are on the host); otherwise the buffer holds
@@ -506,29 +682,16 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     size_t most = 0;
     for (size_t g = 0; g < G; ++g)
         most = std::max(most, keep ? P[g] / 4 + 1 : (size_t)((first_sample / b->sizes[g] + P[g]) / 4 + 1));
+    pf.most = most;
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
                                                   : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / M);
     const size_t first_room = std::min(max_nf / 4 + 1, room);
-    auto grow = [&](size_t cap) -> int { // the buffer with room for cap segments per machine, the old contents kept
-        fvad_speech_segment* d = nullptr;
-        FVAD_HIP(ctx, hipMalloc((void**)&d, std::max<size_t>(cap * M, 1) * sizeof(fvad_speech_segment)));
-        if (dp->segs && dp->seg_cap) {
-            const size_t w = dp->seg_cap * sizeof(fvad_speech_segment);
-            const hipError_t e = hipMemcpy2DAsync(d, cap * sizeof(fvad_speech_segment), dp->segs, w, w, M, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) hipStreamSynchronize(st);
-            if (e != hipSuccess) { hipFree(d); return hip_fail(ctx, e, "hipMemcpy2DAsync"); }
-        }
-        hipFree(dp->segs);
-        dp->segs = d;
-        dp->seg_cap = cap;
-        return FVAD_OK;
-    };
     if (dp->seg_cap < first_room) {
-        const int rc = grow(first_room);
+        const int rc = grow_segs(ctx, dp, M, first_room, st);
         if (rc) return rc;
     }
 
-    VadMachinesArgs a{};
+    VadMachinesArgs& a = pf.a;
     a.cfgs = dp->cfg;
     a.n_configs = (int)NC;
     a.n_streams = (long)S;
@@ -563,71 +726,13 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         a.lane_config = dp->lane_config;
         a.first_sample = first_sample;
     }
-    for (;;) {
-        unsigned paused = 0;
-        a.segs = dp->segs;
-        a.seg_cap = (uint32_t)dp->seg_cap;
-        FVAD_HIP(ctx, hipMemsetAsync(dp->paused, 0, sizeof(unsigned), st));
-        time_begin(ctx, "vad_machines");
-        const int e = fvad_launch_vad_machines(a, st);
-        time_end(ctx);
-        if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
-        FVAD_HIP(ctx, hipMemcpyAsync(&paused, dp->paused, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        FVAD_HIP(ctx, hipStreamSynchronize(st));
-        if (!paused) break;
-        // a machine ran out of room: go on from where each machine stopped, with twice the room (no machine needs more than most)
-        const size_t cap = std::min(2 * dp->seg_cap, most);
-        if (cap <= dp->seg_cap) return set_err(ctx, FVAD_ERR_HIP, "vad machines: more segments than frames allow");
-        const int rc = grow(cap);
-        if (rc) return rc;
-        a.fresh = 0;
-        a.rebase = 0;
+    if (const int rc = launch_part(ctx, dp, pf)) return rc;
+    if (async) { // fvad_vad_batch_part_wait goes on from here
+        dp->flight = std::move(flight);
+        b->part_in_flight = true;
+        return FVAD_OK;
     }
-
-    // ---- results: everything run so far
-    std::vector<uint32_t> count(M);
-    std::vector<fvad_vad_audit> audits(M);
-    std::vector<unsigned long long> stats(2 * M);
-    FVAD_HIP(ctx, hipMemcpyAsync(count.data(), dp->count, M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), dp->audit, M * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), dp->stats, 2 * M * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipStreamSynchronize(st));
-    std::vector<fvad_speech_segment> segs;
-    size_t used = 0; // the part's segments: machine m's new ones at the start of its row
-    if (keep) {
-        for (size_t m = 0; m < M; ++m) used = std::max<size_t>(used, count[m] - dp->count_h[m]);
-        segs.resize(used * M);
-        if (used) {
-            const size_t w = used * sizeof(fvad_speech_segment);
-            FVAD_HIP(ctx, hipMemcpy2DAsync(segs.data(), w, dp->segs, dp->seg_cap * sizeof(fvad_speech_segment), w, M, hipMemcpyDeviceToHost, st));
-            FVAD_HIP(ctx, hipStreamSynchronize(st));
-        }
-    }
-    FVAD_HIP(ctx, hipGetLastError());
-    const bool all_kept = keep && (first_sample == 0 || b->segs_kept);
-    for (size_t m = 0; m < M; ++m) {
-        auto& v = b->segs[m];
-        if (all_kept) {
-            const fvad_speech_segment* sm = segs.data() + m * used;
-            v.insert(v.end(), sm, sm + (count[m] - dp->count_h[m]));
-        } else {
-            std::vector<fvad_speech_segment>().swap(v);
-        }
-        b->exact_evals[m] = stats[2 * m];
-        b->lazy_pushes[m] = stats[2 * m + 1];
-    }
-    b->audits = std::move(audits);
-    dp->count_h = std::move(count);
-    for (size_t g = 0; g < G; ++g)
-        for (size_t s = 0; s < S; ++s)
-            if (n_frames[g * S + s] < P[g]) dp->ended[s] = 1;
-    uint64_t next = first_sample + P[0] * b->sizes[0];
-    for (size_t g = 1; g < G; ++g)
-        if (first_sample + P[g] * b->sizes[g] != next) next = UINT64_MAX; // (the sizes ended apart: no part can follow)
-    dp->next_sample = next;
-    b->segs_kept = all_kept;
-    b->scored = false; // the scores were of the previous segments
-    return FVAD_OK;
+    return finish_part(ctx, b, dp, pf);
 }
 
 // The place (kernels_vad.hip: a lane's rings) of machine (s, c) in a batch of S streams and NC configs run with lane map by_config
@@ -752,6 +857,7 @@ int fvad_vad_batch_run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_b
 {
     if (!ctx) return no_ctx();
     if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     if (b->sizes.size() != 1) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "several frame sizes: fvad_vad_batch_run_device_sized");
     return run_device(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size);
 }
@@ -761,6 +867,7 @@ int fvad_vad_batch_run_device_sized(fvad_ctx* ctx, fvad_vad_batch* b, const floa
 {
     if (!ctx) return no_ctx();
     if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     return run_device(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size);
 }
 
@@ -777,9 +884,10 @@ int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float
 {
     if (!ctx) return no_ctx();
     if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     if (b->sizes.size() != 1) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "several frame sizes: fvad_vad_batch_run_device_part_sized");
     if (first_frame > UINT64_MAX / b->fft_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "first_frame out of range");
-    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_frame * b->fft_size);
+    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, nullptr, rms_stride, n_chunks, chunk_size, first_frame * b->fft_size, false);
 }
 
 int fvad_vad_batch_run_device_part_sized(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
@@ -788,13 +896,77 @@ int fvad_vad_batch_run_device_part_sized(fvad_ctx* ctx, fvad_vad_batch* b, const
 {
     if (!ctx) return no_ctx();
     if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
-    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample);
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
+    return run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, nullptr, rms_stride, n_chunks, chunk_size, first_sample, false);
+}
+
+int fvad_vad_batch_run_device_part_async(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                         const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                                         uint64_t first_sample)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
+    return run_device_part(ctx, b, d_band, band_stride, n_frames, nullptr, d_chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, true);
+}
+
+int fvad_vad_batch_part_wait(fvad_ctx* ctx, fvad_vad_batch* b)
+{
+    if (!b) return ctx ? set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null batch") : FVAD_ERR_INVALID_ARGUMENT;
+    if (!b->part_in_flight) return FVAD_OK;
+    if (!ctx) return no_ctx();
+    DevParts* dp = static_cast<DevParts*>(b->dev_parts.get());
+    if (dp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the part runs on another context");
+    hipSetDevice(ctx->device);
+    const std::unique_ptr<PartFlight> flight = std::move(dp->flight); // (its inputs are freed when the part is done, either way)
+    b->part_in_flight = false;
+    const int rc = finish_part(ctx, b, dp, *flight);
+    if (rc) hipStreamSynchronize(flight->st);
+    return rc;
+}
+
+int fvad_vad_batch_frame_ratios_device(fvad_ctx* ctx, const fvad_vad_batch* b, const float* d_chunk_rms, size_t rms_stride,
+                                       const size_t* n_frames, const size_t* n_chunks, size_t chunk_size, uint64_t first_sample,
+                                       float* d_ratio, size_t ratio_stride)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t S = b->n_streams, G = b->sizes.size();
+    std::vector<size_t> P;
+    if (const char* msg = frame_counts(b, n_frames, n_chunks, chunk_size, &P)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, msg);
+    const size_t max_nf = *std::max_element(P.begin(), P.end());
+    if (max_nf == 0) return FVAD_OK;
+    if (!d_chunk_rms || !d_ratio) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (ratio_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ratio_stride < frames of a stream");
+    if (first_sample % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
+    for (size_t g = 0; g < G; ++g)
+        if (first_sample % b->sizes[g]) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a frame of every size");
+    for (size_t s = 0; s < S; ++s)
+        if (n_chunks[s] > rms_stride) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "rms_stride < chunks of a stream");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    DevScratch scratch;
+    uint64_t* d_sizes = nullptr;
+    long* d_counts = nullptr;
+    const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
+    std::vector<long> counts(n_frames, n_frames + G * S);
+    counts.insert(counts.end(), n_chunks, n_chunks + S);
+    FVAD_HIP(ctx, scratch.alloc(&d_sizes, G));
+    FVAD_HIP(ctx, scratch.alloc(&d_counts, counts.size()));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_counts, counts.data(), counts.size() * sizeof(long), hipMemcpyHostToDevice, st));
+    if (const int rc = device_ratios(ctx, b, d_sizes, d_counts, d_chunk_rms, rms_stride, chunk_size, first_sample, d_ratio, ratio_stride, max_nf, st))
+        return rc;
+    FVAD_HIP(ctx, hipStreamSynchronize(st));
+    FVAD_HIP(ctx, hipGetLastError());
+    return FVAD_OK;
 }
 
 int fvad_vad_batch_score_device(fvad_ctx* ctx, fvad_vad_batch* b)
 {
     if (!ctx) return no_ctx();
     if (!b) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null batch");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
     if (!b->has_refs) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no references to score against");
     if (!dp) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no device parts run");
@@ -813,6 +985,7 @@ int fvad_vad_batch_retain_configs(fvad_ctx* ctx, fvad_vad_batch* b, const uint32
 {
     auto fail = [&](int rc, const char* msg) { return ctx ? set_err(ctx, rc, msg) : rc; };
     if (!b || !keep) return fail(FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return fail(FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
     if (dp && dp->ctx != ctx) return fail(FVAD_ERR_INVALID_ARGUMENT, "the batch's device parts ran on another context");
     std::unique_ptr<fvad_vad_batch> nb(new (std::nothrow) fvad_vad_batch());

@@ -15,6 +15,7 @@ int fvad_vad_batch_set_references(fvad_vad_batch* b, const fvad_segment_sec* ref
                                   const fvad_stat_config* stat_cfgs)
 {
     if (!b || !ref_offsets || !stat_cfgs) return FVAD_ERR_INVALID_ARGUMENT;
+    if (b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT; // (a device part in flight: fvad_vad_batch_part_wait first)
     const size_t S = b->n_streams, NC = b->cfgs.size();
     if (ref_offsets[0] != 0) return FVAD_ERR_INVALID_ARGUMENT;
     for (size_t s = 0; s < S; ++s)
@@ -44,14 +45,14 @@ int fvad_vad_batch_set_references(fvad_vad_batch* b, const fvad_segment_sec* ref
 
 int fvad_vad_batch_set_keep_segments(fvad_vad_batch* b, int keep)
 {
-    if (!b) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
     b->keep_segments = keep != 0;
     return FVAD_OK;
 }
 
 int fvad_vad_batch_score(fvad_vad_batch* b, int n_threads)
 {
-    if (!b || !b->has_refs || !b->segs_kept) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b || !b->has_refs || !b->segs_kept || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
     const size_t NC = b->cfgs.size(), M = b->n_streams * NC;
     const float sr = (float)b->sample_rate;
     std::vector<fvad_single_stats> out(M);
@@ -72,7 +73,7 @@ int fvad_vad_batch_score(fvad_vad_batch* b, int n_threads)
 
 int fvad_vad_batch_config_stats(const fvad_vad_batch* b, size_t config, fvad_single_stats* out)
 {
-    if (!b || !out || config >= b->cfgs.size() || !b->scored) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b || !out || config >= b->cfgs.size() || !b->scored || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
     const size_t NC = b->cfgs.size();
     for (size_t s = 0; s < b->n_streams; ++s) out[s] = b->scores[s * NC + config];
     return FVAD_OK;

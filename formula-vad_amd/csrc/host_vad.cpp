@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "host_vad.h"
+#include "vad_ratio.h"
 
 namespace fvad {
 
@@ -590,28 +591,13 @@ template <class Rms>
 static void frame_ratios(Rms chunk_rms, size_t C, size_t n_chunks, size_t n_frames, uint64_t first_frame, uint64_t first_chunk,
                          size_t fft_size, size_t chunk_size, float* out, uint8_t* has)
 {
-    std::vector<float> ratio(n_chunks), ch(C);
-    for (size_t k = 0; k < n_chunks; ++k) {
-        for (size_t c = 0; c < C; ++c) ch[c] = chunk_rms(c, k);
-        const MetaResult va = analyse_volume(ch.data(), C);
-        Metadata m1; m1.push(va, (float)chunk_size);
-        const MetaResult r1 = m1.to_result();
-        Metadata m2; m2.push(r1, (float)chunk_size);
-        ratio[k] = m2.to_result().volume_ratio;
-    }
+    // the arithmetic is vad_ratio.h's (the device computes the same frames from the same header, kernels_vadratio.hip)
+    std::vector<float> ratio(n_chunks);
+    for (size_t k = 0; k < n_chunks; ++k)
+        ratio[k] = chunk_volume_ratio([&](size_t c) { return chunk_rms(c, k); }, C, (float)chunk_size);
     for (size_t f = 0; f < n_frames; ++f) {
-        Metadata md;
-        const uint64_t from = (first_frame + f) * fft_size, to = from + fft_size;
-        for (uint64_t c = from / chunk_size; c * chunk_size < to; ++c) {
-            const uint64_t lo = std::max<uint64_t>(from, c * chunk_size), hi = std::min<uint64_t>(to, (c + 1) * chunk_size);
-            MetaResult r;
-            r.has_ratio = true;
-            r.volume_ratio = ratio[(size_t)(c - first_chunk)];
-            md.push(r, (float)(hi - lo));
-        }
-        const MetaResult fr = md.to_result();
-        out[f] = fr.volume_ratio;
-        if (has) has[f] = fr.has_ratio ? 1 : 0;
+        out[f] = frame_volume_ratio([&](uint64_t k) { return ratio[(size_t)(k - first_chunk)]; }, (first_frame + f) * fft_size, fft_size, chunk_size);
+        if (has) has[f] = 1;
     }
 }
 
@@ -626,6 +612,28 @@ void sweep_frame_ratios(const float* chunk_rms, size_t rms_stride, size_t C, siz
 
 extern "C" {
 
+int fvad_vad_batch_frame_ratios(const fvad_vad_batch* b, const float* chunk_rms, size_t rms_stride, const size_t* n_frames,
+                                const size_t* n_chunks, size_t chunk_size, uint64_t first_sample, float* ratio, size_t ratio_stride)
+{
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    if (first_sample % chunk_size) return FVAD_ERR_INVALID_ARGUMENT;
+    const size_t S = b->n_streams, C = b->n_channels, G = b->sizes.size();
+    for (size_t g = 0; g < G; ++g) {
+        if (first_sample % b->sizes[g]) return FVAD_ERR_INVALID_ARGUMENT;
+        for (size_t s = 0; s < S; ++s) {
+            const size_t nf = n_frames[g * S + s];
+            if (nf > (n_chunks[s] * chunk_size) / b->sizes[g] || nf > ratio_stride || n_chunks[s] > rms_stride) return FVAD_ERR_INVALID_ARGUMENT;
+            if (nf && (!chunk_rms || !ratio)) return FVAD_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (size_t i = 0; i < G * S; ++i) {
+        const size_t s = i % S, F = b->sizes[i / S];
+        fvad::sweep_frame_ratios(chunk_rms + s * C * rms_stride, rms_stride, C, n_chunks[s], n_frames[i], F, chunk_size, ratio + i * ratio_stride,
+                                 first_sample / F);
+    }
+    return FVAD_OK;
+}
+
 } // extern "C"
 
 // Every machine of b over frames of its own size: n_frames[g] frames of size g from sample first_sample on (every stream the same
@@ -634,6 +642,7 @@ static int run_host(fvad_vad_batch* b, const float* band, size_t band_stride, co
                     size_t rms_stride, size_t n_chunks, size_t chunk_size, uint64_t first_sample, int n_threads)
 {
     const size_t NC = b->cfgs.size(), G = b->sizes.size();
+    if (b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT; // (a device part in flight: fvad_vad_batch_part_wait first)
     // parts follow each other without gaps, and a part starts where a chunk and a frame of every size start (its first chunk is
     // chunk_rms' first column)
     if (first_sample != 0 && (first_sample != b->next_sample || b->machines.size() != b->n_streams * NC)) return FVAD_ERR_INVALID_ARGUMENT;
@@ -728,7 +737,7 @@ int fvad_vad_batch_run_sized(fvad_vad_batch* b, const float* band, size_t band_s
 
 size_t fvad_vad_batch_total_segments(const fvad_vad_batch* b) // (config 0's on a sweep batch)
 {
-    if (b && !b->segs_kept) return SIZE_MAX; // a device run without keeping its segments
+    if (b && (!b->segs_kept || b->part_in_flight)) return SIZE_MAX; // a device run without keeping its segments, or a part in flight
     size_t n = 0;
     if (b) for (size_t s = 0; s < b->n_streams; ++s) n += b->segs[s * b->cfgs.size()].size();
     return n;
@@ -742,7 +751,7 @@ int fvad_vad_batch_segments(const fvad_vad_batch* b, fvad_speech_segment* out, s
 int fvad_vad_batch_config_segments(const fvad_vad_batch* b, size_t config, fvad_speech_segment* out, size_t cap, size_t* offsets)
 {
     if (!b || !offsets || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
-    if (!b->segs_kept) return FVAD_ERR_INVALID_ARGUMENT; // a device run without keeping its segments: none to give
+    if (!b->segs_kept || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT; // a device run without keeping its segments: none to give; a part in flight
     const size_t NC = b->cfgs.size();
     size_t n = 0;
     for (size_t s = 0; s < b->n_streams; ++s) { offsets[s] = n; n += b->segs[s * NC + config].size(); }
@@ -763,7 +772,7 @@ int fvad_vad_batch_audit(const fvad_vad_batch* b, size_t stream, fvad_vad_audit*
 
 int fvad_vad_batch_lazy_stats(const fvad_vad_batch* b, size_t stream, size_t config, uint64_t* exact_evaluations, uint64_t* lazy_pushes)
 {
-    if (!b || stream >= b->n_streams || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b || stream >= b->n_streams || config >= b->cfgs.size() || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
     if (exact_evaluations) *exact_evaluations = b->exact_evals[stream * b->cfgs.size() + config];
     if (lazy_pushes) *lazy_pushes = b->lazy_pushes[stream * b->cfgs.size() + config];
     return FVAD_OK;
@@ -771,7 +780,7 @@ int fvad_vad_batch_lazy_stats(const fvad_vad_batch* b, size_t stream, size_t con
 
 int fvad_vad_batch_config_audit(const fvad_vad_batch* b, size_t stream, size_t config, fvad_vad_audit* out)
 {
-    if (!b || !out || stream >= b->n_streams || config >= b->cfgs.size()) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!b || !out || stream >= b->n_streams || config >= b->cfgs.size() || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
     *out = b->audits[stream * b->cfgs.size() + config];
     return FVAD_OK;
 }

@@ -113,6 +113,9 @@ struct fvad_vad_batch {
     uint64_t next_sample = 0; // where the next host part starts, in samples (UINT64_MAX: the sizes' parts ended apart, none can follow)
     // a run in parts on the GPU (fvad_vad_batch_run_device_part): the machines' state in device memory between the parts
     std::unique_ptr<void, fvad::DevPartsDeleter> dev_parts;
+    // fvad_vad_batch_run_device_part_async has launched a part and fvad_vad_batch_part_wait has not finished it: until then every
+    // call that runs, scores, retains, reads results of or sets something on the batch returns FVAD_ERR_INVALID_ARGUMENT
+    bool part_in_flight = false;
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
     // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
     bool has_refs = false;

@@ -193,6 +193,10 @@ struct fvad_ctx {
     int device = 0;
     int n_cu = 256; // compute units: size of the persistent GEMM grid
     hipStream_t stream = nullptr;
+    // device parts that do not wait (fvad_vad_batch_run_device_part_async) run here, ordered behind `stream` by part_ev; created
+    // on first use
+    hipStream_t part_stream = nullptr;
+    hipEvent_t part_ev = nullptr;
     mutable std::string err;
     // constant tables
     float* d_tables = nullptr;

@@ -255,6 +255,24 @@ struct VadMachinesArgs {
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
 
+// ------------------------------------------------------------------ the frame ratios of a device part (kernels_vadratio.hip)
+// row (size g, stream s) = g * n_streams + s: frames [0, n_frames[row]) of sizes[g] samples from sample first_sample on (a chunk
+// boundary), ratio row at ratio + row * ratio_stride; frames [n_frames[row], max_frames) of the row are set to 0
+struct VadRatioArgs {
+    const float* chunk_rms;    // lane l = s * n_channels + c, chunk k of the part at chunk_rms[l * rms_stride + k] (device)
+    long rms_stride;
+    int n_channels, n_sizes;
+    long n_streams;
+    const uint64_t* sizes;     // [n_sizes] (device); null with one size: fft_size
+    uint64_t fft_size;
+    const long* n_frames;      // [n_sizes][n_streams] (device)
+    const long* n_chunks;      // [n_streams] (device): the chunks of the part chunk_rms holds for the stream
+    uint64_t chunk_size, first_sample;
+    float* ratio;
+    long ratio_stride, max_frames; // max_frames <= ratio_stride
+};
+int fvad_launch_vad_frame_ratios(const VadRatioArgs& a, hipStream_t stream); // hipError_t as int
+
 // ------------------------------------------------------------------ scoring the machines of a VAD batch (kernels_eval.hip)
 // one lane per machine, machine = stream * n_configs + config: the Evaluator statistics of its segments (eval_walk.h)
 struct VadScoreArgs {

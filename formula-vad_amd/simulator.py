@@ -644,7 +644,7 @@ def _check_grid_contexts(ctx, devices):
 
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None):
+             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -703,7 +703,14 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     a decision.  The result then also has share_times (per share: device, instances, wall seconds, stage times) and
     device_bytes_per_share (each share's device_bytes); times and slices are sums over the shares (times in GPU-seconds),
     device_bytes the largest share's, and with more than one share the summary line adds each share's wall time.  With one
-    context (ctx a Context or None, devices None) no thread is started and the result is as described above."""
+    context (ctx a Context or None, devices None) no thread is started and the result is as described above.
+    overlap=True (with slice_chunks, device machines and device scoring; ValueError otherwise): each slice's machines run beside the
+    next slice's reading and denoising -- their frame ratios computed on the device from the engine's chunk RMS, the parts started
+    with fvad_vad_batch_run_device_part_async on the context's second stream and waited for only when their buffers are needed
+    again, at a rung and at the end.  Plain, sized and halving grids, and every share of a ctx / devices list on its own context.
+    On reproducible contexts the statistics, survivors, rungs and evaluated_seconds are those of overlap=False bit for bit.
+    times gains machines_wait (the host time inside the waits, counted in machines too); device_bytes counts the second set
+    of the bands and rms buffers."""
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
@@ -720,6 +727,12 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         raise ValueError(f"score_on: {score_on!r}")
     if score_on == "device" and vad_on != "device":
         raise ValueError("score_on='device' scores next to the device machines: it needs vad_on='device'")
+    if overlap:
+        if slice_chunks is None:
+            raise ValueError("overlap runs a slice's machines beside the next slice's denoising: it needs slice_chunks")
+        if vad_on != "device" or score_on != "device":
+            raise ValueError(f"overlap leaves the machines and their segments on the device: it needs vad_on='device' and "
+                             f"score_on='device' (got {vad_on!r}, {score_on!r})")
     halving = None
     if halving_eta is not None or halving_rungs is not None:
         if halving_eta is None or halving_rungs is None:
@@ -787,7 +800,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         try:
             share_out[s] = _grid_share(ctxs[s], [audio[i] for i in shares[s]], [refs[i] for i in shares[s]], ids, configs,
                                        stat_cfgs, sizes_of if sized else None, F, slice_chunks, vad_on, score_on,
-                                       max(1, n_threads // len(workers)), stats, st, rungs, stop)
+                                       max(1, n_threads // len(workers)), stats, st, rungs, stop, **({"overlap": True} if overlap else {}))
         except (threading.BrokenBarrierError, _Stopped) as e:   # another worker failed
             breaks.append(e)
         except BaseException as e:  # re-raised below, in the caller's thread
@@ -943,13 +956,13 @@ class _Rungs:
 
 
 def _grid_share(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, slice_chunks, vad_on, score_on, n_threads, stats, times,
-                rungs, stop):
+                rungs, stop, overlap=False):
     """run_grid's flow for one share of the instances on its own context: audio / refs the share's instances, ids their plan
     indices (the columns of stats it fills); sizes_of None unless the grid is sized; rungs a _Rungs for successive halving;
     stop an Event another worker sets when it fails.  Returns (slices run, device_bytes: None unsliced)."""
     if slice_chunks is not None:
         return _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on, n_threads, stats,
-                                times, sizes_of, rungs, stop)
+                                times, sizes_of, rungs, stop, overlap)
     _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_on, score_on, n_threads, stats, times, stop)
     return 1, None
 
@@ -1096,7 +1109,8 @@ def _clip_labels(ref, t):
     return a
 
 
-def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts, fr_slice, stats, times, stop):
+def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts, fr_slice, stats, times, stop,
+                    ov=None):
     """_run_grid_sliced with successive halving (run_grid's halving_eta / halving_rungs) over one share: every group's device
     batch alive at once, the slices run one after the other across the groups, so that every rung sees every instance at the
     same point in time.  At a rung's end (rungs.ends: the whole plan's): each group's machines scored on the device against
@@ -1105,7 +1119,8 @@ def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, ru
     F-score (ties to the lower config index); every batch is cut to them (VadSweep.retain) and the full labels go back.  A
     share whose instances have all ended still scores and retains at every rung.  Fills stats (survivors: the whole corpus;
     dropped configs: the last prefix they were scored on) and rungs' survivors, rung, evaluated seconds and log.  Returns
-    (slices run, the largest device memory the share's batches held together)."""
+    (slices run, the largest device memory the share's batches held together).  ov (an _Overlap): the parts do not wait -- a
+    slice's machines run beside the next slice's denoising, and every part is waited for before a rung scores."""
     chunk = 24000
     stat_cfgs = rungs.stat_cfgs
     batches = {}
@@ -1127,9 +1142,14 @@ def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, ru
                 sized = isinstance(b, fv.VadSweepSized)
                 blocks = b.size_blocks() if sized else [(F, 0, b.bands()[0])]
                 sizes = [Fg for Fg, _, _ in blocks] if not sized else b.sizes
-                rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times)
+                dset = None if ov is None else ov.next_set()
+                rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times,
+                                               None if ov is None else ov.sets[dset])
                 nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
                 nf_g = [[max(0, min(n_chunks[i] * chunk // Fg, s1 * chunk // Fg) - s0 * chunk // Fg) for i in members] for Fg in sizes]
+                if ov is not None:
+                    ov.launch(dset, b, fr_slice, nf_g, rms, nc, s0 * chunk)
+                    continue
                 t0 = time.perf_counter()
                 if sized:
                     b.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
@@ -1140,6 +1160,9 @@ def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, ru
             rungs.count(ids, s0, s1)
             if s1 not in rungs.ends:
                 continue
+            if ov is not None:
+                ov.drain()
+                peak = max(peak, sum(b.device_bytes() for b in batches.values()))
             # ---- a rung: score the prefix [0, s1) against the labels cut to it, keep the best 1 / eta
             t0 = time.perf_counter()
             t_end = s1 * chunk / 48000.0
@@ -1160,6 +1183,9 @@ def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, ru
                 batches[nch].set_references([refs[i] for i in members], [stat_cfgs[o] for o in rungs.alive])
             rungs.wait(rungs.logged)
         # ---- the survivors over the whole corpus
+        if ov is not None:
+            ov.drain()
+            peak = max(peak, sum(b.device_bytes() for b in batches.values()))
         t0 = time.perf_counter()
         for nch, members in groups.items():
             b = batches[nch]
@@ -1169,15 +1195,18 @@ def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, ru
         times["scoring"] += time.perf_counter() - t0
         rungs.wait(rungs.ended)
     finally:
-        for b in batches.values():
+        for b in batches.values():   # (closing a batch waits for its part)
             b.close()
     return n_slices, peak
 
 
-def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times):
+def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times, dset=None):
     """one time slice [s0, s1) of a channel-count group (_run_grid_sliced): the slice and its SLICE_HALO_CHUNKS-chunk halo read
     from the mapped files into the pinned host buffer, denoised from zero history, the band sums of the slice's frames for
-    blocks [(F, first band, bins)] written to d["bands"] (stride fr_slice); returns the slice's chunk RMS [lanes][s1 - s0]"""
+    blocks [(F, first band, bins)] written to d["bands"] (stride fr_slice); returns the slice's chunk RMS [lanes][s1 - s0].
+    dset (overlap: a (bands, rms) pair of device buffers): the band sums and the RMS go there and nothing comes back to the
+    host -- returns (device address of the slice's first chunk's RMS, its lane stride); the calls wait for the context's main
+    stream only, never for a device part in flight."""
     chunk = 24000
     start = max(s0 - SLICE_HALO_CHUNKS, 0)
     n = s1 - start
@@ -1196,25 +1225,75 @@ def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, bl
                 else:
                     row[:hi - lo] = a[lo:hi, c]
             row[max(hi - lo, 0):] = 0.0
-    ctx.to_device(d["pcm"], pcm)
+    d_bands, d_rms = (d["bands"], d["rms"]) if dset is None else dset
+    if dset is None:
+        ctx.to_device(d["pcm"], pcm)
+    else:   # queued in front of the engine call, which waits for the main stream (Context.synchronize would wait for the part too)
+        ctx._ck(fv.lib().fvad_ctx_copy_to_device(ctx.h, fv.vp(d["pcm"]), pcm.ctypes.data, pcm.nbytes), "fvad_ctx_copy_to_device")
     ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d["pcm"]), L, n * chunk, n * chunk, fv.vp(d["den"]),
-                                                fv.vp(d["band0"]), fv.vp(d["rms"]), fv.C.byref(opts)),
+                                                fv.vp(d["band0"]), fv.vp(d_rms), fv.C.byref(opts)),
             "fvad_engine_enqueue_device")
-    rms = ctx.to_host(np.empty((L, n), np.float32), d["rms"])
-    rms = np.ascontiguousarray(rms[:, s0 - start:])
+    if dset is None:
+        rms = ctx.to_host(np.empty((L, n), np.float32), d["rms"])
+        rms = np.ascontiguousarray(rms[:, s0 - start:])
+    else:
+        rms = (d_rms + (s0 - start) * 4, n)
     times["denoise"] += time.perf_counter() - t0
     # ---- band sums of the slice's frames: the denoised audio from chunk s0 on (frame-aligned: s0 is a
     # multiple of slice_align(F))
     t0 = time.perf_counter()
     for Fg, j0, bins_g in blocks:
         ctx.band_sums_device(d["den"] + (s0 - start) * chunk * 4, L, n * chunk, (s1 - s0) * chunk, bins_g,
-                             d["bands"] + j0 * L * fr_slice * 4, fr_slice, fft_size=Fg)
+                             d_bands + j0 * L * fr_slice * 4, fr_slice, fft_size=Fg)
     times["bands"] += time.perf_counter() - t0
     return rms
 
 
+class _Overlap:
+    """run_grid(overlap=True): the two sets of the per-slice buffers the machines read (bands, rms), used alternately, and the
+    device parts in flight on them (fvad_vad_batch_run_device_part_async).  A set is written again only after the part that reads
+    it has been waited for, and a batch has one part in flight at most."""
+
+    def __init__(self, ctx, d, times):
+        self.ctx, self.times = ctx, times
+        self.sets = [(d["bands"], d["rms"]), (d["bands2"], d["rms2"])]
+        self.busy = [None, None]   # the batch whose part reads the set
+        self.turn = 0
+        times.setdefault("machines_wait", 0.0)
+
+    def _wait(self, i):
+        b, self.busy[i] = self.busy[i], None
+        if b is not None:
+            t0 = time.perf_counter()
+            b.part_wait(self.ctx)
+            dt = time.perf_counter() - t0
+            self.times["machines_wait"] += dt
+            self.times["machines"] += dt
+
+    def next_set(self):
+        """the buffer set of the next slice, free to be written"""
+        i = self.turn % 2
+        self.turn += 1
+        self._wait(i)
+        return i
+
+    def launch(self, i, b, band_stride, n_frames, rms, n_chunks, first_sample):
+        """b's part on set i (rms: _slice_denoise_and_bands' device address and stride), after b's previous part"""
+        for j in (0, 1):
+            if self.busy[j] is b:
+                self._wait(j)
+        t0 = time.perf_counter()
+        b.run_device_part_async(self.ctx, self.sets[i][0], band_stride, n_frames, rms[0], rms[1], n_chunks, first_sample)
+        self.times["machines"] += time.perf_counter() - t0
+        self.busy[i] = b
+
+    def drain(self):
+        for j in (0, 1):
+            self._wait(j)
+
+
 def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of, rungs,
-                     stop):
+                     stop, overlap=False):
     """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
     SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
     (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
@@ -1225,7 +1304,10 @@ def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, sc
     indices) and times; returns (slices run, device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
     batch, one band-sum pass per size and slice, and parts from sample s0 * chunk (fvad_vad_batch_run_device_part_sized /
     fvad_vad_batch_run_sized).  rungs: a _Rungs for successive halving -- _halving_slices' loop instead of the one below.
-    stop: checked before every slice (_Stopped once another worker has failed)."""
+    stop: checked before every slice (_Stopped once another worker has failed).  overlap (device machines and scoring): a
+    second set of the bands and rms buffers, the frame ratios computed on the device and the parts not waited for
+    (fvad_vad_batch_run_device_part_async): slice k's machines run beside slice k + 1's reading and denoising; times gains
+    machines_wait, the host time spent waiting for parts (it is part of machines)."""
     chunk, H = 24000, SLICE_HALO_CHUNKS
     n_chunks = [a.shape[0] // chunk for a in audio]
     groups = {}
@@ -1253,6 +1335,8 @@ def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, sc
     own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4,
            "band0": lanes_max * (n_max * chunk // F + 1) * 4, "rms": lanes_max * n_max * 4,
            "bands": len(bins) * lanes_max * fr_slice * 4}
+    if overlap:
+        own.update(bands2=own["bands"], rms2=own["rms"])
     opts = fv.EngineOpts()
     fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
     opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
@@ -1265,9 +1349,10 @@ def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, sc
         for k, nb in own.items():
             d[k] = ctx.device_alloc(max(nb, 16))
         host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
+        ov = _Overlap(ctx, d, times) if overlap else None
         if rungs is not None:
             n_slices, batch_peak = _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts,
-                                                   fr_slice, stats, times, stop)
+                                                   fr_slice, stats, times, stop, ov)
             return n_slices, sum(own.values()) + batch_peak + ws
         for nch, members in groups.items():
             L = len(members) * nch
@@ -1287,13 +1372,18 @@ def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, sc
                     _check_stop(stop)
                     s1 = min(s0 + N, K)
                     n_slices += 1
-                    rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times)
+                    dset = None if ov is None else ov.next_set()
+                    rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times,
+                                                   None if ov is None else ov.sets[dset])
                     # each size's frames of the slice, per instance
                     nf_g = [[max(0, min(e, s1 * chunk // Fg) - s0 * chunk // Fg) for e in ends] for (Fg, _, _), ends in zip(blocks, nf_end)]
                     nf = nf_g[0]
                     f0 = s0 * chunk // F
                     nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
                     # ---- the machines
+                    if ov is not None:
+                        ov.launch(dset, dev, fr_slice, nf_g, rms, nc, s0 * chunk)
+                        continue
                     t0 = time.perf_counter()
                     if dev is not None and sized:
                         dev.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
@@ -1322,6 +1412,9 @@ def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, sc
                                                                       n_threads), "fvad_vad_batch_run_part")
                     times["machines"] += time.perf_counter() - t0
                 # ---- scoring
+                if ov is not None:
+                    ov.drain()
+                    batch_peak = max(batch_peak, dev.device_bytes())
                 t0 = time.perf_counter()
                 if dev is not None:
                     if score_on == "device":
@@ -1402,11 +1495,15 @@ def main(argv=None):
                          "rung (the machines and scoring on the GPU)")
     ap.add_argument("--halving-rungs", type=int, default=None,
                     help="with --halving-eta: the number of rungs R (rung k ends at ETA^(k-1-R) of the corpus)")
+    ap.add_argument("--overlap", action="store_true",
+                    help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
+                         "next slice's denoising (a second stream and a second set of band buffers)")
     a = ap.parse_args(argv)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
-                 slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices)
+                 slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
+                 overlap=a.overlap)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)

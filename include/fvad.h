@@ -549,6 +549,39 @@ int fvad_vad_batch_run_device_part_sized(fvad_ctx *ctx, fvad_vad_batch *b, const
                                          const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
                                          const size_t *n_chunks, size_t chunk_size, uint64_t first_sample);
 
+/* Device parts that do not wait: a part's machines beside the next slice's denoising on the same context.
+ * - fvad_vad_batch_run_device_part_async: fvad_vad_batch_run_device_part_sized (it takes every batch, n_frames[g * n_streams + s],
+ *   the same part rules and the same checks) with the chunk RMS on the DEVICE, as fvad_engine_enqueue_device leaves it
+ *   (lane l's chunks at d_chunk_rms + l * rms_stride, from the part's first chunk).  The frame ratios are computed on the device
+ *   (csrc/kernels_vadratio.hip, the host's arithmetic from the same header: the same bits), the machines are launched, and the
+ *   call returns without waiting.  b's results are those of the previous part until fvad_vad_batch_part_wait has returned.
+ * - fvad_vad_batch_part_wait: finishes the part -- waits, grows the segment room and relaunches machines that paused, brings
+ *   back counts, audits and lazy statistics, appends the part's segments with keep_segments 1.  Afterwards b is what the blocking
+ *   part call would have left, bit for bit.  With nothing in flight it returns FVAD_OK.  A part that fails (in either call)
+ *   leaves what a failed blocking part leaves: the run starts again at sample 0.
+ * - The part runs on a second stream of the context (created on first use), behind everything queued on the main stream at the
+ *   time of the call (the band sums and RMS it reads); nothing on the main stream waits for the part, so engine calls made
+ *   between the two calls run beside it.  The kernel-time table (fvad_ctx_set_timing) is the main stream's: it does not list
+ *   the part's kernels.  The caller leaves d_band and d_chunk_rms untouched until fvad_vad_batch_part_wait returns.
+ * - While a part is in flight every other call that runs, scores, retains, reads results of (segments, audits, statistics) or
+ *   sets something on b returns FVAD_ERR_INVALID_ARGUMENT (fvad_vad_batch_total_segments: SIZE_MAX), as do a second _async and a
+ *   _part_wait on another context; b stays usable.  fvad_vad_batch_destroy waits for the part; fvad_ctx_synchronize waits for
+ *   what the part has queued as well (a paused part's relaunch is still fvad_vad_batch_part_wait's).
+ * - fvad_vad_batch_frame_ratios_device: only the frame ratios, row (size g, stream s) at d_ratio + (g * n_streams + s) *
+ *   ratio_stride, n_frames[g * n_streams + s] values each (the rest of a row up to the longest row's length is set to 0), on the
+ *   context's stream; returns when done.  fvad_vad_batch_frame_ratios: the same rows on the host from host RMS -- what the
+ *   blocking device calls hand their machines. */
+int fvad_vad_batch_run_device_part_async(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                                         const size_t *n_frames, const float *d_chunk_rms, size_t rms_stride,
+                                         const size_t *n_chunks, size_t chunk_size, uint64_t first_sample);
+int fvad_vad_batch_part_wait(fvad_ctx *ctx, fvad_vad_batch *b);
+int fvad_vad_batch_frame_ratios_device(fvad_ctx *ctx, const fvad_vad_batch *b, const float *d_chunk_rms, size_t rms_stride,
+                                       const size_t *n_frames, const size_t *n_chunks, size_t chunk_size,
+                                       uint64_t first_sample, float *d_ratio, size_t ratio_stride);
+int fvad_vad_batch_frame_ratios(const fvad_vad_batch *b, const float *chunk_rms, size_t rms_stride, const size_t *n_frames,
+                                const size_t *n_chunks, size_t chunk_size, uint64_t first_sample, float *ratio,
+                                size_t ratio_stride);
+
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;
 int fvad_ra_create(size_t count, int has_initial, double initial_val, fvad_rolling_average **out);
