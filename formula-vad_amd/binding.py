@@ -904,21 +904,41 @@ class VadBatch:
             self.h = vp()
 
 
+def _config_array(configs):
+    """the VadConfig array of a list of override dicts (defaults for the fields a dict leaves out)"""
+    arr = (VadConfig * len(configs))()
+    for i, ov in enumerate(configs):
+        lib().fvad_vad_config_default(C.byref(arr[i]))
+        for k, v in (ov or {}).items():
+            setattr(arr[i], k, v)
+    return arr
+
+
 class VadSweep:
     """fvad_vad_batch with several configs (fvad_vad_batch_create_sweep): one VAD machine per (stream, config), each on its
-    config's speech band.  configs: list of VadConfig overrides dicts (defaults for the fields a dict leaves out)."""
+    config's speech band.  configs: list of VadConfig overrides dicts (defaults for the fields a dict leaves out).  sizes (the
+    distinct frame sizes, here [fft_size]) and size_of_band (each band's index into sizes) are those of frame_sizes()."""
 
     def __init__(self, n_streams, configs, n_channels=1, sample_rate=48000, fft_size=1024):
-        arr = (VadConfig * len(configs))()
-        for i, ov in enumerate(configs):
-            lib().fvad_vad_config_default(C.byref(arr[i]))
-            for k, v in (ov or {}).items():
-                setattr(arr[i], k, v)
         self.h = vp()
-        check(lib().fvad_vad_batch_create_sweep(arr, len(configs), sample_rate, n_channels, fft_size, n_streams, C.byref(self.h)),
-              "fvad_vad_batch_create_sweep")
-        self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, len(configs)
+        check(lib().fvad_vad_batch_create_sweep(_config_array(configs), len(configs), sample_rate, n_channels, fft_size, n_streams,
+                                                C.byref(self.h)), "fvad_vad_batch_create_sweep")
+        self._created(n_streams, n_channels, len(configs))
+
+    def _created(self, n_streams, n_channels, n_configs):
+        self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, n_configs
         assert lib().fvad_vad_batch_n_configs(self.h) == self.n_configs
+        self.sizes, self.size_of_band = self.frame_sizes()
+
+    def frame_sizes(self):
+        """-> (the distinct sizes in first-seen config order, the size index of each band)"""
+        n = sz()
+        sizes = (sz * self.n_configs)()
+        sob = (C.c_uint32 * self.n_configs)()
+        check(lib().fvad_vad_batch_frame_sizes(self.h, sizes, self.n_configs, C.byref(n), sob), "fvad_vad_batch_frame_sizes")
+        n_bands = sz()
+        lib().fvad_vad_batch_bands(self.h, None, 0, C.byref(n_bands), None)
+        return [sizes[g] for g in range(n.value)], [sob[j] for j in range(n_bands.value)]
 
     def bands(self):
         """-> (bins [(min_bin, max_bin)] of the distinct bands, band_of [config])"""
@@ -929,12 +949,36 @@ class VadSweep:
         check(lib().fvad_vad_batch_bands(self.h, bins, self.n_configs, C.byref(n), band_of), "fvad_vad_batch_bands")
         return [(bins[2 * j], bins[2 * j + 1]) for j in range(n.value)], list(band_of)
 
+    def size_blocks(self):
+        """-> [(fft_size, first band, [(min_bin, max_bin)])] per size: the run of band blocks of each size"""
+        bins, _ = VadSweep.bands(self)
+        out = []
+        for g, F in enumerate(self.sizes):
+            js = [j for j in range(len(bins)) if self.size_of_band[j] == g]
+            out.append((F, js[0], [bins[j] for j in js]))
+        return out
+
     def run(self, band, chunk_rms, n_threads=1, chunk_size=24000):
         """band [n_bands][n_streams * n_channels][n_frames] (bands() order), chunk_rms [n_streams * n_channels][n_chunks], float32"""
         assert band.dtype == np.float32 and chunk_rms.dtype == np.float32 and band.flags["C_CONTIGUOUS"] and chunk_rms.flags["C_CONTIGUOUS"]
         assert band.shape[1] == chunk_rms.shape[0] == self.n_streams * self.n_channels
         check(lib().fvad_vad_batch_run(self.h, fptr(band), band.shape[2], band.shape[2], fptr(chunk_rms), chunk_rms.shape[1],
                                        chunk_rms.shape[1], chunk_size, n_threads), "fvad_vad_batch_run")
+
+    def run_sized(self, band, chunk_rms, n_frames, first_sample=0, n_threads=1, chunk_size=24000):
+        """fvad_vad_batch_run_sized: band [n_bands][n_streams * n_channels][stride] (bands() order, C-contiguous),
+        n_frames[g] frames of size g (one size: the count itself will do) from sample first_sample on, chunk_rms [lanes][n_chunks]
+        from the part's first chunk.  first_sample = 0 starts fresh machines; a later part goes on where the last one ended."""
+        assert band.dtype == np.float32 and chunk_rms.dtype == np.float32
+        assert band.flags["C_CONTIGUOUS"]   # (not by the strides: numpy leaves an axis of length 1 whatever stride it had)
+        assert chunk_rms.shape[1] <= 1 or chunk_rms.strides[1] == 4
+        assert band.shape[1] == chunk_rms.shape[0] == self.n_streams * self.n_channels
+        n_frames = [int(x) for x in np.atleast_1d(n_frames)]
+        assert len(n_frames) == len(self.sizes)
+        nf = (sz * len(n_frames))(*n_frames)
+        check(lib().fvad_vad_batch_run_sized(self.h, C.cast(band.ctypes.data, c_float_p), band.shape[2], nf,
+                                             C.cast(chunk_rms.ctypes.data, c_float_p), chunk_rms.strides[0] // 4, chunk_rms.shape[1],
+                                             chunk_size, int(first_sample), n_threads), "fvad_vad_batch_run_sized")
 
     def run_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, chunk_size=24000):
         """fvad_vad_batch_run_device: d_band as Context.band_sums_device writes it (device address), n_frames / n_chunks per
@@ -958,10 +1002,27 @@ class VadSweep:
                 "fvad_vad_batch_run_device_part")
 
     def _sized_counts(self, n_frames, n_chunks):
-        """n_frames [stream] or [size][stream], n_chunks [stream] as the sized calls take them"""
+        """n_frames [stream] (one size) or [size][stream], n_chunks [stream] as the sized calls take them"""
         flat = [int(x) for row in n_frames for x in (row if hasattr(row, "__len__") else [row])]
-        assert len(flat) % self.n_streams == 0 and len(n_chunks) == self.n_streams
+        assert len(flat) == len(self.sizes) * self.n_streams and len(n_chunks) == self.n_streams
         return (sz * len(flat))(*flat), (sz * self.n_streams)(*[int(x) for x in n_chunks])
+
+    def run_device_sized(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, chunk_size=24000):
+        """fvad_vad_batch_run_device_sized: run_device with n_frames [stream] (one size) or [size][stream]; d_band as bands()
+        orders the blocks"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_run_device_sized(ctx.h, self.h, vp(d_band), band_stride, nf, fptr(chunk_rms), chunk_rms.shape[1], nc,
+                                                      chunk_size), "fvad_vad_batch_run_device_sized")
+
+    def run_device_part_sized(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_sample, chunk_size=24000):
+        """fvad_vad_batch_run_device_part_sized: run_device_part in samples -- the frames of every size from sample first_sample on,
+        n_frames [stream] (one size) or [size][stream]"""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        ctx._ck(lib().fvad_vad_batch_run_device_part_sized(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf,
+                                                           fptr(chunk_rms), chunk_rms.shape[1], nc, chunk_size, int(first_sample)),
+                "fvad_vad_batch_run_device_part_sized")
 
     def run_device_part_async(self, ctx, d_band, band_stride, n_frames, d_chunk_rms, rms_stride, n_chunks, first_sample, chunk_size=24000):
         """fvad_vad_batch_run_device_part_async: the sized part call (n_frames [stream] with one size, else [size][stream]) with
@@ -1012,6 +1073,7 @@ class VadSweep:
         else:
             ctx._ck(lib().fvad_vad_batch_retain_configs(ctx.h, self.h, arr, len(keep)), "fvad_vad_batch_retain_configs")
         self.n_configs = len(keep)
+        self.sizes, self.size_of_band = self.frame_sizes()
 
     def segments(self, config):
         """config's segments per stream: [[(from, to, avg_ratio, vad_met_sec)]]"""
@@ -1082,84 +1144,25 @@ class VadSweep:
 
 class VadSweepSized(VadSweep):
     """fvad_vad_batch_create_sweep_sized: a sweep whose configs run on frames of their own sizes (fft_sizes[c] for configs[c]),
-    several frame clocks in one batch.  The query calls (segments, audit, lazy_stats, references, scoring, config_stats,
-    device_bytes) are VadSweep's; bands() names each band's size."""
+    several frame clocks in one batch.  Everything but the constructor is VadSweep's; bands() names each band's size, and run,
+    run_device and run_device_part are the sample-based calls (run_sized, run_device_sized, run_device_part_sized)."""
 
     def __init__(self, n_streams, configs, fft_sizes, n_channels=1, sample_rate=48000):
         assert len(fft_sizes) == len(configs)
-        arr = (VadConfig * len(configs))()
-        for i, ov in enumerate(configs):
-            lib().fvad_vad_config_default(C.byref(arr[i]))
-            for k, v in (ov or {}).items():
-                setattr(arr[i], k, v)
         sizes = (sz * len(configs))(*[int(f) for f in fft_sizes])
         self.h = vp()
-        check(lib().fvad_vad_batch_create_sweep_sized(arr, sizes, len(configs), sample_rate, n_channels, n_streams, C.byref(self.h)),
-              "fvad_vad_batch_create_sweep_sized")
-        self.n_streams, self.n_channels, self.n_configs = n_streams, n_channels, len(configs)
-        self.sizes, self.size_of_band = self.frame_sizes()
-
-    def retain(self, ctx, keep):
-        """VadSweep.retain; the frame sizes and bands are the kept configs' afterwards"""
-        VadSweep.retain(self, ctx, keep)
-        self.sizes, self.size_of_band = self.frame_sizes()
-
-    def frame_sizes(self):
-        """-> (the distinct sizes in first-seen config order, the size index of each band)"""
-        n = sz()
-        sizes = (sz * self.n_configs)()
-        sob = (C.c_uint32 * self.n_configs)()
-        check(lib().fvad_vad_batch_frame_sizes(self.h, sizes, self.n_configs, C.byref(n), sob), "fvad_vad_batch_frame_sizes")
-        n_bands = sz()
-        lib().fvad_vad_batch_bands(self.h, None, 0, C.byref(n_bands), None)
-        return [sizes[g] for g in range(n.value)], [sob[j] for j in range(n_bands.value)]
+        check(lib().fvad_vad_batch_create_sweep_sized(_config_array(configs), sizes, len(configs), sample_rate, n_channels, n_streams,
+                                                      C.byref(self.h)), "fvad_vad_batch_create_sweep_sized")
+        self._created(n_streams, n_channels, len(configs))
 
     def bands(self):
         """-> ([(fft_size, min_bin, max_bin)] of the distinct bands, size-major, band_of [config])"""
         bins, band_of = VadSweep.bands(self)
         return [(self.sizes[self.size_of_band[j]], lo, hi) for j, (lo, hi) in enumerate(bins)], band_of
 
-    def size_blocks(self):
-        """-> [(fft_size, first band, [(min_bin, max_bin)])] per size: the run of band blocks of each size"""
-        bands, _ = self.bands()
-        out = []
-        for g, F in enumerate(self.sizes):
-            js = [j for j in range(len(bands)) if self.size_of_band[j] == g]
-            out.append((F, js[0], [bands[j][1:] for j in js]))
-        return out
-
-    def run(self, band, chunk_rms, n_frames, first_sample=0, n_threads=1, chunk_size=24000):
-        """fvad_vad_batch_run_sized: band [n_bands][n_streams * n_channels][stride] (bands() order; a contiguous last axis),
-        n_frames[g] frames of size g from sample first_sample on, chunk_rms [lanes][n_chunks] from the part's first chunk"""
-        assert band.dtype == np.float32 and chunk_rms.dtype == np.float32
-        assert (band.shape[2] <= 1 or band.strides[2] == 4) and band.strides[1] == band.shape[2] * 4 and band.strides[0] == band.shape[1] * band.strides[1]
-        assert chunk_rms.shape[1] <= 1 or chunk_rms.strides[1] == 4
-        assert band.shape[1] == chunk_rms.shape[0] == self.n_streams * self.n_channels
-        nf = (sz * len(self.sizes))(*[int(x) for x in n_frames])
-        check(lib().fvad_vad_batch_run_sized(self.h, C.cast(band.ctypes.data, c_float_p), band.shape[2], nf,
-                                             C.cast(chunk_rms.ctypes.data, c_float_p), chunk_rms.strides[0] // 4, chunk_rms.shape[1],
-                                             chunk_size, int(first_sample), n_threads), "fvad_vad_batch_run_sized")
-
-    def _counts(self, n_frames, n_chunks):
-        G, S = len(self.sizes), self.n_streams
-        flat = [int(x) for row in n_frames for x in row]
-        assert len(flat) == G * S and len(n_chunks) == S
-        return (sz * (G * S))(*flat), (sz * S)(*[int(x) for x in n_chunks])
-
-    def run_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, chunk_size=24000):
-        """fvad_vad_batch_run_device_sized: n_frames [size][stream], n_chunks [stream]; d_band as bands() orders the blocks"""
-        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
-        nf, nc = self._counts(n_frames, n_chunks)
-        ctx._ck(lib().fvad_vad_batch_run_device_sized(ctx.h, self.h, vp(d_band), band_stride, nf, fptr(chunk_rms), chunk_rms.shape[1], nc,
-                                                      chunk_size), "fvad_vad_batch_run_device_sized")
-
-    def run_device_part(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_sample, chunk_size=24000):
-        """fvad_vad_batch_run_device_part_sized: frames of every size from sample first_sample on, n_frames [size][stream]"""
-        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
-        nf, nc = self._counts(n_frames, n_chunks)
-        ctx._ck(lib().fvad_vad_batch_run_device_part_sized(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf,
-                                                           fptr(chunk_rms), chunk_rms.shape[1], nc, chunk_size, int(first_sample)),
-                "fvad_vad_batch_run_device_part_sized")
+    run = VadSweep.run_sized
+    run_device = VadSweep.run_device_sized
+    run_device_part = VadSweep.run_device_part_sized
 
 
 def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_threads=1):

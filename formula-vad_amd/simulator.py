@@ -19,6 +19,7 @@ SimulationInstance.zig:101-104).  Differences, by design:
   * `preload_audio` only changes how samples are pushed in the reference, not the result.
 """
 import argparse
+import collections
 import itertools
 import json
 import math
@@ -351,6 +352,18 @@ def _agg_row(agg):
 SWEEP_DEVICE_MIN_CONFIGS = 256
 
 
+def _engine_opts(config0, F):
+    """the engine's options for a sweep's denoising pass: it sums config 0's band at F points (FFT.freqToBin as the library
+    computes it); the sweep's bands come from their own pass"""
+    probe = fv.VadSweep(1, [config0], fft_size=F)
+    (min_bin, max_bin), = probe.bands()[0]
+    probe.close()
+    opts = fv.EngineOpts()
+    fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
+    opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
+    return opts
+
+
 def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
     """The denoising pass of a sweep: every channel of every instance is one lane of ONE device batch (ragged lengths padded to
     the longest: chunks are causal, so padding changes no real chunk), fvad_engine_enqueue_device with the denoised audio kept
@@ -380,10 +393,7 @@ def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
             else:
                 host[l, :p.shape[1]] = p[c]
             l += 1
-    # the engine pass sums config 0's band (FFT.freqToBin as the library computes it); the sweep's bands come from their own pass
-    probe = fv.VadSweep(1, [config0], fft_size=F)
-    (min_bin, max_bin), = probe.bands()[0]
-    probe.close()
+    opts = _engine_opts(config0, F)
     d_pcm = dalloc(host.nbytes)
     ctx.to_device(d_pcm, host)
     del host
@@ -391,15 +401,77 @@ def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
     d_band0 = dalloc(n_lanes * max(nf_all, 1) * 4)
     d_rms = dalloc(n_lanes * max(n_ck, 1) * 4)
     if n_ck:
-        opts = fv.EngineOpts()
-        fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
-        opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
         ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d_pcm), n_lanes, stride, L, fv.vp(d_den), fv.vp(d_band0),
                                                     fv.vp(d_rms), fv.C.byref(opts)), "fvad_engine_enqueue_device")
     rms = np.zeros((n_lanes, max(n_ck, 1)), np.float32)
     if n_ck:
         ctx.to_host(rms, d_rms)
     return groups, n_chunks, n_den, nf_all, d_den, rms
+
+
+# What every share of a sweep needs (run_grid makes one per call; run_sweep one without scoring): the configs, their Evaluator
+# StatConfigs and frame sizes (sizes_of[c]; F, the plan's, for every config of a grid without "fft_size"), sized (the grid has
+# "fft_size": the batches are made with fvad_vad_batch_create_sweep_sized), and run_grid's arguments of the same names, n_threads
+# per share
+_SweepJob = collections.namedtuple("_SweepJob", "configs stat_cfgs sizes_of sized F slice_chunks vad_on score_on n_threads overlap")
+
+
+def _new_batch(job, n_streams, nch):
+    """a batch of the job's configs; whichever kind it is, the run paths use its sizes, size_blocks() and sample-based calls"""
+    if job.sized:
+        return fv.VadSweepSized(n_streams, job.configs, job.sizes_of, n_channels=nch)
+    return fv.VadSweep(n_streams, job.configs, n_channels=nch, fft_size=job.F)
+
+
+def _group_band_sums(ctx, b, members, n_chunks, d_gden, n_lanes, n_den, dalloc):
+    """The band sums of a channel-count group of an unsliced sweep, for batch b over the group's n_lanes lanes of denoised audio
+    at d_gden: one fvad_engine_band_sums_device pass per frame size into its run of band blocks.  Returns (the bands' device
+    address, their stride: the frames of the smallest size, the frames to run [size][stream])."""
+    bstride = max(n_den // min(b.sizes), 1)
+    d_gband = dalloc(len(b.size_of_band) * n_lanes * bstride * 4)
+    for Fg, j0, bins_g in b.size_blocks():
+        if n_den // Fg:
+            ctx.band_sums_device(d_gden, n_lanes, n_den, n_den, bins_g, d_gband + j0 * n_lanes * bstride * 4, bstride, fft_size=Fg)
+    return d_gband, bstride, [[n_chunks[i] * 24000 // Fg for i in members] for Fg in b.sizes]
+
+
+def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_chunks, times, done, stop=None):
+    """The machines of a group over _group_band_sums' output: in b on the device, or with vad_on "host" in one single-stream
+    host batch per instance (instances differ in length), closed before the next is made.  done(batch, the instances it
+    holds) is called once a batch's machines have run; their time is added to times["machines"].  With device scoring (the
+    caller has set b's references) the context's kernel timing is on around the run if it was off, and the scoring kernel's
+    time goes to times["scoring"] instead (a caller's own timing records are left alone: the machines' time then includes the
+    scoring).  stop: checked before every host batch."""
+    if job.vad_on == "device":
+        timed = job.score_on == "device" and not ctx.timing
+        if timed:
+            ctx.enable_timing(True)
+        try:
+            t0 = time.perf_counter()
+            b.run_device_sized(ctx, d_gband, bstride, nf, g_rms, [n_chunks[i] for i in members])
+            wall = time.perf_counter() - t0
+            score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
+        finally:
+            if timed:
+                ctx.enable_timing(False)
+        times["machines"] += wall - score_s
+        times["scoring"] += score_s
+        done(b, members)
+        return
+    gband = ctx.to_host(np.empty((len(b.size_of_band), len(members) * nch, bstride), np.float32), d_gband)
+    for k, i in enumerate(members):
+        if stop is not None:
+            _check_stop(stop)
+        one = _new_batch(job, 1, nch)
+        try:
+            t0 = time.perf_counter()
+            nf_i = [row[k] for row in nf]
+            one.run_sized(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :max(max(nf_i), 1)]),
+                          np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), nf_i, n_threads=job.n_threads)
+            times["machines"] += time.perf_counter() - t0
+            done(one, [i])
+        finally:
+            one.close()
 
 
 def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16):
@@ -441,40 +513,27 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
         return a
 
     segs = [[None] * len(audio) for _ in configs]
+    job = _SweepJob(configs=configs, stat_cfgs=None, sizes_of=[F] * len(configs), sized=False, F=F, slice_chunks=None, vad_on=vad_on,
+                    score_on="host", n_threads=n_threads, overlap=False)
+
+    def keep_segments(batch, insts):
+        for c in range(len(configs)):
+            for i, per in zip(insts, batch.segments(c)):
+                segs[c][i] = per
+
+    times = {"machines": 0.0, "scoring": 0.0}
     try:
-        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
+        groups, n_chunks, n_den, _, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
         l0 = 0
         for nch, members in groups.items():
-            sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+            sweep = _new_batch(job, len(members), nch)
             try:
-                bins, _ = sweep.bands()
                 g_lanes = list(range(l0, l0 + len(members) * nch))
                 l0 += len(g_lanes)
-                d_gden = d_den + g_lanes[0] * n_den * 4
-                bstride = max(nf_all, 1)
-                d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                if nf_all:
-                    ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
-                g_rms = np.ascontiguousarray(rms[g_lanes])
-                if vad_on == "device":
-                    sweep.run_device(ctx, d_gband, bstride, [n_chunks[i] * chunk // F for i in members], g_rms,
-                                     [n_chunks[i] for i in members])
-                    for c in range(len(configs)):
-                        per = sweep.segments(c)
-                        for k, i in enumerate(members):
-                            segs[c][i] = per[k]
-                    continue
-                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
-                for k, i in enumerate(members):   # instances differ in length: one host batch each
-                    nf_i = n_chunks[i] * chunk // F
-                    one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
-                    try:
-                        one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]),
-                                np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)]), n_threads=n_threads)
-                        for c in range(len(configs)):
-                            segs[c][i] = one.segments(c)[0]
-                    finally:
-                        one.close()
+                d_gband, bstride, nf = _group_band_sums(ctx, sweep, members, n_chunks, d_den + g_lanes[0] * n_den * 4, len(g_lanes),
+                                                        n_den, dalloc)
+                _group_machines(ctx, job, sweep, members, nch, d_gband, bstride, nf, np.ascontiguousarray(rms[g_lanes]), n_chunks,
+                                times, keep_segments)
             finally:
                 sweep.close()
     finally:
@@ -659,9 +718,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
 
     slice_chunks = N runs the whole pipeline in time slices of N chunks (a positive multiple of slice_align(fft_size), 16 at
     fft_size 1024; ValueError before any GPU work otherwise), so that device and host memory are bounded by the slice, not the
-    corpus (_run_grid_sliced): the audio is read slice by slice from the mapped files (wav_map), each slice denoised from zero
+    corpus (_grid_sliced): the audio is read slice by slice from the mapped files (wav_map), each slice denoised from zero
     history with its SLICE_HALO_CHUNKS-chunk halo, its band sums computed, and the machines run on in parts
-    (fvad_vad_batch_run_device_part, or fvad_vad_batch_run_part with vad_on "host").  On a context with the option
+    (fvad_vad_batch_run_device_part_sized, or fvad_vad_batch_run_sized with vad_on "host").  On a context with the option
     reproducible = 1 the statistics are the unsliced run's bit for bit; by default the NN kernels the engine selects depend on
     the launch size, which can move the gains by about 1e-6 and flip a decision.  None: everything in one pass, as above.
 
@@ -747,12 +806,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         halving = {"eta": int(halving_eta), "rungs": int(halving_rungs)}
     plan = load_plan(plan_path)
     F = plan["fft_size"]
-    if slice_chunks is not None:
-        if sized:
-            check_slice_chunks_sized(slice_chunks, grid["fft_size"])
-        else:
-            check_slice_chunks(slice_chunks, F)
     sizes_of = [F if f is None else f for f in sizes_of]
+    if slice_chunks is not None:
+        check_slice_chunks_sized(slice_chunks, sizes_of)
     stat_cfgs = [_stat_cfg(c) for c in configs]
     if slice_chunks is not None:   # the audio stays in its files: mapped, read slice by slice
         loaded = [(_map_audio(i), _read_labels(i)) for i in plan["instances"]]
@@ -788,6 +844,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     share_times = [{"device": int(devices[s]) if devices is not None else getattr(ctxs[s], "device", None), "instances": shares[s],
                     "wall": 0.0, "times": {}} for s in range(len(shares))]
     share_out = [(0, None)] * len(shares)
+    job = _SweepJob(configs=configs, stat_cfgs=stat_cfgs, sizes_of=sizes_of, sized=sized, F=F,
+                    slice_chunks=None if slice_chunks is None else int(slice_chunks), vad_on=vad_on, score_on=score_on,
+                    n_threads=max(1, n_threads // max(len(workers), 1)), overlap=bool(overlap))
     stop = threading.Event()   # set when a worker fails: the others stop at their next slice or rung
     errs, breaks = [], []
     t_all = time.perf_counter()
@@ -798,9 +857,8 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         st.update(denoise=0.0, bands=0.0, machines=0.0, scoring=0.0)
         ids = np.asarray(shares[s], np.intp)
         try:
-            share_out[s] = _grid_share(ctxs[s], [audio[i] for i in shares[s]], [refs[i] for i in shares[s]], ids, configs,
-                                       stat_cfgs, sizes_of if sized else None, F, slice_chunks, vad_on, score_on,
-                                       max(1, n_threads // len(workers)), stats, st, rungs, stop, **({"overlap": True} if overlap else {}))
+            share_out[s] = _grid_share(ctxs[s], job, [audio[i] for i in shares[s]], [refs[i] for i in shares[s]], ids, stats, st,
+                                       rungs, stop)
         except (threading.BrokenBarrierError, _Stopped) as e:   # another worker failed
             breaks.append(e)
         except BaseException as e:  # re-raised below, in the caller's thread
@@ -955,24 +1013,19 @@ class _Rungs:
                          "seconds": time.perf_counter() - self.t_rung})
 
 
-def _grid_share(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, slice_chunks, vad_on, score_on, n_threads, stats, times,
-                rungs, stop, overlap=False):
-    """run_grid's flow for one share of the instances on its own context: audio / refs the share's instances, ids their plan
-    indices (the columns of stats it fills); sizes_of None unless the grid is sized; rungs a _Rungs for successive halving;
-    stop an Event another worker sets when it fails.  Returns (slices run, device_bytes: None unsliced)."""
-    if slice_chunks is not None:
-        return _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, int(slice_chunks), vad_on, score_on, n_threads, stats,
-                                times, sizes_of, rungs, stop, overlap)
-    _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_on, score_on, n_threads, stats, times, stop)
+def _grid_share(ctx, job, audio, refs, ids, stats, times, rungs, stop):
+    """run_grid's flow for one share of the instances on its own context: job the call's _SweepJob, audio / refs the share's
+    instances, ids their plan indices (the columns of stats it fills); rungs a _Rungs for successive halving; stop an Event
+    another worker sets when it fails.  Returns (slices run, device_bytes: None unsliced)."""
+    if job.slice_chunks is not None:
+        return _grid_sliced(ctx, job, audio, refs, ids, stats, times, rungs, stop)
+    _grid_unsliced(ctx, job, audio, refs, ids, stats, times, stop)
     return 1, None
 
 
-def _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_on, score_on, n_threads, stats, times, stop):
+def _grid_unsliced(ctx, job, audio, refs, ids, stats, times, stop):
     """run_grid without slices over a share: one denoising batch of the share's instances (padded to its longest), then per
     channel-count group the band sums, the machines and the scoring (run_grid's docstring)"""
-    sized = sizes_of is not None
-    NC = len(configs)
-    chunk = 24000
     allocs = []
 
     def dalloc(nbytes):
@@ -980,94 +1033,35 @@ def _grid_unsliced(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, vad_o
         allocs.append(a)
         return a
 
+    def score(batch, insts):
+        if job.score_on == "host":
+            t0 = time.perf_counter()
+            batch.set_references([refs[i] for i in insts], job.stat_cfgs)
+            batch.score(job.n_threads)
+            times["scoring"] += time.perf_counter() - t0
+        for c in range(len(job.configs)):
+            stats[c, ids[insts]] = batch.config_stats(c)
+
     try:
         t0 = time.perf_counter()
-        groups, n_chunks, n_den, nf_all, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
+        groups, n_chunks, n_den, _, d_den, rms = _denoise_for_sweep(ctx, audio, job.F, job.configs[0], dalloc)
         times["denoise"] = time.perf_counter() - t0
         l0 = 0
         for nch, members in groups.items():
             _check_stop(stop)
-            if sized:   # several frame sizes in one batch: one band-sum pass per size into its run of band blocks
-                sweep = fv.VadSweepSized(len(members), configs, sizes_of, n_channels=nch)
-            else:
-                sweep = fv.VadSweep(len(members), configs, n_channels=nch, fft_size=F)
+            sweep = _new_batch(job, len(members), nch)
             try:
                 t0 = time.perf_counter()
-                bins, _ = sweep.bands()
                 g_lanes = list(range(l0, l0 + len(members) * nch))
                 l0 += len(g_lanes)
-                d_gden = d_den + g_lanes[0] * n_den * 4
-                if sized:
-                    bstride = max(n_den // min(sweep.sizes), 1)
-                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                    for Fg, j0, bins_g in sweep.size_blocks():
-                        if n_den // Fg:
-                            ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins_g,
-                                                 d_gband + j0 * len(g_lanes) * bstride * 4, bstride, fft_size=Fg)
-                    nf_run = [[n_chunks[i] * chunk // Fg for i in members] for Fg in sweep.sizes]
-                else:
-                    bstride = max(nf_all, 1)
-                    d_gband = dalloc(len(bins) * len(g_lanes) * bstride * 4)
-                    if nf_all:
-                        ctx.band_sums_device(d_gden, len(g_lanes), n_den, n_den, bins, d_gband, bstride, fft_size=F)
-                    nf_run = [n_chunks[i] * chunk // F for i in members]
+                d_gband, bstride, nf = _group_band_sums(ctx, sweep, members, n_chunks, d_den + g_lanes[0] * n_den * 4, len(g_lanes),
+                                                        n_den, dalloc)
                 g_rms = np.ascontiguousarray(rms[g_lanes])
                 times["bands"] += time.perf_counter() - t0
-                if vad_on == "device":
-                    if score_on == "device":
-                        sweep.set_references([refs[i] for i in members], stat_cfgs)
-                        sweep.keep_segments(False)
-                    # the scoring kernel's time: kernel timing on around this call only, when the caller has it off (a
-                    # caller's own timing records are left alone: the machines' time then includes the scoring)
-                    timed = score_on == "device" and not ctx.timing
-                    if timed:
-                        ctx.enable_timing(True)
-                    try:
-                        t0 = time.perf_counter()
-                        sweep.run_device(ctx, d_gband, bstride, nf_run, g_rms, [n_chunks[i] for i in members])
-                        wall = time.perf_counter() - t0
-                        score_s = ctx.kernel_times().get("vad_score", 0.0) / 1e3 if timed else 0.0
-                    finally:
-                        if timed:
-                            ctx.enable_timing(False)
-                    if score_on == "device":
-                        times["machines"] += wall - score_s
-                        times["scoring"] += score_s
-                    else:
-                        times["machines"] += wall
-                        t0 = time.perf_counter()
-                        sweep.set_references([refs[i] for i in members], stat_cfgs)
-                        sweep.score(n_threads)
-                        times["scoring"] += time.perf_counter() - t0
-                    for c in range(NC):
-                        stats[c, ids[members]] = sweep.config_stats(c)
-                    continue
-                gband = ctx.to_host(np.empty((len(bins), len(g_lanes), bstride), np.float32), d_gband)
-                for k, i in enumerate(members):   # instances differ in length: one host batch each
-                    _check_stop(stop)
-                    if sized:
-                        one = fv.VadSweepSized(1, configs, sizes_of, n_channels=nch)
-                    else:
-                        nf_i = n_chunks[i] * chunk // F
-                        one = fv.VadSweep(1, configs, n_channels=nch, fft_size=F)
-                    try:
-                        t0 = time.perf_counter()
-                        i_rms = np.ascontiguousarray(g_rms[k * nch:(k + 1) * nch, :max(n_chunks[i], 1)])
-                        if sized:
-                            nf_i = [n_chunks[i] * chunk // Fg for Fg in one.sizes]
-                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :max(max(nf_i), 1)]), i_rms, nf_i,
-                                    n_threads=n_threads)
-                        else:
-                            one.run(np.ascontiguousarray(gband[:, k * nch:(k + 1) * nch, :nf_i]), i_rms, n_threads=n_threads)
-                        times["machines"] += time.perf_counter() - t0
-                        t0 = time.perf_counter()
-                        one.set_references([refs[i]], stat_cfgs)
-                        one.score(n_threads)
-                        for c in range(NC):
-                            stats[c, ids[i]] = one.config_stats(c)[0]
-                        times["scoring"] += time.perf_counter() - t0
-                    finally:
-                        one.close()
+                if job.score_on == "device":
+                    sweep.set_references([refs[i] for i in members], job.stat_cfgs)
+                    sweep.keep_segments(False)
+                _group_machines(ctx, job, sweep, members, nch, d_gband, bstride, nf, g_rms, n_chunks, times, score, stop)
             finally:
                 sweep.close()
     finally:
@@ -1109,105 +1103,188 @@ def _clip_labels(ref, t):
     return a
 
 
-def _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts, fr_slice, stats, times, stop,
-                    ov=None):
-    """_run_grid_sliced with successive halving (run_grid's halving_eta / halving_rungs) over one share: every group's device
-    batch alive at once, the slices run one after the other across the groups, so that every rung sees every instance at the
-    same point in time.  At a rung's end (rungs.ends: the whole plan's): each group's machines scored on the device against
-    its labels cut to the rung (or the instance's end) into stats' columns ids[members]; then, with every share's workers
-    at the barrier, rungs.choose aggregates per config over all instances in plan order and keeps the ceil(n / eta) best by
-    F-score (ties to the lower config index); every batch is cut to them (VadSweep.retain) and the full labels go back.  A
-    share whose instances have all ended still scores and retains at every rung.  Fills stats (survivors: the whole corpus;
-    dropped configs: the last prefix they were scored on) and rungs' survivors, rung, evaluated seconds and log.  Returns
-    (slices run, the largest device memory the share's batches held together).  ov (an _Overlap): the parts do not wait -- a
-    slice's machines run beside the next slice's denoising, and every part is waited for before a rung scores."""
-    chunk = 24000
-    stat_cfgs = rungs.stat_cfgs
-    batches = {}
+class _DeviceParts:
+    """a channel-count group's machines of a sliced grid: one device batch (b), run in parts.  sizes and blocks are the
+    batch's frame sizes and size_blocks(), kept up by retain."""
+
+    def __init__(self, ctx, job, nch, refs):
+        self.ctx, self.job, self.refs = ctx, job, refs
+        self.b = _new_batch(job, len(refs), nch)
+        self.sizes, self.blocks = self.b.sizes, self.b.size_blocks()
+        if job.score_on == "device":
+            self.b.set_references(refs, job.stat_cfgs)
+            self.b.keep_segments(False)
+
+    def part(self, d_bands, stride, n_frames, rms, n_chunks, first_sample):
+        """the slice from first_sample on: n_frames [size][stream] of the band sums at d_bands, chunk RMS [lanes][chunks] on the host"""
+        self.b.run_device_part_sized(self.ctx, d_bands, stride, n_frames, rms, n_chunks, first_sample)
+
+    def score(self, stats, cols, alive, refs=None):
+        """everything run so far into stats[o, cols] for the batch's configs o = alive[c]: the device scorer, or with score_on
+        "host" the host scorer on the segments the parts kept.  refs: labels to score against instead of the group's (a
+        rung's, cut to its prefix)"""
+        if refs is not None or self.job.score_on == "host":
+            self.b.set_references(self.refs if refs is None else refs, [self.job.stat_cfgs[o] for o in alive])
+        if self.job.score_on == "device":
+            self.b.score_device(self.ctx)
+        else:
+            self.b.score(self.job.n_threads)
+        for c, o in enumerate(alive):
+            stats[o, cols] = self.b.config_stats(c)
+
+    def retain(self, keep):
+        """cut the batch to its configs keep"""
+        self.b.retain(self.ctx, keep)
+        self.sizes, self.blocks = self.b.sizes, self.b.size_blocks()
+
+    def full_labels(self, alive):
+        """the group's own labels back after a rung's cut ones, for the batch's configs alive"""
+        self.b.set_references(self.refs, [self.job.stat_cfgs[o] for o in alive])
+
+    def device_bytes(self):
+        return self.b.device_bytes()
+
+    def close(self):   # (closing a batch waits for its part)
+        self.b.close()
+
+
+class _HostParts:
+    """_DeviceParts' shape for vad_on "host": one single-stream host batch per instance (instances differ in length), run on in
+    parts over the slice's band sums copied back (fvad_vad_batch_run_sized).  No retain: halving needs device machines."""
+
+    def __init__(self, ctx, job, nch, refs):
+        self.ctx, self.job, self.nch, self.refs = ctx, job, nch, refs
+        self.hosts = [_new_batch(job, 1, nch) for _ in refs]
+        self.sizes, self.blocks = self.hosts[0].sizes, self.hosts[0].size_blocks()
+
+    def part(self, d_bands, stride, n_frames, rms, n_chunks, first_sample):
+        nch = self.nch
+        n_bands = sum(len(bins) for _, _, bins in self.blocks)
+        band = self.ctx.to_host(np.empty((n_bands, len(self.hosts) * nch, stride), np.float32), d_bands)
+        for k, h in enumerate(self.hosts):
+            nf_k = [row[k] for row in n_frames]
+            if max(nf_k) == 0 and first_sample > 0:
+                continue   # ended (its machines keep their results)
+            h.run_sized(np.ascontiguousarray(band[:, k * nch:(k + 1) * nch, :max(max(nf_k), 1)]),
+                        np.ascontiguousarray(rms[k * nch:(k + 1) * nch, :max(n_chunks[k], 1)]), nf_k, first_sample=first_sample,
+                        n_threads=self.job.n_threads)
+
+    def score(self, stats, cols, alive, refs=None):
+        assert refs is None and len(alive) == len(self.job.configs)   # (rungs score device machines only)
+        for k, h in enumerate(self.hosts):
+            h.set_references([self.refs[k]], self.job.stat_cfgs)
+            h.score(self.job.n_threads)
+            for c, o in enumerate(alive):
+                stats[o, cols[k]] = h.config_stats(c)[0]
+
+    def device_bytes(self):
+        return 0
+
+    def close(self):
+        for h in self.hosts:
+            h.close()
+
+
+def _run_slices(ctx, job, audio, refs, ids, groups, n_chunks, K, buf, stats, times, stop, ov=None, rungs=None):
+    """The slice loop of a sliced grid over one share: the time slices [s0, s1) of job.slice_chunks chunks up to chunk K in
+    the outer loop, the channel-count groups {n_channels: [instance]} in the inner one, every group's machines alive
+    (_DeviceParts, or _HostParts with vad_on "host"); a group whose instances have all ended is skipped and not counted.  Each
+    slice is read, denoised and its band sums computed (_slice_denoise_and_bands into buf, _grid_sliced's buffers), then the
+    group's machines run on; an instance gets 0 frames once it has ended.  At the end every machine is scored into stats'
+    columns ids[members].  Returns (slices run, the largest device memory the batches held together).
+    ov (an _Overlap): the parts do not wait -- a slice's machines run beside the next slice's denoising, and every part is
+    waited for before anything is scored.
+    rungs (a _Rungs: successive halving, device machines and scoring; K its rungs.K, so that every rung sees every instance at
+    the same point in time): at a rung's end (rungs.ends: the whole plan's) each group's machines are scored against its labels
+    cut to the rung (or the instance's end); then, with every share's workers at the barrier, rungs.choose aggregates per
+    config over all instances in plan order and keeps the ceil(n / eta) best by F-score (ties to the lower config index);
+    every batch is cut to them (VadSweep.retain) and the full labels go back.  A share whose instances have all ended still
+    scores and retains at every rung.  stats then holds the whole corpus for the survivors and, for a dropped config, the
+    last prefix it was scored on; rungs holds the survivors, rung, evaluated seconds and log."""
+    chunk, N = 24000, job.slice_chunks
+    machines = {}
     peak, n_slices = 0, 0
+
+    def held():
+        return max(peak, sum(m.device_bytes() for m in machines.values()))
+
     try:
         for nch, members in groups.items():
-            b = new_batch(len(members), nch)
-            batches[nch] = b
-            b.set_references([refs[i] for i in members], stat_cfgs)
-            b.keep_segments(False)
-        for s0 in range(0, rungs.K, N):
+            machines[nch] = (_DeviceParts if job.vad_on == "device" else _HostParts)(ctx, job, nch, [refs[i] for i in members])
+        for s0 in range(0, K, N):
             _check_stop(stop)
-            s1 = min(s0 + N, rungs.K)
+            s1 = min(s0 + N, K)
             for nch, members in groups.items():
-                b = batches[nch]
                 if s0 >= max(n_chunks[i] for i in members):
                     continue   # every instance of the group has ended
+                m = machines[nch]
                 n_slices += 1
-                sized = isinstance(b, fv.VadSweepSized)
-                blocks = b.size_blocks() if sized else [(F, 0, b.bands()[0])]
-                sizes = [Fg for Fg, _, _ in blocks] if not sized else b.sizes
                 dset = None if ov is None else ov.next_set()
-                rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times,
+                rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, m.blocks, times,
                                                None if ov is None else ov.sets[dset])
                 nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
-                nf_g = [[max(0, min(n_chunks[i] * chunk // Fg, s1 * chunk // Fg) - s0 * chunk // Fg) for i in members] for Fg in sizes]
+                # each size's frames of the slice, per instance
+                nf = [[max(0, min(n_chunks[i] * chunk // Fg, s1 * chunk // Fg) - s0 * chunk // Fg) for i in members] for Fg in m.sizes]
                 if ov is not None:
-                    ov.launch(dset, b, fr_slice, nf_g, rms, nc, s0 * chunk)
+                    ov.launch(dset, m.b, buf.fr_slice, nf, rms, nc, s0 * chunk)
                     continue
                 t0 = time.perf_counter()
-                if sized:
-                    b.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
-                else:
-                    b.run_device_part(ctx, d["bands"], fr_slice, nf_g[0], rms, nc, s0 * chunk // F)
+                m.part(buf.d["bands"], buf.fr_slice, nf, rms, nc, s0 * chunk)
                 times["machines"] += time.perf_counter() - t0
-            peak = max(peak, sum(b.device_bytes() for b in batches.values()))
+            peak = held()
+            if rungs is None:
+                continue
             rungs.count(ids, s0, s1)
             if s1 not in rungs.ends:
                 continue
             if ov is not None:
                 ov.drain()
-                peak = max(peak, sum(b.device_bytes() for b in batches.values()))
+                peak = held()
             # ---- a rung: score the prefix [0, s1) against the labels cut to it, keep the best 1 / eta
             t0 = time.perf_counter()
             t_end = s1 * chunk / 48000.0
-            cur_cfgs = [stat_cfgs[o] for o in rungs.alive]
             for nch, members in groups.items():
-                b = batches[nch]
-                b.set_references([_clip_labels(refs[i], min(t_end, n_chunks[i] * chunk / 48000.0)) for i in members], cur_cfgs)
-                b.score_device(ctx)
-                for c, o in enumerate(rungs.alive):
-                    stats[o, ids[members]] = b.config_stats(c)
+                machines[nch].score(stats, ids[members], rungs.alive,
+                                    [_clip_labels(refs[i], min(t_end, n_chunks[i] * chunk / 48000.0)) for i in members])
             times["scoring"] += time.perf_counter() - t0
             rungs.wait(rungs.choose)
             t0 = time.perf_counter()
-            for b in batches.values():
-                b.retain(ctx, rungs.keep)
+            for m in machines.values():
+                m.retain(rungs.keep)
             times["retain"] = times.get("retain", 0.0) + time.perf_counter() - t0
-            for nch, members in groups.items():   # the full labels for what follows
-                batches[nch].set_references([refs[i] for i in members], [stat_cfgs[o] for o in rungs.alive])
+            for m in machines.values():
+                m.full_labels(rungs.alive)
             rungs.wait(rungs.logged)
-        # ---- the survivors over the whole corpus
+        # ---- scoring: everything run (with halving: the survivors over the whole corpus)
         if ov is not None:
             ov.drain()
-            peak = max(peak, sum(b.device_bytes() for b in batches.values()))
+            peak = held()
         t0 = time.perf_counter()
         for nch, members in groups.items():
-            b = batches[nch]
-            b.score_device(ctx)
-            for c, o in enumerate(rungs.alive):
-                stats[o, ids[members]] = b.config_stats(c)
+            machines[nch].score(stats, ids[members], range(len(job.configs)) if rungs is None else rungs.alive)
         times["scoring"] += time.perf_counter() - t0
-        rungs.wait(rungs.ended)
+        if rungs is not None:
+            rungs.wait(rungs.ended)
     finally:
-        for b in batches.values():   # (closing a batch waits for its part)
-            b.close()
+        for m in machines.values():
+            m.close()
     return n_slices, peak
 
 
-def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times, dset=None):
-    """one time slice [s0, s1) of a channel-count group (_run_grid_sliced): the slice and its SLICE_HALO_CHUNKS-chunk halo read
+# a sliced share's buffers, allocated once for its largest group and reused slice after slice: d {name: device address}, host
+# (the slice's PCM, pinned), opts (the engine's), fr_slice (the band sums' stride: a full slice's frames at the smallest size)
+_SliceBufs = collections.namedtuple("_SliceBufs", "d host opts fr_slice")
+
+
+def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, blocks, times, dset=None):
+    """one time slice [s0, s1) of a channel-count group (_run_slices): the slice and its SLICE_HALO_CHUNKS-chunk halo read
     from the mapped files into the pinned host buffer, denoised from zero history, the band sums of the slice's frames for
     blocks [(F, first band, bins)] written to d["bands"] (stride fr_slice); returns the slice's chunk RMS [lanes][s1 - s0].
     dset (overlap: a (bands, rms) pair of device buffers): the band sums and the RMS go there and nothing comes back to the
     host -- returns (device address of the slice's first chunk's RMS, its lane stride); the calls wait for the context's main
     stream only, never for a device part in flight."""
     chunk = 24000
+    d, host, opts, fr_slice = buf
     start = max(s0 - SLICE_HALO_CHUNKS, 0)
     n = s1 - start
     L = len(members) * nch
@@ -1292,150 +1369,51 @@ class _Overlap:
             self._wait(j)
 
 
-def _run_grid_sliced(ctx, audio, refs, ids, configs, stat_cfgs, F, N, vad_on, score_on, n_threads, stats, times, sizes_of, rungs,
-                     stop, overlap=False):
-    """run_grid's pipeline in time slices of N chunks: per channel-count group, for each slice [s0, s1) the slice and its
+def _grid_sliced(ctx, job, audio, refs, ids, stats, times, rungs, stop):
+    """run_grid's pipeline in time slices of job.slice_chunks chunks over a share: each slice [s0, s1) and its
     SLICE_HALO_CHUNKS-chunk halo are read from the mapped files (audio[i]: [n_frames][n_channels]), denoised from zero history
     (fvad_engine_enqueue_device over [s0 - halo, s1), as shard.run_sliced_with_vad does), the band sums of the slice's frames
-    computed from the denoised audio at chunk s0 (fvad_engine_band_sums_device), and the machines run on: one device batch
-    per group in parts (fvad_vad_batch_run_device_part), or with vad_on "host" one host batch per instance
-    (fvad_vad_batch_run_part).  An instance gets 0 frames once it has ended.  The device buffers are allocated once, for the
-    largest group, and reused slice after slice.  Fills stats [config][instance][11] (the columns ids: the instances' plan
-    indices) and times; returns (slices run, device_bytes as run_grid describes it).  sizes_of (config c at frame size sizes_of[c]; None: every config at F): one sized
-    batch, one band-sum pass per size and slice, and parts from sample s0 * chunk (fvad_vad_batch_run_device_part_sized /
-    fvad_vad_batch_run_sized).  rungs: a _Rungs for successive halving -- _halving_slices' loop instead of the one below.
-    stop: checked before every slice (_Stopped once another worker has failed).  overlap (device machines and scoring): a
-    second set of the bands and rms buffers, the frame ratios computed on the device and the parts not waited for
-    (fvad_vad_batch_run_device_part_async): slice k's machines run beside slice k + 1's reading and denoising; times gains
-    machines_wait, the host time spent waiting for parts (it is part of machines)."""
-    chunk, H = 24000, SLICE_HALO_CHUNKS
+    computed from the denoised audio at chunk s0 (one fvad_engine_band_sums_device pass per frame size), and the machines run
+    on in parts from sample s0 * chunk (_run_slices).  A plain grid runs one channel-count group after the other, each to its
+    own longest instance, so that one batch is alive at a time; with successive halving (rungs) the slices run across all
+    groups, every group's batch alive.  The device buffers are allocated once, for the largest group, and reused slice after
+    slice.  Fills stats [config][instance][11] (the columns ids: the instances' plan indices) and times; returns (slices run,
+    device_bytes as run_grid describes it).  stop: checked before every slice (_Stopped once another worker has failed).
+    job.overlap (device machines and scoring): a second set of the bands and rms buffers, the frame ratios computed on the
+    device and the parts not waited for (fvad_vad_batch_run_device_part_async): slice k's machines run beside slice k + 1's
+    reading and denoising; times gains machines_wait, the host time spent waiting for parts (it is part of machines)."""
+    chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, job.slice_chunks, job.F
     n_chunks = [a.shape[0] // chunk for a in audio]
     groups = {}
     for i, a in enumerate(audio):
         groups.setdefault(a.shape[1], []).append(i)
-    sized = sizes_of is not None
-
-    def new_batch(n_streams, nch):
-        if sized:
-            return fv.VadSweepSized(n_streams, configs, sizes_of, n_channels=nch)
-        return fv.VadSweep(n_streams, configs, n_channels=nch, fft_size=F)
-
-    probe = new_batch(1, 1)
-    bins, _ = probe.bands()
-    # the frame sizes and each size's run of band blocks
-    blocks = probe.size_blocks() if sized else [(F, 0, bins)]
+    probe = _new_batch(job, 1, 1)
+    n_bands, f_min = len(probe.size_of_band), min(probe.sizes)
     probe.close()
-    f_min = min(Fg for Fg, _, _ in blocks)
-    probe = fv.VadSweep(1, [configs[0]], fft_size=F)   # the engine pass sums config 0's band (unused: the bands come from K4)
-    (min_bin, max_bin), = probe.bands()[0]
-    probe.close()
+    opts = _engine_opts(job.configs[0], F)             # (config 0's band is unused: the bands come from K4)
     n_max = N + H                                      # chunks of a slice with its halo
     lanes_max = max([len(m) * nch for nch, m in groups.items()] + [1])
     fr_slice = N * chunk // f_min                      # frames of a full slice at the smallest size (N * chunk is a multiple of each)
     own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4,
            "band0": lanes_max * (n_max * chunk // F + 1) * 4, "rms": lanes_max * n_max * 4,
-           "bands": len(bins) * lanes_max * fr_slice * 4}
-    if overlap:
+           "bands": n_bands * lanes_max * fr_slice * 4}
+    if job.overlap:
         own.update(bands2=own["bands"], rms2=own["rms"])
-    opts = fv.EngineOpts()
-    fv.lib().fvad_engine_opts_default(fv.C.byref(opts))
-    opts.min_bin, opts.max_bin, opts.fft_size = min_bin, max_bin, F
     d = {}
     host = None
-    batch_peak = 0
-    n_slices = 0
+    n_slices, batch_peak = 0, 0
     ws = ENGINE_WS_BYTES_PER_CHUNK * min(lanes_max * n_max, ENGINE_MAX_LAUNCH_CHUNKS)
     try:
         for k, nb in own.items():
             d[k] = ctx.device_alloc(max(nb, 16))
         host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
-        ov = _Overlap(ctx, d, times) if overlap else None
-        if rungs is not None:
-            n_slices, batch_peak = _halving_slices(ctx, audio, refs, ids, groups, n_chunks, new_batch, F, N, rungs, d, host, opts,
-                                                   fr_slice, stats, times, stop, ov)
-            return n_slices, sum(own.values()) + batch_peak + ws
-        for nch, members in groups.items():
-            L = len(members) * nch
-            K = max(n_chunks[i] for i in members)
-            nf_end = [[n_chunks[i] * chunk // Fg for i in members] for Fg, _, _ in blocks]
-            dev = None
-            hosts = []
-            if vad_on == "device":
-                dev = new_batch(len(members), nch)
-                if score_on == "device":
-                    dev.set_references([refs[i] for i in members], stat_cfgs)
-                    dev.keep_segments(False)
-            else:
-                hosts = [new_batch(1, nch) for _ in members]
-            try:
-                for s0 in range(0, K, N):
-                    _check_stop(stop)
-                    s1 = min(s0 + N, K)
-                    n_slices += 1
-                    dset = None if ov is None else ov.next_set()
-                    rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, d, host, opts, blocks, fr_slice, times,
-                                                   None if ov is None else ov.sets[dset])
-                    # each size's frames of the slice, per instance
-                    nf_g = [[max(0, min(e, s1 * chunk // Fg) - s0 * chunk // Fg) for e in ends] for (Fg, _, _), ends in zip(blocks, nf_end)]
-                    nf = nf_g[0]
-                    f0 = s0 * chunk // F
-                    nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
-                    # ---- the machines
-                    if ov is not None:
-                        ov.launch(dset, dev, fr_slice, nf_g, rms, nc, s0 * chunk)
-                        continue
-                    t0 = time.perf_counter()
-                    if dev is not None and sized:
-                        dev.run_device_part(ctx, d["bands"], fr_slice, nf_g, rms, nc, s0 * chunk)
-                        batch_peak = max(batch_peak, dev.device_bytes())
-                    elif dev is not None:
-                        dev.run_device_part(ctx, d["bands"], fr_slice, nf, rms, nc, f0)
-                        batch_peak = max(batch_peak, dev.device_bytes())
-                    elif sized:
-                        band = ctx.to_host(np.empty((len(bins), L, fr_slice), np.float32), d["bands"])
-                        for k, h in enumerate(hosts):
-                            nf_k = [row[k] for row in nf_g]
-                            if max(nf_k) == 0 and s0 > 0:
-                                continue   # ended (its machines keep their results)
-                            h.run(np.ascontiguousarray(band[:, k * nch:(k + 1) * nch, :max(max(nf_k), 1)]),
-                                  np.ascontiguousarray(rms[k * nch:(k + 1) * nch, :max(nc[k], 1)]), nf_k, first_sample=s0 * chunk,
-                                  n_threads=n_threads)
-                    else:
-                        band = ctx.to_host(np.empty((len(bins), L, fr_slice), np.float32), d["bands"])
-                        for k, h in enumerate(hosts):
-                            if nf[k] == 0 and f0 > 0:
-                                continue   # ended (its machines keep their results)
-                            b = np.ascontiguousarray(band[:, k * nch:(k + 1) * nch, :nf[k]])
-                            r = np.ascontiguousarray(rms[k * nch:(k + 1) * nch, :max(nc[k], 1)])
-                            fv.check(fv.lib().fvad_vad_batch_run_part(h.h, b.ctypes.data_as(fv.c_float_p), max(nf[k], 1), nf[k],
-                                                                      r.ctypes.data_as(fv.c_float_p), r.shape[1], nc[k], chunk, f0,
-                                                                      n_threads), "fvad_vad_batch_run_part")
-                    times["machines"] += time.perf_counter() - t0
-                # ---- scoring
-                if ov is not None:
-                    ov.drain()
-                    batch_peak = max(batch_peak, dev.device_bytes())
-                t0 = time.perf_counter()
-                if dev is not None:
-                    if score_on == "device":
-                        dev.score_device(ctx)
-                    else:
-                        dev.set_references([refs[i] for i in members], stat_cfgs)
-                        dev.score(n_threads)
-                    for c in range(len(configs)):
-                        stats[c, ids[members]] = dev.config_stats(c)
-                else:
-                    for k, (i, h) in enumerate(zip(members, hosts)):
-                        h.set_references([refs[i]], stat_cfgs)
-                        h.score(n_threads)
-                        for c in range(len(configs)):
-                            stats[c, ids[i]] = h.config_stats(c)[0]
-                times["scoring"] += time.perf_counter() - t0
-            finally:
-                if dev is not None:
-                    dev.close()
-                for h in hosts:
-                    h.close()
+        buf = _SliceBufs(d, host, opts, fr_slice)
+        ov = _Overlap(ctx, d, times) if job.overlap else None
+        # halving: every group in one loop to the plan's end; plain: a loop per group to the group's own end
+        runs = [(groups, rungs.K)] if rungs is not None else [({nch: m}, max(n_chunks[i] for i in m)) for nch, m in groups.items()]
+        for run_groups, K in runs:
+            n, peak = _run_slices(ctx, job, audio, refs, ids, run_groups, n_chunks, K, buf, stats, times, stop, ov, rungs)
+            n_slices, batch_peak = n_slices + n, max(batch_peak, peak)
     finally:
         for a in d.values():
             ctx.device_free(a)

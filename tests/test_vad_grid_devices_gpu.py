@@ -138,7 +138,7 @@ def test_a_failing_share(fv, pkg, contexts, tmp_path, monkeypatch):
     plan = write_plan(pkg, tmp_path, STREAMS)
     ctxs = contexts(2)
     victim = ctxs[0]
-    real = fv.VadSweep.run_device_part
+    real = fv.VadSweep.run_device_part_sized
     n = {"victim": 0}
 
     def part(self, ctx, *a, **k):
@@ -150,7 +150,7 @@ def test_a_failing_share(fv, pkg, contexts, tmp_path, monkeypatch):
 
     grid, kw = CASES["halving"]
     before = set(threading.enumerate())
-    monkeypatch.setattr(fv.VadSweep, "run_device_part", part)
+    monkeypatch.setattr(fv.VadSweep, "run_device_part_sized", part)
     with pytest.raises(RuntimeError, match="injected failure"):
         sim.run_grid(plan, grid, ctx=ctxs, out=None, **kw)
     monkeypatch.undo()

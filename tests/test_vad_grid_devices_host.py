@@ -130,8 +130,8 @@ def stand_in(sim, calls, fail_share=None, halting=None):
     """a _grid_share that records its arguments and writes known_stats into its instances' columns; with rungs it takes part
     in every rung as the real one does.  fail_share: the share (by its first instance) that raises at its first rung or, with
     halting set, at once while the others wait for the stop"""
-    def share(ctx, audio, refs, ids, configs, stat_cfgs, sizes_of, F, slice_chunks, vad_on, score_on, n_threads, stats, times,
-              rungs, stop):
+    def share(ctx, job, audio, refs, ids, stats, times, rungs, stop):
+        configs, slice_chunks, n_threads = job.configs, job.slice_chunks, job.n_threads
         calls.append({"device": ctx.device, "ids": list(ids), "n_threads": n_threads, "thread": threading.current_thread(),
                       "n_audio": len(audio)})
         want = known_stats(len(configs), stats.shape[1])

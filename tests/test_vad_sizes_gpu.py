@@ -181,6 +181,49 @@ def test_parts_equal_one_launch(fv, gpu_ctx, nch, lane_map, seg_cap):
         ctx.set_option("vad_seg_cap", None)
 
 
+def test_create_sweep_batch_takes_the_sized_device_calls(fv, gpu_ctx):
+    """a create_sweep batch at 1024 points: run_device_sized equals run_device and run_device_part_sized in 16-chunk parts
+    equals run_device_part, as raw bits; the shorter stream ends inside the second part"""
+    ctx = gpu_ctx
+    F, nch, n_chunks = 1024, 2, [24, 40]
+    cfgs = sweep_configs(8, 41)
+    S, NC = len(n_chunks), len(cfgs)
+    sws = [fv.VadSweep(S, cfgs, n_channels=nch, fft_size=F) for _ in range(4)]
+    frames, sized, frame_parts, sized_parts = sws
+    try:
+        bins, _ = frames.bands()
+        band, rms = synth_sized(S, nch, max(n_chunks), [(F, lo, hi) for lo, hi in bins], 43)
+        ends = [k * CHUNK // F for k in n_chunks]
+        d = upload(ctx, band)
+        try:
+            frames.run_device(ctx, d, band.shape[2], ends, rms, n_chunks)
+            sized.run_device_sized(ctx, d, band.shape[2], ends, rms, n_chunks)
+        finally:
+            ctx.device_free(d)
+        want = results(frames, S, NC)
+        assert_same(results(sized, S, NC), want, NC, S)
+        assert sum(len(x) for c in want[0] for x in c) > 8
+        for c0 in range(0, max(n_chunks), 16):
+            c1 = min(c0 + 16, max(n_chunks))
+            f0 = c0 * CHUNK // F
+            nf = [max(0, min(e, c1 * CHUNK // F) - f0) for e in ends]
+            nc = [max(0, min(k, c1) - c0) for k in n_chunks]
+            part = np.ascontiguousarray(band[:, :, f0:f0 + max(nf)])
+            prms = np.ascontiguousarray(rms[:, c0:c1])
+            d = upload(ctx, part)
+            try:
+                frame_parts.run_device_part(ctx, d, part.shape[2], nf, prms, nc, f0)
+                sized_parts.run_device_part_sized(ctx, d, part.shape[2], [nf] if c0 else nf, prms, nc, c0 * CHUNK)
+            finally:
+                ctx.device_free(d)
+        assert 16 < n_chunks[0] < 32   # (it ended inside the second part)
+        assert_same(results(frame_parts, S, NC), want, NC, S)
+        assert_same(results(sized_parts, S, NC), want, NC, S)
+    finally:
+        for sw in sws:
+            sw.close()
+
+
 def test_device_scoring_one_shot_and_parts(fv, gpu_ctx):
     ctx = gpu_ctx
     nch = 2

@@ -130,6 +130,56 @@ def test_one_size_equals_create_sweep(fv, F):
         b.close()
 
 
+@pytest.mark.parametrize("F", [512, 1024, 960])
+def test_create_sweep_batch_on_the_sized_surface(fv, F):
+    """a create_sweep batch reports its one size and its band blocks, follows a retain, and takes run_sized in parts from
+    first_sample, bit for bit its own run in one call"""
+    cfgs = [dict(CONFIGS[0]), dict(CONFIGS[1]), dict(CONFIGS[3])]   # two distinct bands: configs 0 and 2 share the default one
+    S, nch, n_chunks = 1, 2, 40
+    one = fv.VadSweep(S, cfgs, n_channels=nch, fft_size=F)
+    parts = fv.VadSweep(S, cfgs, n_channels=nch, fft_size=F)
+    try:
+        bins, band_of = parts.bands()
+        assert len(bins) == 2 and band_of == [0, 1, 0]
+        assert parts.sizes == [F] and parts.size_of_band == [0, 0]
+        assert parts.frame_sizes() == ([F], [0, 0])
+        assert parts.size_blocks() == [(F, 0, bins)]
+        band, rms = synth_sized(S, nch, n_chunks, [(F, lo, hi) for lo, hi in bins], 17)
+        nf = n_chunks * CHUNK // F
+        assert band.shape[2] == nf
+        one.run(band, rms, n_threads=2)
+        for c0 in range(0, n_chunks, 16):   # (16 chunks are a whole number of frames at each size)
+            c1 = min(c0 + 16, n_chunks)
+            f0, f1 = c0 * CHUNK // F, min(c1 * CHUNK // F, nf)
+            assert f0 * F == c0 * CHUNK
+            parts.run_sized(np.ascontiguousarray(band[:, :, f0:f1]), np.ascontiguousarray(rms[:, c0:c1]), [f1 - f0],
+                            first_sample=c0 * CHUNK, n_threads=2)
+        ra, rb = results(parts, S, len(cfgs)), results(one, S, len(cfgs))
+        assert seg_bits(ra[0]) == seg_bits(rb[0])
+        assert [[bits(x) for x in row] for row in ra[1]] == [[bits(x) for x in row] for row in rb[1]]
+        assert ra[2] == rb[2]
+        assert any(len(st) for c in ra[0] for st in c)   # (the configs do decide something)
+        # one band of one mono stream cut out of a wider array: numpy keeps the old strides on the axes of length 1
+        mono = fv.VadSweep(1, [cfgs[0]], fft_size=F)
+        ref1 = fv.VadSweep(1, [cfgs[0]], fft_size=F)
+        try:
+            cut = np.ascontiguousarray(band[:1, 1:2, :nf - 3])
+            mono.run_sized(cut, np.ascontiguousarray(rms[1:2]), nf - 3)
+            ref1.run(cut.copy(), np.ascontiguousarray(rms[1:2]))
+            assert seg_bits(results(mono, 1, 1)[0]) == seg_bits(results(ref1, 1, 1)[0]) and results(mono, 1, 1)[1:] == results(ref1, 1, 1)[1:]
+        finally:
+            mono.close()
+            ref1.close()
+        # a retain that drops config 1 drops its band
+        parts.retain(None, [0, 2])
+        assert parts.bands() == ([bins[0]], [0, 0])
+        assert parts.sizes == [F] and parts.size_of_band == [0]
+        assert parts.size_blocks() == [(F, 0, [bins[0]])]
+    finally:
+        one.close()
+        parts.close()
+
+
 def test_mixed_sizes_equal_per_size_batches(fv):
     cfgs, sizes = mixed_configs()
     S, nch = 2, 2
