@@ -320,6 +320,9 @@ pub extern "c" fn fvad_vad_batch_run_device(ctx: *Ctx, b: *VadBatch, d_band: [*]
 pub extern "c" fn fvad_vad_batch_run_device_part(ctx: *Ctx, b: *VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_frame: u64) c_int;
 pub extern "c" fn fvad_vad_batch_score_device(ctx: *Ctx, b: *VadBatch) c_int;
 pub extern "c" fn fvad_vad_batch_device_bytes(b: *const VadBatch) usize;
+/// 0 = no device launch yet, 1 = the batch's last device launch ran the lane form of the machines' kernel, 2 = the cooperative
+/// form (context option vad_chain, see fvad.h)
+pub extern "c" fn fvad_vad_batch_chain_form(b: *const VadBatch, form: *c_int) c_int;
 /// keep configs keep[0] < ... < keep[n_keep - 1] and drop the rest, between runs or device parts (successive halving); ctx may be
 /// null unless the batch holds device part state (see fvad.h)
 pub extern "c" fn fvad_vad_batch_retain_configs(ctx: ?*Ctx, b: *VadBatch, keep: [*]const u32, n_keep: usize) c_int;

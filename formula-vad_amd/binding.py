@@ -239,6 +239,7 @@ SIGNATURES = {
     "fvad_vad_batch_run_device_part": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
     "fvad_vad_batch_score_device": (C.c_int, [vp, vp]),
     "fvad_vad_batch_device_bytes": (sz, [vp]),
+    "fvad_vad_batch_chain_form": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "fvad_vad_batch_retain_configs": (C.c_int, [vp, vp, C.POINTER(C.c_uint32), sz]),
     "fvad_vad_batch_create_sweep_sized": (C.c_int, [C.POINTER(VadConfig), C.POINTER(sz), sz, sz, sz, sz, C.POINTER(vp)]),
     "fvad_vad_batch_frame_sizes": (C.c_int, [vp, C.POINTER(sz), sz, C.POINTER(sz), C.POINTER(C.c_uint32)]),
@@ -433,6 +434,15 @@ class Context:
         """testing / tuning aid (fvad_ctx_set_option); value None restores the default"""
         v = None if value is None else str(value).encode()
         self._ck(lib().fvad_ctx_set_option(self.h, name.encode(), v), "fvad_ctx_set_option")
+        self.__dict__.setdefault("_options_set", {})[name] = None if value in (None, "") else str(value)
+
+    def option_set(self, name):
+        """the value last given to set_option for name on this object (None: the default, or never set); for an option never set
+        here, what fvad_ctx_create read from the environment variable FVAD_<NAME>"""
+        opts = self.__dict__.get("_options_set", {})
+        if name in opts:
+            return opts[name]
+        return os.environ.get("FVAD_" + name.upper()) or None
 
     def options(self, **kv):
         """context manager: set the options, restore the defaults on exit"""
@@ -1061,6 +1071,15 @@ class VadSweep:
     def device_bytes(self):
         """fvad_vad_batch_device_bytes: device memory the batch holds between device parts (0 when it holds none)"""
         return lib().fvad_vad_batch_device_bytes(self.h)
+
+    def chain_form(self):
+        """fvad_vad_batch_chain_form: 0 before the first device launch, 1 when the last device launch ran the lane form of the
+        machines' kernel, 2 when it ran the cooperative form (context option vad_chain)"""
+        f = C.c_int(0)
+        rc = lib().fvad_vad_batch_chain_form(self.h, C.byref(f))
+        if rc:
+            raise FvadError(rc, "fvad_vad_batch_chain_form")
+        return f.value
 
     def retain(self, ctx, keep):
         """fvad_vad_batch_retain_configs: keep configs keep (strictly increasing indices) and drop the rest, between runs or

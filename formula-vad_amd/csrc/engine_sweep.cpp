@@ -377,10 +377,12 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
         FVAD_HIP(ctx, scratch.alloc(&d_segs, cap * (size_t)M));
         a.segs = d_segs;
         a.seg_cap = (uint32_t)cap;
+        a.coop = ctx->tune.vad_chain; // (context option vad_chain, read at every launch: the bits do not depend on it)
         time_begin(ctx, "vad_machines");
         const int e = fvad_launch_vad_machines(a, st);
         time_end(ctx);
         if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
+        b->chain_form = a.coop ? 2 : 1;
         FVAD_HIP(ctx, hipMemcpyAsync(count.data(), d_count, (size_t)M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         FVAD_HIP(ctx, hipStreamSynchronize(st));
         const size_t most = *std::max_element(count.begin(), count.end());
@@ -442,16 +444,18 @@ int grow_segs(fvad_ctx* ctx, DevParts* dp, size_t M, size_t cap, hipStream_t st)
 }
 
 // the machines of a part on its stream (the first launch, and again after a pause); the kernel-time table is the main stream's
-int launch_part(fvad_ctx* ctx, DevParts* dp, PartFlight& pf)
+int launch_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
 {
     pf.a.segs = dp->segs;
     pf.a.seg_cap = (uint32_t)dp->seg_cap;
+    pf.a.coop = ctx->tune.vad_chain; // (context option vad_chain, read at every launch: the bits do not depend on it)
     FVAD_HIP(ctx, hipMemsetAsync(dp->paused, 0, sizeof(unsigned), pf.st));
     const bool timed = pf.st == ctx->stream;
     if (timed) time_begin(ctx, "vad_machines");
     const int e = fvad_launch_vad_machines(pf.a, pf.st);
     if (timed) time_end(ctx);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
+    b->chain_form = pf.a.coop ? 2 : 1;
     return FVAD_OK;
 }
 
@@ -475,7 +479,7 @@ int finish_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
         if (const int rc = grow_segs(ctx, dp, M, cap, st)) return rc;
         pf.a.fresh = 0;
         pf.a.rebase = 0;
-        if (const int rc = launch_part(ctx, dp, pf)) return rc;
+        if (const int rc = launch_part(ctx, b, dp, pf)) return rc;
     }
 
     // ---- results: everything run so far
@@ -726,7 +730,7 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         a.lane_config = dp->lane_config;
         a.first_sample = first_sample;
     }
-    if (const int rc = launch_part(ctx, dp, pf)) return rc;
+    if (const int rc = launch_part(ctx, b, dp, pf)) return rc;
     if (async) { // fvad_vad_batch_part_wait goes on from here
         dp->flight = std::move(flight);
         b->part_in_flight = true;
@@ -869,6 +873,13 @@ int fvad_vad_batch_run_device_sized(fvad_ctx* ctx, fvad_vad_batch* b, const floa
     if (!b || !d_band || !n_frames || !n_chunks || !chunk_rms || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
     if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
     return run_device(ctx, b, d_band, band_stride, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size);
+}
+
+int fvad_vad_batch_chain_form(const fvad_vad_batch* b, int* form)
+{
+    if (!b || !form) return FVAD_ERR_INVALID_ARGUMENT;
+    *form = b->chain_form;
+    return FVAD_OK;
 }
 
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)

@@ -564,6 +564,7 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
     nb->keep_segments = b->keep_segments;
     nb->segs_kept = b->segs_kept;
     nb->next_sample = b->next_sample;
+    nb->chain_form = b->chain_form;
     return FVAD_OK;
 }
 

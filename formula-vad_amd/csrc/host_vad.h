@@ -116,6 +116,8 @@ struct fvad_vad_batch {
     // fvad_vad_batch_run_device_part_async has launched a part and fvad_vad_batch_part_wait has not finished it: until then every
     // call that runs, scores, retains, reads results of or sets something on the batch returns FVAD_ERR_INVALID_ARGUMENT
     bool part_in_flight = false;
+    // fvad_vad_batch_chain_form: 0 = no device launch yet, 1 = the last one ran the lane form of the machines' kernel, 2 = the cooperative form
+    int chain_form = 0;
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
     // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
     bool has_refs = false;

@@ -176,6 +176,7 @@ struct Tuning {
     bool reproducible = false;   // one kernel family (the large-batch one) at every batch size
     int vad_lane_map = 0;        // fvad_vad_batch_run_device: 0 = lanes of a wavefront are one stream's configs, 1 = one config's streams
     int vad_size_order = 0;      // several frame sizes, lanes by stream: 0 = a stream's configs size-major, 1 = in the caller's order
+    int vad_chain = 0;           // the exact long-term chains of the device VAD machines: 0 = each lane its own ("lane"), 1 = by the wavefront ("coop"); same bits
     int vad_seg_cap = 0;         // fvad_vad_batch_run_device: segments per machine the first launch has room for (more: a second launch); 0 = 512 MB in all
     int ws2_variant = 0;         // timing-only variants of gru_ws2_kernel (tools/ws2_variants.py); 0 in production
     unsigned ws2_waits = 0;      // gru_ws2k's first-poll waits for every launch (layer 1 | layer 2 << 16, 10 ns ticks); 0 = per class:

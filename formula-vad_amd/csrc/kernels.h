@@ -238,7 +238,8 @@ struct VadMachinesArgs {
     // segment room (seg_cap past its seg_base) is full before its last frame stops there and sets *paused: the next launch
     // with fresh = 0 goes on from that frame.  rebase: seg_base = the machine's segment count on entry (segments are written
     // at seg[count - seg_base]); else seg_base is kept.
-    int resume, fresh, rebase;
+    // coop = 1 (context option vad_chain "coop", any of the forms): the exact long-term chains by the whole wavefront, the same bits
+    int resume, fresh, rebase, coop;
     uint64_t first_frame;
     fvad::VadLaneState* state;  // [n_machines], machine = stream * n_configs + config
     unsigned* paused;

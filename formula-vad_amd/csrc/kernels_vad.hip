@@ -137,6 +137,35 @@ struct Machine : fvad::VadMachineState { // the step (decide, finish_step) and t
         lt_next = slot(lt_w); // (w + 1 == len == 1: the slot just written, read back after the store)
         if (lazy_update(qn, qo)) lt_exact();
     }
+
+    // lt_push for the cooperative form (vad_machines_coop_kernel): the same steps, but where lt_push runs lt_exact the wavefront
+    // runs the chain together.  The caller has run it before this call if the ring was steady and not anchored; true: the
+    // chain is due after this push (the ring became full, or lazy_update asked for a new anchor)
+    __device__ bool lt_push_flag(float mv)
+    {
+        const uint32_t len = cf.long_len;
+        if (!lt_steady) {
+            slot(lt_w) = mv;
+            lt_w = (lt_w + 1 == len) ? 0 : lt_w + 1;
+            lt_wc += 1;
+            lt_filled = lt_wc;
+            const double sc = 1.0 / (double)lt_wc;
+            double acc = 0.0;
+#pragma unroll 8
+            for (uint32_t i = 0; i < lt_wc; ++i) acc += (double)slot(i) * sc;
+            lt_last = acc;
+            has_last = true;
+            if (lt_wc == len) { lt_steady = true; lt_next = slot(0); return true; }
+            return false;
+        }
+        const uint32_t w = lt_w;
+        const double qn = (double)mv * cf.lt_scalar, qo = lt_q(w, lt_next);
+        slot(w) = mv;
+        if (lt_filled < len) lt_filled += 1;
+        lt_w = (w + 1 == len) ? 0 : w + 1;
+        lt_next = slot(lt_w);
+        return lazy_update(qn, qo);
+    }
 };
 
 // the step's state field by field (a copy of the whole struct takes it through the stack or LDS)
@@ -305,9 +334,268 @@ __global__ __launch_bounds__(64) void vad_machines_kernel(VadMachinesArgs a)
     a.stats[2 * id + 1] = mc.lazy_pushes;
 }
 
+// ------------------------------------------------------------------ the cooperative form (context option vad_chain "coop")
+// The same machines with the same bits, but an exact long-term chain is run by the whole wavefront: in the lane form one lane's
+// chain takes the other 63 lanes through its loop, each dragging its own ring along, and the chain waits for one memory round
+// trip per 64 slots.  Here a lane that would call lt_exact raises a flag; the wavefront ballots the flags and, owner by owner
+// in lane order, all 64 lanes load the owner's ring (lane j the float4 rows j, j + 64, ...), each lane turns its slots into
+// the chain's f64 terms and puts them into an LDS tile in slot order, and the two add chains (the sum and the sum of absolute
+// values) run over the tile in that order: the reference's additions, one after the other.  A tile is kCoopTile slots (four
+// loads of 64 rows); the next tile's loads are in flight and the LDS tiles alternate while the current one is added.
+//
+// A frame has two places for the chain: before the frame's push into the long-term ring (decide's exact(), or a steady ring
+// that was never anchored) and after it (the ring became full, or lazy_update asked for a new anchor); a machine takes at most
+// one of them in a frame.  Control flow around both is wavefront-uniform: lanes without a machine, lanes whose stream has ended
+// and lanes that paused for segment room stay in the frame loop as helpers.  RESUME is a run-time flag here (a.resume): the
+// one-shot launch is the resume form with fresh machines and no state to load or store.
+constexpr int kCoopTile = 1024;                                            // slots of an LDS tile: 256 float4 rows, 4 per lane
+constexpr size_t kCoopLdsBytes = 2 * (size_t)kCoopTile * sizeof(double);   // two tiles of f64 terms, ahead of the short rings
+typedef __attribute__((address_space(3))) double lds_double;
+
+namespace {
+
+__device__ __forceinline__ uint32_t lane_u32(uint32_t x, int o) { return (uint32_t)__builtin_amdgcn_readlane((int)x, o); }
+__device__ __forceinline__ double lane_f64(double x, int o)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    const uint64_t r = (uint64_t)lane_u32((uint32_t)u, o) | (uint64_t)lane_u32((uint32_t)(u >> 32), o) << 32;
+    return __longlong_as_double((long long)r);
+}
+
+// The chain of Machine::lt_exact over the ring of the machine at place m_o (long_len n, lt_filled filled), by all 64 lanes:
+// every lane returns the owner's acc and abs_sum.  `tiles` is the wavefront's 2 * kCoopTile doubles of LDS.
+__device__ __forceinline__ void coop_chain(const float* lt_rings, long n_machines, long m_o, uint32_t n, uint32_t filled, double scalar,
+                                           double q_init, lds_double* tiles, int lane, double* acc_out, double* abs_out)
+{
+    const float* base = lt_rings + 4 * m_o;
+    const long stride = 4 * n_machines;
+    const uint32_t rows = n ? (n + 3) / 4 : 1; // (a ring has at least one slot)
+    constexpr int kU = kCoopTile / 256; // float4 rows of a tile per lane
+    // (a row past the ring's last: that last row again, its terms are not added.  Nothing is read outside the ring, and no
+    // branch stands between the loads and the adds, which would make the adds wait for the next tile's loads too)
+    auto load_tile = [&](uint32_t t, float4 (&x)[kU]) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const uint32_t r = t * (kCoopTile / 4) + (uint32_t)u * 64 + (uint32_t)lane;
+            x[u] = *reinterpret_cast<const float4*>(base + (long)(r < rows ? r : rows - 1) * stride);
+        }
+    };
+    double acc = 0.0, abs_sum = 0.0;
+    float4 cur[kU], nxt[kU];
+    load_tile(0, cur);
+    const uint32_t n_tiles = (rows + kCoopTile / 4 - 1) / (kCoopTile / 4);
+    for (uint32_t t = 0; t < n_tiles; ++t) {
+        load_tile(t + 1, nxt); // (in flight while this tile is added)
+        lds_double* q = tiles + (t & 1) * kCoopTile;
+        // this lane's 4 kU slots as the chain's terms, at their places in slot order
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const uint32_t lr = (uint32_t)u * 64 + (uint32_t)lane; // row within the tile
+            const uint32_t i = t * kCoopTile + 4 * lr;
+            const float xs[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) q[4 * lr + e] = i + e < filled ? (double)xs[e] * scalar : q_init;
+        }
+        __syncthreads(); // (one wavefront: the tile's writes before its reads)
+        const uint32_t cnt = n - t * kCoopTile < (uint32_t)kCoopTile ? n - t * kCoopTile : (uint32_t)kCoopTile;
+        // the adds in slot order, 32 terms read at a time (every lane reads the same address: a broadcast)
+        const uint32_t full = cnt & ~31u;
+        for (uint32_t i = 0; i < full; i += 32) {
+            double c[32];
+#pragma unroll
+            for (int j = 0; j < 32; ++j) c[j] = q[i + j];
+#pragma unroll
+            for (int j = 0; j < 32; ++j) { acc += c[j]; abs_sum += fabs(c[j]); }
+        }
+        for (uint32_t i = full; i < cnt; ++i) { const double d = q[i]; acc += d; abs_sum += fabs(d); }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) cur[u] = nxt[u];
+    }
+    __syncthreads(); // (the next chain's first tile is written after this chain's last reads)
+    *acc_out = acc;
+    *abs_out = abs_sum;
+}
+
+} // namespace
+
+template <bool RINGS_LDS, bool SIZED>
+__global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a)
+{
+    extern __shared__ double vad_coop_lds[]; // [2][kCoopTile] chain terms, then the short rings [st_max + cr_max][64] (RINGS_LDS)
+    using P = typename std::conditional<RINGS_LDS, lds_float*, float*>::type;
+    lds_double* tiles = (lds_double*)vad_coop_lds;
+    const int lane = threadIdx.x;
+    const long m_raw = (long)blockIdx.x * 64 + lane;
+    const bool valid = m_raw < a.n_machines;
+    const long m = valid ? m_raw : a.n_machines - 1; // (a lane without a machine: addresses of the last one, nothing run or stored)
+    const bool RESUME = a.resume != 0;
+    long s;
+    int c;
+    if (a.by_config) { c = (int)(m / a.n_streams); s = m - (long)c * a.n_streams; }
+    else {
+        s = m / a.n_configs;
+        c = (int)(m - s * a.n_configs);
+        if constexpr (SIZED) { if (a.lane_config) c = a.lane_config[c]; }
+    }
+    const long id = s * a.n_configs + c;
+    const VadMachineCfg* cfg = a.cfgs + c;
+
+    Machine<P> mc;
+    mc.cf = *cfg;
+    mc.lt = a.lt_rings + 4 * m;
+    mc.lt_stride = 4 * a.n_machines;
+    P rb;
+    long rs;
+    if constexpr (RINGS_LDS) { rb = (lds_float*)(vad_coop_lds + 2 * kCoopTile) + lane; rs = 64; }
+    else { rb = a.rings + m; rs = a.n_machines; }
+    mc.st = Ring<P>{rb, rs, cfg->short_len, 0, 0, cfg->st_scalar, 0.0};
+    mc.cr = Ring<P>{rb + (long)a.st_max * rs, rs, cfg->ratio_len, 0, 0, cfg->cr_scalar, 0.0};
+    uint64_t F = a.fft_size, first_frame = a.first_frame;
+    long row = s;
+    if constexpr (SIZED) {
+        const uint32_t g = a.size_of[c];
+        F = a.sizes[g];
+        first_frame = a.first_sample / F;
+        row = (long)g * a.n_streams + s;
+    }
+    uint32_t n_segs = 0, seg_base = 0;
+    long k0 = 0;
+    if (valid && RESUME && !a.fresh) {
+        const fvad::VadLaneState& ls = a.state[id];
+        copy_state(mc, ls.m);
+        mc.st.w = ls.st_w; mc.st.wc = ls.st_wc; mc.st.pref = ls.st_pref;
+        mc.cr.w = ls.cr_w; mc.cr.wc = ls.cr_wc; mc.cr.pref = ls.cr_pref;
+        mc.lt_w = ls.lt_w; mc.lt_wc = ls.lt_wc; mc.lt_filled = ls.lt_filled; mc.lt_steady = ls.lt_steady != 0;
+        mc.lt_next = mc.slot(mc.lt_w);
+        n_segs = ls.n_segs;
+        seg_base = a.rebase ? n_segs : ls.seg_base;
+        k0 = ls.next_frame > first_frame ? (long)(ls.next_frame - first_frame) : 0;
+        if constexpr (RINGS_LDS) {
+            for (uint32_t i = 0; i < cfg->short_len; ++i) rb[(long)i * 64] = a.rings[(long)i * a.n_machines + m];
+            for (uint32_t i = 0; i < cfg->ratio_len; ++i)
+                rb[(long)(a.st_max + i) * 64] = a.rings[(long)(a.st_max + i) * a.n_machines + m];
+        }
+    } else if (valid && cfg->has_init) {
+        double acc = 0.0;
+        for (uint32_t i = 0; i < cfg->long_len; ++i) acc += cfg->lt_q_init;
+        mc.lt_last = acc;
+        mc.has_last = true;
+        mc.lt_steady = true;
+        mc.lt_wc = cfg->long_len;
+        mc.lt_next = mc.slot(0);
+    }
+
+    const long nf = valid ? a.n_frames[row] : 0;
+    const int C = a.n_channels;
+    const float* band = a.band + ((long)cfg->band * a.n_lanes + s * C) * a.band_stride;
+    const float* ratio = a.ratio + row * a.ratio_stride;
+    fvad_speech_segment* seg = a.segs + id * (long)a.seg_cap;
+    constexpr int kPre = 4;
+    float nv[kPre], nr = 0.0f;
+    auto fetch = [&](long k) {
+#pragma unroll
+        for (int ch = 0; ch < kPre; ++ch) nv[ch] = ch < C ? band[(long)ch * a.band_stride + k] : 999.0f;
+        nr = ratio[k];
+    };
+    auto min_vol = [&](long k) {
+        float mn = 999;
+#pragma unroll
+        for (int ch = 0; ch < kPre; ++ch) if (ch < C && nv[ch] < mn) mn = nv[ch];
+        for (int ch = kPre; ch < C; ++ch) {
+            const float v = band[(long)ch * a.band_stride + k];
+            if (v < mn) mn = v;
+        }
+        return mn;
+    };
+    // the flagged lanes' chains, owner by owner in lane order; each owner anchors on its own
+    auto run_chains = [&](bool flag) {
+        unsigned long long owners = __ballot(flag);
+        if (owners == 0) return;
+        // the lanes' ring stores of this and earlier frames before the other lanes' loads of those slots
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        while (owners) {
+            const int o = __builtin_ctzll(owners);
+            owners &= owners - 1;
+            double acc, abs_sum;
+            coop_chain(a.lt_rings, a.n_machines, (long)blockIdx.x * 64 + o, lane_u32(mc.cf.long_len, o), lane_u32(mc.lt_filled, o),
+                       lane_f64(mc.cf.lt_scalar, o), lane_f64(mc.cf.lt_q_init, o), tiles, lane, &acc, &abs_sum);
+            if (lane == o) mc.anchor(acc, abs_sum);
+        }
+    };
+    long k_end = nf, k = k0;
+    bool running = k < nf; // this lane still has frames to run (else it only helps)
+    if (running) fetch(k);
+    while (__ballot(running) != 0) { // (at least one running lane moves a frame on in every pass: bounded by the frame counts)
+        if (running && RESUME && n_segs - seg_base >= a.seg_cap) { k_end = k; *a.paused = 1; running = false; }
+        float mv = 0.0f, rt = 0.0f;
+        double st = 0.0, cr = 0.0;
+        bool met = false, before = false, redo = false;
+        if (running) {
+            mv = min_vol(k);
+            rt = nr;
+            if (k + 1 < nf) fetch(k + 1);
+            st = mc.st.push(mv);
+            cr = mc.cr.push(rt);
+            // decide up to its exact(): if it asks for the chain, what it did to the audit with the stale average is undone
+            // and it runs again after the chain (then with a current average: the path below its exact())
+            const fvad_vad_audit au = mc.audit;
+            met = mc.decide(mc.cf, st, cr, [&] { redo = true; });
+            if (redo) mc.audit = au;
+            before = redo || (!met && mc.lt_steady && !mc.lt_anchored);
+        }
+        run_chains(before);
+        bool after = false;
+        if (running) {
+            if (redo) met = mc.decide(mc.cf, st, cr, [] {});
+            if (!met) after = mc.lt_push_flag(mv);
+        }
+        run_chains(after);
+        if (running) {
+            const uint64_t frame = first_frame + (uint64_t)k; // (one-shot: first_frame is 0)
+            const uint64_t sample = SIZED ? a.first_sample + (uint64_t)k * F : frame * F;
+            mc.finish_step(mc.cf, sample, met, true, rt, [&](const fvad_speech_segment& sg) {
+                if (n_segs - seg_base < a.seg_cap) seg[n_segs - seg_base] = sg;
+                ++n_segs;
+            });
+            ++k;
+            running = k < nf;
+        }
+    }
+    if (!valid) return;
+    if (RESUME) {
+        fvad::VadLaneState& ls = a.state[id];
+        copy_state(ls.m, mc);
+        ls.st_w = mc.st.w; ls.st_wc = mc.st.wc; ls.st_pref = mc.st.pref;
+        ls.cr_w = mc.cr.w; ls.cr_wc = mc.cr.wc; ls.cr_pref = mc.cr.pref;
+        ls.lt_w = mc.lt_w; ls.lt_wc = mc.lt_wc; ls.lt_filled = mc.lt_filled; ls.lt_steady = mc.lt_steady ? 1u : 0u;
+        ls.n_segs = n_segs;
+        ls.seg_base = seg_base;
+        ls.next_frame = first_frame + (uint64_t)k_end;
+        if constexpr (RINGS_LDS) {
+            for (uint32_t i = 0; i < cfg->short_len; ++i) a.rings[(long)i * a.n_machines + m] = rb[(long)i * 64];
+            for (uint32_t i = 0; i < cfg->ratio_len; ++i)
+                a.rings[(long)(a.st_max + i) * a.n_machines + m] = rb[(long)(a.st_max + i) * 64];
+        }
+    }
+    a.seg_count[id] = n_segs;
+    a.audits[id] = mc.audit;
+    a.stats[2 * id] = mc.exact_evals;
+    a.stats[2 * id + 1] = mc.lazy_pushes;
+}
+
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream)
 {
     if (a.n_machines <= 0) return (int)hipSuccess;
+    if (a.coop) { // the cooperative form: two chain tiles ahead of the short rings (at most 16 + 48 KB)
+        const size_t lds = kCoopLdsBytes + (a.rings_in_lds ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0);
+        const dim3 grid((unsigned)((a.n_machines + 63) / 64));
+        if (a.sized) {
+            if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_coop_kernel<true, true>), grid, dim3(64), lds, stream, a);
+            else hipLaunchKernelGGL((vad_machines_coop_kernel<false, true>), grid, dim3(64), lds, stream, a);
+        } else if (a.rings_in_lds) hipLaunchKernelGGL((vad_machines_coop_kernel<true, false>), grid, dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((vad_machines_coop_kernel<false, false>), grid, dim3(64), lds, stream, a);
+        return (int)hipGetLastError();
+    }
     const size_t lds = a.rings_in_lds ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0;
     const dim3 grid((unsigned)((a.n_machines + 63) / 64));
     if (a.sized) {

@@ -350,6 +350,39 @@ def _agg_row(agg):
 # configs from which the VAD machines run on the GPU when run_sweep is left to choose: the measured crossover against 16 host threads
 # (tools/vad_sweep_time.py, 21 two-hour streams: the GPU machines are slower below 256 configs, about even at 256)
 SWEEP_DEVICE_MIN_CONFIGS = 256
+# the same threshold with vad_chain="coop" (the machines' exact long-term chains run by the whole wavefront)
+SWEEP_DEVICE_MIN_CONFIGS_COOP = 192
+VAD_CHAINS = ("lane", "coop")
+
+
+def _check_vad_chain(vad_chain):
+    if vad_chain is not None and vad_chain not in VAD_CHAINS:
+        raise ValueError(f"vad_chain: {vad_chain!r} (one of {VAD_CHAINS})")
+
+
+def _auto_vad_on(n_configs, vad_chain):
+    return "device" if n_configs >= (SWEEP_DEVICE_MIN_CONFIGS_COOP if vad_chain == "coop" else SWEEP_DEVICE_MIN_CONFIGS) else "host"
+
+
+class _VadChain:
+    """The context option vad_chain on the contexts of one run_sweep / run_grid call: set on entry (nothing when vad_chain is
+    None), and on a caller's context (owned False) put back on exit to what it was set to before"""
+
+    def __init__(self, vad_chain):
+        self.vad_chain, self.restore = vad_chain, []
+
+    def apply(self, ctx, owned):
+        if self.vad_chain is None or ctx is None:
+            return
+        prev = ctx.option_set("vad_chain")
+        ctx.set_option("vad_chain", self.vad_chain)
+        if not owned:
+            self.restore.append((ctx, prev))
+
+    def close(self):
+        for ctx, prev in self.restore:
+            ctx.set_option("vad_chain", prev)
+        self.restore = []
 
 
 def _engine_opts(config0, F):
@@ -474,7 +507,8 @@ def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_ch
             one.close()
 
 
-def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16):
+def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16,
+              vad_chain=None):
     """Scores many VADMachine configurations over one denoising pass of a plan's instances.
 
     configs: list of VADMachine.Config override dicts (vad_overrides' form); default: the plan's vad_machine_config followed by its
@@ -484,7 +518,10 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     the VAD machines -> per (instance, config) the Evaluator statistics against the labels, aggregated in plan order like
     run_plan's report (statistics.zig:116-172).  vad_on: "device" (fvad_vad_batch_run_device, every (instance, config) machine on
     the GPU), "host" (fvad_vad_batch_run on n_threads host threads over the band sums, one call per instance) or "auto" (the GPU
-    from SWEEP_DEVICE_MIN_CONFIGS configs on); both give the same bits.
+    from SWEEP_DEVICE_MIN_CONFIGS configs on); both give the same bits.  vad_chain "lane" or "coop": the context option of that
+    name for this call (how the device machines run their exact long-term chains; same bits; "auto" then takes
+    SWEEP_DEVICE_MIN_CONFIGS_COOP for "coop"), set on the context the call makes, or on the caller's and put back afterwards;
+    None leaves the context as it is; anything else is a ValueError before any device is touched.
 
     Returns dict(configs, rows [one aggregate dict per config], aggregates [AggregateStats], segments [config][instance],
     stats [config][instance]); prints one table row per config and writes the rows as JSON to json_path if given."""
@@ -492,14 +529,16 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     if configs is None:
         configs = [plan["vad_machine_config"]] + list(plan["alt_vad_machine_configs"])
     configs = [dict(c) for c in configs]
+    _check_vad_chain(vad_chain)
     if vad_on == "auto":
-        vad_on = "device" if len(configs) >= SWEEP_DEVICE_MIN_CONFIGS else "host"
+        vad_on = _auto_vad_on(len(configs), vad_chain)
     if vad_on not in ("device", "host"):
         raise ValueError(f"vad_on: {vad_on!r}")
     F = plan["fft_size"]
     own_ctx = ctx is None
     if own_ctx:
         ctx = _make_ctx(plan, 0, synth_seed)
+    chain = _VadChain(vad_chain)
     loaded = [_read_instance(i) for i in plan["instances"]]
     audio = [a for a, _ in loaded]
     refs = [r for _, r in loaded]
@@ -523,6 +562,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
 
     times = {"machines": 0.0, "scoring": 0.0}
     try:
+        chain.apply(ctx, own_ctx)
         groups, n_chunks, n_den, _, d_den, rms = _denoise_for_sweep(ctx, audio, F, configs[0], dalloc)
         l0 = 0
         for nch, members in groups.items():
@@ -539,6 +579,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     finally:
         for a in allocs:
             ctx.device_free(a)
+        chain.close()
         if own_ctx:
             ctx.close()
     elapsed = time.perf_counter() - t0
@@ -703,7 +744,7 @@ def _check_grid_contexts(ctx, devices):
 
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False):
+             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False, vad_chain=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -769,7 +810,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     again, at a rung and at the end.  Plain, sized and halving grids, and every share of a ctx / devices list on its own context.
     On reproducible contexts the statistics, survivors, rungs and evaluated_seconds are those of overlap=False bit for bit.
     times gains machines_wait (the host time inside the waits, counted in machines too); device_bytes counts the second set
-    of the bands and rms buffers."""
+    of the bands and rms buffers.
+    vad_chain as in run_sweep: set on every context the call makes, and on the caller's contexts for the call."""
+    _check_vad_chain(vad_chain)
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
@@ -777,7 +820,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     sizes_of, configs = expand_grid_sized(grid, None)
     sized = "fft_size" in grid   # (a grid without the key runs every config at the plan's fft_size: expand_grid's configs)
     if vad_on == "auto":
-        vad_on = "device" if len(configs) >= SWEEP_DEVICE_MIN_CONFIGS else "host"
+        vad_on = _auto_vad_on(len(configs), vad_chain)
     if vad_on not in ("device", "host"):
         raise ValueError(f"vad_on: {vad_on!r}")
     if score_on == "auto":
@@ -850,6 +893,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     stop = threading.Event()   # set when a worker fails: the others stop at their next slice or rung
     errs, breaks = [], []
     t_all = time.perf_counter()
+    chain = _VadChain(vad_chain)
 
     def work(s):
         t0 = time.perf_counter()
@@ -870,6 +914,8 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
             share_times[s]["wall"] = time.perf_counter() - t0
 
     try:
+        for c, own in zip(ctxs, owned):
+            chain.apply(c, own)
         if len(workers) == 1:
             work(workers[0])
         else:
@@ -879,6 +925,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
             for t in th:
                 t.join()
     finally:
+        chain.close()
         for c, own in zip(ctxs, owned):
             if own and c is not None:
                 c.close()
@@ -1447,7 +1494,7 @@ def frame_ratios(chunk_rms, n_frames, fft_size=1024, chunk=24000):
     return out
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description="Formula-VAD simulator harness on MI355X")
     ap.add_argument("-i", "--input", required=True, help="Simulation plan (path to JSON)")  # simulator.zig:78-82
     ap.add_argument("--synth-seed", type=int, default=None, help="use random-init NSNet2 weights")
@@ -1473,18 +1520,25 @@ def main(argv=None):
                          "rung (the machines and scoring on the GPU)")
     ap.add_argument("--halving-rungs", type=int, default=None,
                     help="with --halving-eta: the number of rungs R (rung k ends at ETA^(k-1-R) of the corpus)")
+    ap.add_argument("--vad-chain", default=None, choices=VAD_CHAINS,
+                    help="with --sweep / --sweep-grid: how the device VAD machines run their exact long-term chains (context option "
+                         "vad_chain): lane by lane (the default) or by the whole wavefront; same results")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
-                 overlap=a.overlap)
+                 overlap=a.overlap, vad_chain=a.vad_chain)
         return
     if a.sweep:
-        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad)
+        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain)
         return
     run_plan(a.input, synth_seed=a.synth_seed, devices=devices or [0])
 

@@ -330,7 +330,9 @@ const char *fvad_ctx_last_nn_path(const fvad_ctx *ctx);
  * fvad_engine_run's host-buffer pipeline in sixteenths of the call, at most seven, instead of the planned ones) | "trace_run" (a timeline of every fvad_engine_run call on stderr) | "trace_kernels" |
  * "ws_spin_ticks" | "ws2_variant" (diagnostic bit mask; the timing-only bits exist in the diagnostics build alone) |
  * "ws2_waits" | "ws2_calibrate" (below) | "k4_plain_loads" (the band FFT's staging path of unaligned frames) | "gru_lat_tiles" ("1" | "2" | "3": row tiles per
- * workgroup of the low-latency recurrence instead of the cost model's choice; same bits); value NULL or ""
+ * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_chain" ("lane" | "coop": the exact
+ * long-term chains of the device VAD machines lane by lane or by the whole wavefront, see fvad_vad_batch_run_device_part; same bits);
+ * value NULL or ""
  * restores the default.  The environment variables FVAD_<NAME> are read ONCE, by
  * fvad_ctx_create, as initial values (a bad value fails the creation); the data path never reads the environment. */
 int fvad_ctx_set_option(fvad_ctx *ctx, const char *name, const char *value);
@@ -487,12 +489,23 @@ int fvad_vad_batch_run_device(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_b
  * fvad_vad_batch_config_stats), bit-identical to fvad_vad_batch_score on the same segments; FVAD_ERR_INVALID_ARGUMENT without
  * references, without device part state, or when a part kept its segments on the host (score those with fvad_vad_batch_score).
  * fvad_vad_batch_device_bytes: the device memory b holds between parts (0 without part state).
- * A batch holding part state owns device memory of its context: destroy the batch before the context. */
+ * A batch holding part state owns device memory of its context: destroy the batch before the context.
+ * Context option vad_chain ("lane", the default, or "coop"; FVAD_VAD_CHAIN): how the machines' kernel runs an exact long-term
+ * chain (csrc/kernels_vad.hip).  "lane": each lane runs its own machine's chain, the other lanes of its wavefront idling through
+ * it.  "coop": the 64 lanes of the wavefront load the ring of the machine that needs the chain together and the additions run
+ * over it in the reference's order.  Every result (segments, audits, lazy statistics, scores, the state between parts) has the
+ * same bits with either, so the option is read at every launch of _run_device(_sized), _run_device_part(_sized), _part_async
+ * and of a part's relaunch after its segment room grew, and may change between the parts of a run.
+ * fvad_vad_batch_chain_form: *form = 0 before the batch's first device launch, 1 when its last device launch ran the lane form,
+ * 2 when it ran the cooperative form (a launch is counted when it is queued: after _part_async already).  The engine never
+ * refuses "coop": its LDS (two chain tiles of 8 KB on top of the short rings' at most 48 KB) fits every batch, so 1 is only
+ * ever reported with vad_chain "lane". */
 int fvad_vad_batch_run_device_part(fvad_ctx *ctx, fvad_vad_batch *b, const float *d_band, size_t band_stride,
                                    const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
                                    const size_t *n_chunks, size_t chunk_size, uint64_t first_frame);
 int fvad_vad_batch_score_device(fvad_ctx *ctx, fvad_vad_batch *b);
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch *b);
+int fvad_vad_batch_chain_form(const fvad_vad_batch *b, int *form);
 /* Keep configs keep[0] < keep[1] < ... < keep[n_keep - 1] of b and drop the rest, between runs or between the parts of a run
  * (successive halving: drop the configs that lose on a prefix, run the survivors on).  Afterwards b is in every observable way
  * the batch fvad_vad_batch_create_sweep (or _create_sweep_sized) would make from cfgs[keep[0..n_keep)] (and their sizes) after

@@ -7,7 +7,13 @@ with speech-like bursts, generated on the device), N configs that vary threshold
     part (frame ratios, uploads, read-back) separately;
   * fvad_vad_batch_run with T host threads over the same band sums;
   * device against host, bit for bit (segments and audits of every machine).
-python tools/vad_sweep_time.py [--streams 21] [--hours 2] [--configs 1,8,64,256] [--threads 16]"""
+--vad-chain lane | coop sets the context option of that name for the device runs (how the machines run their exact long-term
+chains).  --vad-chain both is the A/B mode for the two forms: per N one warm-up launch, then --reps rounds that alternate
+lane and coop in one process, the machines' kernel time by device events, median [min - max] per form; the K4 comparison and the
+config lane map are left out, the segment room is given from the start (vad_seg_cap) so that every N is one launch, and both
+forms are checked against the host bit for bit.  --vad-chain lane-ab is the same protocol for the lane form alone (for a build
+without the option: the parent's side of an A/B).
+python tools/vad_sweep_time.py [--streams 21] [--hours 2] [--configs 1,8,64,256] [--threads 16] [--vad-chain both --reps 3]"""
 import argparse
 import os
 import sys
@@ -65,6 +71,58 @@ def device_corpus(S, hours, seed, chunk=24000, F=1024):
     return audio, rms, n_chunks
 
 
+def ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf):
+    """--vad-chain both / lane-ab: the machines' kernel per form, alternated in one process (module docstring)"""
+    forms = ["lane", "coop"] if a.vad_chain == "both" else ["lane"]
+    dev = audio.device
+    for N in [int(x) for x in a.configs.split(",")]:
+        cfgs = make_configs(N, a.seed + N)
+        sw = fv.VadSweep(S, cfgs)
+        bins, _ = sw.bands()
+        band = torch.empty((len(bins), S, nf), dtype=torch.float32, device=dev)
+        ctx.band_sums_device(audio.data_ptr(), S, L, L, bins, band.data_ptr(), nf)
+        torch.cuda.synchronize()
+        ctx.set_option("vad_seg_cap", str(min(nf // 4 + 1, a.seg_cap)))   # room from the start: one launch whatever N
+        ms = {f: [] for f in forms}
+        kept = {}
+        try:
+            for rep in range(-1, a.reps):   # (-1: the warm-up, not kept)
+                for f in forms:
+                    if a.vad_chain == "both":
+                        ctx.set_option("vad_chain", f)
+                    ctx.kernel_times()
+                    sw.run_device(ctx, band.data_ptr(), nf, [nf] * S, rms, [n_chunks] * S)
+                    t = ctx.kernel_times().get("vad_machines", float("nan"))
+                    if rep >= 0:
+                        ms[f].append(t)
+                    if rep == 0 and not a.no_host:
+                        kept[f] = ([sw.segments(c) for c in range(N)], [sw.audit(s, c) for s in range(S) for c in range(N)],
+                                   [sw.lazy_stats(s, c) for s in range(S) for c in range(N)])
+        finally:
+            ctx.set_option("vad_seg_cap", None)
+            if a.vad_chain == "both":
+                ctx.set_option("vad_chain", None)
+        host_txt = "host not run"
+        if not a.no_host:
+            hb = band.cpu().numpy()
+            hs = fv.VadSweep(S, cfgs)
+            t0 = time.perf_counter()
+            hs.run(hb, rms, n_threads=a.threads)
+            host = time.perf_counter() - t0
+            want = ([hs.segments(c) for c in range(N)], [hs.audit(s, c) for s in range(S) for c in range(N)],
+                    [hs.lazy_stats(s, c) for s in range(S) for c in range(N)])
+            same = all(kept[f] == want for f in forms)
+            chains = sum(x[0] for x in want[2])
+            host_txt = (f"host {a.threads} threads {host * 1e3:9.1f} ms | {chains} exact chains ({chains * 64.0 / (S * N):.0f} per full "
+                        f"wavefront) | bit-identical to the host: {same}")
+            hs.close()
+            del hb
+        txt = " | ".join(f"{f} {np.median(ms[f]):8.2f} ms [{min(ms[f]):8.2f} - {max(ms[f]):8.2f}]" for f in forms)
+        print(f"N={N:4d} ({(S * N + 63) // 64} wavefronts): GPU VAD kernel {txt} | {host_txt}", flush=True)
+        sw.close()
+        del band
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=21)
@@ -72,6 +130,10 @@ def main():
     ap.add_argument("--configs", default="1,8,64,256")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=4)
+    ap.add_argument("--vad-chain", default=None, choices=("lane", "coop", "both", "lane-ab"))
+    ap.add_argument("--reps", type=int, default=3, help="with --vad-chain both / lane-ab: timed rounds per form")
+    ap.add_argument("--seg-cap", type=int, default=2048, help="with --vad-chain both / lane-ab: segment room per machine")
+    ap.add_argument("--no-host", action="store_true", help="with --vad-chain both / lane-ab: skip the host run (and the bit check)")
     a = ap.parse_args()
     import torch
     pkg = load_package()
@@ -86,6 +148,12 @@ def main():
     d_den = audio.data_ptr()
     print(f"{S} streams x {a.hours:g} h ({nf} frames each), mono, fft 1024", flush=True)
     ctx.enable_timing(True)
+    if a.vad_chain in ("both", "lane-ab"):
+        ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf)
+        ctx.close()
+        return
+    if a.vad_chain:
+        ctx.set_option("vad_chain", a.vad_chain)
     for N in [int(x) for x in a.configs.split(",")]:
         cfgs = make_configs(N, a.seed + N)
         sw = fv.VadSweep(S, cfgs)
