@@ -335,6 +335,15 @@ pub extern "c" fn fvad_vad_batch_run_device_part_async(ctx: *Ctx, b: *VadBatch, 
 pub extern "c" fn fvad_vad_batch_part_wait(ctx: *Ctx, b: *VadBatch) c_int;
 pub extern "c" fn fvad_vad_batch_frame_ratios_device(ctx: *Ctx, b: *const VadBatch, d_chunk_rms: ?[*]const f32, rms_stride: usize, n_frames: [*]const usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, d_ratio: ?[*]f32, ratio_stride: usize) c_int;
 pub extern "c" fn fvad_vad_batch_frame_ratios(b: *const VadBatch, chunk_rms: ?[*]const f32, rms_stride: usize, n_frames: [*]const usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, ratio: ?[*]f32, ratio_stride: usize) c_int;
+/// the short-term and channel-ratio averages from tables (context option vad_avgs, see fvad.h): 0 = no device launch yet, 1 = the
+/// batch's last device launch pushed the short rings, 2 = it read the tables; the bytes of that launch's tables
+pub extern "c" fn fvad_vad_batch_avgs_form(b: *const VadBatch, form: *c_int) c_int;
+pub extern "c" fn fvad_vad_batch_avgs_bytes(b: *const VadBatch) usize;
+/// the tables' keys as pairs (band, ring length) / (size index, ring length) in first-seen config order, and each config's keys
+pub extern "c" fn fvad_vad_batch_avg_keys(b: *const VadBatch, st_keys: ?[*]u32, cr_keys: ?[*]u32, cap: usize, n_st_keys: *usize, n_cr_keys: *usize, st_key: ?[*]u32, cr_key: ?[*]u32) c_int;
+/// a test tap: only the two table kernels of a part; [key][stream][row_stride] f64 each
+pub extern "c" fn fvad_vad_batch_averages_device(ctx: *Ctx, b: *const VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, st_avg: ?[*]f64, cr_avg: ?[*]f64, row_stride: usize) c_int;
+pub extern "c" fn fvad_vad_avg_chain(x: ?[*]const f32, n_frames: usize, first_frame: usize, len: u32, ring: ?[*]const f32, out: ?[*]f64) c_int;
 pub extern "c" fn fvad_ra_create(count: usize, has_initial: c_int, initial_val: f64, out: *?*RollingAverage) c_int;
 pub extern "c" fn fvad_ra_destroy(ra: ?*RollingAverage) void;
 pub extern "c" fn fvad_ra_push(ra: *RollingAverage, sample: f32) f64;

@@ -250,6 +250,13 @@ SIGNATURES = {
     "fvad_vad_batch_part_wait": (C.c_int, [vp, vp]),
     "fvad_vad_batch_frame_ratios_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), sz, C.c_uint64, vp, sz]),
     "fvad_vad_batch_frame_ratios": (C.c_int, [vp, c_float_p, sz, C.POINTER(sz), C.POINTER(sz), sz, C.c_uint64, c_float_p, sz]),
+    "fvad_vad_batch_avgs_form": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "fvad_vad_batch_avgs_bytes": (sz, [vp]),
+    "fvad_vad_batch_avg_keys": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, C.POINTER(sz), C.POINTER(sz),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fvad_vad_batch_averages_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), sz]),
+    "fvad_vad_avg_chain": (C.c_int, [c_float_p, sz, sz, C.c_uint32, c_float_p, C.POINTER(C.c_double)]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
     "fvad_ra_push": (C.c_double, [vp, C.c_float]),
@@ -1081,6 +1088,47 @@ class VadSweep:
             raise FvadError(rc, "fvad_vad_batch_chain_form")
         return f.value
 
+    def avgs_form(self):
+        """fvad_vad_batch_avgs_form: 0 before the first device launch, 1 when the last device launch pushed the short-term and
+        channel-ratio rings, 2 when it read them from the tables (context option vad_avgs)"""
+        f = C.c_int(0)
+        rc = lib().fvad_vad_batch_avgs_form(self.h, C.byref(f))
+        if rc:
+            raise FvadError(rc, "fvad_vad_batch_avgs_form")
+        return f.value
+
+    def avgs_bytes(self):
+        """fvad_vad_batch_avgs_bytes: the tables and min_volume rows of the last device launch's part (0 with the rings)"""
+        return lib().fvad_vad_batch_avgs_bytes(self.h)
+
+    def avg_keys(self):
+        """fvad_vad_batch_avg_keys -> (short keys [(band, ring length)], ratio keys [(size index, ring length)], st_key [config],
+        cr_key [config]), the keys in first-seen config order"""
+        n_st, n_cr = sz(), sz()
+        cap = self.n_configs
+        st, cr = (C.c_uint32 * (2 * cap))(), (C.c_uint32 * (2 * cap))()
+        st_key, cr_key = (C.c_uint32 * cap)(), (C.c_uint32 * cap)()
+        check(lib().fvad_vad_batch_avg_keys(self.h, st, cr, cap, C.byref(n_st), C.byref(n_cr), st_key, cr_key), "fvad_vad_batch_avg_keys")
+        return ([(st[2 * j], st[2 * j + 1]) for j in range(n_st.value)], [(cr[2 * j], cr[2 * j + 1]) for j in range(n_cr.value)],
+                list(st_key), list(cr_key))
+
+    def averages_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_sample=0, chunk_size=24000):
+        """fvad_vad_batch_averages_device (a test tap): only the averages' table kernels for the frames a part call with these
+        arguments would run (n_frames [stream] with one size, else [size][stream]; chunk_rms on the host) -> dict(st float64
+        [short key][stream][max frames], cr [ratio key][stream][max frames] -- entries past a stream's frames are NaN --, and
+        avg_keys()' st_keys, cr_keys, st_key, cr_key).  first_sample > 0 reads the earlier frames from the batch's part state."""
+        assert chunk_rms.dtype == np.float32 and chunk_rms.flags["C_CONTIGUOUS"] and chunk_rms.shape[0] == self.n_streams * self.n_channels
+        nf, nc = self._sized_counts(n_frames, n_chunks)
+        st_keys, cr_keys, st_key, cr_key = self.avg_keys()
+        stride = max(1, max(nf))
+        st = np.full((len(st_keys), self.n_streams, stride), np.nan, np.float64)
+        cr = np.full((len(cr_keys), self.n_streams, stride), np.nan, np.float64)
+        dp = C.POINTER(C.c_double)
+        ctx._ck(lib().fvad_vad_batch_averages_device(ctx.h, self.h, vp(d_band) if d_band else None, band_stride, nf, fptr(chunk_rms),
+                                                     chunk_rms.shape[1], nc, chunk_size, int(first_sample), st.ctypes.data_as(dp),
+                                                     cr.ctypes.data_as(dp), stride), "fvad_vad_batch_averages_device")
+        return {"st": st, "cr": cr, "st_keys": st_keys, "cr_keys": cr_keys, "st_key": st_key, "cr_key": cr_key}
+
     def retain(self, ctx, keep):
         """fvad_vad_batch_retain_configs: keep configs keep (strictly increasing indices) and drop the rest, between runs or
         device parts; new config c is old config keep[c].  ctx: the parts' Context when the batch holds device part state,
@@ -1182,6 +1230,17 @@ class VadSweepSized(VadSweep):
     run = VadSweep.run_sized
     run_device = VadSweep.run_device_sized
     run_device_part = VadSweep.run_device_part_sized
+
+
+def avg_chain(x, length, first_frame=0, ring=None):
+    """fvad_vad_avg_chain: the average of a rolling average of `length` slots (no initial value) after each of the frames
+    first_frame + k, x[k] their inputs (float32) -> float64 [len(x)]; ring: the slots as they were before frame first_frame"""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros(len(x), np.float64)
+    r = None if ring is None else np.ascontiguousarray(ring, np.float32)
+    check(lib().fvad_vad_avg_chain(fptr(x), len(x), int(first_frame), int(length), None if r is None else fptr(r),
+                                   out.ctypes.data_as(C.POINTER(C.c_double))), "fvad_vad_avg_chain")
+    return out
 
 
 def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_threads=1):

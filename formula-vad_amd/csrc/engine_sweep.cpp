@@ -85,12 +85,30 @@ struct DevParts {
     std::vector<uint32_t> count_h;       // every machine's segment count after the last part
     bool segs_on_device = true;          // every part so far left its segments on the device: they are all in segs
     std::unique_ptr<PartFlight> flight;  // a part launched and not yet waited for (fvad_vad_batch_run_device_part_async)
+    // the averages' tables of a part (context option vad_avgs "table"): the min_volume rows and the two tables; they only grow
+    float* mv = nullptr;
+    double *st_tab = nullptr, *cr_tab = nullptr;
+    size_t mv_cap = 0, st_cap = 0, cr_cap = 0; // in elements
+    size_t table_bytes() const { return mv_cap * sizeof(float) + (st_cap + cr_cap) * sizeof(double); }
     ~DevParts()
     {
         hipSetDevice(device);
         if (flight) hipDeviceSynchronize(); // (a batch destroyed with its part in flight: the kernels read what is freed below)
         for (void* p : ptrs) hipFree(p);
         hipFree(segs);
+        hipFree(mv);
+        hipFree(st_tab);
+        hipFree(cr_tab);
+    }
+    template <class T> hipError_t grow(T** p, size_t* cap, size_t need) // (the contents are not kept; nothing in flight reads them)
+    {
+        if (need <= *cap) return hipSuccess;
+        hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+        const hipError_t e = hipMalloc((void**)p, need * sizeof(T));
+        if (e == hipSuccess) *cap = need;
+        return e;
     }
     template <class T> hipError_t alloc(T** p, size_t n)
     {
@@ -273,6 +291,140 @@ std::vector<float> sized_ratios(const fvad_vad_batch* b, const size_t* n_frames,
     return ratio;
 }
 
+// The averages' tables of a part (kernels_vadavgs.hip): the keys with their places in the tables, the tables' sizes.  P[g]: the
+// part's longest row of size g; by_config / order: the lane map and lane order of the machines whose homes hold the history
+struct AvgsPlan {
+    std::vector<VadAvgKey> st, cr;
+    std::vector<long> tab_frames;      // [n_sizes]
+    std::vector<uint64_t> first_frame; // [n_sizes]
+    size_t st_elems = 0, cr_elems = 0, mv_elems = 0, mv_stride = 1;
+    size_t bytes() const { return mv_elems * sizeof(float) + (st_elems + cr_elems) * sizeof(double); }
+};
+AvgsPlan plan_avgs(const fvad_vad_batch* b, const std::vector<size_t>& P, uint64_t first_sample, int by_config, const std::vector<int>& order)
+{
+    const size_t S = b->n_streams, G = b->sizes.size(), NC = b->cfgs.size();
+    AvgsPlan pl;
+    pl.tab_frames.assign(P.begin(), P.end());
+    pl.first_frame.resize(G);
+    for (size_t g = 0; g < G; ++g) pl.first_frame[g] = first_sample / b->sizes[g];
+    pl.mv_stride = std::max<size_t>(*std::max_element(P.begin(), P.end()), 1);
+    pl.mv_elems = (b->bins.size() / 2) * S * pl.mv_stride;
+    auto lane_of = [&](size_t c) { // the lane whose place holds config c's rings (place_of)
+        if (by_config || order.empty()) return (long)c;
+        return (long)(std::find(order.begin(), order.end(), (int)c) - order.begin());
+    };
+    auto lay = [&](const std::vector<uint32_t>& pairs, const std::vector<uint32_t>& key_of, bool is_st, std::vector<VadAvgKey>* out, size_t* elems) {
+        const size_t K = pairs.size() / 2;
+        out->resize(K);
+        std::vector<uint32_t> nk(G, 0);
+        for (size_t j = 0; j < K; ++j) {
+            VadAvgKey& k = (*out)[j];
+            k.src = pairs[2 * j];
+            k.len = pairs[2 * j + 1];
+            k.size = is_st ? b->size_of_band[k.src] : k.src;
+            k.base = (long)nk[k.size]++; // (its index among its size's keys: the size's first entry is added below)
+            k.scalar = 1.0 / (double)k.len; // (vad_machine_cfg's st_scalar / cr_scalar)
+            const size_t c = (size_t)(std::find(key_of.begin(), key_of.end(), (uint32_t)j) - key_of.begin());
+            k.rep = lane_of(c < NC ? c : 0);
+        }
+        std::vector<long> first(G, 0);
+        size_t n = 0;
+        for (size_t g = 0; g < G; ++g) { first[g] = (long)n; n += S * P[g] * nk[g]; }
+        for (VadAvgKey& k : *out) { k.nk = nk[k.size]; k.base += first[k.size]; }
+        *elems = n;
+    };
+    lay(b->st_keys, b->st_key, true, &pl.st, &pl.st_elems);
+    lay(b->cr_keys, b->cr_key, false, &pl.cr, &pl.cr_elems);
+    return pl;
+}
+
+// whether a launch with the context's options may use the tables at all (the budget is checked against the plan)
+bool avgs_wanted_shape(const fvad_vad_batch* b) // (the grid of the tables' kernels: streams x bands or keys)
+{
+    return (long)b->n_streams <= kAvgsGridMax && (long)(b->bins.size() / 2) <= kAvgsGridMax &&
+           (long)((b->st_keys.size() + b->cr_keys.size()) / 2) <= kAvgsGridMax;
+}
+bool avgs_wanted(const fvad_ctx* ctx, const fvad_vad_batch* b)
+{
+    return ctx->tune.vad_avgs == 1 && ctx->tune.vad_chain == 1 && avgs_wanted_shape(b);
+}
+
+// Fill the tables of a part on stream st: upload the plan (into scratch, which lives as long as the launches that read it), run
+// the two kernels.  ma: the machines' launch (band, ratio, frame counts, homes and lane map are taken from it; its table fields
+// are set).  d_mv / d_st / d_cr: buffers of at least the plan's sizes.
+int fill_avgs(fvad_ctx* ctx, const fvad_vad_batch* b, const AvgsPlan& pl, DevScratch& scratch, float* d_mv, double* d_st, double* d_cr,
+              long max_nf, VadMachinesArgs* ma, hipStream_t st)
+{
+    const size_t G = b->sizes.size(), NC = b->cfgs.size();
+    VadAvgKey *d_stk = nullptr, *d_crk = nullptr;
+    uint32_t *d_st_key = nullptr, *d_cr_key = nullptr, *d_sob = nullptr;
+    long* d_tf = nullptr;
+    uint64_t* d_ff = nullptr;
+    FVAD_HIP(ctx, scratch.alloc(&d_stk, pl.st.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_crk, pl.cr.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_st_key, NC));
+    FVAD_HIP(ctx, scratch.alloc(&d_cr_key, NC));
+    FVAD_HIP(ctx, scratch.alloc(&d_sob, b->size_of_band.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_tf, G));
+    FVAD_HIP(ctx, scratch.alloc(&d_ff, G));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_stk, pl.st.data(), pl.st.size() * sizeof(VadAvgKey), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_crk, pl.cr.data(), pl.cr.size() * sizeof(VadAvgKey), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_st_key, b->st_key.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_cr_key, b->cr_key.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_sob, b->size_of_band.data(), b->size_of_band.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_tf, pl.tab_frames.data(), G * sizeof(long), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_ff, pl.first_frame.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VadAvgsArgs va{};
+    va.band = ma->band;
+    va.band_stride = ma->band_stride;
+    va.n_lanes = ma->n_lanes;
+    va.n_channels = ma->n_channels;
+    va.n_bands = (int)(b->bins.size() / 2);
+    va.n_sizes = (int)G;
+    va.n_streams = ma->n_streams;
+    va.size_of_band = d_sob;
+    va.n_frames = ma->n_frames;
+    va.max_frames = max_nf;
+    va.minvol = d_mv;
+    va.minvol_stride = (long)pl.mv_stride;
+    va.ratio = ma->ratio;
+    va.ratio_stride = ma->ratio_stride;
+    va.st_keys = d_stk;
+    va.cr_keys = d_crk;
+    va.n_st_keys = (int)pl.st.size();
+    va.n_cr_keys = (int)pl.cr.size();
+    va.st_tab = d_st;
+    va.cr_tab = d_cr;
+    va.tab_frames = d_tf;
+    va.first_frame = d_ff;
+    va.fresh = pl.first_frame[0] == 0;
+    va.rings = ma->rings;
+    va.st_max = ma->st_max;
+    va.by_config = ma->by_config;
+    va.n_configs = ma->n_configs;
+    va.n_machines = ma->n_machines;
+    const bool timed = st == ctx->stream;
+    if (timed) time_begin(ctx, "vad_minvol");
+    int e = fvad_launch_vad_minvol(va, st);
+    if (timed) time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_minvol");
+    if (timed) time_begin(ctx, "vad_avgs");
+    e = fvad_launch_vad_avgs(va, st);
+    if (timed) time_end(ctx);
+    if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_avgs");
+    ma->table = 1;
+    ma->minvol = d_mv;
+    ma->minvol_stride = (long)pl.mv_stride;
+    ma->st_tab = d_st;
+    ma->cr_tab = d_cr;
+    ma->st_keys = d_stk;
+    ma->cr_keys = d_crk;
+    ma->st_key = d_st_key;
+    ma->cr_key = d_cr_key;
+    ma->tab_frames = d_tf;
+    return FVAD_OK;
+}
+
 // one launch of every machine of b (fvad_vad_batch_run_device and _run_device_sized); n_frames [n_sizes][n_streams]
 int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
                const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size)
@@ -342,12 +494,14 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
     a.seg_count = d_count;
     a.audits = d_audit;
     a.stats = d_stats;
+    std::vector<int> order_h;
     if (G > 1) { // several frame clocks: the sized form of the kernel (one size runs the single-size form, as a create_sweep batch)
         uint64_t* d_sizes = nullptr;
         uint32_t* d_size_of = nullptr;
         int* d_order = nullptr;
         const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
         const std::vector<int> order = lane_order(b, ctx->tune.vad_size_order);
+        order_h = order;
         FVAD_HIP(ctx, scratch.alloc(&d_sizes, G));
         FVAD_HIP(ctx, scratch.alloc(&d_size_of, NC));
         FVAD_HIP(ctx, scratch.alloc(&d_order, NC));
@@ -366,6 +520,21 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
     // first launch when it is small; otherwise the first launch has room for 512 MB of segments over all machines (context option
     // vad_seg_cap: that many per machine instead) and counts past it, and if any machine closed more, a second launch with room for
     // the largest count redoes the run (the machines start fresh in every launch: same results).
+    // the averages' tables (context option vad_avgs "table" with vad_chain "coop", within vad_avgs_max_bytes): filled once, before
+    // the first launch; a second launch for segment room reads them again
+    b->avgs_bytes = 0;
+    if (avgs_wanted(ctx, b) && max_nf) {
+        const AvgsPlan pl = plan_avgs(b, P, 0, a.by_config, order_h);
+        if (pl.bytes() <= ctx->tune.vad_avgs_max_bytes) {
+            float* d_mv = nullptr;
+            double *d_st = nullptr, *d_cr = nullptr;
+            FVAD_HIP(ctx, scratch.alloc(&d_mv, pl.mv_elems));
+            FVAD_HIP(ctx, scratch.alloc(&d_st, pl.st_elems));
+            FVAD_HIP(ctx, scratch.alloc(&d_cr, pl.cr_elems));
+            if (const int rc = fill_avgs(ctx, b, pl, scratch, d_mv, d_st, d_cr, (long)max_nf, &a, st)) return rc;
+            b->avgs_bytes = pl.bytes();
+        }
+    }
     const size_t bound = max_nf / 4 + 1;
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
                                                   : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / (size_t)M);
@@ -383,6 +552,7 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
         time_end(ctx);
         if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
         b->chain_form = a.coop ? 2 : 1;
+        b->avgs_form = a.coop && a.table ? 2 : 1;
         FVAD_HIP(ctx, hipMemcpyAsync(count.data(), d_count, (size_t)M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         FVAD_HIP(ctx, hipStreamSynchronize(st));
         const size_t most = *std::max_element(count.begin(), count.end());
@@ -456,6 +626,7 @@ int launch_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
     if (timed) time_end(ctx);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
     b->chain_form = pf.a.coop ? 2 : 1;
+    b->avgs_form = pf.a.coop && pf.a.table ? 2 : 1; // (a part that filled its tables and is relaunched as the lane form runs the rings)
     return FVAD_OK;
 }
 
@@ -730,6 +901,20 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         a.lane_config = dp->lane_config;
         a.first_sample = first_sample;
     }
+    // The averages' tables of the part (context option vad_avgs "table" with vad_chain "coop", within vad_avgs_max_bytes), filled
+    // once on the part's stream before its first launch: a relaunch after a pause reads them again, and they do not follow the
+    // homes, which every launch that ends rewrites.  Their history comes from the homes as the previous part left them.
+    b->avgs_bytes = 0;
+    if (avgs_wanted(ctx, b) && max_nf) {
+        const AvgsPlan pl = plan_avgs(b, P, first_sample, dp->by_config, dp->order);
+        if (pl.bytes() <= ctx->tune.vad_avgs_max_bytes) {
+            FVAD_HIP(ctx, dp->grow(&dp->mv, &dp->mv_cap, pl.mv_elems));
+            FVAD_HIP(ctx, dp->grow(&dp->st_tab, &dp->st_cap, pl.st_elems));
+            FVAD_HIP(ctx, dp->grow(&dp->cr_tab, &dp->cr_cap, pl.cr_elems));
+            if (const int rc = fill_avgs(ctx, b, pl, pf.scratch, dp->mv, dp->st_tab, dp->cr_tab, (long)max_nf, &a, st)) return rc;
+            b->avgs_bytes = pl.bytes();
+        }
+    }
     if (const int rc = launch_part(ctx, b, dp, pf)) return rc;
     if (async) { // fvad_vad_batch_part_wait goes on from here
         dp->flight = std::move(flight);
@@ -882,11 +1067,97 @@ int fvad_vad_batch_chain_form(const fvad_vad_batch* b, int* form)
     return FVAD_OK;
 }
 
+int fvad_vad_batch_avgs_form(const fvad_vad_batch* b, int* form)
+{
+    if (!b || !form) return FVAD_ERR_INVALID_ARGUMENT;
+    *form = b->avgs_form;
+    return FVAD_OK;
+}
+
+size_t fvad_vad_batch_avgs_bytes(const fvad_vad_batch* b) { return b ? b->avgs_bytes : 0; }
+
+int fvad_vad_batch_averages_device(fvad_ctx* ctx, const fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                                   const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                                   uint64_t first_sample, double* st_avg, double* cr_avg, size_t row_stride)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !n_frames || !n_chunks || chunk_size == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
+    const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, G = b->sizes.size();
+    std::vector<size_t> P;
+    if (const char* msg = frame_counts(b, n_frames, n_chunks, chunk_size, &P)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, msg);
+    const size_t max_nf = *std::max_element(P.begin(), P.end());
+    if (max_nf == 0) return FVAD_OK;
+    if (!d_band || !chunk_rms || !st_avg || !cr_avg) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (band_stride < max_nf || row_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a stride < frames of a stream");
+    if (first_sample % chunk_size) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a chunk boundary");
+    for (size_t g = 0; g < G; ++g)
+        if (first_sample % b->sizes[g]) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts on a frame of every size");
+    if (!avgs_wanted_shape(b)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "more streams, bands or keys than the tables' kernels take");
+    const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+    if (first_sample != 0) { // the history is the part state's: the rings' homes as the last part left them
+        if (!dp) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no device part state to read the earlier frames from");
+        if (dp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the parts of a run are on one context");
+        if (first_sample != dp->next_sample) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a part starts where the previous one ended");
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t ratio_stride = max_nf;
+    const std::vector<float> ratio = sized_ratios(b, n_frames, chunk_rms, rms_stride, n_chunks, chunk_size, first_sample, ratio_stride);
+    const std::vector<long> nf_l(n_frames, n_frames + G * S);
+    std::vector<int> order;
+    if (first_sample != 0) order = dp->order;
+    const int by_config = first_sample != 0 ? dp->by_config : ctx->tune.vad_lane_map;
+    const AvgsPlan pl = plan_avgs(b, P, first_sample, by_config, order);
+    DevScratch scratch;
+    float *d_ratio = nullptr, *d_mv = nullptr;
+    long* d_nf = nullptr;
+    double *d_st = nullptr, *d_cr = nullptr;
+    FVAD_HIP(ctx, scratch.alloc(&d_ratio, ratio.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_nf, nf_l.size()));
+    FVAD_HIP(ctx, scratch.alloc(&d_mv, pl.mv_elems));
+    FVAD_HIP(ctx, scratch.alloc(&d_st, pl.st_elems));
+    FVAD_HIP(ctx, scratch.alloc(&d_cr, pl.cr_elems));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_ratio, ratio.data(), ratio.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(d_nf, nf_l.data(), nf_l.size() * sizeof(long), hipMemcpyHostToDevice, st));
+    VadMachinesArgs a{}; // (only what fill_avgs reads of a launch)
+    a.n_configs = (int)NC;
+    a.n_streams = (long)S;
+    a.by_config = by_config;
+    a.n_channels = (int)C;
+    a.n_machines = (long)(S * NC);
+    a.n_lanes = (long)(S * C);
+    a.band = d_band;
+    a.band_stride = (long)band_stride;
+    a.ratio = d_ratio;
+    a.ratio_stride = (long)ratio_stride;
+    a.n_frames = d_nf;
+    a.rings = first_sample != 0 ? dp->rings : nullptr;
+    a.st_max = first_sample != 0 ? (int)dp->st_max : 0;
+    if (const int rc = fill_avgs(ctx, b, pl, scratch, d_mv, d_st, d_cr, (long)max_nf, &a, st)) return rc;
+    std::vector<double> h_st(pl.st_elems), h_cr(pl.cr_elems);
+    FVAD_HIP(ctx, hipMemcpyAsync(h_st.data(), d_st, h_st.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(h_cr.data(), d_cr, h_cr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    FVAD_HIP(ctx, hipStreamSynchronize(st));
+    FVAD_HIP(ctx, hipGetLastError());
+    auto gather = [&](const std::vector<VadAvgKey>& keys, const std::vector<double>& tab, double* out) {
+        for (size_t j = 0; j < keys.size(); ++j) {
+            const VadAvgKey& k = keys[j];
+            for (size_t s = 0; s < S; ++s)
+                for (size_t f = 0; f < n_frames[k.size * S + s]; ++f)
+                    out[(j * S + s) * row_stride + f] = tab[(size_t)k.base + (s * P[k.size] + f) * k.nk];
+        }
+    };
+    gather(pl.st, h_st, st_avg);
+    gather(pl.cr, h_cr, cr_avg);
+    return FVAD_OK;
+}
+
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)
 {
     const DevParts* dp = b ? static_cast<const DevParts*>(b->dev_parts.get()) : nullptr;
     if (!dp) return 0;
-    return dp->bytes + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
+    return dp->bytes + dp->table_bytes() + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
 }
 
 int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "host_vad.h"
+#include "vad_avgs.h"
 #include "vad_ratio.h"
 
 namespace fvad {
@@ -380,6 +381,7 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
     b->audits.resize(n_streams);
     b->exact_evals.assign(n_streams, 0);
     b->lazy_pushes.assign(n_streams, 0);
+    if (const int rc = fvad::derive_avg_keys(b)) { delete b; return rc; }
     *out = b;
     return FVAD_OK;
 }
@@ -434,6 +436,7 @@ static int make_sweep(const fvad_vad_config* cfgs, size_t n_configs, const std::
     b->audits.resize(n_streams * n_configs);
     b->exact_evals.assign(n_streams * n_configs, 0);
     b->lazy_pushes.assign(n_streams * n_configs, 0);
+    if (const int rc = fvad::derive_avg_keys(b)) { delete b; return rc; }
     *out = b;
     return FVAD_OK;
 }
@@ -477,6 +480,31 @@ void fvad_vad_batch_destroy(fvad_vad_batch* b) { delete b; }
 
 size_t fvad_vad_batch_n_configs(const fvad_vad_batch* b) { return b ? b->cfgs.size() : 0; }
 
+int fvad_vad_batch_avg_keys(const fvad_vad_batch* b, uint32_t* st_keys, uint32_t* cr_keys, size_t cap, size_t* n_st_keys,
+                            size_t* n_cr_keys, uint32_t* st_key, uint32_t* cr_key)
+{
+    if (!b || !n_st_keys || !n_cr_keys) return FVAD_ERR_INVALID_ARGUMENT;
+    *n_st_keys = b->st_keys.size() / 2;
+    *n_cr_keys = b->cr_keys.size() / 2;
+    if (st_key) memcpy(st_key, b->st_key.data(), b->st_key.size() * sizeof(uint32_t));
+    if (cr_key) memcpy(cr_key, b->cr_key.data(), b->cr_key.size() * sizeof(uint32_t));
+    if (cap < *n_st_keys || cap < *n_cr_keys) return FVAD_ERR_BUFFER_TOO_SMALL;
+    if (!st_keys || !cr_keys) return FVAD_ERR_INVALID_ARGUMENT;
+    memcpy(st_keys, b->st_keys.data(), b->st_keys.size() * sizeof(uint32_t));
+    memcpy(cr_keys, b->cr_keys.data(), b->cr_keys.size() * sizeof(uint32_t));
+    return FVAD_OK;
+}
+
+int fvad_vad_avg_chain(const float* x, size_t n_frames, size_t first_frame, uint32_t len, const float* ring, double* out)
+{
+    if (len == 0 || (n_frames && (!x || !out)) || (first_frame && !ring)) return FVAD_ERR_INVALID_ARGUMENT;
+    const double scalar = 1.0 / (double)len;
+    for (size_t k = 0; k < n_frames; ++k)
+        out[k] = fvad::ring_avg_at((uint64_t)(first_frame + k), len, scalar,
+                                   [&](uint32_t i, uint64_t f) { return f >= first_frame ? x[f - first_frame] : ring[i]; });
+    return FVAD_OK;
+}
+
 int fvad_vad_batch_bands(const fvad_vad_batch* b, int32_t* bins, size_t cap, size_t* n_bands, uint32_t* band_of)
 {
     if (!b || !n_bands) return FVAD_ERR_INVALID_ARGUMENT;
@@ -491,6 +519,26 @@ int fvad_vad_batch_bands(const fvad_vad_batch* b, int32_t* bins, size_t cap, siz
 } // extern "C"
 
 namespace fvad {
+
+int derive_avg_keys(fvad_vad_batch* b)
+{
+    const size_t NC = b->cfgs.size();
+    b->st_keys.clear(); b->cr_keys.clear();
+    b->st_key.assign(NC, 0); b->cr_key.assign(NC, 0);
+    auto find = [](std::vector<uint32_t>& keys, uint32_t src, uint32_t len) {
+        size_t j = 0;
+        while (j < keys.size() / 2 && !(keys[2 * j] == src && keys[2 * j + 1] == len)) ++j;
+        if (j == keys.size() / 2) { keys.push_back(src); keys.push_back(len); }
+        return (uint32_t)j;
+    };
+    for (size_t c = 0; c < NC; ++c) {
+        VadMachineCfg k;
+        if (const int rc = vad_machine_cfg(b->cfgs[c], b->sample_rate, b->sizes[b->size_of[c]], &k)) return rc;
+        b->st_key[c] = find(b->st_keys, b->band_of[c], k.short_len);
+        b->cr_key[c] = find(b->cr_keys, b->size_of[c], k.ratio_len);
+    }
+    return FVAD_OK;
+}
 
 int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb)
 {
@@ -533,6 +581,7 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
         nb->sample_rate = b->sample_rate; nb->n_channels = b->n_channels; nb->fft_size = nb->sizes[0]; nb->n_streams = S;
         nb->cfgs.resize(n_keep);
         for (size_t c = 0; c < n_keep; ++c) nb->cfgs[c] = b->cfgs[keep[c]];
+        if (const int rc = derive_avg_keys(nb)) return rc; // (the survivors' keys in their first-seen order, as the bands above)
         // per machine (stream s, config c) -> (s, keep[c])
         const size_t M = S * n_keep;
         nb->segs.resize(M);
@@ -565,6 +614,8 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
     nb->segs_kept = b->segs_kept;
     nb->next_sample = b->next_sample;
     nb->chain_form = b->chain_form;
+    nb->avgs_form = b->avgs_form;
+    nb->avgs_bytes = b->avgs_bytes;
     return FVAD_OK;
 }
 

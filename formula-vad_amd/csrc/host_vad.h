@@ -90,6 +90,8 @@ namespace fvad {
 // recomputed in first-seen order, audits, lazy statistics, stat configs and scores compacted; nb->machines and nb->segs sized but
 // empty (b is not touched).  retain_commit (cannot fail): move b's kept machines and segments into nb, then nb's fields into b
 // (b's device part state too, unless nb already holds the compacted one).
+// b's keys of the averages' tables from its configs, bands and sizes (fvad_vad_batch::st_keys ...): at creation and after a retain
+int derive_avg_keys(fvad_vad_batch* b);
 int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
 void retain_commit(fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
 } // namespace fvad
@@ -118,6 +120,14 @@ struct fvad_vad_batch {
     bool part_in_flight = false;
     // fvad_vad_batch_chain_form: 0 = no device launch yet, 1 = the last one ran the lane form of the machines' kernel, 2 = the cooperative form
     int chain_form = 0;
+    // The keys of the averages' tables (context option vad_avgs "table", kernels_vadavgs.hip), in first-seen config order: a short
+    // key is (band, short_len) -- st_keys holds the pairs --, a ratio key (size index, ratio_len); st_key[c] / cr_key[c] are
+    // config c's.  Configs with one key have the same short-term (channel-ratio) average in every frame of a stream.
+    std::vector<uint32_t> st_keys, cr_keys, st_key, cr_key;
+    // fvad_vad_batch_avgs_form: 0 = no device launch yet, 1 = the last one pushed the short rings, 2 = it read the tables;
+    // avgs_bytes: the tables and min_volume rows of the last launch's part (0 with the rings)
+    int avgs_form = 0;
+    size_t avgs_bytes = 0;
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
     // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
     bool has_refs = false;

@@ -211,6 +211,7 @@ int fvad_launch_irfft_generic(const float* bins, long n_frames, VadFftPlan pl, f
 
 // ------------------------------------------------------------------ VAD machines of a parameter sweep (kernels_vad.hip)
 namespace fvad { struct VadMachineCfg; struct VadLaneState; } // vad_machine.h
+struct VadAvgKey;
 struct VadMachinesArgs {
     const fvad::VadMachineCfg* cfgs; // [n_configs] (device), with their bands
     int n_configs, n_channels;
@@ -253,8 +254,66 @@ struct VadMachinesArgs {
     const uint32_t* size_of;    // [n_configs] (device)
     const int* lane_config;     // [n_configs] (device)
     uint64_t first_sample;
+    // ---- the table form (table = 1 with coop = 1; context option vad_avgs "table"): the short-term and channel-ratio averages
+    // of every frame of the part come from the tables fvad_launch_vad_avgs filled (VadAvgsArgs below: the same pointers), the
+    // frame's min_volume from minvol; the machine pushes no short ring.  A launch that stores state (resume = 1) leaves in
+    // `rings` and state[] what the ring form would have left, bit for bit
+    int table;
+    const float* minvol;        // [n_bands][n_streams][minvol_stride]
+    long minvol_stride;
+    const double* st_tab;       // key j's average of (stream s, frame k of the part) at tab[key.base + (s * tab_frames[key.size] + k) * key.nk]
+    const double* cr_tab;
+    const VadAvgKey* st_keys;   // (VadAvgKey: below, with the tables' kernels)
+    const VadAvgKey* cr_keys;
+    const uint32_t* st_key;     // [n_configs] (device): each config's short key, ratio key
+    const uint32_t* cr_key;
+    const long* tab_frames;     // [n_sizes] (device): the frames of a stream's table rows, per size
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ the averages' tables of a part (kernels_vadavgs.hip, vad_avgs.h)
+// A short key is (band, short_len), a ratio key (size, ratio_len): every config with the same key has the same average in every
+// frame.  Per size the table is [stream][frame][keys of that size], so that a wavefront of one stream's configs reads a frame's
+// averages from a few lines.
+struct VadAvgKey {
+    uint32_t src;     // short key: the band block; ratio key: the size index
+    uint32_t len;     // the ring's length
+    uint32_t size;    // the size index of the key's frame clock
+    uint32_t nk;      // keys of that size in the table (the stride between two frames)
+    long base;        // the key's entry of (stream 0, frame 0)
+    long rep;         // the lane of a machine with this key: its place is rep * n_streams + s by config, s * n_configs + rep by stream
+    double scalar;    // 1 / len as VadMachineCfg has it
+};
+struct VadAvgsArgs {
+    const float* band;          // as VadMachinesArgs
+    long band_stride, n_lanes;
+    int n_channels, n_bands, n_sizes;
+    long n_streams;
+    const uint32_t* size_of_band; // [n_bands] (device); null with one size
+    const long* n_frames;       // [n_sizes][n_streams] (device)
+    long max_frames;            // the longest row of the part
+    float* minvol;              // out: [n_bands][n_streams][minvol_stride]
+    long minvol_stride;
+    const float* ratio;         // row (size, stream) at ratio + row * ratio_stride
+    long ratio_stride;
+    const VadAvgKey* st_keys;   // (device)
+    const VadAvgKey* cr_keys;
+    int n_st_keys, n_cr_keys;
+    double* st_tab;             // out
+    double* cr_tab;
+    const long* tab_frames;     // [n_sizes] (device)
+    const uint64_t* first_frame; // [n_sizes] (device): the part's first frame in each size's frames
+    int fresh;                  // no earlier frames: the homes are not read
+    const float* rings;         // the rings' home [st_max + cr_max][n_machines] at the part's start
+    int st_max, by_config, n_configs;
+    long n_machines;
+};
+// the frame tile of vad_avgs_kernel and vad_minvol_kernel: frames per workgroup
+constexpr int kAvgsTile = 256;
+// (grid: frame tiles x streams x bands or keys -- the caller keeps streams, bands and keys at or below kAvgsGridMax)
+constexpr long kAvgsGridMax = 65535;
+int fvad_launch_vad_minvol(const VadAvgsArgs& a, hipStream_t stream); // hipError_t as int
+int fvad_launch_vad_avgs(const VadAvgsArgs& a, hipStream_t stream);   // (after fvad_launch_vad_minvol on the same stream)
 
 // ------------------------------------------------------------------ the frame ratios of a device part (kernels_vadratio.hip)
 // row (size g, stream s) = g * n_streams + s: frames [0, n_frames[row]) of sizes[g] samples from sample first_sample on (a chunk

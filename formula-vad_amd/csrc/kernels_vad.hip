@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "vad_avgs.h"
 #include "vad_machine.h"
 
 namespace {
@@ -418,7 +419,12 @@ __device__ __forceinline__ void coop_chain(const float* lt_rings, long n_machine
 
 } // namespace
 
-template <bool RINGS_LDS, bool SIZED>
+// TABLE (context option vad_avgs "table", a.table): the frame's short-term and channel-ratio averages are loaded from the tables
+// kernels_vadavgs.hip filled before the launch, and its min_volume from the row that kernel's input was, instead of pushing the
+// two short rings: two f64 loads per frame in place of two chains over LDS.  The form has no short rings (RINGS_LDS is false).
+// A launch that stores state writes into the rings' home and the cursors what the ring form's pushes of the same frames would
+// have left (vad_avgs.h), so every later launch -- of either form, after a retain or not -- goes on from the same bits.
+template <bool RINGS_LDS, bool SIZED, bool TABLE = false>
 __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a)
 {
     extern __shared__ double vad_coop_lds[]; // [2][kCoopTile] chain terms, then the short rings [st_max + cr_max][64] (RINGS_LDS)
@@ -492,7 +498,29 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
     fvad_speech_segment* seg = a.segs + id * (long)a.seg_cap;
     constexpr int kPre = 4;
     float nv[kPre], nr = 0.0f;
+    // the table form's rows: min_volume of (band, stream), the two averages of (key, stream), their next frame's values
+    const float* mv_row = nullptr;
+    const double *st_row = nullptr, *cr_row = nullptr;
+    long st_nk = 0, cr_nk = 0;
+    float nmv = 0.0f;
+    double nst = 0.0, ncr = 0.0;
+    if constexpr (TABLE) {
+        const VadAvgKey& ks = a.st_keys[a.st_key[c]];
+        const VadAvgKey& kc = a.cr_keys[a.cr_key[c]];
+        mv_row = a.minvol + ((long)cfg->band * a.n_streams + s) * a.minvol_stride;
+        st_row = a.st_tab + ks.base + s * a.tab_frames[ks.size] * (long)ks.nk;
+        cr_row = a.cr_tab + kc.base + s * a.tab_frames[kc.size] * (long)kc.nk;
+        st_nk = ks.nk;
+        cr_nk = kc.nk;
+    }
     auto fetch = [&](long k) {
+        if constexpr (TABLE) {
+            nmv = mv_row[k];
+            nr = ratio[k];
+            nst = st_row[k * st_nk];
+            ncr = cr_row[k * cr_nk];
+            return;
+        }
 #pragma unroll
         for (int ch = 0; ch < kPre; ++ch) nv[ch] = ch < C ? band[(long)ch * a.band_stride + k] : 999.0f;
         nr = ratio[k];
@@ -531,11 +559,19 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
         double st = 0.0, cr = 0.0;
         bool met = false, before = false, redo = false;
         if (running) {
-            mv = min_vol(k);
-            rt = nr;
-            if (k + 1 < nf) fetch(k + 1);
-            st = mc.st.push(mv);
-            cr = mc.cr.push(rt);
+            if constexpr (TABLE) {
+                mv = nmv;
+                rt = nr;
+                st = nst;
+                cr = ncr;
+                if (k + 1 < nf) fetch(k + 1);
+            } else {
+                mv = min_vol(k);
+                rt = nr;
+                if (k + 1 < nf) fetch(k + 1);
+                st = mc.st.push(mv);
+                cr = mc.cr.push(rt);
+            }
             // decide up to its exact(): if it asks for the chain, what it did to the audit with the stale average is undone
             // and it runs again after the chain (then with a current average: the path below its exact())
             const fvad_vad_audit au = mc.audit;
@@ -562,6 +598,25 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
         }
     }
     if (!valid) return;
+    if constexpr (TABLE) {
+        if (RESUME) { // the short rings as the ring form's pushes of frames [0, k_end) of the part would have left them
+            const uint64_t done = first_frame + (uint64_t)k_end; // pushes since the stream's start
+            auto settle = [&](Ring<P>& r, const float* row, long home_row) {
+                float* home = a.rings + home_row * a.n_machines + m;
+                const long len = (long)r.len;
+                for (long j = k_end > len ? k_end - len : 0; j < k_end; ++j)
+                    home[(long)((first_frame + (uint64_t)j) % r.len) * a.n_machines] = row[j];
+                r.w = fvad::ring_w_after(done, r.len);
+                r.wc = fvad::ring_wc_after(done, r.len);
+                double acc = 0.0;
+                if (r.wc == r.len)
+                    for (uint32_t i = 0; i < r.w; ++i) acc += (double)home[(long)i * a.n_machines] * r.scalar;
+                r.pref = acc;
+            };
+            settle(mc.st, mv_row, 0);
+            settle(mc.cr, ratio, a.st_max);
+        }
+    }
     if (RESUME) {
         fvad::VadLaneState& ls = a.state[id];
         copy_state(ls.m, mc);
@@ -586,6 +641,12 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream)
 {
     if (a.n_machines <= 0) return (int)hipSuccess;
+    if (a.coop && a.table) { // the table form: the two chain tiles, no short rings
+        const dim3 grid((unsigned)((a.n_machines + 63) / 64));
+        if (a.sized) hipLaunchKernelGGL((vad_machines_coop_kernel<false, true, true>), grid, dim3(64), kCoopLdsBytes, stream, a);
+        else hipLaunchKernelGGL((vad_machines_coop_kernel<false, false, true>), grid, dim3(64), kCoopLdsBytes, stream, a);
+        return (int)hipGetLastError();
+    }
     if (a.coop) { // the cooperative form: two chain tiles ahead of the short rings (at most 16 + 48 KB)
         const size_t lds = kCoopLdsBytes + (a.rings_in_lds ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0);
         const dim3 grid((unsigned)((a.n_machines + 63) / 64));

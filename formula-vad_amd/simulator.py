@@ -353,11 +353,25 @@ SWEEP_DEVICE_MIN_CONFIGS = 256
 # the same threshold with vad_chain="coop" (the machines' exact long-term chains run by the whole wavefront)
 SWEEP_DEVICE_MIN_CONFIGS_COOP = 192
 VAD_CHAINS = ("lane", "coop")
+# vad_avgs: where the device machines' short-term and channel-ratio averages come from (context option vad_avgs, DESIGN section
+# 7.1): each machine's own rings, or tables filled frame-parallel before the launch -- only the cooperative kernel reads those
+VAD_AVGS = ("ring", "table")
 
 
-def _check_vad_chain(vad_chain):
+def _check_vad_chain(vad_chain, vad_avgs=None):
     if vad_chain is not None and vad_chain not in VAD_CHAINS:
         raise ValueError(f"vad_chain: {vad_chain!r} (one of {VAD_CHAINS})")
+    if vad_avgs is not None and vad_avgs not in VAD_AVGS:
+        raise ValueError(f"vad_avgs: {vad_avgs!r} (one of {VAD_AVGS})")
+    if vad_avgs == "table" and vad_chain != "coop":
+        raise ValueError(f"vad_avgs='table' needs vad_chain='coop' (vad_chain: {vad_chain!r}): only the cooperative form of the "
+                         "machines' kernel reads the averages' tables")
+
+
+def _note_avgs(times, b):
+    """times' avgs_form / avgs_bytes after a device launch of b: the largest form (2: a launch read the tables) and table size"""
+    times["avgs_form"] = max(times.get("avgs_form", 0), b.avgs_form())
+    times["avgs_bytes"] = max(times.get("avgs_bytes", 0), b.avgs_bytes())
 
 
 def _auto_vad_on(n_configs, vad_chain):
@@ -365,23 +379,26 @@ def _auto_vad_on(n_configs, vad_chain):
 
 
 class _VadChain:
-    """The context option vad_chain on the contexts of one run_sweep / run_grid call: set on entry (nothing when vad_chain is
-    None), and on a caller's context (owned False) put back on exit to what it was set to before"""
+    """The context options vad_chain and vad_avgs on the contexts of one run_sweep / run_grid call: set on entry (nothing for
+    one that is None), and on a caller's context (owned False) put back on exit to what it was set to before"""
 
-    def __init__(self, vad_chain):
-        self.vad_chain, self.restore = vad_chain, []
+    def __init__(self, vad_chain, vad_avgs=None):
+        self.values, self.restore = {"vad_chain": vad_chain, "vad_avgs": vad_avgs}, []
 
     def apply(self, ctx, owned):
-        if self.vad_chain is None or ctx is None:
+        if ctx is None:
             return
-        prev = ctx.option_set("vad_chain")
-        ctx.set_option("vad_chain", self.vad_chain)
-        if not owned:
-            self.restore.append((ctx, prev))
+        for name, value in self.values.items():
+            if value is None:
+                continue
+            prev = ctx.option_set(name)
+            ctx.set_option(name, value)
+            if not owned:
+                self.restore.append((ctx, name, prev))
 
     def close(self):
-        for ctx, prev in self.restore:
-            ctx.set_option("vad_chain", prev)
+        for ctx, name, prev in reversed(self.restore):
+            ctx.set_option(name, prev)
         self.restore = []
 
 
@@ -489,6 +506,7 @@ def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_ch
                 ctx.enable_timing(False)
         times["machines"] += wall - score_s
         times["scoring"] += score_s
+        _note_avgs(times, b)
         done(b, members)
         return
     gband = ctx.to_host(np.empty((len(b.size_of_band), len(members) * nch, bstride), np.float32), d_gband)
@@ -508,7 +526,7 @@ def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_ch
 
 
 def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16,
-              vad_chain=None):
+              vad_chain=None, vad_avgs=None):
     """Scores many VADMachine configurations over one denoising pass of a plan's instances.
 
     configs: list of VADMachine.Config override dicts (vad_overrides' form); default: the plan's vad_machine_config followed by its
@@ -521,15 +539,18 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     from SWEEP_DEVICE_MIN_CONFIGS configs on); both give the same bits.  vad_chain "lane" or "coop": the context option of that
     name for this call (how the device machines run their exact long-term chains; same bits; "auto" then takes
     SWEEP_DEVICE_MIN_CONFIGS_COOP for "coop"), set on the context the call makes, or on the caller's and put back afterwards;
-    None leaves the context as it is; anything else is a ValueError before any device is touched.
+    None leaves the context as it is; anything else is a ValueError before any device is touched.  vad_avgs "ring" or "table": the
+    context option of that name, handled the same way (the device machines' short-term and channel-ratio averages from their
+    own rings or from tables filled before the launch; same bits); "table" without vad_chain="coop" is a ValueError.
 
     Returns dict(configs, rows [one aggregate dict per config], aggregates [AggregateStats], segments [config][instance],
-    stats [config][instance]); prints one table row per config and writes the rows as JSON to json_path if given."""
+    stats [config][instance], avgs_form, avgs_bytes [VadSweep.avgs_form() / avgs_bytes(): the largest over the device
+    launches; 0 with host machines]); prints one table row per config and writes the rows as JSON to json_path if given."""
+    _check_vad_chain(vad_chain, vad_avgs)
     plan = load_plan(plan_path)
     if configs is None:
         configs = [plan["vad_machine_config"]] + list(plan["alt_vad_machine_configs"])
     configs = [dict(c) for c in configs]
-    _check_vad_chain(vad_chain)
     if vad_on == "auto":
         vad_on = _auto_vad_on(len(configs), vad_chain)
     if vad_on not in ("device", "host"):
@@ -538,7 +559,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     own_ctx = ctx is None
     if own_ctx:
         ctx = _make_ctx(plan, 0, synth_seed)
-    chain = _VadChain(vad_chain)
+    chain = _VadChain(vad_chain, vad_avgs)
     loaded = [_read_instance(i) for i in plan["instances"]]
     audio = [a for a, _ in loaded]
     refs = [r for _, r in loaded]
@@ -595,10 +616,11 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
         aggs.append(agg)
         all_stats.append(stats)
         rows.append(dict(config=c, **_agg_row(agg)))
-    result = {"configs": configs, "rows": rows, "aggregates": aggs, "segments": segs, "stats": all_stats}
+    result = {"configs": configs, "rows": rows, "aggregates": aggs, "segments": segs, "stats": all_stats,
+              "avgs_form": times.get("avgs_form", 0), "avgs_bytes": times.get("avgs_bytes", 0)}
     if json_path:
         with open(json_path, "w") as f:
-            json.dump({"configs": configs, "rows": rows,
+            json.dump({"configs": configs, "rows": rows, "avgs_form": result["avgs_form"], "avgs_bytes": result["avgs_bytes"],
                        "segments": [[[list(map(float, x)) for x in inst] for inst in per] for per in segs]}, f, indent=1)
     if out is not None:
         out.write("| config |      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
@@ -744,7 +766,8 @@ def _check_grid_contexts(ctx, devices):
 
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
-             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False, vad_chain=None):
+             n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False, vad_chain=None,
+             vad_avgs=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -811,8 +834,10 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     On reproducible contexts the statistics, survivors, rungs and evaluated_seconds are those of overlap=False bit for bit.
     times gains machines_wait (the host time inside the waits, counted in machines too); device_bytes counts the second set
     of the bands and rms buffers.
-    vad_chain as in run_sweep: set on every context the call makes, and on the caller's contexts for the call."""
-    _check_vad_chain(vad_chain)
+    vad_chain and vad_avgs as in run_sweep: set on every context the call makes, and on the caller's contexts for the call;
+    times gains avgs_form and avgs_bytes (the largest over the shares' device launches: 2 once a launch read the tables, and
+    the largest part's tables in bytes), which the JSON file carries too."""
+    _check_vad_chain(vad_chain, vad_avgs)
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
@@ -893,7 +918,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     stop = threading.Event()   # set when a worker fails: the others stop at their next slice or rung
     errs, breaks = [], []
     t_all = time.perf_counter()
-    chain = _VadChain(vad_chain)
+    chain = _VadChain(vad_chain, vad_avgs)
 
     def work(s):
         t0 = time.perf_counter()
@@ -934,7 +959,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     times = {}
     for s in workers:
         for k, v in share_times[s]["times"].items():
-            times[k] = times.get(k, 0.0) + v
+            times[k] = max(times.get(k, 0), v) if k in ("avgs_form", "avgs_bytes") else times.get(k, 0.0) + v
+    times.setdefault("avgs_form", 0)
+    times.setdefault("avgs_bytes", 0)
     n_slices = sum(share_out[s][0] for s in workers)
     bytes_per_share = [share_out[s][1] for s in range(len(shares))]
     dev_bytes = max((b for b in bytes_per_share if b is not None), default=None)
@@ -952,7 +979,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     elapsed = time.perf_counter() - t_all
     if json_path:
         with open(json_path, "w") as f:
-            doc = {"grid": grid, "configs": configs, "rows": rows}
+            doc = {"grid": grid, "configs": configs, "rows": rows, "avgs_form": times["avgs_form"], "avgs_bytes": times["avgs_bytes"]}
             if halving is not None:
                 doc.update(survivors=halving["survivors"], rung_times=halving["rungs_run"])
             json.dump(doc, f, indent=1)
@@ -1278,6 +1305,8 @@ def _run_slices(ctx, job, audio, refs, ids, groups, n_chunks, K, buf, stats, tim
                 t0 = time.perf_counter()
                 m.part(buf.d["bands"], buf.fr_slice, nf, rms, nc, s0 * chunk)
                 times["machines"] += time.perf_counter() - t0
+                if job.vad_on == "device":
+                    _note_avgs(times, m.b)
             peak = held()
             if rungs is None:
                 continue
@@ -1393,6 +1422,7 @@ class _Overlap:
             dt = time.perf_counter() - t0
             self.times["machines_wait"] += dt
             self.times["machines"] += dt
+            _note_avgs(self.times, b)
 
     def next_set(self):
         """the buffer set of the next slice, free to be written"""
@@ -1523,6 +1553,10 @@ def arg_parser():
     ap.add_argument("--vad-chain", default=None, choices=VAD_CHAINS,
                     help="with --sweep / --sweep-grid: how the device VAD machines run their exact long-term chains (context option "
                          "vad_chain): lane by lane (the default) or by the whole wavefront; same results")
+    ap.add_argument("--vad-avgs", default=None, choices=VAD_AVGS,
+                    help="with --sweep / --sweep-grid and --vad-chain coop: the device VAD machines' short-term and channel-ratio "
+                         "averages from their own rings (the default) or from tables filled frame-parallel before the launch "
+                         "(context option vad_avgs); same results")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -1535,10 +1569,10 @@ def main(argv=None):
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
-                 overlap=a.overlap, vad_chain=a.vad_chain)
+                 overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs)
         return
     if a.sweep:
-        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain)
+        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs)
         return
     run_plan(a.input, synth_seed=a.synth_seed, devices=devices or [0])
 

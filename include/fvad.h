@@ -330,7 +330,7 @@ const char *fvad_ctx_last_nn_path(const fvad_ctx *ctx);
  * fvad_engine_run's host-buffer pipeline in sixteenths of the call, at most seven, instead of the planned ones) | "trace_run" (a timeline of every fvad_engine_run call on stderr) | "trace_kernels" |
  * "ws_spin_ticks" | "ws2_variant" (diagnostic bit mask; the timing-only bits exist in the diagnostics build alone) |
  * "ws2_waits" | "ws2_calibrate" (below) | "k4_plain_loads" (the band FFT's staging path of unaligned frames) | "gru_lat_tiles" ("1" | "2" | "3": row tiles per
- * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_chain" ("lane" | "coop": the exact
+ * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_avgs" ("ring" | "table") | "vad_avgs_max_bytes" (see fvad_vad_batch_avgs_form) | "vad_chain" ("lane" | "coop": the exact
  * long-term chains of the device VAD machines lane by lane or by the whole wavefront, see fvad_vad_batch_run_device_part; same bits);
  * value NULL or ""
  * restores the default.  The environment variables FVAD_<NAME> are read ONCE, by
@@ -594,6 +594,46 @@ int fvad_vad_batch_frame_ratios_device(fvad_ctx *ctx, const fvad_vad_batch *b, c
 int fvad_vad_batch_frame_ratios(const fvad_vad_batch *b, const float *chunk_rms, size_t rms_stride, const size_t *n_frames,
                                 const size_t *n_chunks, size_t chunk_size, uint64_t first_sample, float *ratio,
                                 size_t ratio_stride);
+
+/* The short-term and channel-ratio averages from tables (context option vad_avgs: "ring", the default, or "table";
+ * FVAD_VAD_AVGS).  VADMachine.run pushes min_volume and the frame's volume ratio into its two short rings whatever it decides, so
+ * the two averages of a frame depend on the stream, the frame, the band and the ring length alone: every config with the same
+ * short key (band, short-term ring length) has the same short-term average, every config with the same ratio key (size index,
+ * channel-ratio ring length) the same ratio average.
+ * - "table": before a part's (or a one-shot run's) first launch two kernels (csrc/kernels_vadavgs.hip) fill the min_volume row of
+ *   every (band, stream) and, one lane per (key, stream, frame), the two averages -- the reference's chain over the ring's slots
+ *   in slot order, with its bits (csrc/vad_avgs.h) -- and the machines read two f64 per frame instead of pushing two rings.  A
+ *   launch uses the tables when vad_avgs is "table", vad_chain is "coop" and the part's tables plus min_volume rows fit in
+ *   vad_avgs_max_bytes (context option, default 16 GiB); otherwise it pushes the rings.  Either way every result and the state
+ *   between parts have the same bits: a table launch leaves the rings and their cursors as the ring form would have, so the
+ *   forms may alternate between the parts of a run, and fvad_vad_batch_retain_configs works unchanged.  A relaunch of a part
+ *   (after its segment room grew, or the one-shot run's second launch) reads the tables filled before the first.
+ * - The tables belong to the batch's device part state: they only grow, are freed with it and count in
+ *   fvad_vad_batch_device_bytes.
+ * - fvad_vad_batch_avgs_form: *form = 0 before the batch's first device launch, 1 when its last device launch pushed the rings, 2
+ *   when it read the tables (counted when the launch is queued, as fvad_vad_batch_chain_form).  fvad_vad_batch_avgs_bytes: the
+ *   bytes of the tables and min_volume rows of that launch's part (0 with the rings).
+ * - fvad_vad_batch_avg_keys: the keys in first-seen config order, as pairs -- st_keys[2 j], st_keys[2 j + 1] = band and ring
+ *   length of short key j, cr_keys likewise size index and ring length -- and each config's keys st_key[c], cr_key[c] (any of
+ *   the four may be NULL to get the counts only; cap: pairs each list has room for, FVAD_ERR_BUFFER_TOO_SMALL below either count).
+ *   Recomputed by fvad_vad_batch_retain_configs for the kept configs.  Needs no device.
+ * - fvad_vad_batch_averages_device (a test tap): only the two table kernels, on the context's stream, for the frames a part call
+ *   with the same d_band, n_frames [n_sizes][n_streams], host chunk_rms, n_chunks, chunk_size and first_sample would run; returns
+ *   when done.  st_avg[(j * n_streams + s) * row_stride + k] = short key j's average after frame k of the part of stream s,
+ *   cr_avg likewise per ratio key (entries past a stream's frames are left alone).  With first_sample > 0 the earlier frames are
+ *   read from b's device part state, which must end at first_sample on this context (FVAD_ERR_INVALID_ARGUMENT otherwise).
+ *   Changes nothing in b.
+ * - fvad_vad_avg_chain: csrc/vad_avgs.h on the host -- out[k] = the average of a ring of `len` slots after frame first_frame + k,
+ *   x[k] that frame's input; with first_frame > 0, ring[i] = slot i as the ring was before frame first_frame (else unused). */
+int fvad_vad_batch_avgs_form(const fvad_vad_batch *b, int *form);
+size_t fvad_vad_batch_avgs_bytes(const fvad_vad_batch *b);
+int fvad_vad_batch_avg_keys(const fvad_vad_batch *b, uint32_t *st_keys, uint32_t *cr_keys, size_t cap, size_t *n_st_keys,
+                            size_t *n_cr_keys, uint32_t *st_key, uint32_t *cr_key);
+int fvad_vad_batch_averages_device(fvad_ctx *ctx, const fvad_vad_batch *b, const float *d_band, size_t band_stride,
+                                   const size_t *n_frames, const float *chunk_rms, size_t rms_stride,
+                                   const size_t *n_chunks, size_t chunk_size, uint64_t first_sample, double *st_avg,
+                                   double *cr_avg, size_t row_stride);
+int fvad_vad_avg_chain(const float *x, size_t n_frames, size_t first_frame, uint32_t len, const float *ring, double *out);
 
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;

@@ -13,7 +13,11 @@ lane and coop in one process, the machines' kernel time by device events, median
 config lane map are left out, the segment room is given from the start (vad_seg_cap) so that every N is one launch, and both
 forms are checked against the host bit for bit.  --vad-chain lane-ab is the same protocol for the lane form alone (for a build
 without the option: the parent's side of an A/B).
-python tools/vad_sweep_time.py [--streams 21] [--hours 2] [--configs 1,8,64,256] [--threads 16] [--vad-chain both --reps 3]"""
+--vad-avgs both is the same A/B protocol for the averages (context option vad_avgs) under vad_chain coop: ring and table
+alternated; besides the machines' kernel it prints the two table kernels' times on their own, table plus machines, the key
+counts and the tables' bytes.  --grid-axes runs it on an axes grid (4 short windows x 8 bands x factors: 32 short keys whatever
+N) instead of make_configs, whose random windows share few keys.
+python tools/vad_sweep_time.py [--streams 21] [--hours 2] [--configs 1,8,64,256] [--threads 16] [--vad-chain both --reps 3] [--vad-avgs both [--grid-axes]]"""
 import argparse
 import os
 import sys
@@ -39,6 +43,17 @@ def make_configs(n, seed):
                     "short_term_speech_avg_sec": float(rng.uniform(0.1, 0.5)),
                     "channel_vol_ratio_avg_sec": float(rng.uniform(0.3, 1.0)),
                     "max_speech_gap_sec": float(rng.uniform(1.0, 3.0)), "min_vad_duration_sec": float(rng.uniform(0.5, 1.0))})
+    return out[:n]
+
+
+def axes_configs(n):
+    """n configs as an axes grid: 4 short windows x 8 bands x (n / 32) factors -- 32 short keys and one ratio key whatever n"""
+    out = []
+    for st in (0.1, 0.2, 0.3, 0.5):
+        for lo, hi in BANDS:
+            for i in range(max(n // 32, 1)):
+                out.append({"speech_min_freq": lo, "speech_max_freq": hi, "short_term_speech_avg_sec": st,
+                            "speech_threshold_factor": 3.0 + 12.0 * i / max(n // 32, 1)})
     return out[:n]
 
 
@@ -72,11 +87,15 @@ def device_corpus(S, hours, seed, chunk=24000, F=1024):
 
 
 def ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf):
-    """--vad-chain both / lane-ab: the machines' kernel per form, alternated in one process (module docstring)"""
-    forms = ["lane", "coop"] if a.vad_chain == "both" else ["lane"]
+    """--vad-chain both / lane-ab: the machines' kernel per form, alternated in one process (module docstring).  --vad-avgs
+    both: under vad_chain coop, the ring form against the table form (context option vad_avgs) -- the machines' kernel, the two
+    table kernels each on their own, and the tables' bytes"""
+    avgs = a.vad_avgs == "both"
+    forms = ["ring", "table"] if avgs else ["lane", "coop"] if a.vad_chain == "both" else ["lane"]
+    grid = a.grid_axes
     dev = audio.device
     for N in [int(x) for x in a.configs.split(",")]:
-        cfgs = make_configs(N, a.seed + N)
+        cfgs = axes_configs(N) if grid else make_configs(N, a.seed + N)
         sw = fv.VadSweep(S, cfgs)
         bins, _ = sw.bands()
         band = torch.empty((len(bins), S, nf), dtype=torch.float32, device=dev)
@@ -84,24 +103,39 @@ def ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf):
         torch.cuda.synchronize()
         ctx.set_option("vad_seg_cap", str(min(nf // 4 + 1, a.seg_cap)))   # room from the start: one launch whatever N
         ms = {f: [] for f in forms}
+        tab = {"vad_minvol": [], "vad_avgs": []}
+        tab_bytes = 0
         kept = {}
         try:
+            if avgs:
+                ctx.set_option("vad_chain", "coop")
             for rep in range(-1, a.reps):   # (-1: the warm-up, not kept)
                 for f in forms:
-                    if a.vad_chain == "both":
+                    if avgs:
+                        ctx.set_option("vad_avgs", f)
+                    elif a.vad_chain == "both":
                         ctx.set_option("vad_chain", f)
                     ctx.kernel_times()
                     sw.run_device(ctx, band.data_ptr(), nf, [nf] * S, rms, [n_chunks] * S)
-                    t = ctx.kernel_times().get("vad_machines", float("nan"))
+                    kt = ctx.kernel_times()
+                    t = kt.get("vad_machines", float("nan"))
+                    if avgs:
+                        assert sw.avgs_form() == (2 if f == "table" else 1), (f, sw.avgs_form())
                     if rep >= 0:
                         ms[f].append(t)
+                        if f == "table":
+                            for k in tab:
+                                tab[k].append(kt.get(k, float("nan")))
+                            tab_bytes = sw.avgs_bytes()
                     if rep == 0 and not a.no_host:
                         kept[f] = ([sw.segments(c) for c in range(N)], [sw.audit(s, c) for s in range(S) for c in range(N)],
                                    [sw.lazy_stats(s, c) for s in range(S) for c in range(N)])
         finally:
             ctx.set_option("vad_seg_cap", None)
-            if a.vad_chain == "both":
+            if a.vad_chain == "both" or avgs:
                 ctx.set_option("vad_chain", None)
+            if avgs:
+                ctx.set_option("vad_avgs", None)
         host_txt = "host not run"
         if not a.no_host:
             hb = band.cpu().numpy()
@@ -118,6 +152,12 @@ def ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf):
             hs.close()
             del hb
         txt = " | ".join(f"{f} {np.median(ms[f]):8.2f} ms [{min(ms[f]):8.2f} - {max(ms[f]):8.2f}]" for f in forms)
+        if avgs:
+            st_keys, cr_keys, _, _ = sw.avg_keys()
+            both = [m + x + y for m, x, y in zip(ms["table"], tab["vad_minvol"], tab["vad_avgs"])]
+            txt += (f" | table kernels: min_volume {np.median(tab['vad_minvol']):7.2f} ms, averages {np.median(tab['vad_avgs']):8.2f} ms"
+                    f" | table + machines {np.median(both):8.2f} ms [{min(both):8.2f} - {max(both):8.2f}] | {len(st_keys)} short keys, "
+                    f"{len(cr_keys)} ratio keys, tables {tab_bytes / 2**30:.2f} GiB")
         print(f"N={N:4d} ({(S * N + 63) // 64} wavefronts): GPU VAD kernel {txt} | {host_txt}", flush=True)
         sw.close()
         del band
@@ -131,6 +171,9 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--vad-chain", default=None, choices=("lane", "coop", "both", "lane-ab"))
+    ap.add_argument("--vad-avgs", default=None, choices=("both",),
+                    help="alternate vad_avgs ring and table under vad_chain coop: the machines' kernel, the two table kernels, the tables' bytes")
+    ap.add_argument("--grid-axes", action="store_true", help="with --vad-avgs both: an axes grid (shared keys) instead of make_configs")
     ap.add_argument("--reps", type=int, default=3, help="with --vad-chain both / lane-ab: timed rounds per form")
     ap.add_argument("--seg-cap", type=int, default=2048, help="with --vad-chain both / lane-ab: segment room per machine")
     ap.add_argument("--no-host", action="store_true", help="with --vad-chain both / lane-ab: skip the host run (and the bit check)")
@@ -148,7 +191,7 @@ def main():
     d_den = audio.data_ptr()
     print(f"{S} streams x {a.hours:g} h ({nf} frames each), mono, fft 1024", flush=True)
     ctx.enable_timing(True)
-    if a.vad_chain in ("both", "lane-ab"):
+    if a.vad_chain in ("both", "lane-ab") or a.vad_avgs == "both":
         ab_forms(a, fv, ctx, torch, audio, rms, n_chunks, S, L, nf)
         ctx.close()
         return
