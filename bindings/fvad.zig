@@ -341,6 +341,14 @@ pub extern "c" fn fvad_vad_batch_avgs_form(b: *const VadBatch, form: *c_int) c_i
 pub extern "c" fn fvad_vad_batch_avgs_bytes(b: *const VadBatch) usize;
 /// the tables' keys as pairs (band, ring length) / (size index, ring length) in first-seen config order, and each config's keys
 pub extern "c" fn fvad_vad_batch_avg_keys(b: *const VadBatch, st_keys: ?[*]u32, cr_keys: ?[*]u32, cap: usize, n_st_keys: *usize, n_cr_keys: *usize, st_key: ?[*]u32, cr_key: ?[*]u32) c_int;
+/// shared triggers (context option vad_trigger, see fvad.h): the keys, the form of the last device launch, the bits' size, the
+/// launches of the two stages, the bits themselves (a test tap) and the finishing walk on the host
+pub extern "c" fn fvad_vad_batch_trigger_keys(b: *const VadBatch, key_of: ?[*]u32, cap: usize, n_keys: *usize, rep: ?[*]u32) c_int;
+pub extern "c" fn fvad_vad_batch_trigger_form(b: *const VadBatch, form: *c_int) c_int;
+pub extern "c" fn fvad_vad_batch_trigger_bytes(b: *const VadBatch) usize;
+pub extern "c" fn fvad_vad_batch_trigger_launches(b: *const VadBatch, machines: ?*u64, finish: ?*u64) c_int;
+pub extern "c" fn fvad_vad_batch_trigger_bits(ctx: *Ctx, b: *const VadBatch, out: [*]u64, row_stride: usize) c_int;
+pub extern "c" fn fvad_vad_finish_bits(cfg: *const VadConfig, sample_rate: usize, fft_size: usize, words: ?[*]const u64, ratios: ?[*]const f32, n_frames: usize, first_sample: u64, state: [*]u64, segs: ?[*]SpeechSegment, seg_cap: usize, n_segs: *usize) c_int;
 /// a test tap: only the two table kernels of a part; [key][stream][row_stride] f64 each
 pub extern "c" fn fvad_vad_batch_averages_device(ctx: *Ctx, b: *const VadBatch, d_band: ?[*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: ?[*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize, first_sample: u64, st_avg: ?[*]f64, cr_avg: ?[*]f64, row_stride: usize) c_int;
 pub extern "c" fn fvad_vad_avg_chain(x: ?[*]const f32, n_frames: usize, first_frame: usize, len: u32, ring: ?[*]const f32, out: ?[*]f64) c_int;

@@ -256,6 +256,13 @@ SIGNATURES = {
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fvad_vad_batch_averages_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64,
                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), sz]),
+    "fvad_vad_batch_trigger_keys": (C.c_int, [vp, C.POINTER(C.c_uint32), sz, C.POINTER(sz), C.POINTER(C.c_uint32)]),
+    "fvad_vad_batch_trigger_form": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "fvad_vad_batch_trigger_bytes": (sz, [vp]),
+    "fvad_vad_batch_trigger_launches": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_vad_batch_trigger_bits": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), sz]),
+    "fvad_vad_finish_bits": (C.c_int, [C.POINTER(VadConfig), sz, sz, C.POINTER(C.c_uint64), c_float_p, sz, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.POINTER(SpeechSegment), sz, C.POINTER(sz)]),
     "fvad_vad_avg_chain": (C.c_int, [c_float_p, sz, sz, C.c_uint32, c_float_p, C.POINTER(C.c_double)]),
     "fvad_ra_create": (C.c_int, [sz, C.c_int, C.c_double, C.POINTER(vp)]),
     "fvad_ra_destroy": (None, [vp]),
@@ -1112,6 +1119,38 @@ class VadSweep:
         return ([(st[2 * j], st[2 * j + 1]) for j in range(n_st.value)], [(cr[2 * j], cr[2 * j + 1]) for j in range(n_cr.value)],
                 list(st_key), list(cr_key))
 
+    def trigger_keys(self):
+        """fvad_vad_batch_trigger_keys -> (key_of [config], rep [key]): each config's trigger key in first-seen config order and
+        each key's first config (context option vad_trigger)"""
+        n = sz()
+        key_of, rep = (C.c_uint32 * self.n_configs)(), (C.c_uint32 * self.n_configs)()
+        check(lib().fvad_vad_batch_trigger_keys(self.h, key_of, self.n_configs, C.byref(n), rep), "fvad_vad_batch_trigger_keys")
+        return list(key_of), [rep[k] for k in range(n.value)]
+
+    def trigger_form(self):
+        """fvad_vad_batch_trigger_form: 0 before a device launch, 1 per-config machines, 2 shared triggers"""
+        f = C.c_int()
+        check(lib().fvad_vad_batch_trigger_form(self.h, C.byref(f)), "fvad_vad_batch_trigger_form")
+        return f.value
+
+    def trigger_bytes(self):
+        """fvad_vad_batch_trigger_bytes: the bits of the last shared part"""
+        return lib().fvad_vad_batch_trigger_bytes(self.h)
+
+    def trigger_launches(self):
+        """fvad_vad_batch_trigger_launches -> (emitting machines' launches, finishing launches), cumulative, shared form"""
+        m, f = C.c_uint64(), C.c_uint64()
+        check(lib().fvad_vad_batch_trigger_launches(self.h, C.byref(m), C.byref(f)), "fvad_vad_batch_trigger_launches")
+        return m.value, f.value
+
+    def trigger_bits(self, ctx, n_words):
+        """fvad_vad_batch_trigger_bits (a test tap): the last shared part's bits -> uint64 [key][stream][n_words]"""
+        n_keys = len(self.trigger_keys()[1])
+        out = np.zeros((n_keys, self.n_streams, int(n_words)), np.uint64)
+        ctx._ck(lib().fvad_vad_batch_trigger_bits(ctx.h, self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_words)),
+                "fvad_vad_batch_trigger_bits")
+        return out
+
     def averages_device(self, ctx, d_band, band_stride, n_frames, chunk_rms, n_chunks, first_sample=0, chunk_size=24000):
         """fvad_vad_batch_averages_device (a test tap): only the averages' table kernels for the frames a part call with these
         arguments would run (n_frames [stream] with one size, else [size][stream]; chunk_rms on the host) -> dict(st float64
@@ -1230,6 +1269,21 @@ class VadSweepSized(VadSweep):
     run = VadSweep.run_sized
     run_device = VadSweep.run_device_sized
     run_device_part = VadSweep.run_device_part_sized
+
+
+def finish_bits(config, words, ratios, n_frames, first_sample=0, state=None, sample_rate=48000, fft_size=1024, seg_cap=None):
+    """fvad_vad_finish_bits: the finishing walk (csrc/vad_finish.h) of one config (overrides dict) over a part's bits (uint64
+    words) and frame ratios (float32) -> (segments as SpeechSegment list, state uint64 [6]); state None = a fresh machine"""
+    words = np.ascontiguousarray(words, np.uint64)
+    ratios = np.ascontiguousarray(ratios, np.float32)
+    st = np.zeros(6, np.uint64) if state is None else np.array(state, np.uint64)
+    cap = int(n_frames) // 4 + 1 if seg_cap is None else int(seg_cap)
+    segs = (SpeechSegment * max(cap, 1))()
+    n = sz()
+    check(lib().fvad_vad_finish_bits(_config_array([config]), sample_rate, fft_size, words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     fptr(ratios), int(n_frames), int(first_sample), st.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     segs, cap, C.byref(n)), "fvad_vad_finish_bits")
+    return [segs[i] for i in range(n.value)], st
 
 
 def avg_chain(x, length, first_frame=0, ring=None):

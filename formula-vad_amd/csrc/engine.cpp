@@ -219,6 +219,17 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
         if (!unset && (!end || *end || v[0] == '-')) return FVAD_ERR_INVALID_ARGUMENT;
         tn.vad_avgs_max_bytes = c;
     }
+    else if (name == "vad_trigger") { // device VAD sweeps: "config" (a machine per config) or "shared" (a trigger machine per key, kernels_vadfinish.hip per config); same bits
+        if (unset || v == "config") tn.vad_trigger = 0;
+        else if (v == "shared") tn.vad_trigger = 1;
+        else return FVAD_ERR_INVALID_ARGUMENT;
+    }
+    else if (name == "vad_trigger_max_bytes") { // the bits' budget per part; unset = 4 GiB
+        char* end = nullptr;
+        const unsigned long long c = unset ? def.vad_trigger_max_bytes : strtoull(v.c_str(), &end, 10);
+        if (!unset && (!end || *end || v[0] == '-')) return FVAD_ERR_INVALID_ARGUMENT;
+        tn.vad_trigger_max_bytes = c;
+    }
     else if (name == "vad_seg_cap") { // fvad_vad_batch_run_device's first segment room per machine (tests: the overflow path); unset = 512 MB over all machines
         long c = 0;
         if (!unset && (!to_long(c) || c < 1 || c > (1L << 24))) return FVAD_ERR_INVALID_ARGUMENT;
@@ -319,7 +330,7 @@ int fvad_ctx_create(int device, fvad_ctx** out)
     if (get_vad_plan(ctx, kVadFft, &pl) != FVAD_OK) { fvad_ctx_destroy(ctx); return FVAD_ERR_HIP; }
     // the tuning variables FVAD_<NAME> are read here, once; a bad value fails the creation rather than being ignored
     for (const char* opt : {"nn_math", "gru_kernel", "gemm_kernel", "h3_waves", "max_chunks", "copy_threads", "ws_spin_ticks",
-                            "no_pipeline", "run_groups", "trace_run", "trace_kernels", "reproducible", "vad_chain", "vad_avgs"}) {
+                            "no_pipeline", "run_groups", "trace_run", "trace_kernels", "reproducible", "vad_chain", "vad_avgs", "vad_trigger"}) {
         std::string env = std::string("FVAD_") + opt;
         for (char& c : env) c = (char)toupper((unsigned char)c);
         const char* v = getenv(env.c_str());

@@ -11,6 +11,7 @@
 
 #include "host_vad.h"
 #include "internal.h"
+#include "vad_finish.h"
 
 using namespace fvad;
 
@@ -52,6 +53,7 @@ struct PartFlight {
     size_t most = 0;               // segments no machine can exceed
     bool keep = false;
     uint64_t first_sample = 0;
+    bool finish = false;           // the shared-trigger form's second stage: launch_part launches the finishing kernel
 };
 
 // The device state of a batch run in parts (fvad_vad_batch_run_device_part), held by the batch between the parts: the machines
@@ -89,16 +91,41 @@ struct DevParts {
     float* mv = nullptr;
     double *st_tab = nullptr, *cr_tab = nullptr;
     size_t mv_cap = 0, st_cap = 0, cr_cap = 0; // in elements
-    size_t table_bytes() const { return mv_cap * sizeof(float) + (st_cap + cr_cap) * sizeof(double); }
+    size_t table_bytes() const { return mv_cap * sizeof(float) + (st_cap + cr_cap) * sizeof(double) + bits_cap * sizeof(unsigned long long); }
+    // The shared-trigger form (context option vad_trigger "shared").  `shared`: this is the state of a batch whose parts run the
+    // finishing kernel over its trigger batch's bits (fvad_vad_batch::trig): no rings, trig_of / finish_order on the device.
+    // `emit`: this is a trigger batch's state; bits: the last part's words (they only grow), trig_h / nf_h: their layout and the
+    // part's frame counts [n_sizes][n_streams] (fvad_vad_batch_trigger_bits)
+    bool shared = false, emit = false;
+    uint32_t* trig_of = nullptr;
+    int* finish_order = nullptr;
+    unsigned long long* bits = nullptr;
+    size_t bits_cap = 0;
+    std::vector<VadTrigKey> trig_h;
+    std::vector<size_t> nf_h;
     ~DevParts()
     {
         hipSetDevice(device);
         if (flight) hipDeviceSynchronize(); // (a batch destroyed with its part in flight: the kernels read what is freed below)
+        free_machines();
+        hipFree(bits);
+    }
+    // everything but the bits and their layout (a trigger batch after a one-shot run: no part can follow, fvad_vad_batch_trigger_bits
+    // still reads the bits); nothing of this state may be in flight
+    void free_machines()
+    {
         for (void* p : ptrs) hipFree(p);
         hipFree(segs);
         hipFree(mv);
         hipFree(st_tab);
         hipFree(cr_tab);
+        ptrs.clear();
+        bytes = 0;
+        cfg = nullptr; lt = nullptr; rings = nullptr; state = nullptr; count = nullptr; audit = nullptr; stats = nullptr; paused = nullptr;
+        segs = nullptr; sizes = nullptr; size_of = nullptr; lane_config = nullptr; trig_of = nullptr; finish_order = nullptr;
+        mv = nullptr; st_tab = nullptr; cr_tab = nullptr;
+        seg_cap = mv_cap = st_cap = cr_cap = 0;
+        next_sample = UINT64_MAX;
     }
     template <class T> hipError_t grow(T** p, size_t* cap, size_t need) // (the contents are not kept; nothing in flight reads them)
     {
@@ -258,6 +285,12 @@ int fvad_engine_band_sums_device(fvad_ctx* ctx, const float* d_denoised, size_t 
 } // extern "C"
 
 namespace {
+
+// (the shared-trigger form, below: whether a run's first launch takes it; emit: the part of a trigger batch)
+bool trigger_wanted(const fvad_ctx* ctx, const fvad_vad_batch* b, const std::vector<size_t>& P);
+int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                    const float* chunk_rms, const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                    uint64_t first_sample, bool async, bool emit = false);
 
 // the configs' derived constants at their own frame sizes, with their bands; the rings' largest lengths
 int derive_cfgs(fvad_ctx* ctx, const fvad_vad_batch* b, std::vector<VadMachineCfg>* hc, uint32_t* lt_max, uint32_t* st_max, uint32_t* cr_max)
@@ -436,7 +469,27 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
     if (band_stride < max_nf) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "band_stride < frames of a stream");
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
+    if (trigger_wanted(ctx, b, P)) {
+        // The shared-trigger form: the run is one fresh part of that form -- the emitting machines once, then the finishing kernel,
+        // which alone runs again when a machine's segment room overflows -- scored on the device where the part left its segments
+        if (const int rc = run_device_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, nullptr, rms_stride, n_chunks, chunk_size, 0, false))
+            return rc;
+        const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+        if (b->has_refs) {
+            std::vector<fvad_single_stats> scores;
+            if (const int rc = score_on_device(ctx, b, dp->segs, dp->count, dp->seg_cap, &scores)) return rc;
+            b->scores = std::move(scores);
+        }
+        b->scored = b->has_refs;
+        b->dev_parts.reset(); // a run in parts cannot go on after this one; of the trigger batch only the bits stay (fvad_vad_batch_trigger_bits)
+        if (b->trig && b->trig->dev_parts) static_cast<DevParts*>(b->trig->dev_parts.get())->free_machines();
+        b->next_sample = 0;
+        return FVAD_OK;
+    }
     b->dev_parts.reset(); // a run in parts cannot go on after this one
+    b->trig.reset();
+    b->trig_of.clear();
+    b->trigger_bytes = 0;
 
     // ---- host: the frame ratios (one row per (size, stream)) and the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
@@ -553,6 +606,7 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
         if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
         b->chain_form = a.coop ? 2 : 1;
         b->avgs_form = a.coop && a.table ? 2 : 1;
+        b->trigger_form = 1;
         FVAD_HIP(ctx, hipMemcpyAsync(count.data(), d_count, (size_t)M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         FVAD_HIP(ctx, hipStreamSynchronize(st));
         const size_t most = *std::max_element(count.begin(), count.end());
@@ -619,14 +673,25 @@ int launch_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
     pf.a.segs = dp->segs;
     pf.a.seg_cap = (uint32_t)dp->seg_cap;
     pf.a.coop = ctx->tune.vad_chain; // (context option vad_chain, read at every launch: the bits do not depend on it)
+    if (pf.a.emit) pf.a.coop = 1;    // (a shared run stays shared: only the cooperative form emits)
     FVAD_HIP(ctx, hipMemsetAsync(dp->paused, 0, sizeof(unsigned), pf.st));
     const bool timed = pf.st == ctx->stream;
+    if (pf.finish) { // the shared form's second stage, alone: the bits are the part's, whatever room the segments needed
+        if (timed) time_begin(ctx, "vad_finish");
+        const int e = fvad_launch_vad_finish(pf.a, pf.st);
+        if (timed) time_end(ctx);
+        if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_finish");
+        b->trig_finish_launches += 1;
+        b->trigger_form = 2;
+        return FVAD_OK;
+    }
     if (timed) time_begin(ctx, "vad_machines");
     const int e = fvad_launch_vad_machines(pf.a, pf.st);
     if (timed) time_end(ctx);
     if (e != (int)hipSuccess) return hip_fail(ctx, (hipError_t)e, "fvad_launch_vad_machines");
     b->chain_form = pf.a.coop ? 2 : 1;
     b->avgs_form = pf.a.coop && pf.a.table ? 2 : 1; // (a part that filled its tables and is relaunched as the lane form runs the rings)
+    b->trigger_form = 1; // (on a trigger batch: its own machines; the batch that owns it reports 2)
     return FVAD_OK;
 }
 
@@ -639,6 +704,14 @@ int finish_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
     const bool keep = pf.keep;
     const uint64_t first_sample = pf.first_sample;
     const std::vector<size_t>& P = pf.P;
+    // the shared form: the trigger batch's part first (it never pauses); its inputs -- the ratios and frame counts the finishing
+    // kernel reads too -- live until this part is done
+    std::unique_ptr<PartFlight> trig_flight;
+    if (pf.finish) {
+        DevParts* tdp = static_cast<DevParts*>(b->trig->dev_parts.get());
+        trig_flight = std::move(tdp->flight);
+        if (const int rc = finish_part(ctx, b->trig.get(), tdp, *trig_flight)) return rc;
+    }
     for (;;) {
         unsigned paused = 0;
         FVAD_HIP(ctx, hipMemcpyAsync(&paused, dp->paused, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -658,8 +731,20 @@ int finish_part(fvad_ctx* ctx, fvad_vad_batch* b, DevParts* dp, PartFlight& pf)
     std::vector<fvad_vad_audit> audits(M);
     std::vector<unsigned long long> stats(2 * M);
     FVAD_HIP(ctx, hipMemcpyAsync(count.data(), dp->count, M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), dp->audit, M * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
-    FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), dp->stats, 2 * M * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (pf.finish) { // a config's audit and lazy statistics are its trigger machine's: decide sees only trigger state
+        const fvad_vad_batch* tb = b->trig.get();
+        const size_t K = tb->cfgs.size();
+        for (size_t s = 0; s < S; ++s)
+            for (size_t c = 0; c < NC; ++c) {
+                const size_t m = s * NC + c, t = s * K + b->trig_of[c];
+                audits[m] = tb->audits[t];
+                stats[2 * m] = tb->exact_evals[t];
+                stats[2 * m + 1] = tb->lazy_pushes[t];
+            }
+    } else {
+        FVAD_HIP(ctx, hipMemcpyAsync(audits.data(), dp->audit, M * sizeof(fvad_vad_audit), hipMemcpyDeviceToHost, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(stats.data(), dp->stats, 2 * M * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    }
     FVAD_HIP(ctx, hipStreamSynchronize(st));
     std::vector<fvad_speech_segment> segs;
     size_t used = 0; // the part's segments: machine m's new ones at the start of its row
@@ -737,13 +822,54 @@ int device_ratios(fvad_ctx* ctx, const fvad_vad_batch* b, const uint64_t* d_size
     return FVAD_OK;
 }
 
+// The bits of a part of trigger batch tb (VadMachinesArgs.bits): per size [stream][word][machines of that size], the sizes one
+// after the other; keys[c]: machine c's place, words: 64-bit words in all.  P[g]: the part's longest row of size g
+struct TrigPlan {
+    std::vector<VadTrigKey> keys;
+    size_t words = 0;
+};
+TrigPlan plan_trigger(const fvad_vad_batch* tb, const std::vector<size_t>& P)
+{
+    const size_t S = tb->n_streams, G = tb->sizes.size(), K = tb->cfgs.size();
+    TrigPlan tp;
+    tp.keys.resize(K);
+    std::vector<uint32_t> nk(G, 0);
+    for (size_t c = 0; c < K; ++c) tp.keys[c].base = (long)nk[tb->size_of[c]]++; // (its index among its size's machines)
+    std::vector<long> first(G, 0);
+    for (size_t g = 0; g < G; ++g) { first[g] = (long)tp.words; tp.words += S * finish_words(P[g]) * nk[g]; }
+    for (size_t c = 0; c < K; ++c) {
+        const uint32_t g = tb->size_of[c];
+        tp.keys[c].base += first[g];
+        tp.keys[c].nk = nk[g];
+        tp.keys[c].words = (uint32_t)finish_words(P[g]);
+    }
+    return tp;
+}
+// the bytes the bits of a part of b's keys would take (the guard of the shared form: computed from shapes)
+size_t trigger_bits_bytes(const fvad_vad_batch* b, const std::vector<size_t>& P)
+{
+    std::vector<size_t> nk(b->sizes.size(), 0);
+    for (const uint32_t c : b->trig_rep) nk[b->size_of[c]] += 1;
+    size_t words = 0;
+    for (size_t g = 0; g < nk.size(); ++g) words += b->n_streams * finish_words(P[g]) * nk[g];
+    return words * sizeof(unsigned long long);
+}
+bool trigger_wanted(const fvad_ctx* ctx, const fvad_vad_batch* b, const std::vector<size_t>& P)
+{
+    return ctx->tune.vad_trigger == 1 && ctx->tune.vad_chain == 1 && trigger_bits_bytes(b, P) <= ctx->tune.vad_trigger_max_bytes;
+}
+
+int run_shared_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                    const float* chunk_rms, const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                    uint64_t first_sample, bool async, const std::vector<size_t>& P, hipStream_t st);
+
 // one part of every machine of b (fvad_vad_batch_run_device_part, _run_device_part_sized and _run_device_part_async); n_frames
 // [n_sizes][n_streams], frames from sample first_sample on.  The blocking calls give the chunk RMS on the host (chunk_rms) and
 // return with the results; the async call gives it on the device (d_chunk_rms) and returns once the part is queued on the
 // context's second stream, behind everything the main stream holds at that moment.
 int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
                     const float* chunk_rms, const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
-                    uint64_t first_sample, bool async)
+                    uint64_t first_sample, bool async, bool emit)
 {
     const size_t S = b->n_streams, NC = b->cfgs.size(), C = b->n_channels, G = b->sizes.size();
     const size_t M = S * NC;
@@ -770,6 +896,15 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     hipStream_t st = ctx->stream;
     if (async)
         if (const int rc = part_stream(ctx, &st)) return rc;
+    // The form of the run is chosen at its first part and kept: shared when the option asks for it, the launch is cooperative and
+    // the part's bits fit the budget; a later part goes on in the form the state has
+    if (!emit) {
+        const bool shared = first_sample == 0 ? trigger_wanted(ctx, b, P) : dp->shared;
+        if (shared)
+            return run_shared_part(ctx, b, d_band, band_stride, n_frames, chunk_rms, d_chunk_rms, rms_stride, n_chunks, chunk_size, first_sample,
+                                   async, P, st);
+        if (first_sample == 0) { b->trig.reset(); b->trig_of.clear(); b->trigger_bytes = 0; }
+    }
 
     // ---- host: the part's frame ratios (the blocking calls) and, for a fresh run, the configs' derived constants
     const size_t ratio_stride = std::max<size_t>(max_nf, 1);
@@ -790,6 +925,7 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         dp->cr_max = cr_max;
         dp->by_config = ctx->tune.vad_lane_map;
         dp->size_order = ctx->tune.vad_size_order;
+        dp->emit = emit;
         // as fvad_vad_batch_run_device: the long-term rings in whole blocks of 64 slots plus one; the short-term and
         // channel-ratio rings in LDS when a workgroup's fit in 48 KB (their home between launches is `rings` either way)
         dp->rings_in_lds = (size_t)(st_max + cr_max) * 64 * sizeof(float) <= 48 * 1024;
@@ -861,7 +997,7 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
                                                   : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / M);
     const size_t first_room = std::min(max_nf / 4 + 1, room);
-    if (dp->seg_cap < first_room) {
+    if (!emit && dp->seg_cap < first_room) { // (emitting machines close no segment: no room)
         const int rc = grow_segs(ctx, dp, M, first_room, st);
         if (rc) return rc;
     }
@@ -915,8 +1051,198 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
             b->avgs_bytes = pl.bytes();
         }
     }
+    if (emit) { // the bits of the part: per size [stream][word][machines of that size]
+        const TrigPlan tp = plan_trigger(b, P);
+        VadTrigKey* d_tk = nullptr;
+        FVAD_HIP(ctx, pf.scratch.alloc(&d_tk, NC));
+        FVAD_HIP(ctx, hipMemcpyAsync(d_tk, tp.keys.data(), NC * sizeof(VadTrigKey), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, dp->grow(&dp->bits, &dp->bits_cap, tp.words));
+        dp->trig_h = tp.keys;
+        dp->nf_h.assign(n_frames, n_frames + G * S);
+        a.emit = 1;
+        a.bits = dp->bits;
+        a.trig_keys = d_tk;
+    }
     if (const int rc = launch_part(ctx, b, dp, pf)) return rc;
+    if (emit) { // (the batch that owns this one finishes it: finish_part)
+        dp->flight = std::move(flight);
+        return FVAD_OK;
+    }
     if (async) { // fvad_vad_batch_part_wait goes on from here
+        dp->flight = std::move(flight);
+        b->part_in_flight = true;
+        return FVAD_OK;
+    }
+    return finish_part(ctx, b, dp, pf);
+}
+
+// The trigger batch of b (fvad_vad_batch::trig): an ordinary sweep batch of each key's first config, with b's own sizes and bands.
+// The first config of a band, of a size or of an averages key is also the first config of its trigger key, so the representatives
+// alone give b's sizes, bands and averages keys in b's order: the band blocks and frame counts b's caller passes are the trigger
+// batch's too.  That is checked here, not assumed.
+int make_trigger_batch(fvad_ctx* ctx, const fvad_vad_batch* b, std::unique_ptr<fvad_vad_batch>* out)
+{
+    std::unique_ptr<fvad_vad_batch> tb(new (std::nothrow) fvad_vad_batch());
+    if (!tb) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "trigger batch");
+    const size_t K = b->trig_rep.size(), S = b->n_streams;
+    tb->sample_rate = b->sample_rate; tb->n_channels = b->n_channels; tb->fft_size = b->fft_size; tb->n_streams = S;
+    tb->sizes = b->sizes;
+    tb->bins = b->bins;
+    tb->size_of_band = b->size_of_band;
+    for (const uint32_t c : b->trig_rep) {
+        tb->cfgs.push_back(b->cfgs[c]);
+        tb->band_of.push_back(b->band_of[c]);
+        tb->size_of.push_back(b->size_of[c]);
+    }
+    tb->segs.resize(S * K);
+    tb->audits.resize(S * K);
+    tb->exact_evals.assign(S * K, 0);
+    tb->lazy_pushes.assign(S * K, 0);
+    tb->keep_segments = false;
+    if (derive_avg_keys(tb.get()) || derive_trigger_keys(tb.get())) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "ring length out of range");
+    bool spans = tb->st_keys == b->st_keys && tb->cr_keys == b->cr_keys && tb->trig_rep.size() == K;
+    std::vector<uint8_t> band_seen(b->bins.size() / 2, 0), size_seen(b->sizes.size(), 0);
+    for (size_t k = 0; k < K; ++k) { band_seen[tb->band_of[k]] = 1; size_seen[tb->size_of[k]] = 1; }
+    for (const uint8_t x : band_seen) spans = spans && x;
+    for (const uint8_t x : size_seen) spans = spans && x;
+    if (!spans) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "internal: trigger keys: the representatives do not span the batch's bands, sizes and averages keys");
+    *out = std::move(tb);
+    return FVAD_OK;
+}
+
+// a stream's lanes in the finishing kernel: configs of one trigger machine side by side (first-seen order within it)
+std::vector<int> finish_order(const std::vector<uint32_t>& trig_of)
+{
+    std::vector<int> o(trig_of.size());
+    for (size_t c = 0; c < o.size(); ++c) o[c] = (int)c;
+    std::stable_sort(o.begin(), o.end(), [&](int x, int y) { return trig_of[(size_t)x] < trig_of[(size_t)y]; });
+    return o;
+}
+
+// the state of a shared batch's finishing machines: what the finishing kernel and the retain gather touch, no rings
+int alloc_shared_state(fvad_ctx* ctx, const fvad_vad_batch* b, const std::vector<uint32_t>& trig_of, DevParts* dp, hipStream_t st)
+{
+    const size_t S = b->n_streams, NC = b->cfgs.size(), G = b->sizes.size(), M = S * NC;
+    std::vector<VadMachineCfg> hc;
+    uint32_t lt_max, st_max, cr_max;
+    if (const int rc = derive_cfgs(ctx, b, &hc, &lt_max, &st_max, &cr_max)) return rc;
+    dp->shared = true;
+    dp->lt_max = dp->st_max = dp->cr_max = 0;
+    FVAD_HIP(ctx, dp->alloc(&dp->cfg, NC));
+    FVAD_HIP(ctx, dp->alloc(&dp->state, M));
+    FVAD_HIP(ctx, dp->alloc(&dp->count, M));
+    FVAD_HIP(ctx, dp->alloc(&dp->audit, M)); // (gathered by a retain with the rest; the results' audits are the trigger batch's)
+    FVAD_HIP(ctx, dp->alloc(&dp->stats, 2 * M));
+    FVAD_HIP(ctx, dp->alloc(&dp->paused, 1));
+    FVAD_HIP(ctx, dp->alloc(&dp->trig_of, NC));
+    FVAD_HIP(ctx, dp->alloc(&dp->finish_order, NC));
+    const std::vector<int> order = finish_order(trig_of);
+    FVAD_HIP(ctx, hipMemcpyAsync(dp->cfg, hc.data(), NC * sizeof(VadMachineCfg), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(dp->trig_of, trig_of.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    FVAD_HIP(ctx, hipMemcpyAsync(dp->finish_order, order.data(), NC * sizeof(int), hipMemcpyHostToDevice, st));
+    if (G > 1) {
+        const std::vector<uint64_t> sizes(b->sizes.begin(), b->sizes.end());
+        FVAD_HIP(ctx, dp->alloc(&dp->sizes, G));
+        FVAD_HIP(ctx, dp->alloc(&dp->size_of, NC));
+        FVAD_HIP(ctx, hipMemcpyAsync(dp->sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(dp->size_of, b->size_of.data(), NC * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    FVAD_HIP(ctx, hipStreamSynchronize(st)); // (the host vectors above end here)
+    return FVAD_OK;
+}
+
+// A part in the shared-trigger form (run_device_part has checked the arguments): the trigger batch's part -- the ratios, the
+// tables if selected and the emitting machines -- and behind it on the same stream the finishing kernel over b's configs.
+int run_shared_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
+                    const float* chunk_rms, const float* d_chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
+                    uint64_t first_sample, bool async, const std::vector<size_t>& P, hipStream_t st)
+{
+    const size_t S = b->n_streams, NC = b->cfgs.size(), G = b->sizes.size(), M = S * NC;
+    const size_t max_nf = *std::max_element(P.begin(), P.end());
+    DevParts* dp = static_cast<DevParts*>(b->dev_parts.get());
+    if (first_sample == 0) {
+        b->dev_parts.reset();
+        b->trig.reset();
+        std::unique_ptr<fvad_vad_batch> tb;
+        if (const int rc = make_trigger_batch(ctx, b, &tb)) return rc;
+        std::unique_ptr<DevParts> fresh(new (std::nothrow) DevParts());
+        if (!fresh) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
+        dp = fresh.get();
+        dp->device = ctx->device;
+        dp->ctx = ctx;
+        if (const int rc = alloc_shared_state(ctx, b, b->trig_key, dp, st)) return rc;
+        dp->ended.assign(S, 0);
+        dp->count_h.assign(M, 0);
+        b->dev_parts = std::unique_ptr<void, DevPartsDeleter>(fresh.release(), DevPartsDeleter{free_dev_parts});
+        b->trig = std::move(tb);
+        b->trig_of = b->trig_key; // (a fresh trigger batch is in first-seen key order)
+        for (auto& v : b->segs) std::vector<fvad_speech_segment>().swap(v);
+    }
+    fvad_vad_batch* tb = b->trig.get();
+    b->machines.clear();
+    const bool keep = b->keep_segments;
+    dp->segs_on_device = dp->segs_on_device && !keep;
+    dp->next_sample = UINT64_MAX;
+
+    // ---- stage one: the trigger batch's part, left in flight on st
+    if (const int rc = run_device_part(ctx, tb, d_band, band_stride, n_frames, chunk_rms, d_chunk_rms, rms_stride, n_chunks, chunk_size,
+                                       first_sample, async, true))
+        return rc;
+    DevParts* tdp = static_cast<DevParts*>(tb->dev_parts.get());
+    const PartFlight& tpf = *tdp->flight;
+    b->trig_machine_launches += 1;
+    b->chain_form = tb->chain_form;
+    b->avgs_form = tb->avgs_form;
+    b->avgs_bytes = tb->avgs_bytes;
+    b->trigger_bytes = tdp->bits_cap ? trigger_bits_bytes(b, P) : 0;
+
+    // ---- stage two: the finishing kernel; segment room as in the per-config form
+    std::unique_ptr<PartFlight> flight(new (std::nothrow) PartFlight());
+    if (!flight) return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part");
+    PartFlight& pf = *flight;
+    pf.st = st;
+    pf.keep = keep;
+    pf.first_sample = first_sample;
+    pf.P = P;
+    pf.n_frames.assign(n_frames, n_frames + G * S);
+    pf.finish = true;
+    size_t most = 0;
+    for (size_t g = 0; g < G; ++g)
+        most = std::max(most, keep ? P[g] / 4 + 1 : (size_t)((first_sample / b->sizes[g] + P[g]) / 4 + 1));
+    pf.most = most;
+    const size_t room = ctx->tune.vad_seg_cap > 0 ? (size_t)ctx->tune.vad_seg_cap
+                                                  : std::max<size_t>(256, (512u << 20) / sizeof(fvad_speech_segment) / M);
+    const size_t first_room = std::min(max_nf / 4 + 1, room);
+    if (dp->seg_cap < first_room)
+        if (const int rc = grow_segs(ctx, dp, M, first_room, st)) return rc;
+    VadMachinesArgs& a = pf.a;
+    a.cfgs = dp->cfg;
+    a.n_configs = (int)NC;
+    a.n_streams = (long)S;
+    a.n_machines = (long)M;
+    a.ratio = tpf.a.ratio;
+    a.ratio_stride = tpf.a.ratio_stride;
+    a.n_frames = tpf.a.n_frames;
+    a.fft_size = b->fft_size;
+    a.seg_count = dp->count;
+    a.resume = 1;
+    a.fresh = first_sample == 0;
+    a.rebase = keep;
+    a.first_frame = first_sample / b->fft_size;
+    a.state = dp->state;
+    a.paused = dp->paused;
+    if (G > 1) {
+        a.sized = 1;
+        a.sizes = dp->sizes;
+        a.size_of = dp->size_of;
+        a.first_sample = first_sample;
+    }
+    a.lane_config = dp->finish_order;
+    a.bits = tdp->bits;
+    a.trig_keys = tpf.a.trig_keys;
+    a.trig_of = dp->trig_of;
+    if (const int rc = launch_part(ctx, b, dp, pf)) return rc;
+    if (async) {
         dp->flight = std::move(flight);
         b->part_in_flight = true;
         return FVAD_OK;
@@ -944,6 +1270,7 @@ int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, co
     std::vector<VadMachineCfg> hc;
     uint32_t lt_max, st_max, cr_max;
     if (const int rc = derive_cfgs(ctx, nb, &hc, &lt_max, &st_max, &cr_max)) return rc;
+    if (dp->shared) lt_max = st_max = cr_max = 0; // (finishing machines have no rings: only the machines' gather runs)
     // (the survivors' rings are never longer than the batch's were: the new rows are a prefix of the old)
     if (lt_max > dp->lt_max || st_max > dp->st_max || cr_max > dp->cr_max) return set_err(ctx, FVAD_ERR_HIP, "retain: rings grew");
     hipSetDevice(ctx->device);
@@ -956,7 +1283,7 @@ int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, co
         np->count_h.resize(M);
         for (size_t s = 0; s < S; ++s)
             for (size_t c = 0; c < n_keep; ++c) np->count_h[s * n_keep + c] = dp->count_h[s * NC + keep[c]];
-        if (G > 1) np->order = lane_order(nb, dp->size_order);
+        if (G > 1 && !dp->shared) np->order = lane_order(nb, dp->size_order);
     } catch (const std::bad_alloc&) {
         return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "device part state");
     }
@@ -970,10 +1297,21 @@ int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, co
     np->rings_in_lds = (size_t)(st_max + cr_max) * 64 * sizeof(float) <= 48 * 1024; // (as run_device_part decides it)
     np->next_sample = dp->next_sample;
     np->segs_on_device = dp->segs_on_device;
-    const size_t lt_rows = ((size_t)lt_max + 63) / 64 * 16 + 16, old_lt_rows = ((size_t)dp->lt_max + 63) / 64 * 16 + 16;
+    np->shared = dp->shared;
+    np->emit = dp->emit;
+    const size_t lt_rows = dp->shared ? 0 : ((size_t)lt_max + 63) / 64 * 16 + 16, old_lt_rows = ((size_t)dp->lt_max + 63) / 64 * 16 + 16;
     FVAD_HIP(ctx, np->alloc(&np->cfg, n_keep));
-    FVAD_HIP(ctx, np->alloc(&np->lt, lt_rows * 4 * M));
-    FVAD_HIP(ctx, np->alloc(&np->rings, (size_t)(st_max + cr_max) * M));
+    if (!dp->shared) {
+        FVAD_HIP(ctx, np->alloc(&np->lt, lt_rows * 4 * M));
+        FVAD_HIP(ctx, np->alloc(&np->rings, (size_t)(st_max + cr_max) * M));
+    } else { // the finishing kernel's maps, by the survivors' trigger machines (nb->trig_of: fvad_vad_batch_retain_configs)
+        const std::vector<int> order = finish_order(nb->trig_of);
+        FVAD_HIP(ctx, np->alloc(&np->trig_of, n_keep));
+        FVAD_HIP(ctx, np->alloc(&np->finish_order, n_keep));
+        FVAD_HIP(ctx, hipMemcpyAsync(np->trig_of, nb->trig_of.data(), n_keep * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipMemcpyAsync(np->finish_order, order.data(), n_keep * sizeof(int), hipMemcpyHostToDevice, st));
+        FVAD_HIP(ctx, hipStreamSynchronize(st));
+    }
     FVAD_HIP(ctx, np->alloc(&np->state, M));
     FVAD_HIP(ctx, np->alloc(&np->count, M));
     FVAD_HIP(ctx, np->alloc(&np->audit, M));
@@ -986,10 +1324,12 @@ int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, co
         const std::vector<uint64_t> sizes(nb->sizes.begin(), nb->sizes.end());
         FVAD_HIP(ctx, np->alloc(&np->sizes, G));
         FVAD_HIP(ctx, np->alloc(&np->size_of, n_keep));
-        FVAD_HIP(ctx, np->alloc(&np->lane_config, n_keep));
         FVAD_HIP(ctx, hipMemcpyAsync(np->sizes, sizes.data(), G * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         FVAD_HIP(ctx, hipMemcpyAsync(np->size_of, nb->size_of.data(), n_keep * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        FVAD_HIP(ctx, hipMemcpyAsync(np->lane_config, np->order.data(), n_keep * sizeof(int), hipMemcpyHostToDevice, st));
+        if (!dp->shared) {
+            FVAD_HIP(ctx, np->alloc(&np->lane_config, n_keep));
+            FVAD_HIP(ctx, hipMemcpyAsync(np->lane_config, np->order.data(), n_keep * sizeof(int), hipMemcpyHostToDevice, st));
+        }
     }
     // new place -> old place, new machine -> old machine (the lane map is the first part's; the lane orders are each batch's own)
     std::vector<long> place_src(M), machine_src(M);
@@ -1014,8 +1354,8 @@ int retain_device(fvad_ctx* ctx, const fvad_vad_batch* b, fvad_vad_batch* nb, co
     a.lt_rows = (long)std::min(lt_rows, old_lt_rows);
     a.rings_src = dp->rings;
     a.rings_dst = np->rings;
-    a.st = (int)st_max;
-    a.cr = (int)cr_max;
+    a.st = dp->shared ? 0 : (int)st_max;
+    a.cr = dp->shared ? 0 : (int)cr_max;
     a.old_st = (int)dp->st_max;
     a.state_src = dp->state;
     a.state_dst = np->state;
@@ -1075,6 +1415,54 @@ int fvad_vad_batch_avgs_form(const fvad_vad_batch* b, int* form)
 }
 
 size_t fvad_vad_batch_avgs_bytes(const fvad_vad_batch* b) { return b ? b->avgs_bytes : 0; }
+
+int fvad_vad_batch_trigger_form(const fvad_vad_batch* b, int* form)
+{
+    if (!b || !form) return FVAD_ERR_INVALID_ARGUMENT;
+    *form = b->trigger_form;
+    return FVAD_OK;
+}
+
+size_t fvad_vad_batch_trigger_bytes(const fvad_vad_batch* b) { return b ? b->trigger_bytes : 0; }
+
+int fvad_vad_batch_trigger_launches(const fvad_vad_batch* b, uint64_t* machines, uint64_t* finish)
+{
+    if (!b) return FVAD_ERR_INVALID_ARGUMENT;
+    if (machines) *machines = b->trig_machine_launches;
+    if (finish) *finish = b->trig_finish_launches;
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_trigger_bits(fvad_ctx* ctx, const fvad_vad_batch* b, uint64_t* out, size_t row_stride)
+{
+    if (!ctx) return no_ctx();
+    if (!b || !out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->part_in_flight) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "a device part is in flight: fvad_vad_batch_part_wait first");
+    const fvad_vad_batch* tb = b->trig.get();
+    const DevParts* tdp = tb ? static_cast<const DevParts*>(tb->dev_parts.get()) : nullptr;
+    if (!tdp || tdp->trig_h.empty() || b->trig_of.size() != b->cfgs.size())
+        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no bits: the last device launch was not a shared part");
+    if (tdp->ctx != ctx) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "the parts ran on another context");
+    const size_t S = b->n_streams, K = b->trig_rep.size();
+    size_t total = 0;
+    for (const VadTrigKey& k : tdp->trig_h) total = std::max(total, (size_t)k.base + ((S * k.words ? S * k.words - 1 : 0)) * k.nk + 1);
+    for (const VadTrigKey& k : tdp->trig_h)
+        if (k.words > row_stride) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "row_stride < words of a stream");
+    total = std::min(total, tdp->bits_cap);
+    hipSetDevice(ctx->device);
+    std::vector<unsigned long long> h(total);
+    if (total) FVAD_HIP(ctx, hipMemcpy(h.data(), tdp->bits, total * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < K; ++j) {
+        const size_t t = b->trig_of[b->trig_rep[j]];
+        const VadTrigKey& k = tdp->trig_h[t];
+        for (size_t s = 0; s < S; ++s) {
+            const size_t nw = finish_words(tdp->nf_h[(size_t)tb->size_of[t] * S + s]); // (the stream's own words: the rest were not written)
+            for (size_t w = 0; w < row_stride; ++w)
+                out[(j * S + s) * row_stride + w] = w < nw ? h[(size_t)k.base + (s * k.words + w) * k.nk] : 0;
+        }
+    }
+    return FVAD_OK;
+}
 
 int fvad_vad_batch_averages_device(fvad_ctx* ctx, const fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
                                    const float* chunk_rms, size_t rms_stride, const size_t* n_chunks, size_t chunk_size,
@@ -1155,9 +1543,11 @@ int fvad_vad_batch_averages_device(fvad_ctx* ctx, const fvad_vad_batch* b, const
 
 size_t fvad_vad_batch_device_bytes(const fvad_vad_batch* b)
 {
-    const DevParts* dp = b ? static_cast<const DevParts*>(b->dev_parts.get()) : nullptr;
-    if (!dp) return 0;
-    return dp->bytes + dp->table_bytes() + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment);
+    if (!b) return 0;
+    const DevParts* dp = static_cast<const DevParts*>(b->dev_parts.get());
+    const size_t own = dp ? dp->bytes + dp->table_bytes() + dp->seg_cap * b->n_streams * b->cfgs.size() * sizeof(fvad_speech_segment) : 0;
+    // a shared run: the trigger machines and their bits (after a one-shot run the bits alone are still held)
+    return own + (b->trig ? fvad_vad_batch_device_bytes(b->trig.get()) : 0);
 }
 
 int fvad_vad_batch_run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t band_stride, const size_t* n_frames,
@@ -1274,8 +1664,37 @@ int fvad_vad_batch_retain_configs(fvad_ctx* ctx, fvad_vad_batch* b, const uint32
     if (!nb) return fail(FVAD_ERR_ALLOC_FAILED, "retain");
     if (const int rc = retain_stage(b, keep, n_keep, nb.get()))
         return fail(rc, rc == FVAD_ERR_ALLOC_FAILED ? "retain" : "keep: a strictly increasing list of config indices, not empty");
-    if (dp)
+    if (dp && dp->shared) {
+        // A shared run: the trigger machines are retained to the survivors' keys with the same gather (their rings shrink as
+        // ever), then the finishing state config by config.  The trigger batch keeps its own order (the old one, thinned out):
+        // the keys fvad_vad_batch_trigger_keys reports are first-seen over the survivors, trig_of maps between the two.
+        const fvad_vad_batch* tb = b->trig.get();
+        std::vector<uint32_t> keep_t;
+        for (size_t c = 0; c < n_keep; ++c) keep_t.push_back(b->trig_of[keep[c]]);
+        std::sort(keep_t.begin(), keep_t.end());
+        keep_t.erase(std::unique(keep_t.begin(), keep_t.end()), keep_t.end());
+        std::unique_ptr<fvad_vad_batch> ntb(new (std::nothrow) fvad_vad_batch());
+        if (!ntb) return fail(FVAD_ERR_ALLOC_FAILED, "retain");
+        if (const int rc = retain_stage(tb, keep_t.data(), keep_t.size(), ntb.get())) return fail(rc, "retain: trigger batch");
+        // the trigger batch numbers sizes and bands as the batch does (the caller's band blocks and frame counts are the batch's)
+        nb->trig_of.resize(n_keep);
+        ntb->sizes = nb->sizes;
+        ntb->bins = nb->bins;
+        ntb->size_of_band = nb->size_of_band;
+        ntb->fft_size = nb->fft_size;
+        for (size_t c = 0; c < n_keep; ++c) {
+            const size_t t = (size_t)(std::lower_bound(keep_t.begin(), keep_t.end(), b->trig_of[keep[c]]) - keep_t.begin());
+            nb->trig_of[c] = (uint32_t)t;
+            ntb->band_of[t] = nb->band_of[c];
+            ntb->size_of[t] = nb->size_of[c];
+        }
+        if (derive_avg_keys(ntb.get()) || derive_trigger_keys(ntb.get())) return fail(FVAD_ERR_INVALID_ARGUMENT, "retain: trigger batch");
+        if (const int rc = retain_device(ctx, tb, ntb.get(), keep_t.data(), keep_t.size())) return rc;
         if (const int rc = retain_device(ctx, b, nb.get(), keep, n_keep)) return rc;
+        nb->trig = std::move(ntb);
+    } else if (dp) {
+        if (const int rc = retain_device(ctx, b, nb.get(), keep, n_keep)) return rc;
+    }
     retain_commit(b, keep, n_keep, nb.get());
     return FVAD_OK;
 }

@@ -18,6 +18,7 @@
 
 #include "host_vad.h"
 #include "vad_avgs.h"
+#include "vad_finish.h"
 #include "vad_ratio.h"
 
 namespace fvad {
@@ -382,6 +383,7 @@ int fvad_vad_batch_create(const fvad_vad_config* cfg, size_t sample_rate, size_t
     b->exact_evals.assign(n_streams, 0);
     b->lazy_pushes.assign(n_streams, 0);
     if (const int rc = fvad::derive_avg_keys(b)) { delete b; return rc; }
+    if (const int rc = fvad::derive_trigger_keys(b)) { delete b; return rc; }
     *out = b;
     return FVAD_OK;
 }
@@ -437,6 +439,7 @@ static int make_sweep(const fvad_vad_config* cfgs, size_t n_configs, const std::
     b->exact_evals.assign(n_streams * n_configs, 0);
     b->lazy_pushes.assign(n_streams * n_configs, 0);
     if (const int rc = fvad::derive_avg_keys(b)) { delete b; return rc; }
+    if (const int rc = fvad::derive_trigger_keys(b)) { delete b; return rc; }
     *out = b;
     return FVAD_OK;
 }
@@ -495,6 +498,53 @@ int fvad_vad_batch_avg_keys(const fvad_vad_batch* b, uint32_t* st_keys, uint32_t
     return FVAD_OK;
 }
 
+int fvad_vad_batch_trigger_keys(const fvad_vad_batch* b, uint32_t* key_of, size_t cap, size_t* n_keys, uint32_t* rep)
+{
+    if (!b || !n_keys) return FVAD_ERR_INVALID_ARGUMENT;
+    *n_keys = b->trig_rep.size();
+    if (key_of) memcpy(key_of, b->trig_key.data(), b->trig_key.size() * sizeof(uint32_t));
+    if (!rep) return FVAD_OK; // (the counts, and each config's key, only)
+    if (cap < *n_keys) return FVAD_ERR_BUFFER_TOO_SMALL;
+    memcpy(rep, b->trig_rep.data(), b->trig_rep.size() * sizeof(uint32_t));
+    return FVAD_OK;
+}
+
+int fvad_vad_finish_bits(const fvad_vad_config* cfg, size_t sample_rate, size_t fft_size, const uint64_t* words, const float* ratios,
+                         size_t n_frames, uint64_t first_sample, uint64_t* state, fvad_speech_segment* segs, size_t seg_cap,
+                         size_t* n_segs)
+{
+    if (!cfg || !state || !n_segs || sample_rate == 0 || fft_size == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    if (n_frames && (!words || !ratios)) return FVAD_ERR_INVALID_ARGUMENT;
+    if (seg_cap && !segs) return FVAD_ERR_INVALID_ARGUMENT;
+    fvad::VadMachineCfg k;
+    if (const int rc = fvad::vad_machine_cfg(*cfg, sample_rate, fft_size, &k)) return rc;
+    if (state[0] > 3) return FVAD_ERR_INVALID_ARGUMENT;
+    fvad::VadMachineState m;
+    uint32_t f32s[2];
+    m.state = (int)state[0];
+    m.speech_start = state[1];
+    m.speech_end = state[2];
+    m.ratio_count = state[3];
+    f32s[0] = (uint32_t)state[4];
+    f32s[1] = (uint32_t)(state[4] >> 32);
+    memcpy(&m.ratio_sum, &f32s[0], 4);
+    memcpy(&m.met_cum, &f32s[1], 4);
+    size_t n = 0;
+    fvad::finish_walk(m, k, 0, n_frames, first_sample, fft_size, [&](uint64_t w) { return words[w]; },
+                      [&](uint64_t f) { return ratios[f]; }, [] { return true; },
+                      [&](const fvad_speech_segment& sg) { if (n < seg_cap) segs[n] = sg; ++n; });
+    state[0] = (uint64_t)m.state;
+    state[1] = m.speech_start;
+    state[2] = m.speech_end;
+    state[3] = m.ratio_count;
+    memcpy(&f32s[0], &m.ratio_sum, 4);
+    memcpy(&f32s[1], &m.met_cum, 4);
+    state[4] = (uint64_t)f32s[0] | (uint64_t)f32s[1] << 32;
+    state[5] += n;
+    *n_segs = n;
+    return n > seg_cap ? FVAD_ERR_BUFFER_TOO_SMALL : FVAD_OK;
+}
+
 int fvad_vad_avg_chain(const float* x, size_t n_frames, size_t first_frame, uint32_t len, const float* ring, double* out)
 {
     if (len == 0 || (n_frames && (!x || !out)) || (first_frame && !ring)) return FVAD_ERR_INVALID_ARGUMENT;
@@ -536,6 +586,36 @@ int derive_avg_keys(fvad_vad_batch* b)
         if (const int rc = vad_machine_cfg(b->cfgs[c], b->sample_rate, b->sizes[b->size_of[c]], &k)) return rc;
         b->st_key[c] = find(b->st_keys, b->band_of[c], k.short_len);
         b->cr_key[c] = find(b->cr_keys, b->size_of[c], k.ratio_len);
+    }
+    return FVAD_OK;
+}
+
+int derive_trigger_keys(fvad_vad_batch* b)
+{
+    struct Key {
+        uint32_t size, band, long_len, short_len, ratio_len;
+        int32_t has_init;
+        uint64_t initial, factor, ratio_threshold; // bit patterns
+        bool operator==(const Key& o) const
+        {
+            return size == o.size && band == o.band && long_len == o.long_len && short_len == o.short_len && ratio_len == o.ratio_len &&
+                   has_init == o.has_init && initial == o.initial && factor == o.factor && ratio_threshold == o.ratio_threshold;
+        }
+    };
+    auto bits = [](double d) { uint64_t u; memcpy(&u, &d, 8); return u; };
+    const size_t NC = b->cfgs.size();
+    std::vector<Key> keys;
+    b->trig_key.assign(NC, 0);
+    b->trig_rep.clear();
+    for (size_t c = 0; c < NC; ++c) {
+        VadMachineCfg k;
+        if (const int rc = vad_machine_cfg(b->cfgs[c], b->sample_rate, b->sizes[b->size_of[c]], &k)) return rc;
+        const Key key{b->size_of[c], b->band_of[c], k.long_len, k.short_len, k.ratio_len, k.has_init, bits(k.initial), bits(k.factor),
+                      bits(k.ratio_threshold)};
+        size_t j = 0;
+        while (j < keys.size() && !(keys[j] == key)) ++j;
+        if (j == keys.size()) { keys.push_back(key); b->trig_rep.push_back((uint32_t)c); }
+        b->trig_key[c] = (uint32_t)j;
     }
     return FVAD_OK;
 }
@@ -582,6 +662,7 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
         nb->cfgs.resize(n_keep);
         for (size_t c = 0; c < n_keep; ++c) nb->cfgs[c] = b->cfgs[keep[c]];
         if (const int rc = derive_avg_keys(nb)) return rc; // (the survivors' keys in their first-seen order, as the bands above)
+        if (const int rc = derive_trigger_keys(nb)) return rc;
         // per machine (stream s, config c) -> (s, keep[c])
         const size_t M = S * n_keep;
         nb->segs.resize(M);
@@ -616,6 +697,10 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
     nb->chain_form = b->chain_form;
     nb->avgs_form = b->avgs_form;
     nb->avgs_bytes = b->avgs_bytes;
+    nb->trigger_form = b->trigger_form;
+    nb->trigger_bytes = b->trigger_bytes;
+    nb->trig_machine_launches = b->trig_machine_launches;
+    nb->trig_finish_launches = b->trig_finish_launches;
     return FVAD_OK;
 }
 

@@ -92,6 +92,8 @@ namespace fvad {
 // (b's device part state too, unless nb already holds the compacted one).
 // b's keys of the averages' tables from its configs, bands and sizes (fvad_vad_batch::st_keys ...): at creation and after a retain
 int derive_avg_keys(fvad_vad_batch* b);
+// b's trigger keys (fvad_vad_batch::trig_key, trig_rep) from its configs, bands and sizes: at creation and after a retain
+int derive_trigger_keys(fvad_vad_batch* b);
 int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
 void retain_commit(fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, fvad_vad_batch* nb);
 } // namespace fvad
@@ -128,6 +130,18 @@ struct fvad_vad_batch {
     // avgs_bytes: the tables and min_volume rows of the last launch's part (0 with the rings)
     int avgs_form = 0;
     size_t avgs_bytes = 0;
+    // The trigger keys (context option vad_trigger "shared", vad_finish.h), in first-seen config order: configs share a key when
+    // everything their trigger derives is equal -- size index, band, the three ring lengths, has_init and initial, factor and
+    // ratio_threshold (floating-point members as bit patterns).  trig_key[c]: config c's key; trig_rep[k]: key k's first config.
+    std::vector<uint32_t> trig_key, trig_rep;
+    // A shared run (engine_sweep.cpp): `trig` is an ordinary batch of one config per key whose machines emit bits instead of
+    // finishing (it owns the trigger machines' part state); trig_of[c]: config c's machine in it (its order is private: after a
+    // retain it is the old order, not first-seen).  trigger_form: 0 = no device launch yet, 1 = per-config machines, 2 = shared.
+    std::unique_ptr<fvad_vad_batch> trig;
+    std::vector<uint32_t> trig_of;
+    int trigger_form = 0;
+    size_t trigger_bytes = 0;                           // the bits of the last part
+    uint64_t trig_machine_launches = 0, trig_finish_launches = 0; // cumulative, shared form
     // scoring (host_eval.cpp, kernels_eval.hip): each stream's labels stably sorted by start with the prefix max of their ends
     // (ref_off: n_streams + 1 offsets), one fvad_stat_config per config; the scores of the segments last run, machine by machine
     bool has_refs = false;

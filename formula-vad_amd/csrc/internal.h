@@ -179,6 +179,8 @@ struct Tuning {
     int vad_chain = 0;           // the exact long-term chains of the device VAD machines: 0 = each lane its own ("lane"), 1 = by the wavefront ("coop"); same bits
     int vad_avgs = 0;            // the short-term and channel-ratio averages of the cooperative machines: 0 = each machine pushes its rings ("ring"), 1 = from tables filled frame-parallel before the launch ("table"); same bits
     unsigned long long vad_avgs_max_bytes = 16ull << 30; // a part whose tables and min_volume rows need more runs the ring form (a guard, not a measurement)
+    int vad_trigger = 0;         // device VAD sweeps: 0 = one full machine per (stream, config) ("config"), 1 = one trigger machine per (stream, trigger key) that emits bits and a finishing kernel per config ("shared", needs vad_chain "coop"); same bits
+    unsigned long long vad_trigger_max_bytes = 4ull << 30; // a part whose bits need more runs the per-config machines (a guard computed from shapes, not a measurement)
     int vad_seg_cap = 0;         // fvad_vad_batch_run_device: segments per machine the first launch has room for (more: a second launch); 0 = 512 MB in all
     int ws2_variant = 0;         // timing-only variants of gru_ws2_kernel (tools/ws2_variants.py); 0 in production
     unsigned ws2_waits = 0;      // gru_ws2k's first-poll waits for every launch (layer 1 | layer 2 << 16, 10 ns ticks); 0 = per class:

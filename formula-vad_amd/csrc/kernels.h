@@ -212,6 +212,7 @@ int fvad_launch_irfft_generic(const float* bins, long n_frames, VadFftPlan pl, f
 // ------------------------------------------------------------------ VAD machines of a parameter sweep (kernels_vad.hip)
 namespace fvad { struct VadMachineCfg; struct VadLaneState; } // vad_machine.h
 struct VadAvgKey;
+struct VadTrigKey;
 struct VadMachinesArgs {
     const fvad::VadMachineCfg* cfgs; // [n_configs] (device), with their bands
     int n_configs, n_channels;
@@ -268,8 +269,30 @@ struct VadMachinesArgs {
     const uint32_t* st_key;     // [n_configs] (device): each config's short key, ratio key
     const uint32_t* cr_key;
     const long* tab_frames;     // [n_sizes] (device): the frames of a stream's table rows, per size
+    // ---- the shared-trigger form (context option vad_trigger "shared", vad_finish.h).  emit = 1 (with coop = 1): a machine runs
+    // its trigger as ever but, in place of the state machine, shifts each frame's threshold_met into 64-bit words -- bit k % 64 of
+    // word k / 64 is frame k of the part, the last word's upper bits zero; it writes no segment, never pauses for room and
+    // leaves seg_count 0.  Config c of the launch is trigger machine c: its word w of stream s at
+    // bits[trig_keys[c].base + (s * trig_keys[c].words + w) * trig_keys[c].nk] (per size [stream][word][machines of that size]).
+    // fvad_launch_vad_finish reads the same words: its config c's are those of trigger machine trig_of[c].
+    int emit;
+    unsigned long long* bits;
+    const VadTrigKey* trig_keys; // [trigger machines] (device)
+    const uint32_t* trig_of;            // [n_configs] (device), the finishing launch only
+};
+struct VadTrigKey {
+    long base;       // the machine's word 0 of stream 0
+    uint32_t nk;     // trigger machines of its size (the stride between two words)
+    uint32_t words;  // words of a stream's row at its size
 };
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
+// The finishing kernel of the shared-trigger form (kernels_vadfinish.hip): one lane per (stream, config), a stream's configs in
+// lane_config's order (may be null); it walks the part's bits (vad_finish.h) from state[machine].next_frame on with the resume
+// form's segment protocol (seg_cap, seg_base, rebase, paused, next_frame, seg_count) and reads of `a` only cfgs, the counts,
+// ratio, n_frames, fft_size / first_frame or sizes / size_of / first_sample, segs, seg_count, state, paused, fresh, rebase,
+// lane_config, bits, trig_keys and trig_of.  Of state[machine] only m's state-machine fields, n_segs, seg_base and next_frame
+// are read and written.
+int fvad_launch_vad_finish(const VadMachinesArgs& a, hipStream_t stream); // hipError_t as int
 
 // ------------------------------------------------------------------ the averages' tables of a part (kernels_vadavgs.hip, vad_avgs.h)
 // A short key is (band, short_len), a ratio key (size, ratio_len): every config with the same key has the same average in every

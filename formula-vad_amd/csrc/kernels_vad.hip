@@ -424,7 +424,12 @@ __device__ __forceinline__ void coop_chain(const float* lt_rings, long n_machine
 // two short rings: two f64 loads per frame in place of two chains over LDS.  The form has no short rings (RINGS_LDS is false).
 // A launch that stores state writes into the rings' home and the cursors what the ring form's pushes of the same frames would
 // have left (vad_avgs.h), so every later launch -- of either form, after a retain or not -- goes on from the same bits.
-template <bool RINGS_LDS, bool SIZED, bool TABLE = false>
+//
+// EMIT (context option vad_trigger "shared", a.emit): the trigger alone.  The lane runs fetch, the pushes or table reads, decide,
+// both chain sections and lt_push_flag as ever and, in place of finish_step, shifts threshold_met into a 64-bit word that it
+// stores after its 64th frame (the last, partial word with its upper bits zero): VadMachinesArgs.bits, which the finishing kernel
+// (kernels_vadfinish.hip) walks once per config of the key.  It closes no segment, so it never pauses for room.
+template <bool RINGS_LDS, bool SIZED, bool TABLE = false, bool EMIT = false>
 __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a)
 {
     extern __shared__ double vad_coop_lds[]; // [2][kCoopTile] chain terms, then the short rings [st_max + cr_max][64] (RINGS_LDS)
@@ -553,8 +558,16 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
     long k_end = nf, k = k0;
     bool running = k < nf; // this lane still has frames to run (else it only helps)
     if (running) fetch(k);
+    // EMIT: the word being filled and where this machine's words of the stream go (word w at bits_row[w * bits_nk])
+    unsigned long long word = 0, *bits_row = nullptr;
+    long bits_nk = 0;
+    if constexpr (EMIT) {
+        const VadTrigKey tk = a.trig_keys[c];
+        bits_row = a.bits + tk.base + s * (long)tk.words * (long)tk.nk;
+        bits_nk = (long)tk.nk;
+    }
     while (__ballot(running) != 0) { // (at least one running lane moves a frame on in every pass: bounded by the frame counts)
-        if (running && RESUME && n_segs - seg_base >= a.seg_cap) { k_end = k; *a.paused = 1; running = false; }
+        if (!EMIT && running && RESUME && n_segs - seg_base >= a.seg_cap) { k_end = k; *a.paused = 1; running = false; }
         float mv = 0.0f, rt = 0.0f;
         double st = 0.0, cr = 0.0;
         bool met = false, before = false, redo = false;
@@ -587,17 +600,25 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
         }
         run_chains(after);
         if (running) {
-            const uint64_t frame = first_frame + (uint64_t)k; // (one-shot: first_frame is 0)
-            const uint64_t sample = SIZED ? a.first_sample + (uint64_t)k * F : frame * F;
-            mc.finish_step(mc.cf, sample, met, true, rt, [&](const fvad_speech_segment& sg) {
-                if (n_segs - seg_base < a.seg_cap) seg[n_segs - seg_base] = sg;
-                ++n_segs;
-            });
+            if constexpr (EMIT) {
+                word |= (unsigned long long)met << (k & 63);
+                if ((k & 63) == 63) { bits_row[(k >> 6) * bits_nk] = word; word = 0; }
+            } else {
+                const uint64_t frame = first_frame + (uint64_t)k; // (one-shot: first_frame is 0)
+                const uint64_t sample = SIZED ? a.first_sample + (uint64_t)k * F : frame * F;
+                mc.finish_step(mc.cf, sample, met, true, rt, [&](const fvad_speech_segment& sg) {
+                    if (n_segs - seg_base < a.seg_cap) seg[n_segs - seg_base] = sg;
+                    ++n_segs;
+                });
+            }
             ++k;
             running = k < nf;
         }
     }
     if (!valid) return;
+    if constexpr (EMIT) {
+        if (nf > k0 && (nf & 63)) bits_row[(nf >> 6) * bits_nk] = word; // (the part's last word: the bits past nf are zero)
+    }
     if constexpr (TABLE) {
         if (RESUME) { // the short rings as the ring form's pushes of frames [0, k_end) of the part would have left them
             const uint64_t done = first_frame + (uint64_t)k_end; // pushes since the stream's start
@@ -641,6 +662,21 @@ __global__ __launch_bounds__(64) void vad_machines_coop_kernel(VadMachinesArgs a
 int fvad_launch_vad_machines(const VadMachinesArgs& a, hipStream_t stream)
 {
     if (a.n_machines <= 0) return (int)hipSuccess;
+    if (a.coop && a.emit) { // the shared-trigger form's first stage: the same launches, the machines emit bits
+        const bool lds_rings = !a.table && a.rings_in_lds;
+        const size_t lds = kCoopLdsBytes + (lds_rings ? (size_t)(a.st_max + a.cr_max) * 64 * sizeof(float) : 0);
+        const dim3 grid((unsigned)((a.n_machines + 63) / 64));
+        if (a.table) {
+            if (a.sized) hipLaunchKernelGGL((vad_machines_coop_kernel<false, true, true, true>), grid, dim3(64), lds, stream, a);
+            else hipLaunchKernelGGL((vad_machines_coop_kernel<false, false, true, true>), grid, dim3(64), lds, stream, a);
+        } else if (a.sized) {
+            if (lds_rings) hipLaunchKernelGGL((vad_machines_coop_kernel<true, true, false, true>), grid, dim3(64), lds, stream, a);
+            else hipLaunchKernelGGL((vad_machines_coop_kernel<false, true, false, true>), grid, dim3(64), lds, stream, a);
+        } else if (lds_rings) hipLaunchKernelGGL((vad_machines_coop_kernel<true, false, false, true>), grid, dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((vad_machines_coop_kernel<false, false, false, true>), grid, dim3(64), lds, stream, a);
+        return (int)hipGetLastError();
+    }
+    if (a.emit) return (int)hipErrorInvalidValue; // (only the cooperative form emits)
     if (a.coop && a.table) { // the table form: the two chain tiles, no short rings
         const dim3 grid((unsigned)((a.n_machines + 63) / 64));
         if (a.sized) hipLaunchKernelGGL((vad_machines_coop_kernel<false, true, true>), grid, dim3(64), kCoopLdsBytes, stream, a);

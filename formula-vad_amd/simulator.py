@@ -356,9 +356,17 @@ VAD_CHAINS = ("lane", "coop")
 # vad_avgs: where the device machines' short-term and channel-ratio averages come from (context option vad_avgs, DESIGN section
 # 7.1): each machine's own rings, or tables filled frame-parallel before the launch -- only the cooperative kernel reads those
 VAD_AVGS = ("ring", "table")
+# vad_trigger: one full device machine per (stream, config), or one trigger machine per (stream, trigger key) that emits bits and
+# a finishing kernel per config (context option vad_trigger) -- only the cooperative kernel emits
+VAD_TRIGGERS = ("config", "shared")
 
 
-def _check_vad_chain(vad_chain, vad_avgs=None):
+def _check_vad_chain(vad_chain, vad_avgs=None, vad_trigger=None):
+    if vad_trigger is not None and vad_trigger not in VAD_TRIGGERS:
+        raise ValueError(f"vad_trigger: {vad_trigger!r} (one of {VAD_TRIGGERS})")
+    if vad_trigger == "shared" and vad_chain != "coop":
+        raise ValueError(f"vad_trigger='shared' needs vad_chain='coop' (vad_chain: {vad_chain!r}): only the cooperative form of the "
+                         "machines' kernel emits the triggers' bits")
     if vad_chain is not None and vad_chain not in VAD_CHAINS:
         raise ValueError(f"vad_chain: {vad_chain!r} (one of {VAD_CHAINS})")
     if vad_avgs is not None and vad_avgs not in VAD_AVGS:
@@ -368,10 +376,17 @@ def _check_vad_chain(vad_chain, vad_avgs=None):
                          "machines' kernel reads the averages' tables")
 
 
+_MAX_TIMES = ("avgs_form", "avgs_bytes", "trigger_form", "trigger_bytes", "trigger_keys")   # forms and sizes: the largest, not a sum
+
+
 def _note_avgs(times, b):
     """times' avgs_form / avgs_bytes after a device launch of b: the largest form (2: a launch read the tables) and table size"""
     times["avgs_form"] = max(times.get("avgs_form", 0), b.avgs_form())
     times["avgs_bytes"] = max(times.get("avgs_bytes", 0), b.avgs_bytes())
+    # the shared-trigger form of the launch: the largest form (2: shared), the bits' size, the keys of the configs it ran
+    times["trigger_form"] = max(times.get("trigger_form", 0), b.trigger_form())
+    times["trigger_bytes"] = max(times.get("trigger_bytes", 0), b.trigger_bytes())
+    times["trigger_keys"] = max(times.get("trigger_keys", 0), len(b.trigger_keys()[1]))
 
 
 def _auto_vad_on(n_configs, vad_chain):
@@ -382,8 +397,8 @@ class _VadChain:
     """The context options vad_chain and vad_avgs on the contexts of one run_sweep / run_grid call: set on entry (nothing for
     one that is None), and on a caller's context (owned False) put back on exit to what it was set to before"""
 
-    def __init__(self, vad_chain, vad_avgs=None):
-        self.values, self.restore = {"vad_chain": vad_chain, "vad_avgs": vad_avgs}, []
+    def __init__(self, vad_chain, vad_avgs=None, vad_trigger=None):
+        self.values, self.restore = {"vad_chain": vad_chain, "vad_avgs": vad_avgs, "vad_trigger": vad_trigger}, []
 
     def apply(self, ctx, owned):
         if ctx is None:
@@ -526,7 +541,7 @@ def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_ch
 
 
 def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16,
-              vad_chain=None, vad_avgs=None):
+              vad_chain=None, vad_avgs=None, vad_trigger=None):
     """Scores many VADMachine configurations over one denoising pass of a plan's instances.
 
     configs: list of VADMachine.Config override dicts (vad_overrides' form); default: the plan's vad_machine_config followed by its
@@ -546,7 +561,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     Returns dict(configs, rows [one aggregate dict per config], aggregates [AggregateStats], segments [config][instance],
     stats [config][instance], avgs_form, avgs_bytes [VadSweep.avgs_form() / avgs_bytes(): the largest over the device
     launches; 0 with host machines]); prints one table row per config and writes the rows as JSON to json_path if given."""
-    _check_vad_chain(vad_chain, vad_avgs)
+    _check_vad_chain(vad_chain, vad_avgs, vad_trigger)
     plan = load_plan(plan_path)
     if configs is None:
         configs = [plan["vad_machine_config"]] + list(plan["alt_vad_machine_configs"])
@@ -559,7 +574,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     own_ctx = ctx is None
     if own_ctx:
         ctx = _make_ctx(plan, 0, synth_seed)
-    chain = _VadChain(vad_chain, vad_avgs)
+    chain = _VadChain(vad_chain, vad_avgs, vad_trigger)
     loaded = [_read_instance(i) for i in plan["instances"]]
     audio = [a for a, _ in loaded]
     refs = [r for _, r in loaded]
@@ -617,10 +632,13 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
         all_stats.append(stats)
         rows.append(dict(config=c, **_agg_row(agg)))
     result = {"configs": configs, "rows": rows, "aggregates": aggs, "segments": segs, "stats": all_stats,
-              "avgs_form": times.get("avgs_form", 0), "avgs_bytes": times.get("avgs_bytes", 0)}
+              "avgs_form": times.get("avgs_form", 0), "avgs_bytes": times.get("avgs_bytes", 0),
+              "trigger_form": times.get("trigger_form", 0), "trigger_bytes": times.get("trigger_bytes", 0),
+              "trigger_keys": times.get("trigger_keys", 0)}
     if json_path:
         with open(json_path, "w") as f:
             json.dump({"configs": configs, "rows": rows, "avgs_form": result["avgs_form"], "avgs_bytes": result["avgs_bytes"],
+                       "trigger_form": result["trigger_form"], "trigger_bytes": result["trigger_bytes"], "trigger_keys": result["trigger_keys"],
                        "segments": [[[list(map(float, x)) for x in inst] for inst in per] for per in segs]}, f, indent=1)
     if out is not None:
         out.write("| config |      P |     TP |     FP |     FN |    TPR |    PPV |    FNR |    FDR | F-score |    FMI |\n")
@@ -767,7 +785,7 @@ def _check_grid_contexts(ctx, devices):
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
              n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False, vad_chain=None,
-             vad_avgs=None):
+             vad_avgs=None, vad_trigger=None):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -837,7 +855,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     vad_chain and vad_avgs as in run_sweep: set on every context the call makes, and on the caller's contexts for the call;
     times gains avgs_form and avgs_bytes (the largest over the shares' device launches: 2 once a launch read the tables, and
     the largest part's tables in bytes), which the JSON file carries too."""
-    _check_vad_chain(vad_chain, vad_avgs)
+    _check_vad_chain(vad_chain, vad_avgs, vad_trigger)
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
@@ -918,7 +936,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     stop = threading.Event()   # set when a worker fails: the others stop at their next slice or rung
     errs, breaks = [], []
     t_all = time.perf_counter()
-    chain = _VadChain(vad_chain, vad_avgs)
+    chain = _VadChain(vad_chain, vad_avgs, vad_trigger)
 
     def work(s):
         t0 = time.perf_counter()
@@ -959,9 +977,9 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     times = {}
     for s in workers:
         for k, v in share_times[s]["times"].items():
-            times[k] = max(times.get(k, 0), v) if k in ("avgs_form", "avgs_bytes") else times.get(k, 0.0) + v
-    times.setdefault("avgs_form", 0)
-    times.setdefault("avgs_bytes", 0)
+            times[k] = max(times.get(k, 0), v) if k in _MAX_TIMES else times.get(k, 0.0) + v
+    for k in _MAX_TIMES:
+        times.setdefault(k, 0)
     n_slices = sum(share_out[s][0] for s in workers)
     bytes_per_share = [share_out[s][1] for s in range(len(shares))]
     dev_bytes = max((b for b in bytes_per_share if b is not None), default=None)
@@ -979,7 +997,8 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     elapsed = time.perf_counter() - t_all
     if json_path:
         with open(json_path, "w") as f:
-            doc = {"grid": grid, "configs": configs, "rows": rows, "avgs_form": times["avgs_form"], "avgs_bytes": times["avgs_bytes"]}
+            doc = {"grid": grid, "configs": configs, "rows": rows, "avgs_form": times["avgs_form"], "avgs_bytes": times["avgs_bytes"],
+                   "trigger_form": times["trigger_form"], "trigger_bytes": times["trigger_bytes"], "trigger_keys": times["trigger_keys"]}
             if halving is not None:
                 doc.update(survivors=halving["survivors"], rung_times=halving["rungs_run"])
             json.dump(doc, f, indent=1)
@@ -1557,6 +1576,10 @@ def arg_parser():
                     help="with --sweep / --sweep-grid and --vad-chain coop: the device VAD machines' short-term and channel-ratio "
                          "averages from their own rings (the default) or from tables filled frame-parallel before the launch "
                          "(context option vad_avgs); same results")
+    ap.add_argument("--vad-trigger", default=None, choices=VAD_TRIGGERS,
+                    help="with --sweep / --sweep-grid and --vad-chain coop: one device VAD machine per config (the default) or one "
+                         "trigger machine per distinct trigger and a finishing kernel per config (context option vad_trigger); "
+                         "same results")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -1569,10 +1592,11 @@ def main(argv=None):
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
-                 overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs)
+                 overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs, vad_trigger=a.vad_trigger)
         return
     if a.sweep:
-        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs)
+        run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs,
+                  vad_trigger=a.vad_trigger)
         return
     run_plan(a.input, synth_seed=a.synth_seed, devices=devices or [0])
 

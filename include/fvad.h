@@ -330,7 +330,7 @@ const char *fvad_ctx_last_nn_path(const fvad_ctx *ctx);
  * fvad_engine_run's host-buffer pipeline in sixteenths of the call, at most seven, instead of the planned ones) | "trace_run" (a timeline of every fvad_engine_run call on stderr) | "trace_kernels" |
  * "ws_spin_ticks" | "ws2_variant" (diagnostic bit mask; the timing-only bits exist in the diagnostics build alone) |
  * "ws2_waits" | "ws2_calibrate" (below) | "k4_plain_loads" (the band FFT's staging path of unaligned frames) | "gru_lat_tiles" ("1" | "2" | "3": row tiles per
- * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_avgs" ("ring" | "table") | "vad_avgs_max_bytes" (see fvad_vad_batch_avgs_form) | "vad_chain" ("lane" | "coop": the exact
+ * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_trigger" ("config" | "shared") | "vad_trigger_max_bytes" (see fvad_vad_batch_trigger_form) | "vad_avgs" ("ring" | "table") | "vad_avgs_max_bytes" (see fvad_vad_batch_avgs_form) | "vad_chain" ("lane" | "coop": the exact
  * long-term chains of the device VAD machines lane by lane or by the whole wavefront, see fvad_vad_batch_run_device_part; same bits);
  * value NULL or ""
  * restores the default.  The environment variables FVAD_<NAME> are read ONCE, by
@@ -634,6 +634,49 @@ int fvad_vad_batch_averages_device(fvad_ctx *ctx, const fvad_vad_batch *b, const
                                    const size_t *n_chunks, size_t chunk_size, uint64_t first_sample, double *st_avg,
                                    double *cr_avg, size_t row_stride);
 int fvad_vad_avg_chain(const float *x, size_t n_frames, size_t first_frame, uint32_t len, const float *ring, double *out);
+
+/* Shared triggers (context option vad_trigger: "config", the default, or "shared"; FVAD_VAD_TRIGGER read at context creation).
+ * The expensive part of a VAD machine is its trigger: the three rolling averages, the lazily exact long-term chain and the
+ * decision.  It does not read min_consecutive_sec_to_open, max_speech_gap_sec or min_vad_duration_sec, and nothing flows back
+ * into it from the state machine (VADMachine.zig:166-178 against :186-309).  Configs whose derived trigger quantities are all
+ * equal -- size index, band block, the three ring lengths (slot counts), has_init and initial, factor and ratio_threshold, the
+ * floating-point members compared as bit patterns -- share a trigger key.
+ * - "shared": a device sweep runs one trigger machine per (stream, key) -- the cooperative kernel of csrc/kernels_vad.hip in a
+ *   form that emits each frame's threshold_met as one bit, ring or table averages, sized or not -- and then one lane per
+ *   (stream, config) of csrc/kernels_vadfinish.hip, which walks those bits through the state machine, the segment statistics and
+ *   the closing of segments (csrc/vad_finish.h; while a machine is closed it jumps from set bit to set bit).  Segments, counts,
+ *   audits, lazy statistics and device scores have the bits of the per-config machines.  When segment room overflows only the
+ *   finishing kernel runs again, over the same bits; the one-shot calls run as one such part.
+ * - A run takes the shared form at its first launch when vad_trigger is "shared", vad_chain is "coop" and the part's bits fit in
+ *   vad_trigger_max_bytes (context option, default 4 GiB: a guard computed from shapes -- S streams x keys x frames / 8 bytes);
+ *   otherwise the per-config machines run.  The form is fixed for the run: a run that began in one form continues in it, and
+ *   changing the option takes effect at the next run's first part.  Part state is not converted between the forms.
+ * - The bits and the finishing state belong to the batch's device part state: they only grow, are freed with it and count in
+ *   fvad_vad_batch_device_bytes.  After a one-shot call, which no part can follow, only the bits are still held (for
+ *   fvad_vad_batch_trigger_bits) until the next run or the batch's end, and device_bytes reports them.
+ *   fvad_vad_batch_retain_configs in a shared run retains the trigger machines to the surviving
+ *   keys and then compacts the per-config state; the keys reported afterwards are first-seen over the survivors.
+ * - fvad_vad_batch_trigger_keys: key_of[c] = config c's key (first-seen config order), rep[k] = key k's first config; either may
+ *   be NULL (counts only); cap: keys rep has room for, FVAD_ERR_BUFFER_TOO_SMALL below *n_keys.  Needs no device; recomputed by
+ *   fvad_vad_batch_retain_configs.
+ * - fvad_vad_batch_trigger_form: 0 before a device launch, 1 per-config machines, 2 shared.  fvad_vad_batch_trigger_bytes: the
+ *   bits of the last shared part.  fvad_vad_batch_trigger_launches: cumulative launches of the emitting machines and of the
+ *   finishing kernel in the shared form (either may be NULL).
+ * - fvad_vad_batch_trigger_bits (a test tap): the last shared part's bits, out[(k * n_streams + s) * row_stride + w] = word w of
+ *   key k, stream s: bit f % 64 of word f / 64 is frame f of the part; bits and words past a stream's frames are zero.
+ * - fvad_vad_finish_bits: the walk of csrc/vad_finish.h on the host, for one config at one frame size over one part's words and
+ *   frame ratios (frame k at sample first_sample + k * fft_size; bits past n_frames are not read).  state: 6 words, in/out, all
+ *   zero = a fresh machine (state, speech_start, speech_end, ratio_count, ratio_sum | met_cum << 32 as f32 bits, segments closed
+ *   so far).  Segments closed in this call go to segs (room seg_cap), *n_segs counts them; FVAD_ERR_BUFFER_TOO_SMALL when they
+ *   did not all fit (the state has moved on all the same). */
+int fvad_vad_batch_trigger_keys(const fvad_vad_batch *b, uint32_t *key_of, size_t cap, size_t *n_keys, uint32_t *rep);
+int fvad_vad_batch_trigger_form(const fvad_vad_batch *b, int *form);
+size_t fvad_vad_batch_trigger_bytes(const fvad_vad_batch *b);
+int fvad_vad_batch_trigger_launches(const fvad_vad_batch *b, uint64_t *machines, uint64_t *finish);
+int fvad_vad_batch_trigger_bits(fvad_ctx *ctx, const fvad_vad_batch *b, uint64_t *out, size_t row_stride);
+int fvad_vad_finish_bits(const fvad_vad_config *cfg, size_t sample_rate, size_t fft_size, const uint64_t *words,
+                         const float *ratios, size_t n_frames, uint64_t first_sample, uint64_t *state,
+                         fvad_speech_segment *segs, size_t seg_cap, size_t *n_segs);
 
 /* RollingAverage.zig:11-56 exposed for parity tests */
 typedef struct fvad_rolling_average fvad_rolling_average;
