@@ -175,6 +175,12 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
         long c = 0;
         if (!unset && (!to_long(c) || c < 1 || c > 3)) return FVAD_ERR_INVALID_ARGUMENT;
         tn.gru_lat_tiles = (int)c;
+    } else if (name == "nn_trim") { // the large-batch f32 family's skipped work (nn_dispatch.cpp run_nn); same bits whatever the value
+        if (unset || v == "all") tn.nn_trim = 3;
+        else if (v == "tiles") tn.nn_trim = 1;
+        else if (v == "rows") tn.nn_trim = 2;
+        else if (v == "none") tn.nn_trim = 0;
+        else return FVAD_ERR_INVALID_ARGUMENT;
     } else if (name == "k4_plain_loads") { if (!to_bool(tn.k4_plain_loads)) return FVAD_ERR_INVALID_ARGUMENT; }
     else if (name == "no_pipeline") { if (!to_bool(tn.no_pipeline)) return FVAD_ERR_INVALID_ARGUMENT; }
     else if (name == "trace_run") { if (!to_bool(tn.trace_run)) return FVAD_ERR_INVALID_ARGUMENT; }

@@ -182,6 +182,9 @@ struct Tuning {
     int vad_trigger = 0;         // device VAD sweeps: 0 = one full machine per (stream, config) ("config"), 1 = one trigger machine per (stream, trigger key) that emits bits and a finishing kernel per config ("shared", needs vad_chain "coop"); same bits
     unsigned long long vad_trigger_max_bytes = 4ull << 30; // a part whose bits need more runs the per-config machines (a guard computed from shapes, not a measurement)
     int vad_seg_cap = 0;         // fvad_vad_batch_run_device: segments per machine the first launch has room for (more: a second launch); 0 = 512 MB in all
+    int nn_trim = 3;             // large-batch f32 family, bit 1: fc2 / fc3 issue no MFMAs for their all-padding 39th column tile; bit 2: layer 1's
+                                 // input projection computes rows 4..53 of a chunk and the recurrence takes rows 0..3 from the previous chunk
+                                 // ("all" | "tiles" | "rows" | "none"; same bits whatever the value)
     int ws2_variant = 0;         // timing-only variants of gru_ws2_kernel (tools/ws2_variants.py); 0 in production
     unsigned ws2_waits = 0;      // gru_ws2k's first-poll waits for every launch (layer 1 | layer 2 << 16, 10 ns ticks); 0 = per class:
     unsigned ws2_waits_cal[4] = {0, 0, 0, 0}; // what ws2_calibrate measured for fvad_gru_ws2_wait_class 1..3; 0 = the kernel's built-in table
@@ -262,7 +265,13 @@ int get_vad_plan(fvad_ctx* ctx, size_t n, VadFftPlan* out, bool force_generic = 
 bool fvad_fft_size_ok(size_t n); // even, 4 .. kVadFftMax
 // NSNet2 on ws.feat -> ws.gains for n_chunks sequences of T rows; gains rows skip..T-1 only
 // n_real: the sequences of the padded batch that are real (the tail layers of a small launch run on their rows only); 0 = all
-int run_nn(fvad_ctx* ctx, long n_chunks_pad, int T, int skip, long n_real = 0);
+// How a launch's sequences are the chunks of the engine's lanes: descs[s].first for s < n_real; chunks_per_lane > 0: every
+// one of the n_lanes lanes has that many chunks in this launch (lane-contiguous), 0: they differ.
+struct NnLanes {
+    const ChunkDesc* descs = nullptr;
+    long n_lanes = 0, chunks_per_lane = 0;
+};
+int run_nn(fvad_ctx* ctx, long n_chunks_pad, int T, int skip, long n_real = 0, const NnLanes* lanes = nullptr);
 int calibrate_ws2_waits(fvad_ctx* ctx);
 
 struct LaneJob {

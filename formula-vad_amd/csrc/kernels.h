@@ -94,9 +94,16 @@ int fvad_launch_panel_gemm_s_rows(const float* A, int lda, const float* Wfrag, c
 int fvad_launch_panel_gemm_s(const float* A, int lda, const float* Wfrag, const float* bias, float* C, int ldc,
                              long rows, int nt, int n_blocks, int S_steps, int act, int map_T, int map_skip,
                              hipStream_t stream, int n_valid_tiles = 0, const unsigned* guard = nullptr);
+// rows of A and C of a panel_gemm3 launch: compact row i = qd * per + tt (qd < n_q) is row qd * T + skip + tt of both; the
+// rows that pad the launch to whole 256-row panels repeat rows of qd = n_q - 1
+struct Gemm3RowMap {
+    int per = 0, T = 0, skip = 0;
+    long n_q = 0;
+};
 int fvad_launch_panel_gemm3(const float* A, int lda, const float* Wfrag, const float* bias, float* C,
                             int ldc, long rows, int nt, int n_blocks, int S_steps, int K, int act,
-                            int n_valid_tiles, int map_T, int map_skip, int n_wg, hipStream_t stream);
+                            int n_valid_tiles, int map_T, int map_skip, int n_wg, hipStream_t stream, bool trim_tiles = false,
+                            const Gemm3RowMap* cmap = nullptr);
 // f16x3 form (kernels_h3.hip): Wfrag from pack_panel_h3, K = true reduction length, sx / sw = input / weight scales.
 // in_ts: A in the split tiled layout (a_ld = K-steps per row tile) or row-major f32 [sequence][seq_T][a_ld];
 // out: 0 row-major f32, 1 tiled f32 (c_ld unit tiles per row tile), 2 split tiled (c_ld K-steps, scaled by out_sx);
@@ -161,7 +168,8 @@ unsigned fvad_gru_ws2_builtin_waits(int wait_class, bool local_layer1 = false); 
 int fvad_launch_gru_gen(const float* gi, int gi_ld, const float* R2frag, const float* bR, float* hout, int h_ld,
                         long n_seq_pad, int T, int J, hipStream_t stream);
 int fvad_launch_gru_rec3(const float* gi, const float* R2frag, const float* bR, float* hout,
-                         long n_seq_pad, int T, int waves, hipStream_t stream, float* hs3 = nullptr);
+                         long n_seq_pad, int T, int waves, hipStream_t stream, float* hs3 = nullptr,
+                         const ChunkDesc* first_of = nullptr, long n_real = 0);
 // bf16x3 form of the dense layers (kernels_b3.hip): Wfrag from pack_panel_b3, K = true reduction length.
 // in_ts: A in the three-piece tiled layout TS3 (a_ld = K-steps per row tile) or row-major f32 [sequence][seq_T][a_ld];
 // out: 0 row-major f32 [sequence][seq_T][c_ld], 2 TS3 (c_ld K-steps per row tile); row_tiles = output row tiles of 16 rows

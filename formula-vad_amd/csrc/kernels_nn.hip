@@ -385,11 +385,20 @@ template <int N> __device__ __forceinline__ void lds_wait(f32x4& dst)
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(dst) : "n"(N));
 }
 
-template <int NT, int RT, int ACT, int SP, int WAVES>
+//
+// Rows (row_map_T > 0): compact row i = qd * row_map_per + tt addresses row qd * row_map_T + row_map_skip + tt of A (fc2: rows
+// 4..53 of every 54-row sequence, per = 50).  CMAP: the same map on the rows of C, with qd clamped to row_map_qmax so that the
+// rows that pad a launch to whole panels repeat a real row (the same value stored twice to the same place).  Only layer 1's
+// input projection uses it: rows 4..53 of every chunk (per 50, T 54, skip 4), and rows 0..3 of the first chunk of every lane
+// (per 4, T 54 x chunks per lane, skip 0) -- the other chunks' rows 0..3 are their predecessor's rows 50..53, bit for bit.
+// TRIMT: a column block whose last tile lies past n_mfma_tiles (fc2 / fc3: 38 tiles of 16 in three blocks of 13) issues no
+// MFMAs for it; the tile's fragment reads, waits and DMA stay as they are (their counts are compile-time constants).
+template <int NT, int RT, int ACT, int SP, int WAVES, bool CMAP = false, bool TRIMT = false>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void panel_gemm3_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ Wfrag,
     const float* __restrict__ bias, float* __restrict__ C, int ldc, int S_steps, int n_blocks,
-    int n_valid_tiles, int row_map_T, int row_map_skip, unsigned n_items, int tail_r)
+    int n_valid_tiles, int row_map_T, int row_map_skip, unsigned n_items, int tail_r, int row_map_per,
+    unsigned row_map_qmax, int n_mfma_tiles)
 {
     __shared__ __attribute__((aligned(16))) float slab[2][NT * SP * 256];
     __shared__ __attribute__((aligned(16))) float sbias[2][NT * 16];
@@ -403,16 +412,18 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
     const int P = (S_steps + SP - 1) / SP;
     constexpr int WAITN = (NT - 1 < 15) ? NT - 1 : 15; // lgkmcnt is a 4-bit field
 
+    auto map_row = [&](unsigned row) -> unsigned {
+        if (row_map_T <= 0) return row;
+        const unsigned per = (unsigned)row_map_per;
+        unsigned qd = row / per;
+        const unsigned tt = row - qd * per;
+        if (CMAP) qd = qd < row_map_qmax ? qd : row_map_qmax;
+        return qd * (unsigned)row_map_T + (unsigned)row_map_skip + tt;
+    };
     auto a_pointer = [&](unsigned item, int rt) -> const float* {
         const unsigned panel = item / (unsigned)n_blocks;
         const unsigned row = ((panel * WAVES + wave) * RT + rt) * 16 + m;
-        unsigned a_row = row;
-        if (row_map_T > 0) {
-            const unsigned per = (unsigned)(row_map_T - row_map_skip);
-            const unsigned qd = row / per;
-            a_row = qd * (unsigned)row_map_T + (unsigned)row_map_skip + (row - qd * per);
-        }
-        return A + (size_t)a_row * (size_t)lda + 4 * q;
+        return A + (size_t)map_row(row) * (size_t)lda + 4 * q;
     };
     // every wavefront issues the same, compile-time number of DMA instructions per phase (surplus
     // ones repeat the last block), which lets the compiler count them in its vmcnt bookkeeping
@@ -475,6 +486,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
         const float* a_nextitem[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) a_nextitem[rt] = has_next ? a_pointer(next_item, rt) : a_ptr[rt];
+        // wavefront-uniform: this item's last tile is all padding columns
+        const bool skip_last = TRIMT && n_mfma_tiles - (int)(item % (unsigned)n_blocks) * NT < NT;
 
         for (int p = 0; p < P; ++p) {
             const int s0 = p * SP;
@@ -531,10 +544,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
                     constexpr int t = decltype(tc)::value;
                     if constexpr (LAST) {
                         lds_wait<((NT - 1 - t) < 15 ? (NT - 1 - t) : 15)>(w[t]);
-                        mfmas(tc);
+                        if (!(TRIMT && t == NT - 1 && skip_last)) mfmas(tc);
                     } else {
                         lds_wait<WAITN>(w[t]);
-                        mfmas(tc);
+                        if (!(TRIMT && t == NT - 1 && skip_last)) mfmas(tc);
                         lds_read_b128<(NT + t) * 1024>(w[t], rd);
                     }
                 });
@@ -562,7 +575,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
         float* c_ptr[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            const unsigned row = ((panel * WAVES + wave) * RT + rt) * 16 + (unsigned)(lane >> 2);
+            unsigned row = ((panel * WAVES + wave) * RT + rt) * 16 + (unsigned)(lane >> 2);
+            if (CMAP) row = map_row(row);
             c_ptr[rt] = C + (size_t)row * (size_t)ldc + nblk * (NT * 16) + 4 * (lane & 3);
         }
         const int valid_t = n_valid_tiles - nblk * NT;
@@ -602,27 +616,38 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
 
 // rows must be a multiple of 256; grid = one persistent workgroup per CU.  Returns -1 when there is no
 // instance for (nt, act).
+// trim_tiles: column blocks with a tile past n_valid_tiles issue no MFMAs for it (the same stores either way).
+// cmap != nullptr (nt 15, no activation): the rows of A AND of C are cmap's map, rows = whole panels covering it.
 int fvad_launch_panel_gemm3(const float* A, int lda, const float* Wfrag, const float* bias, float* C,
                             int ldc, long rows, int nt, int n_blocks, int S_steps, int K, int act,
-                            int n_valid_tiles, int map_T, int map_skip, int n_wg, hipStream_t stream)
+                            int n_valid_tiles, int map_T, int map_skip, int n_wg, hipStream_t stream, bool trim_tiles,
+                            const Gemm3RowMap* cmap)
 {
     if (rows % 256) return -1;
+    int map_per = map_T - map_skip;
+    unsigned map_qmax = 0;
+    if (cmap) {
+        if (cmap->per <= 0 || cmap->T < cmap->skip + cmap->per || cmap->skip < 0 || cmap->n_q <= 0 || rows < cmap->n_q * (long)cmap->per) return -1;
+        map_T = cmap->T; map_skip = cmap->skip; map_per = cmap->per; map_qmax = (unsigned)(cmap->n_q - 1);
+    }
+    const int n_mfma_tiles = trim_tiles ? n_valid_tiles : nt * n_blocks;
     const int n_last = K - 16 * (S_steps - 1); // valid k in the last super-step
     const int tail_r = n_last >= 4 ? 4 : (n_last < 1 ? 4 : n_last);
     const unsigned n_items = (unsigned)((rows / 256) * n_blocks);
     const unsigned grid = n_items < (unsigned)n_wg ? n_items : (unsigned)n_wg;
-#define CASE3(NT_, ACT_, SP_)                                                                         \
-    if (nt == NT_ && act == ACT_) {                                                                   \
-        hipLaunchKernelGGL((panel_gemm3_kernel<NT_, 2, ACT_, SP_, 8>), dim3(grid), dim3(512), 0, stream, \
+#define CASE3(NT_, ACT_, SP_, CMAP_, TRIMT_)                                                          \
+    if (nt == NT_ && act == ACT_ && (cmap != nullptr) == CMAP_) {                                     \
+        hipLaunchKernelGGL((panel_gemm3_kernel<NT_, 2, ACT_, SP_, 8, CMAP_, TRIMT_>), dim3(grid), dim3(512), 0, stream, \
                            A, lda, Wfrag, bias, C, ldc, S_steps, n_blocks, n_valid_tiles, map_T,      \
-                           map_skip, n_items, tail_r);                                                \
+                           map_skip, n_items, tail_r, map_per, map_qmax, n_mfma_tiles);               \
         return 0;                                                                                     \
     }
     // no 19-tile instance: 152 accumulator + 76 fragment registers do not fit 256 VGPRs; fc2/fc3 use
     // three 13-tile column blocks here
-    CASE3(15, FVAD_ACT_NONE, 5)
-    CASE3(13, FVAD_ACT_RELU, 5)
-    CASE3(11, FVAD_ACT_SIGMOID, 6)
+    CASE3(15, FVAD_ACT_NONE, 5, false, false)
+    CASE3(15, FVAD_ACT_NONE, 5, true, false)
+    CASE3(13, FVAD_ACT_RELU, 5, false, true)
+    CASE3(11, FVAD_ACT_SIGMOID, 6, false, false)
 #undef CASE3
     return -1;
 }
@@ -673,7 +698,8 @@ template <int WAVES, int D, bool TS3>
 __global__ __launch_bounds__(WAVES * 64) void gru_rec3_kernel(const float* __restrict__ gi,
                                                               const float* __restrict__ R2frag,
                                                               const float* __restrict__ bR,
-                                                              float* hout, int T, float* hs3)
+                                                              float* hout, int T, float* hs3,
+                                                              const ChunkDesc* __restrict__ descs, unsigned n_real)
 {
     __shared__ __attribute__((aligned(16))) float slab[2][GRU2_SLAB];
     typedef __attribute__((address_space(3))) float lds_float;
@@ -688,10 +714,21 @@ __global__ __launch_bounds__(WAVES * 64) void gru_rec3_kernel(const float* __res
     // for three wavefronts per SIMD.
     typedef const __attribute__((address_space(1))) char* gbytes;
     const size_t seq0 = (size_t)(blockIdx.x * WAVES + wave) * 16;
-    gbytes gi_w = (gbytes)(gi + seq0 * T * (3 * GRU_H));
+    gbytes gi_w = (gbytes)(gi + seq0 * T * (3 * GRU_H)) - (size_t)kWarmupRows * (3 * GRU_H) * 4; // four rows down: gi_off below
     __attribute__((address_space(1))) char* h_w = (__attribute__((address_space(1))) char*)(hout + seq0 * T * GRU_H);
     gbytes bR_b = (gbytes)bR;
-    const unsigned gi_off = ((unsigned)m * (unsigned)T * (3 * GRU_H) + 4u * q) * 4u;
+    // descs != nullptr (layer 1 of the engine's trimmed path, T = 54): gi holds rows 0..3 only for a sequence that is the
+    // `first` chunk of its lane; every other real sequence takes them from its predecessor's rows 50..53 (the same bits: K1
+    // writes the same feature rows in both places), i.e. at (t - 4) rows from its own base.  The steps t < 4 address gi from a
+    // scalar base four rows down, and the lane offset of a `first` sequence carries the four rows back up; from t = 4 on every
+    // lane does.  A padded sequence (>= n_real) reads its predecessor's rows too: they are written, its own are not.
+    constexpr unsigned GI_SHIFT = kWarmupRows * (3 * GRU_H) * 4u; // bytes
+    const unsigned gi_off_own = ((unsigned)m * (unsigned)T * (3 * GRU_H) + 4u * q) * 4u + GI_SHIFT;
+    unsigned gi_off = gi_off_own;
+    if (descs) {
+        const unsigned seq = (unsigned)seq0 + (unsigned)m;
+        if (seq >= n_real || !descs[seq].first) gi_off -= GI_SHIFT;
+    }
     const unsigned h_off = ((unsigned)m * (unsigned)T * GRU_H + 4u * q) * 4u;
     const unsigned b_off = 16u * q;
     // the empty asm keeps the compiler from folding the lane offset into a hoisted 64-bit VGPR base
@@ -755,6 +792,7 @@ __global__ __launch_bounds__(WAVES * 64) void gru_rec3_kernel(const float* __res
     int buf = 0;
 
     for (int t = 1; t < T; ++t) {
+        if (t == kWarmupRows) gi_off = gi_off_own;
         gbytes gi_t = gi_w + (size_t)t * (12 * GRU_H);
         gbytes h_prev = (gbytes)h_w + (size_t)(t - 1) * (4 * GRU_H);
         __attribute__((address_space(1))) char* h_out = h_w + (size_t)t * (4 * GRU_H);
@@ -1287,13 +1325,16 @@ int fvad_launch_gru_gen(const float* gi, int gi_ld, const float* R2frag, const f
 }
 
 // hs3 != nullptr: h is also written as three-piece bf16 fragments (TS3, kernels_b3.hip)
+// first_of != nullptr (T = 54 and more than four rows only): sequence s < n_real reads rows 0..3 of gi from its predecessor's
+// rows 50..53 unless first_of[s].first; sequences >= n_real always do
 int fvad_launch_gru_rec3(const float* gi, const float* R2frag, const float* bR, float* hout,
-                         long n_seq_pad, int T, int waves, hipStream_t stream, float* hs3)
+                         long n_seq_pad, int T, int waves, hipStream_t stream, float* hs3, const ChunkDesc* first_of, long n_real)
 {
+    if (first_of && (T <= kWarmupRows || n_real < 1 || n_real > n_seq_pad)) return -1;
 #define REC3(W_)                                                                                                          \
     if (waves == W_) {                                                                                                    \
-        if (hs3) hipLaunchKernelGGL((gru_rec3_kernel<W_, 2, true>), dim3((unsigned)(n_seq_pad / (16 * W_))), dim3(64 * W_), 0, stream, gi, R2frag, bR, hout, T, hs3); \
-        else hipLaunchKernelGGL((gru_rec3_kernel<W_, 2, false>), dim3((unsigned)(n_seq_pad / (16 * W_))), dim3(64 * W_), 0, stream, gi, R2frag, bR, hout, T, hs3); \
+        if (hs3) hipLaunchKernelGGL((gru_rec3_kernel<W_, 2, true>), dim3((unsigned)(n_seq_pad / (16 * W_))), dim3(64 * W_), 0, stream, gi, R2frag, bR, hout, T, hs3, first_of, (unsigned)n_real); \
+        else hipLaunchKernelGGL((gru_rec3_kernel<W_, 2, false>), dim3((unsigned)(n_seq_pad / (16 * W_))), dim3(64 * W_), 0, stream, gi, R2frag, bR, hout, T, hs3, first_of, (unsigned)n_real); \
         return 0;                                                                                                         \
     }
     REC3(12)

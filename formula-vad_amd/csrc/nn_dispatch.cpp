@@ -423,7 +423,7 @@ static int run_nn_generic(fvad_ctx* ctx, long n_pad, int T, int skip)
     return FVAD_OK;
 }
 
-int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real)
+int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLanes* lanes)
 {
     if (!ctx->dm.loaded) return set_err(ctx, FVAD_ERR_NO_MODEL, "NSNet2 weights not loaded");
     if (n_real <= 0 || n_real > n_pad) n_real = n_pad;
@@ -489,7 +489,7 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real)
         // 11-tile column blocks.  K is the true reduction length (S super-steps of 16 cover it, zero-padded).
         auto gemm = [&](const float* A, int lda, const float* W, const float* b, float* Cc, int ldc, long r, int nt,
                         int nblk, int S, int K, int act, int valid, int mT, int mskip) {
-            return fvad_launch_panel_gemm3(A, lda, W, b, Cc, ldc, r, nt, nblk, S, K, act, valid, mT, mskip, ctx->n_cu, st);
+            return fvad_launch_panel_gemm3(A, lda, W, b, Cc, ldc, r, nt, nblk, S, K, act, valid, mT, mskip, ctx->n_cu, st, (tn.nn_trim & 1) != 0);
         };
         // f16x3 path (kernels_h3.hip): its intermediates (gi, h1, h2, f2, f3) are in the tiled layout, row tiles of
         // 16 sequences at one time step; the features come in and the gains go out row-major
@@ -536,7 +536,29 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real)
                             (gc.version == 3 ? "gru_rec3<" + std::to_string(gc.waves) + ">" : gc.version == 5 ? std::string("gru_ws") : std::string("gru_lat"));
         if (gc.version == 5 && (rc = prepare_gru_ws(ctx, n_pad))) return rc; // only when forced: tuning / tests
         const bool bzr = gc.version == 3;
-        if (fold) {
+        // A chunk's warm-up rows 0..3 are K1's copy of the previous chunk's feature rows 50..53, and the input projection is
+        // row-wise: gi1[g][0..3] == gi1[g - 1][50..53] bit for bit unless chunk g is the first of its lane in this launch
+        // (its rows come from the carry).  So layer 1's projection runs over rows 4..53 of every chunk, plus rows 0..3 of the
+        // lanes' first chunks in one small launch of the same kernel, and gru_rec3 reads the other chunks' rows 0..3 four rows
+        // below their own base.  Condition: the engine's descriptors say which chunks are first; every lane has the same
+        // number of chunks in the launch (the first chunks are then lanes x chunks_per_lane apart: no table); fc1 folded;
+        // gru_rec3; whole 256-row panels of 50-row sequences (n_pad a multiple of 128).  Every other launch computes all 54 rows.
+        const bool trim_rows = (tn.nn_trim & 2) && fold && gc.version == 3 && lanes && lanes->descs && lanes->chunks_per_lane > 0 &&
+                               lanes->n_lanes * lanes->chunks_per_lane == n_real && T == kRowsPerChunk && skip == kWarmupRows &&
+                               (n_pad * (T - skip)) % 256 == 0;
+        if (trim_rows) ctx->last_nn_path += ", gi1 rows 4..53";
+        if (trim_rows) {
+            Gemm3RowMap own, first;
+            own.per = T - skip; own.T = T; own.skip = skip; own.n_q = n_pad;
+            first.per = skip; first.T = (int)(lanes->chunks_per_lane * T); first.skip = 0; first.n_q = lanes->n_lanes;
+            const long first_rows = (lanes->n_lanes * skip + 255) / 256 * 256;
+            time_begin(ctx, "gru1_in_gemm_fc1folded");
+            rc |= fvad_launch_panel_gemm3(ws.feat, kFeatStride, m.gi1f_w.p, m.gi1f_bzr.p, ws.gi, 1200, n_pad * (T - skip), 15, 5, 11, 161, FVAD_ACT_NONE, 75,
+                                          0, 0, ctx->n_cu, st, false, &own);
+            rc |= fvad_launch_panel_gemm3(ws.feat, kFeatStride, m.gi1f_w.p, m.gi1f_bzr.p, ws.gi, 1200, first_rows, 15, 5, 11, 161, FVAD_ACT_NONE, 75,
+                                          0, 0, ctx->n_cu, st, false, &first);
+            time_end(ctx);
+        } else if (fold) {
             time_begin(ctx, "gru1_in_gemm_fc1folded");
             rc |= gemm(ws.feat, kFeatStride, m.gi1f_w.p, bzr ? m.gi1f_bzr.p : m.gi1f_b.p, ws.gi, 1200, rows, 15, 5, 11, 161, FVAD_ACT_NONE, 75, 0, 0);
             time_end(ctx);
@@ -549,7 +571,8 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real)
             time_end(ctx);
         }
         time_begin(ctx, "gru1_rec");
-        rc |= launch_gru(ctx, gc, ws.gi, m.r1v2, m.br1.p, ws.h1, n_pad, T, 0, 1);
+        if (trim_rows) rc |= (n_pad % (16 * gc.waves)) ? -1 : fvad_launch_gru_rec3(ws.gi, m.r1v2.p, m.br1.p, ws.h1, n_pad, T, gc.waves, st, nullptr, lanes->descs, n_real);
+        else rc |= launch_gru(ctx, gc, ws.gi, m.r1v2, m.br1.p, ws.h1, n_pad, T, 0, 1);
         time_end(ctx);
         time_begin(ctx, "gru2_in_gemm");
         rc |= gemm(ws.h1, 400, m.gi2v2_w.p, bzr ? m.gi2_bzr.p : m.gi2_btm.p, ws.gi, 1200, rows, 15, 5, 25, 400, FVAD_ACT_NONE, 75, 0, 0);
@@ -832,6 +855,7 @@ int run_chunks(fvad_ctx* ctx, std::vector<LaneJob>& jobs, long max_chunks, Chunk
         const long cap = std::min<long>(launch_i < plan.size() ? plan[launch_i] : plan.back(), ws.cap_chunks);
         ++launch_i;
         long n = 0;
+        NnLanes nl; // the lanes of this launch, for run_nn
         std::vector<size_t> touched;
         struct Tap { size_t job, chunk0, count; long batch0; };
         std::vector<Tap> taps;
@@ -850,6 +874,8 @@ int run_chunks(fvad_ctx* ctx, std::vector<LaneJob>& jobs, long max_chunks, Chunk
             LaneJob& lj = jobs[j];
             if (lj.n_chunks == 0) { ++j; c = 0; continue; }
             const size_t take = std::min<size_t>(lj.n_chunks - c, (size_t)(cap - n));
+            if (nl.n_lanes++ == 0) nl.chunks_per_lane = (long)take;
+            else if (nl.chunks_per_lane != (long)take) nl.chunks_per_lane = 0;
             if (lj.h_spec || lj.h_feat) taps.push_back({j, c, take, n});
             for (size_t k = 0; k < take; ++k) {
                 ChunkDesc& d = hd[n + (long)k];
@@ -895,7 +921,8 @@ int run_chunks(fvad_ctx* ctx, std::vector<LaneJob>& jobs, long max_chunks, Chunk
                                                kNBins * sizeof(float), t.count * (size_t)kRowsPerChunk, hipMemcpyDeviceToHost, ctx->stream));
         }
         const long n_pad = padded_batch(ctx, n, kRowsPerChunk, kWarmupRows);
-        rc = run_nn(ctx, n_pad, kRowsPerChunk, kWarmupRows, n);
+        nl.descs = dd;
+        rc = run_nn(ctx, n_pad, kRowsPerChunk, kWarmupRows, n, &nl);
         if (rc) return rc;
         time_begin(ctx, "istft320_ola_up3");
         fvad_launch_istft(dd, (int)n, ctx->tb, ws.spec, ws.gains, kFramesPerChunk, 0, ctx->stream, fft_parts);

@@ -329,7 +329,10 @@ const char *fvad_ctx_last_nn_path(const fvad_ctx *ctx);
  * "v3" | "v3nofold") | "h3_waves" ("8" | "12") | "max_chunks" | "copy_threads" | "no_pipeline" | "run_groups" ("1,3,4,8": the lane groups of
  * fvad_engine_run's host-buffer pipeline in sixteenths of the call, at most seven, instead of the planned ones) | "trace_run" (a timeline of every fvad_engine_run call on stderr) | "trace_kernels" |
  * "ws_spin_ticks" | "ws2_variant" (diagnostic bit mask; the timing-only bits exist in the diagnostics build alone) |
- * "ws2_waits" | "ws2_calibrate" (below) | "k4_plain_loads" (the band FFT's staging path of unaligned frames) | "gru_lat_tiles" ("1" | "2" | "3": row tiles per
+ * "ws2_waits" | "ws2_calibrate" (below) | "nn_trim" ("all" | "tiles" | "rows" | "none": what the persistent f32 kernels skip -- "tiles": the MFMAs of
+ * fc2 / fc3's all-padding 39th column tile; "rows": layer 1's input projection of a chunk's four warm-up rows, which the recurrence reads from the
+ * previous chunk of the lane instead, in fvad_engine_* launches whose lanes all have the same number of chunks (fvad_ctx_last_nn_path then ends in
+ * ", gi1 rows 4..53"); same bits whatever the value) | "k4_plain_loads" (the band FFT's staging path of unaligned frames) | "gru_lat_tiles" ("1" | "2" | "3": row tiles per
  * workgroup of the low-latency recurrence instead of the cost model's choice; same bits) | "vad_trigger" ("config" | "shared") | "vad_trigger_max_bytes" (see fvad_vad_batch_trigger_form) | "vad_avgs" ("ring" | "table") | "vad_avgs_max_bytes" (see fvad_vad_batch_avgs_form) | "vad_chain" ("lane" | "coop": the exact
  * long-term chains of the device VAD machines lane by lane or by the whole wavefront, see fvad_vad_batch_run_device_part; same bits);
  * value NULL or ""
