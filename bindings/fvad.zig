@@ -45,9 +45,15 @@ pub const Status = struct {
     pub const err_model_format = -104;
     pub const err_io = -105;
     pub const err_buffer_too_small = -106;
+    pub const err_not_available = -107;
     pub const nn_math_f32 = 0;
     pub const nn_math_f16x3 = 1;
     pub const nn_math_bf16x3 = 2;
+    pub const nn_tap_h1 = 0;
+    pub const nn_tap_h2 = 1;
+    pub const nn_tap_f2 = 2;
+    pub const nn_tap_f3 = 3;
+    pub const nn_tap_gains = 4;
     pub const rec_none = 0;
     pub const rec_started = 1;
     pub const rec_completed = 2;
@@ -284,6 +290,9 @@ pub extern "c" fn fvad_nsnet2_forward(ctx: *Ctx, features: [*]const f32, n_seq: 
 pub extern "c" fn fvad_ctx_set_nn_math(ctx: *Ctx, mode: c_int) c_int;
 pub extern "c" fn fvad_ctx_nn_math_effective(ctx: *const Ctx) c_int;
 pub extern "c" fn fvad_ctx_last_nn_path(ctx: *const Ctx) [*:0]const u8;
+/// a test tap: a layer of the last NSNet2 pass as out[seq][row][unit]; Status.err_not_available for a layer the pass's kernels
+/// never write row-major (see fvad.h)
+pub extern "c" fn fvad_ctx_nn_tap(ctx: *Ctx, layer: c_int, first_seq: usize, n_seq: usize, out: [*]f32, rows_per_seq: *usize, width: *usize) c_int;
 pub extern "c" fn fvad_ctx_set_option(ctx: *Ctx, name: [*:0]const u8, value: ?[*:0]const u8) c_int; // e.g. "reproducible", "1"
 pub extern "c" fn fvad_ctx_ws_fallbacks(ctx: *Ctx, n: *u64) c_int;
 pub extern "c" fn fvad_ctx_ws2_waits(ctx: *const Ctx, wait_class: c_int) u32; // layer 1 | layer 2 << 16, 10 ns ticks

@@ -23,6 +23,8 @@ FVAD_ERR_OUT_OF_RANGE = -6
 FVAD_ERR_NEGATIVE_FREQUENCY = -7
 FVAD_ERR_BUFFER_TOO_SMALL = -106
 FVAD_ERR_MODEL_FORMAT = -104
+FVAD_ERR_NOT_AVAILABLE = -107
+NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
 
 
 class FvadError(RuntimeError):
@@ -200,6 +202,7 @@ SIGNATURES = {
     "fvad_ctx_set_nn_math": (C.c_int, [vp, C.c_int]),
     "fvad_ctx_nn_math_effective": (C.c_int, [vp]),
     "fvad_ctx_last_nn_path": (C.c_char_p, [vp]),
+    "fvad_ctx_nn_tap": (C.c_int, [vp, C.c_int, sz, sz, c_float_p, C.POINTER(sz), C.POINTER(sz)]),
     "fvad_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
     "fvad_ctx_ws_fallbacks": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "fvad_ctx_ws2_waits": (C.c_uint32, [vp, C.c_int]),
@@ -443,6 +446,27 @@ class Context:
 
     def last_nn_path(self):
         return lib().fvad_ctx_last_nn_path(self.h).decode()
+
+    def nn_tap(self, layer, first, n):
+        """fvad_ctx_nn_tap (a test tap): layer "h1" | "h2" | "f2" | "f3" | "gains" of the last NSNet2 pass for its sequences
+        [first, first + n) as a float32 array [n][rows][width]; None where the pass's kernels do not keep that layer"""
+        code = int(NN_TAP_LAYERS.get(layer, layer))
+        L = lib()
+        L.fvad_debug_nn_tap_shape.restype = C.c_int
+        L.fvad_debug_nn_tap_shape.argtypes = [vp, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+        rows, width = sz(0), sz(0)
+        # the entry point takes no capacity: ask for the pass's shape first and size the buffer from it
+        st = L.fvad_debug_nn_tap_shape(self.h, code, C.byref(rows), C.byref(width))
+        if st == FVAD_ERR_NOT_AVAILABLE:
+            return None
+        self._ck(st, "fvad_ctx_nn_tap")
+        buf = np.empty((max(int(n), 1), rows.value, width.value), np.float32)
+        st = L.fvad_ctx_nn_tap(self.h, code, int(first), int(n), fptr(buf), C.byref(rows), C.byref(width))
+        if st == FVAD_ERR_NOT_AVAILABLE:
+            return None
+        self._ck(st, "fvad_ctx_nn_tap")
+        assert buf.shape[1:] == (rows.value, width.value)
+        return buf[: int(n)]
 
     def set_option(self, name, value=None):
         """testing / tuning aid (fvad_ctx_set_option); value None restores the default"""

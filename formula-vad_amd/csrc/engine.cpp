@@ -291,6 +291,7 @@ const char* fvad_status_name(int s)
     case FVAD_ERR_MODEL_FORMAT: return "ModelFormat";
     case FVAD_ERR_IO: return "IoError";
     case FVAD_ERR_BUFFER_TOO_SMALL: return "BufferTooSmall";
+    case FVAD_ERR_NOT_AVAILABLE: return "NotAvailable";
     default: return "Unknown";
     }
 }
@@ -483,6 +484,48 @@ int fvad_ctx_nn_math_effective(const fvad_ctx* ctx)
 }
 
 const char* fvad_ctx_last_nn_path(const fvad_ctx* ctx) { return ctx ? ctx->last_nn_path.c_str() : ""; }
+
+// A test tap: what the last NSNet2 pass left in the workspace, un-padded to out[seq][row][unit].  Copies only: no kernel.
+int fvad_ctx_nn_tap(fvad_ctx* ctx, int layer, size_t first_seq, size_t n_seq, float* out, size_t* rows_per_seq, size_t* width)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!out || !rows_per_seq || !width || n_seq == 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_ctx_nn_tap: null pointer or no sequences");
+    if (layer < FVAD_NN_TAP_H1 || layer > FVAD_NN_TAP_GAINS) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_ctx_nn_tap: unknown layer");
+    const NnTapInfo& t = ctx->nn_tap;
+    if (!t.valid) return set_err(ctx, FVAD_ERR_NOT_AVAILABLE, "fvad_ctx_nn_tap: no NSNet2 pass has run on this context");
+    if (t.generation != ctx->ws.generation)
+        return set_err(ctx, FVAD_ERR_NOT_AVAILABLE, "fvad_ctx_nn_tap: the workspace was reallocated since the last NSNet2 pass");
+    if (!(t.layers >> layer & 1u)) return set_err(ctx, FVAD_ERR_NOT_AVAILABLE, std::string("fvad_ctx_nn_tap: ") + t.why);
+    if (first_seq >= (size_t)t.n_real || n_seq > (size_t)t.n_real - first_seq)
+        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_ctx_nn_tap: sequences past the last pass's " + std::to_string(t.n_real));
+    const Workspace& ws = ctx->ws;
+    const bool hidden = layer == FVAD_NN_TAP_H1 || layer == FVAD_NN_TAP_H2;
+    const float* src = layer == FVAD_NN_TAP_H1 ? ws.h1 : layer == FVAD_NN_TAP_H2 ? ws.h2 : layer == FVAD_NN_TAP_F2 ? ws.f2 : layer == FVAD_NN_TAP_F3 ? ws.f3 : ws.gains;
+    const size_t rows = hidden ? (size_t)t.T : (size_t)(t.T - t.skip); // the dense layers run over a sequence's rows skip .. T-1 only
+    const size_t ld = hidden ? (size_t)t.ld_h : layer == FVAD_NN_TAP_GAINS ? (size_t)t.ld_g : (size_t)t.ld_f;
+    const size_t w = hidden ? (size_t)t.w_h : layer == FVAD_NN_TAP_GAINS ? (size_t)t.w_g : (size_t)t.w_f;
+    if (!src) return set_err(ctx, FVAD_ERR_NOT_AVAILABLE, "fvad_ctx_nn_tap: the layer's buffer is not allocated");
+    hipSetDevice(ctx->device);
+    FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // device rows are [sequence][row] of ld floats, padded columns behind the w units: one strided copy drops them
+    FVAD_HIP(ctx, hipMemcpy2D(out, w * sizeof(float), src + first_seq * rows * ld, ld * sizeof(float), w * sizeof(float), n_seq * rows, hipMemcpyDeviceToHost));
+    *rows_per_seq = rows;
+    *width = w;
+    return FVAD_OK;
+}
+
+// for callers that size fvad_ctx_nn_tap's buffer (the ctypes binding), not part of the ABI in include/fvad.h: rows per sequence and
+// width that fvad_ctx_nn_tap would report for `layer` now, by the same availability rules; copies nothing
+int fvad_debug_nn_tap_shape(fvad_ctx* ctx, int layer, size_t* rows_per_seq, size_t* width)
+{
+    if (!ctx || !rows_per_seq || !width || layer < FVAD_NN_TAP_H1 || layer > FVAD_NN_TAP_GAINS) return FVAD_ERR_INVALID_ARGUMENT;
+    const NnTapInfo& t = ctx->nn_tap;
+    if (!t.valid || t.generation != ctx->ws.generation || !(t.layers >> layer & 1u)) return FVAD_ERR_NOT_AVAILABLE;
+    const bool hidden = layer == FVAD_NN_TAP_H1 || layer == FVAD_NN_TAP_H2;
+    *rows_per_seq = hidden ? (size_t)t.T : (size_t)(t.T - t.skip);
+    *width = hidden ? (size_t)t.w_h : layer == FVAD_NN_TAP_GAINS ? (size_t)t.w_g : (size_t)t.w_f;
+    return FVAD_OK;
+}
 
 // diagnostics for the tests, not part of the ABI in include/fvad.h: the launches a call of `total` chunks is cut into
 // (plan_launches, nn_dispatch.cpp) under the context's current options; returns their number (at most `cap` are written)

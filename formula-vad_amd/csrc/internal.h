@@ -152,6 +152,19 @@ struct Workspace {
     hipEvent_t grp_in[8] = {}, grp_k[8] = {};
 };
 
+// What fvad_ctx_nn_tap needs to know about the last NSNet2 pass: run_nn fills it in as it picks its path.  Rows of every
+// buffer are [sequence][step]; a layer the path never materialises row-major in f32 has its bit clear in `layers`.
+struct NnTapInfo {
+    bool valid = false;       // a pass has run on this context
+    unsigned generation = 0;  // Workspace::generation at that pass: a reallocation since then invalidates the tap
+    long n_pad = 0, n_real = 0;
+    int T = 0, skip = 0;
+    int ld_h = 0, ld_f = 0, ld_g = 0;  // floats per row of h1 / h2 (400), of f2 / f3 (608 or 640), of the gains (176)
+    int w_h = 0, w_f = 0, w_g = 0;     // units per row the caller gets (400 / 600 / 161)
+    unsigned layers = 0;      // bit FVAD_NN_TAP_*: the layer is in the workspace
+    const char* why = "";     // for the message when a layer is not: what the path keeps instead
+};
+
 struct KernelTime {
     std::string name;
     hipEvent_t e0, e1;
@@ -220,6 +233,7 @@ struct fvad_ctx {
     int nn_math = 0; // FVAD_NN_MATH_F32: the reference's arithmetic (NSNet2.zig:220, ORT CPU EP) at every batch size
     fvad::Tuning tune;
     std::string last_nn_path; // what the last NSNet2 pass ran ("f32: panel_gemm3 + gru_rec3<12>", ...)
+    fvad::NnTapInfo nn_tap;   // where that pass left its layers (fvad_ctx_nn_tap, a test tap)
     // timing
     bool timing = false;
     std::vector<fvad::KernelTime> times;

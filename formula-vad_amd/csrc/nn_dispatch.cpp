@@ -348,16 +348,28 @@ template <class F> static int ws_serialised(fvad_ctx* ctx, F&& launch)
     return rc;
 }
 
+// row tiles per workgroup of gru_lat for this launch: the cost model's choice, or the option's where the batch divides
+static int gru_lat_row_tiles(const fvad_ctx* ctx, long n_pad)
+{
+    int rt = 1;
+    (void)gru_lat_cost(n_pad, ctx->n_cu, &rt);
+    if (ctx->tune.gru_lat_tiles > 0) rt = (n_pad % (16 * ctx->tune.gru_lat_tiles) == 0) ? ctx->tune.gru_lat_tiles : 1;
+    return rt;
+}
+// how last_nn_path names it: "gru_lat", "gru_lat (2 row tiles)", "gru_lat (3 row tiles)"
+static std::string gru_lat_name(const fvad_ctx* ctx, long n_pad)
+{
+    const int rt = gru_lat_row_tiles(ctx, n_pad);
+    return rt > 1 ? "gru_lat (" + std::to_string(rt) + " row tiles)" : std::string("gru_lat");
+}
+
 static int launch_gru(fvad_ctx* ctx, GruChoice c, const float* gi, const DevBuf& r_v2, const float* bR,
                       float* hout, long n_pad, int T, int layer, int tile_major)
 {
     if (c.version == 4) {
         // more 16-sequence tiles than CUs: two or three row tiles per workgroup share one stream of R in fewer rounds of
         // workgroups (same bits; 8192 sequences: 4.03 against 4.43 ms per layer, 12288: 5.6 against gru_rec3<4>'s 6.7)
-        int rt = 1;
-        (void)gru_lat_cost(n_pad, ctx->n_cu, &rt);
-        if (ctx->tune.gru_lat_tiles > 0) rt = (n_pad % (16 * ctx->tune.gru_lat_tiles) == 0) ? ctx->tune.gru_lat_tiles : 1;
-        return fvad_launch_gru_lat(gi, r_v2.p, bR, hout, n_pad, T, nullptr, tile_major, ctx->stream, rt);
+        return fvad_launch_gru_lat(gi, r_v2.p, bR, hout, n_pad, T, nullptr, tile_major, ctx->stream, gru_lat_row_tiles(ctx, n_pad));
     }
     if (c.version == 5) {
         Workspace& ws = ctx->ws;
@@ -377,6 +389,20 @@ static int launch_gru(fvad_ctx* ctx, GruChoice c, const float* gi, const DevBuf&
     if (c.version == 3) return fvad_launch_gru_rec3(gi, r_v2.p, bR, hout, n_pad, T, c.waves, ctx->stream);
     return -1;
 }
+
+// fvad_ctx_nn_tap's record of a pass (NnTapInfo): written when the path is chosen, valid once every launch has been issued
+static void record_tap(fvad_ctx* ctx, long n_pad, long n_real, int T, int skip, unsigned layers, int ld_f, const char* why)
+{
+    NnTapInfo& t = ctx->nn_tap;
+    t = NnTapInfo();
+    t.generation = ctx->ws.generation;
+    t.n_pad = n_pad; t.n_real = n_real; t.T = T; t.skip = skip;
+    t.ld_h = 400; t.ld_f = ld_f; t.ld_g = kFeatStride;
+    t.w_h = 400; t.w_f = 600; t.w_g = kNBins;
+    t.layers = layers;
+    t.why = why;
+}
+constexpr unsigned kTapAll = 1u << FVAD_NN_TAP_H1 | 1u << FVAD_NN_TAP_H2 | 1u << FVAD_NN_TAP_F2 | 1u << FVAD_NN_TAP_F3 | 1u << FVAD_NN_TAP_GAINS;
 
 // NSNet2 of any dimensions (DeviceModel::generic): fc1 -> gi1 -> GRU1 -> gi2 -> GRU2 -> fc2 -> fc3 -> fc4 on the
 // run-time-sized kernels; one kernel family, f32 MFMA throughout
@@ -425,9 +451,15 @@ static int run_nn_generic(fvad_ctx* ctx, long n_pad, int T, int skip)
 
 int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLanes* lanes)
 {
+    ctx->nn_tap.valid = false;
     if (!ctx->dm.loaded) return set_err(ctx, FVAD_ERR_NO_MODEL, "NSNet2 weights not loaded");
     if (n_real <= 0 || n_real > n_pad) n_real = n_pad;
-    if (ctx->dm.generic) return run_nn_generic(ctx, n_pad, T, skip);
+    if (ctx->dm.generic) {
+        const int rc = run_nn_generic(ctx, n_pad, T, skip);
+        record_tap(ctx, n_pad, n_real, T, skip, 0, 0, "the run-time-sized kernels of a model of other dimensions are not tapped");
+        ctx->nn_tap.valid = rc == FVAD_OK;
+        return rc;
+    }
     Workspace& ws = ctx->ws;
     const DeviceModel& m = ctx->dm;
     hipStream_t st = ctx->stream;
@@ -479,6 +511,8 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLane
         time_end(ctx);
         if (rc) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no kernel instance for this layer shape");
         FVAD_HIP(ctx, hipGetLastError());
+        record_tap(ctx, n_pad, n_real, T, skip, 0, 0, "the bf16x3 emulation keeps its intermediates as three-piece fragments");
+        ctx->nn_tap.valid = true;
         return FVAD_OK;
     }
     const bool big = h3 || (force ? force[1] != '1' : (tn.reproducible || n_pad >= 2048));
@@ -528,12 +562,17 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLane
             time_end(ctx);
             if (rc) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no kernel instance for this layer shape");
             FVAD_HIP(ctx, hipGetLastError());
+            record_tap(ctx, n_pad, n_real, T, skip, 0, 0, "the f16x3 emulation keeps its intermediates as split tiled fragments");
+            ctx->nn_tap.valid = true;
             return FVAD_OK;
         }
         const bool fold = !(force && strstr(force, "nofold"));
-        const GruChoice gc = pick_gru(ctx, n_pad, T, fold);
+        GruChoice gc = pick_gru(ctx, n_pad, T, fold);
+        // (unfolded fc1 at a small batch: the cost model may name the pipelined recurrence, which belongs to the small-batch
+        // sequence below and has no launch here -- the low-latency kernel takes the layers instead of the pass failing)
+        if (gc.version == 6) gc = {4, 8};
         ctx->last_nn_path = std::string("f32: panel_gemm3") + (fold ? " (fc1 folded)" : "") + " + " +
-                            (gc.version == 3 ? "gru_rec3<" + std::to_string(gc.waves) + ">" : gc.version == 5 ? std::string("gru_ws") : std::string("gru_lat"));
+                            (gc.version == 3 ? "gru_rec3<" + std::to_string(gc.waves) + ">" : gc.version == 5 ? std::string("gru_ws") : gru_lat_name(ctx, n_pad));
         if (gc.version == 5 && (rc = prepare_gru_ws(ctx, n_pad))) return rc; // only when forced: tuning / tests
         const bool bzr = gc.version == 3;
         // A chunk's warm-up rows 0..3 are K1's copy of the previous chunk's feature rows 50..53, and the input projection is
@@ -591,6 +630,8 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLane
         time_end(ctx);
         if (rc) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no kernel instance for this layer shape");
         FVAD_HIP(ctx, hipGetLastError());
+        record_tap(ctx, n_pad, n_real, T, skip, kTapAll, 608, "");
+        ctx->nn_tap.valid = true;
         return FVAD_OK;
     }
     // ---- small batches: a handful of 64-row panels per launch, so every layer is cut into narrow column blocks
@@ -610,7 +651,7 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLane
     }
     if (gcs.version >= 5 && (rc = prepare_gru_ws(ctx, n_pad))) return rc;
     ctx->last_nn_path = std::string("f32: panel_gemm (fc1 folded) + ") + (gcs.version == 6 ? fvad_gru_ws2_kernel_name(n_pad, T, ctx->n_cu, tn.ws2_variant) :
-                        gcs.version == 5 ? "gru_ws" : "gru_lat");
+                        gcs.version == 5 ? std::string("gru_ws") : gru_lat_name(ctx, n_pad));
     if (gcs.version == 6) {
         // both GRU layers in one launch, layer 2 a step behind layer 1, its input projection computed inside
         unsigned* err = ws.ws_sync + 512;
@@ -665,6 +706,10 @@ int run_nn(fvad_ctx* ctx, long n_pad, int T, int skip, long n_real, const NnLane
     time_end(ctx);
     if (rc) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "no kernel instance for this layer shape");
     FVAD_HIP(ctx, hipGetLastError());
+    // the pipelined recurrence hands h1 from workgroup to workgroup through its exchange buffer: only its fallback writes ws.h1
+    record_tap(ctx, n_pad, n_real, T, skip, gcs.version == 6 ? kTapAll & ~(1u << FVAD_NN_TAP_H1) : kTapAll, 640,
+               "the pipelined recurrence (gru_ws2k / gru_ws2m) keeps h1 in its exchange buffer");
+    ctx->nn_tap.valid = true;
     return FVAD_OK;
 }
 
@@ -742,6 +787,7 @@ int calibrate_ws2_waits(fvad_ctx* ctx)
     }
     tn.ws2_waits = saved;
     ctx->last_nn_path = saved_path;
+    ctx->nn_tap.valid = false; // the workspace holds the measurement's passes, not the caller's
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     return rc;

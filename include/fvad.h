@@ -59,7 +59,8 @@ enum {
     FVAD_ERR_NO_MODEL = -103,             /* NSNet2 weights not loaded */
     FVAD_ERR_MODEL_FORMAT = -104,         /* ONNX file unreadable / not the NSNet2 graph */
     FVAD_ERR_IO = -105,
-    FVAD_ERR_BUFFER_TOO_SMALL = -106
+    FVAD_ERR_BUFFER_TOO_SMALL = -106,
+    FVAD_ERR_NOT_AVAILABLE = -107         /* what was asked for does not exist in this state (fvad_ctx_nn_tap) */
 };
 
 const char *fvad_status_name(int status);
@@ -309,6 +310,27 @@ enum { FVAD_NN_MATH_F32 = 0, FVAD_NN_MATH_F16X3 = 1, FVAD_NN_MATH_BF16X3 = 2 };
 int fvad_ctx_set_nn_math(fvad_ctx *ctx, int mode);
 int fvad_ctx_nn_math_effective(const fvad_ctx *ctx);
 const char *fvad_ctx_last_nn_path(const fvad_ctx *ctx);
+/* A test tap, not needed in production: what the context's LAST NSNet2 pass left in the workspace for its sequences
+ * [first_seq, first_seq + n_seq), as out[seq][row][unit] (f32, host pointer, room for n_seq * rows * width floats: at most
+ * n_seq * T * 600).  Waits for the context's stream, then copies; launches no kernel and changes none.
+ *   layer               rows per sequence   width
+ *   FVAD_NN_TAP_H1      T                   400    first GRU's states
+ *   FVAD_NN_TAP_H2      T                   400    second GRU's states
+ *   FVAD_NN_TAP_F2      T - skip            600    relu(fc2); row r is step skip + r
+ *   FVAD_NN_TAP_F3      T - skip            600    relu(fc3)
+ *   FVAD_NN_TAP_GAINS   T - skip            161    sigmoid(fc4): what K3 applies
+ * T and skip are the pass's: fvad_nsnet2_forward's T and 0; 54 and 4 in the engine, where a sequence is a chunk and row 0..3
+ * its warm-up rows.  After an fvad_engine_* or pipeline call the tap describes that call's LAST LAUNCH (a call may be cut into
+ * several: max_chunks_per_launch, or the engine's plan), sequences in launch order, lane-contiguous.  *rows_per_seq and *width
+ * are written on success.
+ * FVAD_ERR_NOT_AVAILABLE (never stale memory) when no pass has run, when a workspace buffer was reallocated or a model loaded
+ * since, and for a layer the pass's kernels never write row-major: h1 of the pipelined small-batch recurrence (gru_ws2k /
+ * gru_ws2m hand it on through their exchange buffer; also in the rare pass whose fallback launch did write it: the tap does
+ * not look at the fallback counter), every layer of the f16x3 / bf16x3 emulations (split fragments) and of a
+ * model of other dimensions.  FVAD_ERR_INVALID_ARGUMENT for a NULL pointer, n_seq == 0, an unknown layer, or sequences past the
+ * pass's real ones (the batch's padding is not tapped). */
+enum { FVAD_NN_TAP_H1 = 0, FVAD_NN_TAP_H2 = 1, FVAD_NN_TAP_F2 = 2, FVAD_NN_TAP_F3 = 3, FVAD_NN_TAP_GAINS = 4 };
+int fvad_ctx_nn_tap(fvad_ctx *ctx, int layer, size_t first_seq, size_t n_seq, float *out, size_t *rows_per_seq, size_t *width);
 /* Bit-reproducibility.  Two launches that select the same NSNet2 kernels (fvad_ctx_last_nn_path names them) give a
  * chunk the same bits wherever in the batch it sits and however lanes and chunks are split.  With FVAD_NN_MATH_F32
  * the engine selects by launch size: up to 1536 sequences the pipelined two-layer weight-stationary recurrence (it

@@ -107,6 +107,16 @@ typedef struct {
  * [T][161], GRU hidden state zero at row 0 of every call (no state tensors exist on the
  * session, NSNet2.zig:57-58,71-112). */
 void orc_nsnet2_forward(const orc_nsnet2_weights *w, const float *features, int T, float *gains);
+/* The same arithmetic, the same gains bit for bit, and every layer behind an activation as well (each may be
+ * NULL): h1, h2 [T][n_hidden], relu(fc2) [T][n_fc2], relu(fc3) [T][n_fc3]. */
+void orc_nsnet2_forward_layers(const orc_nsnet2_weights *w, const float *features, int T, float *gains,
+                               float *h1, float *h2, float *f2, float *f3);
+/* One layer on n_rows independent rows, each from the caller's own inputs: x is the previous layer's output
+ * (features [161] for H1, h1 for H2, h2 for F2, f2 for F3, f3 for GAINS), h_prev the same layer's previous state
+ * (H1 / H2 only, [n_rows][n_hidden]; NULL otherwise). */
+enum { ORC_NSNET2_H1 = 0, ORC_NSNET2_H2 = 1, ORC_NSNET2_F2 = 2, ORC_NSNET2_F3 = 3, ORC_NSNET2_GAINS = 4 };
+void orc_nsnet2_layer_rows(const orc_nsnet2_weights *w, int layer, const float *x, const float *h_prev,
+                           int n_rows, float *y);
 
 typedef struct orc_nsnet2 orc_nsnet2;
 /* NSNet2.init (NSNet2.zig:35-142).  sample_rate must be a multiple of 16000. */

@@ -51,6 +51,20 @@ static inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
  *   n = tanh   (Wh x + Wbh + r * (Rh h + Rbh))
  *   h' = (1 - z) * n + z * h
  */
+/* one GRU step from the input projection's input x and the previous state h: ht = GRU(x, h) */
+static void gru_step(const float *x, const float *h, int n_in, int H, const float *W, const float *R,
+                     const float *B, float *gi, float *gh, float *ht)
+{
+    dense(x, W, B, n_in, 3 * H, gi);
+    dense(h, R, B + 3 * H, H, 3 * H, gh);
+    for (int j = 0; j < H; ++j) {
+        const float z = sigmoidf(gi[j] + gh[j]);
+        const float r = sigmoidf(gi[H + j] + gh[H + j]);
+        const float n = tanhf(gi[2 * H + j] + r * gh[2 * H + j]);
+        ht[j] = (1.0f - z) * n + z * h[j];
+    }
+}
+
 static void gru_layer(const float *x, int T, int n_in, int H, const float *W_, const float *R_,
                       const float *B, float *out)
 {
@@ -60,15 +74,8 @@ static void gru_layer(const float *x, int T, int n_in, int H, const float *W_, c
     float *gi = (float *)malloc(sizeof(float) * 3 * (size_t)H);
     float *gh = (float *)malloc(sizeof(float) * 3 * (size_t)H);
     for (int t = 0; t < T; ++t) {
-        dense(x + (size_t)t * n_in, W, B, n_in, 3 * H, gi);
-        dense(h, R, B + 3 * H, H, 3 * H, gh);
         float *ht = out + (size_t)t * H;
-        for (int j = 0; j < H; ++j) {
-            const float z = sigmoidf(gi[j] + gh[j]);
-            const float r = sigmoidf(gi[H + j] + gh[H + j]);
-            const float n = tanhf(gi[2 * H + j] + r * gh[2 * H + j]);
-            ht[j] = (1.0f - z) * n + z * h[j];
-        }
+        gru_step(x + (size_t)t * n_in, h, n_in, H, W, R, B, gi, gh, ht);
         memcpy(h, ht, sizeof(float) * (size_t)H);
     }
     free(h);
@@ -78,7 +85,8 @@ static void gru_layer(const float *x, int T, int n_in, int H, const float *W_, c
     free(R);
 }
 
-void orc_nsnet2_forward(const orc_nsnet2_weights *w, const float *features, int T, float *gains)
+void orc_nsnet2_forward_layers(const orc_nsnet2_weights *w, const float *features, int T, float *gains,
+                               float *h1_out, float *h2_out, float *f2_out, float *f3_out)
 {
     const int B = w->n_bins, F1 = w->n_fc1, H = w->n_hidden, F2 = w->n_fc2, F3 = w->n_fc3;
     float *a1 = (float *)malloc(sizeof(float) * (size_t)T * F1);
@@ -100,13 +108,58 @@ void orc_nsnet2_forward(const orc_nsnet2_weights *w, const float *features, int 
         float *g = gains + (size_t)t * B;
         dense(a3, fc4, w->fc4_b, F3, B, g);
         for (int j = 0; j < B; ++j) g[j] = sigmoidf(g[j]);
+        if (f2_out) memcpy(f2_out + (size_t)t * F2, a2, sizeof(float) * (size_t)F2);
+        if (f3_out) memcpy(f3_out + (size_t)t * F3, a3, sizeof(float) * (size_t)F3);
     }
+    if (h1_out) memcpy(h1_out, h1, sizeof(float) * (size_t)T * H);
+    if (h2_out) memcpy(h2_out, h2, sizeof(float) * (size_t)T * H);
     free(a1);
     free(h1);
     free(h2);
     free(a2);
     free(a3);
     free(fc1); free(fc2); free(fc3); free(fc4);
+}
+
+void orc_nsnet2_forward(const orc_nsnet2_weights *w, const float *features, int T, float *gains)
+{
+    orc_nsnet2_forward_layers(w, features, T, gains, NULL, NULL, NULL, NULL);
+}
+
+/* One layer, row by row, each row from the inputs the caller hands it (nothing carried from row to
+ * row): the same dense / gru_step as above, so a layer is judged on its own arithmetic. */
+void orc_nsnet2_layer_rows(const orc_nsnet2_weights *w, int layer, const float *x, const float *h_prev,
+                           int n_rows, float *y)
+{
+    const int B = w->n_bins, F1 = w->n_fc1, H = w->n_hidden, F2 = w->n_fc2, F3 = w->n_fc3;
+    if (layer == ORC_NSNET2_H1 || layer == ORC_NSNET2_H2) {
+        const int first = layer == ORC_NSNET2_H1, n_in = first ? F1 : H;
+        float *fc1 = first ? transpose(w->fc1_w, F1, B) : NULL;
+        float *W = transpose(first ? w->gru1_w : w->gru2_w, 3 * H, n_in);
+        float *R = transpose(first ? w->gru1_r : w->gru2_r, 3 * H, H);
+        const float *Bv = first ? w->gru1_b : w->gru2_b;
+        float *a1 = (float *)malloc(sizeof(float) * (size_t)F1);
+        float *gi = (float *)malloc(sizeof(float) * 3 * (size_t)H);
+        float *gh = (float *)malloc(sizeof(float) * 3 * (size_t)H);
+        for (int i = 0; i < n_rows; ++i) {
+            const float *xi = x + (size_t)i * (first ? B : H);
+            if (first) dense(xi, fc1, w->fc1_b, B, F1, a1);
+            gru_step(first ? a1 : xi, h_prev + (size_t)i * H, n_in, H, W, R, Bv, gi, gh, y + (size_t)i * H);
+        }
+        free(fc1); free(W); free(R); free(a1); free(gi); free(gh);
+        return;
+    }
+    const int n_in = layer == ORC_NSNET2_F2 ? H : layer == ORC_NSNET2_F3 ? F2 : F3;
+    const int n_out = layer == ORC_NSNET2_F2 ? F2 : layer == ORC_NSNET2_F3 ? F3 : B;
+    const float *Wm = layer == ORC_NSNET2_F2 ? w->fc2_w : layer == ORC_NSNET2_F3 ? w->fc3_w : w->fc4_w;
+    const float *bv = layer == ORC_NSNET2_F2 ? w->fc2_b : layer == ORC_NSNET2_F3 ? w->fc3_b : w->fc4_b;
+    float *Wt = transpose(Wm, n_out, n_in);
+    for (int i = 0; i < n_rows; ++i) {
+        float *yi = y + (size_t)i * n_out;
+        dense(x + (size_t)i * n_in, Wt, bv, n_in, n_out, yi);
+        for (int j = 0; j < n_out; ++j) yi[j] = layer == ORC_NSNET2_GAINS ? sigmoidf(yi[j]) : fmaxf(yi[j], 0.0f);
+    }
+    free(Wt);
 }
 
 /* ------------------------------------------------------------------ NSNet2 object */

@@ -154,6 +154,8 @@ def lib(native=False):
         "orc_upsample": (C.c_float, [c_float_p, sz, c_float_p, sz, C.c_float, sz]),
         "orc_rms_volume": (C.c_float, [c_float_p, sz, c_float_p, sz]),
         "orc_nsnet2_forward": (None, [C.POINTER(Weights), c_float_p, C.c_int, c_float_p]),
+        "orc_nsnet2_forward_layers": (None, [C.POINTER(Weights), c_float_p, C.c_int] + [c_float_p] * 5),
+        "orc_nsnet2_layer_rows": (None, [C.POINTER(Weights), C.c_int, c_float_p, c_float_p, C.c_int, c_float_p]),
         "orc_nsnet2_create": (vp, [C.c_int, C.POINTER(Weights)]),
         "orc_nsnet2_destroy": (None, [vp]),
         "orc_nsnet2_chunk_size": (sz, [C.c_int]),
@@ -306,6 +308,33 @@ def nsnet2_forward(wd, features):
     g = np.zeros_like(f)
     lib().orc_nsnet2_forward(C.byref(w), fptr(f), f.shape[0], fptr(g))
     return g
+
+
+NSNET2_LAYERS = ("h1", "h2", "f2", "f3", "gains")
+
+
+def nsnet2_forward_layers(wd, features):
+    """orc_nsnet2_forward_layers: {"h1", "h2", "f2", "f3", "gains"} of one sequence [T][161]"""
+    w, keep = make_weights_struct(wd)
+    f = np.ascontiguousarray(features, dtype=np.float32)
+    T = f.shape[0]
+    out = {"gains": np.zeros_like(f), "h1": np.zeros((T, w.n_hidden), np.float32), "h2": np.zeros((T, w.n_hidden), np.float32),
+           "f2": np.zeros((T, w.n_fc2), np.float32), "f3": np.zeros((T, w.n_fc3), np.float32)}
+    lib().orc_nsnet2_forward_layers(C.byref(w), fptr(f), T, fptr(out["gains"]), fptr(out["h1"]), fptr(out["h2"]),
+                                    fptr(out["f2"]), fptr(out["f3"]))
+    return out
+
+
+def nsnet2_layer_rows(wd, layer, x, h_prev=None):
+    """orc_nsnet2_layer_rows: one layer ("h1" ... "gains") on independent rows x [n][n_in] (and h_prev [n][n_hidden])"""
+    w, keep = make_weights_struct(wd)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    hp = None if h_prev is None else np.ascontiguousarray(h_prev, dtype=np.float32)
+    width = {"h1": w.n_hidden, "h2": w.n_hidden, "f2": w.n_fc2, "f3": w.n_fc3, "gains": w.n_bins}[layer]
+    assert (hp is not None) == (layer in ("h1", "h2")) and (hp is None or hp.shape == (x.shape[0], w.n_hidden))
+    y = np.zeros((x.shape[0], width), np.float32)
+    lib().orc_nsnet2_layer_rows(C.byref(w), NSNET2_LAYERS.index(layer), fptr(x), fptr(hp), x.shape[0], fptr(y))
+    return y
 
 
 class Denoiser:

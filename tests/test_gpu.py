@@ -1542,33 +1542,7 @@ def test_k1_spectrogram_and_features_taps_match_oracle(fv, gpu_ctx, weights7, pk
             assert np.array_equal(feat[c, :4], feat[c - 1, 50:])   # copyBackwards of the previous rows 50..53
 
 
-def _nsnet2_float64(w, f):
-    """The ONNX graph in float64 numpy: fc1 -> GRU x2 (gate order z,r,h; linear_before_reset = 1; zero initial
-    state) -> relu(fc2) -> relu(fc3) -> sigmoid(fc4)"""
-    W = {k: np.asarray(v, np.float64) for k, v in w.items()}
-    sig = lambda v: 1.0 / (1.0 + np.exp(-v))  # noqa: E731
-    x = f.astype(np.float64) @ W["fc1_w"].T + W["fc1_b"]
-
-    def gru(x, w_, r_, b_):
-        H = r_.shape[1]
-        wb, rb = b_[: 3 * H], b_[3 * H:]
-        h = np.zeros(H)
-        out = np.empty((x.shape[0], H))
-        for t in range(x.shape[0]):
-            gi = w_ @ x[t] + wb
-            gh = r_ @ h + rb
-            z = sig(gi[:H] + gh[:H])
-            r = sig(gi[H:2 * H] + gh[H:2 * H])
-            n = np.tanh(gi[2 * H:] + r * gh[2 * H:])
-            h = (1 - z) * n + z * h
-            out[t] = h
-        return out
-
-    x = gru(x, W["gru1_w"], W["gru1_r"], W["gru1_b"])
-    x = gru(x, W["gru2_w"], W["gru2_r"], W["gru2_b"])
-    x = np.maximum(x @ W["fc2_w"].T + W["fc2_b"], 0)
-    x = np.maximum(x @ W["fc3_w"].T + W["fc3_b"], 0)
-    return sig(x @ W["fc4_w"].T + W["fc4_b"])
+from nn_layer_cases import nsnet2_float64 as _nsnet2_float64  # noqa: E402  (the float64 model the layer tests share)
 
 
 def test_gpu_against_float64_directly(fv, gpu_ctx, weights7):

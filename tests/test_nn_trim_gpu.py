@@ -7,7 +7,8 @@
          (fvad_ctx_last_nn_path does not end in "gi1 rows 4..53").
 
 Every engine case runs with nn_trim "all" and with "none" (the untrimmed kernels' code path: the yardstick) and the outputs
--- denoised audio, band sums, chunk RMS; the engine has no tap on the gains, the denoised audio is the gains applied -- are
+-- denoised audio, band sums, chunk RMS; the denoised audio is the gains applied (the layers themselves are judged through
+fvad_ctx_nn_tap in test_nn_layers_gpu.py) -- are
 compared as uint32; "all" is also compared with the oracle pipeline on the same samples (denoised 1e-4 of peak, band sums
 and RMS 1e-4 relative, segments exact).  The gains themselves are compared through fvad_nsnet2_forward.
 All under option reproducible: persistent GEMM + gru_rec3 at every launch size, batches padded to 128 sequences.
