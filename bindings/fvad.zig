@@ -23,6 +23,7 @@ const std = @import("std");
 
 pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
+pub const clip_fields = 4; // FVAD_CLIP_FIELDS: a clip is a row of first_lane, n_channels, sample_from, sample_to (u64 each)
 
 // ------------------------------------------------------------------ status codes (the anonymous enum of fvad.h)
 pub const Status = struct {
@@ -58,6 +59,8 @@ pub const Status = struct {
     pub const rec_started = 1;
     pub const rec_completed = 2;
     pub const rec_aborted = 3;
+    pub const clip_f32 = 0;
+    pub const clip_pcm16 = 1;
 };
 
 // ------------------------------------------------------------------ opaque handles
@@ -400,12 +403,19 @@ pub extern "c" fn fvad_comm_rank(c: *const Comm) c_int;
 pub extern "c" fn fvad_stats_allgather(c: *Comm, local_ids: [*]const u32, local_stats: [*]const SingleStats, n_local: usize, n_streams: usize, out: [*]SingleStats) c_int;
 pub extern "c" fn fvad_parse_audacity(txt: [*]const u8, len: usize, out: [*]SegmentSec, cap: usize, n: *usize) c_int;
 
+// batch Recorder: the clips Recorder.finalize builds (Recorder.zig:74-164), cut and picked on the device from resident lanes
+pub extern "c" fn fvad_clips_plan(clips: ?[*]const u64, n_clips: usize, out_format: c_int, offsets: ?[*]u64, total: *u64) c_int;
+pub extern "c" fn fvad_clips_from_segments(segs: ?[*]const SpeechSegment, n_segs: usize, first_lane: u32, n_channels: u32, n_available: u64, clips: ?[*]u64, cap: usize, n_out: *usize, n_skipped: *usize) c_int;
+pub extern "c" fn fvad_clips_export_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
+pub extern "c" fn fvad_clips_export(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
+
 // audio file input / output (host)
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free_i16(channel_pcm: ?[*][*]i16, n_channels: usize) void;
 pub extern "c" fn fvad_wav_write(path: [*:0]const u8, channel_pcm: [*]const [*]const f32, n_channels: usize, n_frames: usize, sample_rate: usize, as_pcm16: c_int) c_int;
+pub extern "c" fn fvad_wav_write_i16(path: [*:0]const u8, channel_pcm: [*]const [*]const i16, n_channels: usize, n_frames: usize, sample_rate: usize) c_int;
 
 // ================================================================== Zig-side wrappers
 /// The reference's error names, recovered from the negative status codes of fvad.h.

@@ -24,6 +24,8 @@ FVAD_ERR_NEGATIVE_FREQUENCY = -7
 FVAD_ERR_BUFFER_TOO_SMALL = -106
 FVAD_ERR_MODEL_FORMAT = -104
 FVAD_ERR_NOT_AVAILABLE = -107
+CLIP_F32, CLIP_PCM16 = 0, 1      # sample formats of fvad_clips_*
+CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, sample_to (uint64 each)
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
 
 
@@ -308,6 +310,14 @@ SIGNATURES = {
                                     C.POINTER(sz), C.POINTER(sz)]),
     "fvad_wav_free_i16": (None, [C.POINTER(C.POINTER(C.c_int16)), sz]),
     "fvad_wav_write": (C.c_int, [C.c_char_p, C.POINTER(c_float_p), sz, sz, sz, C.c_int]),
+    "fvad_wav_write_i16": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_int16)), sz, sz, sz]),
+    "fvad_clips_plan": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_from_segments": (C.c_int, [C.POINTER(SpeechSegment), sz, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), sz,
+                                           C.POINTER(sz), C.POINTER(sz)]),
+    "fvad_clips_export_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                           c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fvad_clips_export": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                    c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -642,6 +652,28 @@ class Context:
         self._ck(lib().fvad_engine_band_sums_device(self.h, vp(d_den), n_lanes, lane_stride, n_samples, fft_size,
                                                     b.ctypes.data_as(C.POINTER(C.c_int32)), b.shape[0], vp(d_band), band_stride),
                  "fvad_engine_band_sums_device")
+
+    def clips_export(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, out_pcm16=False, d_out=None, out_capacity=None):
+        """fvad_clips_export (d_out None: the packed clips come back as a numpy array of the output format) or
+        fvad_clips_export_device (d_out: a device address with room for out_capacity samples).  clips: [n][CLIP_FIELDS] uint64.
+        Returns dict(best_channel, best_rms, runner_up_rms, offsets, total[, out])."""
+        clips = _clip_rows(clips)
+        n = clips.shape[0]
+        offsets, total = clips_plan(clips, out_pcm16)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
+                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_PCM16 if out_pcm16 else CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)))
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total}
+        if d_out is not None:
+            self._ck(lib().fvad_clips_export_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
+                     "fvad_clips_export_device")
+            return res
+        out = np.zeros(max(total, 1), np.int16 if out_pcm16 else np.float32)
+        self._ck(lib().fvad_clips_export(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
+                 "fvad_clips_export")
+        res["out"] = out[:total]
+        return res
 
     def lane_state(self):
         s = vp()
@@ -1336,6 +1368,34 @@ def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_thr
           "fvad_vad_run_many")
 
 
+def _clip_rows(clips):
+    return np.ascontiguousarray(np.asarray(clips, np.uint64).reshape(-1, CLIP_FIELDS))
+
+
+def clips_plan(clips, out_pcm16=False):
+    """fvad_clips_plan: (offsets [n] uint64, total), in samples of the output format"""
+    clips = _clip_rows(clips)
+    offsets = np.zeros(clips.shape[0], np.uint64)
+    total = C.c_uint64(0)
+    check(lib().fvad_clips_plan(clips.ctypes.data_as(C.POINTER(C.c_uint64)), clips.shape[0], CLIP_PCM16 if out_pcm16 else CLIP_F32,
+                                offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan")
+    return offsets, total.value
+
+
+def clips_from_segments(segs, first_lane, n_channels, n_available, cap=None):
+    """fvad_clips_from_segments: segs = [(sample_from, sample_to, ...)] -> (clips [n][CLIP_FIELDS] uint64, n_skipped)"""
+    arr = (SpeechSegment * max(len(segs), 1))()
+    for i, s in enumerate(segs):
+        arr[i].sample_from, arr[i].sample_to = int(s[0]), int(s[1])
+    cap = len(segs) if cap is None else cap
+    clips = np.zeros((max(cap, 1), CLIP_FIELDS), np.uint64)
+    n, skipped = sz(), sz()
+    check(lib().fvad_clips_from_segments(arr, len(segs), first_lane, n_channels, n_available,
+                                         clips.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n), C.byref(skipped)),
+          "fvad_clips_from_segments")
+    return clips[:n.value].copy(), skipped.value
+
+
 def wav_read(path):
     """-> (pcm [n_channels][n_frames] float32, sample_rate)"""
     pcm = C.POINTER(c_float_p)()
@@ -1357,6 +1417,16 @@ def wav_write(path, pcm, sample_rate=48000, pcm16=False):
     pcm = np.ascontiguousarray(np.atleast_2d(pcm), dtype=np.float32)
     ptrs = (c_float_p * pcm.shape[0])(*[fptr(pcm[c]) for c in range(pcm.shape[0])])
     check(lib().fvad_wav_write(path.encode(), ptrs, pcm.shape[0], pcm.shape[1], sample_rate, 1 if pcm16 else 0), "fvad_wav_write")
+
+
+def wav_write_i16(path, pcm, sample_rate=48000):
+    """pcm [n_channels][n_frames] int16 -> PCM16 WAV file, the samples as they are (fvad_wav_write_i16)"""
+    pcm = np.atleast_2d(pcm)
+    assert pcm.dtype == np.int16
+    pcm = np.ascontiguousarray(pcm)
+    i16p = C.POINTER(C.c_int16)
+    ptrs = (i16p * pcm.shape[0])(*[pcm[c].ctypes.data_as(i16p) for c in range(pcm.shape[0])])
+    check(lib().fvad_wav_write_i16(path.encode(), ptrs, pcm.shape[0], pcm.shape[1], sample_rate), "fvad_wav_write_i16")
 
 
 def wav_read_i16(path):

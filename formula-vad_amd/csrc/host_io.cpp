@@ -156,11 +156,12 @@ void fvad_wav_free_i16(int16_t** channel_pcm, size_t n_channels)
 // channels and write IEEE float32 (as_pcm16 == 0) or PCM16.  The reference writes through libsndfile
 // (sf_writef_float: WAV, FLAC or Vorbis by Format); PCM16 here is libsndfile's default float -> short conversion
 // with normalisation on, lrintf(x * 32767) after clipping to [-1, 1] [external: libsndfile's f2s_clip_array].
-int fvad_wav_write(const char* path, const float* const* channel_pcm, size_t n_channels, size_t n_frames, size_t sample_rate,
-                   int as_pcm16)
+// (channel_i16: PCM16 samples written as they are, fvad_wav_write_i16; otherwise channel_pcm)
+static int wav_put(const char* path, const float* const* channel_pcm, const int16_t* const* channel_i16, size_t n_channels,
+                   size_t n_frames, size_t sample_rate, int as_pcm16)
 {
-    if (!path || (n_frames && !channel_pcm) || n_channels == 0 || n_channels > 65535 || sample_rate == 0) return FVAD_ERR_INVALID_ARGUMENT;
-    for (size_t c = 0; c < n_channels && n_frames; ++c) if (!channel_pcm[c]) return FVAD_ERR_CHANNEL_COUNT_MISMATCH;
+    if (!path || (n_frames && !channel_pcm && !channel_i16) || n_channels == 0 || n_channels > 65535 || sample_rate == 0) return FVAD_ERR_INVALID_ARGUMENT;
+    for (size_t c = 0; c < n_channels && n_frames; ++c) if (channel_i16 ? !channel_i16[c] : !channel_pcm[c]) return FVAD_ERR_CHANNEL_COUNT_MISMATCH;
     const size_t bytes_per = as_pcm16 ? 2 : 4;
     const uint64_t data_bytes = (uint64_t)n_frames * n_channels * bytes_per;
     if (data_bytes > 0xFFFFFF00ull) return FVAD_ERR_INVALID_ARGUMENT; // RIFF sizes are 32-bit
@@ -174,6 +175,11 @@ int fvad_wav_write(const char* path, const float* const* channel_pcm, size_t n_c
     size_t o = 44;
     for (size_t i = 0; i < n_frames; ++i)
         for (size_t c = 0; c < n_channels; ++c) {
+            if (channel_i16) {
+                wr16(o, (uint16_t)channel_i16[c][i]);
+                o += 2;
+                continue;
+            }
             const float x = channel_pcm[c][i];
             if (as_pcm16) {
                 const float cl = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);
@@ -191,6 +197,20 @@ int fvad_wav_write(const char* path, const float* const* channel_pcm, size_t n_c
     const size_t put = fwrite(buf.data(), 1, buf.size(), fp);
     const int cl = fclose(fp);
     return (put == buf.size() && cl == 0) ? FVAD_OK : FVAD_ERR_IO;
+}
+
+int fvad_wav_write(const char* path, const float* const* channel_pcm, size_t n_channels, size_t n_frames, size_t sample_rate,
+                   int as_pcm16)
+{
+    return wav_put(path, channel_pcm, nullptr, n_channels, n_frames, sample_rate, as_pcm16);
+}
+
+// PCM16 samples that already are PCM16 (a clip fvad_clips_export packed as FVAD_CLIP_PCM16): written without a conversion, so
+// that fvad_wav_read_i16 returns them
+int fvad_wav_write_i16(const char* path, const int16_t* const* channel_pcm, size_t n_channels, size_t n_frames, size_t sample_rate)
+{
+    if (n_frames && !channel_pcm) return FVAD_ERR_INVALID_ARGUMENT;
+    return wav_put(path, nullptr, channel_pcm, n_channels, n_frames, sample_rate, 1);
 }
 
 } // extern "C"

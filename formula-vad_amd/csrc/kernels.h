@@ -408,3 +408,36 @@ struct VadRetainArgs {
     uint32_t seg_cap;
 };
 int fvad_launch_vad_retain(const VadRetainArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ the batch Recorder (kernels_clips.hip)
+// fvad_clips_export*: a work unit is a tile of kClipTile samples of one (clip, channel).  Unit u of clip c is
+// unit_prefix[c] + channel * n_tiles + tile (the partial sums have the units' order); the gather's tiles are counted by
+// tile_prefix[c] + tile.
+constexpr int kClipTile = 8192;
+struct ClipJob {
+    uint64_t src_off;    // elements from `src` to the clip's first sample in its first lane
+    uint64_t len;        // samples
+    uint64_t out_off;    // elements from `out` to the clip's slot (a multiple of 16 bytes)
+    uint32_t first_unit; // == unit_prefix[c]
+    uint32_t n_tiles, n_channels, pad;
+};
+struct ClipInfo {        // what fvad_clips_export* reports per clip
+    int32_t best_channel;
+    float best_rms, runner_up_rms;
+    uint64_t out_offset;
+};
+struct ClipArgs {
+    const void* src;     // f32 or PCM16 lanes
+    void* out;
+    uint64_t lane_stride;
+    const ClipJob* jobs;           // [n_clips] (device)
+    const uint32_t* unit_prefix;   // [n_clips + 1]
+    const uint32_t* tile_prefix;   // [n_clips + 1]
+    double* partials;              // [n_units]
+    ClipInfo* infos;               // [n_clips]
+    uint32_t n_clips, n_units, n_tiles;
+    int src_i16, out_i16;
+};
+int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream);    // hipError_t as int
+int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream);   // (after fvad_launch_clip_rms on the same stream)
+int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick)

@@ -1,0 +1,189 @@
+// kernels_clips.hip -- the batch Recorder (fvad_clips_export*): per clip the quietest channel over [sample_from, sample_to)
+// (Recorder.findBestChannel, Recorder.zig:113-129) and that channel's samples packed into the clip's slot of one output buffer.
+//
+// Clips run from a fraction of a second to minutes, so the work unit is a tile of kClipTile samples of one (clip, channel): a
+// workgroup finds its clip by a search of a host-built prefix table with its block index (the same in every lane: scalar loads).
+// Nothing is accumulated across workgroups with atomics: clip_rms_kernel stores one f64 partial per (clip, channel, tile),
+// clip_pick_kernel adds a channel's partials in tile order.  A clip's numbers therefore depend on its own samples alone, never on
+// the other clips of the call.
+//
+// A tile is staged through LDS once: clip starts are arbitrary sample indices, so the tile's first byte has any alignment.  The
+// 16-byte aligned body strictly inside the tile is read with 16-byte loads, the elements in front of and behind it one by one
+// -- no byte outside [sample_from, sample_to) is read -- and the LDS image keeps the global address's offset within 16 bytes, so
+// that the body's LDS stores are full width too.  Every later read of the tile is by sample index within the tile.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+
+// the clip whose units [prefix[c], prefix[c + 1]) hold unit u (prefix[0] = 0, prefix[n] > u; every clip has at least one unit)
+__device__ inline uint32_t find_clip(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t u)
+{
+    uint32_t lo = 0, hi = n; // invariant: prefix[lo] <= u < prefix[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (prefix[mid] <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ inline float to_f32(float x) { return x; }
+__device__ inline float to_f32(int16_t s) { return (float)s * (1.0f / 32768.0f); } // s / 32768, exact
+
+template <typename D, typename S> struct Convert;
+template <typename T> struct Convert<T, T> { __device__ static T run(T x) { return x; } }; // equal formats: the bits
+template <> struct Convert<float, int16_t> { __device__ static float run(int16_t s) { return to_f32(s); } };
+template <> struct Convert<int16_t, float> { // fvad_lane.denoised_i16's rule (k3_istft_ola_kernel)
+    __device__ static int16_t run(float y) { return (int16_t)__builtin_rintf(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)); }
+};
+
+// n (1 .. kClipTile) elements from p into lds[shift ..), shift = p's offset within 16 bytes in elements (returned).  lds holds
+// kClipTile + 16 / sizeof(S) elements and is 16-byte aligned.  Ends with a barrier.
+template <typename S>
+__device__ inline int stage_tile(const S* __restrict__ p, int n, S* lds)
+{
+    constexpr int V = 16 / (int)sizeof(S);
+    const int t = threadIdx.x;
+    const int shift = (int)(((uintptr_t)p & 15) / sizeof(S));
+    const int head = min(n, (V - shift) % V);
+    const int nvec = (n - head) / V;
+    const uint4* pv = reinterpret_cast<const uint4*>(p + head);
+    uint4* lv = reinterpret_cast<uint4*>(lds + shift + head); // shift + head is 0 or V whenever nvec > 0
+    for (int v = t; v < nvec; v += kThreads) lv[v] = pv[v];
+    const int tail0 = head + nvec * V;
+    if (t < head) lds[shift + t] = p[t];
+    if (t < n - tail0) lds[shift + tail0 + t] = p[tail0 + t];
+    __syncthreads();
+    return shift;
+}
+
+template <typename S>
+__device__ inline void rms_tile(const ClipArgs& a, S* lds, double* wsum)
+{
+    const uint32_t u = blockIdx.x;
+    const ClipJob j = a.jobs[find_clip(a.unit_prefix, a.n_clips, u)];
+    const uint32_t r = u - j.first_unit;
+    const uint32_t ch = r / j.n_tiles, k = r % j.n_tiles;
+    const uint64_t e0 = (uint64_t)k * kClipTile;
+    const int n = (int)min((uint64_t)kClipTile, j.len - e0);
+    const S* p = static_cast<const S*>(a.src) + j.src_off + (uint64_t)ch * a.lane_stride + e0;
+    const int shift = stage_tile(p, n, lds);
+    // fixed order: a thread adds its samples t, t + 256, ... one after the other, then the tree below
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int e = t; e < n; e += kThreads) {
+        const double x = (double)to_f32(lds[shift + e]); // the product of two f32 is exact in f64
+        s += x * x;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((t & 63) == 0) wsum[t >> 6] = s;
+    __syncthreads();
+    if (t == 0) a.partials[u] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+template <typename D, typename S>
+__device__ inline void gather_tile(const ClipArgs& a, S* lds)
+{
+    constexpr int G = 8; // samples per thread and step: one 16-byte store of PCM16, two of f32
+    const uint32_t g = blockIdx.x;
+    const uint32_t c = find_clip(a.tile_prefix, a.n_clips, g);
+    const ClipJob j = a.jobs[c];
+    const uint32_t k = g - a.tile_prefix[c];
+    const uint32_t ch = (uint32_t)a.infos[c].best_channel;
+    const uint64_t e0 = (uint64_t)k * kClipTile;
+    const int n = (int)min((uint64_t)kClipTile, j.len - e0);
+    const S* p = static_cast<const S*>(a.src) + j.src_off + (uint64_t)ch * a.lane_stride + e0;
+    const int shift = stage_tile(p, n, lds);
+    D* out = static_cast<D*>(a.out) + j.out_off + e0; // 16-byte aligned: the slot is, and kClipTile is a multiple of G
+    for (int q = threadIdx.x * G; q < n; q += kThreads * G) {
+        if (q + G <= n) {
+            alignas(16) D v[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) v[i] = Convert<D, S>::run(lds[shift + q + i]);
+            constexpr int NV = G * (int)sizeof(D) / 16;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) reinterpret_cast<uint4*>(out + q)[i] = reinterpret_cast<const uint4*>(v)[i];
+        } else { // the clip's last samples: nothing is written past the clip
+            for (int i = q; i < n; ++i) out[i] = Convert<D, S>::run(lds[shift + i]);
+        }
+    }
+}
+
+} // namespace
+
+template <typename S>
+__global__ __launch_bounds__(kThreads) void clip_rms_kernel(ClipArgs a)
+{
+    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
+    __shared__ double wsum[kThreads / 64];
+    rms_tile<S>(a, lds, wsum);
+}
+
+// one lane per clip: rms = (float)sqrt(sum / n) per channel, the channel's partials added in tile order; the pick is
+// Recorder.findBestChannel's (strict <, in channel order, from 9999: the lowest index wins a tie)
+__global__ __launch_bounds__(64) void clip_pick_kernel(ClipArgs a)
+{
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= a.n_clips) return;
+    const ClipJob j = a.jobs[c];
+    auto rms_of = [&](uint32_t ch) {
+        const double* p = a.partials + j.first_unit + (uint64_t)ch * j.n_tiles;
+        double s = 0.0;
+        for (uint32_t k = 0; k < j.n_tiles; ++k) s += p[k];
+        return (float)sqrt(s / (double)j.len);
+    };
+    uint32_t best = 0;
+    float best_vol = 9999.0f, rms0 = 0.0f;
+    for (uint32_t ch = 0; ch < j.n_channels; ++ch) {
+        const float vol = rms_of(ch);
+        if (ch == 0) rms0 = vol;
+        if (vol < best_vol) { best = ch; best_vol = vol; }
+    }
+    const float best_rms = best == 0 ? rms0 : best_vol; // (channel 0 also stands when no channel is below 9999)
+    float runner = best_rms;
+    bool have = false;
+    for (uint32_t ch = 0; ch < j.n_channels; ++ch) {
+        if (ch == best) continue;
+        const float vol = rms_of(ch);
+        if (!have || vol < runner) { runner = vol; have = true; }
+    }
+    ClipInfo o;
+    o.best_channel = (int32_t)best;
+    o.best_rms = best_rms;
+    o.runner_up_rms = runner;
+    o.out_offset = j.out_off;
+    a.infos[c] = o;
+}
+
+template <typename D, typename S>
+__global__ __launch_bounds__(kThreads) void clip_gather_kernel(ClipArgs a)
+{
+    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
+    gather_tile<D, S>(a, lds);
+}
+
+int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream)
+{
+    if (a.src_i16) hipLaunchKernelGGL(clip_rms_kernel<int16_t>, dim3(a.n_units), dim3(kThreads), 0, stream, a);
+    else hipLaunchKernelGGL(clip_rms_kernel<float>, dim3(a.n_units), dim3(kThreads), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(clip_pick_kernel, dim3((a.n_clips + 63) / 64), dim3(64), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream)
+{
+    const dim3 grid(a.n_tiles), block(kThreads);
+    if (a.src_i16 && a.out_i16) hipLaunchKernelGGL((clip_gather_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
+    else if (a.src_i16) hipLaunchKernelGGL((clip_gather_kernel<float, int16_t>), grid, block, 0, stream, a);
+    else if (a.out_i16) hipLaunchKernelGGL((clip_gather_kernel<int16_t, float>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((clip_gather_kernel<float, float>), grid, block, 0, stream, a);
+    return (int)hipGetLastError();
+}

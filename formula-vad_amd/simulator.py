@@ -4,6 +4,8 @@ on top of the C ABI -- SURVEY.md section 8 f1/f3.  Plumbing only (JSON, paths, t
 the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
 
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
+    python -m ... simulator.py -i plan.json --export-clips DIR [--clips-pcm16]   (or: run_clips(path, DIR): the plan's speech
+                                                      clips, original and denoised, cut and picked on the GPU)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
     python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
                                                       parameter grid, every machine scored on the GPU, the top K configs by
@@ -194,30 +196,37 @@ def _run_instances(ctx, plan, audio):
     min_bin = int(np.round(np.float32(vm.get("speech_min_freq", 500.0)) / bin_w))
     max_bin = int(np.round(np.float32(vm.get("speech_max_freq", 2000.0)) / bin_w))
     res = ctx.engine_run(lanes, min_bin=min_bin, max_bin=max_bin, fft_size=plan["fft_size"])
-    # host stage: the library's batched form (frame metadata + VAD state machine), one call per instance (instances differ
-    # in length and channel count) -- the instances side by side on host threads, like the reference's thread per file
-    # (simulator.zig:221-232): a two-hour stream's state machine is 36 ms on one core, 21 of them one after the other were
-    # as long as the GPU's part of the plan
-    from concurrent.futures import ThreadPoolExecutor
     first = np.cumsum([0] + [pcm.shape[0] for pcm in audio])
 
     def host_stage(i):
-        C_ = audio[i].shape[0]
-        r = res[first[i]:first[i] + C_]
-        band = np.ascontiguousarray(np.stack([x["band_sum"] for x in r]))      # [channel][frame]
-        rms = np.ascontiguousarray(np.stack([x["chunk_rms"] for x in r]))
-        vb = fv.VadBatch(1, n_channels=C_, fft_size=plan["fft_size"], overrides=vm)
-        try:
-            segs = vb.run(band, rms)[0] if band.shape[1] else []
-            return segs, vb.audit(0)
-        finally:
-            vb.close()
+        r = res[first[i]:first[i] + audio[i].shape[0]]
+        return _vad_host_stage(plan, np.stack([x["band_sum"] for x in r]), np.stack([x["chunk_rms"] for x in r]))
 
-    n_workers = max(1, min(len(audio), os.cpu_count() or 1, 16))
+    return _map_instances(host_stage, len(audio))
+
+
+def _vad_host_stage(plan, band, rms):
+    """The host stage of one instance: the library's batched form (frame metadata + VAD state machine) over the engine's band
+    sums [channel][frame] and chunk RMS [channel][chunk] -> (segments, audit)"""
+    band, rms = np.ascontiguousarray(band), np.ascontiguousarray(rms)
+    vb = fv.VadBatch(1, n_channels=band.shape[0], fft_size=plan["fft_size"], overrides=plan["vad_machine_config"])
+    try:
+        segs = vb.run(band, rms)[0] if band.shape[1] else []
+        return segs, vb.audit(0)
+    finally:
+        vb.close()
+
+
+def _map_instances(host_stage, n):
+    """host_stage(i) for every instance, side by side on host threads, like the reference's thread per file
+    (simulator.zig:221-232): a two-hour stream's state machine is 36 ms on one core, 21 of them one after the other were
+    as long as the GPU's part of the plan (instances differ in length and channel count: one call each)"""
+    from concurrent.futures import ThreadPoolExecutor
+    n_workers = max(1, min(n, os.cpu_count() or 1, 16))
     if n_workers == 1:
-        return [host_stage(i) for i in range(len(audio))]
+        return [host_stage(i) for i in range(n)]
     with ThreadPoolExecutor(max_workers=n_workers) as pool:
-        return list(pool.map(host_stage, range(len(audio))))
+        return list(pool.map(host_stage, range(n)))
 
 
 def _read_instance(inst):
@@ -248,6 +257,35 @@ def instance_shares(n_instances, n_devices):
     """How run_plan and run_grid deal a plan's instances to n_devices contexts: instance i to share i % n_devices, each share
     in plan order -> [[instance]] per share (a share may be empty)"""
     return [[i for i in range(n_instances) if i % n_devices == d] for d in range(n_devices)]
+
+
+def _evaluate(plan, per_inst, refs):
+    """Evaluator + statistics + the report of a plan's per-instance (segments, audit), and the files of output_dir
+    (simulator.zig:127-132,157-168) -> (report text, per-instance results)"""
+    vm = plan["vad_machine_config"]
+    # --- Evaluator + statistics (simulator.zig:127-132)
+    stat_cfg = {"ignore_shorter_than_sec": float(np.float32(vm.get("min_vad_duration_sec", 0.7))),
+                "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
+    names, stats, results = [], [], []
+    for inst, (segs, audit), ref in zip(plan["instances"], per_inst, refs):
+        secs = [(float(np.float32(s[0]) / np.float32(48000)), float(np.float32(s[1]) / np.float32(48000))) for s in segs]
+        infos = ["vr:{} vad:{}s".format(zig_fixed(s[2], 2), zig_fixed(s[3], 1)) for s in segs]  # SimulationInstance.zig:240-244
+        st = fv.stats_from_segments(secs, ref, stat_cfg)
+        names.append(inst["name"])
+        stats.append(st)
+        results.append({"name": inst["name"], "segments": segs, "segments_sec": secs, "debug_info": infos,
+                        "stats": st, "audacity": audacity_txt(secs, infos, ref, stat_cfg), "audit": audit})
+    agg = fv.stats_aggregate(stats)
+    text = report_text(names, stats, agg)
+    if plan["output_dir"]:
+        out_dir = os.path.join(plan["base_path"], plan["output_dir"], str(int(time.time())))  # simulator.zig:157-168
+        os.makedirs(out_dir, exist_ok=True)
+        for r in results:
+            with open(os.path.join(out_dir, f"{r['name']}-audacity.txt"), "w") as f:
+                f.write(r["audacity"])
+        with open(os.path.join(out_dir, "report.txt"), "w") as f:
+            f.write(text)
+    return text, results
 
 
 def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None):
@@ -305,29 +343,7 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
         for i, r in zip(parts[d], done[d]):
             per_inst[i] = r
     elapsed = time.perf_counter() - t0
-    vm = plan["vad_machine_config"]
-    # --- Evaluator + statistics (simulator.zig:127-132)
-    stat_cfg = {"ignore_shorter_than_sec": float(np.float32(vm.get("min_vad_duration_sec", 0.7))),
-                "extrude_start": 5.0, "extrude_end": 10.0, "fill_gaps": 5.0}
-    names, stats, results = [], [], []
-    for inst, (segs, audit), ref in zip(plan["instances"], per_inst, refs):
-        secs = [(float(np.float32(s[0]) / np.float32(48000)), float(np.float32(s[1]) / np.float32(48000))) for s in segs]
-        infos = ["vr:{} vad:{}s".format(zig_fixed(s[2], 2), zig_fixed(s[3], 1)) for s in segs]  # SimulationInstance.zig:240-244
-        st = fv.stats_from_segments(secs, ref, stat_cfg)
-        names.append(inst["name"])
-        stats.append(st)
-        results.append({"name": inst["name"], "segments": segs, "segments_sec": secs, "debug_info": infos,
-                        "stats": st, "audacity": audacity_txt(secs, infos, ref, stat_cfg), "audit": audit})
-    agg = fv.stats_aggregate(stats)
-    text = report_text(names, stats, agg)
-    if plan["output_dir"]:
-        out_dir = os.path.join(plan["base_path"], plan["output_dir"], str(int(time.time())))  # simulator.zig:157-168
-        os.makedirs(out_dir, exist_ok=True)
-        for r in results:
-            with open(os.path.join(out_dir, f"{r['name']}-audacity.txt"), "w") as f:
-                f.write(r["audacity"])
-        with open(os.path.join(out_dir, "report.txt"), "w") as f:
-            f.write(text)
+    text, results = _evaluate(plan, per_inst, refs)
     if out is not None:
         out.write(text)
         audio_s = sum(p.shape[1] for p in audio) / 48000.0
@@ -336,6 +352,120 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
         for c in ctxs:
             c.close()
     return text, results
+
+
+def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
+    """run_clips for the instances of one context -> [(segments, audit, manifest)] in the order given"""
+    if not audio:
+        return []
+    held = []
+
+    def dalloc(nbytes):
+        held.append(ctx.device_alloc(max(int(nbytes), 4)))
+        return held[-1]
+
+    try:
+        F, chunk = plan["fft_size"], 24000
+        r = _denoise_resident(ctx, audio, F, plan["vad_machine_config"], dalloc)
+        band = np.zeros((r.n_lanes, max(r.nf_all, 1)), np.float32)
+        if r.nf_all:
+            ctx.to_host(band, r.d_band0)
+        lane0, l = {}, 0
+        for i in r.order:
+            lane0[i] = l
+            l += audio[i].shape[0]
+
+        def host_stage(i):
+            C_, nck = audio[i].shape[0], r.n_chunks[i]
+            return _vad_host_stage(plan, band[lane0[i]:lane0[i] + C_, :nck * chunk // F], r.rms[lane0[i]:lane0[i] + C_, :nck])
+
+        per_inst = _map_instances(host_stage, len(audio))
+        # one export per kind over every instance's clips: the reference's two recorders, each picking from its own audio
+        kinds = (("original", r.d_pcm, r.stride, r.n_samples, [a.shape[1] for a in audio]),
+                 ("denoised", r.d_den, r.n_den, r.n_den, [n * chunk for n in r.n_chunks]))
+        manifests = [{"name": inst["name"], "sample_rate": 48000, "pcm16": bool(pcm16), "clips": [
+            {"segment": k, "start": int(s[0]), "length": int(s[1] - s[0])} for k, s in enumerate(segs)]} for inst, (segs, _) in zip(insts, per_inst)]
+        for kind, d_src, stride, n_samples, avail in kinds:
+            rows, owner = [], []
+            for i, (segs, _) in enumerate(per_inst):
+                clips, skipped = fv.clips_from_segments(segs, lane0[i], audio[i].shape[0], avail[i])
+                manifests[i][f"{kind}_skipped"] = skipped
+                rows.append(clips)
+                k = 0
+                for c in clips:   # the clips are the kept segments, in order
+                    while (segs[k][0], segs[k][1]) != (c[2], c[3]):
+                        k += 1
+                    owner.append((i, k))
+                    k += 1
+            rows = np.concatenate(rows) if rows else np.zeros((0, fv.CLIP_FIELDS), np.uint64)
+            if not rows.shape[0]:
+                continue
+            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16)
+            for j, (i, k) in enumerate(owner):
+                o, n = int(res["offsets"][j]), int(rows[j, 3] - rows[j, 2])
+                path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], k, kind))
+                if pcm16:
+                    fv.wav_write_i16(path, res["out"][o:o + n])
+                else:
+                    fv.wav_write(path, res["out"][o:o + n])
+                manifests[i]["clips"][k][kind] = {"file": os.path.basename(path), "best_channel": int(res["best_channel"][j]),
+                                                  "best_rms": float(res["best_rms"][j]), "runner_up_rms": float(res["runner_up_rms"][j])}
+        return [(segs, audit, m) for (segs, audit), m in zip(per_inst, manifests)]
+    finally:
+        for d in held:
+            ctx.device_free(d)
+
+
+def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None):
+    """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
+    single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
+    GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
+    device-resident (_denoise_resident), the plan's vad_machine_config per instance (run_plan's host stage),
+    fvad_clips_from_segments, one export of the original and one of the denoised clips, then
+    NAME-####-original.wav / NAME-####-denoised.wav (float32, or PCM16 with pcm16) and NAME-clips.json per instance in out_dir:
+    per segment its start and length in samples and, of each kind, the file, the best channel and both RMS values; a kind whose
+    audio ends before the segment does has no entry there and is counted in KIND_skipped (the denoised audio ends with the last
+    whole chunk).  Returns run_plan's (report text, results), each result with its manifest under "clips".
+    Segments and report are run_plan's whenever both passes select the same NSNet2 kernels (fvad_ctx_last_nn_path): the resident
+    pass pads every lane to the longest instance, so a plan of unequal lengths may be cut into other launches (the context option
+    "reproducible" makes the two agree bit for bit for every plan)."""
+    plan = load_plan(plan_path)
+    own_ctx = ctx is None
+    ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])] if own_ctx else [ctx]
+    try:
+        os.makedirs(out_dir, exist_ok=True)
+        loaded = [_read_instance(i) for i in plan["instances"]]
+        audio, refs = [a for a, _ in loaded], [r for _, r in loaded]
+        parts = instance_shares(len(audio), len(ctxs))
+        done, errs = [None] * len(ctxs), []
+
+        def work(d):
+            try:
+                done[d] = _clips_share(ctxs[d], plan, [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]], out_dir, pcm16)
+            except Exception as e:  # re-raised below, in the caller's thread
+                errs.append(e)
+
+        th = [threading.Thread(target=work, args=(d,)) for d in range(len(ctxs))]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        if errs:
+            raise errs[0]
+        per_inst = [None] * len(audio)
+        for d, part in enumerate(parts):
+            for i, x in zip(part, done[d]):
+                per_inst[i] = x
+        text, results = _evaluate(plan, [(segs, audit) for segs, audit, _ in per_inst], refs)
+        for res, (_, _, manifest) in zip(results, per_inst):
+            res["clips"] = manifest
+            with open(os.path.join(out_dir, f"{manifest['name']}-clips.json"), "w") as f:
+                json.dump(manifest, f, indent=1)
+        return text, results
+    finally:
+        if own_ctx:
+            for c in ctxs:
+                c.close()
 
 
 SWEEP_COLUMNS = ("P", "TP", "FP", "FN", "TPR", "PPV", "FNR", "FDR", "F", "FM")
@@ -429,12 +559,22 @@ def _engine_opts(config0, F):
     return opts
 
 
+_Resident = collections.namedtuple("_Resident", "groups order n_chunks n_lanes n_samples stride n_den nf_all d_pcm d_den d_band0 rms")
+
+
 def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
+    """_denoise_resident as the sweeps take it: (groups, n_chunks, n_den, nf_all, d_den, chunk RMS)"""
+    r = _denoise_resident(ctx, audio, F, config0, dalloc)
+    return r.groups, r.n_chunks, r.n_den, r.nf_all, r.d_den, r.rms
+
+
+def _denoise_resident(ctx, audio, F, config0, dalloc):
     """The denoising pass of a sweep: every channel of every instance is one lane of ONE device batch (ragged lengths padded to
     the longest: chunks are causal, so padding changes no real chunk), fvad_engine_enqueue_device with the denoised audio kept
     (device memory from dalloc).  Instances are grouped by channel count (a VAD batch has one channel count), each group's lanes
-    side by side.  Returns (groups {n_channels: [instance]}, n_chunks [instance], n_den samples per lane, nf_all frames per
-    lane, d_den, chunk RMS [lane][chunk] on the host)."""
+    side by side.  Returns a _Resident: groups {n_channels: [instance]}, order (the instances in lane order), n_chunks [instance],
+    the original lanes d_pcm (n_lanes of n_samples f32, `stride` apart), the denoised lanes d_den (n_den samples each), config 0's
+    band sums d_band0 [lane][nf_all], chunk RMS [lane][chunk] on the host."""
     chunk = 24000
     lens = [p.shape[1] for p in audio]
     n_chunks = [n // chunk for n in lens]
@@ -471,7 +611,7 @@ def _denoise_for_sweep(ctx, audio, F, config0, dalloc):
     rms = np.zeros((n_lanes, max(n_ck, 1)), np.float32)
     if n_ck:
         ctx.to_host(rms, d_rms)
-    return groups, n_chunks, n_den, nf_all, d_den, rms
+    return _Resident(groups, order, n_chunks, n_lanes, L, stride, n_den, nf_all, d_pcm, d_den, d_band0, rms)
 
 
 # What every share of a sweep needs (run_grid makes one per call; run_sweep one without scoring): the configs, their Evaluator
@@ -1580,6 +1720,10 @@ def arg_parser():
                     help="with --sweep / --sweep-grid and --vad-chain coop: one device VAD machine per config (the default) or one "
                          "trigger machine per distinct trigger and a finishing kernel per config (context option vad_trigger); "
                          "same results")
+    ap.add_argument("--export-clips", default=None, metavar="DIR",
+                    help="run the plan and write every completed segment's original and denoised clip (the quietest channel, cut and "
+                         "picked on the GPU) and a NAME-clips.json manifest per instance into DIR")
+    ap.add_argument("--clips-pcm16", action="store_true", help="with --export-clips: the clips as PCM16 (half the bytes over PCIe)")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -1593,6 +1737,10 @@ def main(argv=None):
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
                  overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs, vad_trigger=a.vad_trigger)
+        return
+    if a.export_clips:
+        text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices)
+        sys.stdout.write(text)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs,

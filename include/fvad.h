@@ -772,6 +772,59 @@ size_t fvad_pipeline_n_fft_frames(const fvad_pipeline *p);
 int fvad_pipeline_trace(const fvad_pipeline *p, float *band_volumes, float *vol_ratio,
                         size_t cap_frames);
 
+/* ------------------------------------------------------------------ batch Recorder: speech clips of device-resident lanes
+ * What Recorder.finalize hands to AudioPipeline.Callbacks (Recorder.zig:74-164, AudioPipeline.zig:187-191), for the batch
+ * paths (fvad_engine_run, fvad_engine_enqueue_device*): given clip ranges over lanes that are already on the device, every
+ * channel's RMS over every clip, the quietest channel as Recorder.findBestChannel picks it (Recorder.zig:113-129), and that
+ * channel's samples packed into one buffer -- so that only the clips cross PCIe, not the corpus (csrc/kernels_clips.hip).
+ * - A clip is a row of FVAD_CLIP_FIELDS uint64: first_lane, n_channels, sample_from, sample_to.  Its channels are lanes
+ *   first_lane .. first_lane + n_channels - 1, its samples [sample_from, sample_to).  Clips may overlap and repeat.
+ * - Sample formats: FVAD_CLIP_F32 or FVAD_CLIP_PCM16, for the source lanes and for the packed output independently.  Equal
+ *   formats copy bits; PCM16 -> f32 is s / 32768; f32 -> PCM16 is rint(clamp(y * 32768, -32768, 32767)), as for
+ *   fvad_lane.denoised_i16.
+ * - Per clip the calls report (each array has n_clips entries, host memory, any may be NULL): best_channel, relative to
+ *   first_lane; best_rms, that channel's (float)sqrt(sum of squares / n), the sum in f64; runner_up_rms, the smallest RMS among
+ *   the other channels (best_rms for a mono clip) -- how close the pick was, in the spirit of fvad_vad_audit; out_offsets, the
+ *   clip's slot in the output in samples.  The pick is strict `<` in channel order: the lowest index wins a tie.  The reference
+ *   sums the squares sequentially in f32 (audio_utils.zig:14-24); channels whose RMS differ by less than that sum's round-off
+ *   can be picked differently, and runner_up_rms shows which clips those are.
+ * - INVARIANT: a clip's info and samples are the same bits whatever else is in the call and in whatever order, run after run
+ *   (no atomics; each clip's sums have a fixed order).  A caller short of memory can export in batches.
+ * - Deviation from the live pipeline: the batch form gives a clip to every segment whose end the data reaches.  It does not
+ *   replay MRBRecorder's drop of a pending clip when a recording restarts before the ring has delivered it
+ *   (MRBRecorder.zig:76-118), an artefact of the 10 s ring on the write schedule that fvad_pipeline_* keeps.  With
+ *   max_speech_gap_sec >= 2 (the default) the two agree except at a stream's end.
+ *
+ * fvad_clips_plan (host only): offsets[i] = clip i's slot and *total = the output's size, in samples of out_format; every slot
+ * starts on a 16-byte boundary.  FVAD_ERR_INVALID_ARGUMENT for sample_to <= sample_from, n_channels == 0, a bad format or NULLs.
+ * fvad_clips_from_segments (host only): one clip (first_lane, n_channels, the segment's range) per segment whose sample_to <=
+ * n_available, in order; the others are counted in *n_skipped -- the reference never finalises a recording whose end the stream
+ * does not reach.  n_available is the lane's n_samples for the original audio and n_chunks * 24000 for the denoised audio.
+ * *n_out = the clips the segments give; FVAD_ERR_BUFFER_TOO_SMALL when cap is below it (the first cap are written; clips may be
+ * NULL with cap 0 to count).  FVAD_ERR_INVALID_ARGUMENT for n_channels == 0, NULL counts or a segment with sample_to <= sample_from.
+ * fvad_clips_export_device: d_src holds n_lanes lanes of n_samples (lane l at d_src + l * lane_stride samples), as
+ * fvad_engine_enqueue_device* lays them out; d_out (device, 16-byte aligned) has room for out_capacity samples.  Every error
+ * comes back before any launch: FVAD_ERR_OUT_OF_RANGE for sample_to > n_samples or lanes past n_lanes,
+ * FVAD_ERR_BUFFER_TOO_SMALL when out_capacity is below the plan's total, FVAD_ERR_INVALID_ARGUMENT for NULLs, bad formats, a
+ * misaligned d_out and what fvad_clips_plan refuses.  n_clips == 0 does nothing and succeeds.  The kernels read nothing outside
+ * the clips' ranges and write nothing outside the clips' samples (the padding between slots is left alone).  Returns when the
+ * clips are in d_out.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_gather.  Original and denoised audio are two
+ * calls: the reference has two independent recorders, each picking from its own audio.
+ * fvad_clips_export: the same into host memory `out` -- a device staging buffer of the plan's size, one copy back, then freed;
+ * the padding between slots comes back as zeros. */
+enum { FVAD_CLIP_F32 = 0, FVAD_CLIP_PCM16 = 1 };
+#define FVAD_CLIP_FIELDS 4
+int fvad_clips_plan(const uint64_t *clips, size_t n_clips, int out_format, uint64_t *offsets, uint64_t *total);
+int fvad_clips_from_segments(const fvad_speech_segment *segs, size_t n_segs, uint32_t first_lane, uint32_t n_channels,
+                             uint64_t n_available, uint64_t *clips, size_t cap, size_t *n_out, size_t *n_skipped);
+int fvad_clips_export_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                             size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                             size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                             uint64_t *out_offsets);
+int fvad_clips_export(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                      const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                      int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets);
+
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
 typedef struct {
@@ -857,6 +910,10 @@ void fvad_wav_free_i16(int16_t **channel_pcm, size_t n_channels);
  * callback does with its clip (main.zig saves them): planar channels -> float32 (as_pcm16 == 0) or PCM16 WAV. */
 int fvad_wav_write(const char *path, const float *const *channel_pcm, size_t n_channels,
                    size_t n_frames, size_t sample_rate, int as_pcm16);
+/* The same for samples that already are PCM16 (clips packed by fvad_clips_export as FVAD_CLIP_PCM16, whose rule is not
+ * libsndfile's): written as they are, so that fvad_wav_read_i16 returns them. */
+int fvad_wav_write_i16(const char *path, const int16_t *const *channel_pcm, size_t n_channels, size_t n_frames,
+                       size_t sample_rate);
 
 #ifdef __cplusplus
 }
