@@ -23,6 +23,8 @@ const std = @import("std");
 
 pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
+pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
+pub const wav_info_fields = 6; // FVAD_WAV_INFO_FIELDS: format, n_channels, sample_rate, data_offset, n_frames, bits
 pub const clip_fields = 4; // FVAD_CLIP_FIELDS: a clip is a row of first_lane, n_channels, sample_from, sample_to (u64 each)
 
 // ------------------------------------------------------------------ status codes (the anonymous enum of fvad.h)
@@ -61,6 +63,9 @@ pub const Status = struct {
     pub const rec_aborted = 3;
     pub const clip_f32 = 0;
     pub const clip_pcm16 = 1;
+    pub const ingest_f32 = 0;
+    pub const ingest_pcm16 = 1;
+    pub const ingest_pcm24 = 2;
 };
 
 // ------------------------------------------------------------------ opaque handles
@@ -410,6 +415,11 @@ pub extern "c" fn fvad_clips_export_device(ctx: *Ctx, d_src: *const anyopaque, s
 pub extern "c" fn fvad_clips_export(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
 
 // audio file input / output (host)
+// device-side ingest: interleaved PCM16 / PCM24 / f32 bytes de-interleaved, decoded and zero-padded into planar device lanes
+pub extern "c" fn fvad_wav_probe(path: [*:0]const u8, info: [*]u64) c_int;
+pub extern "c" fn fvad_ingest_check(sources: ?[*]const u64, n_sources: usize, raw_bytes: u64, out_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_ingest_device(ctx: *Ctx, d_raw: ?*const anyopaque, raw_bytes: u64, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_ingest(ctx: *Ctx, src_host: ?[*]const ?*const anyopaque, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;

@@ -26,6 +26,12 @@ FVAD_ERR_MODEL_FORMAT = -104
 FVAD_ERR_NOT_AVAILABLE = -107
 CLIP_F32, CLIP_PCM16 = 0, 1      # sample formats of fvad_clips_*
 CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, sample_to (uint64 each)
+INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
+INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
+WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
+INGEST_SAMPLE_BYTES = {INGEST_F32: 4, INGEST_PCM16: 2, INGEST_PCM24: 3}
+INGEST_TILE_BYTES = 16384        # kIngestTileBytes (csrc/kernels.h): the source bytes a workgroup of the ingest kernel takes
+INGEST_FILL_TILE = 8192          # kIngestFillTile: the zeros of one lane a workgroup writes
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
 
 
@@ -318,6 +324,10 @@ SIGNATURES = {
                                            c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
     "fvad_clips_export": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
                                     c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fvad_wav_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
+    "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
+    "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
+    "fvad_ingest": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
 }
 
 _lib = None
@@ -674,6 +684,34 @@ class Context:
                  "fvad_clips_export")
         res["out"] = out[:total]
         return res
+
+    def ingest(self, sources, out_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, raw=None, raw_bytes=None):
+        """fvad_ingest_device (raw: a device address holding raw_bytes bytes) or fvad_ingest (raw: a list with one C-contiguous
+        numpy / memmap byte buffer per source, or None for a source without frames; a source's byte_offset is relative to its
+        own buffer): sources [n][INGEST_FIELDS] uint64 -> the planar lanes at device address d_lanes (float32, or int16 with
+        out_pcm16), n_lanes of n_samples, lane_stride apart.  Returns when the lanes are written."""
+        sources = _ingest_rows(sources)
+        n = sources.shape[0]
+        fmt = INGEST_PCM16 if out_pcm16 else INGEST_F32
+        rows = sources.ctypes.data_as(C.POINTER(C.c_uint64))
+        if isinstance(raw, (list, tuple)):
+            if len(raw) != n:
+                raise ValueError(f"ingest: {n} sources, {len(raw)} buffers")
+            ptrs = (vp * max(n, 1))()
+            for i, b in enumerate(raw):
+                if b is None or b.size == 0 or int(sources[i, 1]) == 0:   # no frames: no byte is read, whatever byte_offset says
+                    ptrs[i] = None
+                    continue
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"]:
+                    raise ValueError("ingest: a source's bytes are a C-contiguous uint8 array")
+                need = int(sources[i, 0]) + int(sources[i, 1]) * int(sources[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sources[i, 3]), 4)
+                if need > b.size:   # (the library cannot know where a host buffer ends)
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_ingest", f"source {i} reads {need} bytes of a buffer of {b.size}")
+                ptrs[i] = b.ctypes.data
+            self._ck(lib().fvad_ingest(self.h, ptrs, rows, n, fmt, vp(d_lanes), n_lanes, lane_stride, n_samples), "fvad_ingest")
+            return
+        self._ck(lib().fvad_ingest_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, fmt, vp(d_lanes), n_lanes, lane_stride,
+                                          n_samples), "fvad_ingest_device")
 
     def lane_state(self):
         s = vp()
@@ -1394,6 +1432,41 @@ def clips_from_segments(segs, first_lane, n_channels, n_available, cap=None):
                                          clips.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n), C.byref(skipped)),
           "fvad_clips_from_segments")
     return clips[:n.value].copy(), skipped.value
+
+
+def _ingest_rows(sources):
+    return np.ascontiguousarray(np.asarray(sources, np.uint64).reshape(-1, INGEST_FIELDS))
+
+
+def ingest_tile_frames(n_channels, fmt):
+    """frames of a source per workgroup of the ingest kernel: INGEST_TILE_BYTES rounded down to whole frames, in fours"""
+    return INGEST_TILE_BYTES // (n_channels * INGEST_SAMPLE_BYTES[fmt]) // 4 * 4
+
+
+def ingest_check(sources, raw_bytes, out_pcm16, n_lanes, lane_stride, n_samples):
+    """fvad_ingest_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sources = _ingest_rows(sources)
+    return lib().fvad_ingest_check(sources.ctypes.data_as(C.POINTER(C.c_uint64)), sources.shape[0], int(raw_bytes),
+                                   INGEST_PCM16 if out_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def wav_probe(path):
+    """fvad_wav_probe: a WAV file's header without its samples -> dict(format [INGEST_*], n_channels, sample_rate, data_offset,
+    n_frames, bits).  PCM16, PCM24 and 32-bit float; whatever else fvad_wav_read refuses raises FvadError."""
+    info = (C.c_uint64 * WAV_INFO_FIELDS)()
+    check(lib().fvad_wav_probe(path.encode(), info), f"fvad_wav_probe({path})")
+    return dict(zip(("format", "n_channels", "sample_rate", "data_offset", "n_frames", "bits"), (int(x) for x in info)))
+
+
+def wav_map_raw(path):
+    """A WAV file's data chunk as bytes, not read: (raw, info) -- raw a read-only uint8 numpy memmap of the n_frames *
+    n_channels * bits / 8 bytes of its whole frames, interleaved as in the file (what Context.ingest takes), info wav_probe's
+    dict.  Takes 24-bit PCM too, which wav_map refuses."""
+    info = wav_probe(path)
+    n = info["n_frames"] * info["n_channels"] * (info["bits"] // 8)
+    if n == 0:
+        return np.zeros(0, np.uint8), info
+    return np.memmap(path, dtype=np.uint8, mode="r", offset=info["data_offset"], shape=(n,)), info
 
 
 def wav_read(path):

@@ -145,6 +145,10 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
         long c = def.copy_threads;
         if (!unset && (!to_long(c) || c < 1 || c > 256)) return FVAD_ERR_INVALID_ARGUMENT;
         tn.copy_threads = (int)c;
+    } else if (name == "ingest_ring_bytes") {
+        long c = (long)def.ingest_ring_bytes;
+        if (!unset && (!to_long(c) || c < 1024 || c > (1l << 30) || c % 16 != 0)) return FVAD_ERR_INVALID_ARGUMENT;
+        tn.ingest_ring_bytes = (unsigned long long)c;
     } else if (name == "ws_spin_ticks") {
         if (unset) { tn.ws_spin_ticks = def.ws_spin_ticks; tn.ws_spin_auto = true; }
         else {
@@ -336,7 +340,7 @@ int fvad_ctx_create(int device, fvad_ctx** out)
     VadFftPlan pl;
     if (get_vad_plan(ctx, kVadFft, &pl) != FVAD_OK) { fvad_ctx_destroy(ctx); return FVAD_ERR_HIP; }
     // the tuning variables FVAD_<NAME> are read here, once; a bad value fails the creation rather than being ignored
-    for (const char* opt : {"nn_math", "gru_kernel", "gemm_kernel", "h3_waves", "max_chunks", "copy_threads", "ws_spin_ticks",
+    for (const char* opt : {"nn_math", "gru_kernel", "gemm_kernel", "h3_waves", "max_chunks", "copy_threads", "ingest_ring_bytes", "ws_spin_ticks",
                             "no_pipeline", "run_groups", "trace_run", "trace_kernels", "reproducible", "vad_chain", "vad_avgs", "vad_trigger"}) {
         std::string env = std::string("FVAD_") + opt;
         for (char& c : env) c = (char)toupper((unsigned char)c);
@@ -377,6 +381,11 @@ void fvad_ctx_destroy(fvad_ctx* ctx)
     for (Workspace::PinSmall* r : {&ws.small_in, &ws.small_out}) {
         if (r->base) hipHostFree(r->base);
         if (r->ev) hipEventDestroy(r->ev);
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (ws.ingest.pin[k]) hipHostFree(ws.ingest.pin[k]);
+        if (ws.ingest.dev[k]) hipFree(ws.ingest.dev[k]);
+        if (ws.ingest.ev[k]) hipEventDestroy(ws.ingest.ev[k]);
     }
     if (ws.graph.exec) hipGraphExecDestroy(ws.graph.exec);
     if (ws.graph.graph) hipGraphDestroy(ws.graph.graph);

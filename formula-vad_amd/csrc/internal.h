@@ -147,6 +147,9 @@ struct Workspace {
         VadFftJob* h_jobs = nullptr; VadFftJob* d_jobs = nullptr;
         size_t h_jobs_cap = 0;
     } graph;
+    // fvad_ingest's ring (engine_ingest.cpp): two page-locked buffers of `bytes` (a batch's raw bytes, then its tables) and their
+    // device images; ev[s]: the kernels that read slot s's device image have run.  Made on first use, kept by the context.
+    struct IngestRing { char* pin[2] = {nullptr, nullptr}; char* dev[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; size_t bytes = 0; } ingest;
     // copy streams + per-group events of the pipelined host-buffer path (fvad_engine_run)
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     hipEvent_t grp_in[8] = {}, grp_k[8] = {};
@@ -195,6 +198,8 @@ struct Tuning {
     int vad_trigger = 0;         // device VAD sweeps: 0 = one full machine per (stream, config) ("config"), 1 = one trigger machine per (stream, trigger key) that emits bits and a finishing kernel per config ("shared", needs vad_chain "coop"); same bits
     unsigned long long vad_trigger_max_bytes = 4ull << 30; // a part whose bits need more runs the per-config machines (a guard computed from shapes, not a measurement)
     int vad_seg_cap = 0;         // fvad_vad_batch_run_device: segments per machine the first launch has room for (more: a second launch); 0 = 512 MB in all
+    unsigned long long ingest_ring_bytes = 32ull << 20; // fvad_ingest: raw bytes per batch of its two-slot ring (1 KB .. 1 GB, a multiple of 16; tests
+                                 // set it small so that a source is cut several times; the result has the same bits whatever the value)
     int nn_trim = 3;             // large-batch f32 family, bit 1: fc2 / fc3 issue no MFMAs for their all-padding 39th column tile; bit 2: layer 1's
                                  // input projection computes rows 4..53 of a chunk and the recurrence takes rows 0..3 from the previous chunk
                                  // ("all" | "tiles" | "rows" | "none"; same bits whatever the value)

@@ -441,3 +441,31 @@ struct ClipArgs {
 int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream);    // hipError_t as int
 int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream);   // (after fvad_launch_clip_rms on the same stream)
 int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick)
+
+// ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
+// fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
+// multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane
+// of its fill range: unit r of job j is data tile r for r < n_data_tiles, else fill tile (r - n_data_tiles) % n_fill_tiles of
+// channel (r - n_data_tiles) / n_fill_tiles.  A launch serves the jobs of ONE source format; unit_prefix[j] counts the units
+// in front of job j (a job has at least one unit).
+constexpr int kIngestTileBytes = 16384;
+constexpr int kIngestFillTile = 8192;
+constexpr int kIngestMaxChannels = 64;
+struct IngestJob {
+    uint64_t src_off;   // bytes from `raw` to the source's frame 0
+    uint64_t n_frames;
+    uint64_t dst_off;   // elements from `lanes` to the sample frame 0 of channel 0 is written to
+    uint64_t fill_len;  // zeros behind the frames, in every lane of the source
+    uint32_t n_data_tiles, n_fill_tiles; // n_fill_tiles: per lane
+    uint32_t tile_frames, n_channels;
+};
+struct IngestArgs {
+    const uint8_t* raw;
+    void* lanes;        // f32 or PCM16 lanes
+    uint64_t lane_stride;
+    const IngestJob* jobs;        // [n_jobs] (device)
+    const uint32_t* unit_prefix;  // [n_jobs + 1]
+    uint32_t n_jobs, n_units;
+    int src_format, out_i16;      // FVAD_INGEST_*
+};
+int fvad_launch_ingest(const IngestArgs& a, hipStream_t stream); // hipError_t as int

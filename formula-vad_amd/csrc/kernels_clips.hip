@@ -14,10 +14,11 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "stage_tile.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kStageThreads;
 
 // the clip whose units [prefix[c], prefix[c + 1]) hold unit u (prefix[0] = 0, prefix[n] > u; every clip has at least one unit)
 __device__ inline uint32_t find_clip(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t u)
@@ -39,26 +40,6 @@ template <> struct Convert<float, int16_t> { __device__ static float run(int16_t
 template <> struct Convert<int16_t, float> { // fvad_lane.denoised_i16's rule (k3_istft_ola_kernel)
     __device__ static int16_t run(float y) { return (int16_t)__builtin_rintf(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)); }
 };
-
-// n (1 .. kClipTile) elements from p into lds[shift ..), shift = p's offset within 16 bytes in elements (returned).  lds holds
-// kClipTile + 16 / sizeof(S) elements and is 16-byte aligned.  Ends with a barrier.
-template <typename S>
-__device__ inline int stage_tile(const S* __restrict__ p, int n, S* lds)
-{
-    constexpr int V = 16 / (int)sizeof(S);
-    const int t = threadIdx.x;
-    const int shift = (int)(((uintptr_t)p & 15) / sizeof(S));
-    const int head = min(n, (V - shift) % V);
-    const int nvec = (n - head) / V;
-    const uint4* pv = reinterpret_cast<const uint4*>(p + head);
-    uint4* lv = reinterpret_cast<uint4*>(lds + shift + head); // shift + head is 0 or V whenever nvec > 0
-    for (int v = t; v < nvec; v += kThreads) lv[v] = pv[v];
-    const int tail0 = head + nvec * V;
-    if (t < head) lds[shift + t] = p[t];
-    if (t < n - tail0) lds[shift + tail0 + t] = p[tail0 + t];
-    __syncthreads();
-    return shift;
-}
 
 template <typename S>
 __device__ inline void rms_tile(const ClipArgs& a, S* lds, double* wsum)

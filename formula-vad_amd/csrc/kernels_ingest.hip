@@ -1,0 +1,151 @@
+// kernels_ingest.hip -- fvad_ingest*: a corpus's bytes as its files hold them (interleaved frames of little-endian PCM16, PCM24
+// or IEEE float32) de-interleaved, decoded and zero-padded into the planar lanes fvad_engine_enqueue_device* and
+// fvad_clips_export* take.  The four format pairs are exact: PCM16 -> f32 is s / 32768 (fvad_lane.pcm_i16's rule), PCM24 -> f32
+// is s / 8388608 (|s| <= 2^23 fits the f32 significand, the scale is a power of two), PCM16 -> PCM16 and f32 -> f32 move bits
+// (f32 as 32-bit integers: NaN payloads and -0 survive).
+//
+// The work unit follows kernels_clips.hip: a workgroup of 256 lanes takes one tile of one source, found by a search of a
+// host-built prefix table with its block index (the same in every lane); no atomics, a source's output depends on its own bytes
+// alone.  A data tile's bytes are staged through LDS once (stage_tile: 16-byte loads for the aligned body strictly inside the
+// tile, the bytes in front of and behind it one by one, so no byte outside the source's range is read); then every lane takes
+// the samples of ONE channel of a group of consecutive frames from LDS by index and stores them planar.  A group is 16 bytes of
+// the DESTINATION, cut at the destination's 16-byte boundaries (a lane's start has any element alignment: lane_stride and
+// dst_offset are arbitrary), so that a whole group is one 16-byte store and only a run's first and last few samples are
+// element stores; consecutive lanes of the workgroup take consecutive groups of one channel (coalesced stores).  The LDS reads
+// of a group are n_channels * bytes_per_sample apart and the groups of neighbouring lanes 16 destination bytes' worth of frames:
+// for mono f32 that is a 4-way bank conflict on ds_read_b32 (computed, cdna_hip_programming Guideline 4), which a kernel that
+// moves 8 bytes of HBM per sample has the LDS cycles for.  Samples that are not aligned to their own size (a data chunk at
+// an odd offset, f32 frames at 2 modulo 4) and all PCM24 samples are assembled from LDS bytes: no unaligned LDS access.
+// The zero-fill range behind a source's frames is tiled the same way, one lane's zeros per unit.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "stage_tile.h"
+
+namespace {
+
+constexpr int kThreads = kStageThreads;
+
+// the job whose units [prefix[j], prefix[j + 1]) hold unit u (prefix[0] = 0, prefix[n] > u; every job has at least one unit)
+__device__ inline uint32_t find_job(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t u)
+{
+    uint32_t lo = 0, hi = n; // invariant: prefix[lo] <= u < prefix[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (prefix[mid] <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct Pcm24 {}; // 3 bytes, little-endian, two's complement
+
+// Source<S>: bytes per sample and the sample at LDS byte b as its integer image (aligned: b is a multiple of the sample's size)
+template <typename S> struct Source;
+template <> struct Source<int16_t> {
+    static constexpr int kBytes = 2;
+    __device__ static int32_t load(const uint8_t* lds, int b, bool aligned)
+    {
+        if (aligned) return *reinterpret_cast<const int16_t*>(lds + b);
+        return (int16_t)(uint16_t)(lds[b] | (lds[b + 1] << 8));
+    }
+};
+template <> struct Source<Pcm24> {
+    static constexpr int kBytes = 3;
+    __device__ static int32_t load(const uint8_t* lds, int b, bool)
+    {
+        const uint32_t u = (uint32_t)lds[b] | ((uint32_t)lds[b + 1] << 8) | ((uint32_t)lds[b + 2] << 16);
+        return (int32_t)(u << 8) >> 8; // sign-extended
+    }
+};
+template <> struct Source<float> {
+    static constexpr int kBytes = 4;
+    __device__ static int32_t load(const uint8_t* lds, int b, bool aligned)
+    {
+        if (aligned) return (int32_t)*reinterpret_cast<const uint32_t*>(lds + b);
+        return (int32_t)((uint32_t)lds[b] | ((uint32_t)lds[b + 1] << 8) | ((uint32_t)lds[b + 2] << 16) | ((uint32_t)lds[b + 3] << 24));
+    }
+};
+
+// Decode<D, S>: the element stored (E) from the integer image
+template <typename D, typename S> struct Decode;
+template <> struct Decode<float, int16_t> { using E = float; __device__ static E run(int32_t s) { return (float)s * (1.0f / 32768.0f); } };
+template <> struct Decode<float, Pcm24> { using E = float; __device__ static E run(int32_t s) { return (float)s * (1.0f / 8388608.0f); } };
+template <> struct Decode<int16_t, int16_t> { using E = int16_t; __device__ static E run(int32_t s) { return (int16_t)s; } };
+template <> struct Decode<float, float> { using E = uint32_t; __device__ static E run(int32_t s) { return (uint32_t)s; } }; // the bits
+
+// Group g of the run p[0, n): the elements of the g-th 16 destination bytes counted from the 16-byte boundary at or below p.
+// A group wholly inside the run is one 16-byte store, the others (the run's first and last) element stores; a group past the
+// run stores nothing.  sample(i) gives element i of the run.
+template <typename E, typename F>
+__device__ inline void store_group(E* p, int n, int g, F sample)
+{
+    constexpr int G = 16 / (int)sizeof(E);
+    const int a = (int)(((uintptr_t)p & 15) / sizeof(E));
+    const int lo = g * G - a, hi = lo + G;
+    if (lo >= 0 && hi <= n) {
+        alignas(16) E v[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) v[i] = sample(lo + i);
+        *reinterpret_cast<uint4*>(p + lo) = *reinterpret_cast<const uint4*>(v);
+    } else {
+        for (int i = max(lo, 0); i < min(hi, n); ++i) p[i] = sample(i);
+    }
+}
+
+template <typename D, typename S>
+__device__ inline void ingest_tile(const IngestArgs& a, uint8_t* lds)
+{
+    using E = typename Decode<D, S>::E;
+    constexpr int G = 16 / (int)sizeof(E);
+    constexpr int B = Source<S>::kBytes;
+    const uint32_t u = blockIdx.x;
+    const uint32_t ji = find_job(a.unit_prefix, a.n_jobs, u);
+    const IngestJob j = a.jobs[ji];
+    const uint32_t r = u - a.unit_prefix[ji];
+    E* lanes = static_cast<E*>(a.lanes) + j.dst_off;
+    const int t = threadIdx.x;
+    if (r >= j.n_data_tiles) { // zeros: one lane's fill tile
+        const uint32_t q = r - j.n_data_tiles;
+        const uint32_t ch = q / j.n_fill_tiles, k = q % j.n_fill_tiles;
+        const uint64_t e0 = (uint64_t)k * kIngestFillTile;
+        const int n = (int)min((uint64_t)kIngestFillTile, j.fill_len - e0);
+        E* p = lanes + (uint64_t)ch * a.lane_stride + j.n_frames + e0;
+        const int ng = (n + 2 * G - 2) / G; // groups a run of n can touch, whatever its alignment
+        for (int g = t; g < ng; g += kThreads) store_group(p, n, g, [](int) { return (E)0; });
+        return;
+    }
+    const int C = (int)j.n_channels;
+    const uint64_t f0 = (uint64_t)r * j.tile_frames;
+    const int nfr = (int)min((uint64_t)j.tile_frames, j.n_frames - f0);
+    const uint8_t* src = a.raw + j.src_off + f0 * (uint64_t)(C * B);
+    const int shift = stage_tile(src, nfr * C * B, lds);
+    // a frame is C * B bytes, so every sample of the source has frame 0's alignment
+    const bool aligned = B == 3 ? false : ((uintptr_t)src % B) == 0;
+    const int ng = (nfr + 2 * G - 2) / G;
+    for (int i = t; i < C * ng; i += kThreads) {
+        const int c = i / ng, g = i - c * ng;
+        E* p = lanes + (uint64_t)c * a.lane_stride + f0;
+        const uint8_t* at = lds + shift + c * B;
+        store_group(p, nfr, g, [&](int f) { return Decode<D, S>::run(Source<S>::load(at, f * C * B, aligned)); });
+    }
+}
+
+} // namespace
+
+template <typename D, typename S>
+__global__ __launch_bounds__(kThreads) void ingest_kernel(IngestArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kIngestTileBytes + 16];
+    ingest_tile<D, S>(a, lds);
+}
+
+int fvad_launch_ingest(const IngestArgs& a, hipStream_t stream)
+{
+    const dim3 grid(a.n_units), block(kThreads);
+    if (a.src_format == FVAD_INGEST_PCM16 && a.out_i16) hipLaunchKernelGGL((ingest_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
+    else if (a.src_format == FVAD_INGEST_PCM16) hipLaunchKernelGGL((ingest_kernel<float, int16_t>), grid, block, 0, stream, a);
+    else if (a.src_format == FVAD_INGEST_PCM24 && !a.out_i16) hipLaunchKernelGGL((ingest_kernel<float, Pcm24>), grid, block, 0, stream, a);
+    else if (a.src_format == FVAD_INGEST_F32 && !a.out_i16) hipLaunchKernelGGL((ingest_kernel<float, float>), grid, block, 0, stream, a);
+    else return (int)hipErrorInvalidValue; // (the callers refuse the conversions before they get here)
+    return (int)hipGetLastError();
+}

@@ -253,6 +253,74 @@ def _map_audio(inst):
     return pcm
 
 
+INGESTS = ("host", "device")
+
+
+class _RawAudio:
+    """An instance's audio for ingest="device": the bytes of its file's data chunk, mapped and interleaved as the file holds
+    them (fv.wav_map_raw), which fvad_ingest de-interleaves and decodes on the GPU.  n_channels and n_frames are what the
+    harness needs of a loaded instance (_dims); it is no array."""
+
+    def __init__(self, raw, info):
+        self.raw, self.format = raw, info["format"]
+        self.n_channels, self.n_frames = info["n_channels"], info["n_frames"]
+        self.frame_bytes = self.n_channels * (info["bits"] // 8)
+
+    def source(self, frame_from, frame_to, first_lane, dst_offset, fill_to):
+        """the fvad_ingest source row of frames [frame_from, frame_to); frame_to <= frame_from (a slice behind the file's end):
+        a row without frames at byte 0, which only fills"""
+        n = max(frame_to - frame_from, 0)
+        return (frame_from * self.frame_bytes if n else 0, n, self.n_channels, self.format, first_lane, dst_offset, fill_to)
+
+
+def _dims(a, mapped=False):
+    """(n_channels, n_frames) of a loaded instance: a _RawAudio's own, or the shape of the array the host path loads --
+    [n_channels][n_frames] where it reads the files, [n_frames][n_channels] where it maps them (mapped: the sliced grid)"""
+    if isinstance(a, _RawAudio):
+        return a.n_channels, a.n_frames
+    return (a.shape[1], a.shape[0]) if mapped else (a.shape[0], a.shape[1])
+
+
+def _raw_audio(inst):
+    raw, info = fv.wav_map_raw(inst["audio_path"])
+    if info["sample_rate"] != 48000:
+        raise fv.FvadError(-9, f"{inst['name']}: sample rate {info['sample_rate']}")   # VADPipeline.zig:55-58
+    if info["n_channels"] > 64:
+        raise fv.FvadError(fv.FVAD_ERR_INVALID_ARGUMENT, inst["name"], f"{info['n_channels']} channels: fvad_ingest takes 64")
+    return _RawAudio(raw, info)
+
+
+def _check_ingest(ingest):
+    if ingest not in INGESTS:
+        raise ValueError(f"ingest: {ingest!r} (one of {', '.join(INGESTS)})")
+
+
+def _load_instances(plan, ingest, mapped=False):
+    """[(audio, labels)] per instance.  ingest "host": the files read (_read_instance), or mapped for the sliced grid
+    (_map_audio); a file those refuse that fvad_wav_probe takes -- 24-bit PCM -- is refused with a pointer to the other way.
+    ingest "device": every file mapped as bytes (_RawAudio), nothing read."""
+    if ingest == "device":
+        return [(_raw_audio(i), _read_labels(i)) for i in plan["instances"]]
+    loaded = []
+    for i in plan["instances"]:
+        try:
+            loaded.append((_map_audio(i), _read_labels(i)) if mapped else _read_instance(i))
+        except fv.FvadError as e:
+            try:
+                pcm24 = fv.wav_probe(i["audio_path"])["format"] == fv.INGEST_PCM24
+            except fv.FvadError:
+                pcm24 = False
+            if not pcm24:
+                raise
+            raise fv.FvadError(e.status, f"{i['name']}: {i['audio_path']}",
+                               "24-bit PCM is decoded on the GPU only: run with --ingest device (ingest='device')") from e
+    return loaded
+
+
+def _is_raw(audio):
+    return bool(audio) and isinstance(audio[0], _RawAudio)
+
+
 def instance_shares(n_instances, n_devices):
     """How run_plan and run_grid deal a plan's instances to n_devices contexts: instance i to share i % n_devices, each share
     in plan order -> [[instance]] per share (a share may be empty)"""
@@ -373,22 +441,22 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
         lane0, l = {}, 0
         for i in r.order:
             lane0[i] = l
-            l += audio[i].shape[0]
+            l += _dims(audio[i])[0]
 
         def host_stage(i):
-            C_, nck = audio[i].shape[0], r.n_chunks[i]
+            C_, nck = _dims(audio[i])[0], r.n_chunks[i]
             return _vad_host_stage(plan, band[lane0[i]:lane0[i] + C_, :nck * chunk // F], r.rms[lane0[i]:lane0[i] + C_, :nck])
 
         per_inst = _map_instances(host_stage, len(audio))
         # one export per kind over every instance's clips: the reference's two recorders, each picking from its own audio
-        kinds = (("original", r.d_pcm, r.stride, r.n_samples, [a.shape[1] for a in audio]),
+        kinds = (("original", r.d_pcm, r.stride, r.n_samples, [_dims(a)[1] for a in audio]),
                  ("denoised", r.d_den, r.n_den, r.n_den, [n * chunk for n in r.n_chunks]))
         manifests = [{"name": inst["name"], "sample_rate": 48000, "pcm16": bool(pcm16), "clips": [
             {"segment": k, "start": int(s[0]), "length": int(s[1] - s[0])} for k, s in enumerate(segs)]} for inst, (segs, _) in zip(insts, per_inst)]
         for kind, d_src, stride, n_samples, avail in kinds:
             rows, owner = [], []
             for i, (segs, _) in enumerate(per_inst):
-                clips, skipped = fv.clips_from_segments(segs, lane0[i], audio[i].shape[0], avail[i])
+                clips, skipped = fv.clips_from_segments(segs, lane0[i], _dims(audio[i])[0], avail[i])
                 manifests[i][f"{kind}_skipped"] = skipped
                 rows.append(clips)
                 k = 0
@@ -416,7 +484,7 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
             ctx.device_free(d)
 
 
-def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None):
+def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host"):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -428,13 +496,15 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     whole chunk).  Returns run_plan's (report text, results), each result with its manifest under "clips".
     Segments and report are run_plan's whenever both passes select the same NSNet2 kernels (fvad_ctx_last_nn_path): the resident
     pass pads every lane to the longest instance, so a plan of unequal lengths may be cut into other launches (the context option
-    "reproducible" makes the two agree bit for bit for every plan)."""
+    "reproducible" makes the two agree bit for bit for every plan).
+    ingest "device": the files' bytes go to the GPU as they are and are decoded there (run_grid); the same clips and manifests."""
+    _check_ingest(ingest)
     plan = load_plan(plan_path)
     own_ctx = ctx is None
     ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])] if own_ctx else [ctx]
     try:
         os.makedirs(out_dir, exist_ok=True)
-        loaded = [_read_instance(i) for i in plan["instances"]]
+        loaded = _load_instances(plan, ingest)
         audio, refs = [a for a, _ in loaded], [r for _, r in loaded]
         parts = instance_shares(len(audio), len(ctxs))
         done, errs = [None] * len(ctxs), []
@@ -576,32 +646,40 @@ def _denoise_resident(ctx, audio, F, config0, dalloc):
     the original lanes d_pcm (n_lanes of n_samples f32, `stride` apart), the denoised lanes d_den (n_den samples each), config 0's
     band sums d_band0 [lane][nf_all], chunk RMS [lane][chunk] on the host."""
     chunk = 24000
-    lens = [p.shape[1] for p in audio]
+    lens = [_dims(p)[1] for p in audio]
     n_chunks = [n // chunk for n in lens]
     L = max(lens)
     stride = (L + 3) // 4 * 4                        # 16-byte aligned lanes
     groups = {}
     for i, p in enumerate(audio):
-        groups.setdefault(p.shape[0], []).append(i)
+        groups.setdefault(_dims(p)[0], []).append(i)
     order = [i for members in groups.values() for i in members]
-    n_lanes = sum(audio[i].shape[0] for i in order)
+    n_lanes = sum(_dims(audio[i])[0] for i in order)
     n_ck = L // chunk
     n_den = n_ck * chunk
     nf_all = n_den // F
-    host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
-    l = 0
-    for i in order:
-        p = audio[i]
-        for c in range(p.shape[0]):
-            if p.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
-                np.multiply(p[c], np.float32(1.0 / 32768.0), out=host[l, :p.shape[1]], casting="unsafe")
-            else:
-                host[l, :p.shape[1]] = p[c]
-            l += 1
     opts = _engine_opts(config0, F)
-    d_pcm = dalloc(host.nbytes)
-    ctx.to_device(d_pcm, host)
-    del host
+    if _is_raw(audio):   # ingest "device": one source per instance, the lanes decoded and padded to `stride` by the ingest kernel
+        d_pcm = dalloc(n_lanes * stride * 4)
+        rows, l = [], 0
+        for i in order:
+            rows.append(audio[i].source(0, audio[i].n_frames, l, 0, stride))
+            l += audio[i].n_channels
+        ctx.ingest(rows, d_lanes=d_pcm, n_lanes=n_lanes, lane_stride=stride, n_samples=stride, raw=[audio[i].raw for i in order])
+    else:
+        host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
+        l = 0
+        for i in order:
+            p = audio[i]
+            for c in range(p.shape[0]):
+                if p.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                    np.multiply(p[c], np.float32(1.0 / 32768.0), out=host[l, :p.shape[1]], casting="unsafe")
+                else:
+                    host[l, :p.shape[1]] = p[c]
+                l += 1
+        d_pcm = dalloc(host.nbytes)
+        ctx.to_device(d_pcm, host)
+        del host
     d_den = dalloc(n_lanes * n_den * 4)
     d_band0 = dalloc(n_lanes * max(nf_all, 1) * 4)
     d_rms = dalloc(n_lanes * max(n_ck, 1) * 4)
@@ -681,7 +759,7 @@ def _group_machines(ctx, job, b, members, nch, d_gband, bstride, nf, g_rms, n_ch
 
 
 def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout, json_path=None, vad_on="auto", n_threads=16,
-              vad_chain=None, vad_avgs=None, vad_trigger=None):
+              vad_chain=None, vad_avgs=None, vad_trigger=None, ingest="host"):
     """Scores many VADMachine configurations over one denoising pass of a plan's instances.
 
     configs: list of VADMachine.Config override dicts (vad_overrides' form); default: the plan's vad_machine_config followed by its
@@ -700,8 +778,10 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
 
     Returns dict(configs, rows [one aggregate dict per config], aggregates [AggregateStats], segments [config][instance],
     stats [config][instance], avgs_form, avgs_bytes [VadSweep.avgs_form() / avgs_bytes(): the largest over the device
-    launches; 0 with host machines]); prints one table row per config and writes the rows as JSON to json_path if given."""
+    launches; 0 with host machines]); prints one table row per config and writes the rows as JSON to json_path if given.
+    ingest as in run_grid."""
     _check_vad_chain(vad_chain, vad_avgs, vad_trigger)
+    _check_ingest(ingest)
     plan = load_plan(plan_path)
     if configs is None:
         configs = [plan["vad_machine_config"]] + list(plan["alt_vad_machine_configs"])
@@ -715,7 +795,7 @@ def run_sweep(plan_path, ctx=None, synth_seed=None, configs=None, out=sys.stdout
     if own_ctx:
         ctx = _make_ctx(plan, 0, synth_seed)
     chain = _VadChain(vad_chain, vad_avgs, vad_trigger)
-    loaded = [_read_instance(i) for i in plan["instances"]]
+    loaded = _load_instances(plan, ingest)
     audio = [a for a, _ in loaded]
     refs = [r for _, r in loaded]
     t0 = time.perf_counter()
@@ -925,7 +1005,7 @@ def _check_grid_contexts(ctx, devices):
 
 def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=None, ctx=None, synth_seed=None, out=sys.stdout,
              n_threads=16, slice_chunks=None, halving_eta=None, halving_rungs=None, devices=None, overlap=False, vad_chain=None,
-             vad_avgs=None, vad_trigger=None):
+             vad_avgs=None, vad_trigger=None, ingest="host"):
     """A grid sweep: every config of a parameter grid (expand_grid; grid: the dict or a path to its JSON file) scored over one
     denoising pass of a plan's instances, without returning segments.  The flow is run_sweep's (one device batch for the
     denoising, per channel-count group a multi-band K4 pass and the VAD machines); then every (instance, config) machine is
@@ -994,8 +1074,14 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     of the bands and rms buffers.
     vad_chain and vad_avgs as in run_sweep: set on every context the call makes, and on the caller's contexts for the call;
     times gains avgs_form and avgs_bytes (the largest over the shares' device launches: 2 once a launch read the tables, and
-    the largest part's tables in bytes), which the JSON file carries too."""
+    the largest part's tables in bytes), which the JSON file carries too.
+    ingest "host" (the default): the files are read, or with slice_chunks mapped, de-interleaved and converted to f32 on the
+    host and uploaded as f32.  "device": every file's data chunk is mapped as bytes (wav_map_raw), sliced or not, and
+    fvad_ingest takes the bytes to the GPU as they are -- PCM16 at 2 bytes per sample -- where one kernel de-interleaves,
+    decodes and pads them into the same f32 lanes: the same bits downstream, hence the same result.  24-bit PCM files run with
+    "device" only; "host" refuses them (FvadError naming --ingest device)."""
     _check_vad_chain(vad_chain, vad_avgs, vad_trigger)
+    _check_ingest(ingest)
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
     if isinstance(grid, str):
         with open(grid) as f:
@@ -1036,10 +1122,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     if slice_chunks is not None:
         check_slice_chunks_sized(slice_chunks, sizes_of)
     stat_cfgs = [_stat_cfg(c) for c in configs]
-    if slice_chunks is not None:   # the audio stays in its files: mapped, read slice by slice
-        loaded = [(_map_audio(i), _read_labels(i)) for i in plan["instances"]]
-    else:
-        loaded = [_read_instance(i) for i in plan["instances"]]
+    loaded = _load_instances(plan, ingest, mapped=slice_chunks is not None)   # (sliced: the audio stays in its files, mapped)
     for inst, (_, ref) in zip(plan["instances"], loaded):
         if any(x != x for r in ref for x in r):
             raise ValueError(f"{inst['ref_path']}: a NaN label; grid scoring walks the labels sorted by start and needs "
@@ -1066,7 +1149,7 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
         ctxs, owned = list(ctx), [False] * n_shares
     rungs = None
     if halving is not None:   # the schedule over the longest instance of the whole plan, whatever the shares
-        rungs = _Rungs(len(workers), halving, [a.shape[0] // 24000 for a in audio], int(slice_chunks), stats, stat_cfgs)
+        rungs = _Rungs(len(workers), halving, [_dims(a, mapped=True)[1] // 24000 for a in audio], int(slice_chunks), stats, stat_cfgs)
     share_times = [{"device": int(devices[s]) if devices is not None else getattr(ctxs[s], "device", None), "instances": shares[s],
                     "wall": 0.0, "times": {}} for s in range(len(shares))]
     share_out = [(0, None)] * len(shares)
@@ -1525,23 +1608,27 @@ def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, blocks, time
     L = len(members) * nch
     # ---- read and denoise [start, s1): lane l of the group at host[l * n * chunk]
     t0 = time.perf_counter()
-    pcm = host[:L * n * chunk].reshape(L, n * chunk)
-    for k, i in enumerate(members):
-        a = audio[i]
-        lo, hi = start * chunk, min(s1 * chunk, a.shape[0])
-        for c in range(nch):
-            row = pcm[k * nch + c]
-            if hi > lo:
-                if a.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
-                    np.multiply(a[lo:hi, c], np.float32(1.0 / 32768.0), out=row[:hi - lo], casting="unsafe")
-                else:
-                    row[:hi - lo] = a[lo:hi, c]
-            row[max(hi - lo, 0):] = 0.0
     d_bands, d_rms = (d["bands"], d["rms"]) if dset is None else dset
-    if dset is None:
-        ctx.to_device(d["pcm"], pcm)
-    else:   # queued in front of the engine call, which waits for the main stream (Context.synchronize would wait for the part too)
-        ctx._ck(fv.lib().fvad_ctx_copy_to_device(ctx.h, fv.vp(d["pcm"]), pcm.ctypes.data, pcm.nbytes), "fvad_ctx_copy_to_device")
+    if _is_raw(audio):   # ingest "device": one source per member -- the slice and its halo, then zeros to the slice's end; waits for the main stream only
+        rows = [audio[i].source(start * chunk, min(s1 * chunk, audio[i].n_frames), k * nch, 0, n * chunk) for k, i in enumerate(members)]
+        ctx.ingest(rows, d_lanes=d["pcm"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk, raw=[audio[i].raw for i in members])
+    else:
+        pcm = host[:L * n * chunk].reshape(L, n * chunk)
+        for k, i in enumerate(members):
+            a = audio[i]
+            lo, hi = start * chunk, min(s1 * chunk, a.shape[0])
+            for c in range(nch):
+                row = pcm[k * nch + c]
+                if hi > lo:
+                    if a.dtype == np.int16:   # the kernel's PCM16 decode, exact in f32
+                        np.multiply(a[lo:hi, c], np.float32(1.0 / 32768.0), out=row[:hi - lo], casting="unsafe")
+                    else:
+                        row[:hi - lo] = a[lo:hi, c]
+                row[max(hi - lo, 0):] = 0.0
+        if dset is None:
+            ctx.to_device(d["pcm"], pcm)
+        else:   # queued in front of the engine call, which waits for the main stream (Context.synchronize would wait for the part too)
+            ctx._ck(fv.lib().fvad_ctx_copy_to_device(ctx.h, fv.vp(d["pcm"]), pcm.ctypes.data, pcm.nbytes), "fvad_ctx_copy_to_device")
     ctx._ck(fv.lib().fvad_engine_enqueue_device(ctx.h, fv.vp(d["pcm"]), L, n * chunk, n * chunk, fv.vp(d["den"]),
                                                 fv.vp(d["band0"]), fv.vp(d_rms), fv.C.byref(opts)),
             "fvad_engine_enqueue_device")
@@ -1619,10 +1706,10 @@ def _grid_sliced(ctx, job, audio, refs, ids, stats, times, rungs, stop):
     device and the parts not waited for (fvad_vad_batch_run_device_part_async): slice k's machines run beside slice k + 1's
     reading and denoising; times gains machines_wait, the host time spent waiting for parts (it is part of machines)."""
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, job.slice_chunks, job.F
-    n_chunks = [a.shape[0] // chunk for a in audio]
+    n_chunks = [_dims(a, mapped=True)[1] // chunk for a in audio]
     groups = {}
     for i, a in enumerate(audio):
-        groups.setdefault(a.shape[1], []).append(i)
+        groups.setdefault(_dims(a, mapped=True)[0], []).append(i)
     probe = _new_batch(job, 1, 1)
     n_bands, f_min = len(probe.size_of_band), min(probe.sizes)
     probe.close()
@@ -1642,7 +1729,8 @@ def _grid_sliced(ctx, job, audio, refs, ids, stats, times, rungs, stop):
     try:
         for k, nb in own.items():
             d[k] = ctx.device_alloc(max(nb, 16))
-        host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
+        if not _is_raw(audio):   # (ingest "device" stages through the context's own ring)
+            host = ctx.host_alloc(lanes_max * n_max * chunk)   # the slice's PCM, pinned
         buf = _SliceBufs(d, host, opts, fr_slice)
         ov = _Overlap(ctx, d, times) if job.overlap else None
         # halving: every group in one loop to the plan's end; plain: a loop per group to the group's own end
@@ -1727,6 +1815,10 @@ def arg_parser():
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
+    ap.add_argument("--ingest", default="host", choices=INGESTS,
+                    help="with --sweep / --sweep-grid / --export-clips: where the files' samples are de-interleaved and decoded -- on "
+                         "the host, uploaded as f32 (the default), or on the GPU from the files' own bytes (fvad_ingest: PCM16 crosses "
+                         "PCIe at 2 bytes per sample, and 24-bit PCM files are taken); same results")
     return ap
 
 
@@ -1736,15 +1828,15 @@ def main(argv=None):
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,
-                 overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs, vad_trigger=a.vad_trigger)
+                 overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs, vad_trigger=a.vad_trigger, ingest=a.ingest)
         return
     if a.export_clips:
-        text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices)
+        text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest)
         sys.stdout.write(text)
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs,
-                  vad_trigger=a.vad_trigger)
+                  vad_trigger=a.vad_trigger, ingest=a.ingest)
         return
     run_plan(a.input, synth_seed=a.synth_seed, devices=devices or [0])
 

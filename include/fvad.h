@@ -348,7 +348,7 @@ int fvad_ctx_nn_tap(fvad_ctx *ctx, int layer, size_t first_seq, size_t n_seq, fl
  *
  * Testing / tuning aids, none needed in production: name = "reproducible" | "nn_math" ("f32" | "f16x3" | "bf16x3": overrides
  * fvad_ctx_set_nn_math) | "gru_kernel" ("v3w12" | "v3w8" | "v3w4" | "v4w8" | "v5w0" | "v6w0") | "gemm_kernel" ("v1" |
- * "v3" | "v3nofold") | "h3_waves" ("8" | "12") | "max_chunks" | "copy_threads" | "no_pipeline" | "run_groups" ("1,3,4,8": the lane groups of
+ * "v3" | "v3nofold") | "h3_waves" ("8" | "12") | "max_chunks" | "copy_threads" | "ingest_ring_bytes" (fvad_ingest's raw bytes per batch; same bits) | "no_pipeline" | "run_groups" ("1,3,4,8": the lane groups of
  * fvad_engine_run's host-buffer pipeline in sixteenths of the call, at most seven, instead of the planned ones) | "trace_run" (a timeline of every fvad_engine_run call on stderr) | "trace_kernels" |
  * "ws_spin_ticks" | "ws2_variant" (diagnostic bit mask; the timing-only bits exist in the diagnostics build alone) |
  * "ws2_waits" | "ws2_calibrate" (below) | "nn_trim" ("all" | "tiles" | "rows" | "none": what the persistent f32 kernels skip -- "tiles": the MFMAs of
@@ -824,6 +824,59 @@ int fvad_clips_export_device(fvad_ctx *ctx, const void *d_src, int src_format, s
 int fvad_clips_export(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                       const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
                       int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets);
+
+/* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
+ * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
+ * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
+ * decodes and zero-pads them into the planar lanes fvad_engine_enqueue_device* and fvad_clips_export* take.  The host does no
+ * per-sample work, a PCM16 corpus crosses PCIe at 2 bytes per sample, and 24-bit PCM -- which fvad_wav_read refuses -- is usable.
+ * - Format pairs (source -> lanes), all exact: PCM16 -> f32 is (float)s * (1.0f / 32768.0f), fvad_lane.pcm_i16's rule; PCM16 ->
+ *   PCM16 the bits; PCM24 (3 bytes little-endian, sign-extended) -> f32 is (float)s * (1.0f / 8388608.0f), exact because
+ *   |s| <= 2^23 fits the f32 significand and the scale is a power of two (libsndfile's normalised float read of 24-bit PCM
+ *   [external: libsndfile is not part of this build, not verifiable here]); f32 -> f32 the bits, NaN payloads and -0 included.
+ *   PCM24 -> PCM16 and f32 -> PCM16 are conversions, not ingest: FVAD_ERR_INVALID_ARGUMENT.
+ * - A source (a file, or a slice of one) is a row of FVAD_INGEST_FIELDS uint64: byte_offset (where its frame 0 starts in the
+ *   raw bytes: any value, a data chunk usually starts at byte 44), n_frames, n_channels (1 .. 64), format (FVAD_INGEST_*),
+ *   first_lane (channel c goes to lane first_lane + c), dst_offset (the lane sample frame 0 is written to), fill_to (>=
+ *   dst_offset + n_frames: the lane samples [dst_offset + n_frames, fill_to) of the source's lanes are written as zeros -- the
+ *   padding of a ragged batch without a memset).  Lanes are laid out as for fvad_engine_enqueue_device*: lane l at d_lanes +
+ *   l * lane_stride samples of out_format, n_samples each; lane_stride and dst_offset need no alignment.
+ * - Nothing outside a source's bytes [byte_offset, byte_offset + n_frames * n_channels * bytes per sample) is read and nothing
+ *   outside [dst_offset, fill_to) of its lanes is written.  INVARIANT: the lanes get the same bits whatever the order of the
+ *   sources, however they are split over calls, and run after run (no atomics; a source's output depends on its bytes alone).
+ *
+ * fvad_wav_probe (host only): walks the RIFF chunks as fvad_wav_read does (the first "fmt " and "data" chunks,
+ * WAVE_FORMAT_EXTENSIBLE's sub-format, a data length past the end of the file cut to the file, a partial last frame dropped)
+ * WITHOUT reading the samples: info[FVAD_WAV_INFO_FIELDS] = format (FVAD_INGEST_*), n_channels, sample_rate, data_offset (bytes
+ * from the start of the file), n_frames, bits.  PCM16, PCM24 and 32-bit float are accepted; everything fvad_wav_read refuses
+ * except 24-bit PCM is refused the same way (FVAD_ERR_MODEL_FORMAT; FVAD_ERR_IO for a file that cannot be opened).
+ * fvad_ingest_check (host only): every argument rule of the two calls below, in this order: FVAD_ERR_INVALID_ARGUMENT for a bad
+ * out_format, NULL sources, lane_stride < n_samples with several lanes; then per source FVAD_ERR_INVALID_ARGUMENT for a bad
+ * format or pair, n_channels outside 1 .. 64, fill_to < dst_offset + n_frames; then per source FVAD_ERR_OUT_OF_RANGE for lanes
+ * past n_lanes, fill_to > n_samples, byte_offset + bytes > raw_bytes; then FVAD_ERR_INVALID_ARGUMENT when two sources'
+ * destination ranges [dst_offset, fill_to) overlap on a common lane (the order of the writes would decide the result; equal
+ * ranges on different lanes, and adjacent ranges on one lane, are fine).  n_sources == 0 succeeds; a source with n_frames == 0
+ * only fills.
+ * fvad_ingest_device: d_raw holds raw_bytes bytes on the device.  Runs fvad_ingest_check (and refuses NULL pointers and lanes
+ * that are not aligned to their samples) before any launch, returns when the lanes are written, and names `ingest` in
+ * fvad_ctx_kernel_times (one launch per source format present).  A launch takes fewer than 2^24 tiles (16 KB of source bytes or
+ * 8192 zeros of a lane each): a call with more -- some 270 GB of source -- is FVAD_ERR_INVALID_ARGUMENT; ingest in batches.
+ * fvad_ingest: the same for bytes in host memory (mapped files, pageable or page-locked): source i's byte_offset is relative to
+ * src_host[i] (which may be NULL when n_frames == 0).  The bytes are copied, as they are, into a two-slot page-locked ring the
+ * context keeps (context option ingest_ring_bytes / FVAD_INGEST_RING_BYTES at creation: the raw bytes per batch, default 32 MB,
+ * 1 KB .. 1 GB in multiples of 16) and uploaded batch by batch, the kernel running on one batch while the next is copied; a
+ * source larger than what is left of a batch is cut at a multiple of 4 frames.  The result has the same bits however the ring
+ * cuts the sources, and the same as fvad_ingest_device's. */
+enum { FVAD_INGEST_F32 = 0, FVAD_INGEST_PCM16 = 1, FVAD_INGEST_PCM24 = 2 };
+#define FVAD_INGEST_FIELDS 7
+#define FVAD_WAV_INFO_FIELDS 6
+int fvad_wav_probe(const char *path, uint64_t *info);
+int fvad_ingest_check(const uint64_t *sources, size_t n_sources, uint64_t raw_bytes, int out_format, size_t n_lanes,
+                      size_t lane_stride, size_t n_samples);
+int fvad_ingest_device(fvad_ctx *ctx, const void *d_raw, uint64_t raw_bytes, const uint64_t *sources, size_t n_sources,
+                       int out_format, void *d_lanes, size_t n_lanes, size_t lane_stride, size_t n_samples);
+int fvad_ingest(fvad_ctx *ctx, const void *const *src_host, const uint64_t *sources, size_t n_sources, int out_format,
+                void *d_lanes, size_t n_lanes, size_t lane_stride, size_t n_samples);
 
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
