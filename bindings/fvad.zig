@@ -25,6 +25,7 @@ pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
 pub const wav_info_fields = 6; // FVAD_WAV_INFO_FIELDS: format, n_channels, sample_rate, data_offset, n_frames, bits
+pub const clip_split_fields = 7; // FVAD_CLIP_SPLIT_FIELDS: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (u64 each)
 pub const clip_fields = 4; // FVAD_CLIP_FIELDS: a clip is a row of first_lane, n_channels, sample_from, sample_to (u64 each)
 
 // ------------------------------------------------------------------ status codes (the anonymous enum of fvad.h)
@@ -330,6 +331,7 @@ pub extern "c" fn fvad_vad_batch_n_configs(b: *const VadBatch) usize;
 pub extern "c" fn fvad_vad_batch_bands(b: *const VadBatch, bins: ?[*]i32, cap: usize, n_bands: *usize, band_of: ?[*]u32) c_int;
 pub extern "c" fn fvad_vad_batch_config_segments(b: *const VadBatch, config: usize, out: ?[*]SpeechSegment, cap: usize, offsets: [*]usize) c_int;
 pub extern "c" fn fvad_vad_batch_config_audit(b: *const VadBatch, stream: usize, config: usize, out: *VadAudit) c_int;
+pub extern "c" fn fvad_vad_batch_hold_from(b: *const VadBatch, config: usize, hold_from: [*]u64) c_int;
 pub extern "c" fn fvad_vad_batch_lazy_stats(b: *const VadBatch, stream: usize, config: usize, exact_evaluations: ?*u64, lazy_pushes: ?*u64) c_int;
 pub extern "c" fn fvad_vad_batch_run_device(ctx: *Ctx, b: *VadBatch, d_band: [*]const f32, band_stride: usize, n_frames: [*]const usize, chunk_rms: [*]const f32, rms_stride: usize, n_chunks: [*]const usize, chunk_size: usize) c_int;
 /// the same in parts: the machines' state stays in device memory between the parts; a batch holding part state is destroyed
@@ -413,6 +415,10 @@ pub extern "c" fn fvad_clips_plan(clips: ?[*]const u64, n_clips: usize, out_form
 pub extern "c" fn fvad_clips_from_segments(segs: ?[*]const SpeechSegment, n_segs: usize, first_lane: u32, n_channels: u32, n_available: u64, clips: ?[*]u64, cap: usize, n_out: *usize, n_skipped: *usize) c_int;
 pub extern "c" fn fvad_clips_export_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
 pub extern "c" fn fvad_clips_export(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
+// the same over a split source: a head piece in A (the held tail of earlier slices) followed by a body piece in B (the slice)
+pub extern "c" fn fvad_clips_split_check(d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, offsets: ?[*]u64, total: ?*u64) c_int;
+pub extern "c" fn fvad_clips_export_split_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
+pub extern "c" fn fvad_clips_export_split(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
 
 // audio file input / output (host)
 // device-side ingest: interleaved PCM16 / PCM24 / f32 bytes de-interleaved, decoded and zero-padded into planar device lanes

@@ -26,6 +26,7 @@ FVAD_ERR_MODEL_FORMAT = -104
 FVAD_ERR_NOT_AVAILABLE = -107
 CLIP_F32, CLIP_PCM16 = 0, 1      # sample formats of fvad_clips_*
 CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, sample_to (uint64 each)
+CLIP_SPLIT_FIELDS = 7            # a split clip: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (uint64 each)
 INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
 INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
@@ -246,6 +247,7 @@ SIGNATURES = {
     "fvad_vad_batch_config_segments": (C.c_int, [vp, sz, C.POINTER(SpeechSegment), sz, C.POINTER(sz)]),
     "fvad_vad_batch_config_audit": (C.c_int, [vp, sz, sz, C.POINTER(VadAudit)]),
     "fvad_vad_batch_lazy_stats": (C.c_int, [vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_vad_batch_hold_from": (C.c_int, [vp, sz, C.POINTER(C.c_uint64)]),
     "fvad_vad_batch_run_device": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz]),
     "fvad_vad_batch_run_device_part": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz), c_float_p, sz, C.POINTER(sz), sz, C.c_uint64]),
     "fvad_vad_batch_score_device": (C.c_int, [vp, vp]),
@@ -324,6 +326,12 @@ SIGNATURES = {
                                            c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
     "fvad_clips_export": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
                                     c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fvad_clips_split_check": (C.c_int, [vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.c_int,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_split_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                 C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_split": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                          C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
     "fvad_wav_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
@@ -685,6 +693,29 @@ class Context:
         res["out"] = out[:total]
         return res
 
+    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None):
+        """fvad_clips_export_split (d_out None) or fvad_clips_export_split_device: a and b are the two source buffers as
+        (device address or None, n_lanes, lane_stride, n_samples); clips: [n][CLIP_SPLIT_FIELDS] uint64, channel c of a clip
+        being a[a_lane + c][a_from, a_from + a_len) followed by b[b_lane + c][b_from, b_from + b_len).  Returns what
+        clips_export does."""
+        clips = _clip_split_rows(clips)
+        n = clips.shape[0]
+        offsets, total = clips_plan([(0, 1, 0, int(r[3]) + int(r[6])) for r in clips], out_pcm16) if n else (None, 0)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        args = (self.h, vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3], CLIP_PCM16 if src_pcm16 else CLIP_F32,
+                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_PCM16 if out_pcm16 else CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)))
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total}
+        if d_out is not None:
+            self._ck(lib().fvad_clips_export_split_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
+                     "fvad_clips_export_split_device")
+            return res
+        out = np.zeros(max(total, 1), np.int16 if out_pcm16 else np.float32)
+        self._ck(lib().fvad_clips_export_split(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
+                 "fvad_clips_export_split")
+        res["out"] = out[:total]
+        return res
+
     def ingest(self, sources, out_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, raw=None, raw_bytes=None):
         """fvad_ingest_device (raw: a device address holding raw_bytes bytes) or fvad_ingest (raw: a list with one C-contiguous
         numpy / memmap byte buffer per source, or None for a source without frames; a source's byte_offset is relative to its
@@ -1011,6 +1042,17 @@ class VadBatch:
                                             chunk_size, first_frame, n_threads), "fvad_vad_batch_run_part")
         return self._segments() if want_segments else None
 
+    def hold_from(self):
+        """fvad_vad_batch_hold_from: per stream the smallest sample_from a segment not yet reported can still get --
+        the audio a run sliced in time must keep.  Defined after host runs only."""
+        out = (C.c_uint64 * self.n_streams)()
+        st = lib().fvad_vad_batch_hold_from(self.h, 0, out)
+        if st == FVAD_ERR_INVALID_ARGUMENT:
+            raise FvadError(st, "fvad_vad_batch_hold_from", "a bad config, a part in flight, or the last run was a device run: "
+                            "the machines' state is not on the host")
+        check(st, "fvad_vad_batch_hold_from")
+        return list(out)
+
     def audit(self, stream):
         a = VadAudit()
         check(lib().fvad_vad_batch_audit(self.h, stream, C.byref(a)), "fvad_vad_batch_audit")
@@ -1287,6 +1329,17 @@ class VadSweep:
         flat = [(a.sample_from, a.sample_to, a.avg_channel_vol_ratio, a.vad_met_sec) for a in arr[:n]]
         return [flat[offs[s]:offs[s + 1]] for s in range(self.n_streams)]
 
+    def hold_from(self, config=0):
+        """fvad_vad_batch_hold_from: per stream the smallest sample_from a segment not yet reported by `config`'s machines can still get --
+        the audio a run sliced in time must keep.  Defined after host runs only."""
+        out = (C.c_uint64 * self.n_streams)()
+        st = lib().fvad_vad_batch_hold_from(self.h, config, out)
+        if st == FVAD_ERR_INVALID_ARGUMENT:
+            raise FvadError(st, "fvad_vad_batch_hold_from", "a bad config, a part in flight, or the last run was a device run: "
+                            "the machines' state is not on the host")
+        check(st, "fvad_vad_batch_hold_from")
+        return list(out)
+
     def audit(self, stream, config):
         a = VadAudit()
         check(lib().fvad_vad_batch_config_audit(self.h, stream, config, C.byref(a)), "fvad_vad_batch_config_audit")
@@ -1408,6 +1461,25 @@ def vad_run_many(machines, bands, ratios, first_index=None, fft_size=1024, n_thr
 
 def _clip_rows(clips):
     return np.ascontiguousarray(np.asarray(clips, np.uint64).reshape(-1, CLIP_FIELDS))
+
+
+def _clip_split_rows(clips):
+    return np.ascontiguousarray(np.asarray(clips, np.uint64).reshape(-1, CLIP_SPLIT_FIELDS))
+
+
+def clips_split_check(a, b, src_pcm16, clips, out_pcm16=False, out=1 << 20, out_capacity=None, device_out=True, src_format=None,
+                      out_format=None):
+    """fvad_clips_split_check (host only; a, b as for Context.clips_export_split, `out` an address) -> (status, offsets, total)"""
+    clips = _clip_split_rows(clips)
+    n = clips.shape[0]
+    offsets, total = np.zeros(n, np.uint64), C.c_uint64(0)
+    st = lib().fvad_clips_split_check(vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
+                                      (CLIP_PCM16 if src_pcm16 else CLIP_F32) if src_format is None else src_format,
+                                      clips.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                      (CLIP_PCM16 if out_pcm16 else CLIP_F32) if out_format is None else out_format, vp(out),
+                                      (1 << 62) if out_capacity is None else out_capacity, int(device_out),
+                                      offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    return st, offsets, total.value
 
 
 def clips_plan(clips, out_pcm16=False):

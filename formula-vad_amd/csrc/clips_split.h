@@ -1,0 +1,25 @@
+// clips_split.h -- the argument rules of fvad_clips_export_split(_device), host only (host_clips_split.cpp), shared with the
+// export itself (engine_clips_split.cpp)
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/fvad.h"
+
+namespace fvad {
+
+constexpr uint64_t kSplitTile = 8192; // kClipTile of kernels.h (engine_clips_split.cpp asserts it)
+
+struct SplitRow { uint64_t n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len; };
+inline SplitRow split_row(const uint64_t* clips, size_t i)
+{
+    const uint64_t* r = clips + i * FVAD_CLIP_SPLIT_FIELDS;
+    return {r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+}
+
+// fvad_clips_split_check with the reason of a refusal in *why (a literal)
+int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
+                      size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
+                      const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why);
+
+} // namespace fvad

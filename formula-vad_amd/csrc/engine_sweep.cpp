@@ -646,6 +646,7 @@ int run_device(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_t ban
     b->scored = b->has_refs;
     if (b->has_refs) b->scores = std::move(scores);
     b->machines.clear(); // nothing to continue from: a later fvad_vad_batch_run_part must start at frame 0
+    b->state_on_device = true;
     b->next_sample = 0;
     return FVAD_OK;
 }
@@ -955,6 +956,7 @@ int run_device_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
         for (auto& v : b->segs) std::vector<fvad_speech_segment>().swap(v);
     }
     b->machines.clear(); // a host part cannot go on from a device part
+    b->state_on_device = true;
     const bool keep = b->keep_segments;
     dp->segs_on_device = dp->segs_on_device && !keep;
     dp->next_sample = UINT64_MAX; // (until this part has run: after an error the run starts again at sample 0)
@@ -1180,6 +1182,7 @@ int run_shared_part(fvad_ctx* ctx, fvad_vad_batch* b, const float* d_band, size_
     }
     fvad_vad_batch* tb = b->trig.get();
     b->machines.clear();
+    b->state_on_device = true;
     const bool keep = b->keep_segments;
     dp->segs_on_device = dp->segs_on_device && !keep;
     dp->next_sample = UINT64_MAX;

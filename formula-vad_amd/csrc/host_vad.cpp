@@ -695,6 +695,7 @@ int retain_stage(const fvad_vad_batch* b, const uint32_t* keep, size_t n_keep, f
     nb->segs_kept = b->segs_kept;
     nb->next_sample = b->next_sample;
     nb->chain_form = b->chain_form;
+    nb->state_on_device = b->state_on_device;
     nb->avgs_form = b->avgs_form;
     nb->avgs_bytes = b->avgs_bytes;
     nb->trigger_form = b->trigger_form;
@@ -807,6 +808,7 @@ static int run_host(fvad_vad_batch* b, const float* band, size_t band_stride, co
             for (size_t ch = 0; ch < C; ++ch) vols[ch] = bb[ch * band_stride + f];
             m.run((first_frame + f) * F, vols.data(), has[f] != 0, ratio[f]);
         }
+        m.next_index = (first_frame + nf) * F;
         b->segs[s * NC + c] = m.segments; // (everything so far: a segment is appended when it closes)
         b->audits[s * NC + c] = m.audit;
         b->exact_evals[s * NC + c] = m.exact_evals;
@@ -842,6 +844,7 @@ static int run_host(fvad_vad_batch* b, const float* band, size_t band_stride, co
     for (size_t g = 1; g < G; ++g)
         if (first_sample + n_frames[g] * b->sizes[g] != b->next_sample) b->next_sample = UINT64_MAX; // (the sizes ended apart)
     b->segs_kept = true;
+    b->state_on_device = false;
     b->scored = false; // the scores were of the previous segments
     return FVAD_OK;
 }
@@ -898,6 +901,21 @@ int fvad_vad_batch_config_segments(const fvad_vad_batch* b, size_t config, fvad_
     for (size_t s = 0; s < b->n_streams; ++s) {
         const auto& v = b->segs[s * NC + config];
         if (!v.empty()) memcpy(out + offsets[s], v.data(), v.size() * sizeof(fvad_speech_segment));
+    }
+    return FVAD_OK;
+}
+
+int fvad_vad_batch_hold_from(const fvad_vad_batch* b, size_t config, uint64_t* hold_from)
+{
+    if (!b || !hold_from || config >= b->cfgs.size() || b->part_in_flight) return FVAD_ERR_INVALID_ARGUMENT;
+    if (b->state_on_device) return FVAD_ERR_INVALID_ARGUMENT; // after a device run the machines' state is not on the host
+    const size_t NC = b->cfgs.size();
+    for (size_t s = 0; s < b->n_streams; ++s) {
+        if (b->machines.empty()) { hold_from[s] = 0; continue; } // nothing has run
+        const fvad::VadMachine& m = *b->machines[s * NC + config];
+        // a closed machine's next segment starts at the next frame at the earliest, less its pre-roll; an opening, open or closing
+        // one has fixed its speech_start, and sample_from with it (vad_machine.h)
+        hold_from[s] = fvad::offset_start(m.cf, m.state == fvad::VadMachineState::CLOSED ? m.next_index : m.speech_start);
     }
     return FVAD_OK;
 }

@@ -46,6 +46,7 @@ struct VadMachine : VadMachineState { // src/AudioPipeline/VADMachine.zig; the s
     size_t n_channels;
     RollingAverage long_term, short_term, ch_ratio;
     std::vector<fvad_speech_segment> segments;
+    uint64_t next_index = 0; // the first sample of the next frame to run (fvad_vad_batch_hold_from)
     // the long-term average is lazily exact (see host_vad.cpp): pushes on the full ring update the bound of vad_machine.h, and
     // the chain over the ring's cached products runs only when that bound cannot settle a comparison
     bool lt_lazy = true; // FVAD_VAD_EAGER=1 in the environment: run the chain on every push (testing aid)
@@ -120,6 +121,8 @@ struct fvad_vad_batch {
     // fvad_vad_batch_run_device_part_async has launched a part and fvad_vad_batch_part_wait has not finished it: until then every
     // call that runs, scores, retains, reads results of or sets something on the batch returns FVAD_ERR_INVALID_ARGUMENT
     bool part_in_flight = false;
+    // the last run was a device run: the machines' state is in device memory or gone, not in `machines` (fvad_vad_batch_hold_from)
+    bool state_on_device = false;
     // fvad_vad_batch_chain_form: 0 = no device launch yet, 1 = the last one ran the lane form of the machines' kernel, 2 = the cooperative form
     int chain_form = 0;
     // The keys of the averages' tables (context option vad_avgs "table", kernels_vadavgs.hip), in first-seen config order: a short

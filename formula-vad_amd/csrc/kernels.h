@@ -442,6 +442,22 @@ int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream);    // hipError_
 int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream);   // (after fvad_launch_clip_rms on the same stream)
 int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick)
 
+// The split-source form (kernels_clips_split.hip, fvad_clips_export_split*): a clip's channel ch is a_len samples at
+// a + a_off + ch * a_stride followed by len - a_len samples at b + b_off + ch * b_stride, and is read as if it were one run.
+// Units, tiles (counted from the clip's first sample), partials and infos are ClipArgs', and clip_pick_kernel runs on `c` as it
+// is; c.src / c.lane_stride are piece A's, c.jobs[i].src_off is not used.
+struct ClipSplit {
+    uint64_t a_off, a_len, b_off, pad; // elements; a_len <= c.jobs[i].len
+};
+struct ClipSplitArgs {
+    ClipArgs c;
+    const void* b;
+    uint64_t b_stride;
+    const ClipSplit* splits; // [n_clips] (device)
+};
+int fvad_launch_clip_rms_split(const ClipSplitArgs& a, hipStream_t stream);    // hipError_t as int
+int fvad_launch_clip_gather_split(const ClipSplitArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.c) after the rms)
+
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
 // multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane

@@ -484,7 +484,7 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
             ctx.device_free(d)
 
 
-def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host"):
+def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -497,21 +497,31 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     Segments and report are run_plan's whenever both passes select the same NSNet2 kernels (fvad_ctx_last_nn_path): the resident
     pass pads every lane to the longest instance, so a plan of unequal lengths may be cut into other launches (the context option
     "reproducible" makes the two agree bit for bit for every plan).
-    ingest "device": the files' bytes go to the GPU as they are and are decoded there (run_grid); the same clips and manifests."""
+    ingest "device": the files' bytes go to the GPU as they are and are decoded there (run_grid); the same clips and manifests.
+    slice_chunks N: the same files, manifests, report and return value from time slices of N chunks (_clips_sliced_share), the
+    device memory bounded by a slice and the held tails instead of the corpus; None is the resident path above.
+    info (a dict): filled with "held_peak_bytes", the most device memory the held tails took on one context, and "slices"."""
     _check_ingest(ingest)
     plan = load_plan(plan_path)
+    if slice_chunks is not None:
+        check_slice_chunks(slice_chunks, plan["fft_size"])
     own_ctx = ctx is None
     ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])] if own_ctx else [ctx]
     try:
         os.makedirs(out_dir, exist_ok=True)
-        loaded = _load_instances(plan, ingest)
+        loaded = _load_instances(plan, ingest, mapped=slice_chunks is not None)
         audio, refs = [a for a, _ in loaded], [r for _, r in loaded]
         parts = instance_shares(len(audio), len(ctxs))
         done, errs = [None] * len(ctxs), []
+        notes = [{} for _ in ctxs]
 
         def work(d):
             try:
-                done[d] = _clips_share(ctxs[d], plan, [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]], out_dir, pcm16)
+                insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
+                if slice_chunks is None:
+                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16)
+                else:
+                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d])
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -531,11 +541,184 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
             res["clips"] = manifest
             with open(os.path.join(out_dir, f"{manifest['name']}-clips.json"), "w") as f:
                 json.dump(manifest, f, indent=1)
+        if info is not None and slice_chunks is not None:
+            info["held_peak_bytes"] = max([n.get("held_peak_bytes", 0) for n in notes] + [0])
+            info["slices"] = sum(n.get("slices", 0) for n in notes)
         return text, results
     finally:
         if own_ctx:
             for c in ctxs:
                 c.close()
+
+
+class _HeldTails:
+    """The audio of earlier slices that a sliced run_clips still needs, of one kind (original or denoised) for one channel-count
+    group: every lane's samples [base, end) as f32 in a device buffer of L lanes `stride` apart, and a second buffer that the
+    next carry writes (fvad_clips_export_split_device over this buffer and the slice, equal formats: the bits).  One base for
+    the whole group -- the smallest any of its streams needs -- keeps the buffer a plain lane layout."""
+
+    def __init__(self, ctx, n_lanes):
+        self.ctx, self.L = ctx, n_lanes
+        self.bufs = [[None, 0], [None, 0]]   # [device address, bytes]
+        self.cur = 0
+        self.base = self.end = 0
+        self.stride = 0
+
+    def a(self):
+        """the held buffer as fvad_clips_export_split's A"""
+        if self.end == self.base:
+            return (None, 0, 0, 0)
+        return (self.bufs[self.cur][0], self.L, self.stride, self.end - self.base)
+
+    def bytes(self):
+        return sum(b[1] for b in self.bufs)
+
+    def carry(self, b, b_abs0, b_from, b_to, hold):
+        """keep [hold, b_to) of every lane: [hold, b_from) from the held buffer, the rest from the slice's lanes b (A/B tuple;
+        its sample 0 is absolute sample b_abs0, [b_from, b_to) of it valid).  hold None: nothing is needed any more."""
+        if hold is None or hold >= b_to:
+            self.base = self.end = b_to
+            return
+        hold = max(hold, self.base)
+        n = b_to - hold
+        n_a = max(min(b_from, self.end) - hold, 0)
+        assert self.end == b_from or n_a == 0
+        stride = (n + 3) // 4 * 4
+        other = self.bufs[1 - self.cur]
+        if other[1] < self.L * stride * 4:           # the plan's total says so: grow
+            if other[0] is not None:
+                self.ctx.device_free(other[0])
+                other[0], other[1] = None, 0
+            other[0], other[1] = self.ctx.device_alloc(self.L * stride * 4), self.L * stride * 4
+        rows = [(1, l if n_a else 0, hold - self.base if n_a else 0, n_a, l, hold + n_a - b_abs0, n - n_a) for l in range(self.L)]
+        res = self.ctx.clips_export_split(self.a(), b, False, rows, out_pcm16=False, d_out=other[0], out_capacity=self.L * stride)
+        assert [int(o) for o in res["offsets"]] == [l * stride for l in range(self.L)]   # the lanes' new bases
+        self.cur, self.base, self.end, self.stride = 1 - self.cur, hold, b_to, stride
+
+    def close(self):
+        for b in self.bufs:
+            if b[0] is not None:
+                self.ctx.device_free(b[0])
+                b[0], b[1] = None, 0
+
+
+def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note):
+    """run_clips(slice_chunks=N) for the instances of one context -> [(segments, audit, manifest)] in the order given.
+    Channel-count group after group, each in time slices [s0, s1) of N chunks read, denoised and band-summed as a sliced grid's
+    (_slice_denoise_and_bands; audio mapped or raw), one single-config host batch per instance run on part by part (_HostParts).
+    After each part, per kind (the reference's two recorders): the clips due -- the segments reported so far whose end the
+    kind's audio has reached -- are exported in ONE fvad_clips_export_split over the held tail (A) and the slice's lanes (B:
+    [s0, s1) of them is valid, the halo is not), the others stay pending or, once their stream has ended, are counted skipped;
+    then the tail every pending or still possible clip needs (fvad_vad_batch_hold_from, the pending clips' starts) is carried
+    into the other held buffer (_HeldTails).  The slices run one chunk past a group's last whole chunk where a file ends inside a
+    chunk, so that the original audio's last samples are reached.  note: "held_peak_bytes", "slices"."""
+    if not audio:
+        return []
+    chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
+    dims = [_dims(a, mapped=True) for a in audio]
+    n_frames, n_chunks = [d[1] for d in dims], [d[1] // chunk for d in dims]
+    groups = {}
+    for i, d in enumerate(dims):
+        groups.setdefault(d[0], []).append(i)
+    job = _SweepJob([plan["vad_machine_config"]], [None], [F], False, F, N, "host", "host", 1, False)
+    opts = _engine_opts(job.configs[0], F)
+    n_max, fr_slice = N + H, N * chunk // F
+    lanes_max = max(len(m) * nch for nch, m in groups.items())
+    own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4, "band0": lanes_max * (n_max * chunk // F + 1) * 4,
+           "rms": lanes_max * n_max * 4, "bands": lanes_max * fr_slice * 4}
+    d, host = {}, None
+    times = collections.defaultdict(float)
+    segs_of, audits = [[] for _ in audio], [None] * len(audio)
+    entries = [{} for _ in audio]                   # [instance]{(segment, kind): manifest entry}
+    skipped = [{"original": 0, "denoised": 0} for _ in audio]
+    note.update(held_peak_bytes=0, slices=0)
+    try:
+        for k, nb in own.items():
+            d[k] = ctx.device_alloc(max(nb, 16))
+        if not _is_raw(audio):
+            host = ctx.host_alloc(lanes_max * n_max * chunk)
+        buf = _SliceBufs(d, host, opts, fr_slice)
+        for nch, members in groups.items():
+            L = len(members) * nch
+            m = _HostParts(ctx, job, nch, [None] * len(members))
+            tails = {"original": _HeldTails(ctx, L), "denoised": _HeldTails(ctx, L)}
+            pending = {kind: [[] for _ in members] for kind in tails}     # [member][(segment, from, to)]
+            seen = [0] * len(members)
+            try:
+                K = max(-(-n_frames[i] // chunk) for i in members)
+                for s0 in range(0, K, N):
+                    s1 = min(s0 + N, K)
+                    start = max(s0 - H, 0)
+                    n = s1 - start
+                    note["slices"] += 1
+                    rms = _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, m.blocks, times)
+                    nc = [max(0, min(n_chunks[i], s1) - s0) for i in members]
+                    nf = [[max(0, min(n_chunks[i] * chunk // F, s1 * chunk // F) - s0 * chunk // F) for i in members]]
+                    if max(nf[0]) > 0 or s0 == 0:
+                        m.part(d["bands"], fr_slice, nf, rms, nc, s0 * chunk)
+                    holds = []
+                    for k, i in enumerate(members):
+                        segs = m.hosts[k].segments(0)[0]
+                        for kind in tails:
+                            pending[kind][k] += [(j, int(sg[0]), int(sg[1])) for j, sg in enumerate(segs[seen[k]:], seen[k])]
+                        seen[k], segs_of[i] = len(segs), segs
+                        holds.append(None if s1 >= n_chunks[i] else m.hosts[k].hold_from(0)[0])   # (an ended machine reports nothing more)
+                    for kind, d_b in (("original", d["pcm"]), ("denoised", d["den"])):
+                        t = tails[kind]
+                        b = (d_b, L, n * chunk, n * chunk)
+                        rows, owner, need = [], [], []
+                        for k, i in enumerate(members):
+                            reach = min(n_frames[i], s1 * chunk) if kind == "original" else min(n_chunks[i], s1) * chunk
+                            ended = s1 * chunk >= n_frames[i] if kind == "original" else s1 >= n_chunks[i]
+                            still = []
+                            for j, a0, a1 in pending[kind][k]:
+                                if a1 > reach:
+                                    if ended:   # Recorder.finalize never runs for a recording whose end the stream does not reach
+                                        skipped[i][kind] += 1
+                                    else:
+                                        still.append((j, a0, a1))
+                                    continue
+                                cut = min(max(a0, s0 * chunk), a1)                      # the seam: [a0, cut) is held, [cut, a1) in the slice
+                                n_a, n_b = cut - a0, a1 - cut
+                                assert n_a == 0 or t.base <= a0 < t.end == s0 * chunk, "a due clip starts in front of the held tail"
+                                rows.append((nch, k * nch if n_a else 0, a0 - t.base if n_a else 0, n_a,
+                                             k * nch if n_b else 0, cut - start * chunk if n_b else 0, n_b))
+                                owner.append((i, j))
+                            pending[kind][k] = still
+                            need += [a0 for _, a0, _ in still] + ([] if holds[k] is None else [holds[k]])
+                        if rows:
+                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16)
+                            for r, (i, j), o, bc, br, rr in zip(rows, owner, res["offsets"], res["best_channel"], res["best_rms"], res["runner_up_rms"]):
+                                o, n_clip = int(o), r[3] + r[6]
+                                path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], j, kind))
+                                (fv.wav_write_i16 if pcm16 else fv.wav_write)(path, res["out"][o:o + n_clip])
+                                entries[i][(j, kind)] = {"file": os.path.basename(path), "best_channel": int(bc), "best_rms": float(br),
+                                                         "runner_up_rms": float(rr)}
+                        t.carry(b, start * chunk, s0 * chunk, s1 * chunk, min(need) if need else None)
+                    note["held_peak_bytes"] = max(note["held_peak_bytes"], sum(t.bytes() for t in tails.values()))
+                for k, i in enumerate(members):
+                    audits[i] = m.hosts[k].audit(0, 0)
+            finally:
+                for t in tails.values():
+                    t.close()
+                m.close()
+    finally:
+        for a in d.values():
+            ctx.device_free(a)
+        if host is not None:
+            ctx.host_free(host)
+    out = []
+    for i, inst in enumerate(insts):
+        manifest = {"name": inst["name"], "sample_rate": 48000, "pcm16": bool(pcm16), "clips": []}
+        for j, sg in enumerate(segs_of[i]):
+            c = {"segment": j, "start": int(sg[0]), "length": int(sg[1] - sg[0])}
+            for kind in ("original", "denoised"):
+                if (j, kind) in entries[i]:
+                    c[kind] = entries[i][(j, kind)]
+            manifest["clips"].append(c)
+        manifest["original_skipped"], manifest["denoised_skipped"] = skipped[i]["original"], skipped[i]["denoised"]
+        out.append((segs_of[i], audits[i], manifest))
+    return out
 
 
 SWEEP_COLUMNS = ("P", "TP", "FP", "FN", "TPR", "PPV", "FNR", "FDR", "F", "FM")
@@ -1789,7 +1972,7 @@ def arg_parser():
                                                           "print the top configs (on --devices, default device 0)")
     ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
     ap.add_argument("--slice-chunks", type=int, default=None,
-                    help="with --sweep-grid: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
+                    help="with --sweep-grid or --export-clips: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
                          "sizes, of the lcm over them), device and host "
                          "memory bounded by the slice instead of the corpus")
     ap.add_argument("--halving-eta", type=int, default=None,
@@ -1831,8 +2014,12 @@ def main(argv=None):
                  overlap=a.overlap, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs, vad_trigger=a.vad_trigger, ingest=a.ingest)
         return
     if a.export_clips:
-        text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest)
+        info = {}
+        text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest,
+                            slice_chunks=a.slice_chunks, info=info)
         sys.stdout.write(text)
+        if info:
+            sys.stdout.write(f"\n[{info['slices']} slices; held tails: {info['held_peak_bytes'] / 2 ** 20:.1f} MiB of device memory at most]\n")
         return
     if a.sweep:
         run_sweep(a.input, synth_seed=a.synth_seed, json_path=a.sweep_json, vad_on=a.sweep_vad, vad_chain=a.vad_chain, vad_avgs=a.vad_avgs,

@@ -825,6 +825,52 @@ int fvad_clips_export(fvad_ctx *ctx, const void *d_src, int src_format, size_t n
                       const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
                       int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets);
 
+/* ------------------------------------------------------------------ batch Recorder over a split source
+ * For runs sliced in time: a clip may begin in audio of earlier slices and end in the current one, so its samples are a head
+ * piece in one device buffer (A: the held tail of earlier slices) followed by a body piece in another (B: the current slice's
+ * lanes) -- the SplitSlice MRBRecorder reads a recording from its ring as (MRBRecorder.zig:160-192), and what fvad_fft_forward
+ * takes as (first, n1, second, n2).  The kernels read the two pieces as one run (csrc/kernels_clips_split.hip).
+ * - A split clip is a row of FVAD_CLIP_SPLIT_FIELDS uint64: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len.  Its
+ *   channel c is A[a_lane + c][a_from, a_from + a_len) followed by B[b_lane + c][b_from, b_from + b_len).  Either length may be
+ *   0, not both; a piece of no samples has no other rule.  d_a (d_b) may be NULL when no row takes samples from it.
+ * - A and B have one sample format, src_format; each has its own lane count, stride and sample count.
+ * - Slots, formats, conversions and the per-clip reports are fvad_clips_export's: the slots are those fvad_clips_plan gives
+ *   clips of lengths a_len + b_len in the same order.
+ * - INVARIANT: a split clip's samples, best_channel, best_rms and runner_up_rms are the bits fvad_clips_export_device gives
+ *   for the same samples laid out contiguously, wherever the seam is (tiles and sums are counted from the clip's first sample).
+ *   Equal formats move the bits (NaN payloads, -0, denormals), so a mono clip per lane with equal formats carries a tail from
+ *   one held buffer to the other; out_offsets are then the lanes' new bases.
+ *
+ * fvad_clips_split_check (host only; pointers are addresses, nothing is read through d_a, d_b or out): every argument rule of
+ * the two exports, in the one order both report them in -- FVAD_ERR_INVALID_ARGUMENT for NULL clips / out, a bad format or a
+ * NULL source that a row takes samples from; for a source not aligned to its samples or (device_out) an out not 16-byte
+ * aligned; for a stride below its sample count (of a buffer of more than one lane); for a row with both lengths 0 or no
+ * channels; FVAD_ERR_OUT_OF_RANGE for a piece past its buffer's samples or lanes; FVAD_ERR_BUFFER_TOO_SMALL when out_capacity
+ * is below the total; FVAD_ERR_INVALID_ARGUMENT when the total's bytes at `out` overlap A's or B's address range, and for more
+ * than 2^31 - 1 (clip, channel, tile) units of 8192 samples.  Fills offsets (may be NULL) and *total (may be NULL; 0 until the
+ * rows' own rules have passed).  n_clips == 0 succeeds.
+ * fvad_clips_export_split_device / fvad_clips_export_split: as fvad_clips_export_device / fvad_clips_export; every error comes
+ * back before any launch.  fvad_ctx_kernel_times names clip_rms_split, clip_pick, clip_gather_split. */
+#define FVAD_CLIP_SPLIT_FIELDS 7
+int fvad_clips_split_check(const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b, size_t b_lanes,
+                           size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips, size_t n_clips,
+                           int out_format, const void *out, size_t out_capacity, int device_out, uint64_t *offsets,
+                           uint64_t *total);
+int fvad_clips_export_split_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                   const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                   const uint64_t *clips, size_t n_clips, int out_format, void *d_out, size_t out_capacity,
+                                   int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets);
+int fvad_clips_export_split(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b,
+                            size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips,
+                            size_t n_clips, int out_format, void *out, size_t out_capacity, int32_t *best_channel,
+                            float *best_rms, float *runner_up_rms, uint64_t *out_offsets);
+/* fvad_vad_batch_hold_from (host only): per stream, the smallest sample_from that a segment not yet reported by machine
+ * (stream, config) can still get -- what a caller that slices a run in time must keep of the audio behind it.  A closed machine:
+ * next - min(start_buffer, next), next the first sample of the next frame to run; an opening, open or closing one: its pending
+ * segment's sample_from.  A batch that has run nothing: 0.  Defined after host runs (fvad_vad_batch_run, _run_part,
+ * _run_sized); after a device run the machines' state is not on the host: FVAD_ERR_INVALID_ARGUMENT. */
+int fvad_vad_batch_hold_from(const fvad_vad_batch *b, size_t config, uint64_t *hold_from);
+
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
  * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
