@@ -419,6 +419,14 @@ pub extern "c" fn fvad_clips_export(ctx: *Ctx, d_src: *const anyopaque, src_form
 pub extern "c" fn fvad_clips_split_check(d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, offsets: ?[*]u64, total: ?*u64) c_int;
 pub extern "c" fn fvad_clips_export_split_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
 pub extern "c" fn fvad_clips_export_split(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64) c_int;
+// with a stride: of clip i the samples skips[i], skips[i] + step, ... of the picked channel (step 3: the denoiser's own 16 kHz)
+pub const clip_step_max = 16; // FVAD_CLIP_STEP_MAX
+pub extern "c" fn fvad_clips_phase_skips(sample_from: ?[*]const u64, n_clips: usize, step: u32, phase: u32, skips: ?[*]u32) c_int;
+pub extern "c" fn fvad_clips_plan_strided(lens: ?[*]const u64, skips: ?[*]const u32, n_clips: usize, step: u32, out_format: c_int, out_lens: ?[*]u64, offsets: ?[*]u64, total: *u64) c_int;
+pub extern "c" fn fvad_clips_export_strided_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
+pub extern "c" fn fvad_clips_export_strided(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
+pub extern "c" fn fvad_clips_export_split_strided_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
+pub extern "c" fn fvad_clips_export_split_strided(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
 
 // audio file input / output (host)
 // device-side ingest: interleaved PCM16 / PCM24 / f32 bytes de-interleaved, decoded and zero-padded into planar device lanes

@@ -27,6 +27,7 @@ FVAD_ERR_NOT_AVAILABLE = -107
 CLIP_F32, CLIP_PCM16 = 0, 1      # sample formats of fvad_clips_*
 CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, sample_to (uint64 each)
 CLIP_SPLIT_FIELDS = 7            # a split clip: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (uint64 each)
+CLIP_STEP_MAX = 16               # the largest step of the strided clip exports
 INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
 INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
@@ -332,6 +333,19 @@ SIGNATURES = {
                                                  C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
     "fvad_clips_export_split": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
                                           C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64)]),
+    "fvad_clips_phase_skips": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fvad_clips_plan_strided": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), sz, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_strided_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                                   c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fvad_clips_export_strided": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                            c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fvad_clips_export_split_strided_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                         C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                                         C.POINTER(C.c_uint32)]),
+    "fvad_clips_export_split_strided": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                  C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                                  C.POINTER(C.c_uint32)]),
     "fvad_wav_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
@@ -671,12 +685,18 @@ class Context:
                                                     b.ctypes.data_as(C.POINTER(C.c_int32)), b.shape[0], vp(d_band), band_stride),
                  "fvad_engine_band_sums_device")
 
-    def clips_export(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, out_pcm16=False, d_out=None, out_capacity=None):
+    def clips_export(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, out_pcm16=False, d_out=None, out_capacity=None,
+                     step=1, skips=None):
         """fvad_clips_export (d_out None: the packed clips come back as a numpy array of the output format) or
         fvad_clips_export_device (d_out: a device address with room for out_capacity samples).  clips: [n][CLIP_FIELDS] uint64.
-        Returns dict(best_channel, best_rms, runner_up_rms, offsets, total[, out])."""
+        Returns dict(best_channel, best_rms, runner_up_rms, offsets, total[, out]).
+        step != 1 or skips: fvad_clips_export_strided(_device) -- of clip i the samples skips[i], skips[i] + step, ... (skips None:
+        all 0); the dict then has "out_lens" too."""
         clips = _clip_rows(clips)
         n = clips.shape[0]
+        if step != 1 or skips is not None:
+            return self._clips_export_strided("fvad_clips_export_strided", (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples),
+                                              clips, clips[:, 3] - clips[:, 2], out_pcm16, d_out, out_capacity, step, skips)
         offsets, total = clips_plan(clips, out_pcm16)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
         args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
@@ -693,13 +713,35 @@ class Context:
         res["out"] = out[:total]
         return res
 
-    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None):
+    def _clips_export_strided(self, name, src_args, clips, lens, out_pcm16, d_out, out_capacity, step, skips):
+        """the four strided calls: `name` (+ "_device" with d_out), src_args the arguments between ctx and the clips"""
+        n = clips.shape[0]
+        skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+        out_lens, offsets, total = clips_plan_strided(lens, skips, step, out_pcm16) if n else (np.zeros(0, np.uint64), None, 0)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        args = (self.h, *src_args, clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_PCM16 if out_pcm16 else CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)))
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "out_lens": out_lens}
+        if d_out is not None:
+            self._ck(getattr(lib(), name + "_device")(*args, vp(d_out), total if out_capacity is None else out_capacity, *info), name + "_device")
+            return res
+        out = np.zeros(max(total, 1), np.int16 if out_pcm16 else np.float32)
+        self._ck(getattr(lib(), name)(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info), name)
+        res["out"] = out[:total]
+        return res
+
+    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None, step=1, skips=None):
         """fvad_clips_export_split (d_out None) or fvad_clips_export_split_device: a and b are the two source buffers as
         (device address or None, n_lanes, lane_stride, n_samples); clips: [n][CLIP_SPLIT_FIELDS] uint64, channel c of a clip
         being a[a_lane + c][a_from, a_from + a_len) followed by b[b_lane + c][b_from, b_from + b_len).  Returns what
-        clips_export does."""
+        clips_export does; step / skips as there (fvad_clips_export_split_strided(_device))."""
         clips = _clip_split_rows(clips)
         n = clips.shape[0]
+        if step != 1 or skips is not None:
+            return self._clips_export_strided("fvad_clips_export_split_strided", (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
+                                              CLIP_PCM16 if src_pcm16 else CLIP_F32), clips, clips[:, 3] + clips[:, 6], out_pcm16, d_out,
+                                              out_capacity, step, skips)
         offsets, total = clips_plan([(0, 1, 0, int(r[3]) + int(r[6])) for r in clips], out_pcm16) if n else (None, 0)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
         args = (self.h, vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3], CLIP_PCM16 if src_pcm16 else CLIP_F32,
@@ -1490,6 +1532,28 @@ def clips_plan(clips, out_pcm16=False):
     check(lib().fvad_clips_plan(clips.ctypes.data_as(C.POINTER(C.c_uint64)), clips.shape[0], CLIP_PCM16 if out_pcm16 else CLIP_F32,
                                 offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan")
     return offsets, total.value
+
+
+def clips_phase_skips(sample_from, step, phase):
+    """fvad_clips_phase_skips: per clip the first kept sample, so that the kept samples are the lane indices = phase (mod step)"""
+    sample_from = np.ascontiguousarray(np.asarray(sample_from, np.uint64).reshape(-1))
+    skips = np.zeros(sample_from.shape[0], np.uint32)
+    check(lib().fvad_clips_phase_skips(sample_from.ctypes.data_as(C.POINTER(C.c_uint64)), sample_from.shape[0], step, phase,
+                                       skips.ctypes.data_as(C.POINTER(C.c_uint32))), "fvad_clips_phase_skips")
+    return skips
+
+
+def clips_plan_strided(lens, skips, step, out_pcm16=False):
+    """fvad_clips_plan_strided: (out_lens [n] uint64, offsets [n] uint64, total), in samples of the output format; skips None: 0"""
+    lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
+    n = lens.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+    out_lens, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
+    check(lib().fvad_clips_plan_strided(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, step,
+                                        CLIP_PCM16 if out_pcm16 else CLIP_F32, out_lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_strided")
+    return out_lens, offsets, int(total.value)
 
 
 def clips_from_segments(segs, first_lane, n_channels, n_available, cap=None):

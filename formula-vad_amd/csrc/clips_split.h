@@ -17,9 +17,14 @@ inline SplitRow split_row(const uint64_t* clips, size_t i)
     return {r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
 }
 
-// fvad_clips_split_check with the reason of a refusal in *why (a literal)
+struct Strided; // clips_strided.h
+
+// fvad_clips_split_check with the reason of a refusal in *why (a literal).  strided (may be NULL): the rules of
+// fvad_clips_export_split*_strided as well, directly after the rows' own; offsets, total and the capacity rule are then the
+// strided slots'
 int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
                       size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
-                      const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why);
+                      const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why,
+                      const Strided* strided);
 
 } // namespace fvad

@@ -1,12 +1,16 @@
 // engine_clips.cpp -- the batch Recorder: fvad_clips_plan / _from_segments (host only) and fvad_clips_export(_device), which
 // run kernels_clips.hip over device-resident lanes.  The reference finalises one AudioBuffer per completed segment, the quietest
 // channel over [sample_from, sample_to) (Recorder.zig:74-164); here every clip of a call is picked and packed in three launches
-// and only the packed clips leave the device.
+// and only the packed clips leave the device.  The strided forms (fvad_clips_export_strided*) are the same calls with the strided
+// rules and slots (clips_strided.h) and kernels_clips_strided.hip's gather over tiles of its own.
 #include <vector>
 
+#include "clips_strided.h"
 #include "internal.h"
 
 using namespace fvad;
+
+static_assert(kStridedSrcTile == (uint64_t)kClipTile && FVAD_CLIP_STEP_MAX == kClipStepMax, "clips_strided.h counts the kernels' tiles");
 
 namespace {
 
@@ -38,10 +42,11 @@ int plan_clips(const uint64_t* clips, size_t n, int out_format, uint64_t* offset
 }
 
 // Every rule of fvad_clips_export(_device), in one order for both forms: arguments, then every clip's own rules, then its range
-// and lanes, then the capacity.  Fills offsets and total.
+// and lanes, then the capacity.  Fills offsets and total.  strided (may be NULL): the strided exports' rules directly after the
+// clips' own, and their slots in place of the full-rate ones.
 int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                  const uint64_t* clips, size_t n_clips, int out_format, const void* out, size_t out_capacity, bool device_out,
-                 std::vector<uint64_t>& offsets, uint64_t& total)
+                 std::vector<uint64_t>& offsets, uint64_t& total, const Strided* strided)
 {
     if (!d_src || !clips || !out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: NULL argument");
     if (!format_ok(src_format) || !format_ok(out_format)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: unknown sample format");
@@ -51,6 +56,18 @@ int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t 
     offsets.resize(n_clips);
     if (plan_clips(clips, n_clips, out_format, offsets.data(), &total) != FVAD_OK)
         return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: a clip with sample_to <= sample_from or no channels");
+    if (strided) {
+        if (!strided_step_ok(strided->step)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_strided: a step of 0 or above FVAD_CLIP_STEP_MAX");
+        const char* why = "";
+        total = 0;
+        for (size_t i = 0; i < n_clips; ++i) {
+            const ClipRow c = row(clips, i);
+            uint64_t out_len;
+            offsets[i] = total;
+            if (!strided_slot(*strided, i, c.sample_to - c.sample_from, 16 / format_bytes(out_format), &total, &out_len, &why))
+                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_strided: ") + why);
+        }
+    }
     for (size_t i = 0; i < n_clips; ++i) {
         const ClipRow c = row(clips, i);
         if (c.sample_to > n_samples) return set_err(ctx, FVAD_ERR_OUT_OF_RANGE, "fvad_clips_export: a clip ends past n_samples");
@@ -60,6 +77,13 @@ int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t 
     if (total > out_capacity) return set_err(ctx, FVAD_ERR_BUFFER_TOO_SMALL, "fvad_clips_export: out_capacity is below fvad_clips_plan's total");
     return FVAD_OK;
 }
+
+int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                  const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
+                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided);
+int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided);
 
 } // namespace
 
@@ -99,13 +123,57 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
                              size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
                              uint64_t* out_offsets)
 {
+    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
+                         best_channel, best_rms, runner_up_rms, out_offsets, nullptr);
+}
+
+int fvad_clips_export(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                      const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity,
+                      int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
+{
+    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
+                       best_rms, runner_up_rms, out_offsets, nullptr);
+}
+
+int fvad_clips_export_strided_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                     size_t n_samples, const uint64_t* clips, size_t n_clips, int out_format, void* d_out,
+                                     size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                     uint64_t* out_offsets, uint32_t step, const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
+                         best_channel, best_rms, runner_up_rms, out_offsets, &s);
+}
+
+int fvad_clips_export_strided(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                              const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity,
+                              int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step,
+                              const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
+                       best_rms, runner_up_rms, out_offsets, &s);
+}
+
+} // extern "C"
+
+namespace {
+
+// fvad_clips_export_device (strided NULL) and fvad_clips_export_strided_device
+int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                  const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
+                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided)
+{
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
     const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                                 true, offsets, total);
+                                 true, offsets, total, strided);
     if (bad != FVAD_OK) return bad;
+    // a step of 1 keeps every sample: the full-rate gather, whose tiles are the strided gather's
+    const uint32_t step = strided ? strided->step : 1;
+    const uint64_t tile_out = clip_tile_out(step);
     // the tables: one job per clip and the two prefix tables the workgroups search
     std::vector<ClipJob> jobs(n_clips);
     std::vector<uint32_t> unit_prefix(n_clips + 1), tile_prefix(n_clips + 1);
@@ -114,6 +182,8 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
         const ClipRow c = row(clips, i);
         const uint64_t len = c.sample_to - c.sample_from;
         const uint64_t nt = (len + kClipTile - 1) / kClipTile;
+        const uint32_t skip = strided && strided->skips ? strided->skips[i] : 0;
+        const uint64_t out_len = (len - skip + step - 1) / step;
         unit_prefix[i] = (uint32_t)units;
         tile_prefix[i] = (uint32_t)tiles;
         ClipJob& j = jobs[i];
@@ -123,10 +193,10 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
         j.first_unit = (uint32_t)units;
         j.n_tiles = (uint32_t)nt;
         j.n_channels = (uint32_t)c.n_channels;
-        j.pad = 0;
+        j.skip = skip;
         units += nt * c.n_channels;
-        tiles += nt;
-        if (units > 0x7fffffffull) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: more than 2^31 tiles in one call: export in batches");
+        tiles += (out_len + tile_out - 1) / tile_out; // (step 1: nt)
+        if (units > 0x7fffffffull || tiles > 0x7fffffffull) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: more than 2^31 tiles in one call: export in batches");
     }
     unit_prefix[n_clips] = (uint32_t)units;
     tile_prefix[n_clips] = (uint32_t)tiles;
@@ -164,8 +234,13 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
         time_begin(ctx, "clip_pick");
         FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_pick(a, ctx->stream));
         time_end(ctx);
-        time_begin(ctx, "clip_gather");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather(a, ctx->stream));
+        if (step == 1) {
+            time_begin(ctx, "clip_gather");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather(a, ctx->stream));
+        } else {
+            time_begin(ctx, "clip_gather_strided");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_strided(ClipStridedArgs{a, step, (uint32_t)tile_out}, ctx->stream));
+        }
         time_end(ctx);
         FVAD_HIP(ctx, hipMemcpyAsync(infos.data(), d + o_info, n_clips * sizeof(ClipInfo), hipMemcpyDeviceToHost, ctx->stream));
         FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -184,16 +259,17 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
     return FVAD_OK;
 }
 
-int fvad_clips_export(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                      const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity,
-                      int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
+// fvad_clips_export (strided NULL) and fvad_clips_export_strided
+int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
     const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity,
-                                 false, offsets, total);
+                                 false, offsets, total, strided);
     if (bad != FVAD_OK) return bad;
     // a device staging buffer of the plan's size, one copy back, then freed (hipMalloc returns 256-byte aligned memory)
     hipSetDevice(ctx->device);
@@ -202,8 +278,8 @@ int fvad_clips_export(fvad_ctx* ctx, const void* d_src, int src_format, size_t n
     if (hipMalloc(&d_out, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export: hipMalloc of the staging buffer failed"); }
     // the padding between slots is never written by the kernels: zero it, so that the host gets no stale device memory
     hipError_t e = hipMemsetAsync(d_out, 0, bytes, ctx->stream);
-    int rc = e == hipSuccess ? fvad_clips_export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format,
-                                                        d_out, (size_t)total, best_channel, best_rms, runner_up_rms, out_offsets)
+    int rc = e == hipSuccess ? export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out,
+                                             (size_t)total, best_channel, best_rms, runner_up_rms, out_offsets, strided)
                              : hip_fail(ctx, e, "fvad_clips_export: hipMemsetAsync");
     if (rc == FVAD_OK) {
         e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -214,4 +290,4 @@ int fvad_clips_export(fvad_ctx* ctx, const void* d_src, int src_format, size_t n
     return rc;
 }
 
-} // extern "C"
+} // namespace

@@ -1,9 +1,11 @@
 // engine_clips_split.cpp -- fvad_clips_export_split(_device): the batch Recorder over a split source (kernels_clips_split.hip).
 // The argument rules are fvad_clips_split_check's (host_clips_split.cpp); here are the tables a launch searches -- engine_clips.cpp's,
-// plus one ClipSplit per clip -- and the three launches.
+// plus one ClipSplit per clip -- and the three launches.  The strided forms (fvad_clips_export_split*_strided) are the same calls
+// with the strided rules and slots (clips_strided.h) and kernels_clips_strided.hip's gather over tiles of its own.
 #include <vector>
 
 #include "clips_split.h"
+#include "clips_strided.h"
 #include "internal.h"
 
 using namespace fvad;
@@ -14,31 +16,32 @@ namespace {
 
 int check_call(const fvad_ctx* ctx, const char* who, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
                size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
-               const void* out, size_t out_capacity, bool device_out, std::vector<uint64_t>& offsets, uint64_t& total)
+               const void* out, size_t out_capacity, bool device_out, std::vector<uint64_t>& offsets, uint64_t& total,
+               const Strided* strided)
 {
     offsets.resize(n_clips);
     const char* why = "";
     const int rc = clips_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
-                                     out_format, out, out_capacity, device_out, offsets.data(), &total, &why);
+                                     out_format, out, out_capacity, device_out, offsets.data(), &total, &why, strided);
     return rc == FVAD_OK ? rc : set_err(ctx, rc, std::string(who) + ": " + why);
 }
 
-} // namespace
-
-extern "C" {
-
-int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
-                                   size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
-                                   size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
-                                   float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
+// fvad_clips_export_split_device (strided NULL) and fvad_clips_export_split_strided_device
+int export_split_device(fvad_ctx* ctx, const char* who, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                        size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                        int out_format, void* d_out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                        uint64_t* out_offsets, const Strided* strided)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
-    const int bad = check_call(ctx, "fvad_clips_export_split", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples,
-                               src_format, clips, n_clips, out_format, d_out, out_capacity, true, offsets, total);
+    const int bad = check_call(ctx, who, d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
+                               out_format, d_out, out_capacity, true, offsets, total, strided);
     if (bad != FVAD_OK) return bad;
+    // a step of 1 keeps every sample: the full-rate gather, whose tiles are the strided gather's
+    const uint32_t step = strided ? strided->step : 1;
+    const uint64_t tile_out = clip_tile_out(step);
     // the tables: engine_clips.cpp's job per clip and prefix tables (the check has bounded the units), and the clips' pieces
     std::vector<ClipJob> jobs(n_clips);
     std::vector<ClipSplit> splits(n_clips);
@@ -48,6 +51,8 @@ int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lane
         const SplitRow c = split_row(clips, i);
         const uint64_t len = c.a_len + c.b_len;
         const uint64_t nt = (len + kClipTile - 1) / kClipTile;
+        const uint32_t skip = strided && strided->skips ? strided->skips[i] : 0;
+        const uint64_t out_len = (len - skip + step - 1) / step;
         unit_prefix[i] = (uint32_t)units;
         tile_prefix[i] = (uint32_t)tiles;
         ClipJob& j = jobs[i];
@@ -57,14 +62,14 @@ int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lane
         j.first_unit = (uint32_t)units;
         j.n_tiles = (uint32_t)nt;
         j.n_channels = (uint32_t)c.n_channels;
-        j.pad = 0;
+        j.skip = skip;
         ClipSplit& s = splits[i];
         s.a_off = c.a_len ? c.a_lane * (uint64_t)a_stride + c.a_from : 0; // (a piece of no samples is never addressed)
         s.a_len = c.a_len;
         s.b_off = c.b_len ? c.b_lane * (uint64_t)b_stride + c.b_from : 0;
         s.pad = 0;
         units += nt * c.n_channels;
-        tiles += nt;
+        tiles += (out_len + tile_out - 1) / tile_out; // (step 1: nt)
     }
     unit_prefix[n_clips] = (uint32_t)units;
     tile_prefix[n_clips] = (uint32_t)tiles;
@@ -76,7 +81,7 @@ int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lane
                  o_tp = o_up + up16((n_clips + 1) * 4), o_part = o_tp + up16((n_clips + 1) * 4),
                  o_info = o_part + up16(units * sizeof(double)), bytes = o_info + up16(n_clips * sizeof(ClipInfo));
     char* d = nullptr;
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export_split: hipMalloc of the clip tables failed"); }
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, std::string(who) + ": hipMalloc of the clip tables failed"); }
     std::vector<ClipInfo> infos(n_clips);
     auto run = [&]() -> int {
         FVAD_HIP(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), n_clips * sizeof(ClipJob), hipMemcpyHostToDevice, ctx->stream));
@@ -106,8 +111,13 @@ int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lane
         time_begin(ctx, "clip_pick");
         FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_pick(a.c, ctx->stream));
         time_end(ctx);
-        time_begin(ctx, "clip_gather_split");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_split(a, ctx->stream));
+        if (step == 1) {
+            time_begin(ctx, "clip_gather_split");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_split(a, ctx->stream));
+        } else {
+            time_begin(ctx, "clip_gather_strided_split");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_strided_split(ClipSplitStridedArgs{a, step, (uint32_t)tile_out}, ctx->stream));
+        }
         time_end(ctx);
         FVAD_HIP(ctx, hipMemcpyAsync(infos.data(), d + o_info, n_clips * sizeof(ClipInfo), hipMemcpyDeviceToHost, ctx->stream));
         FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -126,28 +136,29 @@ int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lane
     return FVAD_OK;
 }
 
-int fvad_clips_export_split(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
-                            size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
-                            int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms,
-                            float* runner_up_rms, uint64_t* out_offsets)
+// fvad_clips_export_split (strided NULL) and fvad_clips_export_split_strided
+int export_split_host(fvad_ctx* ctx, const char* who, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                      size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                      int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                      uint64_t* out_offsets, const Strided* strided)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
-    const int bad = check_call(ctx, "fvad_clips_export_split", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples,
-                               src_format, clips, n_clips, out_format, out, out_capacity, false, offsets, total);
+    const int bad = check_call(ctx, who, d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
+                               out_format, out, out_capacity, false, offsets, total, strided);
     if (bad != FVAD_OK) return bad;
     // a device staging buffer of the plan's size, one copy back, then freed, as fvad_clips_export does
     hipSetDevice(ctx->device);
     const size_t bytes = (size_t)total * (out_format == FVAD_CLIP_PCM16 ? 2 : 4);
     void* d_out = nullptr;
-    if (hipMalloc(&d_out, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export_split: hipMalloc of the staging buffer failed"); }
+    if (hipMalloc(&d_out, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, std::string(who) + ": hipMalloc of the staging buffer failed"); }
     // the padding between slots is never written by the kernels: zero it, so that the host gets no stale device memory
     hipError_t e = hipMemsetAsync(d_out, 0, bytes, ctx->stream);
-    int rc = e == hipSuccess ? fvad_clips_export_split_device(ctx, d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples,
-                                                              src_format, clips, n_clips, out_format, d_out, (size_t)total, best_channel,
-                                                              best_rms, runner_up_rms, out_offsets)
+    int rc = e == hipSuccess ? export_split_device(ctx, who, d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format,
+                                                   clips, n_clips, out_format, d_out, (size_t)total, best_channel, best_rms, runner_up_rms,
+                                                   out_offsets, strided)
                              : hip_fail(ctx, e, "fvad_clips_export_split: hipMemsetAsync");
     if (rc == FVAD_OK) {
         e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -156,6 +167,49 @@ int fvad_clips_export_split(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size
     }
     hipFree(d_out);
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                   size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                   size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
+                                   float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
+{
+    return export_split_device(ctx, "fvad_clips_export_split", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format,
+                               clips, n_clips, out_format, d_out, out_capacity, best_channel, best_rms, runner_up_rms, out_offsets, nullptr);
+}
+
+int fvad_clips_export_split(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                            size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                            int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms,
+                            float* runner_up_rms, uint64_t* out_offsets)
+{
+    return export_split_host(ctx, "fvad_clips_export_split", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format,
+                             clips, n_clips, out_format, out, out_capacity, best_channel, best_rms, runner_up_rms, out_offsets, nullptr);
+}
+
+int fvad_clips_export_split_strided_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                           const void* d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                           const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity,
+                                           int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets,
+                                           uint32_t step, const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_split_device(ctx, "fvad_clips_export_split_strided", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples,
+                               src_format, clips, n_clips, out_format, d_out, out_capacity, best_channel, best_rms, runner_up_rms, out_offsets, &s);
+}
+
+int fvad_clips_export_split_strided(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                    size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                    size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                                    float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_split_host(ctx, "fvad_clips_export_split_strided", d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples,
+                             src_format, clips, n_clips, out_format, out, out_capacity, best_channel, best_rms, runner_up_rms, out_offsets, &s);
 }
 
 } // extern "C"

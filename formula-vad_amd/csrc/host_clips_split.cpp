@@ -2,6 +2,7 @@
 // forms report them in, without a device (plain C++: tests/sanitize/clips_split_san.cpp builds this file alone).  Pointers are
 // addresses here; nothing is read through d_a, d_b or out.
 #include "clips_split.h"
+#include "clips_strided.h"
 
 namespace {
 
@@ -35,7 +36,8 @@ namespace fvad {
 
 int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
                       size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
-                      const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why)
+                      const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why,
+                      const Strided* strided)
 {
     const char* dummy;
     if (!why) why = &dummy;
@@ -66,6 +68,17 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
         if (at > UINT64_MAX - per16 || len > UINT64_MAX - per16 - at) { *why = "the clips' total does not fit 64 bits"; return FVAD_ERR_INVALID_ARGUMENT; }
         at += (len + per16 - 1) / per16 * per16;
     }
+    if (strided) { // a strided export: its own rules, and its slots in place of the full-rate ones
+        if (!strided_step_ok(strided->step)) { *why = "a step of 0 or above FVAD_CLIP_STEP_MAX"; return FVAD_ERR_INVALID_ARGUMENT; }
+        at = 0;
+        for (size_t i = 0; i < n_clips; ++i) {
+            const SplitRow r = split_row(clips, i);
+            const uint64_t slot = at;
+            uint64_t out_len;
+            if (!strided_slot(*strided, i, r.a_len + r.b_len, per16, &at, &out_len, why)) return FVAD_ERR_INVALID_ARGUMENT;
+            if (offsets) offsets[i] = slot;
+        }
+    }
     if (total) *total = at;
     // ranges and lanes
     for (size_t i = 0; i < n_clips; ++i) {
@@ -83,8 +96,8 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
         *why = "the output overlaps a source";
         return FVAD_ERR_INVALID_ARGUMENT;
     }
-    // the grid: one workgroup per (clip, channel, tile)
-    uint64_t units = 0;
+    // the grid: one workgroup per (clip, channel, tile); a strided gather has tiles of its own, of at most as many samples
+    uint64_t units = 0, gather = 0;
     for (size_t i = 0; i < n_clips; ++i) {
         const SplitRow r = split_row(clips, i);
         const uint64_t len = r.a_len + r.b_len, nt = len / kSplitTile + (len % kSplitTile != 0);
@@ -92,6 +105,13 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
         if (__builtin_mul_overflow(nt, r.n_channels, &u) || __builtin_add_overflow(units, u, &units) || units > 0x7fffffffull) {
             *why = "more than 2^31 tiles in one call: export in batches";
             return FVAD_ERR_INVALID_ARGUMENT;
+        }
+        if (strided) {
+            const uint64_t to = strided_tile_out(strided->step), n = (len - (strided->skips ? strided->skips[i] : 0) + strided->step - 1) / strided->step;
+            if (__builtin_add_overflow(gather, n / to + (n % to != 0), &gather) || gather > 0x7fffffffull) {
+                *why = "more than 2^31 tiles in one call: export in batches";
+                return FVAD_ERR_INVALID_ARGUMENT;
+            }
         }
     }
     return FVAD_OK;
@@ -105,5 +125,5 @@ extern "C" int fvad_clips_split_check(const void* d_a, size_t a_lanes, size_t a_
                                       uint64_t* offsets, uint64_t* total)
 {
     return fvad::clips_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
-                                   out_format, out, out_capacity, device_out, offsets, total, nullptr);
+                                   out_format, out, out_capacity, device_out, offsets, total, nullptr, nullptr);
 }

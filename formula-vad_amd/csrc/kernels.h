@@ -419,7 +419,8 @@ struct ClipJob {
     uint64_t len;        // samples
     uint64_t out_off;    // elements from `out` to the clip's slot (a multiple of 16 bytes)
     uint32_t first_unit; // == unit_prefix[c]
-    uint32_t n_tiles, n_channels, pad;
+    uint32_t n_tiles, n_channels;
+    uint32_t skip;       // the strided gathers' first kept sample (< step); 0 and unused everywhere else
 };
 struct ClipInfo {        // what fvad_clips_export* reports per clip
     int32_t best_channel;
@@ -457,6 +458,26 @@ struct ClipSplitArgs {
 };
 int fvad_launch_clip_rms_split(const ClipSplitArgs& a, hipStream_t stream);    // hipError_t as int
 int fvad_launch_clip_gather_split(const ClipSplitArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.c) after the rms)
+
+// The strided gathers (kernels_clips_strided.hip, fvad_clips_export*_strided): of the picked channel the samples skip,
+// skip + step, ... of the clip (skip = jobs[i].skip < step), out_len = ceil((len - skip) / step) of them into the clip's slot.
+// RMS and pick are the kernels above over every sample; only the gather differs.  Its tiles are counted in OUTPUT samples from
+// the clip's first kept sample: tile k holds outputs [k * tile_out, ...), i.e. source samples from skip + k * tile_out * step,
+// and c.tile_prefix / c.n_tiles count these tiles (the RMS units keep kClipTile and jobs[i].n_tiles).
+constexpr uint32_t kClipStepMax = 16; // FVAD_CLIP_STEP_MAX
+// floor(kClipTile / step) rounded down to a multiple of 8: a tile's first output is on a 16-byte boundary of its slot in
+// either output format, and its (tile_out - 1) * step + 1 source samples fit stage_tile's LDS image
+constexpr uint32_t clip_tile_out(uint32_t step) { return (uint32_t)kClipTile / step / 8 * 8; }
+struct ClipStridedArgs {
+    ClipArgs c;
+    uint32_t step, tile_out;
+};
+struct ClipSplitStridedArgs {
+    ClipSplitArgs s;
+    uint32_t step, tile_out;
+};
+int fvad_launch_clip_gather_strided(const ClipStridedArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_strided_split(const ClipSplitStridedArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
 
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in

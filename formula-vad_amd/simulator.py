@@ -5,7 +5,8 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
 
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
     python -m ... simulator.py -i plan.json --export-clips DIR [--clips-pcm16]   (or: run_clips(path, DIR): the plan's speech
-                                                      clips, original and denoised, cut and picked on the GPU)
+                                                      clips, original and denoised, cut and picked on the GPU;
+                                                      --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
     python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
                                                       parameter grid, every machine scored on the GPU, the top K configs by
@@ -422,7 +423,37 @@ def run_plan(plan_path, ctx=None, synth_seed=None, out=sys.stdout, devices=None)
     return text, results
 
 
-def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
+CLIP_RATES = {48000: 1, 16000: 3}                  # a clip kind's rate -> the export's step
+CLIP_PHASE = {"denoised": 2, "original": 0}        # the lane indices (mod 3) kept at 16 kHz: the interpolator's native samples
+                                                   # (resample.zig:32-79); what downsampleAudio feeds NSNet2 (resample.zig:9-29)
+
+
+def _clip_rates(original_rate, denoised_rate):
+    for what, rate in (("original_rate", original_rate), ("denoised_rate", denoised_rate)):
+        if rate not in CLIP_RATES:
+            raise ValueError(f"run_clips: {what} {rate!r} is neither 48000 nor 16000")
+    return {"original": original_rate, "denoised": denoised_rate}
+
+
+def _clip_skips(kind, rate, sample_from):
+    """(step, skips or None) of one export of `kind` clips starting at the absolute lane indices sample_from"""
+    step = CLIP_RATES[rate]
+    return (1, None) if step == 1 else (step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind]))
+
+
+def _write_clip(path, samples, pcm16, rate):
+    (fv.wav_write_i16 if pcm16 else fv.wav_write)(path, samples, rate)
+
+
+def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample, length):
+    """a kind's manifest entry; a kind at 48 kHz has the keys it always had"""
+    e = {"file": os.path.basename(path), "best_channel": int(best_channel), "best_rms": float(best_rms), "runner_up_rms": float(runner_up_rms)}
+    if rate != 48000:
+        e.update(sample_rate=rate, first_sample=int(first_sample), length=int(length))
+    return e
+
+
+def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates):
     """run_clips for the instances of one context -> [(segments, audit, manifest)] in the order given"""
     if not audio:
         return []
@@ -468,23 +499,23 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16):
             rows = np.concatenate(rows) if rows else np.zeros((0, fv.CLIP_FIELDS), np.uint64)
             if not rows.shape[0]:
                 continue
-            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16)
+            step, skips = _clip_skips(kind, rates[kind], rows[:, 2])
+            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16, step=step, skips=skips)
+            lens = res["out_lens"] if step != 1 else rows[:, 3] - rows[:, 2]
             for j, (i, k) in enumerate(owner):
-                o, n = int(res["offsets"][j]), int(rows[j, 3] - rows[j, 2])
+                o, n = int(res["offsets"][j]), int(lens[j])
                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], k, kind))
-                if pcm16:
-                    fv.wav_write_i16(path, res["out"][o:o + n])
-                else:
-                    fv.wav_write(path, res["out"][o:o + n])
-                manifests[i]["clips"][k][kind] = {"file": os.path.basename(path), "best_channel": int(res["best_channel"][j]),
-                                                  "best_rms": float(res["best_rms"][j]), "runner_up_rms": float(res["runner_up_rms"][j])}
+                _write_clip(path, res["out"][o:o + n], pcm16, rates[kind])
+                manifests[i]["clips"][k][kind] = _clip_entry(path, res["best_channel"][j], res["best_rms"][j], res["runner_up_rms"][j], rates[kind],
+                                                             int(rows[j, 2]) + (0 if skips is None else int(skips[j])), n)
         return [(segs, audit, m) for (segs, audit), m in zip(per_inst, manifests)]
     finally:
         for d in held:
             ctx.device_free(d)
 
 
-def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None):
+def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None,
+              denoised_rate=48000, original_rate=48000):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -500,8 +531,16 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     ingest "device": the files' bytes go to the GPU as they are and are decoded there (run_grid); the same clips and manifests.
     slice_chunks N: the same files, manifests, report and return value from time slices of N chunks (_clips_sliced_share), the
     device memory bounded by a slice and the held tails instead of the corpus; None is the resident path above.
-    info (a dict): filled with "held_peak_bytes", the most device memory the held tails took on one context, and "slices"."""
+    info (a dict): filled with "held_peak_bytes", the most device memory the held tails took on one context, and "slices".
+    denoised_rate / original_rate (48000 or 16000; anything else raises before any work): at 16000 a kind's clips are every third
+    sample of what 48000 gives -- fvad_clips_export*_strided, so that only they cross PCIe -- picked as at 48000, over every
+    sample.  The denoised kind keeps the lane indices = 2 (mod 3): K3's interpolator writes [lerp, lerp, sample] per 16 kHz
+    sample, so these are NSNet2's own output and nothing is lost.  The original kind keeps the indices = 0 (mod 3), the
+    reference's downsampleAudio: what NSNet2 was fed, WITHOUT an anti-alias filter -- it aliases exactly as the network's input
+    does.  The files then say 16000 and the kind's manifest entries gain "sample_rate", "first_sample" (the absolute 48 kHz index
+    of the first kept sample) and "length"; at 48000 files and manifests are byte for byte what they were."""
     _check_ingest(ingest)
+    rates = _clip_rates(original_rate, denoised_rate)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
         check_slice_chunks(slice_chunks, plan["fft_size"])
@@ -519,9 +558,9 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
             try:
                 insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
                 if slice_chunks is None:
-                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16)
+                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates)
                 else:
-                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d])
+                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates)
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -602,7 +641,7 @@ class _HeldTails:
                 b[0], b[1] = None, 0
 
 
-def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note):
+def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note, rates):
     """run_clips(slice_chunks=N) for the instances of one context -> [(segments, audit, manifest)] in the order given.
     Channel-count group after group, each in time slices [s0, s1) of N chunks read, denoised and band-summed as a sliced grid's
     (_slice_denoise_and_bands; audio mapped or raw), one single-config host batch per instance run on part by part (_HostParts).
@@ -611,7 +650,9 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
     [s0, s1) of them is valid, the halo is not), the others stay pending or, once their stream has ended, are counted skipped;
     then the tail every pending or still possible clip needs (fvad_vad_batch_hold_from, the pending clips' starts) is carried
     into the other held buffer (_HeldTails).  The slices run one chunk past a group's last whole chunk where a file ends inside a
-    chunk, so that the original audio's last samples are reached.  note: "held_peak_bytes", "slices"."""
+    chunk, so that the original audio's last samples are reached.  note: "held_peak_bytes", "slices".
+    rates: a kind at 16000 exports with step 3, the skips from the clips' absolute sample_from (a clip's seam has no part in
+    them); the carry of the held tails stays a step-1 export."""
     if not audio:
         return []
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
@@ -683,17 +724,19 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
                                 assert n_a == 0 or t.base <= a0 < t.end == s0 * chunk, "a due clip starts in front of the held tail"
                                 rows.append((nch, k * nch if n_a else 0, a0 - t.base if n_a else 0, n_a,
                                              k * nch if n_b else 0, cut - start * chunk if n_b else 0, n_b))
-                                owner.append((i, j))
+                                owner.append((i, j, a0))
                             pending[kind][k] = still
                             need += [a0 for _, a0, _ in still] + ([] if holds[k] is None else [holds[k]])
                         if rows:
-                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16)
-                            for r, (i, j), o, bc, br, rr in zip(rows, owner, res["offsets"], res["best_channel"], res["best_rms"], res["runner_up_rms"]):
-                                o, n_clip = int(o), r[3] + r[6]
+                            step, skips = _clip_skips(kind, rates[kind], [a0 for _, _, a0 in owner])
+                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16, step=step, skips=skips)
+                            lens = res["out_lens"] if step != 1 else [r[3] + r[6] for r in rows]
+                            for q, ((i, j, a0), o) in enumerate(zip(owner, res["offsets"])):
+                                o, n_clip = int(o), int(lens[q])
                                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], j, kind))
-                                (fv.wav_write_i16 if pcm16 else fv.wav_write)(path, res["out"][o:o + n_clip])
-                                entries[i][(j, kind)] = {"file": os.path.basename(path), "best_channel": int(bc), "best_rms": float(br),
-                                                         "runner_up_rms": float(rr)}
+                                _write_clip(path, res["out"][o:o + n_clip], pcm16, rates[kind])
+                                entries[i][(j, kind)] = _clip_entry(path, res["best_channel"][q], res["best_rms"][q], res["runner_up_rms"][q],
+                                                                    rates[kind], a0 + (0 if skips is None else int(skips[q])), n_clip)
                         t.carry(b, start * chunk, s0 * chunk, s1 * chunk, min(need) if need else None)
                     note["held_peak_bytes"] = max(note["held_peak_bytes"], sum(t.bytes() for t in tails.values()))
                 for k, i in enumerate(members):
@@ -1995,6 +2038,12 @@ def arg_parser():
                     help="run the plan and write every completed segment's original and denoised clip (the quietest channel, cut and "
                          "picked on the GPU) and a NAME-clips.json manifest per instance into DIR")
     ap.add_argument("--clips-pcm16", action="store_true", help="with --export-clips: the clips as PCM16 (half the bytes over PCIe)")
+    ap.add_argument("--clips-denoised-rate", type=int, default=48000, metavar="HZ",
+                    help="with --export-clips: 48000 or 16000 -- at 16000 the denoised clips are NSNet2's own 16 kHz output (every third "
+                         "sample, the ones K3's interpolator did not make up): a third of the bytes, nothing lost")
+    ap.add_argument("--clips-original-rate", type=int, default=48000, metavar="HZ",
+                    help="with --export-clips: 48000 or 16000 -- at 16000 the original clips are decimated as NSNet2's input is "
+                         "(every third sample, no anti-alias filter: it aliases)")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -2016,7 +2065,7 @@ def main(argv=None):
     if a.export_clips:
         info = {}
         text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest,
-                            slice_chunks=a.slice_chunks, info=info)
+                            slice_chunks=a.slice_chunks, info=info, denoised_rate=a.clips_denoised_rate, original_rate=a.clips_original_rate)
         sys.stdout.write(text)
         if info:
             sys.stdout.write(f"\n[{info['slices']} slices; held tails: {info['held_peak_bytes'] / 2 ** 20:.1f} MiB of device memory at most]\n")

@@ -871,6 +871,58 @@ int fvad_clips_export_split(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size
  * _run_sized); after a device run the machines' state is not on the host: FVAD_ERR_INVALID_ARGUMENT. */
 int fvad_vad_batch_hold_from(const fvad_vad_batch *b, size_t config, uint64_t *hold_from);
 
+/* ------------------------------------------------------------------ batch Recorder with a stride: clips at the denoiser's rate
+ * NSNet2 works at 16 kHz; its output comes back to 48 kHz as [lerp, lerp, sample] per 16 kHz sample (resample.zig:32-79), so in
+ * a denoised lane the samples at index = 2 (mod 3) are the network's own output, bit for bit, and the others a fused lerp of
+ * their neighbours.  A recogniser takes 16 kHz: these calls export every step-th sample of a clip and nothing else crosses PCIe
+ * (csrc/kernels_clips_strided.hip).
+ * - Per clip a skip < step: the output is samples skip, skip + step, skip + 2 step, ... of the clip's picked channel,
+ *   out_len = ceil((len - skip) / step) of them, converted by fvad_clips_export's rules (equal formats move the bits).
+ * - The channel is picked exactly as fvad_clips_export picks it, over EVERY sample of the clip.
+ * - INVARIANT: for the same clip best_channel, best_rms and runner_up_rms are the bits the full-rate export gives, and the
+ *   samples are that export's samples[skip::step] -- for the split form wherever the seam is (the stride runs through it).
+ * - Slots: 16-byte aligned, in clip order, sized by out_len (fvad_clips_plan_strided).  step == 1 (every skip 0) gives the
+ *   full-rate exports' bits and offsets.
+ * - Step 3 with the skips of phase 2 is lossless with respect to the denoiser.  With phase 0 on the original audio it is the
+ *   reference's downsampleAudio (resample.zig:9-29: lane index = 0 mod 3, NO anti-alias filter) -- sample for sample what
+ *   NSNet2 was fed, aliasing included.  A filtered decimator is a different feature.
+ *
+ * fvad_clips_phase_skips (host only): skips[i] = (phase + step - sample_from[i] mod step) mod step, so that the kept samples
+ * are the lane indices = phase (mod step).  FVAD_ERR_INVALID_ARGUMENT for step == 0, step > FVAD_CLIP_STEP_MAX, phase >= step
+ * or NULLs with n_clips > 0.
+ * fvad_clips_plan_strided (host only): out_lens[i], offsets[i] and *total for clips of lens[i] samples, in samples of
+ * out_format; skips NULL means all zero.  FVAD_ERR_INVALID_ARGUMENT for step == 0, step > FVAD_CLIP_STEP_MAX, a skip >= step,
+ * a clip with len <= skip (no sample kept), a bad format, NULLs, or a total that does not fit 64 bits.
+ * fvad_clips_export_strided_device / fvad_clips_export_strided / fvad_clips_export_split_strided_device /
+ * fvad_clips_export_split_strided: the full-rate call's arguments, then step and skips (host memory, n_clips entries, or NULL:
+ * all zero).  Every error comes back before any launch, in the full-rate call's order with the rules above (step, then per clip
+ * its skip) directly after the rows' own rules; out_capacity is checked against the strided total and out_offsets are the
+ * strided slots.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_gather_strided (split: clip_rms_split, clip_pick,
+ * clip_gather_strided_split); with step == 1 the gather is the full-rate one under its own name.
+ * Deviation from a plain "argument list plus two": none in the lists; fvad_clips_phase_skips also refuses phase >= step. */
+#define FVAD_CLIP_STEP_MAX 16
+int fvad_clips_phase_skips(const uint64_t *sample_from, size_t n_clips, uint32_t step, uint32_t phase, uint32_t *skips);
+int fvad_clips_plan_strided(const uint64_t *lens, const uint32_t *skips, size_t n_clips, uint32_t step, int out_format,
+                            uint64_t *out_lens, uint64_t *offsets, uint64_t *total);
+int fvad_clips_export_strided_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                     size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                     size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                     uint64_t *out_offsets, uint32_t step, const uint32_t *skips);
+int fvad_clips_export_strided(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                              size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *out,
+                              size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                              uint64_t *out_offsets, uint32_t step, const uint32_t *skips);
+int fvad_clips_export_split_strided_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                           const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                           const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                           size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                           uint64_t *out_offsets, uint32_t step, const uint32_t *skips);
+int fvad_clips_export_split_strided(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                    const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                    const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                                    int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
+                                    uint32_t step, const uint32_t *skips);
+
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
  * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
