@@ -427,6 +427,14 @@ pub extern "c" fn fvad_clips_export_strided_device(ctx: *Ctx, d_src: *const anyo
 pub extern "c" fn fvad_clips_export_strided(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
 pub extern "c" fn fvad_clips_export_split_strided_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
 pub extern "c" fn fvad_clips_export_split_strided(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32) c_int;
+// with a FIR filter: output q of a clip is sum_k taps[k] * x[skip + q * step + k - (n_taps - 1) / 2], the clip zero-extended
+pub const clip_fir_taps_max = 513; // FVAD_CLIP_FIR_TAPS_MAX
+pub extern "c" fn fvad_clips_fir_design(step: u32, half: u32, cutoff: f64, beta: f64, taps: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_fir_check(taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_fir_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_fir(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_split_fir_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_split_fir(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, taps: ?[*]const f32, n_taps: u32) c_int;
 
 // audio file input / output (host)
 // device-side ingest: interleaved PCM16 / PCM24 / f32 bytes de-interleaved, decoded and zero-padded into planar device lanes

@@ -28,6 +28,7 @@ CLIP_F32, CLIP_PCM16 = 0, 1      # sample formats of fvad_clips_*
 CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, sample_to (uint64 each)
 CLIP_SPLIT_FIELDS = 7            # a split clip: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (uint64 each)
 CLIP_STEP_MAX = 16               # the largest step of the strided clip exports
+CLIP_FIR_TAPS_MAX = 513          # the most taps of the filtered clip exports
 INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
 INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
@@ -346,6 +347,20 @@ SIGNATURES = {
     "fvad_clips_export_split_strided": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
                                                   C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
                                                   C.POINTER(C.c_uint32)]),
+    "fvad_clips_fir_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p]),
+    "fvad_clips_fir_check": (C.c_int, [c_float_p, C.c_uint32]),
+    "fvad_clips_export_fir_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                               c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), c_float_p,
+                                               C.c_uint32]),
+    "fvad_clips_export_fir": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                        c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), c_float_p,
+                                        C.c_uint32]),
+    "fvad_clips_export_split_fir_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                     C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                                     C.POINTER(C.c_uint32), c_float_p, C.c_uint32]),
+    "fvad_clips_export_split_fir": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                              C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                              C.POINTER(C.c_uint32), c_float_p, C.c_uint32]),
     "fvad_wav_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
@@ -686,17 +701,19 @@ class Context:
                  "fvad_engine_band_sums_device")
 
     def clips_export(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, out_pcm16=False, d_out=None, out_capacity=None,
-                     step=1, skips=None):
+                     step=1, skips=None, taps=None):
         """fvad_clips_export (d_out None: the packed clips come back as a numpy array of the output format) or
         fvad_clips_export_device (d_out: a device address with room for out_capacity samples).  clips: [n][CLIP_FIELDS] uint64.
         Returns dict(best_channel, best_rms, runner_up_rms, offsets, total[, out]).
         step != 1 or skips: fvad_clips_export_strided(_device) -- of clip i the samples skips[i], skips[i] + step, ... (skips None:
-        all 0); the dict then has "out_lens" too."""
+        all 0); the dict then has "out_lens" too.
+        taps (an odd number of float32, at most CLIP_FIR_TAPS_MAX): fvad_clips_export_fir(_device) -- the same clips, skips and slots,
+        output q of a clip being sum_k taps[k] * x[skips[i] + q * step + k - (len(taps) - 1) / 2] over the zero-extended clip."""
         clips = _clip_rows(clips)
         n = clips.shape[0]
-        if step != 1 or skips is not None:
-            return self._clips_export_strided("fvad_clips_export_strided", (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples),
-                                              clips, clips[:, 3] - clips[:, 2], out_pcm16, d_out, out_capacity, step, skips)
+        if step != 1 or skips is not None or taps is not None:
+            return self._clips_export_strided("fvad_clips_export_fir" if taps is not None else "fvad_clips_export_strided", (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples),
+                                              clips, clips[:, 3] - clips[:, 2], out_pcm16, d_out, out_capacity, step, skips, taps)
         offsets, total = clips_plan(clips, out_pcm16)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
         args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
@@ -713,8 +730,9 @@ class Context:
         res["out"] = out[:total]
         return res
 
-    def _clips_export_strided(self, name, src_args, clips, lens, out_pcm16, d_out, out_capacity, step, skips):
-        """the four strided calls: `name` (+ "_device" with d_out), src_args the arguments between ctx and the clips"""
+    def _clips_export_strided(self, name, src_args, clips, lens, out_pcm16, d_out, out_capacity, step, skips, taps=None):
+        """the four strided calls and the four filtered ones (taps): `name` (+ "_device" with d_out), src_args the arguments
+        between ctx and the clips"""
         n = clips.shape[0]
         skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
         out_lens, offsets, total = clips_plan_strided(lens, skips, step, out_pcm16) if n else (np.zeros(0, np.uint64), None, 0)
@@ -722,6 +740,9 @@ class Context:
         args = (self.h, *src_args, clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_PCM16 if out_pcm16 else CLIP_F32)
         info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
                 step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if taps is not None:
+            taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+            info += (fptr(taps), taps.shape[0])
         res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "out_lens": out_lens}
         if d_out is not None:
             self._ck(getattr(lib(), name + "_device")(*args, vp(d_out), total if out_capacity is None else out_capacity, *info), name + "_device")
@@ -731,17 +752,17 @@ class Context:
         res["out"] = out[:total]
         return res
 
-    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None, step=1, skips=None):
+    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None, step=1, skips=None, taps=None):
         """fvad_clips_export_split (d_out None) or fvad_clips_export_split_device: a and b are the two source buffers as
         (device address or None, n_lanes, lane_stride, n_samples); clips: [n][CLIP_SPLIT_FIELDS] uint64, channel c of a clip
         being a[a_lane + c][a_from, a_from + a_len) followed by b[b_lane + c][b_from, b_from + b_len).  Returns what
-        clips_export does; step / skips as there (fvad_clips_export_split_strided(_device))."""
+        clips_export does; step / skips / taps as there (fvad_clips_export_split_strided(_device), fvad_clips_export_split_fir(_device))."""
         clips = _clip_split_rows(clips)
         n = clips.shape[0]
-        if step != 1 or skips is not None:
-            return self._clips_export_strided("fvad_clips_export_split_strided", (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
+        if step != 1 or skips is not None or taps is not None:
+            return self._clips_export_strided("fvad_clips_export_split_fir" if taps is not None else "fvad_clips_export_split_strided", (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
                                               CLIP_PCM16 if src_pcm16 else CLIP_F32), clips, clips[:, 3] + clips[:, 6], out_pcm16, d_out,
-                                              out_capacity, step, skips)
+                                              out_capacity, step, skips, taps)
         offsets, total = clips_plan([(0, 1, 0, int(r[3]) + int(r[6])) for r in clips], out_pcm16) if n else (None, 0)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
         args = (self.h, vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3], CLIP_PCM16 if src_pcm16 else CLIP_F32,
@@ -1541,6 +1562,22 @@ def clips_phase_skips(sample_from, step, phase):
     check(lib().fvad_clips_phase_skips(sample_from.ctypes.data_as(C.POINTER(C.c_uint64)), sample_from.shape[0], step, phase,
                                        skips.ctypes.data_as(C.POINTER(C.c_uint32))), "fvad_clips_phase_skips")
     return skips
+
+
+def clips_fir_design(step, half=0, cutoff=0.0, beta=0.0):
+    """fvad_clips_fir_design: the 2 half + 1 float32 taps of a Kaiser-windowed sinc of unit sum (half 0: 16 step, cutoff 0:
+    0.45 / step cycles per input sample, beta 0: 6)"""
+    taps = np.zeros(CLIP_FIR_TAPS_MAX, np.float32)
+    check(lib().fvad_clips_fir_design(step, half, cutoff, beta, fptr(taps)), "fvad_clips_fir_design")
+    return taps[:2 * (half if half else 16 * step) + 1].copy()
+
+
+def clips_fir_check(taps):
+    """fvad_clips_fir_check -> status (0: the taps are an odd number of finite values, at most CLIP_FIR_TAPS_MAX)"""
+    if taps is None:
+        return lib().fvad_clips_fir_check(None, 0)
+    taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+    return lib().fvad_clips_fir_check(fptr(taps), taps.shape[0])
 
 
 def clips_plan_strided(lens, skips, step, out_pcm16=False):

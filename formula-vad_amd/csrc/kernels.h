@@ -479,6 +479,26 @@ struct ClipSplitStridedArgs {
 int fvad_launch_clip_gather_strided(const ClipStridedArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
 int fvad_launch_clip_gather_strided_split(const ClipSplitStridedArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
 
+// The filtered gathers (kernels_clips_fir.hip, fvad_clips_export*_fir): output q of a clip is the FIR sum of n_taps taps over the
+// picked channel's samples around c = skip + q * step, the clip zero-extended.  Tiles are counted in OUTPUT samples from the
+// clip's first kept sample as the strided gathers' are, with a tile that leaves room for the filter's halo on both sides.
+constexpr uint32_t kClipFirTapsMax = 513; // FVAD_CLIP_FIR_TAPS_MAX
+// ((kClipTile - n_taps) / step + 1) rounded down to a multiple of 8: the (tile_out - 1) * step + n_taps source samples of a
+// tile, halo and zero extension included, fit kClipTile
+constexpr uint32_t clip_fir_tile_out(uint32_t step, uint32_t n_taps) { return (((uint32_t)kClipTile - n_taps) / step + 1) / 8 * 8; }
+struct ClipFirArgs {
+    ClipArgs c;
+    const float* taps;   // [n_taps] (device), branch by branch: taps[j], taps[j + step], ... for j = 0 .. step - 1
+    uint32_t step, tile_out, n_taps, pad;
+};
+struct ClipSplitFirArgs {
+    ClipSplitArgs s;
+    const float* taps;
+    uint32_t step, tile_out, n_taps, pad;
+};
+int fvad_launch_clip_gather_fir(const ClipFirArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_fir_split(const ClipSplitFirArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
+
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
 // multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane

@@ -6,7 +6,8 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
     python -m ... simulator.py -i plan.json           (or: run_plan(path))
     python -m ... simulator.py -i plan.json --export-clips DIR [--clips-pcm16]   (or: run_clips(path, DIR): the plan's speech
                                                       clips, original and denoised, cut and picked on the GPU;
-                                                      --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate)
+                                                      --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
+                                                      --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
     python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
                                                       parameter grid, every machine scored on the GPU, the top K configs by
@@ -428,32 +429,55 @@ CLIP_PHASE = {"denoised": 2, "original": 0}        # the lane indices (mod 3) ke
                                                    # (resample.zig:32-79); what downsampleAudio feeds NSNet2 (resample.zig:9-29)
 
 
-def _clip_rates(original_rate, denoised_rate):
-    for what, rate in (("original_rate", original_rate), ("denoised_rate", denoised_rate)):
-        if rate not in CLIP_RATES:
-            raise ValueError(f"run_clips: {what} {rate!r} is neither 48000 nor 16000")
-    return {"original": original_rate, "denoised": denoised_rate}
+CLIP_FIR_RATES = {24000: 2, 16000: 3, 8000: 6}     # a filtered kind's rate -> the export's step (48000 would leave the filter nothing to do)
+CLIP_FILTERS = ("none", "fir")
 
 
-def _clip_skips(kind, rate, sample_from):
-    """(step, skips or None) of one export of `kind` clips starting at the absolute lane indices sample_from"""
-    step = CLIP_RATES[rate]
-    return (1, None) if step == 1 else (step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind]))
+def _clip_rates(original_rate, denoised_rate, original_filter="none", denoised_filter="none"):
+    """-> ({kind: rate}, {kind: None, or the filter of a filtered kind}); raises ValueError for what run_clips does not offer"""
+    rates, firs = {"original": original_rate, "denoised": denoised_rate}, {}
+    for kind, filt in (("original", original_filter), ("denoised", denoised_filter)):
+        rate = rates[kind]
+        if filt not in CLIP_FILTERS:
+            raise ValueError(f"run_clips: {kind}_filter {filt!r} is neither 'none' nor 'fir'")
+        if filt == "none":
+            if rate not in CLIP_RATES:
+                raise ValueError(f"run_clips: {kind}_rate {rate!r} is neither 48000 nor 16000")
+            firs[kind] = None
+            continue
+        if rate not in CLIP_FIR_RATES:
+            raise ValueError(f"run_clips: {kind}_rate {rate!r} with {kind}_filter 'fir' is none of 24000, 16000 and 8000")
+        step = CLIP_FIR_RATES[rate]
+        # the default design of fvad_clips_fir_design for the step, its parameters spelt out for the manifest
+        firs[kind] = {"step": step, "half": 16 * step, "cutoff": 0.45 / step, "beta": 6.0, "taps": fv.clips_fir_design(step)}
+    return rates, firs
+
+
+def _clip_skips(kind, rate, sample_from, fir=None):
+    """(step, skips or None, taps or None) of one export of `kind` clips starting at the absolute lane indices sample_from.  At
+    step 3 a filtered kind keeps the lane indices an unfiltered run keeps (first_sample agrees); at steps 2 and 6 phase 0"""
+    if fir is None:
+        step = CLIP_RATES[rate]
+        return (1, None, None) if step == 1 else (step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind]), None)
+    step = fir["step"]
+    return step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind] if step == 3 else 0), fir["taps"]
 
 
 def _write_clip(path, samples, pcm16, rate):
     (fv.wav_write_i16 if pcm16 else fv.wav_write)(path, samples, rate)
 
 
-def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample, length):
-    """a kind's manifest entry; a kind at 48 kHz has the keys it always had"""
+def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample, length, fir=None):
+    """a kind's manifest entry; a kind at 48 kHz has the keys it always had, an unfiltered kind at 16 kHz too"""
     e = {"file": os.path.basename(path), "best_channel": int(best_channel), "best_rms": float(best_rms), "runner_up_rms": float(runner_up_rms)}
     if rate != 48000:
         e.update(sample_rate=rate, first_sample=int(first_sample), length=int(length))
+    if fir is not None:
+        e["filter"] = {"design": "kaiser_sinc", "half": fir["half"], "cutoff": fir["cutoff"], "beta": fir["beta"], "taps": int(len(fir["taps"]))}
     return e
 
 
-def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates):
+def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs):
     """run_clips for the instances of one context -> [(segments, audit, manifest)] in the order given"""
     if not audio:
         return []
@@ -499,15 +523,15 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates):
             rows = np.concatenate(rows) if rows else np.zeros((0, fv.CLIP_FIELDS), np.uint64)
             if not rows.shape[0]:
                 continue
-            step, skips = _clip_skips(kind, rates[kind], rows[:, 2])
-            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16, step=step, skips=skips)
+            step, skips, taps = _clip_skips(kind, rates[kind], rows[:, 2], firs[kind])
+            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16, step=step, skips=skips, taps=taps)
             lens = res["out_lens"] if step != 1 else rows[:, 3] - rows[:, 2]
             for j, (i, k) in enumerate(owner):
                 o, n = int(res["offsets"][j]), int(lens[j])
                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], k, kind))
                 _write_clip(path, res["out"][o:o + n], pcm16, rates[kind])
                 manifests[i]["clips"][k][kind] = _clip_entry(path, res["best_channel"][j], res["best_rms"][j], res["runner_up_rms"][j], rates[kind],
-                                                             int(rows[j, 2]) + (0 if skips is None else int(skips[j])), n)
+                                                             int(rows[j, 2]) + (0 if skips is None else int(skips[j])), n, firs[kind])
         return [(segs, audit, m) for (segs, audit), m in zip(per_inst, manifests)]
     finally:
         for d in held:
@@ -515,7 +539,7 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates):
 
 
 def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None,
-              denoised_rate=48000, original_rate=48000):
+              denoised_rate=48000, original_rate=48000, original_filter="none", denoised_filter="none"):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -538,9 +562,17 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     sample, so these are NSNet2's own output and nothing is lost.  The original kind keeps the indices = 0 (mod 3), the
     reference's downsampleAudio: what NSNet2 was fed, WITHOUT an anti-alias filter -- it aliases exactly as the network's input
     does.  The files then say 16000 and the kind's manifest entries gain "sample_rate", "first_sample" (the absolute 48 kHz index
-    of the first kept sample) and "length"; at 48000 files and manifests are byte for byte what they were."""
+    of the first kept sample) and "length"; at 48000 files and manifests are byte for byte what they were.
+    original_filter / denoised_filter ("none" or "fir"): with "fir" that kind's clips are low-pass filtered while they are
+    decimated -- fvad_clips_export*_fir with fvad_clips_fir_design's default taps for the step (Kaiser-windowed sinc, 32 step + 1
+    taps, cutoff 0.45 / step) -- and its rate may be 24000, 16000 or 8000 (steps 2, 3, 6); 48000 raises, like every other
+    combination run_clips does not offer, before any work.  Each clip is filtered as a finite signal (zeros outside it), so a
+    file is what filtering and decimating the 48000 file with the same taps gives, and a sliced run holds no more audio than
+    before.  The pick and both RMS values are still taken over every unfiltered sample.  At 16000 the kept lane indices, hence
+    "first_sample" and "length", are those of the unfiltered run; at 24000 and 8000 they are the indices = 0 (mod step).  A
+    filtered kind's manifest entries gain "filter": {"design": "kaiser_sinc", "half", "cutoff", "beta", "taps"}."""
     _check_ingest(ingest)
-    rates = _clip_rates(original_rate, denoised_rate)
+    rates, firs = _clip_rates(original_rate, denoised_rate, original_filter, denoised_filter)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
         check_slice_chunks(slice_chunks, plan["fft_size"])
@@ -558,9 +590,9 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
             try:
                 insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
                 if slice_chunks is None:
-                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates)
+                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates, firs)
                 else:
-                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates)
+                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates, firs)
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -641,7 +673,7 @@ class _HeldTails:
                 b[0], b[1] = None, 0
 
 
-def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note, rates):
+def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note, rates, firs):
     """run_clips(slice_chunks=N) for the instances of one context -> [(segments, audit, manifest)] in the order given.
     Channel-count group after group, each in time slices [s0, s1) of N chunks read, denoised and band-summed as a sliced grid's
     (_slice_denoise_and_bands; audio mapped or raw), one single-config host batch per instance run on part by part (_HostParts).
@@ -652,7 +684,8 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
     into the other held buffer (_HeldTails).  The slices run one chunk past a group's last whole chunk where a file ends inside a
     chunk, so that the original audio's last samples are reached.  note: "held_peak_bytes", "slices".
     rates: a kind at 16000 exports with step 3, the skips from the clips' absolute sample_from (a clip's seam has no part in
-    them); the carry of the held tails stays a step-1 export."""
+    them); firs: a filtered kind exports with its step and taps, the filter running through the seam; the carry of the held
+    tails stays a step-1 export."""
     if not audio:
         return []
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
@@ -728,15 +761,15 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
                             pending[kind][k] = still
                             need += [a0 for _, a0, _ in still] + ([] if holds[k] is None else [holds[k]])
                         if rows:
-                            step, skips = _clip_skips(kind, rates[kind], [a0 for _, _, a0 in owner])
-                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16, step=step, skips=skips)
+                            step, skips, taps = _clip_skips(kind, rates[kind], [a0 for _, _, a0 in owner], firs[kind])
+                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16, step=step, skips=skips, taps=taps)
                             lens = res["out_lens"] if step != 1 else [r[3] + r[6] for r in rows]
                             for q, ((i, j, a0), o) in enumerate(zip(owner, res["offsets"])):
                                 o, n_clip = int(o), int(lens[q])
                                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], j, kind))
                                 _write_clip(path, res["out"][o:o + n_clip], pcm16, rates[kind])
                                 entries[i][(j, kind)] = _clip_entry(path, res["best_channel"][q], res["best_rms"][q], res["runner_up_rms"][q],
-                                                                    rates[kind], a0 + (0 if skips is None else int(skips[q])), n_clip)
+                                                                    rates[kind], a0 + (0 if skips is None else int(skips[q])), n_clip, firs[kind])
                         t.carry(b, start * chunk, s0 * chunk, s1 * chunk, min(need) if need else None)
                     note["held_peak_bytes"] = max(note["held_peak_bytes"], sum(t.bytes() for t in tails.values()))
                 for k, i in enumerate(members):
@@ -2044,6 +2077,11 @@ def arg_parser():
     ap.add_argument("--clips-original-rate", type=int, default=48000, metavar="HZ",
                     help="with --export-clips: 48000 or 16000 -- at 16000 the original clips are decimated as NSNet2's input is "
                          "(every third sample, no anti-alias filter: it aliases)")
+    ap.add_argument("--clips-original-filter", default="none", choices=CLIP_FILTERS,
+                    help="with --export-clips: fir -- the original clips are low-pass filtered while they are decimated (a Kaiser-windowed "
+                         "sinc of 32 step + 1 taps on the GPU); --clips-original-rate may then be 24000, 16000 or 8000")
+    ap.add_argument("--clips-denoised-filter", default="none", choices=CLIP_FILTERS,
+                    help="with --export-clips: fir -- the same for the denoised clips (at 16000 they need no filter: use it for 24000 or 8000)")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -2065,7 +2103,8 @@ def main(argv=None):
     if a.export_clips:
         info = {}
         text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest,
-                            slice_chunks=a.slice_chunks, info=info, denoised_rate=a.clips_denoised_rate, original_rate=a.clips_original_rate)
+                            slice_chunks=a.slice_chunks, info=info, denoised_rate=a.clips_denoised_rate, original_rate=a.clips_original_rate,
+                            original_filter=a.clips_original_filter, denoised_filter=a.clips_denoised_filter)
         sys.stdout.write(text)
         if info:
             sys.stdout.write(f"\n[{info['slices']} slices; held tails: {info['held_peak_bytes'] / 2 ** 20:.1f} MiB of device memory at most]\n")

@@ -885,7 +885,7 @@ int fvad_vad_batch_hold_from(const fvad_vad_batch *b, size_t config, uint64_t *h
  *   full-rate exports' bits and offsets.
  * - Step 3 with the skips of phase 2 is lossless with respect to the denoiser.  With phase 0 on the original audio it is the
  *   reference's downsampleAudio (resample.zig:9-29: lane index = 0 mod 3, NO anti-alias filter) -- sample for sample what
- *   NSNet2 was fed, aliasing included.  A filtered decimator is a different feature.
+ *   NSNet2 was fed, aliasing included.  The filtered decimator is fvad_clips_export_fir* (the next block).
  *
  * fvad_clips_phase_skips (host only): skips[i] = (phase + step - sample_from[i] mod step) mod step, so that the kept samples
  * are the lane indices = phase (mod step).  FVAD_ERR_INVALID_ARGUMENT for step == 0, step > FVAD_CLIP_STEP_MAX, phase >= step
@@ -922,6 +922,64 @@ int fvad_clips_export_split_strided(fvad_ctx *ctx, const void *d_a, size_t a_lan
                                     const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
                                     int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
                                     uint32_t step, const uint32_t *skips);
+
+/* ------------------------------------------------------------------ batch Recorder with a filter: anti-aliased clips
+ * The strided export keeps every step-th sample and nothing else, so whatever the lane holds above the new Nyquist frequency
+ * folds into the exported band (a 10 kHz tone in a 48 kHz lane leaves a step-3 export as a 6 kHz tone at full level).  A
+ * filtered export is a strided export plus `const float *taps, uint32_t n_taps` in host memory: a FIR filter applied while the
+ * clip is decimated (csrc/kernels_clips_fir.hip), so that only the kept, band-limited samples leave the device.
+ * - n_taps is odd, 1 <= n_taps <= FVAD_CLIP_FIR_TAPS_MAX; H = (n_taps - 1) / 2; the taps need not be symmetric.
+ * - Clip, pick, step, skip, out_len = ceil((len - skip) / step), slots and out_offsets are exactly the strided export's
+ *   (fvad_clips_plan_strided plans it).  step == 1 is a plain FIR without decimation, n_taps == 1 a scaled strided export.
+ * - Output q of a clip is centred on clip sample c = skip + q * step of the picked channel:
+ *       y[q] = sum over k = 0 .. n_taps - 1 of taps[k] * x[c + k - H]
+ *   x[i] is the clip's sample i as f32 (PCM16: s / 32768, exact) and 0 for i < 0 or i >= len; the sum is accumulated in f32 and
+ *   converted by fvad_clips_export's rule for an f32 source (f32: as it is; PCM16: rint(clamp(y * 32768, -32768, 32767))).
+ * - The clip is filtered as a finite signal, zero-extended: nothing outside [sample_from, sample_to) is read.  So a filtered
+ *   clip is what decimating the full-rate exported clip on the host with the same taps gives, and a sliced run needs no more
+ *   held audio than fvad_vad_batch_hold_from keeps.
+ * - RMS and pick run over every sample of the UNFILTERED clip: best_channel, best_rms and runner_up_rms are the full-rate
+ *   export's bits.
+ * - INVARIANTS.  An output's bits do not depend on the call form (contiguous or split, device or host output), on where the
+ *   seam of a split clip is, on which tile of the gather the output falls in, or on the other clips of the call.  The PCM16
+ *   output is the f32 output of the same call converted by the rule above, bit for bit.  A PCM16 source gives the bits of an
+ *   f32 source that holds s / 32768.  (Every output is one f32 fma chain from +0 in an order that depends on step and n_taps
+ *   alone; the order itself is not part of the contract.)
+ *
+ * fvad_clips_fir_design (host only): taps[0 .. 2 half] of a Kaiser-windowed sinc, computed in float64:
+ *   h[k] = 2 cutoff sinc(2 cutoff (k - half)) * kaiser(2 half + 1, beta)[k], normalised to unit sum, then rounded to f32;
+ *   cutoff in cycles per input sample, I0 by its power series.  half == 0 selects half = 16 step, cutoff == 0 selects
+ *   cutoff = 0.45 / step, beta == 0 selects beta = 6.  FVAD_ERR_INVALID_ARGUMENT for a step outside 1..FVAD_CLIP_STEP_MAX,
+ *   half > 256, a cutoff not in (0, 0.5] (0 apart), a negative or non-finite beta, or NULL.
+ * fvad_clips_fir_check (host only): the tap rules without a device -- FVAD_ERR_INVALID_ARGUMENT for NULL taps, n_taps of 0,
+ *   an even n_taps, n_taps above FVAD_CLIP_FIR_TAPS_MAX or a non-finite tap.
+ * fvad_clips_export_fir_device / fvad_clips_export_fir / fvad_clips_export_split_fir_device / fvad_clips_export_split_fir:
+ *   the matching strided call's arguments, then taps and n_taps.  Every error comes back before any launch; the tap rules are
+ *   reported directly after the strided rules for step and skips, before ranges and lanes.  fvad_ctx_kernel_times names
+ *   clip_rms, clip_pick, clip_gather_fir (split: clip_rms_split, clip_pick, clip_gather_fir_split), at every step. */
+#define FVAD_CLIP_FIR_TAPS_MAX 513
+int fvad_clips_fir_design(uint32_t step, uint32_t half, double cutoff, double beta, float *taps);
+int fvad_clips_fir_check(const float *taps, uint32_t n_taps);
+int fvad_clips_export_fir_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                 size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                 size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                 uint64_t *out_offsets, uint32_t step, const uint32_t *skips, const float *taps,
+                                 uint32_t n_taps);
+int fvad_clips_export_fir(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                          size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *out,
+                          size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                          uint64_t *out_offsets, uint32_t step, const uint32_t *skips, const float *taps, uint32_t n_taps);
+int fvad_clips_export_split_fir_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                       const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                       const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                       size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                       uint64_t *out_offsets, uint32_t step, const uint32_t *skips, const float *taps,
+                                       uint32_t n_taps);
+int fvad_clips_export_split_fir(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                                int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
+                                uint32_t step, const uint32_t *skips, const float *taps, uint32_t n_taps);
 
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
