@@ -363,9 +363,15 @@ int fvad_launch_panel_gemm_s_rows(const float* A, int lda, const float* Wfrag, c
 //     the read of tile t for step s+1 is issued right after the MFMAs of tile t in step s, so every
 //     wait is lgkmcnt(NT-1) on data requested ~NT MFMA groups earlier; the compiler no longer sees
 //     LDS reads that could alias the DMA;
-//   * loads the activations of the next item's first two super-steps before the epilogue stores
-//     (vmcnt retires in order on gfx9: a load issued after the stores cannot be waited for without
-//     waiting for the stores too), so the stores have two super-steps to drain in the background.
+//   * requests the activations two super-steps ahead, straight through item boundaries: super-step s
+//     starts by taking the operand of s+1 (requested at the top of s-1) out of `apre` and requesting
+//     that of s+2 into it -- past the item's last super-step the next item's first two.  The loop has one
+//     s_waitcnt vmcnt per super-step, at its top; the earlier form (operand of s+1 requested in s and
+//     copied at the end of s, the next item's second operand requested in front of the epilogue stores
+//     and selected by `sg == 0`) compiled to two, top and bottom, and measured 1.2-3.9 % slower per layer
+//     at the headline launch (LAB_NOTES).  The next item's first two operands are requested before the
+//     epilogue stores either way (vmcnt retires in order on gfx9: a load issued after the stores
+//     cannot be waited for without waiting for the stores too).
 template <int T, int N> struct StaticFor {
     template <class F> static __device__ __forceinline__ void run(F&& f) {
         f(std::integral_constant<int, T>{});
@@ -506,13 +512,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
                 constexpr bool LAST = decltype(last_c)::value;
                 const int sg = s0 + s;
                 f32x4 a1[RT];
-                if (sg == 0) {
 #pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) a1[rt] = apre[rt]; // requested before the previous epilogue
-                } else {
-#pragma unroll
-                    for (int rt = 0; rt < RT; ++rt)
-                        a1[rt] = *(gptr4)((sg + 1 < S_steps) ? a_ptr[rt] + 16 * (sg + 1) : a_nextitem[rt]);
+                for (int rt = 0; rt < RT; ++rt) {
+                    a1[rt] = apre[rt]; // the operand of sg + 1, requested a super-step ago; sg + 2 (S_steps >= 2) takes its place
+                    apre[rt] = *(gptr4)((sg + 2 < S_steps) ? a_ptr[rt] + 16 * (sg + 2) : a_nextitem[rt] + 16 * (sg + 2 - S_steps));
                 }
                 // MFMA r of a super-step reduces over k = 16 sg + 4q + r: when K is not a multiple of 16 the
                 // last super-step's higher r are all padding (K = 161: only r = 0 carries k = 160)
@@ -561,9 +564,8 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2
             buf ^= 1;
         }
 
-        // epilogue of this item; the next item's first slab is already in LDS
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) apre[rt] = *(gptr4)(a_nextitem[rt] + 16);
+        // epilogue of this item; the next item's first slab is already in LDS, its first two activation operands are in
+        // a0 and apre (requested by this item's last two super-steps)
         const int nblk = (int)(item % (unsigned)n_blocks);
         const unsigned panel = item / (unsigned)n_blocks;
         // The store path merges adjacent lanes only: in the MFMA layout (lane = m + 16 q) adjacent lanes
@@ -623,7 +625,7 @@ int fvad_launch_panel_gemm3(const float* A, int lda, const float* Wfrag, const f
                             int n_valid_tiles, int map_T, int map_skip, int n_wg, hipStream_t stream, bool trim_tiles,
                             const Gemm3RowMap* cmap)
 {
-    if (rows % 256) return -1;
+    if (rows % 256 || S_steps < 2) return -1; // (the activation operands are requested two super-steps ahead)
     int map_per = map_T - map_skip;
     unsigned map_qmax = 0;
     if (cmap) {
