@@ -24,6 +24,9 @@ const std = @import("std");
 pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
+pub const resample_fields = 11; // FVAD_RESAMPLE_FIELDS: ingest_fields' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
+pub const resample_up_max = 640; // FVAD_RESAMPLE_UP_MAX
+pub const resample_taps_max = 20481; // FVAD_RESAMPLE_TAPS_MAX
 pub const wav_info_fields = 6; // FVAD_WAV_INFO_FIELDS: format, n_channels, sample_rate, data_offset, n_frames, bits
 pub const clip_split_fields = 7; // FVAD_CLIP_SPLIT_FIELDS: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (u64 each)
 pub const clip_fields = 4; // FVAD_CLIP_FIELDS: a clip is a row of first_lane, n_channels, sample_from, sample_to (u64 each)
@@ -442,6 +445,15 @@ pub extern "c" fn fvad_wav_probe(path: [*:0]const u8, info: [*]u64) c_int;
 pub extern "c" fn fvad_ingest_check(sources: ?[*]const u64, n_sources: usize, raw_bytes: u64, out_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest_device(ctx: *Ctx, d_raw: ?*const anyopaque, raw_bytes: u64, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest(ctx: *Ctx, src_host: ?[*]const ?*const anyopaque, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+// resampling ingest: files at another rate filtered and re-timed into 48 kHz f32 lanes (a rational up/down polyphase resampler)
+pub extern "c" fn fvad_resample_ratio(rate_in: u32, rate_out: u32, up: *u32, down: *u32) c_int;
+pub extern "c" fn fvad_resample_out_frames(file_frames: u64, up: u32, down: u32) u64;
+pub extern "c" fn fvad_resample_design(up: u32, down: u32, half: u32, cutoff: f64, beta: f64, taps: [*]f32, n_taps: *u32) c_int;
+pub extern "c" fn fvad_resample_window(up: u32, down: u32, n_taps: u32, file_frames: u64, out_from: u64, n_out: u64, frame_lo: *u64, frame_hi: *u64) c_int;
+pub extern "c" fn fvad_ingest_resample_tile(up: u32, down: u32, n_taps: u32, n_channels: u32, format: u32) u64;
+pub extern "c" fn fvad_ingest_resample_check(sources: ?[*]const u64, n_sources: usize, raw_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, out_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_ingest_resample_device(ctx: *Ctx, d_raw: ?*const anyopaque, raw_bytes: u64, sources: ?[*]const u64, n_sources: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_ingest_resample(ctx: *Ctx, src_host: ?[*]const ?*const anyopaque, sources: ?[*]const u64, n_sources: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;

@@ -34,6 +34,9 @@ INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, 
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
 INGEST_SAMPLE_BYTES = {INGEST_F32: 4, INGEST_PCM16: 2, INGEST_PCM24: 3}
 INGEST_TILE_BYTES = 16384        # kIngestTileBytes (csrc/kernels.h): the source bytes a workgroup of the ingest kernel takes
+RESAMPLE_FIELDS = 11             # a resample source: INGEST_FIELDS' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
+RESAMPLE_UP_MAX = 640            # FVAD_RESAMPLE_UP_MAX
+RESAMPLE_TAPS_MAX = 20481        # FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1)
 INGEST_FILL_TILE = 8192          # kIngestFillTile: the zeros of one lane a workgroup writes
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
 
@@ -365,6 +368,14 @@ SIGNATURES = {
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
     "fvad_ingest": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
+    "fvad_resample_ratio": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fvad_resample_out_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "fvad_resample_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p, C.POINTER(C.c_uint32)]),
+    "fvad_resample_window": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_ingest_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "fvad_ingest_resample_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_int, sz, sz, sz]),
+    "fvad_ingest_resample_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, vp, sz, sz, sz]),
+    "fvad_ingest_resample": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, vp, sz, sz, sz]),
 }
 
 _lib = None
@@ -806,6 +817,34 @@ class Context:
             return
         self._ck(lib().fvad_ingest_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, fmt, vp(d_lanes), n_lanes, lane_stride,
                                           n_samples), "fvad_ingest_device")
+
+    def ingest_resample(self, sources, up, down, taps, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, raw=None, raw_bytes=None):
+        """fvad_ingest_resample_device (raw: a device address holding raw_bytes bytes) or fvad_ingest_resample (raw: a list with
+        one byte buffer per source, as for `ingest`; a source's byte_offset is where its frame frame_base lies in its own
+        buffer): sources [n][RESAMPLE_FIELDS] uint64 of files at 1 / (up / down) of the lanes' rate -> float32 lanes at device
+        address d_lanes.  One ratio and one set of taps (float32, an odd count) per call."""
+        sources = _resample_rows(sources)
+        n = sources.shape[0]
+        rows = sources.ctypes.data_as(C.POINTER(C.c_uint64))
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        tail = (up, down, fptr(taps), taps.shape[0], vp(d_lanes), n_lanes, lane_stride, n_samples)
+        if isinstance(raw, (list, tuple)):
+            if len(raw) != n:
+                raise ValueError(f"ingest_resample: {n} sources, {len(raw)} buffers")
+            ptrs = (vp * max(n, 1))()
+            for i, b in enumerate(raw):
+                if b is None or b.size == 0 or int(sources[i, 1]) == 0:   # no frames given: no byte is read
+                    ptrs[i] = None
+                    continue
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"]:
+                    raise ValueError("ingest_resample: a source's bytes are a C-contiguous uint8 array")
+                need = int(sources[i, 0]) + int(sources[i, 1]) * int(sources[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sources[i, 3]), 4)
+                if need > b.size:   # (the library cannot know where a host buffer ends)
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_ingest_resample", f"source {i} reads {need} bytes of a buffer of {b.size}")
+                ptrs[i] = b.ctypes.data
+            self._ck(lib().fvad_ingest_resample(self.h, ptrs, rows, n, *tail), "fvad_ingest_resample")
+            return
+        self._ck(lib().fvad_ingest_resample_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, *tail), "fvad_ingest_resample_device")
 
     def lane_state(self):
         s = vp()
@@ -1621,6 +1660,56 @@ def ingest_check(sources, raw_bytes, out_pcm16, n_lanes, lane_stride, n_samples)
     sources = _ingest_rows(sources)
     return lib().fvad_ingest_check(sources.ctypes.data_as(C.POINTER(C.c_uint64)), sources.shape[0], int(raw_bytes),
                                    INGEST_PCM16 if out_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def _resample_rows(sources):
+    return np.ascontiguousarray(np.asarray(sources, np.uint64).reshape(-1, RESAMPLE_FIELDS))
+
+
+def resample_ratio(rate_in, rate_out=48000):
+    """fvad_resample_ratio: (up, down) = rate_out / rate_in in lowest terms; FvadError for a zero rate or up > RESAMPLE_UP_MAX"""
+    up, down = C.c_uint32(0), C.c_uint32(0)
+    check(lib().fvad_resample_ratio(rate_in, rate_out, C.byref(up), C.byref(down)), f"fvad_resample_ratio({rate_in}, {rate_out})")
+    return up.value, down.value
+
+
+def resample_out_frames(file_frames, up, down):
+    """fvad_resample_out_frames: ceil(file_frames * up / down)"""
+    return int(lib().fvad_resample_out_frames(int(file_frames), up, down))
+
+
+def resample_design(up, down, half=0, cutoff=0.0, beta=0.0):
+    """fvad_resample_design: the 2 half max(up, down) + 1 float32 taps of a Kaiser-windowed sinc that sum to `up` (half 0: 16,
+    cutoff 0: 0.45 / max(up, down) cycles per sample of the up-times-oversampled input, beta 0: 6)"""
+    taps, n = np.zeros(RESAMPLE_TAPS_MAX, np.float32), C.c_uint32(0)
+    check(lib().fvad_resample_design(up, down, half, cutoff, beta, fptr(taps), C.byref(n)), "fvad_resample_design")
+    return taps[:n.value].copy()
+
+
+def resample_window(up, down, n_taps, file_frames, out_from, n_out):
+    """fvad_resample_window: (frame_lo, frame_hi), the file's frames that outputs [out_from, out_from + n_out) read"""
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    check(lib().fvad_resample_window(up, down, n_taps, int(file_frames), int(out_from), int(n_out), C.byref(lo), C.byref(hi)),
+          "fvad_resample_window")
+    return int(lo.value), int(hi.value)
+
+
+def ingest_resample_tile(up, down, n_taps, n_channels, fmt):
+    """fvad_ingest_resample_tile: outputs of one channel per workgroup of the resampling ingest kernel (0: the taps are too long
+    for frames this wide)"""
+    return int(lib().fvad_ingest_resample_tile(up, down, n_taps, n_channels, fmt))
+
+
+def ingest_resample_check(sources, raw_bytes, up, down, taps, n_lanes, lane_stride, n_samples, out_pcm16=False):
+    """fvad_ingest_resample_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sources = _resample_rows(sources)
+    if taps is None:
+        tp, nt = None, 0
+    else:
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        tp, nt = fptr(taps), taps.shape[0]
+    return lib().fvad_ingest_resample_check(sources.ctypes.data_as(C.POINTER(C.c_uint64)), sources.shape[0], int(raw_bytes), up, down,
+                                            tp, nt, INGEST_PCM16 if out_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
 
 
 def wav_probe(path):

@@ -526,3 +526,31 @@ struct IngestArgs {
     int src_format, out_i16;      // FVAD_INGEST_*
 };
 int fvad_launch_ingest(const IngestArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ resampling ingest (kernels_ingest_resample.hip)
+// fvad_ingest_resample*: a work unit is a tile of one source -- tile_out consecutive outputs (resample_tile of resample.h, a
+// multiple of 4) of every channel, whose window of source frames is staged through LDS -- or, after the n_data_tiles, a fill
+// tile as above.  Output i of the job is output out_from + i of the FILE; frame f of the file lies at raw + src_off +
+// (f - frame_base) * frame bytes.  One ratio and one tap table (resample_table's layout) per launch.
+struct IngestResampleJob {
+    uint64_t src_off;    // bytes from `raw` to the file's frame frame_base
+    uint64_t frame_base, file_frames;
+    uint64_t out_from, n_out;
+    uint64_t dst_off;    // elements from `lanes` to the sample output out_from of channel 0 is written to
+    uint64_t fill_len;   // zeros behind the outputs, in every lane of the source
+    uint32_t n_data_tiles, n_fill_tiles; // n_fill_tiles: per lane
+    uint32_t tile_out, n_channels;
+};
+struct IngestResampleArgs {
+    const uint8_t* raw;
+    float* lanes;
+    uint64_t lane_stride;
+    const IngestResampleJob* jobs; // [n_jobs] (device)
+    const uint32_t* unit_prefix;   // [n_jobs + 1]
+    const float* table;            // [ceil(n_taps / up)][up] (device)
+    uint32_t n_jobs, n_units;
+    uint32_t up, down, n_taps;
+    int src_format;                // FVAD_INGEST_*
+    uint32_t lds_bytes;            // the largest window of a tile of these jobs + 16
+};
+int fvad_launch_ingest_resample(const IngestResampleArgs& a, hipStream_t stream); // hipError_t as int

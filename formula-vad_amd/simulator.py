@@ -24,6 +24,7 @@ SimulationInstance.zig:101-104).  Differences, by design:
 """
 import argparse
 import collections
+import functools
 import itertools
 import json
 import math
@@ -231,13 +232,17 @@ def _map_instances(host_stage, n):
         return list(pool.map(host_stage, range(n)))
 
 
+# (the reference refuses such a file; here the GPU resamples it while it is ingested)
+OTHER_RATE_HINT = "a file that is not at 48 kHz is resampled on the GPU only: run with --ingest device (ingest='device')"
+
+
 def _read_instance(inst):
     try:    # PCM16 files stay 16-bit all the way to the GPU (half the PCIe / HBM bytes; converted by the kernel
         pcm, sr = fv.wav_read_i16(inst["audio_path"])   # that reads them, bit-identical to converting first)
     except fv.FvadError:
         pcm, sr = fv.wav_read(inst["audio_path"])
     if sr != 48000:
-        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
+        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}", OTHER_RATE_HINT)   # VADPipeline.zig:55-58
     with open(inst["ref_path"], "rb") as f:
         return pcm, fv.parse_audacity(f.read())
 
@@ -251,28 +256,63 @@ def _map_audio(inst):
     """an instance's audio mapped, not read (fv.wav_map): [n_frames][n_channels] int16 or float32"""
     pcm, sr = fv.wav_map(inst["audio_path"])
     if sr != 48000:
-        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}")   # VADPipeline.zig:55-58
+        raise fv.FvadError(-9, f"{inst['name']}: sample rate {sr}", OTHER_RATE_HINT)   # VADPipeline.zig:55-58
     return pcm
 
 
 INGESTS = ("host", "device")
 
 
+@functools.lru_cache(maxsize=None)
+def _resample_design(rate):
+    """(up, down, taps) of a file rate: fvad_resample_ratio to 48 kHz and fvad_resample_design's default taps, made once per rate"""
+    up, down = fv.resample_ratio(rate, 48000)
+    return up, down, fv.resample_design(up, down)
+
+
 class _RawAudio:
     """An instance's audio for ingest="device": the bytes of its file's data chunk, mapped and interleaved as the file holds
     them (fv.wav_map_raw), which fvad_ingest de-interleaves and decodes on the GPU.  n_channels and n_frames are what the
-    harness needs of a loaded instance (_dims); it is no array."""
+    harness needs of a loaded instance (_dims); it is no array.
+    A file at another rate (`rate` != 48000) is resampled while it is ingested (fvad_ingest_resample, _resample_design's ratio
+    and taps): n_frames is then its 48 kHz output count and `source` takes 48 kHz coordinates, so that everything downstream
+    sees an ordinary 48 kHz instance; file_frames is what the file holds."""
 
     def __init__(self, raw, info):
         self.raw, self.format = raw, info["format"]
         self.n_channels, self.n_frames = info["n_channels"], info["n_frames"]
         self.frame_bytes = self.n_channels * (info["bits"] // 8)
+        self.rate = info.get("sample_rate", 48000)
+        if self.rate != 48000:
+            self.up, self.down, self.taps = _resample_design(self.rate)
+            self.file_frames = info["n_frames"]
+            self.n_frames = fv.resample_out_frames(self.file_frames, self.up, self.down)
 
     def source(self, frame_from, frame_to, first_lane, dst_offset, fill_to):
         """the fvad_ingest source row of frames [frame_from, frame_to); frame_to <= frame_from (a slice behind the file's end):
-        a row without frames at byte 0, which only fills"""
+        a row without frames at byte 0, which only fills.  At another rate: the fvad_ingest_resample row of the 48 kHz outputs
+        [frame_from, frame_to), whose given frames are exactly the window of that range (fvad_resample_window)"""
         n = max(frame_to - frame_from, 0)
-        return (frame_from * self.frame_bytes if n else 0, n, self.n_channels, self.format, first_lane, dst_offset, fill_to)
+        if self.rate == 48000:
+            return (frame_from * self.frame_bytes if n else 0, n, self.n_channels, self.format, first_lane, dst_offset, fill_to)
+        lo, hi = fv.resample_window(self.up, self.down, self.taps.size, self.file_frames, frame_from, n) if n else (0, 0)
+        return (lo * self.frame_bytes, hi - lo, self.n_channels, self.format, first_lane, dst_offset, fill_to,
+                lo, self.file_frames, frame_from if n else 0, n)
+
+
+def _ingest_rows(ctx, members, rows, **lanes):
+    """The sources `rows` of the instances `members` (_RawAudio each) into the lanes: one fvad_ingest call for the 48 kHz members
+    and one fvad_ingest_resample call per other rate present (one ratio and one set of taps per call)."""
+    by_rate = {}
+    for a, row in zip(members, rows):
+        by_rate.setdefault(a.rate, []).append((a, row))
+    for rate, pairs in by_rate.items():
+        raws, rs = [a.raw for a, _ in pairs], [r for _, r in pairs]
+        if rate == 48000:
+            ctx.ingest(rs, raw=raws, **lanes)
+        else:
+            a = pairs[0][0]
+            ctx.ingest_resample(rs, a.up, a.down, a.taps, raw=raws, **lanes)
 
 
 def _dims(a, mapped=False):
@@ -286,7 +326,10 @@ def _dims(a, mapped=False):
 def _raw_audio(inst):
     raw, info = fv.wav_map_raw(inst["audio_path"])
     if info["sample_rate"] != 48000:
-        raise fv.FvadError(-9, f"{inst['name']}: sample rate {info['sample_rate']}")   # VADPipeline.zig:55-58
+        try:   # any rate with a ratio to 48 kHz that fvad_resample_ratio takes (up <= 640) is resampled by the ingest
+            fv.resample_ratio(info["sample_rate"], 48000)
+        except fv.FvadError:
+            raise fv.FvadError(-9, f"{inst['name']}: sample rate {info['sample_rate']}", "no ratio to 48000 with up <= 640") from None
     if info["n_channels"] > 64:
         raise fv.FvadError(fv.FVAD_ERR_INVALID_ARGUMENT, inst["name"], f"{info['n_channels']} channels: fvad_ingest takes 64")
     return _RawAudio(raw, info)
@@ -553,6 +596,9 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     pass pads every lane to the longest instance, so a plan of unequal lengths may be cut into other launches (the context option
     "reproducible" makes the two agree bit for bit for every plan).
     ingest "device": the files' bytes go to the GPU as they are and are decoded there (run_grid); the same clips and manifests.
+    With it a file at another rate (44.1 kHz, 16 kHz ...) is resampled to 48 kHz while it is ingested (fvad_ingest_resample,
+    the default design): segments, manifests and reports stay in 48 kHz terms, and the clips of such an instance -- the
+    "original" kind too -- are clips of the RESAMPLED audio, not of the file's own samples.
     slice_chunks N: the same files, manifests, report and return value from time slices of N chunks (_clips_sliced_share), the
     device memory bounded by a slice and the held tails instead of the corpus; None is the resident path above.
     info (a dict): filled with "held_peak_bytes", the most device memory the held tails took on one context, and "slices".
@@ -924,7 +970,7 @@ def _denoise_resident(ctx, audio, F, config0, dalloc):
         for i in order:
             rows.append(audio[i].source(0, audio[i].n_frames, l, 0, stride))
             l += audio[i].n_channels
-        ctx.ingest(rows, d_lanes=d_pcm, n_lanes=n_lanes, lane_stride=stride, n_samples=stride, raw=[audio[i].raw for i in order])
+        _ingest_rows(ctx, [audio[i] for i in order], rows, d_lanes=d_pcm, n_lanes=n_lanes, lane_stride=stride, n_samples=stride)
     else:
         host = np.zeros((n_lanes, stride), np.float32)   # filled channel by channel: no other f32 copy of the corpus
         l = 0
@@ -1338,7 +1384,10 @@ def run_grid(plan_path, grid, top=20, vad_on="auto", score_on="auto", json_path=
     host and uploaded as f32.  "device": every file's data chunk is mapped as bytes (wav_map_raw), sliced or not, and
     fvad_ingest takes the bytes to the GPU as they are -- PCM16 at 2 bytes per sample -- where one kernel de-interleaves,
     decodes and pads them into the same f32 lanes: the same bits downstream, hence the same result.  24-bit PCM files run with
-    "device" only; "host" refuses them (FvadError naming --ingest device)."""
+    "device" only; "host" refuses them (FvadError naming --ingest device).  The same holds for files at another rate than 48 kHz
+    (44.1 kHz, 32 kHz, 16 kHz ...: any rate whose ratio to 48000 has up <= 640): with "device" fvad_ingest_resample filters and
+    re-times them into 48 kHz lanes while it decodes them (one call per rate beside the 48 kHz files' fvad_ingest), labels,
+    segments and reports stay in 48 kHz terms, and a sliced run equals the unsliced one; "host" refuses them with status -9."""
     _check_vad_chain(vad_chain, vad_avgs, vad_trigger)
     _check_ingest(ingest)
     n_shares = _check_grid_contexts(ctx, devices)   # None: one context, today's path without a thread
@@ -1870,7 +1919,7 @@ def _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, blocks, time
     d_bands, d_rms = (d["bands"], d["rms"]) if dset is None else dset
     if _is_raw(audio):   # ingest "device": one source per member -- the slice and its halo, then zeros to the slice's end; waits for the main stream only
         rows = [audio[i].source(start * chunk, min(s1 * chunk, audio[i].n_frames), k * nch, 0, n * chunk) for k, i in enumerate(members)]
-        ctx.ingest(rows, d_lanes=d["pcm"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk, raw=[audio[i].raw for i in members])
+        _ingest_rows(ctx, [audio[i] for i in members], rows, d_lanes=d["pcm"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk)
     else:
         pcm = host[:L * n * chunk].reshape(L, n * chunk)
         for k, i in enumerate(members):
@@ -2088,7 +2137,8 @@ def arg_parser():
     ap.add_argument("--ingest", default="host", choices=INGESTS,
                     help="with --sweep / --sweep-grid / --export-clips: where the files' samples are de-interleaved and decoded -- on "
                          "the host, uploaded as f32 (the default), or on the GPU from the files' own bytes (fvad_ingest: PCM16 crosses "
-                         "PCIe at 2 bytes per sample, and 24-bit PCM files are taken); same results")
+                         "PCIe at 2 bytes per sample, and 24-bit PCM files are taken); same results.  Files at other rates than 48 kHz "
+                         "(44.1 kHz, 16 kHz ...) run with device only: they are resampled to 48 kHz while they are ingested")
     return ap
 
 

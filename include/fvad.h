@@ -1034,6 +1034,87 @@ int fvad_ingest_device(fvad_ctx *ctx, const void *d_raw, uint64_t raw_bytes, con
 int fvad_ingest(fvad_ctx *ctx, const void *const *src_host, const uint64_t *sources, size_t n_sources, int out_format,
                 void *d_lanes, size_t n_lanes, size_t lane_stride, size_t n_samples);
 
+/* ------------------------------------------------------------------ resampling ingest: corpora at other rates into 48 kHz lanes
+ * The batch paths run at 48 kHz.  A file at another rate (44.1 kHz, 32 kHz, 16 kHz ...) goes to the device as its own bytes, as
+ * with fvad_ingest, and ONE kernel (csrc/kernels_ingest_resample.hip) decodes, de-interleaves, filters and re-times it: a
+ * rational up/down polyphase resampler inside the ingest.  The lanes are ordinary 48 kHz f32 lanes.
+ * THE DEFINITION
+ * - A ratio is up/down = rate_out/rate_in in lowest terms (fvad_resample_ratio): 44100 -> 48000 is 160/147, 32000 3/2,
+ *   22050 320/147, 16000 3/1, 24000 2/1, 8000 6/1, 96000 1/2, 11025 640/147.  1 <= up <= FVAD_RESAMPLE_UP_MAX, down >= 1.
+ * - The prototype is taps[0 .. 2 K], an odd count n_taps <= FVAD_RESAMPLE_TAPS_MAX with centre K; it need not be symmetric.
+ * - A file of file_frames frames has out_frames = ceil(file_frames * up / down) outputs (fvad_resample_out_frames).
+ * - Output o of a channel is
+ *       y[o] = sum over n of x[n] * taps[K + o * down - n * up],   over every n whose tap index lies in [0, 2 K],
+ *   x[n] the decoded sample of frame n (fvad_ingest's rules: PCM16 s / 32768, PCM24 s / 8388608, f32 the value) and 0 outside
+ *   [0, file_frames).  The filter is centred (zero phase): output o sits at time o / rate_out of the file, so segments, labels
+ *   and clip indices need no delay correction.  A file is filtered as a finite signal; nothing outside it is read.
+ * - Index arithmetic is 64-bit throughout (o * down passes 2^32 after 10.1 minutes of 44.1 kHz audio); file_frames * up must
+ *   stay below 2^62.
+ * - The lanes are f32.  PCM16 lanes would be a conversion: FVAD_ERR_INVALID_ARGUMENT, as fvad_ingest says for PCM24 -> PCM16.
+ * - INVARIANTS, all bit for bit.  A file's lane bits do not depend on how the file is cut into sources or calls (time slices),
+ *   on the order of the sources, on the other sources of the call, on which tile of the kernel an output falls in, on the call
+ *   form (device bytes or host bytes), on ingest_ring_bytes or on the destination's alignment.  A PCM16 source gives the bits of
+ *   an f32 source holding s / 32768, PCM24 likewise with s / 8388608.  No atomics; nothing outside [dst_offset, fill_to) of a
+ *   source's lanes is written.  (Every output is one f32 fma chain from +0 in an order that depends on up, down, n_taps and
+ *   o mod up alone; the order itself is not part of the contract.)
+ * - A source is a row of FVAD_RESAMPLE_FIELDS uint64: byte_offset (where frame `frame_base` lies in the raw bytes), n_frames
+ *   (the frames given), n_channels, format, first_lane, dst_offset (the lane sample output out_from is written to), fill_to (>=
+ *   dst_offset + n_out; zeros behind the outputs), frame_base, file_frames, out_from, n_out.  The row asks for outputs
+ *   [out_from, out_from + n_out) of the file and gives frames [frame_base, frame_base + n_frames) of it: a slice of a file is a
+ *   row whose given frames cover the window of its outputs, and is then the whole file's result by construction.  One ratio and
+ *   one set of taps per call.
+ *
+ * Host only (csrc/host_resample.cpp):
+ * fvad_resample_ratio: up/down = rate_out/rate_in reduced by their gcd; FVAD_ERR_INVALID_ARGUMENT for a zero rate, NULL or
+ *   up > FVAD_RESAMPLE_UP_MAX.
+ * fvad_resample_out_frames: ceil(file_frames * up / down), saturated at UINT64_MAX; 0 for a ratio that is none.
+ * fvad_resample_design: fvad_clips_fir_design's rule with m = max(up, down): K = half * m, taps[0 .. 2 K] with
+ *   h[k] = 2 cutoff sinc(2 cutoff (k - K)) * kaiser(2 K + 1, beta)[k] in float64, normalised to sum `up` (unit DC gain), then
+ *   rounded to f32; *n_taps = 2 K + 1.  cutoff is in cycles per sample of the up-times-oversampled input.  half == 0 selects
+ *   16, cutoff == 0 selects 0.45 / m, beta == 0 selects 6.  FVAD_ERR_INVALID_ARGUMENT for a ratio that is none, 2 half m + 1 >
+ *   FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1, the default design at the largest up), a cutoff not in (0, 0.5] (0 apart), a
+ *   negative or non-finite beta, or NULL.  The default design, computed from these taps in float64 (tools/resample_response.py):
+ *     ratios 160/147, 320/147, 640/147: pass-band ripple up to 0.40/m 0.11 dB, stop band from 0.60/m -69.8 dB (160/147: -69.9),
+ *                                       33 taps a phase, the phases' DC gains within 2.8e-4 of each other
+ *     ratios 3/1, 3/2:                  0.11 dB, -72.1 dB, 33 taps a phase, 2.3e-4
+ *     ratio 6/1:                        0.11 dB, -70.8 dB, 33 taps a phase, 2.6e-4
+ *     ratios 2/1, 1/2:                  0.11 dB, -74.1 dB, 33 taps a phase (1/2: 65, one phase), 2.1e-4
+ * fvad_resample_window: the input frames [*frame_lo, *frame_hi) that outputs [out_from, out_from + n_out) read, clipped to the
+ *   file; an empty window (n_out == 0, a phase without taps) has *frame_lo == *frame_hi.
+ * fvad_ingest_resample_tile: the kernel's outputs of one channel per tile for frames of n_channels samples of `format`; 0 when
+ *   the window of 4 outputs does not fit the 64 KB of LDS a tile stages (such a source is refused).
+ * fvad_ingest_resample_check: every argument rule of the two calls below, in this order: FVAD_ERR_INVALID_ARGUMENT for an
+ *   out_format other than FVAD_INGEST_F32, a ratio that is none, taps that fail (NULL, an even or zero count, more than
+ *   FVAD_RESAMPLE_TAPS_MAX, a non-finite tap); n_sources == 0 succeeds here; NULL sources, lane_stride < n_samples with several
+ *   lanes; then per source FVAD_ERR_INVALID_ARGUMENT for a bad format, n_channels outside 1 .. 64, file_frames * up >= 2^62,
+ *   out_from + n_out > out_frames(file_frames), fill_to < dst_offset + n_out, given frames that leave the file, given frames
+ *   that do not cover fvad_resample_window of the row, a tile of 0; then per source FVAD_ERR_OUT_OF_RANGE for lanes past
+ *   n_lanes, fill_to > n_samples, byte_offset + bytes > raw_bytes; then FVAD_ERR_INVALID_ARGUMENT for overlapping destinations
+ *   (fvad_ingest_check's rule).  A source with n_out == 0 only fills.
+ * fvad_ingest_resample_device / fvad_ingest_resample: fvad_ingest_device's and fvad_ingest's forms.  Both run the check (and
+ *   refuse NULL pointers and lanes not aligned to 4 bytes) before any launch, return when the lanes are written and name
+ *   `ingest_resample` in fvad_ctx_kernel_times.  The host form cuts a source into batches of the context's ring in OUTPUT
+ *   coordinates and copies each batch's window (batches overlap by the filter's reach); a ring smaller than the window of 4
+ *   outputs is enlarged for the call. */
+#define FVAD_RESAMPLE_FIELDS 11
+#define FVAD_RESAMPLE_UP_MAX 640
+#define FVAD_RESAMPLE_TAPS_MAX 20481
+int fvad_resample_ratio(uint32_t rate_in, uint32_t rate_out, uint32_t *up, uint32_t *down);
+uint64_t fvad_resample_out_frames(uint64_t file_frames, uint32_t up, uint32_t down);
+int fvad_resample_design(uint32_t up, uint32_t down, uint32_t half, double cutoff, double beta, float *taps, uint32_t *n_taps);
+int fvad_resample_window(uint32_t up, uint32_t down, uint32_t n_taps, uint64_t file_frames, uint64_t out_from, uint64_t n_out,
+                         uint64_t *frame_lo, uint64_t *frame_hi);
+uint64_t fvad_ingest_resample_tile(uint32_t up, uint32_t down, uint32_t n_taps, uint32_t n_channels, uint32_t format);
+int fvad_ingest_resample_check(const uint64_t *sources, size_t n_sources, uint64_t raw_bytes, uint32_t up, uint32_t down,
+                               const float *taps, uint32_t n_taps, int out_format, size_t n_lanes, size_t lane_stride,
+                               size_t n_samples);
+int fvad_ingest_resample_device(fvad_ctx *ctx, const void *d_raw, uint64_t raw_bytes, const uint64_t *sources, size_t n_sources,
+                                uint32_t up, uint32_t down, const float *taps, uint32_t n_taps, void *d_lanes, size_t n_lanes,
+                                size_t lane_stride, size_t n_samples);
+int fvad_ingest_resample(fvad_ctx *ctx, const void *const *src_host, const uint64_t *sources, size_t n_sources, uint32_t up,
+                         uint32_t down, const float *taps, uint32_t n_taps, void *d_lanes, size_t n_lanes, size_t lane_stride,
+                         size_t n_samples);
+
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
 typedef struct {
