@@ -445,6 +445,15 @@ pub extern "c" fn fvad_wav_probe(path: [*:0]const u8, info: [*]u64) c_int;
 pub extern "c" fn fvad_ingest_check(sources: ?[*]const u64, n_sources: usize, raw_bytes: u64, out_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest_device(ctx: *Ctx, d_raw: ?*const anyopaque, raw_bytes: u64, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest(ctx: *Ctx, src_host: ?[*]const ?*const anyopaque, sources: ?[*]const u64, n_sources: usize, out_format: c_int, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+// with a resampler: clip i leaves as ceil(len * up / down) samples, y[o] = sum_n x[n] * taps[K + o * down - n * up], the clip zero-extended
+pub extern "c" fn fvad_clips_resample_check(up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_resample_tile(up: u32, down: u32, n_taps: u32) u64;
+pub extern "c" fn fvad_clips_plan_resampled(lens: ?[*]const u64, n_clips: usize, up: u32, down: u32, out_format: c_int, out_lens: ?[*]u64, offsets: ?[*]u64, total: *u64) c_int;
+pub extern "c" fn fvad_clips_export_resampled_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_resampled(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_split_resampled_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+pub extern "c" fn fvad_clips_export_split_resampled(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+
 // resampling ingest: files at another rate filtered and re-timed into 48 kHz f32 lanes (a rational up/down polyphase resampler)
 pub extern "c" fn fvad_resample_ratio(rate_in: u32, rate_out: u32, up: *u32, down: *u32) c_int;
 pub extern "c" fn fvad_resample_out_frames(file_frames: u64, up: u32, down: u32) u64;

@@ -364,6 +364,22 @@ SIGNATURES = {
     "fvad_clips_export_split_fir": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
                                               C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
                                               C.POINTER(C.c_uint32), c_float_p, C.c_uint32]),
+    "fvad_clips_resample_check": (C.c_int, [C.c_uint32, C.c_uint32, c_float_p, C.c_uint32]),
+    "fvad_clips_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "fvad_clips_plan_resampled": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_resampled_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                                     c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, c_float_p,
+                                                     C.c_uint32]),
+    "fvad_clips_export_resampled": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                              c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, c_float_p,
+                                              C.c_uint32]),
+    "fvad_clips_export_split_resampled_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                           C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                                           C.c_uint32, c_float_p, C.c_uint32]),
+    "fvad_clips_export_split_resampled": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                    C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
+                                                    C.c_uint32, c_float_p, C.c_uint32]),
     "fvad_wav_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
@@ -712,16 +728,21 @@ class Context:
                  "fvad_engine_band_sums_device")
 
     def clips_export(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, out_pcm16=False, d_out=None, out_capacity=None,
-                     step=1, skips=None, taps=None):
+                     step=1, skips=None, taps=None, up=None, down=None):
         """fvad_clips_export (d_out None: the packed clips come back as a numpy array of the output format) or
         fvad_clips_export_device (d_out: a device address with room for out_capacity samples).  clips: [n][CLIP_FIELDS] uint64.
         Returns dict(best_channel, best_rms, runner_up_rms, offsets, total[, out]).
         step != 1 or skips: fvad_clips_export_strided(_device) -- of clip i the samples skips[i], skips[i] + step, ... (skips None:
         all 0); the dict then has "out_lens" too.
         taps (an odd number of float32, at most CLIP_FIR_TAPS_MAX): fvad_clips_export_fir(_device) -- the same clips, skips and slots,
-        output q of a clip being sum_k taps[k] * x[skips[i] + q * step + k - (len(taps) - 1) / 2] over the zero-extended clip."""
+        output q of a clip being sum_k taps[k] * x[skips[i] + q * step + k - (len(taps) - 1) / 2] over the zero-extended clip.
+        up, down (with taps, an odd number of float32, at most RESAMPLE_TAPS_MAX; step 1 and no skips):
+        fvad_clips_export_resampled(_device) -- clip i leaves as ceil(len * up / down) samples at up / down of the lanes' rate."""
         clips = _clip_rows(clips)
         n = clips.shape[0]
+        if up is not None or down is not None:
+            return self._clips_export_resampled("fvad_clips_export_resampled", (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples),
+                                                clips, clips[:, 3] - clips[:, 2], out_pcm16, d_out, out_capacity, step, skips, taps, up, down)
         if step != 1 or skips is not None or taps is not None:
             return self._clips_export_strided("fvad_clips_export_fir" if taps is not None else "fvad_clips_export_strided", (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples),
                                               clips, clips[:, 3] - clips[:, 2], out_pcm16, d_out, out_capacity, step, skips, taps)
@@ -763,13 +784,39 @@ class Context:
         res["out"] = out[:total]
         return res
 
-    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None, step=1, skips=None, taps=None):
+    def _clips_export_resampled(self, name, src_args, clips, lens, out_pcm16, d_out, out_capacity, step, skips, taps, up, down):
+        """the four resampled calls: `name` (+ "_device" with d_out), src_args the arguments between ctx and the clips"""
+        if up is None or down is None or taps is None or step != 1 or skips is not None:
+            raise ValueError("a resampled clip export takes up, down and taps, and neither step nor skips")
+        n = clips.shape[0]
+        out_lens, offsets, total = clips_plan_resampled(lens, up, down, out_pcm16) if n else (np.zeros(0, np.uint64), None, 0)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        args = (self.h, *src_args, clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_PCM16 if out_pcm16 else CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                int(up), int(down), fptr(taps), taps.shape[0])
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "out_lens": out_lens}
+        if d_out is not None:
+            self._ck(getattr(lib(), name + "_device")(*args, vp(d_out), total if out_capacity is None else out_capacity, *info), name + "_device")
+            return res
+        out = np.zeros(max(total, 1), np.int16 if out_pcm16 else np.float32)
+        self._ck(getattr(lib(), name)(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info), name)
+        res["out"] = out[:total]
+        return res
+
+    def clips_export_split(self, a, b, src_pcm16, clips, out_pcm16=False, d_out=None, out_capacity=None, step=1, skips=None, taps=None,
+                           up=None, down=None):
         """fvad_clips_export_split (d_out None) or fvad_clips_export_split_device: a and b are the two source buffers as
         (device address or None, n_lanes, lane_stride, n_samples); clips: [n][CLIP_SPLIT_FIELDS] uint64, channel c of a clip
         being a[a_lane + c][a_from, a_from + a_len) followed by b[b_lane + c][b_from, b_from + b_len).  Returns what
-        clips_export does; step / skips / taps as there (fvad_clips_export_split_strided(_device), fvad_clips_export_split_fir(_device))."""
+        clips_export does; step / skips / taps / up / down as there (fvad_clips_export_split_strided(_device),
+        fvad_clips_export_split_fir(_device), fvad_clips_export_split_resampled(_device))."""
         clips = _clip_split_rows(clips)
         n = clips.shape[0]
+        if up is not None or down is not None:
+            return self._clips_export_resampled("fvad_clips_export_split_resampled", (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
+                                                CLIP_PCM16 if src_pcm16 else CLIP_F32), clips, clips[:, 3] + clips[:, 6], out_pcm16, d_out,
+                                                out_capacity, step, skips, taps, up, down)
         if step != 1 or skips is not None or taps is not None:
             return self._clips_export_strided("fvad_clips_export_split_fir" if taps is not None else "fvad_clips_export_split_strided", (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3],
                                               CLIP_PCM16 if src_pcm16 else CLIP_F32), clips, clips[:, 3] + clips[:, 6], out_pcm16, d_out,
@@ -1630,6 +1677,33 @@ def clips_plan_strided(lens, skips, step, out_pcm16=False):
                                         CLIP_PCM16 if out_pcm16 else CLIP_F32, out_lens.ctypes.data_as(C.POINTER(C.c_uint64)),
                                         offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_strided")
     return out_lens, offsets, int(total.value)
+
+
+def clips_plan_resampled(lens, up, down, out_pcm16=False):
+    """fvad_clips_plan_resampled: (out_lens [n] uint64 = ceil(len * up / down), offsets [n] uint64, total), in samples of the
+    output format"""
+    lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
+    n = lens.shape[0]
+    out_lens, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
+    check(lib().fvad_clips_plan_resampled(lens.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(up), int(down), CLIP_PCM16 if out_pcm16 else CLIP_F32,
+                                          out_lens.ctypes.data_as(C.POINTER(C.c_uint64)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          C.byref(total)), "fvad_clips_plan_resampled")
+    return out_lens, offsets, int(total.value)
+
+
+def clips_resample_check(up, down, taps):
+    """fvad_clips_resample_check -> status (0: up / down is a ratio, the taps are an odd number of finite values, at most
+    RESAMPLE_TAPS_MAX, and the window of 8 outputs fits a tile of the gather)"""
+    if taps is None:
+        return lib().fvad_clips_resample_check(int(up), int(down), None, 0)
+    taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+    return lib().fvad_clips_resample_check(int(up), int(down), fptr(taps), taps.shape[0])
+
+
+def clips_resample_tile(up, down, n_taps):
+    """fvad_clips_resample_tile: outputs per workgroup of the resampling clip gather (0: the window of 8 outputs does not fit, or
+    the ratio or the tap count is none)"""
+    return int(lib().fvad_clips_resample_tile(int(up), int(down), int(n_taps)))
 
 
 def clips_from_segments(segs, first_lane, n_channels, n_available, cap=None):

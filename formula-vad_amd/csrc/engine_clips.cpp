@@ -3,10 +3,13 @@
 // channel over [sample_from, sample_to) (Recorder.zig:74-164); here every clip of a call is picked and packed in three launches
 // and only the packed clips leave the device.  The strided forms (fvad_clips_export_strided*) are the same calls with the strided
 // rules and slots (clips_strided.h) and kernels_clips_strided.hip's gather over tiles of its own; the filtered forms
-// (fvad_clips_export_fir*) are the strided calls with the tap rules (clips_fir.h) and kernels_clips_fir.hip's gather.
+// (fvad_clips_export_fir*) are the strided calls with the tap rules (clips_fir.h) and kernels_clips_fir.hip's gather; the
+// resampled forms (fvad_clips_export_resampled*) are the full-rate calls with the ratio and tap rules and the slots of
+// clips_resample.h and kernels_clips_resample.hip's gather.
 #include <vector>
 
 #include "clips_fir.h"
+#include "clips_resample.h"
 #include "clips_strided.h"
 #include "internal.h"
 
@@ -14,6 +17,7 @@ using namespace fvad;
 
 static_assert(kStridedSrcTile == (uint64_t)kClipTile && FVAD_CLIP_STEP_MAX == kClipStepMax, "clips_strided.h counts the kernels' tiles");
 static_assert(kFirSrcTile == (uint64_t)kClipTile && FVAD_CLIP_FIR_TAPS_MAX == kClipFirTapsMax, "clips_fir.h counts the kernels' tiles");
+static_assert(kResampledWindow == (uint64_t)kClipTile, "clips_resample.h counts the kernels' window");
 
 namespace {
 
@@ -47,9 +51,10 @@ int plan_clips(const uint64_t* clips, size_t n, int out_format, uint64_t* offset
 // Every rule of fvad_clips_export(_device), in one order for both forms: arguments, then every clip's own rules, then its range
 // and lanes, then the capacity.  Fills offsets and total.  strided (may be NULL): the strided exports' rules directly after the
 // clips' own, and their slots in place of the full-rate ones.  fir (may be NULL, with strided only): the tap rules after those.
+// rs (may be NULL, without strided): the resampled exports' ratio and tap rules in the same place, and their slots.
 int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                  const uint64_t* clips, size_t n_clips, int out_format, const void* out, size_t out_capacity, bool device_out,
-                 std::vector<uint64_t>& offsets, uint64_t& total, const Strided* strided, const Fir* fir)
+                 std::vector<uint64_t>& offsets, uint64_t& total, const Strided* strided, const Fir* fir, const Resampled* rs)
 {
     if (!d_src || !clips || !out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: NULL argument");
     if (!format_ok(src_format) || !format_ok(out_format)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: unknown sample format");
@@ -72,6 +77,20 @@ int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t 
         }
         if (fir && !fir_taps_ok(*fir, &why)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_fir: ") + why);
     }
+    if (rs) {
+        const char* why = "";
+        if (!resampled_ok(*rs, &why)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_resampled: ") + why);
+        total = 0;
+        for (size_t i = 0; i < n_clips; ++i) {
+            const ClipRow c = row(clips, i);
+            uint64_t out_len;
+            offsets[i] = total;
+            if ((u128)(c.sample_to - c.sample_from) * rs->up >= (u128)kResampleFramesUp)
+                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_resampled: a clip of 2^62 / up samples or more");
+            if (!resampled_slot(Ratio{rs->up, rs->down}, c.sample_to - c.sample_from, 16 / format_bytes(out_format), &total, &out_len, &why))
+                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_resampled: ") + why);
+        }
+    }
     for (size_t i = 0; i < n_clips; ++i) {
         const ClipRow c = row(clips, i);
         if (c.sample_to > n_samples) return set_err(ctx, FVAD_ERR_OUT_OF_RANGE, "fvad_clips_export: a clip ends past n_samples");
@@ -84,10 +103,10 @@ int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t 
 
 int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                   const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
-                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir);
+                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs = nullptr);
 int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                 const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
-                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir);
+                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs = nullptr);
 
 } // namespace
 
@@ -181,25 +200,46 @@ int fvad_clips_export_fir(fvad_ctx* ctx, const void* d_src, int src_format, size
                        best_rms, runner_up_rms, out_offsets, &s, &f);
 }
 
+int fvad_clips_export_resampled_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                       size_t n_samples, const uint64_t* clips, size_t n_clips, int out_format, void* d_out,
+                                       size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                       uint64_t* out_offsets, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps)
+{
+    const Resampled r{up, down, taps, n_taps};
+    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
+                         best_channel, best_rms, runner_up_rms, out_offsets, nullptr, nullptr, &r);
+}
+
+int fvad_clips_export_resampled(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity,
+                                int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t up,
+                                uint32_t down, const float* taps, uint32_t n_taps)
+{
+    const Resampled r{up, down, taps, n_taps};
+    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
+                       best_rms, runner_up_rms, out_offsets, nullptr, nullptr, &r);
+}
+
 } // extern "C"
 
 namespace {
 
-// fvad_clips_export_device (strided NULL), fvad_clips_export_strided_device and fvad_clips_export_fir_device (fir not NULL)
+// fvad_clips_export_device (strided NULL), fvad_clips_export_strided_device, fvad_clips_export_fir_device (fir not NULL) and
+// fvad_clips_export_resampled_device (rs not NULL, strided NULL)
 int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                   const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
-                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir)
+                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
     const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                                 true, offsets, total, strided, fir);
+                                 true, offsets, total, strided, fir, rs);
     if (bad != FVAD_OK) return bad;
     // a step of 1 keeps every sample: the full-rate gather, whose tiles are the strided gather's
     const uint32_t step = strided ? strided->step : 1;
-    const uint64_t tile_out = fir ? clip_fir_tile_out(step, fir->n_taps) : clip_tile_out(step);
+    const uint64_t tile_out = rs ? resampled_tile_out(Ratio{rs->up, rs->down}, rs->n_taps) : fir ? clip_fir_tile_out(step, fir->n_taps) : clip_tile_out(step);
     // the tables: one job per clip and the two prefix tables the workgroups search
     std::vector<ClipJob> jobs(n_clips);
     std::vector<uint32_t> unit_prefix(n_clips + 1), tile_prefix(n_clips + 1);
@@ -209,7 +249,7 @@ int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lan
         const uint64_t len = c.sample_to - c.sample_from;
         const uint64_t nt = (len + kClipTile - 1) / kClipTile;
         const uint32_t skip = strided && strided->skips ? strided->skips[i] : 0;
-        const uint64_t out_len = (len - skip + step - 1) / step;
+        const uint64_t out_len = rs ? resample_out_frames(len, Ratio{rs->up, rs->down}) : (len - skip + step - 1) / step;
         unit_prefix[i] = (uint32_t)units;
         tile_prefix[i] = (uint32_t)tiles;
         ClipJob& j = jobs[i];
@@ -232,8 +272,9 @@ int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lan
     auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
     const size_t o_jobs = 0, o_up = o_jobs + up16(n_clips * sizeof(ClipJob)), o_tp = o_up + up16((n_clips + 1) * 4),
                  o_part = o_tp + up16((n_clips + 1) * 4), o_info = o_part + up16(units * sizeof(double)),
-                 o_taps = o_info + up16(n_clips * sizeof(ClipInfo)), bytes = o_taps + up16(fir ? fir->n_taps * sizeof(float) : 0);
-    const std::vector<float> taps = fir ? fir_branches(*fir, step) : std::vector<float>();
+                 o_taps = o_info + up16(n_clips * sizeof(ClipInfo)), bytes = o_taps + up16(rs ? (size_t)resample_phase_taps(rs->up, rs->n_taps) * rs->up * sizeof(float) : fir ? fir->n_taps * sizeof(float) : 0);
+    // the taps as the gather walks them: branch by branch (fir) or [j][o mod up] (resampled)
+    const std::vector<float> taps = rs ? resample_table(Taps{rs->taps, rs->n_taps}, Ratio{rs->up, rs->down}) : fir ? fir_branches(*fir, step) : std::vector<float>();
     char* d = nullptr;
     if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export: hipMalloc of the clip tables failed"); }
     std::vector<ClipInfo> infos(n_clips);
@@ -241,7 +282,7 @@ int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lan
         FVAD_HIP(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), n_clips * sizeof(ClipJob), hipMemcpyHostToDevice, ctx->stream));
         FVAD_HIP(ctx, hipMemcpyAsync(d + o_up, unit_prefix.data(), (n_clips + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
         FVAD_HIP(ctx, hipMemcpyAsync(d + o_tp, tile_prefix.data(), (n_clips + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (fir) FVAD_HIP(ctx, hipMemcpyAsync(d + o_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if (fir || rs) FVAD_HIP(ctx, hipMemcpyAsync(d + o_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         ClipArgs a{};
         a.src = d_src;
         a.out = d_out;
@@ -262,7 +303,10 @@ int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lan
         time_begin(ctx, "clip_pick");
         FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_pick(a, ctx->stream));
         time_end(ctx);
-        if (fir) {
+        if (rs) {
+            time_begin(ctx, "clip_gather_resampled");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_resampled(ClipResampleArgs{a, reinterpret_cast<const float*>(d + o_taps), rs->up, rs->down, (uint32_t)tile_out, rs->n_taps}, ctx->stream));
+        } else if (fir) {
             time_begin(ctx, "clip_gather_fir");
             FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_fir(ClipFirArgs{a, reinterpret_cast<const float*>(d + o_taps), step, (uint32_t)tile_out, fir->n_taps, 0}, ctx->stream));
         } else if (step == 1) {
@@ -290,17 +334,18 @@ int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lan
     return FVAD_OK;
 }
 
-// fvad_clips_export (strided NULL), fvad_clips_export_strided and fvad_clips_export_fir (fir not NULL)
+// fvad_clips_export (strided NULL), fvad_clips_export_strided, fvad_clips_export_fir (fir not NULL) and
+// fvad_clips_export_resampled (rs not NULL, strided NULL)
 int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                 const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
-                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir)
+                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets;
     uint64_t total = 0;
     const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity,
-                                 false, offsets, total, strided, fir);
+                                 false, offsets, total, strided, fir, rs);
     if (bad != FVAD_OK) return bad;
     // a device staging buffer of the plan's size, one copy back, then freed (hipMalloc returns 256-byte aligned memory)
     hipSetDevice(ctx->device);
@@ -310,7 +355,7 @@ int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes
     // the padding between slots is never written by the kernels: zero it, so that the host gets no stale device memory
     hipError_t e = hipMemsetAsync(d_out, 0, bytes, ctx->stream);
     int rc = e == hipSuccess ? export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out,
-                                             (size_t)total, best_channel, best_rms, runner_up_rms, out_offsets, strided, fir)
+                                             (size_t)total, best_channel, best_rms, runner_up_rms, out_offsets, strided, fir, rs)
                              : hip_fail(ctx, e, "fvad_clips_export: hipMemsetAsync");
     if (rc == FVAD_OK) {
         e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);

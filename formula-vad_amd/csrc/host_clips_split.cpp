@@ -2,6 +2,7 @@
 // forms report them in, without a device (plain C++: tests/sanitize/clips_split_san.cpp builds this file alone).  Pointers are
 // addresses here; nothing is read through d_a, d_b or out.
 #include "clips_fir.h"
+#include "clips_resample.h"
 #include "clips_split.h"
 #include "clips_strided.h"
 
@@ -38,7 +39,7 @@ namespace fvad {
 int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
                       size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
                       const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why,
-                      const Strided* strided, const Fir* fir)
+                      const Strided* strided, const Fir* fir, const Resampled* rs)
 {
     const char* dummy;
     if (!why) why = &dummy;
@@ -81,6 +82,18 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
         }
         if (fir && !fir_taps_ok(*fir, why)) return FVAD_ERR_INVALID_ARGUMENT;
     }
+    if (rs) { // a resampled export: its ratio and taps, and its slots in place of the full-rate ones
+        if (!resampled_ok(*rs, why)) return FVAD_ERR_INVALID_ARGUMENT;
+        at = 0;
+        for (size_t i = 0; i < n_clips; ++i) {
+            const SplitRow r = split_row(clips, i);
+            const uint64_t slot = at;
+            uint64_t out_len;
+            if ((u128)(r.a_len + r.b_len) * rs->up >= (u128)kResampleFramesUp) { *why = "a clip of 2^62 / up samples or more"; return FVAD_ERR_INVALID_ARGUMENT; }
+            if (!resampled_slot(Ratio{rs->up, rs->down}, r.a_len + r.b_len, per16, &at, &out_len, why)) return FVAD_ERR_INVALID_ARGUMENT;
+            if (offsets) offsets[i] = slot;
+        }
+    }
     if (total) *total = at;
     // ranges and lanes
     for (size_t i = 0; i < n_clips; ++i) {
@@ -108,6 +121,13 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
             *why = "more than 2^31 tiles in one call: export in batches";
             return FVAD_ERR_INVALID_ARGUMENT;
         }
+        if (rs) {
+            const uint64_t to = resampled_tile_out(Ratio{rs->up, rs->down}, rs->n_taps), n = resample_out_frames(len, Ratio{rs->up, rs->down});
+            if (__builtin_add_overflow(gather, n / to + (n % to != 0), &gather) || gather > 0x7fffffffull) {
+                *why = "more than 2^31 tiles in one call: export in batches";
+                return FVAD_ERR_INVALID_ARGUMENT;
+            }
+        }
         if (strided) {
             const uint64_t to = fir ? fir_tile_out(strided->step, fir->n_taps) : strided_tile_out(strided->step), n = (len - (strided->skips ? strided->skips[i] : 0) + strided->step - 1) / strided->step;
             if (__builtin_add_overflow(gather, n / to + (n % to != 0), &gather) || gather > 0x7fffffffull) {
@@ -127,5 +147,5 @@ extern "C" int fvad_clips_split_check(const void* d_a, size_t a_lanes, size_t a_
                                       uint64_t* offsets, uint64_t* total)
 {
     return fvad::clips_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
-                                   out_format, out, out_capacity, device_out, offsets, total, nullptr, nullptr, nullptr);
+                                   out_format, out, out_capacity, device_out, offsets, total, nullptr, nullptr, nullptr, nullptr);
 }

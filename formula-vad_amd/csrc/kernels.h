@@ -499,6 +499,24 @@ struct ClipSplitFirArgs {
 int fvad_launch_clip_gather_fir(const ClipFirArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
 int fvad_launch_clip_gather_fir_split(const ClipSplitFirArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
 
+// The resampling gathers (kernels_clips_resample.hip, fvad_clips_export*_resampled): output o of a clip is the polyphase sum
+// sum_j table[j * up + o mod up] * x[q - j], q = (K + o * down) / up, over the picked channel's samples, the clip zero-extended;
+// out_len = ceil(len * up / down).  Tiles are counted in OUTPUT samples from the clip's first output (tile_out of them, a
+// multiple of 8: resampled_tile_out of clips_resample.h); a tile's window of at most kClipTile clip samples is staged once.
+constexpr uint32_t kClipResampleTableLds = 6144; // table entries (24 KB) that are kept in LDS beside the window; a longer table stays in global memory
+struct ClipResampleArgs {
+    ClipArgs c;
+    const float* table;  // [ceil(n_taps / up) * up] (device): resample_table of resample.h
+    uint32_t up, down, tile_out, n_taps;
+};
+struct ClipSplitResampleArgs {
+    ClipSplitArgs s;
+    const float* table;
+    uint32_t up, down, tile_out, n_taps;
+};
+int fvad_launch_clip_gather_resampled(const ClipResampleArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_resampled_split(const ClipSplitResampleArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
+
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
 // multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane

@@ -473,7 +473,24 @@ CLIP_PHASE = {"denoised": 2, "original": 0}        # the lane indices (mod 3) ke
 
 
 CLIP_FIR_RATES = {24000: 2, 16000: 3, 8000: 6}     # a filtered kind's rate -> the export's step (48000 would leave the filter nothing to do)
-CLIP_FILTERS = ("none", "fir")
+CLIP_FILTERS = ("none", "fir", "resample")
+
+
+def _clip_resample(kind, rate):
+    """the filter of a kind exported through the resampling gather at `rate`: up/down = rate/48000 in lowest terms and
+    fvad_resample_design's default taps, its parameters spelt out for the manifest; ValueError for a rate that has none"""
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate <= 0 or rate == 48000 or rate >= 1 << 32:
+        raise ValueError(f"run_clips: {kind}_rate {rate!r} with {kind}_filter 'resample' is no rate other than 48000")
+    try:
+        up, down = fv.resample_ratio(48000, int(rate))
+        taps = fv.resample_design(up, down)
+    except fv.FvadError:
+        raise ValueError(f"run_clips: {kind}_rate {rate!r} with {kind}_filter 'resample': no ratio to 48000 with up <= {fv.RESAMPLE_UP_MAX} "
+                         f"whose default design fits {fv.RESAMPLE_TAPS_MAX} taps") from None
+    if fv.clips_resample_check(up, down, taps) != 0:
+        raise ValueError(f"run_clips: {kind}_rate {rate!r} with {kind}_filter 'resample': the filter's window fits no tile of the gather")
+    m = max(up, down)
+    return {"up": up, "down": down, "half": 16, "cutoff": 0.45 / m, "beta": 6.0, "taps": taps}
 
 
 def _clip_rates(original_rate, denoised_rate, original_filter="none", denoised_filter="none"):
@@ -482,11 +499,14 @@ def _clip_rates(original_rate, denoised_rate, original_filter="none", denoised_f
     for kind, filt in (("original", original_filter), ("denoised", denoised_filter)):
         rate = rates[kind]
         if filt not in CLIP_FILTERS:
-            raise ValueError(f"run_clips: {kind}_filter {filt!r} is neither 'none' nor 'fir'")
+            raise ValueError(f"run_clips: {kind}_filter {filt!r} is none of 'none', 'fir' and 'resample'")
         if filt == "none":
             if rate not in CLIP_RATES:
                 raise ValueError(f"run_clips: {kind}_rate {rate!r} is neither 48000 nor 16000")
             firs[kind] = None
+            continue
+        if filt == "resample":
+            firs[kind] = _clip_resample(kind, rate)
             continue
         if rate not in CLIP_FIR_RATES:
             raise ValueError(f"run_clips: {kind}_rate {rate!r} with {kind}_filter 'fir' is none of 24000, 16000 and 8000")
@@ -498,12 +518,24 @@ def _clip_rates(original_rate, denoised_rate, original_filter="none", denoised_f
 
 def _clip_skips(kind, rate, sample_from, fir=None):
     """(step, skips or None, taps or None) of one export of `kind` clips starting at the absolute lane indices sample_from.  At
-    step 3 a filtered kind keeps the lane indices an unfiltered run keeps (first_sample agrees); at steps 2 and 6 phase 0"""
+    step 3 a filtered kind keeps the lane indices an unfiltered run keeps (first_sample agrees); at steps 2 and 6 phase 0.  A
+    resampled kind has neither step nor skips: its phase starts at the clip (_clip_export_args adds up and down)"""
+    if fir is not None and "up" in fir:
+        return 1, None, fir["taps"]
     if fir is None:
         step = CLIP_RATES[rate]
         return (1, None, None) if step == 1 else (step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind]), None)
     step = fir["step"]
     return step, fv.clips_phase_skips(sample_from, step, CLIP_PHASE[kind] if step == 3 else 0), fir["taps"]
+
+
+def _clip_export_args(kind, rate, sample_from, fir):
+    """-> (the keyword arguments of one clips_export / clips_export_split of `kind`, skips or None, whether the result has out_lens)"""
+    step, skips, taps = _clip_skips(kind, rate, sample_from, fir)
+    kw = dict(step=step, skips=skips, taps=taps)
+    if fir is not None and "up" in fir:
+        kw.update(up=fir["up"], down=fir["down"])
+    return kw, skips, step != 1 or "up" in kw
 
 
 def _write_clip(path, samples, pcm16, rate):
@@ -515,7 +547,10 @@ def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample,
     e = {"file": os.path.basename(path), "best_channel": int(best_channel), "best_rms": float(best_rms), "runner_up_rms": float(runner_up_rms)}
     if rate != 48000:
         e.update(sample_rate=rate, first_sample=int(first_sample), length=int(length))
-    if fir is not None:
+    if fir is not None and "up" in fir:
+        e["filter"] = {"design": "kaiser_sinc_polyphase", "up": fir["up"], "down": fir["down"], "half": fir["half"], "cutoff": fir["cutoff"],
+                       "beta": fir["beta"], "taps": int(len(fir["taps"]))}
+    elif fir is not None:
         e["filter"] = {"design": "kaiser_sinc", "half": fir["half"], "cutoff": fir["cutoff"], "beta": fir["beta"], "taps": int(len(fir["taps"]))}
     return e
 
@@ -566,9 +601,9 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs):
             rows = np.concatenate(rows) if rows else np.zeros((0, fv.CLIP_FIELDS), np.uint64)
             if not rows.shape[0]:
                 continue
-            step, skips, taps = _clip_skips(kind, rates[kind], rows[:, 2], firs[kind])
-            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16, step=step, skips=skips, taps=taps)
-            lens = res["out_lens"] if step != 1 else rows[:, 3] - rows[:, 2]
+            kw, skips, has_lens = _clip_export_args(kind, rates[kind], rows[:, 2], firs[kind])
+            res = ctx.clips_export(d_src, False, r.n_lanes, stride, n_samples, rows, out_pcm16=pcm16, **kw)
+            lens = res["out_lens"] if has_lens else rows[:, 3] - rows[:, 2]
             for j, (i, k) in enumerate(owner):
                 o, n = int(res["offsets"][j]), int(lens[j])
                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], k, kind))
@@ -616,7 +651,13 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     file is what filtering and decimating the 48000 file with the same taps gives, and a sliced run holds no more audio than
     before.  The pick and both RMS values are still taken over every unfiltered sample.  At 16000 the kept lane indices, hence
     "first_sample" and "length", are those of the unfiltered run; at 24000 and 8000 they are the indices = 0 (mod step).  A
-    filtered kind's manifest entries gain "filter": {"design": "kaiser_sinc", "half", "cutoff", "beta", "taps"}."""
+    filtered kind's manifest entries gain "filter": {"design": "kaiser_sinc", "half", "cutoff", "beta", "taps"}.
+    With "resample" that kind's clips leave at any other rate R: fvad_clips_export*_resampled at up/down = R/48000 in lowest terms
+    with fvad_resample_design's default taps (K = 16 max(up, down), cutoff 0.45 / max(up, down), beta 6).  R is any rate but 48000
+    whose ratio has up <= 640 and whose default design fits 20481 taps -- 44100, 32000, 22050 and 11025; 24000, 16000 and 8000
+    too --, anything else raises before any work.  Output o of a clip sits o / R seconds after the clip's first sample: the phase
+    starts at the clip, so "first_sample" is the segment's own start and "length" is ceil(len * up / down).  The manifest entries
+    gain "filter": {"design": "kaiser_sinc_polyphase", "up", "down", "half", "cutoff", "beta", "taps"}."""
     _check_ingest(ingest)
     rates, firs = _clip_rates(original_rate, denoised_rate, original_filter, denoised_filter)
     plan = load_plan(plan_path)
@@ -807,9 +848,9 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
                             pending[kind][k] = still
                             need += [a0 for _, a0, _ in still] + ([] if holds[k] is None else [holds[k]])
                         if rows:
-                            step, skips, taps = _clip_skips(kind, rates[kind], [a0 for _, _, a0 in owner], firs[kind])
-                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16, step=step, skips=skips, taps=taps)
-                            lens = res["out_lens"] if step != 1 else [r[3] + r[6] for r in rows]
+                            kw, skips, has_lens = _clip_export_args(kind, rates[kind], [a0 for _, _, a0 in owner], firs[kind])
+                            res = ctx.clips_export_split(t.a(), b, False, rows, out_pcm16=pcm16, **kw)
+                            lens = res["out_lens"] if has_lens else [r[3] + r[6] for r in rows]
                             for q, ((i, j, a0), o) in enumerate(zip(owner, res["offsets"])):
                                 o, n_clip = int(o), int(lens[q])
                                 path = os.path.join(out_dir, "{}-{:04d}-{}.wav".format(insts[i]["name"], j, kind))
@@ -2128,9 +2169,12 @@ def arg_parser():
                          "(every third sample, no anti-alias filter: it aliases)")
     ap.add_argument("--clips-original-filter", default="none", choices=CLIP_FILTERS,
                     help="with --export-clips: fir -- the original clips are low-pass filtered while they are decimated (a Kaiser-windowed "
-                         "sinc of 32 step + 1 taps on the GPU); --clips-original-rate may then be 24000, 16000 or 8000")
+                         "sinc of 32 step + 1 taps on the GPU); --clips-original-rate may then be 24000, 16000 or 8000.  resample -- the "
+                         "clips are resampled on the GPU (a polyphase Kaiser-windowed sinc): --clips-original-rate may then be any other "
+                         "rate whose ratio to 48000 has up <= 640, such as 44100, 32000, 22050 or 11025")
     ap.add_argument("--clips-denoised-filter", default="none", choices=CLIP_FILTERS,
-                    help="with --export-clips: fir -- the same for the denoised clips (at 16000 they need no filter: use it for 24000 or 8000)")
+                    help="with --export-clips: fir -- the same for the denoised clips (at 16000 they need no filter: use it for 24000 or 8000); "
+                         "resample -- the same for the denoised clips")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")

@@ -981,6 +981,88 @@ int fvad_clips_export_split_fir(fvad_ctx *ctx, const void *d_a, size_t a_lanes, 
                                 int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
                                 uint32_t step, const uint32_t *skips, const float *taps, uint32_t n_taps);
 
+/* ------------------------------------------------------------------ batch Recorder with a resampler: clips at any rate
+ * The strided and filtered exports leave at whole fractions of the lanes' 48 kHz.  A resampled export is a full-rate export
+ * plus `uint32_t up, uint32_t down, const float *taps, uint32_t n_taps` (taps in host memory): a rational up/down polyphase
+ * resampler applied while the clip is gathered (csrc/kernels_clips_resample.hip), the resampling ingest's arithmetic (below) on
+ * the way out.
+ * THE DEFINITION
+ * - up/down = rate_out/48000 in lowest terms, as fvad_resample_ratio(48000, rate_out, ...) gives it: 44100 is 147/160, 32000
+ *   2/3, 22050 147/320, 11025 147/640, 16000 1/3, 96000 2/1.  1 <= up <= FVAD_RESAMPLE_UP_MAX, down >= 1.
+ * - n_taps is odd and <= FVAD_RESAMPLE_TAPS_MAX, the centre K = (n_taps - 1) / 2; the taps need not be symmetric.  One ratio and
+ *   one set of taps per call.
+ * - Clip, pick and the per-clip reports are exactly the full-rate export's: RMS and pick run over every sample of the
+ *   UNRESAMPLED clip, and best_channel, best_rms and runner_up_rms are the full-rate export's bits.
+ * - For a clip of len samples of its picked channel, x[0 .. len) is the clip as f32 (PCM16: s / 32768, exact) and x is 0 outside
+ *   [0, len).  out_len = ceil(len * up / down) = fvad_resample_out_frames(len, up, down), and
+ *       y[o] = sum over n of x[n] * taps[K + o * down - n * up],   over every n whose tap index lies in [0, 2 K],
+ *   accumulated in f32 and converted by fvad_clips_export's rule for an f32 source (f32: as it is; PCM16:
+ *   rint(clamp(y * 32768, -32768, 32767))).  Output o sits o / rate_out seconds after the clip's first sample: the phase is
+ *   counted from the CLIP's start, never from the lane index or the seam of a split clip.
+ * - The clip is filtered as a finite signal: nothing outside [sample_from, sample_to) is read.  So a file is what resampling
+ *   the exported 48 kHz clip on the host with the same taps gives, and a sliced run holds no more audio than
+ *   fvad_vad_batch_hold_from keeps.
+ * - Index arithmetic is 64-bit (o * down passes 2^32 in a 29 M-sample clip at down = 640); len * up must stay below 2^62.
+ * - Slots are 16-byte aligned, in clip order, sized by out_len (fvad_clips_plan_resampled plans them).
+ * - INVARIANTS, all bit for bit.  An output's bits do not depend on the call form (contiguous or split, device or host output),
+ *   on where the seam of a split clip lies, on which tile of the gather the output falls in, or on the other clips of the call
+ *   and their order.  The PCM16 output is the f32 output of the same call converted by the rule above.  A PCM16 source gives the
+ *   bits of an f32 source that holds s / 32768.  (Every output is one f32 fma chain from +0 in an order that depends on up,
+ *   down, n_taps and o mod up alone; the order itself is not part of the contract, and bit equality with the filtered export
+ *   at up == 1 is not promised.  up == down == 1 with the single tap 1.0 gives the full-rate export's bits, a -0.0 sample
+ *   apart, which leaves as +0.0.)
+ * - The default taps are fvad_resample_design(up, down, 0, 0, 0, ...): with m = max(up, down), K = 16 m, cutoff 0.45 / m,
+ *   beta 6, sum up; 5121 taps at 147/160 and FVAD_RESAMPLE_TAPS_MAX at 147/640.  Computed from these taps in float64
+ *   (tools/resample_response.py; the prototype's shape depends on m alone, so ripple and stop band are the ingest's at the
+ *   mirrored ratio; the phases are others):
+ *     ratio 147/160 (44100): pass-band ripple up to 0.40/m 0.11 dB, stop band from 0.60/m -69.9 dB,  35 taps a phase, the phases'
+ *                            DC gains within 3.4e-4 of each other
+ *     ratio 147/320 (22050): 0.11 dB, -69.8 dB,  70 taps a phase, 1.4e-4
+ *     ratio 147/640 (11025): 0.11 dB, -69.8 dB, 140 taps a phase, 6.5e-5
+ *     ratio 2/3 (32000):     0.11 dB, -72.1 dB,  49 taps a phase, 1.7e-4
+ *     ratio 1/3 (16000):     0.11 dB, -72.1 dB,  97 taps, one phase
+ *
+ * Host only (csrc/host_clips_resample.cpp):
+ * fvad_clips_resample_check: FVAD_ERR_INVALID_ARGUMENT for a ratio that is none (up == 0, up > FVAD_RESAMPLE_UP_MAX,
+ *   down == 0); then for taps that fail fvad_ingest_resample_check's tap rules (NULL, a zero or even count, more than
+ *   FVAD_RESAMPLE_TAPS_MAX, a non-finite tap); then for a tile of 0.
+ * fvad_clips_resample_tile: the gather's outputs per tile, the most (a multiple of 8, at most 8192) whose window
+ *   floor(((n - 1) down + 2 K) / up) + 1 fits the 8192 clip samples a tile stages; 0 when not even 8 outputs' window fits (such
+ *   a call is refused), for a ratio that is none or a tap count that is none.
+ * fvad_clips_plan_resampled: out_lens[i] = ceil(lens[i] * up / down), the slots' offsets and their total in samples of
+ *   out_format, as fvad_clips_plan_strided plans its own.  FVAD_ERR_INVALID_ARGUMENT for a ratio that is none, a clip of length
+ *   0, a bad format, NULL, or a total (an out_len that saturates at UINT64_MAX included) that does not fit 64 bits.
+ * fvad_clips_export_resampled_device / fvad_clips_export_resampled / fvad_clips_export_split_resampled_device /
+ * fvad_clips_export_split_resampled: the matching full-rate call's arguments, then up, down, taps and n_taps.  Every error
+ *   comes back before any launch, in the full-rate call's order; fvad_clips_resample_check's rules, then a clip with
+ *   len * up >= 2^62 or a total past 64 bits, are reported directly after the rows' own rules, before ranges and lanes.
+ *   out_capacity is checked against the resampled total and out_offsets are the resampled slots; more than 2^31 - 1 (clip, tile)
+ *   units in one call is FVAD_ERR_INVALID_ARGUMENT.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_gather_resampled
+ *   (split: clip_rms_split, clip_pick, clip_gather_resampled_split). */
+int fvad_clips_resample_check(uint32_t up, uint32_t down, const float *taps, uint32_t n_taps);
+uint64_t fvad_clips_resample_tile(uint32_t up, uint32_t down, uint32_t n_taps);
+int fvad_clips_plan_resampled(const uint64_t *lens, size_t n_clips, uint32_t up, uint32_t down, int out_format,
+                              uint64_t *out_lens, uint64_t *offsets, uint64_t *total);
+int fvad_clips_export_resampled_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                       size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                       size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                       uint64_t *out_offsets, uint32_t up, uint32_t down, const float *taps, uint32_t n_taps);
+int fvad_clips_export_resampled(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *out,
+                                size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                uint64_t *out_offsets, uint32_t up, uint32_t down, const float *taps, uint32_t n_taps);
+int fvad_clips_export_split_resampled_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                             const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                             const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                             size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                             uint64_t *out_offsets, uint32_t up, uint32_t down, const float *taps,
+                                             uint32_t n_taps);
+int fvad_clips_export_split_resampled(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                      const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                      const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                                      int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
+                                      uint32_t up, uint32_t down, const float *taps, uint32_t n_taps);
+
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
  * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
