@@ -24,6 +24,8 @@ const std = @import("std");
 pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
+pub const egress_fields = 6; // FVAD_EGRESS_FIELDS: a sink is a row of byte_offset, n_frames, n_channels, format, first_lane, src_offset (u64 each)
+pub const wav_header_bytes = 44; // FVAD_WAV_HEADER_BYTES
 pub const resample_fields = 11; // FVAD_RESAMPLE_FIELDS: ingest_fields' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
 pub const resample_up_max = 640; // FVAD_RESAMPLE_UP_MAX
 pub const resample_taps_max = 20481; // FVAD_RESAMPLE_TAPS_MAX
@@ -463,6 +465,12 @@ pub extern "c" fn fvad_ingest_resample_tile(up: u32, down: u32, n_taps: u32, n_c
 pub extern "c" fn fvad_ingest_resample_check(sources: ?[*]const u64, n_sources: usize, raw_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, out_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest_resample_device(ctx: *Ctx, d_raw: ?*const anyopaque, raw_bytes: u64, sources: ?[*]const u64, n_sources: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_ingest_resample(ctx: *Ctx, src_host: ?[*]const ?*const anyopaque, sources: ?[*]const u64, n_sources: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_lanes: ?*anyopaque, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+
+// device-side egress: planar device lanes converted to a file's sample format and interleaved into the bytes of its data chunk
+pub extern "c" fn fvad_wav_header(format: c_int, n_channels: u32, sample_rate: u32, n_frames: u64, out: ?[*]u8, cap: usize, n_bytes: ?*usize) c_int;
+pub extern "c" fn fvad_egress_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_egress_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, d_out: ?*anyopaque, out_bytes: u64) c_int;
+pub extern "c" fn fvad_egress(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, dst_host: ?[*]const ?*anyopaque) c_int;
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;

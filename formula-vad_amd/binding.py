@@ -37,6 +37,8 @@ INGEST_TILE_BYTES = 16384        # kIngestTileBytes (csrc/kernels.h): the source
 RESAMPLE_FIELDS = 11             # a resample source: INGEST_FIELDS' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
 RESAMPLE_UP_MAX = 640            # FVAD_RESAMPLE_UP_MAX
 RESAMPLE_TAPS_MAX = 20481        # FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1)
+EGRESS_FIELDS = 6                # a sink: byte_offset, n_frames, n_channels, format (the file's), first_lane, src_offset (uint64 each)
+WAV_HEADER_BYTES = 44            # FVAD_WAV_HEADER_BYTES: fvad_wav_header's canonical header
 INGEST_FILL_TILE = 8192          # kIngestFillTile: the zeros of one lane a workgroup writes
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
 
@@ -384,6 +386,10 @@ SIGNATURES = {
     "fvad_ingest_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_ingest_device": (C.c_int, [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
     "fvad_ingest": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, sz, sz]),
+    "fvad_wav_header": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp, sz, C.POINTER(sz)]),
+    "fvad_egress_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
+    "fvad_egress_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, vp, C.c_uint64]),
+    "fvad_egress": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.POINTER(vp)]),
     "fvad_resample_ratio": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fvad_resample_out_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "fvad_resample_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p, C.POINTER(C.c_uint32)]),
@@ -892,6 +898,35 @@ class Context:
             self._ck(lib().fvad_ingest_resample(self.h, ptrs, rows, n, *tail), "fvad_ingest_resample")
             return
         self._ck(lib().fvad_ingest_resample_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, *tail), "fvad_ingest_resample_device")
+
+    def egress(self, sinks, src_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, out=None, out_bytes=None):
+        """fvad_egress_device (out: a device address holding out_bytes bytes) or fvad_egress (out: a list with one writable
+        C-contiguous numpy / memmap byte buffer per sink, or None for a sink without frames; a sink's byte_offset is relative to
+        its own buffer): sinks [n][EGRESS_FIELDS] uint64 <- the planar lanes at device address d_lanes (float32, or int16 with
+        src_pcm16), n_lanes of n_samples, lane_stride apart, converted to each sink's file format and interleaved.  Returns
+        when the bytes are written."""
+        sinks = _egress_rows(sinks)
+        n = sinks.shape[0]
+        fmt = INGEST_PCM16 if src_pcm16 else INGEST_F32
+        rows = sinks.ctypes.data_as(C.POINTER(C.c_uint64))
+        if isinstance(out, (list, tuple)):
+            if len(out) != n:
+                raise ValueError(f"egress: {n} sinks, {len(out)} buffers")
+            ptrs = (vp * max(n, 1))()
+            for i, b in enumerate(out):
+                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no frames: no byte is written, whatever byte_offset says
+                    ptrs[i] = None
+                    continue
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
+                    raise ValueError("egress: a sink's bytes are a writable C-contiguous uint8 array")
+                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
+                if need > b.size:   # (the library cannot know where a host buffer ends)
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress", f"sink {i} writes {need} bytes of a buffer of {b.size}")
+                ptrs[i] = b.ctypes.data
+            self._ck(lib().fvad_egress(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, ptrs), "fvad_egress")
+            return
+        self._ck(lib().fvad_egress_device(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, vp(out), int(out_bytes or 0)),
+                 "fvad_egress_device")
 
     def lane_state(self):
         s = vp()
@@ -1734,6 +1769,26 @@ def ingest_check(sources, raw_bytes, out_pcm16, n_lanes, lane_stride, n_samples)
     sources = _ingest_rows(sources)
     return lib().fvad_ingest_check(sources.ctypes.data_as(C.POINTER(C.c_uint64)), sources.shape[0], int(raw_bytes),
                                    INGEST_PCM16 if out_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def _egress_rows(sinks):
+    return np.ascontiguousarray(np.asarray(sinks, np.uint64).reshape(-1, EGRESS_FIELDS))
+
+
+def egress_check(sinks, out_bytes, src_pcm16, n_lanes, lane_stride, n_samples):
+    """fvad_egress_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sinks = _egress_rows(sinks)
+    return lib().fvad_egress_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes),
+                                   INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def wav_header(fmt, n_channels, sample_rate, n_frames):
+    """fvad_wav_header: the 44 bytes in front of the samples of a canonical WAV file of format fmt (INGEST_F32, INGEST_PCM16 or
+    INGEST_PCM24); FvadError for what fvad_wav_write refuses (no or too many channels, a zero rate, more than 4 GB of data)"""
+    out, n = np.zeros(WAV_HEADER_BYTES, np.uint8), sz(0)
+    check(lib().fvad_wav_header(int(fmt), int(n_channels), int(sample_rate), int(n_frames), out.ctypes.data, out.size, C.byref(n)),
+          "fvad_wav_header")
+    return out[:n.value].tobytes()
 
 
 def _resample_rows(sources):

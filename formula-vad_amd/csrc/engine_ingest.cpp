@@ -136,6 +136,12 @@ int ensure_ring(fvad_ctx* ctx, size_t raw)
 
 } // namespace
 
+int fvad::ingest_ring_ensure(fvad_ctx* ctx, size_t raw, size_t* table_bytes)
+{
+    *table_bytes = kTableBytes;
+    return ensure_ring(ctx, raw);
+}
+
 extern "C" {
 
 int fvad_ingest_device(fvad_ctx* ctx, const void* d_raw, uint64_t raw_bytes, const uint64_t* sources, size_t n_sources,

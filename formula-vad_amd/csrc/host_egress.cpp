@@ -1,0 +1,83 @@
+// host_egress.cpp -- the host-only half of the device-side egress (fvad_egress*, engine_egress.cpp): fvad_wav_header, the
+// 44-byte canonical header host_io.cpp's wav_put writes (and its 24-bit PCM form, which wav_put has not), and fvad_egress_check,
+// every argument rule of the device calls.  Plain C++ without HIP headers, like host_ingest.cpp, so that it can be tested (and
+// run under sanitizers) on a machine without a device.
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/fvad.h"
+
+namespace {
+void wr16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
+void wr32(uint8_t* p, uint32_t v) { wr16(p, v & 0xffff); wr16(p + 2, v >> 16); }
+uint64_t sample_bytes(uint64_t format) { return format == FVAD_INGEST_PCM16 ? 2 : format == FVAD_INGEST_PCM24 ? 3 : 4; }
+
+struct Range { uint64_t from, to; };
+} // namespace
+
+extern "C" {
+
+int fvad_wav_header(int format, uint32_t n_channels, uint32_t sample_rate, uint64_t n_frames, uint8_t* out, size_t cap, size_t* n_bytes)
+{
+    if (n_bytes) *n_bytes = 0;
+    if (!out || !n_bytes) return FVAD_ERR_INVALID_ARGUMENT;
+    if (format != FVAD_INGEST_F32 && format != FVAD_INGEST_PCM16 && format != FVAD_INGEST_PCM24) return FVAD_ERR_INVALID_ARGUMENT;
+    if (n_channels == 0 || n_channels > 65535 || sample_rate == 0) return FVAD_ERR_INVALID_ARGUMENT; // wav_put's refusals
+    const uint64_t bytes_per = sample_bytes((uint64_t)format), frame_bytes = n_channels * bytes_per;
+    if (n_frames > 0xFFFFFF00ull / frame_bytes) return FVAD_ERR_INVALID_ARGUMENT; // RIFF sizes are 32-bit
+    const uint64_t data_bytes = n_frames * frame_bytes;
+    *n_bytes = FVAD_WAV_HEADER_BYTES;
+    if (cap < FVAD_WAV_HEADER_BYTES) return FVAD_ERR_BUFFER_TOO_SMALL;
+    memcpy(out, "RIFF", 4); wr32(out + 4, (uint32_t)(36 + data_bytes)); memcpy(out + 8, "WAVEfmt ", 8);
+    wr32(out + 16, 16); wr16(out + 20, format == FVAD_INGEST_F32 ? 3 : 1); wr16(out + 22, n_channels); wr32(out + 24, sample_rate);
+    wr32(out + 28, (uint32_t)(sample_rate * frame_bytes)); wr16(out + 32, (uint32_t)frame_bytes); wr16(out + 34, (uint32_t)(bytes_per * 8));
+    memcpy(out + 36, "data", 4); wr32(out + 40, (uint32_t)data_bytes);
+    return FVAD_OK;
+}
+
+// The order: arguments; then every sink's own rules (format and pair, channels); then every sink's ranges (lanes, samples
+// against n_samples, bytes against out_bytes); then the overlap of two sinks' bytes.
+int fvad_egress_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, int src_format, size_t n_lanes, size_t lane_stride,
+                      size_t n_samples)
+{
+    if (src_format != FVAD_INGEST_F32 && src_format != FVAD_INGEST_PCM16) return FVAD_ERR_INVALID_ARGUMENT;
+    if (n_sinks == 0) return FVAD_OK;
+    if (!sinks) return FVAD_ERR_INVALID_ARGUMENT;
+    if (n_lanes > 1 && lane_stride < n_samples) return FVAD_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n_sinks; ++i) {
+        const uint64_t* r = sinks + i * FVAD_EGRESS_FIELDS;
+        const uint64_t n_channels = r[2], format = r[3];
+        if (format != FVAD_INGEST_F32 && format != FVAD_INGEST_PCM16 && format != FVAD_INGEST_PCM24) return FVAD_ERR_INVALID_ARGUMENT;
+        // PCM16 lanes go to PCM16 files only: PCM16 -> f32 and PCM16 -> PCM24 are conversions, not egress
+        if (src_format == FVAD_INGEST_PCM16 && format != FVAD_INGEST_PCM16) return FVAD_ERR_INVALID_ARGUMENT;
+        if (n_channels < 1 || n_channels > 64) return FVAD_ERR_INVALID_ARGUMENT;
+    }
+    size_t n_ranges = 0;
+    for (size_t i = 0; i < n_sinks; ++i) {
+        const uint64_t* r = sinks + i * FVAD_EGRESS_FIELDS;
+        const uint64_t byte_offset = r[0], n_frames = r[1], n_channels = r[2], format = r[3], first_lane = r[4], src_offset = r[5];
+        if (first_lane >= n_lanes || n_channels > n_lanes - first_lane) return FVAD_ERR_OUT_OF_RANGE;
+        if (src_offset > n_samples || n_frames > n_samples - src_offset) return FVAD_ERR_OUT_OF_RANGE;
+        const uint64_t frame_bytes = n_channels * sample_bytes(format);
+        if (n_frames > UINT64_MAX / frame_bytes) return FVAD_ERR_OUT_OF_RANGE;
+        if (byte_offset > out_bytes || n_frames * frame_bytes > out_bytes - byte_offset) return FVAD_ERR_OUT_OF_RANGE;
+        if (n_frames) ++n_ranges;
+    }
+    // two sinks may not write one byte: the order of the writes would decide the result.  The ranges sorted by their start
+    // must not reach into their successors (a range that ends where the next one starts is fine).
+    std::vector<Range> ranges;
+    ranges.reserve(n_ranges);
+    for (size_t i = 0; i < n_sinks; ++i) {
+        const uint64_t* r = sinks + i * FVAD_EGRESS_FIELDS;
+        if (r[1] == 0) continue; // writes nothing
+        ranges.push_back({r[0], r[0] + r[1] * r[2] * sample_bytes(r[3])});
+    }
+    std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.from < y.from; });
+    for (size_t k = 1; k < ranges.size(); ++k)
+        if (ranges[k].from < ranges[k - 1].to) return FVAD_ERR_INVALID_ARGUMENT;
+    return FVAD_OK;
+}
+
+} // extern "C"

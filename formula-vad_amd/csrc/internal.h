@@ -312,4 +312,7 @@ int run_chunks(fvad_ctx* ctx, std::vector<LaneJob>& jobs, long max_chunks, Chunk
                ChunkDesc* capture_dev = nullptr, long* n_launches = nullptr);
 void time_begin(fvad_ctx* ctx, const char* name);
 void time_end(fvad_ctx* ctx);
+// fvad_ingest's ring (Workspace::IngestRing, engine_ingest.cpp) made to hold `raw` bytes a slot plus its table room, for the
+// calls that share it (engine_egress.cpp); *table_bytes: that room, sized for 4096 IngestJobs in three sets
+int ingest_ring_ensure(fvad_ctx* ctx, size_t raw, size_t* table_bytes);
 } // namespace fvad

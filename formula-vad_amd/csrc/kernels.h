@@ -572,3 +572,25 @@ struct IngestResampleArgs {
     uint32_t lds_bytes;            // the largest window of a tile of these jobs + 16
 };
 int fvad_launch_ingest_resample(const IngestResampleArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ device-side egress (kernels_egress.hip)
+// fvad_egress*: the ingest's inverse.  A work unit is a tile of one sink -- kIngestTileBytes of its DESTINATION bytes rounded
+// down to whole frames in multiples of 4 (tile_frames, the ingest's rule), every channel of them.  A launch serves the jobs of
+// ONE format pair; unit_prefix[j] counts the units in front of job j (a job has at least one unit).
+struct EgressJob {
+    uint64_t dst_off;   // bytes from `out` to the sink's frame 0
+    uint64_t n_frames;
+    uint64_t src_off;   // elements from `lanes` to the sample frame 0 of channel 0 is taken from
+    uint32_t n_tiles, tile_frames;
+    uint32_t n_channels, pad_;
+};
+struct EgressArgs {
+    const void* lanes;  // f32 or PCM16 lanes
+    uint64_t lane_stride;
+    uint8_t* out;
+    const EgressJob* jobs;        // [n_jobs] (device)
+    const uint32_t* unit_prefix;  // [n_jobs + 1]
+    uint32_t n_jobs, n_units;
+    int src_format, file_format;  // FVAD_INGEST_*
+};
+int fvad_launch_egress(const EgressArgs& a, hipStream_t stream); // hipError_t as int

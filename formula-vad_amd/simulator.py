@@ -8,6 +8,9 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
                                                       clips, original and denoised, cut and picked on the GPU;
                                                       --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
                                                       --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
+    python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32]   (or: run_denoise(path,
+                                                      DIR): the denoised recordings as WAV files, converted and interleaved
+                                                      on the GPU)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
     python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
                                                       parameter grid, every machine scored on the GPU, the top K configs by
@@ -882,6 +885,168 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
         manifest["original_skipped"], manifest["denoised_skipped"] = skipped[i]["original"], skipped[i]["denoised"]
         out.append((segs_of[i], audits[i], manifest))
     return out
+
+
+# ---------------------------------------------------------------- the denoised recordings themselves (fvad_egress)
+DENOISED_FORMATS = {"pcm16": fv.INGEST_PCM16, "pcm24": fv.INGEST_PCM24, "f32": fv.INGEST_F32}
+
+
+def _check_denoised_format(fmt):
+    if fmt not in DENOISED_FORMATS:
+        raise ValueError(f"denoised format: {fmt!r} (one of {', '.join(DENOISED_FORMATS)})")
+
+
+class _DenoisedFile:
+    """NAME-denoised.wav of one instance, created at its final size -- fvad_wav_header's 44 bytes, then a hole of n_frames
+    frames -- and mapped for fvad_egress to fill (`map`: the whole file as bytes, None for a file without frames)."""
+
+    def __init__(self, out_dir, inst, fmt, n_channels, n_frames):
+        code = DENOISED_FORMATS[fmt]
+        self.frame_bytes = n_channels * fv.INGEST_SAMPLE_BYTES[code]
+        self.manifest = {"name": inst["name"], "file": os.path.join(out_dir, f"{inst['name']}-denoised.wav"), "format": fmt,
+                         "channels": n_channels, "frames": n_frames, "sample_rate": 48000}
+        head = fv.wav_header(code, n_channels, 48000, n_frames)   # (raises for more than 4 GB of data, like fvad_wav_write)
+        size = len(head) + n_frames * self.frame_bytes
+        with open(self.manifest["file"], "wb") as f:
+            f.write(head)
+            f.truncate(size)
+        self.map = np.memmap(self.manifest["file"], dtype=np.uint8, mode="r+", shape=(size,)) if n_frames else None
+
+    def sink(self, frame_from, n_frames, first_lane, src_offset):
+        """the fvad_egress sink row of the file's frames [frame_from, frame_from + n_frames)"""
+        n_channels, code = self.manifest["channels"], DENOISED_FORMATS[self.manifest["format"]]
+        return (fv.WAV_HEADER_BYTES + frame_from * self.frame_bytes, n_frames, n_channels, code, first_lane, src_offset)
+
+    def close(self):
+        self.map = None   # unmapped without msync: the written pages are the page cache's, as after fvad_wav_write's fwrite + fclose
+
+
+def _denoise_share(ctx, plan, insts, audio, out_dir, fmt):
+    """run_denoise for the instances of one context, resident: _denoise_resident's lanes, one fvad_egress over every file"""
+    if not audio:
+        return []
+    held = []
+
+    def dalloc(nbytes):
+        held.append(ctx.device_alloc(max(int(nbytes), 4)))
+        return held[-1]
+
+    files = []
+    try:
+        r = _denoise_resident(ctx, audio, plan["fft_size"], plan["vad_machine_config"], dalloc)
+        lane0, l = {}, 0
+        for i in r.order:
+            lane0[i] = l
+            l += _dims(audio[i])[0]
+        files = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000) for inst, a, n in zip(insts, audio, r.n_chunks)]
+        sinks = [f.sink(0, f.manifest["frames"], lane0[i], 0) for i, f in enumerate(files)]
+        ctx.egress(sinks, d_lanes=r.d_den, n_lanes=r.n_lanes, lane_stride=r.n_den, n_samples=r.n_den, out=[f.map for f in files])
+        return [f.manifest for f in files]
+    finally:
+        for f in files:
+            f.close()
+        for d in held:
+            ctx.device_free(d)
+
+
+def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks):
+    """run_denoise(slice_chunks=N) for the instances of one context: channel-count group after group in time slices [s0, s1) of
+    N chunks, read and denoised as a sliced grid's (_slice_denoise_and_bands, without bands; audio mapped or raw); each slice's
+    frames go to their place in the files -- byte 44 + s0 * 24000 * frame bytes -- in one fvad_egress over the group's members
+    that still have chunks there.  The device holds one slice and its halo."""
+    if not audio:
+        return []
+    chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
+    dims = [_dims(a, mapped=True) for a in audio]
+    n_chunks = [d[1] // chunk for d in dims]
+    groups = {}
+    for i, d in enumerate(dims):
+        groups.setdefault(d[0], []).append(i)
+    opts = _engine_opts(plan["vad_machine_config"], F)
+    n_max = N + H
+    lanes_max = max(len(m) * nch for nch, m in groups.items())
+    own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4, "band0": lanes_max * (n_max * chunk // F + 1) * 4,
+           "rms": lanes_max * n_max * 4, "bands": 16}
+    d, host, files = {}, None, []
+    times = collections.defaultdict(float)
+    try:
+        for k, nb in own.items():
+            d[k] = ctx.device_alloc(max(nb, 16))
+        if not _is_raw(audio):
+            host = ctx.host_alloc(lanes_max * n_max * chunk)
+        buf = _SliceBufs(d, host, opts, N * chunk // F)
+        files = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk) for inst, dm, n in zip(insts, dims, n_chunks)]
+        for nch, members in groups.items():
+            L = len(members) * nch
+            K = max(n_chunks[i] for i in members)
+            for s0 in range(0, K, N):
+                s1 = min(s0 + N, K)
+                start = max(s0 - H, 0)
+                n = s1 - start
+                _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, (), times)
+                live = [(k, i) for k, i in enumerate(members) if n_chunks[i] > s0]
+                sinks = [files[i].sink(s0 * chunk, (min(n_chunks[i], s1) - s0) * chunk, k * nch, (s0 - start) * chunk) for k, i in live]
+                ctx.egress(sinks, d_lanes=d["den"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk, out=[files[i].map for _, i in live])
+        return [f.manifest for f in files]
+    finally:
+        for f in files:
+            f.close()
+        for a in d.values():
+            ctx.device_free(a)
+        if host is not None:
+            ctx.host_free(host)
+
+
+def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None):
+    """The plan's recordings, denoised, as WAV files: per instance NAME-denoised.wav in out_dir with all of the instance's
+    channels at 48 kHz, as PCM16 (fmt "pcm16": rint(clamp(y * 32768)), the rule of the PCM16 clips and of
+    fvad_lane.denoised_i16, not fvad_wav_write's), 24-bit PCM ("pcm24") or float32 ("f32": the lanes' bits, the file
+    fvad_wav_write writes).  A file has as many frames as the denoised lanes hold -- whole chunks of 24000, as run_clips
+    documents: a partial last chunk is not denoised.  Each file is created at its final size with fvad_wav_header, mapped, and
+    filled by fvad_egress: the GPU converts and interleaves, the host moves bytes.  Instances are dealt to `devices` like
+    run_clips; the denoising is _denoise_resident's (the context option "reproducible" makes it agree bit for bit with every
+    other path), or with slice_chunks N the sliced grid's, device memory bounded by a slice -- the same bytes.  ingest "device":
+    the files' bytes are decoded on the GPU (run_grid); the same bytes again.  A bad fmt, ingest or slice_chunks raises before
+    any work.  Returns a manifest per instance, in plan order: name, file, format, channels, frames, sample_rate."""
+    _check_ingest(ingest)
+    _check_denoised_format(fmt)
+    plan = load_plan(plan_path)
+    if slice_chunks is not None:
+        check_slice_chunks(slice_chunks, plan["fft_size"])
+    own_ctx = ctx is None
+    ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])] if own_ctx else [ctx]
+    try:
+        os.makedirs(out_dir, exist_ok=True)
+        audio = [a for a, _ in _load_instances(plan, ingest, mapped=slice_chunks is not None)]
+        parts = instance_shares(len(audio), len(ctxs))
+        done, errs = [None] * len(ctxs), []
+
+        def work(d):
+            try:
+                insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
+                if slice_chunks is None:
+                    done[d] = _denoise_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt)
+                else:
+                    done[d] = _denoise_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, slice_chunks)
+            except Exception as e:  # re-raised below, in the caller's thread
+                errs.append(e)
+
+        th = [threading.Thread(target=work, args=(d,)) for d in range(len(ctxs))]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        if errs:
+            raise errs[0]
+        manifests = [None] * len(audio)
+        for d, part in enumerate(parts):
+            for i, m in zip(part, done[d]):
+                manifests[i] = m
+        return manifests
+    finally:
+        if own_ctx:
+            for c in ctxs:
+                c.close()
 
 
 SWEEP_COLUMNS = ("P", "TP", "FP", "FN", "TPR", "PPV", "FNR", "FDR", "F", "FM")
@@ -2138,7 +2303,7 @@ def arg_parser():
                                                           "print the top configs (on --devices, default device 0)")
     ap.add_argument("--top", type=int, default=20, help="with --sweep-grid: rows to print (by F-score)")
     ap.add_argument("--slice-chunks", type=int, default=None,
-                    help="with --sweep-grid or --export-clips: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
+                    help="with --sweep-grid, --export-clips or --export-denoised: run in time slices of N chunks (a multiple of 16 at fft_size 1024; with several "
                          "sizes, of the lcm over them), device and host "
                          "memory bounded by the slice instead of the corpus")
     ap.add_argument("--halving-eta", type=int, default=None,
@@ -2178,17 +2343,40 @@ def arg_parser():
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
+    ap.add_argument("--export-denoised", default=None, metavar="DIR",
+                    help="write every instance's denoised recording to DIR as NAME-denoised.wav (all its channels at 48 kHz, whole "
+                         "chunks), converted and interleaved on the GPU (fvad_egress); not with --sweep, --sweep-grid or --export-clips; "
+                         "takes --slice-chunks, --ingest and --devices")
+    ap.add_argument("--denoised-format", default=None, choices=tuple(DENOISED_FORMATS),
+                    help="with --export-denoised: pcm16 (the default), pcm24 or f32")
     ap.add_argument("--ingest", default="host", choices=INGESTS,
-                    help="with --sweep / --sweep-grid / --export-clips: where the files' samples are de-interleaved and decoded -- on "
+                    help="with --sweep / --sweep-grid / --export-clips / --export-denoised: where the files' samples are de-interleaved and decoded -- on "
                          "the host, uploaded as f32 (the default), or on the GPU from the files' own bytes (fvad_ingest: PCM16 crosses "
                          "PCIe at 2 bytes per sample, and 24-bit PCM files are taken); same results.  Files at other rates than 48 kHz "
                          "(44.1 kHz, 16 kHz ...) run with device only: they are resampled to 48 kHz while they are ingested")
     return ap
 
 
+def check_modes(a):
+    """--export-denoised is a mode of its own: ValueError, before any work, when it is combined with a sweep or the clip export,
+    or when --denoised-format comes without it"""
+    if a.export_denoised:
+        others = [name for name, on in (("--sweep", a.sweep), ("--sweep-grid", a.sweep_grid), ("--export-clips", a.export_clips)) if on]
+        if others:
+            raise ValueError(f"--export-denoised cannot be combined with {', '.join(others)} (one pass writes one kind of output)")
+    elif a.denoised_format is not None:
+        raise ValueError("--denoised-format needs --export-denoised")
+
+
 def main(argv=None):
     a = arg_parser().parse_args(argv)
+    check_modes(a)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
+    if a.export_denoised:
+        for m in run_denoise(a.input, a.export_denoised, fmt=a.denoised_format or "pcm16", synth_seed=a.synth_seed, devices=devices,
+                             ingest=a.ingest, slice_chunks=a.slice_chunks):
+            sys.stdout.write(f"{m['file']}: {m['channels']} x {m['frames']} frames, {m['format']}\n")
+        return
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,
                  slice_chunks=a.slice_chunks, halving_eta=a.halving_eta, halving_rungs=a.halving_rungs, devices=devices,

@@ -1197,6 +1197,63 @@ int fvad_ingest_resample(fvad_ctx *ctx, const void *const *src_host, const uint6
                          uint32_t down, const float *taps, uint32_t n_taps, void *d_lanes, size_t n_lanes, size_t lane_stride,
                          size_t n_samples);
 
+/* ------------------------------------------------------------------ device-side egress: planar lanes into a file's bytes
+ * The ingest's inverse, the way out for whole recordings: ONE kernel (csrc/kernels_egress.hip) converts planar device lanes --
+ * the denoised lanes of fvad_engine_enqueue_device*, or any others -- to the sample format of a WAV file and interleaves them
+ * into the bytes of its data chunk.  The host does no per-sample work, a PCM16 file crosses PCIe at 2 bytes per sample, and
+ * 24-bit PCM files, which fvad_wav_write cannot write, can be written.
+ * - A sink (a file, or a time slice of one) is a row of FVAD_EGRESS_FIELDS uint64: byte_offset (where its frame 0 goes in the
+ *   output bytes: any value, a data chunk usually starts at byte 44, which is 12 modulo 16), n_frames, n_channels (1 .. 64),
+ *   format (the FILE's sample format, FVAD_INGEST_*), first_lane (channel c is lane first_lane + c), src_offset (the lane
+ *   sample frame 0 is taken from).  Lanes are laid out as for fvad_ingest: lane l at d_lanes + l * lane_stride samples of
+ *   src_format (FVAD_INGEST_F32 or FVAD_INGEST_PCM16), n_samples each; nothing needs alignment beyond the sample's size.
+ *   Sample (f, c) of a sink goes to byte_offset + (f * n_channels + c) * bytes per sample, little-endian.
+ * - Format pairs (lanes -> file): f32 -> f32 the bits (moved as 32-bit integers: NaN payloads and -0 survive); f32 -> PCM16 is
+ *   rint(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)), ties to even, NaN gives -32768 (as fmaxf gives there): the rule of
+ *   fvad_lane.denoised_i16 and of PCM16 clips (csrc/clip_device.h) -- NOT fvad_wav_write's libsndfile rule
+ *   lrintf(clip(x, -1, 1) * 32767), so a PCM16 file written here and one fvad_wav_write(as_pcm16) wrote differ; f32 -> PCM24 is
+ *   rint(fminf(fmaxf(y * 8388608.0f, -8388608.0f), 8388607.0f)) written as its low three bytes (the scale is a power of two and
+ *   both bounds are exact in f32: the inverse of fvad_ingest's s / 8388608 for every value that came from a 24-bit file, as
+ *   the PCM16 rule is of s / 32768); PCM16 -> PCM16 the bits.  PCM16 lanes -> f32 or PCM24 files are conversions, not egress:
+ *   FVAD_ERR_INVALID_ARGUMENT.
+ * - INVARIANTS, all bit for bit.  No byte outside [byte_offset, byte_offset + n_frames * n_channels * bytes per sample) of a
+ *   sink is written; no sample outside [src_offset, src_offset + n_frames) of its lanes is read.  The output does not depend on
+ *   the order of the sinks, on how a file is cut into sinks or calls, on ingest_ring_bytes, on the call form (device bytes or
+ *   host bytes), or on the alignment of either side.  No atomics; a sink's bytes depend on its lanes' samples alone.
+ *
+ * fvad_wav_header (host only): the FVAD_WAV_HEADER_BYTES (44) bytes of the canonical header -- RIFF, "fmt " of length 16, no
+ *   "fact" chunk, "data" -- into out[0 .. cap), *n_bytes = 44.  For f32 (tag 3, 32 bits) and PCM16 (tag 1, 16 bits) byte for
+ *   byte what fvad_wav_write / fvad_wav_write_i16 put in front of their samples; for PCM24 tag 1, 24 bits, block align 3 *
+ *   n_channels.  FVAD_ERR_INVALID_ARGUMENT for a bad format, zero or more than 65535 channels, a zero rate, data bytes above
+ *   0xFFFFFF00 (their refusals) or NULL; FVAD_ERR_BUFFER_TOO_SMALL for cap < 44 (with *n_bytes set).  fvad_wav_probe on header
+ *   + data returns the arguments back.
+ * fvad_egress_check (host only): every argument rule of the two calls below, in this order: FVAD_ERR_INVALID_ARGUMENT for a bad
+ *   src_format, NULL sinks, lane_stride < n_samples with several lanes; then per sink FVAD_ERR_INVALID_ARGUMENT for a bad format
+ *   or pair, n_channels outside 1 .. 64; then per sink FVAD_ERR_OUT_OF_RANGE for lanes past n_lanes, src_offset + n_frames >
+ *   n_samples, byte_offset + bytes > out_bytes (all sums checked for 64-bit overflow); then FVAD_ERR_INVALID_ARGUMENT when two
+ *   sinks' byte ranges overlap (the order of the writes would decide the result; ranges that touch are fine).  n_sinks == 0
+ *   succeeds; a sink with n_frames == 0 writes nothing.
+ * fvad_egress_device: d_out holds out_bytes bytes on the device.  Runs fvad_egress_check (and refuses NULL pointers and lanes
+ *   that are not aligned to their samples) before any launch, returns when the bytes are written, and names `egress` in
+ *   fvad_ctx_kernel_times (one launch per file format present).  A launch takes fewer than 2^24 tiles (16 KB of output bytes
+ *   each): a call with more is FVAD_ERR_INVALID_ARGUMENT; write in batches.
+ * fvad_egress: the same for bytes in host memory (a mapped output file, pageable or page-locked memory): sink i's byte_offset
+ *   is relative to dst_host[i] (which may be NULL when n_frames == 0), and the overlap rule applies to the absolute host ranges.
+ *   The kernel writes batch after batch into the two-slot page-locked ring fvad_ingest uses (ingest_ring_bytes: the output bytes
+ *   per batch); each batch is copied back and moved into place with memcpy while the kernel fills the other slot.  A sink larger
+ *   than what is left of a batch is cut at a multiple of 4 frames.  The bytes are the same however the ring cuts the sinks, and
+ *   the same as fvad_egress_device's. */
+#define FVAD_EGRESS_FIELDS 6
+#define FVAD_WAV_HEADER_BYTES 44
+int fvad_wav_header(int format, uint32_t n_channels, uint32_t sample_rate, uint64_t n_frames, uint8_t *out, size_t cap,
+                    size_t *n_bytes);
+int fvad_egress_check(const uint64_t *sinks, size_t n_sinks, uint64_t out_bytes, int src_format, size_t n_lanes,
+                      size_t lane_stride, size_t n_samples);
+int fvad_egress_device(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                       const uint64_t *sinks, size_t n_sinks, void *d_out, uint64_t out_bytes);
+int fvad_egress(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                const uint64_t *sinks, size_t n_sinks, void *const *dst_host);
+
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
 typedef struct {
