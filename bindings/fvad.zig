@@ -25,6 +25,7 @@ pub const abi_version = 3; // FVAD_ABI_VERSION
 pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
 pub const egress_fields = 6; // FVAD_EGRESS_FIELDS: a sink is a row of byte_offset, n_frames, n_channels, format, first_lane, src_offset (u64 each)
+pub const egress_resample_fields = 10; // FVAD_EGRESS_RESAMPLE_FIELDS: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from (u64 each)
 pub const wav_header_bytes = 44; // FVAD_WAV_HEADER_BYTES
 pub const resample_fields = 11; // FVAD_RESAMPLE_FIELDS: ingest_fields' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
 pub const resample_up_max = 640; // FVAD_RESAMPLE_UP_MAX
@@ -471,6 +472,12 @@ pub extern "c" fn fvad_wav_header(format: c_int, n_channels: u32, sample_rate: u
 pub extern "c" fn fvad_egress_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_egress_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, d_out: ?*anyopaque, out_bytes: u64) c_int;
 pub extern "c" fn fvad_egress(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, dst_host: ?[*]const ?*anyopaque) c_int;
+// resampling egress: the same at another rate, a rational polyphase resampler in front of the conversion
+pub extern "c" fn fvad_egress_resample_tile(up: u32, down: u32, n_taps: u32, n_channels: u32, format: u32) u64;
+pub extern "c" fn fvad_egress_resample_ready(up: u32, down: u32, n_taps: u32, stream_frames: u64, frames_have: u64) u64;
+pub extern "c" fn fvad_egress_resample_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_egress_resample_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_out: ?*anyopaque, out_bytes: u64) c_int;
+pub extern "c" fn fvad_egress_resample(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, dst_host: ?[*]const ?*anyopaque) c_int;
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;

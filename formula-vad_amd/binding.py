@@ -38,6 +38,7 @@ RESAMPLE_FIELDS = 11             # a resample source: INGEST_FIELDS' seven (n_fr
 RESAMPLE_UP_MAX = 640            # FVAD_RESAMPLE_UP_MAX
 RESAMPLE_TAPS_MAX = 20481        # FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1)
 EGRESS_FIELDS = 6                # a sink: byte_offset, n_frames, n_channels, format (the file's), first_lane, src_offset (uint64 each)
+EGRESS_RESAMPLE_FIELDS = 10      # a resampled sink: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from
 WAV_HEADER_BYTES = 44            # FVAD_WAV_HEADER_BYTES: fvad_wav_header's canonical header
 INGEST_FILL_TILE = 8192          # kIngestFillTile: the zeros of one lane a workgroup writes
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
@@ -390,6 +391,11 @@ SIGNATURES = {
     "fvad_egress_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_egress_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, vp, C.c_uint64]),
     "fvad_egress": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.POINTER(vp)]),
+    "fvad_egress_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "fvad_egress_resample_ready": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "fvad_egress_resample_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_int, sz, sz, sz]),
+    "fvad_egress_resample_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, vp, C.c_uint64]),
+    "fvad_egress_resample": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.POINTER(vp)]),
     "fvad_resample_ratio": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fvad_resample_out_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "fvad_resample_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p, C.POINTER(C.c_uint32)]),
@@ -927,6 +933,37 @@ class Context:
             return
         self._ck(lib().fvad_egress_device(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, vp(out), int(out_bytes or 0)),
                  "fvad_egress_device")
+
+    def egress_resample(self, sinks, up, down, taps, src_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, out=None, out_bytes=None):
+        """fvad_egress_resample_device (out: a device address holding out_bytes bytes) or fvad_egress_resample (out: a list with
+        one writable C-contiguous numpy / memmap byte buffer per row, or None for a row without outputs; a row's byte_offset is
+        relative to its own buffer): sinks [n][EGRESS_RESAMPLE_FIELDS] uint64 <- the planar float32 lanes at device address
+        d_lanes, resampled by up / down with `taps` (float32, an odd count), converted to each row's file format and
+        interleaved.  One ratio and one set of taps per call (src_pcm16 lanes are refused by the library).  Returns when the
+        bytes are written."""
+        sinks = _egress_resample_rows(sinks)
+        n = sinks.shape[0]
+        fmt = INGEST_PCM16 if src_pcm16 else INGEST_F32
+        rows = sinks.ctypes.data_as(C.POINTER(C.c_uint64))
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        head = (self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, up, down, fptr(taps), taps.shape[0])
+        if isinstance(out, (list, tuple)):
+            if len(out) != n:
+                raise ValueError(f"egress_resample: {n} rows, {len(out)} buffers")
+            ptrs = (vp * max(n, 1))()
+            for i, b in enumerate(out):
+                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no outputs: no byte is written, whatever byte_offset says
+                    ptrs[i] = None
+                    continue
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
+                    raise ValueError("egress_resample: a row's bytes are a writable C-contiguous uint8 array")
+                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
+                if need > b.size:   # (the library cannot know where a host buffer ends)
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress_resample", f"row {i} writes {need} bytes of a buffer of {b.size}")
+                ptrs[i] = b.ctypes.data
+            self._ck(lib().fvad_egress_resample(*head, ptrs), "fvad_egress_resample")
+            return
+        self._ck(lib().fvad_egress_resample_device(*head, vp(out), int(out_bytes or 0)), "fvad_egress_resample_device")
 
     def lane_state(self):
         s = vp()
@@ -1780,6 +1817,34 @@ def egress_check(sinks, out_bytes, src_pcm16, n_lanes, lane_stride, n_samples):
     sinks = _egress_rows(sinks)
     return lib().fvad_egress_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes),
                                    INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def _egress_resample_rows(sinks):
+    return np.ascontiguousarray(np.asarray(sinks, np.uint64).reshape(-1, EGRESS_RESAMPLE_FIELDS))
+
+
+def egress_resample_tile(up, down, n_taps, n_channels, fmt):
+    """fvad_egress_resample_tile: output frames per workgroup of the resampling egress kernel (0: the window of 4 outputs does
+    not fit a tile, or arguments that are none)"""
+    return int(lib().fvad_egress_resample_tile(up, down, n_taps, n_channels, fmt))
+
+
+def egress_resample_ready(up, down, n_taps, stream_frames, frames_have):
+    """fvad_egress_resample_ready: the leading outputs of a stream of stream_frames lane samples whose whole window lies below
+    frames_have (all of them once frames_have >= stream_frames): what a time slice can finish"""
+    return int(lib().fvad_egress_resample_ready(up, down, n_taps, int(stream_frames), int(frames_have)))
+
+
+def egress_resample_check(sinks, out_bytes, up, down, taps, n_lanes, lane_stride, n_samples, src_pcm16=False):
+    """fvad_egress_resample_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sinks = _egress_resample_rows(sinks)
+    if taps is None:
+        tp, nt = None, 0
+    else:
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        tp, nt = fptr(taps), taps.shape[0]
+    return lib().fvad_egress_resample_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes), up, down, tp, nt,
+                                            INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
 
 
 def wav_header(fmt, n_channels, sample_rate, n_frames):

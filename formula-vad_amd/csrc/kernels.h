@@ -594,3 +594,30 @@ struct EgressArgs {
     int src_format, file_format;  // FVAD_INGEST_*
 };
 int fvad_launch_egress(const EgressArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ resampling egress (kernels_egress_resample.hip)
+// fvad_egress_resample*: the egress with the clips' polyphase resampler in front of its conversion.  A work unit is a tile of
+// one row -- tile_out consecutive OUTPUT frames (egress_resample_tile of egress_resample.h: a multiple of 4 whose bytes fit
+// kIngestTileBytes and whose window of one channel fits kClipTile lane samples), every channel of them.  Output i of the job
+// is output out_from + i of the STREAM; stream sample s of channel c lies at lanes + src_off + c * lane_stride +
+// (s - frame_base).  One ratio and one tap table (resample_table's layout) per launch, the jobs of ONE file format.
+struct EgressResampleJob {
+    uint64_t dst_off;    // bytes from `out` to output out_from
+    uint64_t out_from, n_out;
+    uint64_t src_off;    // elements from `lanes` to stream sample frame_base of channel 0
+    uint64_t frame_base, stream_frames;
+    uint32_t n_tiles, tile_out;
+    uint32_t n_channels, pad_;
+};
+struct EgressResampleArgs {
+    const float* lanes;
+    uint64_t lane_stride;
+    uint8_t* out;
+    const EgressResampleJob* jobs; // [n_jobs] (device)
+    const uint32_t* unit_prefix;   // [n_jobs + 1]
+    const float* table;            // [ceil(n_taps / up)][up] (device)
+    uint32_t n_jobs, n_units;
+    uint32_t up, down, n_taps;
+    int file_format;               // FVAD_INGEST_*
+};
+int fvad_launch_egress_resample(const EgressResampleArgs& a, hipStream_t stream); // hipError_t as int

@@ -8,7 +8,7 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
                                                       clips, original and denoised, cut and picked on the GPU;
                                                       --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
                                                       --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
-    python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32]   (or: run_denoise(path,
+    python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source]   (or: run_denoise(path,
                                                       DIR): the denoised recordings as WAV files, converted and interleaved
                                                       on the GPU)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
@@ -896,16 +896,75 @@ def _check_denoised_format(fmt):
         raise ValueError(f"denoised format: {fmt!r} (one of {', '.join(DENOISED_FORMATS)})")
 
 
+def _denoised_resample(rate):
+    """the filter of recordings written at `rate` (run_denoise(rate=...)): up/down = rate/48000 in lowest terms and
+    fvad_resample_design's default taps, its parameters spelt out for the manifest; ValueError for a rate that has none"""
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate <= 0 or rate >= 1 << 32:
+        raise ValueError(f"run_denoise: rate {rate!r} (None, 'source' or a sample rate)")
+    try:
+        up, down = fv.resample_ratio(48000, int(rate))
+        taps = fv.resample_design(up, down)
+    except fv.FvadError:
+        raise ValueError(f"run_denoise: rate {rate!r}: no ratio to 48000 with up <= {fv.RESAMPLE_UP_MAX} whose default design fits "
+                         f"{fv.RESAMPLE_TAPS_MAX} taps") from None
+    m = max(up, down)
+    return {"rate": int(rate), "up": up, "down": down, "half": 16, "cutoff": 0.45 / m, "beta": 6.0, "taps": taps}
+
+
+def _check_denoised_rate(rate):
+    if rate is None or (isinstance(rate, str) and rate == "source") or (not isinstance(rate, bool) and rate == 48000):
+        return
+    _denoised_resample(rate)
+
+
+def _denoised_filters(rate, audio, dims, fmt):
+    """per instance the _denoised_resample filter its recording leaves through, None for one that leaves at 48 kHz (fvad_egress).
+    rate: an integer for every file, or "source" -- each instance at its own file's rate, which ingest="device" knows
+    (_RawAudio.rate) and the host path, which takes 48 kHz files only, does not need.  ValueError, before any file exists, for a
+    recording whose frames fit no tile of the kernel or whose data would pass 4 GB."""
+    code, made, out = DENOISED_FORMATS[fmt], {}, []
+    for a, (nch, n_frames) in zip(audio, dims):
+        r = (a.rate if isinstance(a, _RawAudio) else 48000) if isinstance(rate, str) else int(rate)
+        if r == 48000:
+            out.append(None)
+            continue
+        if r not in made:
+            made[r] = _denoised_resample(r)
+        f = made[r]
+        if fv.egress_resample_tile(f["up"], f["down"], f["taps"].size, nch, code) == 0:
+            raise ValueError(f"run_denoise: rate {r}: the filter's window fits no tile of the kernel for {nch} channels")
+        frames = fv.resample_out_frames(n_frames // 24000 * 24000, f["up"], f["down"])
+        if frames * nch * fv.INGEST_SAMPLE_BYTES[code] > 0xFFFFFF00:
+            raise ValueError(f"run_denoise: rate {r}: more than 4 GB of data in one file")
+        out.append(f)
+    return out
+
+
+def _by_filter(pairs):
+    """[(filter, x)] -> [(filter, [x])], one entry per distinct ratio (one ratio and one set of taps per fvad_egress_resample call)"""
+    groups = {}
+    for f, x in pairs:
+        groups.setdefault(f["rate"], (f, []))[1].append(x)
+    return list(groups.values())
+
+
 class _DenoisedFile:
     """NAME-denoised.wav of one instance, created at its final size -- fvad_wav_header's 44 bytes, then a hole of n_frames
-    frames -- and mapped for fvad_egress to fill (`map`: the whole file as bytes, None for a file without frames)."""
+    frames -- and mapped for fvad_egress to fill (`map`: the whole file as bytes, None for a file without frames).  With a
+    filter `rs` (_denoised_resample) the file holds the ceil(n_frames up / down) frames of the stream of n_frames lane samples
+    at the filter's rate, for fvad_egress_resample to fill."""
 
-    def __init__(self, out_dir, inst, fmt, n_channels, n_frames):
+    def __init__(self, out_dir, inst, fmt, n_channels, n_frames, rs=None):
         code = DENOISED_FORMATS[fmt]
         self.frame_bytes = n_channels * fv.INGEST_SAMPLE_BYTES[code]
+        self.rs, self.stream_frames, self.written, rate = rs, n_frames, 0, 48000
+        if rs is not None:
+            n_frames, rate = fv.resample_out_frames(n_frames, rs["up"], rs["down"]), rs["rate"]
         self.manifest = {"name": inst["name"], "file": os.path.join(out_dir, f"{inst['name']}-denoised.wav"), "format": fmt,
-                         "channels": n_channels, "frames": n_frames, "sample_rate": 48000}
-        head = fv.wav_header(code, n_channels, 48000, n_frames)   # (raises for more than 4 GB of data, like fvad_wav_write)
+                         "channels": n_channels, "frames": n_frames, "sample_rate": rate}
+        if rs is not None:
+            self.manifest["resample"] = {k: rs[k] for k in ("up", "down", "half", "cutoff", "beta")}
+        head = fv.wav_header(code, n_channels, rate, n_frames)   # (raises for more than 4 GB of data, like fvad_wav_write)
         size = len(head) + n_frames * self.frame_bytes
         with open(self.manifest["file"], "wb") as f:
             f.write(head)
@@ -917,12 +976,25 @@ class _DenoisedFile:
         n_channels, code = self.manifest["channels"], DENOISED_FORMATS[self.manifest["format"]]
         return (fv.WAV_HEADER_BYTES + frame_from * self.frame_bytes, n_frames, n_channels, code, first_lane, src_offset)
 
+    def sink_resampled(self, out_to, first_lane, src_offset, frame_base, n_frames):
+        """the fvad_egress_resample row of the file's outputs [written, out_to), which then count as written; the lanes hold the
+        stream's samples [frame_base, frame_base + n_frames) from src_offset on"""
+        n_channels, code = self.manifest["channels"], DENOISED_FORMATS[self.manifest["format"]]
+        out_from, self.written = self.written, max(out_to, self.written)
+        return (fv.WAV_HEADER_BYTES + out_from * self.frame_bytes, self.written - out_from, n_channels, code, first_lane, src_offset,
+                frame_base, n_frames, self.stream_frames, out_from)
+
+    def ready(self, frames_have):
+        """fvad_egress_resample_ready: the file's leading outputs that the stream's samples below frames_have can finish"""
+        return fv.egress_resample_ready(self.rs["up"], self.rs["down"], self.rs["taps"].size, self.stream_frames, frames_have)
+
     def close(self):
         self.map = None   # unmapped without msync: the written pages are the page cache's, as after fvad_wav_write's fwrite + fclose
 
 
-def _denoise_share(ctx, plan, insts, audio, out_dir, fmt):
-    """run_denoise for the instances of one context, resident: _denoise_resident's lanes, one fvad_egress over every file"""
+def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None):
+    """run_denoise for the instances of one context, resident: _denoise_resident's lanes, one fvad_egress over every file --
+    with `filters` (_denoised_filters) over the files that leave at 48 kHz, and one fvad_egress_resample per other ratio"""
     if not audio:
         return []
     held = []
@@ -938,9 +1010,15 @@ def _denoise_share(ctx, plan, insts, audio, out_dir, fmt):
         for i in r.order:
             lane0[i] = l
             l += _dims(audio[i])[0]
-        files = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000) for inst, a, n in zip(insts, audio, r.n_chunks)]
-        sinks = [f.sink(0, f.manifest["frames"], lane0[i], 0) for i, f in enumerate(files)]
-        ctx.egress(sinks, d_lanes=r.d_den, n_lanes=r.n_lanes, lane_stride=r.n_den, n_samples=r.n_den, out=[f.map for f in files])
+        files = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000, rs)
+                 for inst, a, n, rs in zip(insts, audio, r.n_chunks, filters or [None] * len(insts))]
+        lanes = dict(d_lanes=r.d_den, n_lanes=r.n_lanes, lane_stride=r.n_den, n_samples=r.n_den)
+        plain = [i for i, f in enumerate(files) if f.rs is None]
+        if plain:
+            ctx.egress([files[i].sink(0, files[i].manifest["frames"], lane0[i], 0) for i in plain], out=[files[i].map for i in plain], **lanes)
+        for rs, idx in _by_filter([(f.rs, i) for i, f in enumerate(files) if f.rs is not None]):
+            rows = [files[i].sink_resampled(files[i].manifest["frames"], lane0[i], 0, 0, files[i].stream_frames) for i in idx]
+            ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for i in idx], **lanes)
         return [f.manifest for f in files]
     finally:
         for f in files:
@@ -949,14 +1027,22 @@ def _denoise_share(ctx, plan, insts, audio, out_dir, fmt):
             ctx.device_free(d)
 
 
-def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks):
+def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, filters=None):
     """run_denoise(slice_chunks=N) for the instances of one context: channel-count group after group in time slices [s0, s1) of
     N chunks, read and denoised as a sliced grid's (_slice_denoise_and_bands, without bands; audio mapped or raw); each slice's
     frames go to their place in the files -- byte 44 + s0 * 24000 * frame bytes -- in one fvad_egress over the group's members
-    that still have chunks there.  The device holds one slice and its halo."""
+    that still have chunks there.  The device holds one slice and its halo.
+    A member that leaves at another rate (`filters`) cannot finish, in a slice, the outputs whose filter window reaches into the
+    next one: it writes the outputs [written, fvad_egress_resample_ready(frames up to the slice's end)) and leaves the others to
+    the next slice, which reads their window's older part from its halo -- the slice buffer from chunk max(s0 - H, 0) on is what
+    the row is given.  The halo's chunks from the third on are the resident run's (SLICE_HALO_CHUNKS' comment), and the filter
+    reaches no further back than that.  A member's last slice has the stream's last sample and writes everything that is left."""
     if not audio:
         return []
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
+    for rs in filters or ():
+        # the outputs a slice defers read at most (2 K + down) / up + 1 samples below the slice's first: inside the halo's exact part
+        assert rs is None or (rs["taps"].size - 1 + rs["down"]) // rs["up"] + 1 <= (H - 2) * chunk, "the halo covers the filter's reach"
     dims = [_dims(a, mapped=True) for a in audio]
     n_chunks = [d[1] // chunk for d in dims]
     groups = {}
@@ -975,7 +1061,7 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks):
         if not _is_raw(audio):
             host = ctx.host_alloc(lanes_max * n_max * chunk)
         buf = _SliceBufs(d, host, opts, N * chunk // F)
-        files = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk) for inst, dm, n in zip(insts, dims, n_chunks)]
+        files = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk, rs) for inst, dm, n, rs in zip(insts, dims, n_chunks, filters or [None] * len(insts))]
         for nch, members in groups.items():
             L = len(members) * nch
             K = max(n_chunks[i] for i in members)
@@ -985,8 +1071,15 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks):
                 n = s1 - start
                 _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, (), times)
                 live = [(k, i) for k, i in enumerate(members) if n_chunks[i] > s0]
-                sinks = [files[i].sink(s0 * chunk, (min(n_chunks[i], s1) - s0) * chunk, k * nch, (s0 - start) * chunk) for k, i in live]
-                ctx.egress(sinks, d_lanes=d["den"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk, out=[files[i].map for _, i in live])
+                lanes = dict(d_lanes=d["den"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk)
+                plain = [(k, i) for k, i in live if files[i].rs is None]
+                if plain:
+                    sinks = [files[i].sink(s0 * chunk, (min(n_chunks[i], s1) - s0) * chunk, k * nch, (s0 - start) * chunk) for k, i in plain]
+                    ctx.egress(sinks, out=[files[i].map for _, i in plain], **lanes)
+                for rs, ki in _by_filter([(files[i].rs, (k, i)) for k, i in live if files[i].rs is not None]):
+                    rows = [files[i].sink_resampled(files[i].ready(min(s1, n_chunks[i]) * chunk), k * nch, 0, start * chunk,
+                                                    (min(n_chunks[i], s1) - start) * chunk) for k, i in ki]
+                    ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for _, i in ki], **lanes)
         return [f.manifest for f in files]
     finally:
         for f in files:
@@ -997,7 +1090,7 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks):
             ctx.host_free(host)
 
 
-def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None):
+def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, rate=None):
     """The plan's recordings, denoised, as WAV files: per instance NAME-denoised.wav in out_dir with all of the instance's
     channels at 48 kHz, as PCM16 (fmt "pcm16": rint(clamp(y * 32768)), the rule of the PCM16 clips and of
     fvad_lane.denoised_i16, not fvad_wav_write's), 24-bit PCM ("pcm24") or float32 ("f32": the lanes' bits, the file
@@ -1007,27 +1100,39 @@ def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devi
     run_clips; the denoising is _denoise_resident's (the context option "reproducible" makes it agree bit for bit with every
     other path), or with slice_chunks N the sliced grid's, device memory bounded by a slice -- the same bytes.  ingest "device":
     the files' bytes are decoded on the GPU (run_grid); the same bytes again.  A bad fmt, ingest or slice_chunks raises before
-    any work.  Returns a manifest per instance, in plan order: name, file, format, channels, frames, sample_rate."""
+    any work.  Returns a manifest per instance, in plan order: name, file, format, channels, frames, sample_rate.
+    rate: None or 48000 write the lanes' own 48 kHz.  An integer R writes every file at R, and "source" each instance at its own
+    file's rate (what ingest="device" resampled it from; 48000 otherwise): fvad_egress_resample with fvad_resample_design's
+    default taps for up/down = R/48000, one call per distinct ratio, beside fvad_egress for the instances at 48000.  Such a file
+    holds ceil(frames up / down) frames, output o at o / R seconds of the recording; its manifest says the resampled frames and
+    sample_rate and gains "resample": {up, down, half, cutoff, beta}.  Sliced, device-ingested and resident runs write the same
+    bytes on a "reproducible" context.  A rate without a ratio (up <= 640), a default design that does not fit, frames that
+    fit no tile or more than 4 GB of data raise ValueError before any work."""
     _check_ingest(ingest)
     _check_denoised_format(fmt)
+    _check_denoised_rate(rate)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
         check_slice_chunks(slice_chunks, plan["fft_size"])
     own_ctx = ctx is None
     ctxs = [_make_ctx(plan, d, synth_seed) for d in (devices or [0])] if own_ctx else [ctx]
     try:
-        os.makedirs(out_dir, exist_ok=True)
         audio = [a for a, _ in _load_instances(plan, ingest, mapped=slice_chunks is not None)]
+        filters = None
+        if rate is not None and (isinstance(rate, str) or rate != 48000):
+            filters = _denoised_filters(rate, audio, [_dims(a, mapped=slice_chunks is not None) for a in audio], fmt)
+        os.makedirs(out_dir, exist_ok=True)
         parts = instance_shares(len(audio), len(ctxs))
         done, errs = [None] * len(ctxs), []
 
         def work(d):
             try:
                 insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
+                filters_d = None if filters is None else [filters[i] for i in parts[d]]
                 if slice_chunks is None:
-                    done[d] = _denoise_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt)
+                    done[d] = _denoise_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, filters_d)
                 else:
-                    done[d] = _denoise_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, slice_chunks)
+                    done[d] = _denoise_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, slice_chunks, filters_d)
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -2349,6 +2454,10 @@ def arg_parser():
                          "takes --slice-chunks, --ingest and --devices")
     ap.add_argument("--denoised-format", default=None, choices=tuple(DENOISED_FORMATS),
                     help="with --export-denoised: pcm16 (the default), pcm24 or f32")
+    ap.add_argument("--denoised-rate", default=None, metavar="R|source",
+                    help="with --export-denoised: write the recordings at R Hz instead of 48000 (44100, 32000, 22050, 16000 ...: any rate "
+                         "whose ratio to 48000 has up <= 640), or with `source` each at its own file's rate (known with --ingest device); "
+                         "resampled on the GPU in front of the conversion (fvad_egress_resample)")
     ap.add_argument("--ingest", default="host", choices=INGESTS,
                     help="with --sweep / --sweep-grid / --export-clips / --export-denoised: where the files' samples are de-interleaved and decoded -- on "
                          "the host, uploaded as f32 (the default), or on the GPU from the files' own bytes (fvad_ingest: PCM16 crosses "
@@ -2359,13 +2468,25 @@ def arg_parser():
 
 def check_modes(a):
     """--export-denoised is a mode of its own: ValueError, before any work, when it is combined with a sweep or the clip export,
-    or when --denoised-format comes without it"""
+    or when --denoised-format or --denoised-rate comes without it"""
     if a.export_denoised:
         others = [name for name, on in (("--sweep", a.sweep), ("--sweep-grid", a.sweep_grid), ("--export-clips", a.export_clips)) if on]
         if others:
             raise ValueError(f"--export-denoised cannot be combined with {', '.join(others)} (one pass writes one kind of output)")
     elif a.denoised_format is not None:
         raise ValueError("--denoised-format needs --export-denoised")
+    elif a.denoised_rate is not None:
+        raise ValueError("--denoised-rate needs --export-denoised")
+
+
+def _parse_denoised_rate(text):
+    """--denoised-rate's value: None, "source" or an integer (anything else: ValueError, as run_denoise says it)"""
+    if text is None or text == "source":
+        return text
+    try:
+        return int(text)
+    except ValueError:
+        raise ValueError(f"--denoised-rate {text!r}: a sample rate or `source`") from None
 
 
 def main(argv=None):
@@ -2374,8 +2495,9 @@ def main(argv=None):
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.export_denoised:
         for m in run_denoise(a.input, a.export_denoised, fmt=a.denoised_format or "pcm16", synth_seed=a.synth_seed, devices=devices,
-                             ingest=a.ingest, slice_chunks=a.slice_chunks):
-            sys.stdout.write(f"{m['file']}: {m['channels']} x {m['frames']} frames, {m['format']}\n")
+                             ingest=a.ingest, slice_chunks=a.slice_chunks, rate=_parse_denoised_rate(a.denoised_rate)):
+            at = "" if m["sample_rate"] == 48000 else f" at {m['sample_rate']} Hz"
+            sys.stdout.write(f"{m['file']}: {m['channels']} x {m['frames']} frames, {m['format']}{at}\n")
         return
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,

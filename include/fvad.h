@@ -1254,6 +1254,76 @@ int fvad_egress_device(fvad_ctx *ctx, const void *d_lanes, int src_format, size_
 int fvad_egress(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                 const uint64_t *sinks, size_t n_sinks, void *const *dst_host);
 
+/* ------------------------------------------------------------------ resampling egress: denoised recordings at another rate
+ * fvad_egress writes a recording at the lanes' 48 kHz.  A corpus at 44.1 kHz (32 kHz, 16 kHz ...) wants its denoised recordings
+ * back at its own rate: ONE kernel (csrc/kernels_egress_resample.hip) is the egress kernel with the rational polyphase resampler
+ * of the clip export in front of its conversion.  The lanes never leave the device as f32, the host does no per-sample work.
+ * THE DEFINITION
+ * - Source lanes are planar f32 at 48 kHz (FVAD_INGEST_F32, laid out as for fvad_egress).  PCM16 lanes are refused with
+ *   FVAD_ERR_INVALID_ARGUMENT, as the resampling ingest refuses PCM16 lanes.
+ * - up/down = rate_out/48000 in lowest terms, as fvad_resample_ratio(48000, rate_out, ...) gives it: 44100 is 147/160, 32000
+ *   2/3, 16000 1/3.  1 <= up <= FVAD_RESAMPLE_UP_MAX, down >= 1.  The taps are an odd count n_taps <= FVAD_RESAMPLE_TAPS_MAX in
+ *   host memory with centre K = (n_taps - 1) / 2; they need not be symmetric.  One ratio and one set of taps per call.
+ * - A stream of stream_frames lane samples per channel has out_frames = ceil(stream_frames * up / down) output frames
+ *   (fvad_resample_out_frames).  Output o of channel c is
+ *       y[o] = sum over n of x_c[n] * taps[K + o * down - n * up],   over every n whose tap index lies in [0, 2 K],
+ *   x_c the stream's samples of lane first_lane + c and 0 outside [0, stream_frames), accumulated in f32 as one fma chain from
+ *   +0 (the chain's order is kernels_clips_resample.hip's and, as there, not part of the contract).  The filter is centred: output
+ *   o sits at time o / rate_out of the stream.  y is converted to the file's format by fvad_egress's rules for f32 lanes: f32
+ *   keeps the value, PCM16 is rint(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)), PCM24 the same with 8388608 / 8388607, its
+ *   low three bytes.  Sample (o, c) is written little-endian at byte_offset + ((o - out_from) * n_channels + c) * bytes per
+ *   sample.
+ * - A sink row is FVAD_EGRESS_RESAMPLE_FIELDS uint64: byte_offset (where output out_from goes), n_out, n_channels (1 .. 64),
+ *   format (the FILE's, FVAD_INGEST_*), first_lane, src_offset (the lane sample that holds stream sample frame_base),
+ *   frame_base, n_frames (the lanes hold the stream samples [frame_base, frame_base + n_frames) for this row), stream_frames,
+ *   out_from.  A recording is a stream, not a finite clip: a time slice cannot finish the outputs whose window reaches into the
+ *   next slice, so a row names its outputs [out_from, out_from + n_out) and the frames it is given apart, as the resampling
+ *   ingest's row does.  The given frames must cover fvad_resample_window(up, down, n_taps, stream_frames, out_from, n_out); a
+ *   superset is fine.  Nothing outside [src_offset, src_offset + n_frames) of a lane is read, nothing outside the given frames
+ *   and [0, stream_frames) enters a sum.  Index arithmetic is 64-bit (o * down passes 2^32 after 11 minutes at 147/160);
+ *   stream_frames * up must stay below 2^62.
+ * - INVARIANTS, all bit for bit.  A stream's bytes do not depend on how it is cut into rows or calls (time slices, any out_from,
+ *   any superset of the window), on the order of the rows or the other rows of the call, on which tile of the kernel an output
+ *   falls in, on the call form (device bytes or host bytes), on ingest_ring_bytes or on the alignment of either side.  The PCM16
+ *   and PCM24 bytes of an output are the conversion of the f32 value the same row gives as an f32 file.  No byte outside a row's
+ *   range is written, also where another row touches it.  No atomics.  up == down == 1 with the single tap 1.0 gives
+ *   fvad_egress's bytes, a -0.0 sample apart (fma(1, -0, +0) is +0).
+ *
+ * Host only (csrc/host_egress_resample.cpp, the rules in csrc/egress_resample.h):
+ * fvad_egress_resample_tile: the kernel's output frames per tile for frames of n_channels samples of `format`: the most, a
+ *   multiple of 4, whose bytes fit the egress's 16 KB tile and whose window of one channel fits the 8192 lane samples a tile
+ *   stages; 0 when not even 4 outputs' window fits (such a row is refused) or for arguments that are none.
+ * fvad_egress_resample_ready: the number of leading outputs of a stream whose whole window lies below frames_have: out_frames
+ *   when frames_have >= stream_frames, otherwise ceil((frames_have * up - K) / down) clamped to [0, out_frames] (128-bit
+ *   intermediates); 0 for a ratio or a tap count that is none.  What a sliced caller can finish with the frames it has.
+ * fvad_egress_resample_check: every argument rule of the two calls below, in this order: FVAD_ERR_INVALID_ARGUMENT for a
+ *   src_format other than FVAD_INGEST_F32, a ratio that is none, taps that fail (NULL, an even or zero count, more than
+ *   FVAD_RESAMPLE_TAPS_MAX, a non-finite tap); n_sinks == 0 succeeds here; NULL sinks, lane_stride < n_samples with several
+ *   lanes; then per row FVAD_ERR_INVALID_ARGUMENT for a bad format, n_channels outside 1 .. 64, stream_frames * up >= 2^62,
+ *   out_from + n_out > out_frames(stream_frames), given frames that leave the stream, given frames that do not cover
+ *   fvad_resample_window of the row, a tile of 0; then per row FVAD_ERR_OUT_OF_RANGE for lanes past n_lanes, src_offset +
+ *   n_frames > n_samples, byte_offset + bytes > out_bytes (all sums checked for 64-bit overflow); then
+ *   FVAD_ERR_INVALID_ARGUMENT when two rows' byte ranges overlap (ranges that touch are fine).  A row with n_out == 0 writes
+ *   nothing.
+ * fvad_egress_resample_device / fvad_egress_resample: fvad_egress_device's and fvad_egress's forms.  Both run the check (and
+ *   refuse NULL pointers and lanes not aligned to 4 bytes) before any launch, return when the bytes are written and name
+ *   `egress_resample` in fvad_ctx_kernel_times (one launch per file format present, fewer than 2^24 tiles each).  The tap table
+ *   is uploaded once per call.  The host form goes through the ring fvad_ingest and fvad_egress use and cuts a row into pieces
+ *   in OUTPUT frames at multiples of 4: a piece is the row with out_from advanced and the same given frames (the lanes are on
+ *   the device already: no window is copied), so the bytes cannot depend on the cut. */
+#define FVAD_EGRESS_RESAMPLE_FIELDS 10
+uint64_t fvad_egress_resample_tile(uint32_t up, uint32_t down, uint32_t n_taps, uint32_t n_channels, uint32_t format);
+uint64_t fvad_egress_resample_ready(uint32_t up, uint32_t down, uint32_t n_taps, uint64_t stream_frames, uint64_t frames_have);
+int fvad_egress_resample_check(const uint64_t *sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down,
+                               const float *taps, uint32_t n_taps, int src_format, size_t n_lanes, size_t lane_stride,
+                               size_t n_samples);
+int fvad_egress_resample_device(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride,
+                                size_t n_samples, const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down,
+                                const float *taps, uint32_t n_taps, void *d_out, uint64_t out_bytes);
+int fvad_egress_resample(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                         const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down, const float *taps, uint32_t n_taps,
+                         void *const *dst_host);
+
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
 typedef struct {
