@@ -26,6 +26,7 @@ pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
 pub const egress_fields = 6; // FVAD_EGRESS_FIELDS: a sink is a row of byte_offset, n_frames, n_channels, format, first_lane, src_offset (u64 each)
 pub const egress_resample_fields = 10; // FVAD_EGRESS_RESAMPLE_FIELDS: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from (u64 each)
+pub const egress_mix_fields = 8; // FVAD_EGRESS_MIX_FIELDS: egress_fields' six (src_offset: into the denoised lanes), then orig_offset, orig_zeros (u64 each)
 pub const wav_header_bytes = 44; // FVAD_WAV_HEADER_BYTES
 pub const resample_fields = 11; // FVAD_RESAMPLE_FIELDS: ingest_fields' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
 pub const resample_up_max = 640; // FVAD_RESAMPLE_UP_MAX
@@ -286,6 +287,7 @@ pub extern "c" fn fvad_nsnet2_window(window320: [*]f32) void;
 pub extern "c" fn fvad_nsnet2_create(ctx: *Ctx, sample_rate: usize, out: *?*NSNet2) c_int;
 pub extern "c" fn fvad_nsnet2_destroy(d: ?*NSNet2) void;
 pub extern "c" fn fvad_nsnet2_chunk_size(in_sample_rate: usize) usize;
+pub extern "c" fn fvad_nsnet2_delay(in_sample_rate: usize, delay: ?*u64) c_int;
 pub extern "c" fn fvad_nsnet2_denoise(d: *NSNet2, first: ?[*]const f32, n_first: usize, second: ?[*]const f32, n_second: usize, denoised_result: [*]f32, n_result: usize) c_int;
 
 // batched engine
@@ -478,6 +480,10 @@ pub extern "c" fn fvad_egress_resample_ready(up: u32, down: u32, n_taps: u32, st
 pub extern "c" fn fvad_egress_resample_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_egress_resample_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_out: ?*anyopaque, out_bytes: u64) c_int;
 pub extern "c" fn fvad_egress_resample(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, dst_host: ?[*]const ?*anyopaque) c_int;
+// two-source egress: the original lanes beside the denoised ones, weighted and summed in front of the conversion
+pub extern "c" fn fvad_egress_mix_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, src_format: c_int, w_orig: f32, w_den: f32, n_lanes: usize, orig_stride: usize, orig_samples: usize, den_stride: usize, den_samples: usize) c_int;
+pub extern "c" fn fvad_egress_mix_device(ctx: *Ctx, d_orig: ?*const anyopaque, orig_stride: usize, orig_samples: usize, d_den: ?*const anyopaque, den_stride: usize, den_samples: usize, src_format: c_int, n_lanes: usize, w_orig: f32, w_den: f32, sinks: ?[*]const u64, n_sinks: usize, d_out: ?*anyopaque, out_bytes: u64) c_int;
+pub extern "c" fn fvad_egress_mix(ctx: *Ctx, d_orig: ?*const anyopaque, orig_stride: usize, orig_samples: usize, d_den: ?*const anyopaque, den_stride: usize, den_samples: usize, src_format: c_int, n_lanes: usize, w_orig: f32, w_den: f32, sinks: ?[*]const u64, n_sinks: usize, dst_host: ?[*]const ?*anyopaque) c_int;
 pub extern "c" fn fvad_wav_read(path: [*:0]const u8, channel_pcm: *[*][*]f32, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;
 pub extern "c" fn fvad_wav_free(channel_pcm: ?[*][*]f32, n_channels: usize) void;
 pub extern "c" fn fvad_wav_read_i16(path: [*:0]const u8, channel_pcm: *[*][*]i16, n_channels: *usize, n_frames: *usize, sample_rate: *usize) c_int;

@@ -39,6 +39,7 @@ RESAMPLE_UP_MAX = 640            # FVAD_RESAMPLE_UP_MAX
 RESAMPLE_TAPS_MAX = 20481        # FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1)
 EGRESS_FIELDS = 6                # a sink: byte_offset, n_frames, n_channels, format (the file's), first_lane, src_offset (uint64 each)
 EGRESS_RESAMPLE_FIELDS = 10      # a resampled sink: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from
+EGRESS_MIX_FIELDS = 8            # a two-source sink: EGRESS_FIELDS' six (src_offset: into the denoised lanes), then orig_offset, orig_zeros
 WAV_HEADER_BYTES = 44            # FVAD_WAV_HEADER_BYTES: fvad_wav_header's canonical header
 INGEST_FILL_TILE = 8192          # kIngestFillTile: the zeros of one lane a workgroup writes
 NN_TAP_LAYERS = {"h1": 0, "h2": 1, "f2": 2, "f3": 3, "gains": 4}
@@ -203,6 +204,7 @@ SIGNATURES = {
     "fvad_nsnet2_create": (C.c_int, [vp, sz, C.POINTER(vp)]),
     "fvad_nsnet2_destroy": (None, [vp]),
     "fvad_nsnet2_chunk_size": (sz, [sz]),
+    "fvad_nsnet2_delay": (C.c_int, [sz, C.POINTER(C.c_uint64)]),
     "fvad_nsnet2_denoise": (C.c_int, [vp, c_float_p, sz, c_float_p, sz, c_float_p, sz]),
     "fvad_lane_state_create": (C.c_int, [vp, C.POINTER(vp)]),
     "fvad_lane_state_reset": (None, [vp]),
@@ -391,6 +393,9 @@ SIGNATURES = {
     "fvad_egress_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, sz, sz, sz]),
     "fvad_egress_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, vp, C.c_uint64]),
     "fvad_egress": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.POINTER(vp)]),
+    "fvad_egress_mix_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_int, C.c_float, C.c_float, sz, sz, sz, sz, sz]),
+    "fvad_egress_mix_device": (C.c_int, [vp, vp, sz, sz, vp, sz, sz, C.c_int, sz, C.c_float, C.c_float, C.POINTER(C.c_uint64), sz, vp, C.c_uint64]),
+    "fvad_egress_mix": (C.c_int, [vp, vp, sz, sz, vp, sz, sz, C.c_int, sz, C.c_float, C.c_float, C.POINTER(C.c_uint64), sz, C.POINTER(vp)]),
     "fvad_egress_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "fvad_egress_resample_ready": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
     "fvad_egress_resample_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_int, sz, sz, sz]),
@@ -933,6 +938,37 @@ class Context:
             return
         self._ck(lib().fvad_egress_device(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, vp(out), int(out_bytes or 0)),
                  "fvad_egress_device")
+
+    def egress_mix(self, sinks, w_orig, w_den, d_orig=None, orig_stride=0, orig_samples=0, d_den=None, den_stride=0, den_samples=0, n_lanes=0,
+                   src_pcm16=False, out=None, out_bytes=None):
+        """fvad_egress_mix_device (out: a device address holding out_bytes bytes) or fvad_egress_mix (out: a list with one
+        writable C-contiguous numpy / memmap byte buffer per sink, or None for a sink without frames; a sink's byte_offset is
+        relative to its own buffer): sinks [n][EGRESS_MIX_FIELDS] uint64 <- w_orig * the original lanes at device address d_orig
+        (n_lanes of orig_samples float32, orig_stride apart) + w_den * the denoised lanes at d_den, converted to each sink's file
+        format and interleaved.  The lanes of a zero weight are not read and may be None (src_pcm16 lanes are refused by the
+        library).  Returns when the bytes are written."""
+        sinks = _egress_mix_rows(sinks)
+        n = sinks.shape[0]
+        rows = sinks.ctypes.data_as(C.POINTER(C.c_uint64))
+        head = (self.h, vp(d_orig), orig_stride, orig_samples, vp(d_den), den_stride, den_samples, INGEST_PCM16 if src_pcm16 else INGEST_F32,
+                n_lanes, float(w_orig), float(w_den), rows, n)
+        if isinstance(out, (list, tuple)):
+            if len(out) != n:
+                raise ValueError(f"egress_mix: {n} sinks, {len(out)} buffers")
+            ptrs = (vp * max(n, 1))()
+            for i, b in enumerate(out):
+                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no frames: no byte is written, whatever byte_offset says
+                    ptrs[i] = None
+                    continue
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
+                    raise ValueError("egress_mix: a sink's bytes are a writable C-contiguous uint8 array")
+                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
+                if need > b.size:   # (the library cannot know where a host buffer ends)
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress_mix", f"sink {i} writes {need} bytes of a buffer of {b.size}")
+                ptrs[i] = b.ctypes.data
+            self._ck(lib().fvad_egress_mix(*head, ptrs), "fvad_egress_mix")
+            return
+        self._ck(lib().fvad_egress_mix_device(*head, vp(out), int(out_bytes or 0)), "fvad_egress_mix_device")
 
     def egress_resample(self, sinks, up, down, taps, src_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, out=None, out_bytes=None):
         """fvad_egress_resample_device (out: a device address holding out_bytes bytes) or fvad_egress_resample (out: a list with
@@ -1817,6 +1853,25 @@ def egress_check(sinks, out_bytes, src_pcm16, n_lanes, lane_stride, n_samples):
     sinks = _egress_rows(sinks)
     return lib().fvad_egress_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes),
                                    INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def _egress_mix_rows(sinks):
+    return np.ascontiguousarray(np.asarray(sinks, np.uint64).reshape(-1, EGRESS_MIX_FIELDS))
+
+
+def egress_mix_check(sinks, out_bytes, w_orig, w_den, n_lanes, orig_stride, orig_samples, den_stride, den_samples, src_pcm16=False):
+    """fvad_egress_mix_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sinks = _egress_mix_rows(sinks)
+    return lib().fvad_egress_mix_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes),
+                                       INGEST_PCM16 if src_pcm16 else INGEST_F32, float(w_orig), float(w_den), n_lanes, orig_stride,
+                                       orig_samples, den_stride, den_samples)
+
+
+def nsnet2_delay(sample_rate):
+    """fvad_nsnet2_delay: the samples (of sample_rate) by which NSNet2's denoised output lags its input, 482 at 48000"""
+    d = C.c_uint64(0)
+    check(lib().fvad_nsnet2_delay(int(sample_rate), C.byref(d)), "fvad_nsnet2_delay")
+    return int(d.value)
 
 
 def _egress_resample_rows(sinks):

@@ -10,7 +10,9 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
                                                       --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
     python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source]   (or: run_denoise(path,
                                                       DIR): the denoised recordings as WAV files, converted and interleaved
-                                                      on the GPU)
+                                                      on the GPU; --denoised-kinds denoised,original,residual,mix
+                                                      --denoised-mix W: the time-aligned original, what was removed and a
+                                                      wet/dry mix beside them)
     python -m ... simulator.py -i plan.json --sweep   (or: run_sweep(path): every config of the plan, one table row each)
     python -m ... simulator.py -i plan.json --sweep-grid grid.json [--top K] [--devices 0,1]   (or: run_grid(path, grid): a
                                                       parameter grid, every machine scored on the GPU, the top K configs by
@@ -948,19 +950,71 @@ def _by_filter(pairs):
     return list(groups.values())
 
 
+DENOISED_KINDS = ("denoised", "original", "residual", "mix")
+
+
+def _check_denoised_kinds(kinds, mix, rate):
+    """run_denoise's kinds / mix -> None (today's single denoised file) or the kinds as a tuple; ValueError for an unknown or
+    repeated kind, no kind at all, a mix outside (0, 1), a mix without the kind "mix" or the kind without a mix, and for
+    another rate than the lanes' together with a kind that reads the original (the resampling egress has one source)"""
+    if kinds is None:
+        if mix is not None:
+            raise ValueError("run_denoise: mix comes with the kind 'mix' (kinds=(..., 'mix'))")
+        return None
+    if isinstance(kinds, str) or not isinstance(kinds, (list, tuple)) or not kinds:
+        raise ValueError(f"run_denoise: kinds {kinds!r} (a sequence of {', '.join(DENOISED_KINDS)})")
+    for k in kinds:
+        if k not in DENOISED_KINDS:
+            raise ValueError(f"run_denoise: kind {k!r} (one of {', '.join(DENOISED_KINDS)})")
+    if len(set(kinds)) != len(kinds):
+        raise ValueError(f"run_denoise: kinds {kinds!r} name a kind twice")
+    if "mix" in kinds:
+        if isinstance(mix, bool) or not isinstance(mix, (int, float, np.integer, np.floating)) or not 0.0 < float(mix) < 1.0:
+            raise ValueError(f"run_denoise: the kind 'mix' needs mix=W with 0 < W < 1 (mix: {mix!r})")
+    elif mix is not None:
+        raise ValueError("run_denoise: mix comes with the kind 'mix' (kinds=(..., 'mix'))")
+    if any(k != "denoised" for k in kinds) and not (rate is None or (not isinstance(rate, (bool, str)) and rate == 48000)):
+        raise ValueError(f"run_denoise: rate {rate!r} with kinds {tuple(kinds)!r}: the kinds that read the original are written at 48000 only")
+    return tuple(kinds)
+
+
+def _kind_weights(kind, mix):
+    """(w_orig, w_den) of a kind of fvad_egress_mix, float32: the aligned original, what the denoiser removed, or W of the
+    denoised and the rest (1 - W, in float32) of the aligned original"""
+    if kind == "original":
+        return np.float32(1.0), np.float32(0.0)
+    if kind == "residual":
+        return np.float32(1.0), np.float32(-1.0)
+    return np.float32(1.0) - np.float32(mix), np.float32(mix)
+
+
+def _kind_entry(f, kind, mix, delay):
+    """a kind's entry of an instance's manifest: the file's own manifest without the name, the kind, its weights (None for the
+    denoised file, which fvad_egress writes) and the delay of its frames behind the input file's"""
+    w = (None, None) if kind == "denoised" else tuple(float(x) for x in _kind_weights(kind, mix))
+    e = {k: v for k, v in f.manifest.items() if k != "name"}
+    e.update(kind=kind, w_orig=w[0], w_den=w[1], delay=delay)
+    return e
+
+
+def _kind_manifests(insts, kinds, files, mix, delay):
+    """[instance] {"name", "kinds": [entry per kind, in the order asked for]} from files {kind: [instance's _DenoisedFile]}"""
+    return [{"name": inst["name"], "kinds": [_kind_entry(files[k][i], k, mix, delay) for k in kinds]} for i, inst in enumerate(insts)]
+
+
 class _DenoisedFile:
-    """NAME-denoised.wav of one instance, created at its final size -- fvad_wav_header's 44 bytes, then a hole of n_frames
+    """NAME-denoised.wav of one instance (NAME-<kind>.wav for another kind of run_denoise), created at its final size -- fvad_wav_header's 44 bytes, then a hole of n_frames
     frames -- and mapped for fvad_egress to fill (`map`: the whole file as bytes, None for a file without frames).  With a
     filter `rs` (_denoised_resample) the file holds the ceil(n_frames up / down) frames of the stream of n_frames lane samples
     at the filter's rate, for fvad_egress_resample to fill."""
 
-    def __init__(self, out_dir, inst, fmt, n_channels, n_frames, rs=None):
+    def __init__(self, out_dir, inst, fmt, n_channels, n_frames, rs=None, kind="denoised"):
         code = DENOISED_FORMATS[fmt]
         self.frame_bytes = n_channels * fv.INGEST_SAMPLE_BYTES[code]
         self.rs, self.stream_frames, self.written, rate = rs, n_frames, 0, 48000
         if rs is not None:
             n_frames, rate = fv.resample_out_frames(n_frames, rs["up"], rs["down"]), rs["rate"]
-        self.manifest = {"name": inst["name"], "file": os.path.join(out_dir, f"{inst['name']}-denoised.wav"), "format": fmt,
+        self.manifest = {"name": inst["name"], "file": os.path.join(out_dir, f"{inst['name']}-{kind}.wav"), "format": fmt,
                          "channels": n_channels, "frames": n_frames, "sample_rate": rate}
         if rs is not None:
             self.manifest["resample"] = {k: rs[k] for k in ("up", "down", "half", "cutoff", "beta")}
@@ -975,6 +1029,11 @@ class _DenoisedFile:
         """the fvad_egress sink row of the file's frames [frame_from, frame_from + n_frames)"""
         n_channels, code = self.manifest["channels"], DENOISED_FORMATS[self.manifest["format"]]
         return (fv.WAV_HEADER_BYTES + frame_from * self.frame_bytes, n_frames, n_channels, code, first_lane, src_offset)
+
+    def sink_mix(self, frame_from, n_frames, first_lane, src_offset, orig_offset, orig_zeros):
+        """the fvad_egress_mix row of the file's frames [frame_from, frame_from + n_frames): sink()'s, then where the original
+        lanes' partner of the first frame behind the orig_zeros leading zeros lies"""
+        return self.sink(frame_from, n_frames, first_lane, src_offset) + (orig_offset, orig_zeros)
 
     def sink_resampled(self, out_to, first_lane, src_offset, frame_base, n_frames):
         """the fvad_egress_resample row of the file's outputs [written, out_to), which then count as written; the lanes hold the
@@ -992,9 +1051,12 @@ class _DenoisedFile:
         self.map = None   # unmapped without msync: the written pages are the page cache's, as after fvad_wav_write's fwrite + fclose
 
 
-def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None):
+def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None, kinds=None, mix=None):
     """run_denoise for the instances of one context, resident: _denoise_resident's lanes, one fvad_egress over every file --
-    with `filters` (_denoised_filters) over the files that leave at 48 kHz, and one fvad_egress_resample per other ratio"""
+    with `filters` (_denoised_filters) over the files that leave at 48 kHz, and one fvad_egress_resample per other ratio.
+    With `kinds`: the denoised files as before if they are asked for, and per other kind one fvad_egress_mix over the original
+    and the denoised lanes, which both lie on the device: frame n of a file pairs denoised sample n with original sample n - D,
+    D = fvad_nsnet2_delay(48000), zeros in front."""
     if not audio:
         return []
     held = []
@@ -1003,15 +1065,16 @@ def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None):
         held.append(ctx.device_alloc(max(int(nbytes), 4)))
         return held[-1]
 
-    files = []
+    files, mixed = [], {}
     try:
         r = _denoise_resident(ctx, audio, plan["fft_size"], plan["vad_machine_config"], dalloc)
         lane0, l = {}, 0
         for i in r.order:
             lane0[i] = l
             l += _dims(audio[i])[0]
-        files = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000, rs)
-                 for inst, a, n, rs in zip(insts, audio, r.n_chunks, filters or [None] * len(insts))]
+        if kinds is None or "denoised" in kinds:
+            files = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000, rs)
+                     for inst, a, n, rs in zip(insts, audio, r.n_chunks, filters or [None] * len(insts))]
         lanes = dict(d_lanes=r.d_den, n_lanes=r.n_lanes, lane_stride=r.n_den, n_samples=r.n_den)
         plain = [i for i, f in enumerate(files) if f.rs is None]
         if plain:
@@ -1019,15 +1082,27 @@ def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None):
         for rs, idx in _by_filter([(f.rs, i) for i, f in enumerate(files) if f.rs is not None]):
             rows = [files[i].sink_resampled(files[i].manifest["frames"], lane0[i], 0, 0, files[i].stream_frames) for i in idx]
             ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for i in idx], **lanes)
-        return [f.manifest for f in files]
+        if kinds is None:
+            return [f.manifest for f in files]
+        D = fv.nsnet2_delay(48000)
+        both = dict(d_orig=r.d_pcm, orig_stride=r.stride, orig_samples=r.n_samples, d_den=r.d_den, den_stride=r.n_den, den_samples=r.n_den,
+                    n_lanes=r.n_lanes)
+        for kind in kinds:
+            if kind == "denoised":
+                continue
+            mixed[kind] = [_DenoisedFile(out_dir, inst, fmt, _dims(a)[0], n * 24000, kind=kind) for inst, a, n in zip(insts, audio, r.n_chunks)]
+            rows = [f.sink_mix(0, f.manifest["frames"], lane0[i], 0, 0, min(D, f.manifest["frames"])) for i, f in enumerate(mixed[kind])]
+            w_orig, w_den = _kind_weights(kind, mix)
+            ctx.egress_mix(rows, w_orig, w_den, out=[f.map for f in mixed[kind]], **both)
+        return _kind_manifests(insts, kinds, dict(mixed, denoised=files), mix, D)
     finally:
-        for f in files:
+        for f in files + [f for fs in mixed.values() for f in fs]:
             f.close()
         for d in held:
             ctx.device_free(d)
 
 
-def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, filters=None):
+def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, filters=None, kinds=None, mix=None):
     """run_denoise(slice_chunks=N) for the instances of one context: channel-count group after group in time slices [s0, s1) of
     N chunks, read and denoised as a sliced grid's (_slice_denoise_and_bands, without bands; audio mapped or raw); each slice's
     frames go to their place in the files -- byte 44 + s0 * 24000 * frame bytes -- in one fvad_egress over the group's members
@@ -1053,7 +1128,8 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
     lanes_max = max(len(m) * nch for nch, m in groups.items())
     own = {"pcm": lanes_max * n_max * chunk * 4, "den": lanes_max * n_max * chunk * 4, "band0": lanes_max * (n_max * chunk // F + 1) * 4,
            "rms": lanes_max * n_max * 4, "bands": 16}
-    d, host, files = {}, None, []
+    d, host, files, mixed = {}, None, [], {}
+    D = fv.nsnet2_delay(48000) if kinds else 0
     times = collections.defaultdict(float)
     try:
         for k, nb in own.items():
@@ -1061,7 +1137,11 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
         if not _is_raw(audio):
             host = ctx.host_alloc(lanes_max * n_max * chunk)
         buf = _SliceBufs(d, host, opts, N * chunk // F)
-        files = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk, rs) for inst, dm, n, rs in zip(insts, dims, n_chunks, filters or [None] * len(insts))]
+        if kinds is None or "denoised" in kinds:
+            files = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk, rs) for inst, dm, n, rs in zip(insts, dims, n_chunks, filters or [None] * len(insts))]
+        for kind in kinds or ():
+            if kind != "denoised":
+                mixed[kind] = [_DenoisedFile(out_dir, inst, fmt, dm[0], n * chunk, kind=kind) for inst, dm, n in zip(insts, dims, n_chunks)]
         for nch, members in groups.items():
             L = len(members) * nch
             K = max(n_chunks[i] for i in members)
@@ -1072,17 +1152,34 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
                 _slice_denoise_and_bands(ctx, audio, members, nch, s0, s1, buf, (), times)
                 live = [(k, i) for k, i in enumerate(members) if n_chunks[i] > s0]
                 lanes = dict(d_lanes=d["den"], n_lanes=L, lane_stride=n * chunk, n_samples=n * chunk)
-                plain = [(k, i) for k, i in live if files[i].rs is None]
+                plain = [(k, i) for k, i in live if files and files[i].rs is None]
                 if plain:
                     sinks = [files[i].sink(s0 * chunk, (min(n_chunks[i], s1) - s0) * chunk, k * nch, (s0 - start) * chunk) for k, i in plain]
                     ctx.egress(sinks, out=[files[i].map for _, i in plain], **lanes)
-                for rs, ki in _by_filter([(files[i].rs, (k, i)) for k, i in live if files[i].rs is not None]):
+                for rs, ki in _by_filter([(files[i].rs, (k, i)) for k, i in live if files and files[i].rs is not None]):
                     rows = [files[i].sink_resampled(files[i].ready(min(s1, n_chunks[i]) * chunk), k * nch, 0, start * chunk,
                                                     (min(n_chunks[i], s1) - start) * chunk) for k, i in ki]
                     ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for _, i in ki], **lanes)
-        return [f.manifest for f in files]
+                # the other kinds: the slice's frames of the denoised buffer and their partners D samples earlier in the original
+                # buffer, which starts at the same chunk -- in the halo for every slice but the first, whose first D frames are zeros
+                if not mixed:
+                    continue
+                assert s0 == 0 or (s0 - start) * chunk >= D, "the halo covers the delay"
+                both = dict(d_orig=d["pcm"], orig_stride=n * chunk, orig_samples=n * chunk, d_den=d["den"], den_stride=n * chunk,
+                            den_samples=n * chunk, n_lanes=L)
+                for kind, fs in mixed.items():
+                    rows = []
+                    for k, i in live:
+                        frames = (min(n_chunks[i], s1) - s0) * chunk
+                        at = ((s0 - start) * chunk, 0, min(D, frames)) if s0 == 0 else ((s0 - start) * chunk, (s0 - start) * chunk - D, 0)
+                        rows.append(fs[i].sink_mix(s0 * chunk, frames, k * nch, *at))
+                    w_orig, w_den = _kind_weights(kind, mix)
+                    ctx.egress_mix(rows, w_orig, w_den, out=[fs[i].map for _, i in live], **both)
+        if kinds is None:
+            return [f.manifest for f in files]
+        return _kind_manifests(insts, kinds, dict(mixed, denoised=files), mix, D)
     finally:
-        for f in files:
+        for f in files + [f for fs in mixed.values() for f in fs]:
             f.close()
         for a in d.values():
             ctx.device_free(a)
@@ -1090,7 +1187,8 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
             ctx.host_free(host)
 
 
-def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, rate=None):
+def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, rate=None,
+                kinds=None, mix=None):
     """The plan's recordings, denoised, as WAV files: per instance NAME-denoised.wav in out_dir with all of the instance's
     channels at 48 kHz, as PCM16 (fmt "pcm16": rint(clamp(y * 32768)), the rule of the PCM16 clips and of
     fvad_lane.denoised_i16, not fvad_wav_write's), 24-bit PCM ("pcm24") or float32 ("f32": the lanes' bits, the file
@@ -1107,10 +1205,22 @@ def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devi
     holds ceil(frames up / down) frames, output o at o / R seconds of the recording; its manifest says the resampled frames and
     sample_rate and gains "resample": {up, down, half, cutoff, beta}.  Sliced, device-ingested and resident runs write the same
     bytes on a "reproducible" context.  A rate without a ratio (up <= 640), a default design that does not fit, frames that
-    fit no tile or more than 4 GB of data raise ValueError before any work."""
+    fit no tile or more than 4 GB of data raise ValueError before any work.
+    kinds: None is the above and returns what it always returned.  Otherwise a sequence of "denoised", "original", "residual",
+    "mix": per instance and kind NAME-<kind>.wav in fmt, every one with the denoised file's frames, channels and rate.  The
+    denoised samples lag the input's by D = fvad_nsnet2_delay(48000) = 482 samples (include/fvad.h has the derivation), and the
+    input file is 10 ms early, maybe at another rate or format and a partial chunk longer: no partner for an A/B comparison.
+    "original" is the input delayed by D -- frame n is x[n - D], zeros for n < D --, "residual" what the denoiser took out,
+    x[n - D] - y[n], and "mix" (with mix=W, 0 < W < 1) W of the denoised and f32(1) - f32(W) of the delayed original.  They are
+    written by fvad_egress_mix from the original and the denoised lanes where both lie on the device already, one call per
+    kind, no lane memory of their own; the "denoised" kind is today's file, through fvad_egress.  With kinds the manifest of an
+    instance is {"name", "kinds": [one entry per kind: file, kind, w_orig, w_den (None for "denoised"), delay, frames, format,
+    channels, sample_rate]}.  An unknown kind, a mix out of range or without its kind, or a rate other than 48000 together with
+    a kind other than "denoised" raise ValueError before any work."""
     _check_ingest(ingest)
     _check_denoised_format(fmt)
     _check_denoised_rate(rate)
+    kinds = _check_denoised_kinds(kinds, mix, rate)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
         check_slice_chunks(slice_chunks, plan["fft_size"])
@@ -1130,9 +1240,9 @@ def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devi
                 insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
                 filters_d = None if filters is None else [filters[i] for i in parts[d]]
                 if slice_chunks is None:
-                    done[d] = _denoise_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, filters_d)
+                    done[d] = _denoise_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, filters_d, kinds, mix)
                 else:
-                    done[d] = _denoise_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, slice_chunks, filters_d)
+                    done[d] = _denoise_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, fmt, slice_chunks, filters_d, kinds, mix)
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -2458,6 +2568,13 @@ def arg_parser():
                     help="with --export-denoised: write the recordings at R Hz instead of 48000 (44100, 32000, 22050, 16000 ...: any rate "
                          "whose ratio to 48000 has up <= 640), or with `source` each at its own file's rate (known with --ingest device); "
                          "resampled on the GPU in front of the conversion (fvad_egress_resample)")
+    ap.add_argument("--denoised-kinds", default=None, metavar="K[,K...]",
+                    help="with --export-denoised: the files to write per instance, NAME-K.wav each, of denoised, original (the input "
+                         "delayed by the denoiser's 482 samples, so that it lines up with the denoised file), residual (what the denoiser "
+                         "took out: that original minus the denoised) and mix (see --denoised-mix); weighted and summed on the GPU in "
+                         "front of the conversion (fvad_egress_mix); all but denoised at 48000 Hz only")
+    ap.add_argument("--denoised-mix", default=None, type=float, metavar="W",
+                    help="with --denoised-kinds ...,mix: W of the denoised and 1 - W of the aligned original, 0 < W < 1")
     ap.add_argument("--ingest", default="host", choices=INGESTS,
                     help="with --sweep / --sweep-grid / --export-clips / --export-denoised: where the files' samples are de-interleaved and decoded -- on "
                          "the host, uploaded as f32 (the default), or on the GPU from the files' own bytes (fvad_ingest: PCM16 crosses "
@@ -2477,6 +2594,10 @@ def check_modes(a):
         raise ValueError("--denoised-format needs --export-denoised")
     elif a.denoised_rate is not None:
         raise ValueError("--denoised-rate needs --export-denoised")
+    elif a.denoised_kinds is not None:
+        raise ValueError("--denoised-kinds needs --export-denoised")
+    elif a.denoised_mix is not None:
+        raise ValueError("--denoised-mix needs --export-denoised")
 
 
 def _parse_denoised_rate(text):
@@ -2494,10 +2615,13 @@ def main(argv=None):
     check_modes(a)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.export_denoised:
+        kinds = None if a.denoised_kinds is None else tuple(k for k in a.denoised_kinds.split(",") if k != "")
         for m in run_denoise(a.input, a.export_denoised, fmt=a.denoised_format or "pcm16", synth_seed=a.synth_seed, devices=devices,
-                             ingest=a.ingest, slice_chunks=a.slice_chunks, rate=_parse_denoised_rate(a.denoised_rate)):
-            at = "" if m["sample_rate"] == 48000 else f" at {m['sample_rate']} Hz"
-            sys.stdout.write(f"{m['file']}: {m['channels']} x {m['frames']} frames, {m['format']}{at}\n")
+                             ingest=a.ingest, slice_chunks=a.slice_chunks, rate=_parse_denoised_rate(a.denoised_rate), kinds=kinds,
+                             mix=a.denoised_mix):
+            for e in [m] if kinds is None else m["kinds"]:
+                at = "" if e["sample_rate"] == 48000 else f" at {e['sample_rate']} Hz"
+                sys.stdout.write(f"{e['file']}: {e['channels']} x {e['frames']} frames, {e['format']}{at}\n")
         return
     if a.sweep_grid:
         run_grid(a.input, a.sweep_grid, top=a.top, vad_on=a.sweep_vad, json_path=a.sweep_json, synth_seed=a.synth_seed,

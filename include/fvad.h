@@ -181,6 +181,17 @@ typedef struct fvad_nsnet2 fvad_nsnet2;
 int fvad_nsnet2_create(fvad_ctx *ctx, size_t sample_rate, fvad_nsnet2 **out);
 void fvad_nsnet2_destroy(fvad_nsnet2 *d);                               /* NSNet2.zig:144-155 */
 size_t fvad_nsnet2_chunk_size(size_t in_sample_rate);                   /* NSNet2.zig:157-159 */
+/* The lag of the denoised samples behind the input's (host only): denoised[n] belongs to input[n - *delay], in samples of
+ * in_sample_rate = r * 16000.  Two parts.  NSNet2 keeps the previous chunk's last hop in front of its input
+ * (NSNet2.zig:175-197: audio_input[0..n_hop] is the last n_hop samples of the chunk before), so the network's output sample j
+ * belongs to its input sample j - 160: 160 samples of 16 kHz, 160 r of the input.  And the up-sampler writes r - 1 interpolated
+ * samples IN FRONT of every network sample (resample.zig:44-46: "[interp1, interp2, first, ...]"), so network sample j lies at
+ * output index r j + (r - 1), while the down-sampler took it from input index r j (resample.zig:20-21).  Together
+ * denoised[r j + r - 1] belongs to input[r (j - 160)]: *delay = 161 r - 1, 482 at 48000 (160 at 16000, 321 at 32000).  The
+ * interpolated samples in between are a linear blend of two neighbours and have no single partner; at 48000 the samples that
+ * have one are those at 2 modulo 3.  Whoever mixes or subtracts the two without this shift builds a comb filter.
+ * FVAD_ERR_INVALID_SAMPLE_RATE for the rates fvad_nsnet2_create refuses, FVAD_ERR_INVALID_ARGUMENT for NULL. */
+int fvad_nsnet2_delay(size_t in_sample_rate, uint64_t *delay);
 /* NSNet2.denoise(samples: SplitSlice, denoised_result)  NSNet2.zig:161-237.  Host pointers;
  * carries the same cross-chunk state (input hop, overlap-add tail, 4 feature rows,
  * last_sample: NSNet2.zig:27-33). */
@@ -1323,6 +1334,62 @@ int fvad_egress_resample_device(fvad_ctx *ctx, const void *d_lanes, int src_form
 int fvad_egress_resample(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                          const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down, const float *taps, uint32_t n_taps,
                          void *const *dst_host);
+
+/* ------------------------------------------------------------------ two-source egress: the original beside the denoised
+ * fvad_egress writes one lane set.  A user of a denoiser also wants the original to compare against, what was taken out (the
+ * residual) and a wet/dry mix -- all of them functions of the ORIGINAL lanes and the DENOISED lanes, which the engine has on
+ * the device side by side.  ONE kernel (csrc/kernels_egress_mix.hip) is the egress kernel with two sources and two weights;
+ * it needs no third lane set, and each kind of file is one more call.
+ * THE DEFINITION
+ * - Both lane sets are planar f32 (src_format FVAD_INGEST_F32; PCM16 lanes are refused with FVAD_ERR_INVALID_ARGUMENT, as the
+ *   conversions are): d_orig is n_lanes lanes of orig_samples, orig_stride apart, d_den n_lanes lanes of den_samples,
+ *   den_stride apart; lane l of one pairs with lane l of the other.  Nothing needs alignment beyond 4 bytes.
+ * - A sink row is FVAD_EGRESS_MIX_FIELDS uint64: fvad_egress's six -- byte_offset, n_frames, n_channels (1 .. 64), format (the
+ *   FILE's), first_lane, src_offset (into the DENOISED lanes) -- then orig_offset and orig_zeros.  For frame f, channel c:
+ *       y = den[first_lane + c][src_offset + f]
+ *       x = +0.0f                                                  for f < orig_zeros
+ *       x = orig[first_lane + c][orig_offset + (f - orig_zeros)]   otherwise.
+ *   The kernel knows nothing of fvad_nsnet2_delay: the caller states the pairing (a whole recording: src_offset = orig_offset
+ *   = 0, orig_zeros = the delay; a time slice pairs its own buffers with orig_zeros = 0).
+ * - Two finite f32 weights per call, not both zero:
+ *       w_orig == 0:  v = w_den (x) y; the original lanes are not read, d_orig may be NULL;
+ *       w_den == 0:   v = w_orig (x) x; the denoised lanes are not read, d_den may be NULL;
+ *       otherwise:    v = (w_orig (x) x) (+) (w_den (x) y),
+ *   (x) and (+) single f32 operations, each rounded to nearest even, never contracted into an fma: numpy's float32 arithmetic
+ *   is the exact model.  A zero weight never meets an infinity.  (1, 0) is the aligned original, (1, -1) the residual,
+ *   (1 - W, W) a wet/dry mix.
+ * - v is converted and interleaved exactly as fvad_egress converts an f32 lane sample: its bits, PCM16 or PCM24 by the rules
+ *   above.  A NaN input gives a NaN in an f32 file (the payload is not promised) and the minimum in a PCM file.
+ * - INVARIANTS, all bit for bit.  No byte outside [byte_offset, byte_offset + n_frames * n_channels * bytes per sample) of a
+ *   sink is written; no denoised sample outside [src_offset, src_offset + n_frames) and no original sample outside
+ *   [orig_offset, orig_offset + n_frames - min(orig_zeros, n_frames)) of its lanes is read.  The output does not depend on the
+ *   order of the sinks, on how a file is cut into sinks or calls, on ingest_ring_bytes, on the call form (device bytes or host
+ *   bytes), or on the alignment of any of the three sides.  No atomics.  With w_orig = 0, w_den = 1 and no NaN in the lanes
+ *   the bytes are fvad_egress's.
+ *
+ * fvad_egress_mix_check (host only, csrc/host_egress_mix.cpp): every argument rule of the two calls below, in this order:
+ *   FVAD_ERR_INVALID_ARGUMENT for a weight that is not finite, two zero weights, a src_format other than FVAD_INGEST_F32;
+ *   n_sinks == 0 succeeds here; NULL sinks, a stride smaller than its length with several lanes (of a source whose weight is
+ *   not zero); then per sink FVAD_ERR_INVALID_ARGUMENT for a bad format, n_channels outside 1 .. 64; then per sink
+ *   FVAD_ERR_OUT_OF_RANGE for lanes past n_lanes, src_offset + n_frames > den_samples (only when w_den != 0), orig_offset +
+ *   (n_frames - min(orig_zeros, n_frames)) > orig_samples (only when w_orig != 0), byte_offset + bytes > out_bytes (all sums
+ *   checked for 64-bit overflow); then FVAD_ERR_INVALID_ARGUMENT when two sinks' byte ranges overlap (ranges that touch are
+ *   fine).  A sink with n_frames == 0 writes nothing.
+ * fvad_egress_mix_device / fvad_egress_mix: fvad_egress_device's and fvad_egress's forms.  Both run the check (and refuse a NULL
+ *   output, and lanes of a source whose weight is not zero that are NULL or not aligned to 4 bytes) before any launch, return when
+ *   the bytes are written and name `egress_mix` in fvad_ctx_kernel_times (one launch per file format present, fewer than 2^24
+ *   tiles each).  The host form goes through the ring fvad_ingest and fvad_egress use and cuts a sink at multiples of 4 frames:
+ *   the piece from frame k on is the sink with src_offset + k, orig_zeros - min(orig_zeros, k) and orig_offset + k -
+ *   min(orig_zeros, k), so the bytes cannot depend on the cut. */
+#define FVAD_EGRESS_MIX_FIELDS 8
+int fvad_egress_mix_check(const uint64_t *sinks, size_t n_sinks, uint64_t out_bytes, int src_format, float w_orig, float w_den,
+                          size_t n_lanes, size_t orig_stride, size_t orig_samples, size_t den_stride, size_t den_samples);
+int fvad_egress_mix_device(fvad_ctx *ctx, const void *d_orig, size_t orig_stride, size_t orig_samples, const void *d_den,
+                           size_t den_stride, size_t den_samples, int src_format, size_t n_lanes, float w_orig, float w_den,
+                           const uint64_t *sinks, size_t n_sinks, void *d_out, uint64_t out_bytes);
+int fvad_egress_mix(fvad_ctx *ctx, const void *d_orig, size_t orig_stride, size_t orig_samples, const void *d_den,
+                    size_t den_stride, size_t den_samples, int src_format, size_t n_lanes, float w_orig, float w_den,
+                    const uint64_t *sinks, size_t n_sinks, void *const *dst_host);
 
 /* ------------------------------------------------------------------ Evaluator (host)
  * src/Evaluator.zig:90-156 + src/Evaluator/statistics.zig */
