@@ -26,6 +26,7 @@ pub const comm_id_bytes = 128; // FVAD_COMM_ID_BYTES
 pub const ingest_fields = 7; // FVAD_INGEST_FIELDS: a source is a row of byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (u64 each)
 pub const egress_fields = 6; // FVAD_EGRESS_FIELDS: a sink is a row of byte_offset, n_frames, n_channels, format, first_lane, src_offset (u64 each)
 pub const egress_resample_fields = 10; // FVAD_EGRESS_RESAMPLE_FIELDS: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from (u64 each)
+pub const egress_step_max = 16; // FVAD_EGRESS_STEP_MAX: the src_step of fvad_egress_resample_strided* is 1 .. this
 pub const egress_mix_fields = 8; // FVAD_EGRESS_MIX_FIELDS: egress_fields' six (src_offset: into the denoised lanes), then orig_offset, orig_zeros (u64 each)
 pub const wav_header_bytes = 44; // FVAD_WAV_HEADER_BYTES
 pub const resample_fields = 11; // FVAD_RESAMPLE_FIELDS: ingest_fields' seven (n_frames: the frames given), then frame_base, file_frames, out_from, n_out
@@ -480,6 +481,10 @@ pub extern "c" fn fvad_egress_resample_ready(up: u32, down: u32, n_taps: u32, st
 pub extern "c" fn fvad_egress_resample_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
 pub extern "c" fn fvad_egress_resample_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, d_out: ?*anyopaque, out_bytes: u64) c_int;
 pub extern "c" fn fvad_egress_resample(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, dst_host: ?[*]const ?*anyopaque) c_int;
+// strided resampling egress: the same over a stream that lies src_step apart in its lanes (the network's own 16 kHz samples)
+pub extern "c" fn fvad_egress_resample_strided_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_step: u32, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize) c_int;
+pub extern "c" fn fvad_egress_resample_strided_device(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_step: u32, d_out: ?*anyopaque, out_bytes: u64) c_int;
+pub extern "c" fn fvad_egress_resample_strided(ctx: *Ctx, d_lanes: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, sinks: ?[*]const u64, n_sinks: usize, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32, src_step: u32, dst_host: ?[*]const ?*anyopaque) c_int;
 // two-source egress: the original lanes beside the denoised ones, weighted and summed in front of the conversion
 pub extern "c" fn fvad_egress_mix_check(sinks: ?[*]const u64, n_sinks: usize, out_bytes: u64, src_format: c_int, w_orig: f32, w_den: f32, n_lanes: usize, orig_stride: usize, orig_samples: usize, den_stride: usize, den_samples: usize) c_int;
 pub extern "c" fn fvad_egress_mix_device(ctx: *Ctx, d_orig: ?*const anyopaque, orig_stride: usize, orig_samples: usize, d_den: ?*const anyopaque, den_stride: usize, den_samples: usize, src_format: c_int, n_lanes: usize, w_orig: f32, w_den: f32, sinks: ?[*]const u64, n_sinks: usize, d_out: ?*anyopaque, out_bytes: u64) c_int;

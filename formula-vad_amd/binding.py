@@ -38,6 +38,7 @@ RESAMPLE_FIELDS = 11             # a resample source: INGEST_FIELDS' seven (n_fr
 RESAMPLE_UP_MAX = 640            # FVAD_RESAMPLE_UP_MAX
 RESAMPLE_TAPS_MAX = 20481        # FVAD_RESAMPLE_TAPS_MAX (= 2 * 16 * 640 + 1)
 EGRESS_FIELDS = 6                # a sink: byte_offset, n_frames, n_channels, format (the file's), first_lane, src_offset (uint64 each)
+EGRESS_STEP_MAX = 16             # the largest src_step of the strided resampling egress
 EGRESS_RESAMPLE_FIELDS = 10      # a resampled sink: byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from
 EGRESS_MIX_FIELDS = 8            # a two-source sink: EGRESS_FIELDS' six (src_offset: into the denoised lanes), then orig_offset, orig_zeros
 WAV_HEADER_BYTES = 44            # FVAD_WAV_HEADER_BYTES: fvad_wav_header's canonical header
@@ -401,6 +402,9 @@ SIGNATURES = {
     "fvad_egress_resample_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_int, sz, sz, sz]),
     "fvad_egress_resample_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, vp, C.c_uint64]),
     "fvad_egress_resample": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.POINTER(vp)]),
+    "fvad_egress_resample_strided_check": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint64, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_uint32, C.c_int, sz, sz, sz]),
+    "fvad_egress_resample_strided_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_uint32, vp, C.c_uint64]),
+    "fvad_egress_resample_strided": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "fvad_resample_ratio": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fvad_resample_out_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "fvad_resample_design": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p, C.POINTER(C.c_uint32)]),
@@ -977,12 +981,24 @@ class Context:
         d_lanes, resampled by up / down with `taps` (float32, an odd count), converted to each row's file format and
         interleaved.  One ratio and one set of taps per call (src_pcm16 lanes are refused by the library).  Returns when the
         bytes are written."""
+        self._egress_resample("fvad_egress_resample", (), sinks, up, down, taps, src_pcm16, d_lanes, n_lanes, lane_stride, n_samples, out, out_bytes)
+
+    def egress_resample_strided(self, sinks, up, down, taps, src_step, src_pcm16=False, d_lanes=None, n_lanes=0, lane_stride=0, n_samples=0, out=None,
+                                out_bytes=None):
+        """fvad_egress_resample_strided_device / fvad_egress_resample_strided: egress_resample over the stream that lies src_step
+        (1 .. EGRESS_STEP_MAX) apart in the lanes: stream sample n of a row is lane sample src_offset + (n - frame_base) * src_step,
+        and the row's stream_frames, out_from, frame_base and n_frames count strided samples."""
+        self._egress_resample("fvad_egress_resample_strided", (int(src_step),), sinks, up, down, taps, src_pcm16, d_lanes, n_lanes, lane_stride,
+                              n_samples, out, out_bytes)
+
+    def _egress_resample(self, name, step, sinks, up, down, taps, src_pcm16, d_lanes, n_lanes, lane_stride, n_samples, out, out_bytes):
+        """the two call forms of egress_resample and egress_resample_strided (step: () or (src_step,), behind the taps)"""
         sinks = _egress_resample_rows(sinks)
         n = sinks.shape[0]
         fmt = INGEST_PCM16 if src_pcm16 else INGEST_F32
         rows = sinks.ctypes.data_as(C.POINTER(C.c_uint64))
         taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
-        head = (self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, up, down, fptr(taps), taps.shape[0])
+        head = (self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, up, down, fptr(taps), taps.shape[0]) + step
         if isinstance(out, (list, tuple)):
             if len(out) != n:
                 raise ValueError(f"egress_resample: {n} rows, {len(out)} buffers")
@@ -995,11 +1011,11 @@ class Context:
                     raise ValueError("egress_resample: a row's bytes are a writable C-contiguous uint8 array")
                 need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
                 if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress_resample", f"row {i} writes {need} bytes of a buffer of {b.size}")
+                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, name, f"row {i} writes {need} bytes of a buffer of {b.size}")
                 ptrs[i] = b.ctypes.data
-            self._ck(lib().fvad_egress_resample(*head, ptrs), "fvad_egress_resample")
+            self._ck(getattr(lib(), name)(*head, ptrs), name)
             return
-        self._ck(lib().fvad_egress_resample_device(*head, vp(out), int(out_bytes or 0)), "fvad_egress_resample_device")
+        self._ck(getattr(lib(), name + "_device")(*head, vp(out), int(out_bytes or 0)), name + "_device")
 
     def lane_state(self):
         s = vp()
@@ -1900,6 +1916,18 @@ def egress_resample_check(sinks, out_bytes, up, down, taps, n_lanes, lane_stride
         tp, nt = fptr(taps), taps.shape[0]
     return lib().fvad_egress_resample_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes), up, down, tp, nt,
                                             INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
+
+
+def egress_resample_strided_check(sinks, out_bytes, up, down, taps, src_step, n_lanes, lane_stride, n_samples, src_pcm16=False):
+    """fvad_egress_resample_strided_check: the status (FVAD_OK or the error the device calls would return), without a device"""
+    sinks = _egress_resample_rows(sinks)
+    if taps is None:
+        tp, nt = None, 0
+    else:
+        taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        tp, nt = fptr(taps), taps.shape[0]
+    return lib().fvad_egress_resample_strided_check(sinks.ctypes.data_as(C.POINTER(C.c_uint64)), sinks.shape[0], int(out_bytes), up, down, tp, nt,
+                                                    int(src_step), INGEST_PCM16 if src_pcm16 else INGEST_F32, n_lanes, lane_stride, n_samples)
 
 
 def wav_header(fmt, n_channels, sample_rate, n_frames):

@@ -5,11 +5,14 @@
 // (Workspace::IngestRing, sized by the context option ingest_ring_bytes; both calls return only when their last batch is done,
 // so the ring is idle whenever any of its users starts).  ev[s] here means: slot s's bytes have arrived in its page-locked
 // buffer.  The tap table goes up once per call.
+// fvad_egress_resample_strided_device / fvad_egress_resample_strided are the same two calls over a stream that lies src_step
+// apart in its lanes (kernels_egress_strided.hip; the rules are host_egress_strided.cpp's): the internals here take a step, 0
+// for the plain entries, which go on launching kernels_egress_resample.hip's kernel as they did.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "egress_resample.h"
+#include "egress_strided.h"
 #include "internal.h"
 
 using namespace fvad;
@@ -78,8 +81,9 @@ bool build_tables(const std::vector<Row>& rows, size_t lane_stride, const Ratio&
 }
 
 // the launches of one set of tables whose blob is at d_blob (queued on ctx->stream)
+// step 0: the plain kernel over contiguous lanes; otherwise the strided kernel
 int launch_tables(fvad_ctx* ctx, const Tables& t, const char* d_blob, const void* d_lanes, size_t lane_stride, const float* d_table,
-                  const Ratio& q, uint32_t n_taps, void* d_out)
+                  const Ratio& q, uint32_t n_taps, uint32_t step, void* d_out)
 {
     for (int f = 0; f < 3; ++f) {
         const Tables::Set& set = t.set[f];
@@ -97,19 +101,22 @@ int launch_tables(fvad_ctx* ctx, const Tables& t, const char* d_blob, const void
         a.down = q.down;
         a.n_taps = n_taps;
         a.file_format = f;
-        time_begin(ctx, "egress_resample");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_egress_resample(a, ctx->stream));
+        time_begin(ctx, step ? "egress_strided" : "egress_resample");
+        FVAD_HIP(ctx, (hipError_t)(step ? fvad_launch_egress_strided(EgressStridedArgs{a, step}, ctx->stream) : fvad_launch_egress_resample(a, ctx->stream)));
         time_end(ctx);
     }
     return FVAD_OK;
 }
 
 int check_call(const fvad_ctx* ctx, const char* who, const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down,
-               const float* taps, uint32_t n_taps, int src_format, const void* d_lanes, size_t n_lanes, size_t lane_stride, size_t n_samples)
+               const float* taps, uint32_t n_taps, bool strided, uint32_t step, int src_format, const void* d_lanes, size_t n_lanes, size_t lane_stride,
+               size_t n_samples)
 {
-    const int rc = fvad_egress_resample_check(sinks, n_sinks, out_bytes, up, down, taps, n_taps, src_format, n_lanes, lane_stride, n_samples);
+    const int rc = strided ? fvad_egress_resample_strided_check(sinks, n_sinks, out_bytes, up, down, taps, n_taps, step, src_format, n_lanes, lane_stride, n_samples)
+                           : fvad_egress_resample_check(sinks, n_sinks, out_bytes, up, down, taps, n_taps, src_format, n_lanes, lane_stride, n_samples);
     if (rc != FVAD_OK) return set_err(ctx, rc, std::string(who) + (rc == FVAD_ERR_OUT_OF_RANGE ? ": a row's lanes, samples or bytes are out of range"
-                                                                                                 : ": a bad argument, ratio, tap or row (fvad_egress_resample_check)"));
+                                                                                                 : strided ? ": a bad argument, ratio, step, tap or row (fvad_egress_resample_strided_check)"
+                                                                                                           : ": a bad argument, ratio, tap or row (fvad_egress_resample_check)"));
     if ((uintptr_t)d_lanes % 4 != 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string(who) + ": the lanes are not aligned to their samples");
     return FVAD_OK;
 }
@@ -118,34 +125,31 @@ int check_call(const fvad_ctx* ctx, const char* who, const uint64_t* sinks, size
 constexpr size_t kBatchRows = 2048;
 static_assert(kBatchRows * sizeof(EgressResampleJob) <= 4096 * sizeof(IngestJob), "the ring's table room");
 
-} // namespace
-
-extern "C" {
-
-int fvad_egress_resample_device(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                                const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
-                                void* d_out, uint64_t out_bytes)
+// the device form of both entries (strided: `step` is the caller's, checked below; otherwise 0)
+int device_call(fvad_ctx* ctx, const std::string& who, bool strided, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride,
+                size_t n_samples, const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps, uint32_t step,
+                void* d_out, uint64_t out_bytes)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (n_sinks && (!d_lanes || !d_out)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample_device: NULL argument");
-    const int bad = check_call(ctx, "fvad_egress_resample_device", sinks, n_sinks, out_bytes, up, down, taps, n_taps, src_format, d_lanes, n_lanes, lane_stride, n_samples);
+    if (n_sinks && (!d_lanes || !d_out)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+    const int bad = check_call(ctx, who.c_str(), sinks, n_sinks, out_bytes, up, down, taps, n_taps, strided, step, src_format, d_lanes, n_lanes, lane_stride, n_samples);
     if (bad != FVAD_OK) return bad;
     if (n_sinks == 0) return FVAD_OK;
     const Ratio q{up, down};
     std::vector<Row> all(n_sinks);
     for (size_t i = 0; i < n_sinks; ++i) all[i] = row(sinks, i);
     Tables t;
-    if (!build_tables(all, lane_stride, q, n_taps, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample_device: more than 2^24 tiles in one call: write in batches");
+    if (!build_tables(all, lane_stride, q, n_taps, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": more than 2^24 tiles in one call: write in batches");
     if (t.blob.empty()) return FVAD_OK; // nothing to write
     const std::vector<float> table = resample_table(Taps{taps, n_taps}, q);
     const size_t o_blob = up16(table.size() * 4);
     hipSetDevice(ctx->device);
     char* d = nullptr; // the tap table, then the row tables
-    if (hipMalloc((void**)&d, o_blob + t.blob.size()) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_egress_resample_device: hipMalloc of the tables failed"); }
+    if (hipMalloc((void**)&d, o_blob + t.blob.size()) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, who + ": hipMalloc of the tables failed"); }
     auto run = [&]() -> int {
         FVAD_HIP(ctx, hipMemcpyAsync(d, table.data(), table.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         FVAD_HIP(ctx, hipMemcpyAsync(d + o_blob, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice, ctx->stream));
-        const int rc = launch_tables(ctx, t, d + o_blob, d_lanes, lane_stride, reinterpret_cast<const float*>(d), q, n_taps, d_out);
+        const int rc = launch_tables(ctx, t, d + o_blob, d_lanes, lane_stride, reinterpret_cast<const float*>(d), q, n_taps, step, d_out);
         if (rc != FVAD_OK) return rc;
         FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return FVAD_OK;
@@ -161,13 +165,13 @@ int fvad_egress_resample_device(fvad_ctx* ctx, const void* d_lanes, int src_form
 // cover the row's window, so they cover the piece's, and the lanes are on the device already: nothing of the window is copied
 // and the bytes cannot depend on the cut.  While the device fills one slot, this thread moves the other slot's batch from its
 // page-locked buffer to where the caller wants it.
-int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                         const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
-                         void* const* dst_host)
+int host_call(fvad_ctx* ctx, const std::string& who, bool strided, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride,
+              size_t n_samples, const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps, uint32_t step,
+              void* const* dst_host)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (n_sinks && (!dst_host || !d_lanes)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample: NULL argument");
-    if (n_sinks && !sinks) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample: NULL sinks");
+    if (n_sinks && (!dst_host || !d_lanes)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+    if (n_sinks && !sinks) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": NULL sinks");
     // the rules, with every row's bytes at their absolute host address (fvad_egress's way: an address that wraps is saturated,
     // which the range rule then refuses)
     std::vector<uint64_t> placed(sinks, sinks + n_sinks * FVAD_EGRESS_RESAMPLE_FIELDS);
@@ -176,10 +180,10 @@ int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, siz
         const uint64_t base = (uint64_t)(uintptr_t)dst_host[i];
         at = at > UINT64_MAX - base ? UINT64_MAX : base + at;
     }
-    const int bad = check_call(ctx, "fvad_egress_resample", placed.data(), n_sinks, UINT64_MAX, up, down, taps, n_taps, src_format, d_lanes, n_lanes, lane_stride, n_samples);
+    const int bad = check_call(ctx, who.c_str(), placed.data(), n_sinks, UINT64_MAX, up, down, taps, n_taps, strided, step, src_format, d_lanes, n_lanes, lane_stride, n_samples);
     if (bad != FVAD_OK) return bad;
     for (size_t i = 0; i < n_sinks; ++i)
-        if (!dst_host[i] && row(sinks, i).n_out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample: a row with outputs and no bytes");
+        if (!dst_host[i] && row(sinks, i).n_out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": a row with outputs and no bytes");
     if (n_sinks == 0) return FVAD_OK;
     const Ratio q{up, down};
     hipSetDevice(ctx->device);
@@ -191,7 +195,7 @@ int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, siz
     const size_t o_tables = up16(cap);
     const std::vector<float> table = resample_table(Taps{taps, n_taps}, q);
     float* d_table = nullptr;
-    if (hipMalloc((void**)&d_table, table.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_egress_resample: hipMalloc of the tap table failed"); }
+    if (hipMalloc((void**)&d_table, table.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, who + ": hipMalloc of the tap table failed"); }
 
     std::vector<Row> batch;                               // the pieces of the batch being planned, byte_offset within the slot
     struct Move { size_t at; char* to; size_t bytes; };
@@ -208,12 +212,12 @@ int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, siz
     };
     auto flush = [&]() -> int {
         if (batch.empty()) return FVAD_OK;
-        if (!build_tables(batch, lane_stride, q, n_taps, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample: more than 2^24 tiles in one batch");
-        if (t.blob.size() > table_room) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_egress_resample: a batch's tables outgrew the ring"); // (kBatchRows keeps them inside)
+        if (!build_tables(batch, lane_stride, q, n_taps, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": more than 2^24 tiles in one batch");
+        if (t.blob.size() > table_room) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": a batch's tables outgrew the ring"); // (kBatchRows keeps them inside)
         // the slot is free: the batch it held was drained while the other slot's was in flight
         memcpy(ring.pin[slot] + o_tables, t.blob.data(), t.blob.size());
         FVAD_HIP(ctx, hipMemcpyAsync(ring.dev[slot] + o_tables, ring.pin[slot] + o_tables, t.blob.size(), hipMemcpyHostToDevice, ctx->stream));
-        const int rc = launch_tables(ctx, t, ring.dev[slot] + o_tables, d_lanes, lane_stride, d_table, q, n_taps, ring.dev[slot]);
+        const int rc = launch_tables(ctx, t, ring.dev[slot] + o_tables, d_lanes, lane_stride, d_table, q, n_taps, step, ring.dev[slot]);
         if (rc != FVAD_OK) return rc;
         FVAD_HIP(ctx, hipMemcpyAsync(ring.pin[slot], ring.dev[slot], used, hipMemcpyDeviceToHost, ctx->stream));
         FVAD_HIP(ctx, hipEventRecord(ring.ev[slot], ctx->stream));
@@ -262,6 +266,38 @@ int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, siz
     (void)hipStreamSynchronize(ctx->stream); // the ring is idle when the call returns, whatever happened
     hipFree(d_table);
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int fvad_egress_resample_device(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
+                                void* d_out, uint64_t out_bytes)
+{
+    return device_call(ctx, "fvad_egress_resample_device", false, d_lanes, src_format, n_lanes, lane_stride, n_samples, sinks, n_sinks, up, down, taps, n_taps, 0, d_out, out_bytes);
+}
+
+int fvad_egress_resample(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                         const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
+                         void* const* dst_host)
+{
+    return host_call(ctx, "fvad_egress_resample", false, d_lanes, src_format, n_lanes, lane_stride, n_samples, sinks, n_sinks, up, down, taps, n_taps, 0, dst_host);
+}
+
+int fvad_egress_resample_strided_device(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                        const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
+                                        uint32_t src_step, void* d_out, uint64_t out_bytes)
+{
+    return device_call(ctx, "fvad_egress_resample_strided_device", true, d_lanes, src_format, n_lanes, lane_stride, n_samples, sinks, n_sinks, up, down, taps, n_taps, src_step, d_out, out_bytes);
+}
+
+int fvad_egress_resample_strided(fvad_ctx* ctx, const void* d_lanes, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                 const uint64_t* sinks, size_t n_sinks, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
+                                 uint32_t src_step, void* const* dst_host)
+{
+    return host_call(ctx, "fvad_egress_resample_strided", true, d_lanes, src_format, n_lanes, lane_stride, n_samples, sinks, n_sinks, up, down, taps, n_taps, src_step, dst_host);
 }
 
 } // extern "C"

@@ -621,3 +621,13 @@ struct EgressResampleArgs {
     int file_format;               // FVAD_INGEST_*
 };
 int fvad_launch_egress_resample(const EgressResampleArgs& a, hipStream_t stream); // hipError_t as int
+
+// ------------------------------------------------------------------ strided resampling egress (kernels_egress_strided.hip)
+// fvad_egress_resample_strided*: the resampling egress over a stream that lies `step` apart in its lanes.  The jobs, the tile
+// and the tables are the resampling egress's, counted in STRIDED samples; stream sample s of channel c lies at lanes + src_off
+// + c * lane_stride + (s - frame_base) * step.
+struct EgressStridedArgs {
+    EgressResampleArgs r;
+    uint32_t step;                 // 1 .. FVAD_EGRESS_STEP_MAX
+};
+int fvad_launch_egress_strided(const EgressStridedArgs& s, hipStream_t stream); // hipError_t as int

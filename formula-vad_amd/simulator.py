@@ -8,7 +8,7 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
                                                       clips, original and denoised, cut and picked on the GPU;
                                                       --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
                                                       --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
-    python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source]   (or: run_denoise(path,
+    python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source] [--denoised-source lanes|network]   (or: run_denoise(path,
                                                       DIR): the denoised recordings as WAV files, converted and interleaved
                                                       on the GPU; --denoised-kinds denoised,original,residual,mix
                                                       --denoised-mix W: the time-aligned original, what was removed and a
@@ -919,23 +919,70 @@ def _check_denoised_rate(rate):
     _denoised_resample(rate)
 
 
-def _denoised_filters(rate, audio, dims, fmt):
+DENOISED_SOURCES = ("lanes", "network")
+# The network's own samples in the 48 kHz lanes.  NSNet2 works at 16 kHz and K3 brings its output back to 48 kHz by x3 linear
+# interpolation: network sample j lands unchanged at lane index 3 j + 2, the two samples in front of it are lerps.  So the stream
+# lane[NETWORK_PHASE + NETWORK_STEP * j] is the network's output bit for bit, and source="network" reads nothing else.  (The
+# delay D = fvad_nsnet2_delay(48000) of _denoise_share counts lane samples of the same clock.)
+NETWORK_STEP, NETWORK_PHASE = 3, 2
+NETWORK_RATE = 48000 // NETWORK_STEP
+
+
+def _check_denoised_source(source, kinds):
+    """run_denoise's source; ValueError for an unknown one and for "network" with a kind that reads the original"""
+    if source not in DENOISED_SOURCES:
+        raise ValueError(f"run_denoise: source {source!r} (one of {', '.join(DENOISED_SOURCES)})")
+    if source == "network" and kinds is not None and any(k != "denoised" for k in kinds):
+        raise ValueError(f"run_denoise: source 'network' with kinds {tuple(kinds)!r}: the kinds that read the original are written from the lanes")
+
+
+def _network_resample(rate):
+    """the filter of recordings written at `rate` from the network's 16 kHz stream (run_denoise(source="network")): up/down =
+    rate/16000 in lowest terms.  At 16000 the single tap 1.0: the file holds the network's samples themselves.  Otherwise
+    fvad_resample_design's default taps; when 3 divides up the file is put on the 48 kHz lanes' clock: stream sample j sits at
+    lane time 3 j + 2, so output o belongs at fine index o down - L, L = 2 up / 3, and the lag goes into the taps -- L zeros on
+    each side of the centre's move, taps' = [0] * 2 L + taps (centre K + L; they need not be symmetric): "lead" 0.  When 3 does
+    not divide up (16000, 32000, 8000) no lag is applied -- a shift of 2/3 of a stream sample would cost the exactness that is
+    the point at 16000 -- and the file's clock is "lead" = 2 samples of 48 kHz ahead.  ValueError for a rate that has no ratio
+    with up <= 640 or whose lagged design passes FVAD_RESAMPLE_TAPS_MAX taps."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate <= 0 or rate >= 1 << 32:
+        raise ValueError(f"run_denoise: rate {rate!r} (None, 'source' or a sample rate)")
+    own = {"rate": int(rate), "source": "network", "step": NETWORK_STEP, "phase": NETWORK_PHASE}
+    if int(rate) == NETWORK_RATE:
+        return dict(own, up=1, down=1, taps=np.array([1.0], np.float32), lag=0, lead=NETWORK_PHASE, half=None)
+    try:
+        up, down = fv.resample_ratio(NETWORK_RATE, int(rate))
+        taps = fv.resample_design(up, down)
+    except fv.FvadError:
+        raise ValueError(f"run_denoise: rate {rate!r}: no ratio to {NETWORK_RATE} with up <= {fv.RESAMPLE_UP_MAX} whose default design fits "
+                         f"{fv.RESAMPLE_TAPS_MAX} taps") from None
+    lag = NETWORK_PHASE * up // NETWORK_STEP if up % NETWORK_STEP == 0 else 0
+    if taps.size + 2 * lag > fv.RESAMPLE_TAPS_MAX:
+        raise ValueError(f"run_denoise: rate {rate!r}: the default design lagged by {lag} has {taps.size + 2 * lag} taps, more than "
+                         f"{fv.RESAMPLE_TAPS_MAX}")
+    taps = np.concatenate([np.zeros(2 * lag, np.float32), taps])
+    return dict(own, up=up, down=down, half=16, cutoff=0.45 / max(up, down), beta=6.0, taps=taps, lag=lag,
+                lead=0 if up % NETWORK_STEP == 0 else NETWORK_PHASE)
+
+
+def _denoised_filters(rate, audio, dims, fmt, source="lanes"):
     """per instance the _denoised_resample filter its recording leaves through, None for one that leaves at 48 kHz (fvad_egress).
+    With source "network" every instance has a filter, _network_resample's (rate None: 48000), over the network's stream.
     rate: an integer for every file, or "source" -- each instance at its own file's rate, which ingest="device" knows
     (_RawAudio.rate) and the host path, which takes 48 kHz files only, does not need.  ValueError, before any file exists, for a
     recording whose frames fit no tile of the kernel or whose data would pass 4 GB."""
     code, made, out = DENOISED_FORMATS[fmt], {}, []
     for a, (nch, n_frames) in zip(audio, dims):
-        r = (a.rate if isinstance(a, _RawAudio) else 48000) if isinstance(rate, str) else int(rate)
-        if r == 48000:
+        r = (a.rate if isinstance(a, _RawAudio) else 48000) if isinstance(rate, str) else 48000 if rate is None else int(rate)
+        if r == 48000 and source == "lanes":
             out.append(None)
             continue
         if r not in made:
-            made[r] = _denoised_resample(r)
+            made[r] = _network_resample(r) if source == "network" else _denoised_resample(r)
         f = made[r]
         if fv.egress_resample_tile(f["up"], f["down"], f["taps"].size, nch, code) == 0:
             raise ValueError(f"run_denoise: rate {r}: the filter's window fits no tile of the kernel for {nch} channels")
-        frames = fv.resample_out_frames(n_frames // 24000 * 24000, f["up"], f["down"])
+        frames = fv.resample_out_frames(n_frames // 24000 * (24000 // f.get("step", 1)), f["up"], f["down"])
         if frames * nch * fv.INGEST_SAMPLE_BYTES[code] > 0xFFFFFF00:
             raise ValueError(f"run_denoise: rate {r}: more than 4 GB of data in one file")
         out.append(f)
@@ -1006,17 +1053,24 @@ class _DenoisedFile:
     """NAME-denoised.wav of one instance (NAME-<kind>.wav for another kind of run_denoise), created at its final size -- fvad_wav_header's 44 bytes, then a hole of n_frames
     frames -- and mapped for fvad_egress to fill (`map`: the whole file as bytes, None for a file without frames).  With a
     filter `rs` (_denoised_resample) the file holds the ceil(n_frames up / down) frames of the stream of n_frames lane samples
-    at the filter's rate, for fvad_egress_resample to fill."""
+    at the filter's rate, for fvad_egress_resample to fill.  A filter over the network's stream (_network_resample: it has a
+    "step") counts the stream's samples, n_frames / step of them, and is filled by fvad_egress_resample_strided."""
 
     def __init__(self, out_dir, inst, fmt, n_channels, n_frames, rs=None, kind="denoised"):
         code = DENOISED_FORMATS[fmt]
         self.frame_bytes = n_channels * fv.INGEST_SAMPLE_BYTES[code]
+        if rs is not None:
+            n_frames //= rs.get("step", 1)
         self.rs, self.stream_frames, self.written, rate = rs, n_frames, 0, 48000
         if rs is not None:
             n_frames, rate = fv.resample_out_frames(n_frames, rs["up"], rs["down"]), rs["rate"]
         self.manifest = {"name": inst["name"], "file": os.path.join(out_dir, f"{inst['name']}-{kind}.wav"), "format": fmt,
                          "channels": n_channels, "frames": n_frames, "sample_rate": rate}
-        if rs is not None:
+        if rs is not None and "source" in rs:
+            self.manifest.update(source=rs["source"], lead=rs["lead"])
+            if rs["half"] is not None:   # (the single tap at the network's own rate is no resampling)
+                self.manifest["resample"] = {k: rs[k] for k in ("up", "down", "half", "cutoff", "beta", "lag")}
+        elif rs is not None:
             self.manifest["resample"] = {k: rs[k] for k in ("up", "down", "half", "cutoff", "beta")}
         head = fv.wav_header(code, n_channels, rate, n_frames)   # (raises for more than 4 GB of data, like fvad_wav_write)
         size = len(head) + n_frames * self.frame_bytes
@@ -1037,7 +1091,7 @@ class _DenoisedFile:
 
     def sink_resampled(self, out_to, first_lane, src_offset, frame_base, n_frames):
         """the fvad_egress_resample row of the file's outputs [written, out_to), which then count as written; the lanes hold the
-        stream's samples [frame_base, frame_base + n_frames) from src_offset on"""
+        stream's samples [frame_base, frame_base + n_frames) from src_offset on (the network's stream: `step` apart)"""
         n_channels, code = self.manifest["channels"], DENOISED_FORMATS[self.manifest["format"]]
         out_from, self.written = self.written, max(out_to, self.written)
         return (fv.WAV_HEADER_BYTES + out_from * self.frame_bytes, self.written - out_from, n_channels, code, first_lane, src_offset,
@@ -1049,6 +1103,14 @@ class _DenoisedFile:
 
     def close(self):
         self.map = None   # unmapped without msync: the written pages are the page cache's, as after fvad_wav_write's fwrite + fclose
+
+
+def _egress_resampled(ctx, rs, rows, out, lanes):
+    """one filter's rows: fvad_egress_resample over the lanes, or fvad_egress_resample_strided over the network's stream in them"""
+    if "step" in rs:
+        ctx.egress_resample_strided(rows, rs["up"], rs["down"], rs["taps"], rs["step"], out=out, **lanes)
+    else:
+        ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=out, **lanes)
 
 
 def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None, kinds=None, mix=None):
@@ -1080,8 +1142,8 @@ def _denoise_share(ctx, plan, insts, audio, out_dir, fmt, filters=None, kinds=No
         if plain:
             ctx.egress([files[i].sink(0, files[i].manifest["frames"], lane0[i], 0) for i in plain], out=[files[i].map for i in plain], **lanes)
         for rs, idx in _by_filter([(f.rs, i) for i, f in enumerate(files) if f.rs is not None]):
-            rows = [files[i].sink_resampled(files[i].manifest["frames"], lane0[i], 0, 0, files[i].stream_frames) for i in idx]
-            ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for i in idx], **lanes)
+            rows = [files[i].sink_resampled(files[i].manifest["frames"], lane0[i], rs.get("phase", 0), 0, files[i].stream_frames) for i in idx]
+            _egress_resampled(ctx, rs, rows, [files[i].map for i in idx], lanes)
         if kinds is None:
             return [f.manifest for f in files]
         D = fv.nsnet2_delay(48000)
@@ -1117,7 +1179,8 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
     for rs in filters or ():
         # the outputs a slice defers read at most (2 K + down) / up + 1 samples below the slice's first: inside the halo's exact part
-        assert rs is None or (rs["taps"].size - 1 + rs["down"]) // rs["up"] + 1 <= (H - 2) * chunk, "the halo covers the filter's reach"
+        # (a filter over the network's stream reaches `step` lane samples per stream sample)
+        assert rs is None or rs.get("step", 1) * ((rs["taps"].size - 1 + rs["down"]) // rs["up"] + 1) <= (H - 2) * chunk, "the halo covers the filter's reach"
     dims = [_dims(a, mapped=True) for a in audio]
     n_chunks = [d[1] // chunk for d in dims]
     groups = {}
@@ -1157,9 +1220,12 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
                     sinks = [files[i].sink(s0 * chunk, (min(n_chunks[i], s1) - s0) * chunk, k * nch, (s0 - start) * chunk) for k, i in plain]
                     ctx.egress(sinks, out=[files[i].map for _, i in plain], **lanes)
                 for rs, ki in _by_filter([(files[i].rs, (k, i)) for k, i in live if files and files[i].rs is not None]):
-                    rows = [files[i].sink_resampled(files[i].ready(min(s1, n_chunks[i]) * chunk), k * nch, 0, start * chunk,
-                                                    (min(n_chunks[i], s1) - start) * chunk) for k, i in ki]
-                    ctx.egress_resample(rows, rs["up"], rs["down"], rs["taps"], out=[files[i].map for _, i in ki], **lanes)
+                    # in stream samples: a chunk is `sc` of them (the network's stream: a slice begins at a multiple of 24000 lane
+                    # samples, so the phase holds in every slice buffer)
+                    sc = chunk // rs.get("step", 1)
+                    rows = [files[i].sink_resampled(files[i].ready(min(s1, n_chunks[i]) * sc), k * nch, rs.get("phase", 0), start * sc,
+                                                    (min(n_chunks[i], s1) - start) * sc) for k, i in ki]
+                    _egress_resampled(ctx, rs, rows, [files[i].map for _, i in ki], lanes)
                 # the other kinds: the slice's frames of the denoised buffer and their partners D samples earlier in the original
                 # buffer, which starts at the same chunk -- in the halo for every slice but the first, whose first D frames are zeros
                 if not mixed:
@@ -1188,7 +1254,7 @@ def _denoise_sliced_share(ctx, plan, insts, audio, out_dir, fmt, slice_chunks, f
 
 
 def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, rate=None,
-                kinds=None, mix=None):
+                kinds=None, mix=None, source="lanes"):
     """The plan's recordings, denoised, as WAV files: per instance NAME-denoised.wav in out_dir with all of the instance's
     channels at 48 kHz, as PCM16 (fmt "pcm16": rint(clamp(y * 32768)), the rule of the PCM16 clips and of
     fvad_lane.denoised_i16, not fvad_wav_write's), 24-bit PCM ("pcm24") or float32 ("f32": the lanes' bits, the file
@@ -1216,11 +1282,24 @@ def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devi
     kind, no lane memory of their own; the "denoised" kind is today's file, through fvad_egress.  With kinds the manifest of an
     instance is {"name", "kinds": [one entry per kind: file, kind, w_orig, w_den (None for "denoised"), delay, frames, format,
     channels, sample_rate]}.  An unknown kind, a mix out of range or without its kind, or a rate other than 48000 together with
-    a kind other than "denoised" raise ValueError before any work."""
+    a kind other than "denoised" raise ValueError before any work.
+    source: "lanes" is all of the above.  The 48 kHz lanes are the x3 LINEAR interpolation of NSNet2's 16 kHz output (a network
+    tone at 6 kHz stands in them at -3.8 dB with an image at 10 kHz at -11.8 dB); "network" writes the denoised file
+    from the network's own samples instead, lane[3 j + 2], with fvad_egress_resample_strided: at rate 16000 the samples
+    themselves (a third of the bytes, nothing lost), at None / 48000 the default 3/1 design in place of the lerp, at another
+    rate R one filter for R/16000 (_network_resample).  A file holds ceil(n * 8000 * up / down) frames for n chunks, the count
+    source="lanes" gives at R.  Its manifest gains "source": "network", "lead" -- 0 when 3 divides up: the file is on the lanes'
+    clock; otherwise 2: its clock is two 48 kHz samples (41.7 us) ahead -- and, except at 16000, "resample" with a "lag".
+    "network" with a kind other than "denoised", an unknown source, a rate without a ratio to 16000 (up <= 640) or whose
+    lagged design passes the tap limit (11025) raise ValueError before any work."""
     _check_ingest(ingest)
     _check_denoised_format(fmt)
-    _check_denoised_rate(rate)
-    kinds = _check_denoised_kinds(kinds, mix, rate)
+    if source == "network" and not (rate is None or (isinstance(rate, str) and rate == "source")):
+        _network_resample(rate)
+    else:
+        _check_denoised_rate(rate)
+    kinds = _check_denoised_kinds(kinds, mix, None if source == "network" else rate)
+    _check_denoised_source(source, kinds)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
         check_slice_chunks(slice_chunks, plan["fft_size"])
@@ -1229,8 +1308,8 @@ def run_denoise(plan_path, out_dir, fmt="pcm16", ctx=None, synth_seed=None, devi
     try:
         audio = [a for a, _ in _load_instances(plan, ingest, mapped=slice_chunks is not None)]
         filters = None
-        if rate is not None and (isinstance(rate, str) or rate != 48000):
-            filters = _denoised_filters(rate, audio, [_dims(a, mapped=slice_chunks is not None) for a in audio], fmt)
+        if source == "network" or (rate is not None and (isinstance(rate, str) or rate != 48000)):
+            filters = _denoised_filters(rate, audio, [_dims(a, mapped=slice_chunks is not None) for a in audio], fmt, source)
         os.makedirs(out_dir, exist_ok=True)
         parts = instance_shares(len(audio), len(ctxs))
         done, errs = [None] * len(ctxs), []
@@ -2568,6 +2647,10 @@ def arg_parser():
                     help="with --export-denoised: write the recordings at R Hz instead of 48000 (44100, 32000, 22050, 16000 ...: any rate "
                          "whose ratio to 48000 has up <= 640), or with `source` each at its own file's rate (known with --ingest device); "
                          "resampled on the GPU in front of the conversion (fvad_egress_resample)")
+    ap.add_argument("--denoised-source", default=None, choices=DENOISED_SOURCES,
+                    help="with --export-denoised: lanes (the default: the 48 kHz lanes, NSNet2's output linearly interpolated) or network "
+                         "(NSNet2's own 16 kHz samples, every third lane sample: lossless at --denoised-rate 16000, band-limited "
+                         "interpolation instead of the lerp at 48000, one filter at any other rate; fvad_egress_resample_strided)")
     ap.add_argument("--denoised-kinds", default=None, metavar="K[,K...]",
                     help="with --export-denoised: the files to write per instance, NAME-K.wav each, of denoised, original (the input "
                          "delayed by the denoiser's 482 samples, so that it lines up with the denoised file), residual (what the denoiser "
@@ -2585,7 +2668,7 @@ def arg_parser():
 
 def check_modes(a):
     """--export-denoised is a mode of its own: ValueError, before any work, when it is combined with a sweep or the clip export,
-    or when --denoised-format or --denoised-rate comes without it"""
+    or when --denoised-format, --denoised-rate or --denoised-source comes without it"""
     if a.export_denoised:
         others = [name for name, on in (("--sweep", a.sweep), ("--sweep-grid", a.sweep_grid), ("--export-clips", a.export_clips)) if on]
         if others:
@@ -2594,6 +2677,8 @@ def check_modes(a):
         raise ValueError("--denoised-format needs --export-denoised")
     elif a.denoised_rate is not None:
         raise ValueError("--denoised-rate needs --export-denoised")
+    elif a.denoised_source is not None:
+        raise ValueError("--denoised-source needs --export-denoised")
     elif a.denoised_kinds is not None:
         raise ValueError("--denoised-kinds needs --export-denoised")
     elif a.denoised_mix is not None:
@@ -2618,7 +2703,7 @@ def main(argv=None):
         kinds = None if a.denoised_kinds is None else tuple(k for k in a.denoised_kinds.split(",") if k != "")
         for m in run_denoise(a.input, a.export_denoised, fmt=a.denoised_format or "pcm16", synth_seed=a.synth_seed, devices=devices,
                              ingest=a.ingest, slice_chunks=a.slice_chunks, rate=_parse_denoised_rate(a.denoised_rate), kinds=kinds,
-                             mix=a.denoised_mix):
+                             mix=a.denoised_mix, source=a.denoised_source or "lanes"):
             for e in [m] if kinds is None else m["kinds"]:
                 at = "" if e["sample_rate"] == 48000 else f" at {e['sample_rate']} Hz"
                 sys.stdout.write(f"{e['file']}: {e['channels']} x {e['frames']} frames, {e['format']}{at}\n")

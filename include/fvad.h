@@ -1335,6 +1335,49 @@ int fvad_egress_resample(fvad_ctx *ctx, const void *d_lanes, int src_format, siz
                          const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down, const float *taps, uint32_t n_taps,
                          void *const *dst_host);
 
+/* ------------------------------------------------------------------ strided resampling egress: recordings from the network's samples
+ * NSNet2 works at 16 kHz.  The 48 kHz lanes the engine keeps are the reference's x3 LINEAR interpolation of the network's
+ * output: network sample j lands unchanged at lane index 3 j + 2 and the two samples in front of it are lerps.  A lerp is a
+ * triangular filter: a network tone at 6 kHz stands in the lanes at -3.8 dB with images at 10 kHz (-11.8 dB, both against the
+ * network's tone) and 22 kHz (-20 dB); a 7.5 kHz tone at -6.1 dB, its image at 8.5 kHz at -8.1 dB.  The VAD wants exactly these
+ * lanes; a listener does not.  The stream lane[3 j + 2] is the network's output bit for bit, and ONE kernel (csrc/kernels_egress_strided.hip), the
+ * resampling egress over a stream that lies src_step apart in its lanes, writes recordings from it: at 16 kHz (1/1 with the
+ * tap 1.0) lossless at a third of the bytes, at 48 kHz (3/1) a band-limited interpolation in place of the lerp, at 44.1 kHz one
+ * filter (441/160) in place of two.
+ * THE DEFINITION is fvad_egress_resample's with one more argument, src_step in 1 .. FVAD_EGRESS_STEP_MAX, and another meaning
+ * of the word "stream":
+ * - Stream sample n of channel c is lane sample src_offset + (n - frame_base) * src_step of lane first_lane + c, for
+ *   frame_base <= n < frame_base + n_frames.  The row keeps its FVAD_EGRESS_RESAMPLE_FIELDS fields and their order;
+ *   stream_frames, out_from, frame_base and n_frames count STRIDED samples.  fvad_resample_window, fvad_egress_resample_ready
+ *   and fvad_egress_resample_tile are used as they are (the tile's window is 8192 staged samples whatever the step).
+ * - The sum, its ascending f32 fma chain from +0 with the zeros outside [0, stream_frames) skipped, the conversion and the
+ *   interleaving are fvad_egress_resample's.  So the bytes equal fvad_egress_resample's over a compacted copy of the lanes, and
+ *   with src_step == 1 over the same lanes, bit for bit; every invariant of fvad_egress_resample holds.
+ * - Nothing outside [src_offset, src_offset + (n_frames - 1) * src_step] of a lane is read, and no sample off the stride
+ *   enters a sum (they may be NaN).
+ * - The default 3/1 design (fvad_resample_design(3, 1, 0, 0, 0): 97 taps), from tools/resample_response.py: a pass-band ripple
+ *   of 0.108 dB up to 6.4 kHz of the 16 kHz stream (-0.10 .. +0.01 dB) and a stop band of -72.1 dB from 9.6 kHz on; in between
+ *   the transition band falls through -66.6 dB at 8.5 kHz.  Every image of a network tone up to 6.4 kHz lies at 9.6 kHz or above.
+ *
+ * fvad_egress_resample_strided_check (host only, csrc/host_egress_strided.cpp, the rules in csrc/egress_strided.h):
+ *   fvad_egress_resample_check's rules in its order, with two changes: FVAD_ERR_INVALID_ARGUMENT for a src_step outside
+ *   1 .. FVAD_EGRESS_STEP_MAX directly after the ratio's rule, and the lane range rule is n_frames == 0 || src_offset +
+ *   (n_frames - 1) * src_step + 1 <= n_samples, evaluated without wrapping, FVAD_ERR_OUT_OF_RANGE otherwise.
+ * fvad_egress_resample_strided_device / fvad_egress_resample_strided: fvad_egress_resample_device's and
+ *   fvad_egress_resample's forms.  Both run the check (and refuse NULL pointers and lanes not aligned to 4 bytes) before any
+ *   launch, return when the bytes are written and name `egress_strided` in fvad_ctx_kernel_times (one launch per file format
+ *   present).  The tap table is uploaded once per call; the host form cuts rows at the ring as fvad_egress_resample does. */
+#define FVAD_EGRESS_STEP_MAX 16
+int fvad_egress_resample_strided_check(const uint64_t *sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down,
+                                       const float *taps, uint32_t n_taps, uint32_t src_step, int src_format, size_t n_lanes,
+                                       size_t lane_stride, size_t n_samples);
+int fvad_egress_resample_strided_device(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride,
+                                        size_t n_samples, const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down,
+                                        const float *taps, uint32_t n_taps, uint32_t src_step, void *d_out, uint64_t out_bytes);
+int fvad_egress_resample_strided(fvad_ctx *ctx, const void *d_lanes, int src_format, size_t n_lanes, size_t lane_stride,
+                                 size_t n_samples, const uint64_t *sinks, size_t n_sinks, uint32_t up, uint32_t down,
+                                 const float *taps, uint32_t n_taps, uint32_t src_step, void *const *dst_host);
+
 /* ------------------------------------------------------------------ two-source egress: the original beside the denoised
  * fvad_egress writes one lane set.  A user of a denoiser also wants the original to compare against, what was taken out (the
  * residual) and a wet/dry mix -- all of them functions of the ORIGINAL lanes and the DENOISED lanes, which the engine has on
