@@ -1,11 +1,13 @@
-// egress_device.h -- device helpers of the egress kernel (kernels_egress.hip), the mirror of ingest_device.h and stage_tile.h:
-// the 16-byte source groups of a lane run, the file formats' samples written into staged LDS bytes, and a tile of bytes with an
-// arbitrary destination drained from LDS.
+// egress_device.h -- device helpers of the egress kernels (kernels_egress.hip, kernels_egress_resample.hip,
+// kernels_egress_mix.hip), the mirror of ingest_device.h and stage_tile.h: the 16-byte source groups of a lane run, an f32 value
+// as a file format's sample, the file formats' samples written into staged LDS bytes, a tile of
+// bytes with an arbitrary destination drained from LDS, and the launch of a file format's instantiation.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "../../include/fvad.h"
 #include "ingest_device.h" // find_job, Pcm24
 #include "stage_tile.h"    // kStageThreads
 
@@ -27,6 +29,18 @@ __device__ inline void load_group(const E* __restrict__ p, int n, int g, F put)
         for (int i = max(lo, 0); i < min(hi, n); ++i) put(i, p[i]);
     }
 }
+
+// Quant<F>: an f32 value as the file sample's integer image.  f32: its bits (NaN payloads and -0 survive); PCM16:
+// rint(fminf(fmaxf(y * 32768, -32768), 32767)), Convert<int16_t, float> of clip_device.h; PCM24 the same with 8388608 and 8388607,
+// its low three bytes written.  (y * scale quiets a signalling NaN, fmaxf then gives the lower bound.)
+template <typename F> struct Quant;
+template <> struct Quant<float> { __device__ static uint32_t run(float y) { return __float_as_uint(y); } };
+template <> struct Quant<int16_t> {
+    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)); }
+};
+template <> struct Quant<Pcm24> {
+    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 8388608.0f, -8388608.0f), 8388607.0f)); }
+};
 
 // Sink<F>: bytes per sample of the file format and the sample's integer image stored at LDS byte b, little-endian (aligned: b is
 // a multiple of the sample's size)
@@ -75,4 +89,16 @@ __device__ inline void drain_tile(uint8_t* __restrict__ dst, int n, int shift, c
     const int tail0 = head + nvec * 16;
     if (t < head) dst[t] = lds[shift + t];
     if (t < n - tail0) dst[tail0 + t] = lds[shift + tail0 + t];
+}
+
+// The instantiation of a file format: launch(F{}) queues the kernel whose file sample type is F; the result is the launch's
+// hipError_t as int.
+template <typename L>
+inline int launch_file_format(int file_format, L launch)
+{
+    if (file_format == FVAD_INGEST_F32) launch(float{});
+    else if (file_format == FVAD_INGEST_PCM16) launch(int16_t{});
+    else if (file_format == FVAD_INGEST_PCM24) launch(Pcm24{});
+    else return (int)hipErrorInvalidValue; // (the callers refuse the formats before they get here)
+    return (int)hipGetLastError();
 }

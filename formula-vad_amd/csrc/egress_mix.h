@@ -1,4 +1,4 @@
-// egress_mix.h -- the two-source egress (fvad_egress_mix*): what engine_egress_mix.cpp builds and kernels_egress_mix.hip reads.
+// egress_mix.h -- the two-source egress (fvad_egress_mix*): what engine_egress.cpp builds and kernels_egress_mix.hip reads.
 // A header of its own, not a part of kernels.h: the translation units of the other egress kernels do not see it.
 // A work unit is kernels_egress.hip's: a tile of one sink -- kIngestTileBytes of its DESTINATION bytes rounded down to whole
 // frames in multiples of 4 (tile_frames), every channel of them.  Frame f of the sink pairs denoised sample den_off + f with

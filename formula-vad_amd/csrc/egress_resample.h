@@ -1,6 +1,6 @@
 // egress_resample.h -- the rules of the resampling egress (fvad_egress_resample*), host only: the kernel's tile and the outputs
 // a stream's leading frames can finish.  The ratio, the output count, the window and the tap rules are resample.h's.  Inline, so
-// that host_egress_resample.cpp (the check), engine_egress_resample.cpp (the tables) and, through the job the engine builds,
+// that host_egress_resample.cpp (the check), engine_egress.cpp (the tables) and, through the job the engine builds,
 // kernels_egress_resample.hip state the tile once, and host_egress_resample.cpp still builds alone
 // (tests/sanitize/egress_resample_san.cpp).
 #pragma once
@@ -9,7 +9,7 @@
 namespace fvad {
 
 constexpr uint64_t kEgressResampleTileBytes = 16384; // a tile's DESTINATION bytes at most: kIngestTileBytes (drain_tile and the LDS image are the egress's)
-constexpr uint64_t kEgressResampleWindow = 8192;     // the lane samples of one channel a tile stages at most: kClipTile (engine_egress_resample.cpp asserts both)
+constexpr uint64_t kEgressResampleWindow = 8192;     // the lane samples of one channel a tile stages at most: kClipTile (engine_egress.cpp asserts both)
 
 // The kernel's tile in OUTPUT frames: the most frames, a multiple of 4, whose bytes fit kEgressResampleTileBytes and whose
 // window of one channel, floor(((n - 1) down + 2 K) / up) + 1 lane samples, fits kEgressResampleWindow; 0 when not even 4 do.
@@ -32,5 +32,10 @@ inline uint64_t egress_resample_ready(const Ratio& r, uint32_t n_taps, uint64_t 
     const u128 n = (have - K + r.down - 1) / r.down;
     return n < (u128)out_frames ? (uint64_t)n : out_frames;
 }
+
+// fvad_egress_resample_check (strided false, step unused) and fvad_egress_resample_strided_check (true, its src_step) in one:
+// host_egress_resample.cpp
+int egress_resample_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps,
+                          bool strided, uint32_t step, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples);
 
 } // namespace fvad

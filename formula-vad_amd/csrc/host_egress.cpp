@@ -2,19 +2,16 @@
 // 44-byte canonical header host_io.cpp's wav_put writes (and its 24-bit PCM form, which wav_put has not), and fvad_egress_check,
 // every argument rule of the device calls.  Plain C++ without HIP headers, like host_ingest.cpp, so that it can be tested (and
 // run under sanitizers) on a machine without a device.
-#include <algorithm>
 #include <cstdint>
 #include <cstring>
-#include <vector>
 
-#include "../../include/fvad.h"
+#include "egress_rules.h"
+
+using namespace fvad;
 
 namespace {
 void wr16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
 void wr32(uint8_t* p, uint32_t v) { wr16(p, v & 0xffff); wr16(p + 2, v >> 16); }
-uint64_t sample_bytes(uint64_t format) { return format == FVAD_INGEST_PCM16 ? 2 : format == FVAD_INGEST_PCM24 ? 3 : 4; }
-
-struct Range { uint64_t from, to; };
 } // namespace
 
 extern "C" {
@@ -25,7 +22,7 @@ int fvad_wav_header(int format, uint32_t n_channels, uint32_t sample_rate, uint6
     if (!out || !n_bytes) return FVAD_ERR_INVALID_ARGUMENT;
     if (format != FVAD_INGEST_F32 && format != FVAD_INGEST_PCM16 && format != FVAD_INGEST_PCM24) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_channels == 0 || n_channels > 65535 || sample_rate == 0) return FVAD_ERR_INVALID_ARGUMENT; // wav_put's refusals
-    const uint64_t bytes_per = sample_bytes((uint64_t)format), frame_bytes = n_channels * bytes_per;
+    const uint64_t bytes_per = sample_bytes_of((uint64_t)format), frame_bytes = n_channels * bytes_per;
     if (n_frames > 0xFFFFFF00ull / frame_bytes) return FVAD_ERR_INVALID_ARGUMENT; // RIFF sizes are 32-bit
     const uint64_t data_bytes = n_frames * frame_bytes;
     *n_bytes = FVAD_WAV_HEADER_BYTES;
@@ -38,7 +35,7 @@ int fvad_wav_header(int format, uint32_t n_channels, uint32_t sample_rate, uint6
 }
 
 // The order: arguments; then every sink's own rules (format and pair, channels); then every sink's ranges (lanes, samples
-// against n_samples, bytes against out_bytes); then the overlap of two sinks' bytes.
+// against n_samples, bytes against out_bytes); then the overlap of two sinks' bytes (both of egress_rules.h).
 int fvad_egress_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, int src_format, size_t n_lanes, size_t lane_stride,
                       size_t n_samples)
 {
@@ -54,29 +51,14 @@ int fvad_egress_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes,
         if (src_format == FVAD_INGEST_PCM16 && format != FVAD_INGEST_PCM16) return FVAD_ERR_INVALID_ARGUMENT;
         if (n_channels < 1 || n_channels > 64) return FVAD_ERR_INVALID_ARGUMENT;
     }
-    size_t n_ranges = 0;
     for (size_t i = 0; i < n_sinks; ++i) {
         const uint64_t* r = sinks + i * FVAD_EGRESS_FIELDS;
-        const uint64_t byte_offset = r[0], n_frames = r[1], n_channels = r[2], format = r[3], first_lane = r[4], src_offset = r[5];
+        const uint64_t n_frames = r[1], n_channels = r[2], first_lane = r[4], src_offset = r[5];
         if (first_lane >= n_lanes || n_channels > n_lanes - first_lane) return FVAD_ERR_OUT_OF_RANGE;
         if (src_offset > n_samples || n_frames > n_samples - src_offset) return FVAD_ERR_OUT_OF_RANGE;
-        const uint64_t frame_bytes = n_channels * sample_bytes(format);
-        if (n_frames > UINT64_MAX / frame_bytes) return FVAD_ERR_OUT_OF_RANGE;
-        if (byte_offset > out_bytes || n_frames * frame_bytes > out_bytes - byte_offset) return FVAD_ERR_OUT_OF_RANGE;
-        if (n_frames) ++n_ranges;
+        if (!egress_bytes_ok(r, out_bytes)) return FVAD_ERR_OUT_OF_RANGE;
     }
-    // two sinks may not write one byte: the order of the writes would decide the result.  The ranges sorted by their start
-    // must not reach into their successors (a range that ends where the next one starts is fine).
-    std::vector<Range> ranges;
-    ranges.reserve(n_ranges);
-    for (size_t i = 0; i < n_sinks; ++i) {
-        const uint64_t* r = sinks + i * FVAD_EGRESS_FIELDS;
-        if (r[1] == 0) continue; // writes nothing
-        ranges.push_back({r[0], r[0] + r[1] * r[2] * sample_bytes(r[3])});
-    }
-    std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.from < y.from; });
-    for (size_t k = 1; k < ranges.size(); ++k)
-        if (ranges[k].from < ranges[k - 1].to) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!egress_rows_disjoint(sinks, n_sinks, FVAD_EGRESS_FIELDS)) return FVAD_ERR_INVALID_ARGUMENT;
     return FVAD_OK;
 }
 

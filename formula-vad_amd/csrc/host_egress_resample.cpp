@@ -1,15 +1,14 @@
-// host_egress_resample.cpp -- the host-only half of the resampling egress (fvad_egress_resample*, engine_egress_resample.cpp):
-// the kernel's tile, the outputs a stream's leading frames can finish, and fvad_egress_resample_check, every argument rule of
-// the device calls.  Plain C++ without HIP headers, like host_egress.cpp (tests/sanitize/egress_resample_san.cpp builds this
-// file and host_resample.cpp alone).
-#include <algorithm>
-
-#include "egress_resample.h"
+// host_egress_resample.cpp -- the host-only half of the resampling egress (fvad_egress_resample*, engine_egress.cpp): the
+// kernel's tile, the outputs a stream's leading frames can finish, and fvad_egress_resample_check, every argument rule of the
+// device calls -- written once for it and for the strided form (host_egress_strided.cpp's entry calls it with its step).  Plain
+// C++ without HIP headers, like host_egress.cpp (tests/sanitize/egress_resample_san.cpp builds this file and host_resample.cpp
+// alone).
+#include "egress_rules.h"
+#include "egress_strided.h"
 
 using namespace fvad;
 
 namespace {
-struct Range { uint64_t from, to; };
 bool taps_count_ok(uint32_t n_taps) { return n_taps != 0 && n_taps % 2 == 1 && n_taps <= FVAD_RESAMPLE_TAPS_MAX; }
 } // namespace
 
@@ -28,15 +27,20 @@ uint64_t fvad_egress_resample_ready(uint32_t up, uint32_t down, uint32_t n_taps,
     return egress_resample_ready(Ratio{up, down}, n_taps, stream_frames, frames_have);
 }
 
-// The order: arguments (lane format, ratio, taps; then sinks, lane_stride); then every row's own rules (format, channels, the
-// stream's length, the outputs against the stream, the given frames against the stream and against the window, the tile); then
-// every row's ranges (lanes, given frames against n_samples, bytes against out_bytes); then the overlap of two rows' bytes.
-int fvad_egress_resample_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down, const float* taps,
-                               uint32_t n_taps, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples)
+} // extern "C"
+
+// Both checks.  The order: arguments (lane format, ratio, the step of the strided check, taps; then sinks, lane_stride); then every
+// row's own rules (format, channels, the stream's length, the outputs against the stream, the given frames against the stream
+// and against the window, the tile); then every row's ranges (lanes, given frames against n_samples -- `step` apart in the
+// strided check, where a row without frames touches no sample whatever its src_offset --, bytes against out_bytes); then the
+// overlap of two rows' bytes (both of egress_rules.h).  Every count of a strided row is in STRIDED samples.
+int fvad::egress_resample_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down, const float* taps,
+                                uint32_t n_taps, bool strided, uint32_t step, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples)
 {
     if (src_format != FVAD_INGEST_F32) return FVAD_ERR_INVALID_ARGUMENT; // PCM16 lanes would be a conversion; anything else is no format
     const Ratio q{up, down};
     if (!ratio_ok(q)) return FVAD_ERR_INVALID_ARGUMENT;
+    if (strided && !egress_step_ok(step)) return FVAD_ERR_INVALID_ARGUMENT;
     const char* why;
     if (!resample_taps_ok(Taps{taps, n_taps}, &why)) return FVAD_ERR_INVALID_ARGUMENT;
     if (n_sinks == 0) return FVAD_OK;
@@ -55,29 +59,24 @@ int fvad_egress_resample_check(const uint64_t* sinks, size_t n_sinks, uint64_t o
         if (hi > lo && (frame_base > lo || frame_base + n_frames < hi)) return FVAD_ERR_INVALID_ARGUMENT; // the slice would not be the stream
         if (egress_resample_tile(q, n_taps, n_channels, format) == 0) return FVAD_ERR_INVALID_ARGUMENT; // taps too long for a tile
     }
-    size_t n_ranges = 0;
     for (size_t i = 0; i < n_sinks; ++i) {
         const uint64_t* r = sinks + i * FVAD_EGRESS_RESAMPLE_FIELDS;
-        const uint64_t byte_offset = r[0], n_out = r[1], n_channels = r[2], format = r[3], first_lane = r[4], src_offset = r[5], n_frames = r[7];
+        const uint64_t n_channels = r[2], first_lane = r[4], src_offset = r[5], n_frames = r[7];
         if (first_lane >= n_lanes || n_channels > n_lanes - first_lane) return FVAD_ERR_OUT_OF_RANGE;
-        if (src_offset > n_samples || n_frames > n_samples - src_offset) return FVAD_ERR_OUT_OF_RANGE;
-        const uint64_t frame_bytes = n_channels * sample_bytes_of(format);
-        if (n_out > UINT64_MAX / frame_bytes) return FVAD_ERR_OUT_OF_RANGE;
-        if (byte_offset > out_bytes || n_out * frame_bytes > out_bytes - byte_offset) return FVAD_ERR_OUT_OF_RANGE;
-        if (n_out) ++n_ranges;
+        if (strided ? !egress_strided_span_ok(src_offset, n_frames, step, n_samples) : (src_offset > n_samples || n_frames > n_samples - src_offset))
+            return FVAD_ERR_OUT_OF_RANGE;
+        if (!egress_bytes_ok(r, out_bytes)) return FVAD_ERR_OUT_OF_RANGE;
     }
-    // two rows may not write one byte (fvad_egress_check's rule; ranges that touch are fine)
-    std::vector<Range> ranges;
-    ranges.reserve(n_ranges);
-    for (size_t i = 0; i < n_sinks; ++i) {
-        const uint64_t* r = sinks + i * FVAD_EGRESS_RESAMPLE_FIELDS;
-        if (r[1] == 0) continue; // writes nothing
-        ranges.push_back({r[0], r[0] + r[1] * r[2] * sample_bytes_of(r[3])});
-    }
-    std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.from < y.from; });
-    for (size_t k = 1; k < ranges.size(); ++k)
-        if (ranges[k].from < ranges[k - 1].to) return FVAD_ERR_INVALID_ARGUMENT;
+    if (!egress_rows_disjoint(sinks, n_sinks, FVAD_EGRESS_RESAMPLE_FIELDS)) return FVAD_ERR_INVALID_ARGUMENT;
     return FVAD_OK;
+}
+
+extern "C" {
+
+int fvad_egress_resample_check(const uint64_t* sinks, size_t n_sinks, uint64_t out_bytes, uint32_t up, uint32_t down, const float* taps,
+                               uint32_t n_taps, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples)
+{
+    return egress_resample_check(sinks, n_sinks, out_bytes, up, down, taps, n_taps, false, 0, src_format, n_lanes, lane_stride, n_samples);
 }
 
 } // extern "C"

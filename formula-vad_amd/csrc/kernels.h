@@ -622,7 +622,7 @@ struct EgressResampleArgs {
 };
 int fvad_launch_egress_resample(const EgressResampleArgs& a, hipStream_t stream); // hipError_t as int
 
-// ------------------------------------------------------------------ strided resampling egress (kernels_egress_strided.hip)
+// ------------------------------------------------------------------ strided resampling egress (kernels_egress_resample.hip, egress_strided_kernel)
 // fvad_egress_resample_strided*: the resampling egress over a stream that lies `step` apart in its lanes.  The jobs, the tile
 // and the tables are the resampling egress's, counted in STRIDED samples; stream sample s of channel c lies at lanes + src_off
 // + c * lane_stride + (s - frame_base) * step.

@@ -1,8 +1,7 @@
 // kernels_egress.hip -- fvad_egress*: planar device lanes (f32 or PCM16) converted to a file's sample format and interleaved
 // into the bytes of its data chunk -- little-endian PCM16, PCM24 or IEEE float32 frames -- the inverse of kernels_ingest.hip.
 // The four format pairs: f32 -> f32 and PCM16 -> PCM16 move bits (f32 as 32-bit integers: NaN payloads and -0 survive);
-// f32 -> PCM16 is rint(fminf(fmaxf(y * 32768, -32768), 32767)), Convert<int16_t, float> of clip_device.h; f32 -> PCM24 the same
-// with 8388608 and 8388607, its low three bytes written.  (y * scale quiets a signalling NaN, fmaxf then gives the lower bound.)
+// f32 -> PCM16 and f32 -> PCM24 are Quant<F> of egress_device.h.
 //
 // The work unit follows kernels_ingest.hip: a workgroup of 256 lanes takes one tile of one sink, found by a search of a
 // host-built prefix table with its block index (the same in every lane); no atomics, a sink's bytes depend on its lanes alone.
@@ -38,18 +37,11 @@ namespace {
 
 constexpr int kThreads = kStageThreads;
 
-// Encode<F, S>: the lane element loaded (E, an integer image) and the file sample's integer image made from it
+// Encode<F, S>: the lane element loaded (E, an integer image) and the file sample's integer image made from it: PCM16 lanes as
+// they are, f32 lanes by Quant<F> (f32 -> f32: the bits go through two casts and no arithmetic)
 template <typename F, typename S> struct Encode;
-template <> struct Encode<float, float> { using E = uint32_t; __device__ static uint32_t run(E s) { return s; } }; // the bits
 template <> struct Encode<int16_t, int16_t> { using E = uint16_t; __device__ static uint32_t run(E s) { return s; } };
-template <> struct Encode<int16_t, float> {
-    using E = uint32_t;
-    __device__ static uint32_t run(E s) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(__uint_as_float(s) * 32768.0f, -32768.0f), 32767.0f)); }
-};
-template <> struct Encode<Pcm24, float> {
-    using E = uint32_t;
-    __device__ static uint32_t run(E s) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(__uint_as_float(s) * 8388608.0f, -8388608.0f), 8388607.0f)); }
-};
+template <typename F> struct Encode<F, float> { using E = uint32_t; __device__ static uint32_t run(E s) { return Quant<F>::run(__uint_as_float(s)); } };
 
 template <typename F, typename S>
 __device__ inline void egress_tile(const EgressArgs& a, uint8_t* lds)
@@ -92,10 +84,9 @@ __global__ __launch_bounds__(kThreads) void egress_kernel(EgressArgs a)
 int fvad_launch_egress(const EgressArgs& a, hipStream_t stream)
 {
     const dim3 grid(a.n_units), block(kThreads);
-    if (a.src_format == FVAD_INGEST_PCM16 && a.file_format == FVAD_INGEST_PCM16) hipLaunchKernelGGL((egress_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.src_format == FVAD_INGEST_F32 && a.file_format == FVAD_INGEST_F32) hipLaunchKernelGGL((egress_kernel<float, float>), grid, block, 0, stream, a);
-    else if (a.src_format == FVAD_INGEST_F32 && a.file_format == FVAD_INGEST_PCM16) hipLaunchKernelGGL((egress_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else if (a.src_format == FVAD_INGEST_F32 && a.file_format == FVAD_INGEST_PCM24) hipLaunchKernelGGL((egress_kernel<Pcm24, float>), grid, block, 0, stream, a);
-    else return (int)hipErrorInvalidValue; // (the callers refuse the conversions before they get here)
+    if (a.src_format == FVAD_INGEST_F32)
+        return launch_file_format(a.file_format, [&](auto f) { hipLaunchKernelGGL((egress_kernel<decltype(f), float>), grid, block, 0, stream, a); });
+    if (a.src_format != FVAD_INGEST_PCM16 || a.file_format != FVAD_INGEST_PCM16) return (int)hipErrorInvalidValue; // (the callers refuse the conversions before they get here)
+    hipLaunchKernelGGL((egress_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
     return (int)hipGetLastError();
 }

@@ -41,16 +41,6 @@ namespace {
 constexpr int kThreads = kStageThreads;
 enum Mode { kDen = 0, kOrig = 1, kBoth = 2 };
 
-// Quant<F>: the f32 result as the file sample's integer image (fvad_egress's rules for f32 lanes)
-template <typename F> struct Quant;
-template <> struct Quant<float> { __device__ static uint32_t run(float y) { return __float_as_uint(y); } };
-template <> struct Quant<int16_t> {
-    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)); }
-};
-template <> struct Quant<Pcm24> {
-    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 8388608.0f, -8388608.0f), 8388607.0f)); }
-};
-
 // One 4-byte / 8-byte load that stays one: written as `*p`, four neighbouring 4-byte loads are fused by the compiler's load
 // vectoriser into ONE 16-byte load at an address that is only 4-byte aligned (the target reports such a load as legal), and
 // the branches of load_four then fold into that single load.  A relaxed load at single-thread scope is an ordinary
@@ -159,11 +149,7 @@ template <int M>
 int launch(const EgressMixArgs& a, hipStream_t stream)
 {
     const dim3 grid(a.n_units), block(kThreads);
-    if (a.file_format == FVAD_INGEST_F32) hipLaunchKernelGGL((egress_mix_kernel<float, M>), grid, block, 0, stream, a);
-    else if (a.file_format == FVAD_INGEST_PCM16) hipLaunchKernelGGL((egress_mix_kernel<int16_t, M>), grid, block, 0, stream, a);
-    else if (a.file_format == FVAD_INGEST_PCM24) hipLaunchKernelGGL((egress_mix_kernel<Pcm24, M>), grid, block, 0, stream, a);
-    else return (int)hipErrorInvalidValue; // (the callers refuse the formats before they get here)
-    return (int)hipGetLastError();
+    return launch_file_format(a.file_format, [&](auto f) { hipLaunchKernelGGL((egress_mix_kernel<decltype(f), M>), grid, block, 0, stream, a); });
 }
 
 } // namespace

@@ -36,33 +36,52 @@
 //   bytes apart; C channels of f32: gcd(C, 32)-way (64 channels: every lane of a half on one bank, 32-way, on 1 / 35 of the
 //   LDS instructions).
 // Occupancy: 72.0 KB of LDS with the table (2 workgroups of 4 wavefronts on a compute unit's 160 KB), 48.0 KB without (3).
+//
+// fvad_egress_resample_strided* (egress_strided_kernel) is the same tile body over a STRIDED stream.  Stream sample s of channel
+// c is lane sample src_off + c lane_stride + (s - frame_base) step: NSNet2's own 16 kHz output lies 3 apart in the 48 kHz lanes
+// (K3 puts network sample j unchanged at lane index 3 j + 2 and lerps the two in front of it), and a recording made from that
+// stream carries neither the lerp's droop nor its images.  The sum, its ascending-j f32 fma chain from +0 with the zero extension
+// skipped, the conversion (Quant<F>), placement (Sink<F>::store) and drain_tile, the tile (egress_resample_tile: the window is
+// 8192 STAGED samples whatever the step), the per-channel loop and the LDS-or-global tap table are one text below (polyphase_tile),
+// every count in STRIDED samples.  So the bytes are fvad_egress_resample's over a compacted copy of the lanes, and with step 1
+// over the lanes themselves.  What differs is the staging alone, under `if constexpr (kStrided)`: for each channel the tile's
+// window of n <= kClipTile stream samples is staged COMPACTED into win[] by stage_tile_strided, from the lane span of
+// (n - 1) step + 1 samples at src_off + c lane_stride + (lo - frame_base) step (64-bit; inside the span (n - 1) step < 2^17 is
+// 32-bit).  Only on-stride samples are loaded: no byte outside the span is read and no off-stride sample can reach an output.
+//
+// The strided staging's cost, computed.  Two forms read the span: dword loads `step` apart, or 16-byte contiguous loads of which
+// only the on-stride words are written to LDS.  A 128-byte line holds 32 / step on-stride samples, so at step <= 32 both touch
+// every line of the span once per tile: the same (n - 1) step / 32 + 1 lines through the vector cache, the same HBM bytes -- the
+// lanes' bytes, what fvad_egress_resample reads for the same recording.  They differ in instructions.  Per lane and full window
+// (n = 8192):
+// - dword loads: 32 loads and 32 LDS writes whatever the step; a wavefront's load spans 64 step words = 2 step lines (6 at
+//   step 3); the writes are 64 consecutive words, conflict-free (Guideline 4: ds_write_b32 is banked (a / 4) mod 32 within each
+//   32-lane half);
+// - 16-byte loads: 8 step loads (24 at step 3, 128 at step 16), 1 KB each, and min(4, ceil(4 / step) + 1) predicated LDS writes
+//   per load (4 at step 3: 96), neighbouring writers 4 words apart at step 3: 11 lanes of a half over 44 words, 2-way on 3 banks;
+//   plus stage_tile's head and tail.
+// The dword form is taken: no more instructions at step 3 (64 against 120), fewer from step 4 on, no conflicts, no head or tail,
+// and the read bound holds by construction.  It is the one place in the egress kernels where neighbouring lanes do not load
+// neighbouring addresses.  The rest of the LDS cost is the plain kernel's, unchanged; at 1/1 with one tap (a 16 kHz recording of
+// the network's samples) an output is one window read, one fma and one image write.
+// Occupancy of the strided kernel, from the resource-usage output: 73 744 B of LDS with the table (2 workgroups: 2 waves per
+// SIMD), 49 168 B without (3); 48 VGPRs in all six instances (the staging loop's loads are unrolled and in flight together), no
+// scratch.  LDS, not registers, sets the occupancy.
 #include <hip/hip_runtime.h>
 
 #include "egress_device.h"
 #include "kernels.h"
+#include "stage_tile_strided.h"
 
 namespace {
 
 constexpr int kThreads = kStageThreads;
 
-// Quant<F>: the f32 result as the file sample's integer image (fvad_egress's rules for f32 lanes)
-template <typename F> struct Quant;
-template <> struct Quant<float> { __device__ static uint32_t run(float y) { return __float_as_uint(y); } };
-template <> struct Quant<int16_t> {
-    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f)); }
-};
-template <> struct Quant<Pcm24> {
-    __device__ static uint32_t run(float y) { return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(y * 8388608.0f, -8388608.0f), 8388607.0f)); }
-};
-
-} // namespace
-
-template <typename F, bool TL>
-__global__ __launch_bounds__(kThreads) void egress_resample_kernel(EgressResampleArgs a)
+// One tile of either kernel: win[] holds a channel's window (kClipTile samples, and stage_tile's 4 of alignment slack in the
+// plain kernel), img[] the tile's byte image, tab_lds[] the tap table when TL.  `step` is read by the strided kernel alone.
+template <typename F, bool TL, bool kStrided>
+__device__ inline void polyphase_tile(const EgressResampleArgs& a, uint32_t step, float* win, uint8_t* img, float* tab_lds)
 {
-    __shared__ __attribute__((aligned(16))) float win[kClipTile + 4];
-    __shared__ __attribute__((aligned(16))) uint8_t img[kIngestTileBytes + 16];
-    __shared__ float tab_lds[TL ? kClipResampleTableLds : 1];
     constexpr int B = Sink<F>::kBytes;
     const uint32_t u = blockIdx.x;
     const uint32_t ji = find_job(a.unit_prefix, a.n_jobs, u);
@@ -94,9 +113,16 @@ __global__ __launch_bounds__(kThreads) void egress_resample_kernel(EgressResampl
     const bool aligned = B == 3 ? false : (shift % B) == 0;
     for (int c = 0; c < C; ++c) {
         if (c) __syncthreads(); // the previous channel's window is read
+        // the window's first sample in its lane: the check has made sure lo >= frame_base and that the window (strided: its
+        // span) lies in the lane.  ws: where stage_tile put it in win[]; the strided staging compacts it to win[0]
         int ws = 0;
-        if (n > 0) ws = stage_tile(a.lanes + j.src_off + (uint64_t)c * a.lane_stride + (lo - j.frame_base), n, win);
-        else __syncthreads();
+        if constexpr (kStrided) {
+            if (n > 0) stage_tile_strided(a.lanes + j.src_off + (uint64_t)c * a.lane_stride + (lo - j.frame_base) * step, n, step, win);
+            else __syncthreads();
+        } else {
+            if (n > 0) ws = stage_tile(a.lanes + j.src_off + (uint64_t)c * a.lane_stride + (lo - j.frame_base), n, win);
+            else __syncthreads();
+        }
         uint8_t* at = img + shift + c * B;
         for (int e = tid; e < n_out; e += kThreads) {
             float acc = 0.0f;
@@ -123,23 +149,44 @@ __global__ __launch_bounds__(kThreads) void egress_resample_kernel(EgressResampl
     drain_tile(dst, n_out * C * B, shift, img);
 }
 
+} // namespace
+
+template <typename F, bool TL>
+__global__ __launch_bounds__(kThreads) void egress_resample_kernel(EgressResampleArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float win[kClipTile + 4];
+    __shared__ __attribute__((aligned(16))) uint8_t img[kIngestTileBytes + 16];
+    __shared__ float tab_lds[TL ? kClipResampleTableLds : 1];
+    polyphase_tile<F, TL, false>(a, 0, win, img, tab_lds);
+}
+
+template <typename F, bool TL>
+__global__ __launch_bounds__(kThreads) void egress_strided_kernel(EgressStridedArgs s)
+{
+    __shared__ float win[kClipTile];
+    __shared__ __attribute__((aligned(16))) uint8_t img[kIngestTileBytes + 16];
+    __shared__ float tab_lds[TL ? kClipResampleTableLds : 1];
+    polyphase_tile<F, TL, true>(s.r, s.step, win, img, tab_lds);
+}
+
 namespace {
 
-template <bool TL>
-int launch(const EgressResampleArgs& a, hipStream_t stream)
+template <typename F, bool TL> auto kernel_of(const EgressResampleArgs&) { return egress_resample_kernel<F, TL>; }
+template <typename F, bool TL> auto kernel_of(const EgressStridedArgs&) { return egress_strided_kernel<F, TL>; }
+
+// args: a kernel's argument, r: the EgressResampleArgs in it.  The tap table is staged in LDS when it fits there.
+template <typename A>
+int launch(const A& args, const EgressResampleArgs& r, hipStream_t stream)
 {
-    const dim3 grid(a.n_units), block(kThreads);
-    if (a.file_format == FVAD_INGEST_F32) hipLaunchKernelGGL((egress_resample_kernel<float, TL>), grid, block, 0, stream, a);
-    else if (a.file_format == FVAD_INGEST_PCM16) hipLaunchKernelGGL((egress_resample_kernel<int16_t, TL>), grid, block, 0, stream, a);
-    else if (a.file_format == FVAD_INGEST_PCM24) hipLaunchKernelGGL((egress_resample_kernel<Pcm24, TL>), grid, block, 0, stream, a);
-    else return (int)hipErrorInvalidValue; // (the callers refuse the formats before they get here)
-    return (int)hipGetLastError();
+    const dim3 grid(r.n_units), block(kThreads);
+    const bool in_lds = (uint64_t)((r.n_taps + r.up - 1) / r.up) * r.up <= kClipResampleTableLds;
+    return launch_file_format(r.file_format, [&](auto f) {
+        using F = decltype(f);
+        hipLaunchKernelGGL((in_lds ? kernel_of<F, true>(args) : kernel_of<F, false>(args)), grid, block, 0, stream, args);
+    });
 }
 
 } // namespace
 
-int fvad_launch_egress_resample(const EgressResampleArgs& a, hipStream_t stream)
-{
-    const bool in_lds = (uint64_t)((a.n_taps + a.up - 1) / a.up) * a.up <= kClipResampleTableLds;
-    return in_lds ? launch<true>(a, stream) : launch<false>(a, stream);
-}
+int fvad_launch_egress_resample(const EgressResampleArgs& a, hipStream_t stream) { return launch(a, a, stream); }
+int fvad_launch_egress_strided(const EgressStridedArgs& s, hipStream_t stream) { return launch(s, s.r, stream); }

@@ -1,5 +1,5 @@
 // stage_tile_strided.h -- every step-th f32 of a run staged COMPACTED through LDS once, by a workgroup of kStageThreads lanes
-// (kernels_egress_strided.hip: a tile's window of a stream that lies `step` apart in its lane).  stage_tile's sibling for a
+// (kernels_egress_resample.hip, egress_strided_kernel: a tile's window of a stream that lies `step` apart in its lane).  stage_tile's sibling for a
 // source of which only one sample in `step` is wanted.
 #pragma once
 #include "stage_tile.h"

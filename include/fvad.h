@@ -1340,7 +1340,7 @@ int fvad_egress_resample(fvad_ctx *ctx, const void *d_lanes, int src_format, siz
  * output: network sample j lands unchanged at lane index 3 j + 2 and the two samples in front of it are lerps.  A lerp is a
  * triangular filter: a network tone at 6 kHz stands in the lanes at -3.8 dB with images at 10 kHz (-11.8 dB, both against the
  * network's tone) and 22 kHz (-20 dB); a 7.5 kHz tone at -6.1 dB, its image at 8.5 kHz at -8.1 dB.  The VAD wants exactly these
- * lanes; a listener does not.  The stream lane[3 j + 2] is the network's output bit for bit, and ONE kernel (csrc/kernels_egress_strided.hip), the
+ * lanes; a listener does not.  The stream lane[3 j + 2] is the network's output bit for bit, and ONE kernel (csrc/kernels_egress_resample.hip), the
  * resampling egress over a stream that lies src_step apart in its lanes, writes recordings from it: at 16 kHz (1/1 with the
  * tap 1.0) lossless at a third of the bytes, at 48 kHz (3/1) a band-limited interpolation in place of the lerp, at 44.1 kHz one
  * filter (441/160) in place of two.
