@@ -459,6 +459,14 @@ pub extern "c" fn fvad_clips_export_resampled_device(ctx: *Ctx, d_src: *const an
 pub extern "c" fn fvad_clips_export_resampled(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
 pub extern "c" fn fvad_clips_export_split_resampled_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
 pub extern "c" fn fvad_clips_export_split_resampled(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, up: u32, down: u32, taps: ?[*]const f32, n_taps: u32) c_int;
+// with a recogniser's front end: clip i leaves as [floor(L / hop)][n_mels] log-mel features of its strided stream (f32)
+pub const clip_mel_nfft_max = 2048; // FVAD_CLIP_MEL_NFFT_MAX
+pub const clip_mel_bands_max = 128; // FVAD_CLIP_MEL_BANDS_MAX
+pub extern "c" fn fvad_mel_design(sample_rate: f64, n_fft: u32, n_mels: u32, fmin: f64, fmax: f64, matrix: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_plan_mel(lens: ?[*]const u64, skips: ?[*]const u32, n_clips: usize, step: u32, n_fft: u32, hop: u32, n_mels: u32, n_frames: ?[*]u64, offsets: ?[*]u64, total: *u64) c_int;
+pub extern "c" fn fvad_clips_mel_check(d_src: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: ?[*]const f32, n_mels: u32, matrix: ?[*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, offsets: ?[*]u64, total: ?*u64) c_int;
+pub extern "c" fn fvad_clips_export_mel_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, feat_max: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_export_mel(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, feat_max: ?[*]f32) c_int;
 
 // resampling ingest: files at another rate filtered and re-timed into 48 kHz f32 lanes (a rational up/down polyphase resampler)
 pub extern "c" fn fvad_resample_ratio(rate_in: u32, rate_out: u32, up: *u32, down: *u32) c_int;

@@ -29,6 +29,8 @@ CLIP_FIELDS = 4                  # a clip: first_lane, n_channels, sample_from, 
 CLIP_SPLIT_FIELDS = 7            # a split clip: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len (uint64 each)
 CLIP_STEP_MAX = 16               # the largest step of the strided clip exports
 CLIP_FIR_TAPS_MAX = 513          # the most taps of the filtered clip exports
+CLIP_MEL_NFFT_MAX = 2048         # the largest n_fft of the log-mel clip exports
+CLIP_MEL_BANDS_MAX = 128         # the most mel bands of the log-mel clip exports
 INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
 INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
@@ -370,6 +372,20 @@ SIGNATURES = {
     "fvad_clips_export_split_fir": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
                                               C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64), C.c_uint32,
                                               C.POINTER(C.c_uint32), c_float_p, C.c_uint32]),
+    "fvad_mel_design": (C.c_int, [C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p]),
+    "fvad_clips_plan_mel": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_mel_check": (C.c_int, [vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.c_int, C.c_uint32,
+                                       C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_mel_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                               c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                               C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                               C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_export_mel": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                        c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                               C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                               C.POINTER(C.c_uint64), c_float_p]),
     "fvad_clips_resample_check": (C.c_int, [C.c_uint32, C.c_uint32, c_float_p, C.c_uint32]),
     "fvad_clips_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "fvad_clips_plan_resampled": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
@@ -780,6 +796,42 @@ class Context:
         out = np.zeros(max(total, 1), np.int16 if out_pcm16 else np.float32)
         self._ck(lib().fvad_clips_export(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
                  "fvad_clips_export")
+        res["out"] = out[:total]
+        return res
+
+    def clips_export_mel(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, step=1, skips=None, hop=160,
+                         floor=1e-10, norm=None, d_out=None, out_capacity=None):
+        """fvad_clips_export_mel (d_out None: the features come back as a float32 array) or fvad_clips_export_mel_device (d_out:
+        a device address with room for out_capacity floats): log-mel features of the clips' picked channels.  window: [n_fft]
+        float32, matrix: [n_mels][n_fft / 2 + 1] float32, norm: None or (range, offset, scale).
+        Returns dict(best_channel, best_rms, runner_up_rms, offsets, total, n_frames, feat_max[, out]); clip i's features are
+        out[offsets[i] : offsets[i] + n_frames[i] * n_mels].reshape(n_frames[i], n_mels)."""
+        clips = _clip_rows(clips)
+        n = clips.shape[0]
+        window = np.ascontiguousarray(np.asarray(window, np.float32).reshape(-1))
+        matrix = np.ascontiguousarray(np.asarray(matrix, np.float32))
+        n_fft, n_mels = window.shape[0], matrix.shape[0]
+        if matrix.ndim != 2 or matrix.shape[1] != n_fft // 2 + 1:
+            raise ValueError("matrix must be [n_mels][n_fft / 2 + 1] for the window's n_fft")
+        skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+        norm = None if norm is None else np.ascontiguousarray(np.asarray(norm, np.float32).reshape(3))
+        frames, offsets, total = clips_plan_mel(clips[:, 3] - clips[:, 2], skips, step, n_fft, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        n_frames, feat_max = np.zeros(n, np.uint64), np.zeros(n, np.float32)
+        args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
+                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n_fft, hop, fptr(window), n_mels, fptr(matrix),
+                floor, None if norm is None else fptr(norm), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(feat_max))
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "n_frames": n_frames,
+               "feat_max": feat_max}
+        if d_out is not None:
+            self._ck(lib().fvad_clips_export_mel_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
+                     "fvad_clips_export_mel_device")
+            return res
+        out = np.zeros(max(total, 1), np.float32)
+        self._ck(lib().fvad_clips_export_mel(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
+                 "fvad_clips_export_mel")
         res["out"] = out[:total]
         return res
 
@@ -1813,6 +1865,45 @@ def clips_plan_resampled(lens, up, down, out_pcm16=False):
                                           out_lens.ctypes.data_as(C.POINTER(C.c_uint64)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
                                           C.byref(total)), "fvad_clips_plan_resampled")
     return out_lens, offsets, int(total.value)
+
+
+def mel_design(sample_rate, n_fft, n_mels, fmin, fmax):
+    """fvad_mel_design: Slaney's mel filter bank [n_mels][n_fft / 2 + 1] float32 (librosa.filters.mel's formula)"""
+    matrix = np.zeros((max(int(n_mels), 1), max(int(n_fft), 0) // 2 + 1), np.float32)
+    check(lib().fvad_mel_design(sample_rate, int(n_fft), int(n_mels), fmin, fmax, fptr(matrix)), "fvad_mel_design")
+    return matrix
+
+
+def clips_plan_mel(lens, skips, step, n_fft, hop, n_mels):
+    """fvad_clips_plan_mel: (n_frames [n] uint64, offsets [n] uint64, total), offsets and total in floats; skips None: 0"""
+    lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
+    n = lens.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+    n_frames, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
+    check(lib().fvad_clips_plan_mel(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(step), int(n_fft),
+                                    int(hop), int(n_mels), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_mel")
+    return n_frames, offsets, int(total.value)
+
+
+def clips_mel_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, n_fft, hop,
+                    window, n_mels, matrix, floor, norm, out_format=CLIP_F32):
+    """fvad_clips_mel_check (host only; d_src and out are addresses) -> (status, n_frames, offsets, total).  window, matrix and
+    norm are float32 arrays or None (NULL), passed as they are"""
+    clips = None if clips is None else _clip_rows(clips)
+    n = 0 if clips is None else clips.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
+    keep = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix, norm)]
+    n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
+    st = lib().fvad_clips_mel_check(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
+                                    None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
+                                    out_capacity, int(device_out), int(step),
+                                    None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_fft), int(hop),
+                                    None if keep[0] is None else fptr(keep[0]), int(n_mels), None if keep[1] is None else fptr(keep[1]),
+                                    floor, None if keep[2] is None else fptr(keep[2]), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    return st, n_frames[:n], offsets[:n], int(total.value)
 
 
 def clips_resample_check(up, down, taps):

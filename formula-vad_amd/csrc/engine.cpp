@@ -240,6 +240,11 @@ static int apply_option(fvad_ctx* ctx, const std::string& name, const char* valu
         if (!unset && (!end || *end || v[0] == '-')) return FVAD_ERR_INVALID_ARGUMENT;
         tn.vad_trigger_max_bytes = c;
     }
+    else if (name == "clip_mel_fft") { // fvad_clips_export_mel*: "auto" (n_fft == 400 on the eight-frames-per-wavefront transform) or "generic" (every size on the generic one)
+        if (unset || v == "auto") tn.clip_mel_generic = false;
+        else if (v == "generic") tn.clip_mel_generic = true;
+        else return FVAD_ERR_INVALID_ARGUMENT;
+    }
     else if (name == "vad_seg_cap") { // fvad_vad_batch_run_device's first segment room per machine (tests: the overflow path); unset = 512 MB over all machines
         long c = 0;
         if (!unset && (!to_long(c) || c < 1 || c > (1L << 24))) return FVAD_ERR_INVALID_ARGUMENT;
@@ -341,7 +346,7 @@ int fvad_ctx_create(int device, fvad_ctx** out)
     if (get_vad_plan(ctx, kVadFft, &pl) != FVAD_OK) { fvad_ctx_destroy(ctx); return FVAD_ERR_HIP; }
     // the tuning variables FVAD_<NAME> are read here, once; a bad value fails the creation rather than being ignored
     for (const char* opt : {"nn_math", "gru_kernel", "gemm_kernel", "h3_waves", "max_chunks", "copy_threads", "ingest_ring_bytes", "ws_spin_ticks",
-                            "no_pipeline", "run_groups", "trace_run", "trace_kernels", "reproducible", "vad_chain", "vad_avgs", "vad_trigger"}) {
+                            "no_pipeline", "run_groups", "trace_run", "trace_kernels", "reproducible", "vad_chain", "vad_avgs", "vad_trigger", "clip_mel_fft"}) {
         std::string env = std::string("FVAD_") + opt;
         for (char& c : env) c = (char)toupper((unsigned char)c);
         const char* v = getenv(env.c_str());

@@ -198,6 +198,7 @@ struct Tuning {
     int vad_trigger = 0;         // device VAD sweeps: 0 = one full machine per (stream, config) ("config"), 1 = one trigger machine per (stream, trigger key) that emits bits and a finishing kernel per config ("shared", needs vad_chain "coop"); same bits
     unsigned long long vad_trigger_max_bytes = 4ull << 30; // a part whose bits need more runs the per-config machines (a guard computed from shapes, not a measurement)
     int vad_seg_cap = 0;         // fvad_vad_batch_run_device: segments per machine the first launch has room for (more: a second launch); 0 = 512 MB in all
+    bool clip_mel_generic = false; // fvad_clips_export_mel*: n_fft == 400 on the generic transform too ("auto" | "generic": tests and the A/B)
     unsigned long long ingest_ring_bytes = 32ull << 20; // fvad_ingest: raw bytes per batch of its two-slot ring (1 KB .. 1 GB, a multiple of 16; tests
                                  // set it small so that a source is cut several times; the result has the same bits whatever the value)
     int nn_trim = 3;             // large-batch f32 family, bit 1: fc2 / fc3 issue no MFMAs for their all-padding 39th column tile; bit 2: layer 1's

@@ -517,6 +517,35 @@ struct ClipSplitResampleArgs {
 int fvad_launch_clip_gather_resampled(const ClipResampleArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
 int fvad_launch_clip_gather_resampled_split(const ClipSplitResampleArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
 
+// The log-mel features (kernels_clips_mel.hip, fvad_clips_export_mel*): of the picked channel's strided stream s[i] = sample
+// skip + i * step (L = ceil((len - skip) / step) of them) the frames t < T = floor(L / hop) of n_fft taps, centred with
+// reflection, as power spectrum -> mel bands -> log10.  RMS and pick are the kernels above over every sample.  A tile is
+// clip_mel_tile_frames consecutive frames of one clip; c.tile_prefix / c.n_tiles count these tiles, c.out is f32 and
+// jobs[i].out_off the clip's slot of [T][n_mels] floats.
+constexpr uint32_t kClipMelNfftMax = 2048;  // FVAD_CLIP_MEL_NFFT_MAX
+constexpr uint32_t kClipMelBandsMax = 128;  // FVAD_CLIP_MEL_BANDS_MAX
+constexpr uint32_t kClipMelTileFrames = 32; // four wavefronts of eight frames in the 400-point form
+// the frames of a tile: its window (F - 1) hop + n_fft of the stream fits kClipTile staged samples
+constexpr uint32_t clip_mel_tile_frames(uint32_t n_fft, uint32_t hop)
+{
+    return ((uint32_t)kClipTile - n_fft) / hop + 1 < kClipMelTileFrames ? ((uint32_t)kClipTile - n_fft) / hop + 1 : kClipMelTileFrames;
+}
+struct ClipMelArgs {
+    ClipArgs c;
+    VadFftPlan pl;         // n = n_fft: tw, st and the radices of the generic transform (win and norm are not used)
+    const float* window;   // [n_fft] (device), the caller's
+    const float* matrix_t; // [n_fft / 2 + 1][n_mels] (device): the caller's matrix transposed, so that lanes m read neighbours
+    float* tile_max;       // [c.n_tiles]: a tile's largest feature
+    float* feat_max;       // [c.n_clips]: a clip's largest feature (clip_mel_max)
+    uint32_t step, hop, n_mels, tile_frames;
+    float floor, log_floor; // log_floor = log10(floor), evaluated on the host in double and rounded once
+    float norm_range, norm_offset, norm_scale;
+    int fft400;            // the eight-frames-per-wavefront transform (n_fft == 400 only)
+};
+int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
+int fvad_launch_clip_mel_max(const ClipMelArgs& a, hipStream_t stream);  // (after fvad_launch_clip_mel)
+int fvad_launch_clip_mel_norm(const ClipMelArgs& a, hipStream_t stream); // (after fvad_launch_clip_mel_max)
+
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
 // multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane

@@ -7,7 +7,8 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
     python -m ... simulator.py -i plan.json --export-clips DIR [--clips-pcm16]   (or: run_clips(path, DIR): the plan's speech
                                                       clips, original and denoised, cut and picked on the GPU;
                                                       --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
-                                                      --clips-original-filter fir: anti-aliased, also at 24000 and 8000)
+                                                      --clips-original-filter fir: anti-aliased, also at 24000 and 8000;
+                                                      --clips-features logmel: the denoised clips' log-mel features as .npy)
     python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source] [--denoised-source lanes|network]   (or: run_denoise(path,
                                                       DIR): the denoised recordings as WAV files, converted and interleaved
                                                       on the GPU; --denoised-kinds denoised,original,residual,mix
@@ -560,7 +561,71 @@ def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample,
     return e
 
 
-def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs):
+CLIP_FEATURES = (None, "logmel")
+CLIP_FEATURES_NORM = {None: None, "whisper": (8.0, 4.0, 0.25)}   # (range, offset, scale), the maximum taken per clip
+# Whisper's front end on NSNet2's own 16 kHz samples: step 3 at the denoised kind's phase, 400-point periodic Hann, hop 160,
+# 80 Slaney bands over 0 .. 8 kHz, log10(max(., 1e-10))
+LOGMEL = dict(step=3, n_fft=400, hop=160, n_mels=80, sample_rate=16000, fmin=0.0, fmax=8000.0, floor=1e-10)
+
+
+def _check_features(features, features_norm, slice_chunks):
+    """ValueError for what run_clips does not offer with features, before any work"""
+    if features not in CLIP_FEATURES:
+        raise ValueError(f"features = {features!r}: one of {CLIP_FEATURES}")
+    if features_norm not in CLIP_FEATURES_NORM:
+        raise ValueError(f"features_norm = {features_norm!r}: one of {tuple(CLIP_FEATURES_NORM)}")
+    if features is None and features_norm is not None:
+        raise ValueError("features_norm needs features")
+    if features is not None and slice_chunks is not None:
+        raise ValueError("features with slice_chunks: the split-source form of fvad_clips_export_mel does not exist yet")
+
+
+def logmel_window():
+    """the periodic Hann window of LOGMEL's n_fft, float32"""
+    n = LOGMEL["n_fft"]
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)
+
+
+def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, manifests, features_norm):
+    """the features of run_clips: one fvad_clips_export_mel over the denoised lanes' clips, NAME-####-denoised.logmel.npy per
+    clip and its manifest entry under "features".  A clip too short for one reflected frame has no entry and is counted in
+    features_skipped"""
+    p = LOGMEL
+    rows, owner = [], []
+    for i, (segs, _) in enumerate(per_inst):
+        clips, _ = fv.clips_from_segments(segs, lane0[i], n_channels[i], avail[i])
+        manifests[i]["features_skipped"] = 0
+        k = 0
+        for c in clips:
+            while (segs[k][0], segs[k][1]) != (c[2], c[3]):
+                k += 1
+            skip = int(fv.clips_phase_skips(c[2:3], p["step"], CLIP_PHASE["denoised"])[0])
+            L = -(-(int(c[3] - c[2]) - skip) // p["step"])
+            if L >= p["n_fft"] // 2 + 1 and L >= p["hop"]:
+                rows.append(c)
+                owner.append((i, k))
+            else:
+                manifests[i]["features_skipped"] += 1
+            k += 1
+    if not rows:
+        return
+    rows = np.array(rows, np.uint64)
+    skips = fv.clips_phase_skips(rows[:, 2], p["step"], CLIP_PHASE["denoised"])
+    matrix = fv.mel_design(p["sample_rate"], p["n_fft"], p["n_mels"], p["fmin"], p["fmax"])
+    res = ctx.clips_export_mel(r.d_den, False, r.n_lanes, r.n_den, r.n_den, rows, logmel_window(), matrix, step=p["step"], skips=skips,
+                               hop=p["hop"], floor=p["floor"], norm=CLIP_FEATURES_NORM[features_norm])
+    for j, (i, k) in enumerate(owner):
+        o, T = int(res["offsets"][j]), int(res["n_frames"][j])
+        path = os.path.join(out_dir, "{}-{:04d}-denoised.logmel.npy".format(insts[i]["name"], k))
+        np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
+        manifests[i]["clips"][k]["features"] = {
+            "file": os.path.basename(path), "frames": T, "n_mels": p["n_mels"], "n_fft": p["n_fft"], "hop": p["hop"],
+            "sample_rate": p["sample_rate"], "first_sample": int(rows[j, 2]) + int(skips[j]), "best_channel": int(res["best_channel"][j]),
+            "max": float(res["feat_max"][j]), "floor": p["floor"], "norm": features_norm,
+            "mel": {"design": "slaney", "fmin": p["fmin"], "fmax": p["fmax"]}}
+
+
+def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs, features=None, features_norm=None):
     """run_clips for the instances of one context -> [(segments, audit, manifest)] in the order given"""
     if not audio:
         return []
@@ -615,6 +680,9 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs):
                 _write_clip(path, res["out"][o:o + n], pcm16, rates[kind])
                 manifests[i]["clips"][k][kind] = _clip_entry(path, res["best_channel"][j], res["best_rms"][j], res["runner_up_rms"][j], rates[kind],
                                                              int(rows[j, 2]) + (0 if skips is None else int(skips[j])), n, firs[kind])
+        if features is not None:
+            _features_share(ctx, r, insts, per_inst, lane0, [_dims(a)[0] for a in audio], [n * chunk for n in r.n_chunks], out_dir, manifests,
+                            features_norm)
         return [(segs, audit, m) for (segs, audit), m in zip(per_inst, manifests)]
     finally:
         for d in held:
@@ -622,7 +690,7 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs):
 
 
 def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None,
-              denoised_rate=48000, original_rate=48000, original_filter="none", denoised_filter="none"):
+              denoised_rate=48000, original_rate=48000, original_filter="none", denoised_filter="none", features=None, features_norm=None):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -662,8 +730,18 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     whose ratio has up <= 640 and whose default design fits 20481 taps -- 44100, 32000, 22050 and 11025; 24000, 16000 and 8000
     too --, anything else raises before any work.  Output o of a clip sits o / R seconds after the clip's first sample: the phase
     starts at the clip, so "first_sample" is the segment's own start and "length" is ceil(len * up / down).  The manifest entries
-    gain "filter": {"design": "kaiser_sinc_polyphase", "up", "down", "half", "cutoff", "beta", "taps"}."""
+    gain "filter": {"design": "kaiser_sinc_polyphase", "up", "down", "half", "cutoff", "beta", "taps"}.
+    features "logmel": after the usual exports, one fvad_clips_export_mel over the denoised lanes' clips -- whatever rate and
+    filter the denoised WAV files have -- with LOGMEL's parameters: the network's own 16 kHz samples (step 3, phase 2), 400-point
+    periodic Hann, hop 160, fvad_mel_design(16000, 400, 80, 0, 8000), floor 1e-10.  Per clip NAME-####-denoised.logmel.npy
+    (np.save, float32 [frames, 80]; frames = floor(L / 160) of the clip's L 16 kHz samples) and in its manifest entry "features":
+    {file, frames, n_mels, n_fft, hop, sample_rate, first_sample, best_channel, max, floor, norm, mel: {design, fmin, fmax}}; a
+    clip too short for one frame (under 201 samples at 16 kHz) has none and is counted in features_skipped.  features_norm
+    "whisper": (max(x, max - 8) + 4) / 4 with the maximum taken per clip ("max" stays the un-normalised one).  An unknown
+    features or features_norm, features_norm without features, and features with slice_chunks (the split-source form of the
+    feature export does not exist yet) raise before any work.  With features None every file and manifest is what it was."""
     _check_ingest(ingest)
+    _check_features(features, features_norm, slice_chunks)
     rates, firs = _clip_rates(original_rate, denoised_rate, original_filter, denoised_filter)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
@@ -682,7 +760,7 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
             try:
                 insts_d, audio_d = [plan["instances"][i] for i in parts[d]], [audio[i] for i in parts[d]]
                 if slice_chunks is None:
-                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates, firs)
+                    done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates, firs, features, features_norm)
                 else:
                     done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates, firs)
             except Exception as e:  # re-raised below, in the caller's thread
@@ -2634,6 +2712,12 @@ def arg_parser():
     ap.add_argument("--clips-denoised-filter", default="none", choices=CLIP_FILTERS,
                     help="with --export-clips: fir -- the same for the denoised clips (at 16000 they need no filter: use it for 24000 or 8000); "
                          "resample -- the same for the denoised clips")
+    ap.add_argument("--clips-features", default=None, metavar="KIND",
+                    help="with --export-clips: logmel -- also write every denoised clip's log-mel features, computed on the GPU from the "
+                         "network's own 16 kHz samples (400-point Hann, hop 160, 80 Slaney bands, log10), as NAME-####-denoised.logmel.npy; "
+                         "not with --slice-chunks")
+    ap.add_argument("--clips-features-norm", default=None, metavar="NORM",
+                    help="with --clips-features: whisper -- (max(x, max - 8) + 4) / 4, the maximum taken per clip")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")
@@ -2698,6 +2782,9 @@ def _parse_denoised_rate(text):
 def main(argv=None):
     a = arg_parser().parse_args(argv)
     check_modes(a)
+    if (a.clips_features is not None or a.clips_features_norm is not None) and not a.export_clips:
+        raise ValueError("--clips-features and --clips-features-norm need --export-clips")
+    _check_features(a.clips_features, a.clips_features_norm, a.slice_chunks)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.export_denoised:
         kinds = None if a.denoised_kinds is None else tuple(k for k in a.denoised_kinds.split(",") if k != "")
@@ -2717,7 +2804,8 @@ def main(argv=None):
         info = {}
         text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest,
                             slice_chunks=a.slice_chunks, info=info, denoised_rate=a.clips_denoised_rate, original_rate=a.clips_original_rate,
-                            original_filter=a.clips_original_filter, denoised_filter=a.clips_denoised_filter)
+                            original_filter=a.clips_original_filter, denoised_filter=a.clips_denoised_filter, features=a.clips_features,
+                            features_norm=a.clips_features_norm)
         sys.stdout.write(text)
         if info:
             sys.stdout.write(f"\n[{info['slices']} slices; held tails: {info['held_peak_bytes'] / 2 ** 20:.1f} MiB of device memory at most]\n")

@@ -1074,6 +1074,82 @@ int fvad_clips_export_split_resampled(fvad_ctx *ctx, const void *d_a, size_t a_l
                                       int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
                                       uint32_t up, uint32_t down, const float *taps, uint32_t n_taps);
 
+/* ------------------------------------------------------------------ batch Recorder with a front end: log-mel features of clips
+ * A recogniser does not take 16 kHz audio, it takes a log-mel spectrogram of it (Whisper: 400-point periodic-Hann STFT, hop 160,
+ * frames centred with reflection, power spectrum, 80 Slaney mel bands, log10(max(., 1e-10))).  These calls compute it from the
+ * device-resident lanes; per clip only [T][n_mels] floats cross PCIe (csrc/kernels_clips_mel.hip).  For a clip row:
+ * - Channel: picked exactly as fvad_clips_export picks it, over EVERY sample of the clip; best_channel, best_rms and
+ *   runner_up_rms are that call's bits.
+ * - Feature stream: s[i] = f32(clip sample skip + i * step) of the picked channel, i < L = ceil((len - skip) / step); step in
+ *   1..FVAD_CLIP_STEP_MAX and skip < step as in fvad_clips_plan_strided, skips as fvad_clips_phase_skips gives them (step 3 with
+ *   phase 2 on the denoised lanes: NSNet2's own 16 kHz samples).  PCM16 lanes give s / 32768.
+ * - Frames: n_fft even in 4..FVAD_CLIP_MEL_NFFT_MAX, hop in 1..n_fft, pad = n_fft / 2, T = floor(L / hop) frames -- torch.stft
+ *   with center = True and its last frame dropped, Whisper's convention.  Frame t, tap i reads s[rho(t * hop + i - pad)] with
+ *   rho(j) = -j for j < 0 and 2 (L - 1) - j for j >= L (reflection that does not repeat the edge).  A clip with L < pad + 1 or
+ *   T == 0 is refused.  Nothing outside the clip's samples is read, and no sample off the stride.
+ * - Spectrum: X = rfft(frame * window), window[n_fft] f32 from the caller; P[k] = re^2 + im^2 in f32, k = 0 .. n_fft / 2;
+ *   mel[m] = sum_k M[m][k] * P[k] with M[n_mels][n_fft / 2 + 1] f32 row-major from the caller, n_mels in
+ *   1..FVAD_CLIP_MEL_BANDS_MAX, one rounded product and one rounded sum per k in ascending k, no atomics;
+ *   feat = log10f(fmaxf(mel, floor)), floor a finite positive f32.  log10f(floor) itself is evaluated once per call on the host
+ *   (log10 in double, rounded to f32) and is what every mel <= floor gives: digital silence is exactly that value in every band.
+ * - Output: per clip [T][n_mels] f32, frame-major, in slots that are 16-byte aligned and in clip order (fvad_clips_plan_mel);
+ *   out_format must be FVAD_CLIP_F32, out_capacity and the offsets count floats.  The device form never writes the padding
+ *   between slots; the host form zeroes it, as fvad_clips_export does.
+ * - Per-clip reports: the four of fvad_clips_export, n_frames (T) and feat_max, the clip's largest feature before any
+ *   normalisation (a maximum has no rounding: a fixed tree per tile, then the tiles in order).
+ * - Normalisation, norm = (range, offset, scale), three finite f32, or NULL for none:
+ *   feat' = (fmaxf(feat, feat_max - range) + offset) * scale -- one rounded subtraction, one rounded sum, one rounded product,
+ *   never contracted (numpy float32 is the exact model).  (8, 4, 0.25) is Whisper's.  DEVIATION: the maximum is taken per CLIP;
+ *   Whisper takes it over its 30 s window, so a clip cut from a longer window can come out with another clamp.
+ * - INVARIANTS, bit for bit: a frame's features depend on that frame's samples and the call's parameters alone -- not on the
+ *   other clips, their order, the tile or wavefront slot the frame lands in, the alignment of either side or the call form --
+ *   and are the same run after run.  Which transform runs depends on n_fft and the context option clip_mel_fft alone ("auto":
+ *   n_fft == 400 on the eight-frames-per-wavefront transform, every other size on the generic mixed-radix one; "generic": every
+ *   size on the generic one; environment twin FVAD_CLIP_MEL_FFT), never on the size of the call.  The two transforms agree to
+ *   rounding, not bit for bit.
+ *
+ * fvad_mel_design (host only): matrix[n_mels][n_fft / 2 + 1] of Slaney's filter bank, evaluated in double and rounded once.
+ *   mel(f) = 3 f / 200 below 1 kHz and 15 + ln(f / 1000) / (ln 6.4 / 27) above; n_mels + 2 points equally spaced in mel from
+ *   fmin to fmax give the edges f_0 .. f_{n_mels + 1}; filter m is the triangle over the bin frequencies k * sample_rate / n_fft
+ *   that rises from f_m to f_{m+1} and falls to f_{m+2}, times 2 / (f_{m+2} - f_m).  FVAD_ERR_INVALID_ARGUMENT for fmin < 0,
+ *   fmax > sample_rate / 2, fmin >= fmax, a sample rate that is not positive and finite, NULL, or n_fft / n_mels outside the
+ *   exports' ranges.  This is librosa.filters.mel's formula (htk = False, norm = "slaney"); librosa was not at hand, so the
+ *   designer is checked against the formula written out independently, not against librosa's output.
+ * fvad_clips_plan_mel (host only): n_frames[i], offsets[i] and *total (floats) for clips of lens[i] samples; skips NULL means all
+ *   zero.  FVAD_ERR_INVALID_ARGUMENT for a bad step, n_fft, hop or n_mels, a skip >= step, a clip with len <= skip, L < pad + 1
+ *   or no frame, NULLs, or a total that does not fit 64 bits.
+ * fvad_clips_mel_check (host only; d_src and out are addresses, nothing is read through them): every argument rule of the two
+ *   exports in the one order both report them in -- NULLs, formats, alignment (device_out: out 16-byte aligned), lane_stride,
+ *   the rows' own rules, then step, n_fft, hop, n_mels, per clip its skip and frames (fvad_clips_plan_mel's rules), a window,
+ *   matrix, floor or norm value that is not finite (floor also: not positive), then FVAD_ERR_OUT_OF_RANGE for a clip past
+ *   n_samples or n_lanes, FVAD_ERR_BUFFER_TOO_SMALL for out_capacity below the total, and more than 2^31 - 1 units or tiles of
+ *   frames in one call.  Fills n_frames, offsets and *total (each may be NULL) as far as the rules held.
+ * fvad_clips_export_mel_device / fvad_clips_export_mel: the full-rate call's arguments, then step, skips, n_fft, hop, window,
+ *   n_mels, matrix, floor, norm (window, matrix, norm: host memory) and the two new reports (each may be NULL).  Every error
+ *   comes back before any launch.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_mel400 or clip_mel, clip_mel_max and,
+ *   with norm, clip_mel_norm.  The split-source form (sliced runs) does not exist yet. */
+#define FVAD_CLIP_MEL_NFFT_MAX 2048
+#define FVAD_CLIP_MEL_BANDS_MAX 128
+int fvad_mel_design(double sample_rate, uint32_t n_fft, uint32_t n_mels, double fmin, double fmax, float *matrix);
+int fvad_clips_plan_mel(const uint64_t *lens, const uint32_t *skips, size_t n_clips, uint32_t step, uint32_t n_fft, uint32_t hop,
+                        uint32_t n_mels, uint64_t *n_frames, uint64_t *offsets, uint64_t *total);
+int fvad_clips_mel_check(const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                         const uint64_t *clips, size_t n_clips, int out_format, const void *out, size_t out_capacity,
+                         int device_out, uint32_t step, const uint32_t *skips, uint32_t n_fft, uint32_t hop, const float *window,
+                         uint32_t n_mels, const float *matrix, float floor, const float *norm, uint64_t *n_frames,
+                         uint64_t *offsets, uint64_t *total);
+int fvad_clips_export_mel_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                 size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                 size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                 uint64_t *out_offsets, uint32_t step, const uint32_t *skips, uint32_t n_fft, uint32_t hop,
+                                 const float *window, uint32_t n_mels, const float *matrix, float floor, const float *norm,
+                                 uint64_t *n_frames, float *feat_max);
+int fvad_clips_export_mel(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                          const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                          int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets, uint32_t step,
+                          const uint32_t *skips, uint32_t n_fft, uint32_t hop, const float *window, uint32_t n_mels,
+                          const float *matrix, float floor, const float *norm, uint64_t *n_frames, float *feat_max);
+
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
  * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
