@@ -1,5 +1,5 @@
-// clip_device.h -- device helpers shared by the batch Recorder's kernels (kernels_clips.hip, kernels_clips_split.hip): the search
-// of a prefix table and the sample conversions.
+// clip_device.h -- device helpers shared by the batch Recorder's kernels (kernels_clips*.hip): the search of a prefix
+// table and the sample conversions.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // clips_mel.h -- the rules of a log-mel clip export (fvad_clips_plan_mel, fvad_clips_mel_check, fvad_clips_export_mel*), host
 // only: the frame parameters, a clip's feature stream, its frame count and slot, and every argument rule of the two exports in
-// the one order both report them in.  Inline, so that host_clips_mel.cpp and engine_clips_mel.cpp state them once and the host
+// the one order both report them in.  Inline, so that host_clips_mel.cpp and engine_clips.cpp state them once and the host
 // file still builds alone (tests/sanitize/clips_mel_san.cpp).
 #pragma once
 #include <cmath>
@@ -12,7 +12,7 @@
 
 namespace fvad {
 
-constexpr uint64_t kMelSrcTile = 8192;  // kClipTile of kernels.h (engine_clips_mel.cpp asserts it)
+constexpr uint64_t kMelSrcTile = 8192;  // kClipTile of kernels.h (engine_clips.cpp asserts it)
 constexpr uint64_t kMelTileFrames = 32; // kClipMelTileFrames of kernels.h
 
 struct Mel {

@@ -1,28 +1,249 @@
-// engine_clips.cpp -- the batch Recorder: fvad_clips_plan / _from_segments (host only) and fvad_clips_export(_device), which
-// run kernels_clips.hip over device-resident lanes.  The reference finalises one AudioBuffer per completed segment, the quietest
+// engine_clips.cpp -- the batch Recorder: fvad_clips_plan / _from_segments (host only) and every fvad_clips_export*, which run
+// kernels_clips*.hip over device-resident lanes.  The reference finalises one AudioBuffer per completed segment, the quietest
 // channel over [sample_from, sample_to) (Recorder.zig:74-164); here every clip of a call is picked and packed in three launches
-// and only the packed clips leave the device.  The strided forms (fvad_clips_export_strided*) are the same calls with the strided
-// rules and slots (clips_strided.h) and kernels_clips_strided.hip's gather over tiles of its own; the filtered forms
-// (fvad_clips_export_fir*) are the strided calls with the tap rules (clips_fir.h) and kernels_clips_fir.hip's gather; the
-// resampled forms (fvad_clips_export_resampled*) are the full-rate calls with the ratio and tap rules and the slots of
-// clips_resample.h and kernels_clips_resample.hip's gather.
+// and only the packed clips leave the device.
+//
+// One engine for every form.  Written once: the tables a launch searches (build_tables, over a description per clip), the one
+// allocation that holds them beside the form's own parts, its uploads, the ClipArgs, RMS and pick, the read-back and the scatter
+// to the caller's arrays (run_clips, over either source), and the host-output wrapper (via_staging).  A form supplies its check,
+// its rows, its parts and its launches:
+// - fvad_clips_export*: a clip's channel is one run of a lane; rules in check_export, reported as "fvad_clips_export: ..."
+// - fvad_clips_export_split*: a head piece in buffer A followed by a body piece in buffer B; rules in fvad_clips_split_check's
+//   order (host_clips_split.cpp), reported as "<the entry point>: ..."
+//   Both in four forms (ClipForm of clips_rules.h): full rate, strided (kernels_clips_strided.hip), filtered
+//   (kernels_clips_fir.hip) and resampled (kernels_clips_resample.hip); the form's part is its taps as the gather walks them.
+// - fvad_clips_export_mel*: log-mel features of the picked channel's strided stream (kernels_clips_mel.hip) in place of a
+//   gather; rules in clips_mel.h, shared with the host-only fvad_clips_mel_check; parts: window, matrix and the maxima.
+#include <cmath>
+#include <type_traits>
 #include <vector>
 
-#include "clips_fir.h"
-#include "clips_resample.h"
-#include "clips_strided.h"
+#include "clips_mel.h"
+#include "clips_split.h"
 #include "internal.h"
 
 using namespace fvad;
 
+static_assert(kClipSrcTile == (uint64_t)kClipTile, "clips_rules.h and host_clips_split.cpp count the kernels' tiles");
 static_assert(kStridedSrcTile == (uint64_t)kClipTile && FVAD_CLIP_STEP_MAX == kClipStepMax, "clips_strided.h counts the kernels' tiles");
 static_assert(kFirSrcTile == (uint64_t)kClipTile && FVAD_CLIP_FIR_TAPS_MAX == kClipFirTapsMax, "clips_fir.h counts the kernels' tiles");
 static_assert(kResampledWindow == (uint64_t)kClipTile, "clips_resample.h counts the kernels' window");
+static_assert(kMelSrcTile == (uint64_t)kClipTile && kMelTileFrames == (uint64_t)kClipMelTileFrames, "clips_mel.h counts the kernels' tiles");
+static_assert(FVAD_CLIP_MEL_NFFT_MAX == kClipMelNfftMax && FVAD_CLIP_MEL_BANDS_MAX == kClipMelBandsMax, "fvad.h states the kernels' limits");
 
 namespace {
 
-bool format_ok(int f) { return f == FVAD_CLIP_F32 || f == FVAD_CLIP_PCM16; }
-size_t format_bytes(int f) { return f == FVAD_CLIP_PCM16 ? 2 : 4; }
+// ------------------------------------------------------------------ what every form shares
+
+// one clip as the tables see it: its samples (src_off, or the pieces of a split clip), its slot and its gather tiles
+struct ClipDesc {
+    uint64_t len, n_channels, src_off, out_off, gather_tiles;
+    uint32_t skip;
+    ClipSplit split;
+};
+
+// one job per clip and the two prefix tables the workgroups search; splits only for a split source
+struct ClipTables {
+    std::vector<ClipJob> jobs;
+    std::vector<ClipSplit> splits;
+    std::vector<uint32_t> unit_prefix, tile_prefix;
+    uint64_t units = 0, tiles = 0;
+};
+
+// false: more than 2^31 - 1 RMS units or gather tiles
+template <typename Desc>
+bool build_tables(size_t n_clips, bool split, Desc desc, ClipTables& t)
+{
+    t.jobs.resize(n_clips);
+    t.splits.resize(split ? n_clips : 0);
+    t.unit_prefix.resize(n_clips + 1);
+    t.tile_prefix.resize(n_clips + 1);
+    for (size_t i = 0; i < n_clips; ++i) {
+        const ClipDesc c = desc(i);
+        const uint64_t nt = (c.len + kClipTile - 1) / kClipTile;
+        t.unit_prefix[i] = (uint32_t)t.units;
+        t.tile_prefix[i] = (uint32_t)t.tiles;
+        ClipJob& j = t.jobs[i];
+        j.src_off = c.src_off;
+        j.len = c.len;
+        j.out_off = c.out_off;
+        j.first_unit = (uint32_t)t.units;
+        j.n_tiles = (uint32_t)nt;
+        j.n_channels = (uint32_t)c.n_channels;
+        j.skip = c.skip;
+        if (split) t.splits[i] = c.split;
+        t.units += nt * c.n_channels;
+        t.tiles += c.gather_tiles;
+        if (t.units > 0x7fffffffull || t.tiles > 0x7fffffffull) return false;
+    }
+    t.unit_prefix[n_clips] = (uint32_t)t.units;
+    t.tile_prefix[n_clips] = (uint32_t)t.tiles;
+    return true;
+}
+
+// what a call reports per clip; each may be NULL
+struct ClipReport {
+    int32_t* best_channel;
+    float *best_rms, *runner_up_rms;
+    uint64_t* out_offsets;
+};
+
+// a part of the call's one allocation: uploaded from `up` before the launches and read back into `down` after them (either
+// may be NULL); dev is where run_clips put it
+struct Part {
+    const void* up;
+    void* down;
+    size_t bytes;
+    char* dev;
+};
+
+// the source's share of the arguments; run_clips fills in the tables
+ClipArgs source_args(const void* src, size_t lane_stride, int src_format, int out_format, void* d_out)
+{
+    ClipArgs c{};
+    c.src = src;
+    c.out = d_out;
+    c.lane_stride = lane_stride;
+    c.src_i16 = src_format == FVAD_CLIP_PCM16;
+    c.out_i16 = out_format == FVAD_CLIP_PCM16;
+    return c;
+}
+
+ClipArgs& base(ClipArgs& a) { return a; }
+ClipArgs& base(ClipSplitArgs& a) { return a.c; }
+template <typename B> constexpr bool kSplit = std::is_same<B, ClipSplitArgs>::value;
+
+// The device work of a call over source B: one allocation for the tables, the partials, the infos and the form's extra parts
+// (every part 16-byte aligned), the uploads, RMS and pick, then gather(a, x) -- the form's launches, x its parts in place --,
+// the read-back, the free on every path and the scatter to the caller's arrays.
+template <typename B, typename Gather>
+int run_clips(fvad_ctx* ctx, const std::string& who, B a, const ClipTables& t, const std::vector<Part>& extras, Gather gather, const ClipReport& rep)
+{
+    const size_t n_clips = t.jobs.size();
+    std::vector<ClipInfo> infos(n_clips);
+    enum { kJobs, kSplits, kUnitPrefix, kTilePrefix, kPartials, kInfos, kExtras };
+    std::vector<Part> parts = {{t.jobs.data(), nullptr, n_clips * sizeof(ClipJob), nullptr},
+                               {t.splits.data(), nullptr, t.splits.size() * sizeof(ClipSplit), nullptr},
+                               {t.unit_prefix.data(), nullptr, (n_clips + 1) * 4, nullptr},
+                               {t.tile_prefix.data(), nullptr, (n_clips + 1) * 4, nullptr},
+                               {nullptr, nullptr, t.units * sizeof(double), nullptr},
+                               {nullptr, infos.data(), n_clips * sizeof(ClipInfo), nullptr}};
+    parts.insert(parts.end(), extras.begin(), extras.end());
+    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    size_t bytes = 0;
+    for (const Part& p : parts) bytes += up16(p.bytes);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, who + ": hipMalloc of the clip tables failed"); }
+    bytes = 0;
+    for (Part& p : parts) { p.dev = d + bytes; bytes += up16(p.bytes); }
+    auto run = [&]() -> int {
+        for (const Part& p : parts)
+            if (p.up && p.bytes) FVAD_HIP(ctx, hipMemcpyAsync(p.dev, p.up, p.bytes, hipMemcpyHostToDevice, ctx->stream));
+        ClipArgs& c = base(a);
+        c.jobs = reinterpret_cast<const ClipJob*>(parts[kJobs].dev);
+        c.unit_prefix = reinterpret_cast<const uint32_t*>(parts[kUnitPrefix].dev);
+        c.tile_prefix = reinterpret_cast<const uint32_t*>(parts[kTilePrefix].dev);
+        c.partials = reinterpret_cast<double*>(parts[kPartials].dev);
+        c.infos = reinterpret_cast<ClipInfo*>(parts[kInfos].dev);
+        c.n_clips = (uint32_t)n_clips;
+        c.n_units = (uint32_t)t.units;
+        c.n_tiles = (uint32_t)t.tiles;
+        if constexpr (kSplit<B>) a.splits = reinterpret_cast<const ClipSplit*>(parts[kSplits].dev);
+        time_begin(ctx, kSplit<B> ? "clip_rms_split" : "clip_rms");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_rms(a, ctx->stream));
+        time_end(ctx);
+        time_begin(ctx, "clip_pick");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_pick(c, ctx->stream));
+        time_end(ctx);
+        const int rc = gather(a, parts.data() + kExtras);
+        if (rc != FVAD_OK) return rc;
+        for (const Part& p : parts)
+            if (p.down && p.bytes) FVAD_HIP(ctx, hipMemcpyAsync(p.down, p.dev, p.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return FVAD_OK;
+    };
+    const int rc = run();
+    if (rc != FVAD_OK) (void)hipStreamSynchronize(ctx->stream);
+    hipFree(d);
+    if (rc != FVAD_OK) return rc;
+    for (size_t i = 0; i < n_clips; ++i) {
+        if (rep.best_channel) rep.best_channel[i] = infos[i].best_channel;
+        if (rep.best_rms) rep.best_rms[i] = infos[i].best_rms;
+        if (rep.runner_up_rms) rep.runner_up_rms[i] = infos[i].runner_up_rms;
+        if (rep.out_offsets) rep.out_offsets[i] = infos[i].out_offset;
+    }
+    return FVAD_OK;
+}
+
+// The host-output form of a call whose rules held against the caller's own buffer: a device staging buffer of the plan's
+// `bytes` (hipMalloc returns 256-byte aligned memory), device(d_out), one copy back, then freed.  who names the entry point,
+// family the export's family in what a failed memset or copy says.
+template <typename Device>
+int via_staging(fvad_ctx* ctx, const std::string& who, const std::string& family, void* out, size_t bytes, Device device)
+{
+    hipSetDevice(ctx->device);
+    void* d_out = nullptr;
+    if (hipMalloc(&d_out, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, who + ": hipMalloc of the staging buffer failed"); }
+    // the padding between slots is never written by the kernels: zero it, so that the host gets no stale device memory
+    hipError_t e = hipMemsetAsync(d_out, 0, bytes, ctx->stream);
+    int rc = e == hipSuccess ? device(d_out) : hip_fail(ctx, e, (family + ": hipMemsetAsync").c_str());
+    if (rc == FVAD_OK) {
+        e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = hip_fail(ctx, e, (family + ": copy back").c_str());
+    }
+    hipFree(d_out);
+    return rc;
+}
+
+// ------------------------------------------------------------------ the four sample forms, over either source
+
+// run_clips with the form's part -- the taps as the gather walks them: branch by branch (fir) or [j][o mod up] (resampled) --
+// and its gather
+template <typename B>
+int run_form(fvad_ctx* ctx, const std::string& who, const B& src, const ClipTables& t, const ClipForm& f, const ClipReport& rep)
+{
+    // a step of 1 keeps every sample: the full-rate gather, whose tiles are the strided gather's
+    const uint32_t step = f.strided ? f.strided->step : 1, tile_out = (uint32_t)form_tile_out(f);
+    const std::vector<float> taps = f.rs ? resample_table(Taps{f.rs->taps, f.rs->n_taps}, Ratio{f.rs->up, f.rs->down}) : f.fir ? fir_branches(*f.fir, step) : std::vector<float>();
+    auto gather = [&](const B& a, const Part* x) -> int {
+        const float* d_taps = reinterpret_cast<const float*>(x[0].dev);
+        if (f.rs) {
+            time_begin(ctx, kSplit<B> ? "clip_gather_resampled_split" : "clip_gather_resampled");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_resampled(ClipResampleArgs<B>{a, d_taps, f.rs->up, f.rs->down, tile_out, f.rs->n_taps}, ctx->stream));
+        } else if (f.fir) {
+            time_begin(ctx, kSplit<B> ? "clip_gather_fir_split" : "clip_gather_fir");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_fir(ClipFirArgs<B>{a, d_taps, step, tile_out, f.fir->n_taps, 0}, ctx->stream));
+        } else if (step == 1) {
+            time_begin(ctx, kSplit<B> ? "clip_gather_split" : "clip_gather");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather(a, ctx->stream));
+        } else {
+            time_begin(ctx, kSplit<B> ? "clip_gather_strided_split" : "clip_gather_strided");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_strided(ClipStridedArgs<B>{a, step, tile_out}, ctx->stream));
+        }
+        time_end(ctx);
+        return FVAD_OK;
+    };
+    return run_clips(ctx, who, src, t, {Part{taps.data(), nullptr, taps.size() * sizeof(float), nullptr}}, gather, rep);
+}
+
+// where a call's samples go: the caller's buffer (device or host memory), its capacity in samples of `format`, and the report
+struct ClipOut {
+    int format;
+    void* p;
+    size_t capacity;
+    ClipReport rep;
+};
+
+// ------------------------------------------------------------------ fvad_clips_export*: a clip's channel is one run
+
+struct Lanes {
+    const void* d_src;
+    int format;
+    size_t n_lanes, lane_stride, n_samples;
+    const uint64_t* clips;
+    size_t n_clips;
+};
 
 struct ClipRow { uint64_t first_lane, n_channels, sample_from, sample_to; };
 ClipRow row(const uint64_t* clips, size_t i)
@@ -30,85 +251,232 @@ ClipRow row(const uint64_t* clips, size_t i)
     const uint64_t* r = clips + i * FVAD_CLIP_FIELDS;
     return {r[0], r[1], r[2], r[3]};
 }
-
-// the argument rules of fvad_clips_plan, shared with the export: every slot starts on a 16-byte boundary
-int plan_clips(const uint64_t* clips, size_t n, int out_format, uint64_t* offsets, uint64_t* total)
+// a row's length, 0 for a row that breaks its own rules
+uint64_t row_len(const uint64_t* clips, size_t i)
 {
-    const uint64_t per16 = 16 / format_bytes(out_format);
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const ClipRow c = row(clips, i);
-        if (c.sample_to <= c.sample_from || c.n_channels == 0) return FVAD_ERR_INVALID_ARGUMENT;
-        if (offsets) offsets[i] = at;
-        const uint64_t len = c.sample_to - c.sample_from;
-        if (len > UINT64_MAX - at - per16) return FVAD_ERR_INVALID_ARGUMENT; // (the total would not fit 64 bits)
-        at += (len + per16 - 1) / per16 * per16;
-    }
-    if (total) *total = at;
-    return FVAD_OK;
+    const ClipRow c = row(clips, i);
+    return c.sample_to <= c.sample_from || c.n_channels == 0 ? 0 : c.sample_to - c.sample_from;
 }
 
-// Every rule of fvad_clips_export(_device), in one order for both forms: arguments, then every clip's own rules, then its range
-// and lanes, then the capacity.  Fills offsets and total.  strided (may be NULL): the strided exports' rules directly after the
-// clips' own, and their slots in place of the full-rate ones.  fir (may be NULL, with strided only): the tap rules after those.
-// rs (may be NULL, without strided): the resampled exports' ratio and tap rules in the same place, and their slots.
-int check_export(const fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                 const uint64_t* clips, size_t n_clips, int out_format, const void* out, size_t out_capacity, bool device_out,
-                 std::vector<uint64_t>& offsets, uint64_t& total, const Strided* strided, const Fir* fir, const Resampled* rs)
+// Every rule of fvad_clips_export*(_device), in one order for both outputs: arguments, then every clip's own rules and the
+// form's (clip_slots of clips_rules.h), then its range and lanes, then the capacity.  Fills offsets and total.
+int check_export(const fvad_ctx* ctx, const Lanes& s, const ClipOut& o, bool device_out, const ClipForm& form, std::vector<uint64_t>& offsets, uint64_t& total)
 {
-    if (!d_src || !clips || !out) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: NULL argument");
-    if (!format_ok(src_format) || !format_ok(out_format)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: unknown sample format");
-    if (device_out && (uintptr_t)out % 16 != 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: the output must be 16-byte aligned");
-    if ((uintptr_t)d_src % format_bytes(src_format) != 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: the source is not aligned to its samples");
-    if (n_lanes > 1 && lane_stride < n_samples) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: lane_stride < n_samples");
-    offsets.resize(n_clips);
-    if (plan_clips(clips, n_clips, out_format, offsets.data(), &total) != FVAD_OK)
-        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: a clip with sample_to <= sample_from or no channels");
-    if (strided) {
-        if (!strided_step_ok(strided->step)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_strided: a step of 0 or above FVAD_CLIP_STEP_MAX");
-        const char* why = "";
-        total = 0;
-        for (size_t i = 0; i < n_clips; ++i) {
-            const ClipRow c = row(clips, i);
-            uint64_t out_len;
-            offsets[i] = total;
-            if (!strided_slot(*strided, i, c.sample_to - c.sample_from, 16 / format_bytes(out_format), &total, &out_len, &why))
-                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_strided: ") + why);
-        }
-        if (fir && !fir_taps_ok(*fir, &why)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_fir: ") + why);
-    }
-    if (rs) {
-        const char* why = "";
-        if (!resampled_ok(*rs, &why)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_resampled: ") + why);
-        total = 0;
-        for (size_t i = 0; i < n_clips; ++i) {
-            const ClipRow c = row(clips, i);
-            uint64_t out_len;
-            offsets[i] = total;
-            if ((u128)(c.sample_to - c.sample_from) * rs->up >= (u128)kResampleFramesUp)
-                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_resampled: a clip of 2^62 / up samples or more");
-            if (!resampled_slot(Ratio{rs->up, rs->down}, c.sample_to - c.sample_from, 16 / format_bytes(out_format), &total, &out_len, &why))
-                return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string("fvad_clips_export_resampled: ") + why);
-        }
-    }
-    for (size_t i = 0; i < n_clips; ++i) {
-        const ClipRow c = row(clips, i);
-        if (c.sample_to > n_samples) return set_err(ctx, FVAD_ERR_OUT_OF_RANGE, "fvad_clips_export: a clip ends past n_samples");
-        if (c.first_lane >= n_lanes || c.n_channels > n_lanes - c.first_lane)
+    if (!s.d_src || !s.clips || !o.p) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: NULL argument");
+    if (!format_ok(s.format) || !format_ok(o.format)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: unknown sample format");
+    if (device_out && (uintptr_t)o.p % 16 != 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: the output must be 16-byte aligned");
+    if ((uintptr_t)s.d_src % format_bytes(s.format) != 0) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: the source is not aligned to its samples");
+    if (s.n_lanes > 1 && s.lane_stride < s.n_samples) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: lane_stride < n_samples");
+    offsets.resize(s.n_clips);
+    const char *family = "", *why = "";
+    if (!clip_slots(form, s.n_clips, [&](size_t i) { return row_len(s.clips, i); }, "", 16 / format_bytes(o.format), offsets.data(), &total, &family, &why))
+        return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, *family ? std::string("fvad_clips_export_") + family + ": " + why
+                                                               : std::string("fvad_clips_export: a clip with sample_to <= sample_from or no channels"));
+    for (size_t i = 0; i < s.n_clips; ++i) {
+        const ClipRow c = row(s.clips, i);
+        if (c.sample_to > s.n_samples) return set_err(ctx, FVAD_ERR_OUT_OF_RANGE, "fvad_clips_export: a clip ends past n_samples");
+        if (c.first_lane >= s.n_lanes || c.n_channels > s.n_lanes - c.first_lane)
             return set_err(ctx, FVAD_ERR_OUT_OF_RANGE, "fvad_clips_export: a clip's lanes end past n_lanes");
     }
-    if (total > out_capacity) return set_err(ctx, FVAD_ERR_BUFFER_TOO_SMALL, "fvad_clips_export: out_capacity is below fvad_clips_plan's total");
+    if (total > o.capacity) return set_err(ctx, FVAD_ERR_BUFFER_TOO_SMALL, "fvad_clips_export: out_capacity is below fvad_clips_plan's total");
     return FVAD_OK;
 }
 
-int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                  const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
-                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs = nullptr);
-int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
-                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs = nullptr);
+int export_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const ClipForm& form)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets;
+    uint64_t total = 0;
+    const int bad = check_export(ctx, s, o, true, form, offsets, total);
+    if (bad != FVAD_OK) return bad;
+    ClipTables t;
+    const auto desc = [&](size_t i) {
+        const ClipRow c = row(s.clips, i);
+        const uint64_t len = c.sample_to - c.sample_from;
+        return ClipDesc{len, c.n_channels, c.first_lane * (uint64_t)s.lane_stride + c.sample_from, offsets[i], form_gather_tiles(form, i, len), form_skip(form, i), {}};
+    };
+    if (!build_tables(s.n_clips, false, desc, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: more than 2^31 tiles in one call: export in batches");
+    hipSetDevice(ctx->device);
+    return run_form(ctx, "fvad_clips_export", source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, form, o.rep);
+}
+
+int export_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const ClipForm& form)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets;
+    uint64_t total = 0;
+    const int bad = check_export(ctx, s, o, false, form, offsets, total);
+    if (bad != FVAD_OK) return bad;
+    return via_staging(ctx, "fvad_clips_export", "fvad_clips_export", o.p, (size_t)total * format_bytes(o.format),
+                       [&](void* d_out) { return export_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, form); });
+}
+
+// ------------------------------------------------------------------ fvad_clips_export_split*: a head piece in A, a body piece in B
+
+struct SplitLanes {
+    const void* d_a;
+    size_t a_lanes, a_stride, a_samples;
+    const void* d_b;
+    size_t b_lanes, b_stride, b_samples;
+    int format;
+    const uint64_t* clips;
+    size_t n_clips;
+};
+
+int check_split(const fvad_ctx* ctx, const char* who, const SplitLanes& s, const ClipOut& o, bool device_out, const ClipForm& form,
+                std::vector<uint64_t>& offsets, uint64_t& total)
+{
+    offsets.resize(s.n_clips);
+    const char* why = "";
+    const int rc = clips_split_check(s.d_a, s.a_lanes, s.a_stride, s.a_samples, s.d_b, s.b_lanes, s.b_stride, s.b_samples, s.format, s.clips, s.n_clips,
+                                     o.format, o.p, o.capacity, device_out, offsets.data(), &total, &why, form);
+    return rc == FVAD_OK ? rc : set_err(ctx, rc, std::string(who) + ": " + why);
+}
+
+int export_split_device(fvad_ctx* ctx, const char* who, const SplitLanes& s, const ClipOut& o, const ClipForm& form)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets;
+    uint64_t total = 0;
+    const int bad = check_split(ctx, who, s, o, true, form, offsets, total);
+    if (bad != FVAD_OK) return bad;
+    ClipTables t;
+    const auto desc = [&](size_t i) {
+        const SplitRow c = split_row(s.clips, i);
+        const uint64_t len = c.a_len + c.b_len;
+        // (a piece of no samples is never addressed)
+        const ClipSplit sp{c.a_len ? c.a_lane * (uint64_t)s.a_stride + c.a_from : 0, c.a_len, c.b_len ? c.b_lane * (uint64_t)s.b_stride + c.b_from : 0, 0};
+        return ClipDesc{len, c.n_channels, 0, offsets[i], form_gather_tiles(form, i, len), form_skip(form, i), sp};
+    };
+    if (!build_tables(s.n_clips, true, desc, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string(who) + ": more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
+    hipSetDevice(ctx->device);
+    const ClipSplitArgs src{source_args(s.d_a, s.a_stride, s.format, o.format, o.p), s.d_b, s.b_stride, nullptr};
+    return run_form(ctx, who, src, t, form, o.rep);
+}
+
+int export_split_host(fvad_ctx* ctx, const char* who, const SplitLanes& s, const ClipOut& o, const ClipForm& form)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets;
+    uint64_t total = 0;
+    const int bad = check_split(ctx, who, s, o, false, form, offsets, total);
+    if (bad != FVAD_OK) return bad;
+    return via_staging(ctx, who, "fvad_clips_export_split", o.p, (size_t)total * format_bytes(o.format),
+                       [&](void* d_out) { return export_split_device(ctx, who, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, form); });
+}
+
+// ------------------------------------------------------------------ fvad_clips_export_mel*: features in place of samples
+
+struct MelCall {
+    Mel m;
+    const float* window;
+    const float* matrix;
+    float floor;
+    const float* norm;
+    uint64_t* n_frames; // what the call reports per clip beside ClipReport; each may be NULL
+    float* feat_max;
+};
+
+int mel_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets(s.n_clips), frames(s.n_clips);
+    uint64_t total = 0;
+    const char* why = "";
+    const int bad = mel_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 1, mc.m, mc.window,
+                              mc.matrix, mc.floor, mc.norm, frames.data(), offsets.data(), &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_mel: ") + why);
+    const Mel& m = mc.m;
+    const uint32_t tf = clip_mel_tile_frames(m.n_fft, m.hop), n_bins = m.n_fft / 2 + 1;
+    ClipTables t;
+    const auto desc = [&](size_t i) {
+        const ClipRow c = row(s.clips, i);
+        return ClipDesc{c.sample_to - c.sample_from, c.n_channels, c.first_lane * (uint64_t)s.lane_stride + c.sample_from, offsets[i], (frames[i] + tf - 1) / tf, m.skips ? m.skips[i] : 0, {}};
+    };
+    if (!build_tables(s.n_clips, false, desc, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_mel: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
+    // the matrix as the kernels read it: [bin][band]
+    std::vector<float> matrix_t((size_t)n_bins * m.n_mels);
+    for (uint32_t b = 0; b < m.n_mels; ++b)
+        for (uint32_t k = 0; k < n_bins; ++k) matrix_t[(size_t)k * m.n_mels + b] = mc.matrix[(size_t)b * n_bins + k];
+
+    hipSetDevice(ctx->device);
+    ClipMelArgs a{};
+    // the transform's tables (twiddles, un-mixing factors, radices), cached per context and size
+    { const int rc = get_vad_plan(ctx, m.n_fft, &a.pl, true); if (rc != FVAD_OK) return rc; }
+    std::vector<float> fmax(s.n_clips);
+    enum { kWindow, kMatrix, kTileMax, kFeatMax };
+    const std::vector<Part> parts = {{mc.window, nullptr, m.n_fft * sizeof(float), nullptr},
+                                     {matrix_t.data(), nullptr, matrix_t.size() * sizeof(float), nullptr},
+                                     {nullptr, nullptr, t.tiles * sizeof(float), nullptr},
+                                     {nullptr, fmax.data(), s.n_clips * sizeof(float), nullptr}};
+    auto features = [&](const ClipArgs& c, const Part* x) -> int {
+        a.c = c;
+        a.window = reinterpret_cast<const float*>(x[kWindow].dev);
+        a.matrix_t = reinterpret_cast<const float*>(x[kMatrix].dev);
+        a.tile_max = reinterpret_cast<float*>(x[kTileMax].dev);
+        a.feat_max = reinterpret_cast<float*>(x[kFeatMax].dev);
+        a.step = m.step;
+        a.hop = m.hop;
+        a.n_mels = m.n_mels;
+        a.tile_frames = tf;
+        a.floor = mc.floor;
+        a.log_floor = (float)std::log10((double)mc.floor);
+        if (mc.norm) { a.norm_range = mc.norm[0]; a.norm_offset = mc.norm[1]; a.norm_scale = mc.norm[2]; }
+        a.fft400 = m.n_fft == 400 && !ctx->tune.clip_mel_generic;
+        time_begin(ctx, a.fft400 ? "clip_mel400" : "clip_mel");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel(a, ctx->stream));
+        time_end(ctx);
+        time_begin(ctx, "clip_mel_max");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel_max(a, ctx->stream));
+        time_end(ctx);
+        if (mc.norm) {
+            time_begin(ctx, "clip_mel_norm");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel_norm(a, ctx->stream));
+            time_end(ctx);
+        }
+        return FVAD_OK;
+    };
+    const int rc = run_clips(ctx, "fvad_clips_export_mel", source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
+    if (rc != FVAD_OK) return rc;
+    for (size_t i = 0; i < s.n_clips; ++i) {
+        if (mc.n_frames) mc.n_frames[i] = frames[i];
+        if (mc.feat_max) mc.feat_max[i] = fmax[i];
+    }
+    return FVAD_OK;
+}
+
+int mel_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    // every rule against the caller's own buffer first
+    uint64_t total = 0;
+    const char* why = "";
+    const int bad = mel_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 0, mc.m, mc.window,
+                              mc.matrix, mc.floor, mc.norm, nullptr, nullptr, &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_mel: ") + why);
+    return via_staging(ctx, "fvad_clips_export_mel", "fvad_clips_export_mel", o.p, (size_t)total * sizeof(float),
+                       [&](void* d_out) { return mel_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, mc); });
+}
+
+// the argument rules of fvad_clips_plan: the full-rate slots
+int plan_clips(const uint64_t* clips, size_t n, int out_format, uint64_t* offsets, uint64_t* total)
+{
+    const char *family, *why;
+    uint64_t at = 0;
+    if (!clip_slots(ClipForm{}, n, [&](size_t i) { return row_len(clips, i); }, "", 16 / format_bytes(out_format), offsets, &at, &family, &why)) return FVAD_ERR_INVALID_ARGUMENT;
+    *total = at;
+    return FVAD_OK;
+}
 
 } // namespace
+
+// ------------------------------------------------------------------ the entry points
 
 extern "C" {
 
@@ -146,16 +514,18 @@ int fvad_clips_export_device(fvad_ctx* ctx, const void* d_src, int src_format, s
                              size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
                              uint64_t* out_offsets)
 {
-    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                         best_channel, best_rms, runner_up_rms, out_offsets, nullptr, nullptr);
+    return export_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                         ClipForm{});
 }
 
 int fvad_clips_export(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
                       const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity,
                       int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
 {
-    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
-                       best_rms, runner_up_rms, out_offsets, nullptr, nullptr);
+    return export_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                       ClipForm{});
 }
 
 int fvad_clips_export_strided_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride,
@@ -164,8 +534,9 @@ int fvad_clips_export_strided_device(fvad_ctx* ctx, const void* d_src, int src_f
                                      uint64_t* out_offsets, uint32_t step, const uint32_t* skips)
 {
     const Strided s{step, skips};
-    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                         best_channel, best_rms, runner_up_rms, out_offsets, &s, nullptr);
+    return export_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                         ClipForm{&s, nullptr, nullptr});
 }
 
 int fvad_clips_export_strided(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -174,8 +545,9 @@ int fvad_clips_export_strided(fvad_ctx* ctx, const void* d_src, int src_format, 
                               const uint32_t* skips)
 {
     const Strided s{step, skips};
-    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
-                       best_rms, runner_up_rms, out_offsets, &s, nullptr);
+    return export_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                       ClipForm{&s, nullptr, nullptr});
 }
 
 int fvad_clips_export_fir_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -185,8 +557,9 @@ int fvad_clips_export_fir_device(fvad_ctx* ctx, const void* d_src, int src_forma
 {
     const Strided s{step, skips};
     const Fir f{taps, n_taps};
-    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                         best_channel, best_rms, runner_up_rms, out_offsets, &s, &f);
+    return export_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                         ClipForm{&s, &f, nullptr});
 }
 
 int fvad_clips_export_fir(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -196,8 +569,9 @@ int fvad_clips_export_fir(fvad_ctx* ctx, const void* d_src, int src_format, size
 {
     const Strided s{step, skips};
     const Fir f{taps, n_taps};
-    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
-                       best_rms, runner_up_rms, out_offsets, &s, &f);
+    return export_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                       ClipForm{&s, &f, nullptr});
 }
 
 int fvad_clips_export_resampled_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride,
@@ -206,8 +580,9 @@ int fvad_clips_export_resampled_device(fvad_ctx* ctx, const void* d_src, int src
                                        uint64_t* out_offsets, uint32_t up, uint32_t down, const float* taps, uint32_t n_taps)
 {
     const Resampled r{up, down, taps, n_taps};
-    return export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                         best_channel, best_rms, runner_up_rms, out_offsets, nullptr, nullptr, &r);
+    return export_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                         ClipForm{nullptr, nullptr, &r});
 }
 
 int fvad_clips_export_resampled(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -216,154 +591,125 @@ int fvad_clips_export_resampled(fvad_ctx* ctx, const void* d_src, int src_format
                                 uint32_t down, const float* taps, uint32_t n_taps)
 {
     const Resampled r{up, down, taps, n_taps};
-    return export_host(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, best_channel,
-                       best_rms, runner_up_rms, out_offsets, nullptr, nullptr, &r);
+    return export_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                       ClipForm{nullptr, nullptr, &r});
+}
+
+int fvad_clips_export_split_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                   size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                   size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
+                                   float* best_rms, float* runner_up_rms, uint64_t* out_offsets)
+{
+    return export_split_device(ctx, "fvad_clips_export_split", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                               ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                               ClipForm{});
+}
+
+int fvad_clips_export_split(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                            size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                            int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms,
+                            float* runner_up_rms, uint64_t* out_offsets)
+{
+    return export_split_host(ctx, "fvad_clips_export_split", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                             ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                             ClipForm{});
+}
+
+int fvad_clips_export_split_strided_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                           const void* d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                           const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity,
+                                           int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets,
+                                           uint32_t step, const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_split_device(ctx, "fvad_clips_export_split_strided", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                               ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                               ClipForm{&s, nullptr, nullptr});
+}
+
+int fvad_clips_export_split_strided(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                    size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                    size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                                    float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips)
+{
+    const Strided s{step, skips};
+    return export_split_host(ctx, "fvad_clips_export_split_strided", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                             ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                             ClipForm{&s, nullptr, nullptr});
+}
+
+int fvad_clips_export_split_fir_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                       size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                       size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
+                                       float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips,
+                                       const float* taps, uint32_t n_taps)
+{
+    const Strided s{step, skips};
+    const Fir f{taps, n_taps};
+    return export_split_device(ctx, "fvad_clips_export_split_fir", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                               ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                               ClipForm{&s, &f, nullptr});
+}
+
+int fvad_clips_export_split_fir(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                                int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms,
+                                float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips, const float* taps,
+                                uint32_t n_taps)
+{
+    const Strided s{step, skips};
+    const Fir f{taps, n_taps};
+    return export_split_host(ctx, "fvad_clips_export_split_fir", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                             ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                             ClipForm{&s, &f, nullptr});
+}
+
+int fvad_clips_export_split_resampled_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                             const void* d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                             const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity,
+                                             int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets,
+                                             uint32_t up, uint32_t down, const float* taps, uint32_t n_taps)
+{
+    const Resampled r{up, down, taps, n_taps};
+    return export_split_device(ctx, "fvad_clips_export_split_resampled", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                               ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                               ClipForm{nullptr, nullptr, &r});
+}
+
+int fvad_clips_export_split_resampled(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                      size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips,
+                                      size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                                      float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t up, uint32_t down,
+                                      const float* taps, uint32_t n_taps)
+{
+    const Resampled r{up, down, taps, n_taps};
+    return export_split_host(ctx, "fvad_clips_export_split_resampled", SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                             ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                             ClipForm{nullptr, nullptr, &r});
+}
+
+int fvad_clips_export_mel_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                 const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity,
+                                 int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step,
+                                 const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels,
+                                 const float* matrix, float floor, const float* norm, uint64_t* n_frames, float* feat_max)
+{
+    return mel_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                      ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                      MelCall{Mel{step, skips, n_fft, hop, n_mels}, window, matrix, floor, norm, n_frames, feat_max});
+}
+
+int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                          const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                          float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips,
+                          uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix, float floor,
+                          const float* norm, uint64_t* n_frames, float* feat_max)
+{
+    return mel_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                    ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                    MelCall{Mel{step, skips, n_fft, hop, n_mels}, window, matrix, floor, norm, n_frames, feat_max});
 }
 
 } // extern "C"
 
-namespace {
-
-// fvad_clips_export_device (strided NULL), fvad_clips_export_strided_device, fvad_clips_export_fir_device (fir not NULL) and
-// fvad_clips_export_resampled_device (rs not NULL, strided NULL)
-int export_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                  const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity, int32_t* best_channel,
-                  float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs)
-{
-    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (n_clips == 0) return FVAD_OK;
-    std::vector<uint64_t> offsets;
-    uint64_t total = 0;
-    const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out, out_capacity,
-                                 true, offsets, total, strided, fir, rs);
-    if (bad != FVAD_OK) return bad;
-    // a step of 1 keeps every sample: the full-rate gather, whose tiles are the strided gather's
-    const uint32_t step = strided ? strided->step : 1;
-    const uint64_t tile_out = rs ? resampled_tile_out(Ratio{rs->up, rs->down}, rs->n_taps) : fir ? clip_fir_tile_out(step, fir->n_taps) : clip_tile_out(step);
-    // the tables: one job per clip and the two prefix tables the workgroups search
-    std::vector<ClipJob> jobs(n_clips);
-    std::vector<uint32_t> unit_prefix(n_clips + 1), tile_prefix(n_clips + 1);
-    uint64_t units = 0, tiles = 0;
-    for (size_t i = 0; i < n_clips; ++i) {
-        const ClipRow c = row(clips, i);
-        const uint64_t len = c.sample_to - c.sample_from;
-        const uint64_t nt = (len + kClipTile - 1) / kClipTile;
-        const uint32_t skip = strided && strided->skips ? strided->skips[i] : 0;
-        const uint64_t out_len = rs ? resample_out_frames(len, Ratio{rs->up, rs->down}) : (len - skip + step - 1) / step;
-        unit_prefix[i] = (uint32_t)units;
-        tile_prefix[i] = (uint32_t)tiles;
-        ClipJob& j = jobs[i];
-        j.src_off = c.first_lane * (uint64_t)lane_stride + c.sample_from;
-        j.len = len;
-        j.out_off = offsets[i];
-        j.first_unit = (uint32_t)units;
-        j.n_tiles = (uint32_t)nt;
-        j.n_channels = (uint32_t)c.n_channels;
-        j.skip = skip;
-        units += nt * c.n_channels;
-        tiles += (out_len + tile_out - 1) / tile_out; // (step 1: nt)
-        if (units > 0x7fffffffull || tiles > 0x7fffffffull) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export: more than 2^31 tiles in one call: export in batches");
-    }
-    unit_prefix[n_clips] = (uint32_t)units;
-    tile_prefix[n_clips] = (uint32_t)tiles;
-
-    hipSetDevice(ctx->device);
-    // one allocation for the call's tables, every part 16-byte aligned
-    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
-    const size_t o_jobs = 0, o_up = o_jobs + up16(n_clips * sizeof(ClipJob)), o_tp = o_up + up16((n_clips + 1) * 4),
-                 o_part = o_tp + up16((n_clips + 1) * 4), o_info = o_part + up16(units * sizeof(double)),
-                 o_taps = o_info + up16(n_clips * sizeof(ClipInfo)), bytes = o_taps + up16(rs ? (size_t)resample_phase_taps(rs->up, rs->n_taps) * rs->up * sizeof(float) : fir ? fir->n_taps * sizeof(float) : 0);
-    // the taps as the gather walks them: branch by branch (fir) or [j][o mod up] (resampled)
-    const std::vector<float> taps = rs ? resample_table(Taps{rs->taps, rs->n_taps}, Ratio{rs->up, rs->down}) : fir ? fir_branches(*fir, step) : std::vector<float>();
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export: hipMalloc of the clip tables failed"); }
-    std::vector<ClipInfo> infos(n_clips);
-    auto run = [&]() -> int {
-        FVAD_HIP(ctx, hipMemcpyAsync(d + o_jobs, jobs.data(), n_clips * sizeof(ClipJob), hipMemcpyHostToDevice, ctx->stream));
-        FVAD_HIP(ctx, hipMemcpyAsync(d + o_up, unit_prefix.data(), (n_clips + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        FVAD_HIP(ctx, hipMemcpyAsync(d + o_tp, tile_prefix.data(), (n_clips + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (fir || rs) FVAD_HIP(ctx, hipMemcpyAsync(d + o_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        ClipArgs a{};
-        a.src = d_src;
-        a.out = d_out;
-        a.lane_stride = lane_stride;
-        a.jobs = reinterpret_cast<const ClipJob*>(d + o_jobs);
-        a.unit_prefix = reinterpret_cast<const uint32_t*>(d + o_up);
-        a.tile_prefix = reinterpret_cast<const uint32_t*>(d + o_tp);
-        a.partials = reinterpret_cast<double*>(d + o_part);
-        a.infos = reinterpret_cast<ClipInfo*>(d + o_info);
-        a.n_clips = (uint32_t)n_clips;
-        a.n_units = (uint32_t)units;
-        a.n_tiles = (uint32_t)tiles;
-        a.src_i16 = src_format == FVAD_CLIP_PCM16;
-        a.out_i16 = out_format == FVAD_CLIP_PCM16;
-        time_begin(ctx, "clip_rms");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_rms(a, ctx->stream));
-        time_end(ctx);
-        time_begin(ctx, "clip_pick");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_pick(a, ctx->stream));
-        time_end(ctx);
-        if (rs) {
-            time_begin(ctx, "clip_gather_resampled");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_resampled(ClipResampleArgs{a, reinterpret_cast<const float*>(d + o_taps), rs->up, rs->down, (uint32_t)tile_out, rs->n_taps}, ctx->stream));
-        } else if (fir) {
-            time_begin(ctx, "clip_gather_fir");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_fir(ClipFirArgs{a, reinterpret_cast<const float*>(d + o_taps), step, (uint32_t)tile_out, fir->n_taps, 0}, ctx->stream));
-        } else if (step == 1) {
-            time_begin(ctx, "clip_gather");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather(a, ctx->stream));
-        } else {
-            time_begin(ctx, "clip_gather_strided");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_gather_strided(ClipStridedArgs{a, step, (uint32_t)tile_out}, ctx->stream));
-        }
-        time_end(ctx);
-        FVAD_HIP(ctx, hipMemcpyAsync(infos.data(), d + o_info, n_clips * sizeof(ClipInfo), hipMemcpyDeviceToHost, ctx->stream));
-        FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FVAD_OK;
-    };
-    const int rc = run();
-    if (rc != FVAD_OK) (void)hipStreamSynchronize(ctx->stream);
-    hipFree(d);
-    if (rc != FVAD_OK) return rc;
-    for (size_t i = 0; i < n_clips; ++i) {
-        if (best_channel) best_channel[i] = infos[i].best_channel;
-        if (best_rms) best_rms[i] = infos[i].best_rms;
-        if (runner_up_rms) runner_up_rms[i] = infos[i].runner_up_rms;
-        if (out_offsets) out_offsets[i] = infos[i].out_offset;
-    }
-    return FVAD_OK;
-}
-
-// fvad_clips_export (strided NULL), fvad_clips_export_strided, fvad_clips_export_fir (fir not NULL) and
-// fvad_clips_export_resampled (rs not NULL, strided NULL)
-int export_host(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
-                const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
-                float* best_rms, float* runner_up_rms, uint64_t* out_offsets, const Strided* strided, const Fir* fir, const Resampled* rs)
-{
-    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (n_clips == 0) return FVAD_OK;
-    std::vector<uint64_t> offsets;
-    uint64_t total = 0;
-    const int bad = check_export(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity,
-                                 false, offsets, total, strided, fir, rs);
-    if (bad != FVAD_OK) return bad;
-    // a device staging buffer of the plan's size, one copy back, then freed (hipMalloc returns 256-byte aligned memory)
-    hipSetDevice(ctx->device);
-    const size_t bytes = (size_t)total * format_bytes(out_format);
-    void* d_out = nullptr;
-    if (hipMalloc(&d_out, bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, "fvad_clips_export: hipMalloc of the staging buffer failed"); }
-    // the padding between slots is never written by the kernels: zero it, so that the host gets no stale device memory
-    hipError_t e = hipMemsetAsync(d_out, 0, bytes, ctx->stream);
-    int rc = e == hipSuccess ? export_device(ctx, d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, d_out,
-                                             (size_t)total, best_channel, best_rms, runner_up_rms, out_offsets, strided, fir, rs)
-                             : hip_fail(ctx, e, "fvad_clips_export: hipMemsetAsync");
-    if (rc == FVAD_OK) {
-        e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "fvad_clips_export: copy back");
-    }
-    hipFree(d_out);
-    return rc;
-}
-
-} // namespace

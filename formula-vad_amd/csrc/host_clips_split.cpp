@@ -1,15 +1,9 @@
 // host_clips_split.cpp -- fvad_clips_split_check: every argument rule of fvad_clips_export_split(_device), in the one order both
 // forms report them in, without a device (plain C++: tests/sanitize/clips_split_san.cpp builds this file alone).  Pointers are
 // addresses here; nothing is read through d_a, d_b or out.
-#include "clips_fir.h"
-#include "clips_resample.h"
 #include "clips_split.h"
-#include "clips_strided.h"
 
 namespace {
-
-bool format_ok(int f) { return f == FVAD_CLIP_F32 || f == FVAD_CLIP_PCM16; }
-uint64_t format_bytes(int f) { return f == FVAD_CLIP_PCM16 ? 2 : 4; }
 
 // the bytes [lo, hi) a buffer of n_lanes lanes covers, saturating at the top of the address space
 struct Range { uint64_t lo, hi; };
@@ -39,7 +33,7 @@ namespace fvad {
 int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
                       size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
                       const void* out, size_t out_capacity, int device_out, uint64_t* offsets, uint64_t* total, const char** why,
-                      const Strided* strided, const Fir* fir, const Resampled* rs)
+                      const ClipForm& form)
 {
     const char* dummy;
     if (!why) why = &dummy;
@@ -59,41 +53,15 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
     if (device_out && (uintptr_t)out % 16 != 0) { *why = "the output must be 16-byte aligned"; return FVAD_ERR_INVALID_ARGUMENT; }
     // strides
     if ((a_lanes > 1 && a_stride < a_samples) || (b_lanes > 1 && b_stride < b_samples)) { *why = "a stride below its sample count"; return FVAD_ERR_INVALID_ARGUMENT; }
-    // every row's own rules, and the slots fvad_clips_plan gives clips of these lengths
-    const uint64_t per16 = 16 / ob;
-    uint64_t at = 0;
-    for (size_t i = 0; i < n_clips; ++i) {
+    // every row's own rules and the slots fvad_clips_plan gives clips of these lengths, then the form's rules and slots
+    const auto len = [&](size_t i) {
         const SplitRow r = split_row(clips, i);
-        uint64_t len;
-        if (r.n_channels == 0 || __builtin_add_overflow(r.a_len, r.b_len, &len) || len == 0) { *why = "a clip with both lengths 0 or no channels"; return FVAD_ERR_INVALID_ARGUMENT; }
-        if (offsets) offsets[i] = at;
-        if (at > UINT64_MAX - per16 || len > UINT64_MAX - per16 - at) { *why = "the clips' total does not fit 64 bits"; return FVAD_ERR_INVALID_ARGUMENT; }
-        at += (len + per16 - 1) / per16 * per16;
-    }
-    if (strided) { // a strided export: its own rules, and its slots in place of the full-rate ones
-        if (!strided_step_ok(strided->step)) { *why = "a step of 0 or above FVAD_CLIP_STEP_MAX"; return FVAD_ERR_INVALID_ARGUMENT; }
-        at = 0;
-        for (size_t i = 0; i < n_clips; ++i) {
-            const SplitRow r = split_row(clips, i);
-            const uint64_t slot = at;
-            uint64_t out_len;
-            if (!strided_slot(*strided, i, r.a_len + r.b_len, per16, &at, &out_len, why)) return FVAD_ERR_INVALID_ARGUMENT;
-            if (offsets) offsets[i] = slot;
-        }
-        if (fir && !fir_taps_ok(*fir, why)) return FVAD_ERR_INVALID_ARGUMENT;
-    }
-    if (rs) { // a resampled export: its ratio and taps, and its slots in place of the full-rate ones
-        if (!resampled_ok(*rs, why)) return FVAD_ERR_INVALID_ARGUMENT;
-        at = 0;
-        for (size_t i = 0; i < n_clips; ++i) {
-            const SplitRow r = split_row(clips, i);
-            const uint64_t slot = at;
-            uint64_t out_len;
-            if ((u128)(r.a_len + r.b_len) * rs->up >= (u128)kResampleFramesUp) { *why = "a clip of 2^62 / up samples or more"; return FVAD_ERR_INVALID_ARGUMENT; }
-            if (!resampled_slot(Ratio{rs->up, rs->down}, r.a_len + r.b_len, per16, &at, &out_len, why)) return FVAD_ERR_INVALID_ARGUMENT;
-            if (offsets) offsets[i] = slot;
-        }
-    }
+        uint64_t n;
+        return r.n_channels == 0 || __builtin_add_overflow(r.a_len, r.b_len, &n) ? 0 : n;
+    };
+    const char* family;
+    uint64_t at = 0;
+    if (!clip_slots(form, n_clips, len, "a clip with both lengths 0 or no channels", 16 / ob, offsets, &at, &family, why)) return FVAD_ERR_INVALID_ARGUMENT;
     if (total) *total = at;
     // ranges and lanes
     for (size_t i = 0; i < n_clips; ++i) {
@@ -115,25 +83,15 @@ int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a
     uint64_t units = 0, gather = 0;
     for (size_t i = 0; i < n_clips; ++i) {
         const SplitRow r = split_row(clips, i);
-        const uint64_t len = r.a_len + r.b_len, nt = len / kSplitTile + (len % kSplitTile != 0);
+        const uint64_t len = r.a_len + r.b_len, nt = len / kClipSrcTile + (len % kClipSrcTile != 0);
         uint64_t u;
         if (__builtin_mul_overflow(nt, r.n_channels, &u) || __builtin_add_overflow(units, u, &units) || units > 0x7fffffffull) {
             *why = "more than 2^31 tiles in one call: export in batches";
             return FVAD_ERR_INVALID_ARGUMENT;
         }
-        if (rs) {
-            const uint64_t to = resampled_tile_out(Ratio{rs->up, rs->down}, rs->n_taps), n = resample_out_frames(len, Ratio{rs->up, rs->down});
-            if (__builtin_add_overflow(gather, n / to + (n % to != 0), &gather) || gather > 0x7fffffffull) {
-                *why = "more than 2^31 tiles in one call: export in batches";
-                return FVAD_ERR_INVALID_ARGUMENT;
-            }
-        }
-        if (strided) {
-            const uint64_t to = fir ? fir_tile_out(strided->step, fir->n_taps) : strided_tile_out(strided->step), n = (len - (strided->skips ? strided->skips[i] : 0) + strided->step - 1) / strided->step;
-            if (__builtin_add_overflow(gather, n / to + (n % to != 0), &gather) || gather > 0x7fffffffull) {
-                *why = "more than 2^31 tiles in one call: export in batches";
-                return FVAD_ERR_INVALID_ARGUMENT;
-            }
+        if (__builtin_add_overflow(gather, form_gather_tiles(form, i, len), &gather) || gather > 0x7fffffffull) {
+            *why = "more than 2^31 tiles in one call: export in batches";
+            return FVAD_ERR_INVALID_ARGUMENT;
         }
     }
     return FVAD_OK;
@@ -147,5 +105,5 @@ extern "C" int fvad_clips_split_check(const void* d_a, size_t a_lanes, size_t a_
                                       uint64_t* offsets, uint64_t* total)
 {
     return fvad::clips_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips,
-                                   out_format, out, out_capacity, device_out, offsets, total, nullptr, nullptr, nullptr, nullptr);
+                                   out_format, out, out_capacity, device_out, offsets, total, nullptr, fvad::ClipForm{});
 }

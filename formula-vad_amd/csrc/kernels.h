@@ -439,11 +439,8 @@ struct ClipArgs {
     uint32_t n_clips, n_units, n_tiles;
     int src_i16, out_i16;
 };
-int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream);    // hipError_t as int
-int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream);   // (after fvad_launch_clip_rms on the same stream)
-int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick)
 
-// The split-source form (kernels_clips_split.hip, fvad_clips_export_split*): a clip's channel ch is a_len samples at
+// The split-source form (fvad_clips_export_split*; staged by clip_source_device.h): a clip's channel ch is a_len samples at
 // a + a_off + ch * a_stride followed by len - a_len samples at b + b_off + ch * b_stride, and is read as if it were one run.
 // Units, tiles (counted from the clip's first sample), partials and infos are ClipArgs', and clip_pick_kernel runs on `c` as it
 // is; c.src / c.lane_stride are piece A's, c.jobs[i].src_off is not used.
@@ -456,8 +453,12 @@ struct ClipSplitArgs {
     uint64_t b_stride;
     const ClipSplit* splits; // [n_clips] (device)
 };
-int fvad_launch_clip_rms_split(const ClipSplitArgs& a, hipStream_t stream);    // hipError_t as int
-int fvad_launch_clip_gather_split(const ClipSplitArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.c) after the rms)
+// every launch of the Recorder: hipError_t as int, and one overload per source (B below is ClipArgs or ClipSplitArgs)
+int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream);
+int fvad_launch_clip_rms(const ClipSplitArgs& a, hipStream_t stream);
+int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream);   // (after fvad_launch_clip_rms on the same stream; a split call's a.c)
+int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather(const ClipSplitArgs& a, hipStream_t stream);
 
 // The strided gathers (kernels_clips_strided.hip, fvad_clips_export*_strided): of the picked channel the samples skip,
 // skip + step, ... of the clip (skip = jobs[i].skip < step), out_len = ceil((len - skip) / step) of them into the clip's slot.
@@ -468,16 +469,12 @@ constexpr uint32_t kClipStepMax = 16; // FVAD_CLIP_STEP_MAX
 // floor(kClipTile / step) rounded down to a multiple of 8: a tile's first output is on a 16-byte boundary of its slot in
 // either output format, and its (tile_out - 1) * step + 1 source samples fit stage_tile's LDS image
 constexpr uint32_t clip_tile_out(uint32_t step) { return (uint32_t)kClipTile / step / 8 * 8; }
-struct ClipStridedArgs {
-    ClipArgs c;
+template <typename B> struct ClipStridedArgs {
+    B s; // the source
     uint32_t step, tile_out;
 };
-struct ClipSplitStridedArgs {
-    ClipSplitArgs s;
-    uint32_t step, tile_out;
-};
-int fvad_launch_clip_gather_strided(const ClipStridedArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
-int fvad_launch_clip_gather_strided_split(const ClipSplitStridedArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
+int fvad_launch_clip_gather_strided(const ClipStridedArgs<ClipArgs>& a, hipStream_t stream); // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_strided(const ClipStridedArgs<ClipSplitArgs>& a, hipStream_t stream);
 
 // The filtered gathers (kernels_clips_fir.hip, fvad_clips_export*_fir): output q of a clip is the FIR sum of n_taps taps over the
 // picked channel's samples around c = skip + q * step, the clip zero-extended.  Tiles are counted in OUTPUT samples from the
@@ -486,36 +483,26 @@ constexpr uint32_t kClipFirTapsMax = 513; // FVAD_CLIP_FIR_TAPS_MAX
 // ((kClipTile - n_taps) / step + 1) rounded down to a multiple of 8: the (tile_out - 1) * step + n_taps source samples of a
 // tile, halo and zero extension included, fit kClipTile
 constexpr uint32_t clip_fir_tile_out(uint32_t step, uint32_t n_taps) { return (((uint32_t)kClipTile - n_taps) / step + 1) / 8 * 8; }
-struct ClipFirArgs {
-    ClipArgs c;
+template <typename B> struct ClipFirArgs {
+    B s;
     const float* taps;   // [n_taps] (device), branch by branch: taps[j], taps[j + step], ... for j = 0 .. step - 1
     uint32_t step, tile_out, n_taps, pad;
 };
-struct ClipSplitFirArgs {
-    ClipSplitArgs s;
-    const float* taps;
-    uint32_t step, tile_out, n_taps, pad;
-};
-int fvad_launch_clip_gather_fir(const ClipFirArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
-int fvad_launch_clip_gather_fir_split(const ClipSplitFirArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
+int fvad_launch_clip_gather_fir(const ClipFirArgs<ClipArgs>& a, hipStream_t stream); // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_fir(const ClipFirArgs<ClipSplitArgs>& a, hipStream_t stream);
 
 // The resampling gathers (kernels_clips_resample.hip, fvad_clips_export*_resampled): output o of a clip is the polyphase sum
 // sum_j table[j * up + o mod up] * x[q - j], q = (K + o * down) / up, over the picked channel's samples, the clip zero-extended;
 // out_len = ceil(len * up / down).  Tiles are counted in OUTPUT samples from the clip's first output (tile_out of them, a
 // multiple of 8: resampled_tile_out of clips_resample.h); a tile's window of at most kClipTile clip samples is staged once.
 constexpr uint32_t kClipResampleTableLds = 6144; // table entries (24 KB) that are kept in LDS beside the window; a longer table stays in global memory
-struct ClipResampleArgs {
-    ClipArgs c;
+template <typename B> struct ClipResampleArgs {
+    B s;
     const float* table;  // [ceil(n_taps / up) * up] (device): resample_table of resample.h
     uint32_t up, down, tile_out, n_taps;
 };
-struct ClipSplitResampleArgs {
-    ClipSplitArgs s;
-    const float* table;
-    uint32_t up, down, tile_out, n_taps;
-};
-int fvad_launch_clip_gather_resampled(const ClipResampleArgs& a, hipStream_t stream);            // (after fvad_launch_clip_pick)
-int fvad_launch_clip_gather_resampled_split(const ClipSplitResampleArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick(a.s.c))
+int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipArgs>& a, hipStream_t stream); // (after fvad_launch_clip_pick)
+int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipSplitArgs>& a, hipStream_t stream);
 
 // The log-mel features (kernels_clips_mel.hip, fvad_clips_export_mel*): of the picked channel's strided stream s[i] = sample
 // skip + i * step (L = ceil((len - skip) / step) of them) the frames t < T = floor(L / hop) of n_fft taps, centred with

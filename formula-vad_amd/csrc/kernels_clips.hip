@@ -7,80 +7,51 @@
 // clip_pick_kernel adds a channel's partials in tile order.  A clip's numbers therefore depend on its own samples alone, never on
 // the other clips of the call.
 //
-// A tile is staged through LDS once: clip starts are arbitrary sample indices, so the tile's first byte has any alignment.  The
-// 16-byte aligned body strictly inside the tile is read with 16-byte loads, the elements in front of and behind it one by one
-// -- no byte outside [sample_from, sample_to) is read -- and the LDS image keeps the global address's offset within 16 bytes, so
-// that the body's LDS stores are full width too.  Every later read of the tile is by sample index within the tile.
+// A tile is staged through LDS once, by the clip source (clip_source_device.h), and every later read of it is by sample index
+// within the tile.  Each kernel is instantiated for both sources: a clip's channel as one run (fvad_clips_export*), or a head
+// piece in buffer A followed by a body piece in buffer B (fvad_clips_export_split*), as MRBRecorder reads a recording from its
+// ring as a SplitSlice (MRBRecorder.zig:160-192).  A run sliced in time keeps only the tail of earlier slices (A) beside the
+// current slice's lanes (B); a clip may lie in either or across the seam, and the carry of the tail itself is a split export of
+// one mono clip per lane.  Tiles are counted from the clip's first sample, never from the seam, and the sum order below is one
+// text: a split clip's samples, pick and RMS values are the bits of the same samples laid out contiguously.
 #include <hip/hip_runtime.h>
 
 #include "clip_device.h"
+#include "clip_source_device.h"
 #include "kernels.h"
-#include "stage_tile.h"
 
 namespace {
 
 constexpr int kThreads = kStageThreads;
 
-template <typename S>
-__device__ inline void rms_tile(const ClipArgs& a, S* lds, double* wsum)
+} // namespace
+
+// one f64 partial per (clip, channel, tile), the tiles counted from the clip's first sample
+template <typename S, typename B>
+__global__ __launch_bounds__(kThreads) void clip_rms_kernel(B a)
 {
+    __shared__ __attribute__((aligned(16))) S lds[ClipSource<B>::template lds_elems<S>()];
+    __shared__ double wsum[kThreads / 64];
+    const ClipArgs& c = clip_args(a);
     const uint32_t u = blockIdx.x;
-    const ClipJob j = a.jobs[find_clip(a.unit_prefix, a.n_clips, u)];
+    const uint32_t clip = find_clip(c.unit_prefix, c.n_clips, u);
+    const ClipJob j = c.jobs[clip];
     const uint32_t r = u - j.first_unit;
     const uint32_t ch = r / j.n_tiles, k = r % j.n_tiles;
     const uint64_t e0 = (uint64_t)k * kClipTile;
     const int n = (int)min((uint64_t)kClipTile, j.len - e0);
-    const S* p = static_cast<const S*>(a.src) + j.src_off + (uint64_t)ch * a.lane_stride + e0;
-    const int shift = stage_tile(p, n, lds);
+    const auto at = ClipSource<B>::template stage<S>(a, clip, ch, e0, n, lds);
     // fixed order: a thread adds its samples t, t + 256, ... one after the other, then the tree below
     const int t = threadIdx.x;
     double s = 0.0;
     for (int e = t; e < n; e += kThreads) {
-        const double x = (double)to_f32(lds[shift + e]); // the product of two f32 is exact in f64
+        const double x = (double)to_f32(lds[at(e)]); // the product of two f32 is exact in f64
         s += x * x;
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if ((t & 63) == 0) wsum[t >> 6] = s;
     __syncthreads();
-    if (t == 0) a.partials[u] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
-template <typename D, typename S>
-__device__ inline void gather_tile(const ClipArgs& a, S* lds)
-{
-    constexpr int G = 8; // samples per thread and step: one 16-byte store of PCM16, two of f32
-    const uint32_t g = blockIdx.x;
-    const uint32_t c = find_clip(a.tile_prefix, a.n_clips, g);
-    const ClipJob j = a.jobs[c];
-    const uint32_t k = g - a.tile_prefix[c];
-    const uint32_t ch = (uint32_t)a.infos[c].best_channel;
-    const uint64_t e0 = (uint64_t)k * kClipTile;
-    const int n = (int)min((uint64_t)kClipTile, j.len - e0);
-    const S* p = static_cast<const S*>(a.src) + j.src_off + (uint64_t)ch * a.lane_stride + e0;
-    const int shift = stage_tile(p, n, lds);
-    D* out = static_cast<D*>(a.out) + j.out_off + e0; // 16-byte aligned: the slot is, and kClipTile is a multiple of G
-    for (int q = threadIdx.x * G; q < n; q += kThreads * G) {
-        if (q + G <= n) {
-            alignas(16) D v[G];
-#pragma unroll
-            for (int i = 0; i < G; ++i) v[i] = Convert<D, S>::run(lds[shift + q + i]);
-            constexpr int NV = G * (int)sizeof(D) / 16;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) reinterpret_cast<uint4*>(out + q)[i] = reinterpret_cast<const uint4*>(v)[i];
-        } else { // the clip's last samples: nothing is written past the clip
-            for (int i = q; i < n; ++i) out[i] = Convert<D, S>::run(lds[shift + i]);
-        }
-    }
-}
-
-} // namespace
-
-template <typename S>
-__global__ __launch_bounds__(kThreads) void clip_rms_kernel(ClipArgs a)
-{
-    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
-    __shared__ double wsum[kThreads / 64];
-    rms_tile<S>(a, lds, wsum);
+    if (t == 0) c.partials[u] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
 // one lane per clip: rms = (float)sqrt(sum / n) per channel, the channel's partials added in tile order; the pick is
@@ -119,19 +90,59 @@ __global__ __launch_bounds__(64) void clip_pick_kernel(ClipArgs a)
     a.infos[c] = o;
 }
 
-template <typename D, typename S>
-__global__ __launch_bounds__(kThreads) void clip_gather_kernel(ClipArgs a)
+// the picked channel's samples into the clip's slot, 8 consecutive outputs per lane and pass
+template <typename D, typename S, typename B>
+__global__ __launch_bounds__(kThreads) void clip_gather_kernel(B a)
 {
-    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
-    gather_tile<D, S>(a, lds);
+    __shared__ __attribute__((aligned(16))) S lds[ClipSource<B>::template lds_elems<S>()];
+    constexpr int G = 8; // samples per thread and step: one 16-byte store of PCM16, two of f32
+    const ClipArgs& c = clip_args(a);
+    const uint32_t g = blockIdx.x;
+    const uint32_t clip = find_clip(c.tile_prefix, c.n_clips, g);
+    const ClipJob j = c.jobs[clip];
+    const uint32_t k = g - c.tile_prefix[clip];
+    const uint32_t ch = (uint32_t)c.infos[clip].best_channel;
+    const uint64_t e0 = (uint64_t)k * kClipTile;
+    const int n = (int)min((uint64_t)kClipTile, j.len - e0);
+    const auto at = ClipSource<B>::template stage<S>(a, clip, ch, e0, n, lds);
+    D* out = static_cast<D*>(c.out) + j.out_off + e0; // 16-byte aligned: the slot is, and kClipTile is a multiple of G
+    for (int q = threadIdx.x * G; q < n; q += kThreads * G) {
+        if (q + G <= n) {
+            alignas(16) D v[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) v[i] = Convert<D, S>::run(lds[at(q + i)]);
+            constexpr int NV = G * (int)sizeof(D) / 16;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) reinterpret_cast<uint4*>(out + q)[i] = reinterpret_cast<const uint4*>(v)[i];
+        } else { // the clip's last samples: nothing is written past the clip
+            for (int i = q; i < n; ++i) out[i] = Convert<D, S>::run(lds[at(i)]);
+        }
+    }
 }
 
-int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream)
+namespace {
+
+template <typename B>
+int launch_rms(const B& a, hipStream_t stream)
 {
-    if (a.src_i16) hipLaunchKernelGGL(clip_rms_kernel<int16_t>, dim3(a.n_units), dim3(kThreads), 0, stream, a);
-    else hipLaunchKernelGGL(clip_rms_kernel<float>, dim3(a.n_units), dim3(kThreads), 0, stream, a);
+    const dim3 grid(clip_args(a).n_units), block(kThreads);
+    if (clip_args(a).src_i16) hipLaunchKernelGGL((clip_rms_kernel<int16_t, B>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((clip_rms_kernel<float, B>), grid, block, 0, stream, a);
     return (int)hipGetLastError();
 }
+
+template <typename B>
+int launch_gather(const B& a, hipStream_t stream)
+{
+    return launch_clip_formats(clip_args(a), [&](auto d, auto s, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((clip_gather_kernel<decltype(d), decltype(s), B>), grid, block, 0, stream, a);
+    });
+}
+
+} // namespace
+
+int fvad_launch_clip_rms(const ClipArgs& a, hipStream_t stream) { return launch_rms(a, stream); }
+int fvad_launch_clip_rms(const ClipSplitArgs& a, hipStream_t stream) { return launch_rms(a, stream); }
 
 int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream)
 {
@@ -139,12 +150,5 @@ int fvad_launch_clip_pick(const ClipArgs& a, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
-int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream)
-{
-    const dim3 grid(a.n_tiles), block(kThreads);
-    if (a.src_i16 && a.out_i16) hipLaunchKernelGGL((clip_gather_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.src_i16) hipLaunchKernelGGL((clip_gather_kernel<float, int16_t>), grid, block, 0, stream, a);
-    else if (a.out_i16) hipLaunchKernelGGL((clip_gather_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_kernel<float, float>), grid, block, 0, stream, a);
-    return (int)hipGetLastError();
-}
+int fvad_launch_clip_gather(const ClipArgs& a, hipStream_t stream) { return launch_gather(a, stream); }
+int fvad_launch_clip_gather(const ClipSplitArgs& a, hipStream_t stream) { return launch_gather(a, stream); }

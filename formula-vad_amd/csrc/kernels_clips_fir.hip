@@ -3,16 +3,16 @@
 // x the picked channel of the clip as f32 (PCM16: s / 32768, exact), 0 outside [0, len), accumulated in f32 by fma and converted
 // by Convert<D, float>.  The strided gathers (kernels_clips_strided.hip) keep every step-th sample and so fold everything above
 // the new Nyquist frequency into the band; here only the kept, band-limited samples leave the device.  RMS and pick are
-// kernels_clips.hip's and kernels_clips_split.hip's over EVERY sample of the UNFILTERED clip, so the pick and both RMS values are
-// the full-rate export's bits.
+// kernels_clips.hip's over EVERY sample of the UNFILTERED clip, so the pick and both RMS values are the full-rate export's bits.
 //
 // Work unit: a tile of tile_out = ((kClipTile - n_taps) / step + 1) / 8 * 8 OUTPUT samples of one clip, counted from the clip's
 // first kept sample (never from the seam of a split clip); step 3 with 97 taps: 2696 outputs, step 16 with 513 taps: 480.  The
 // tile's window is the (n_out - 1) * step + n_taps clip samples [c_first - H, c_last + H]; the part of it inside [0, len) is
-// staged by stage_tile / stage_split as they are (no byte outside the clip is read), and the zero extension is WRITTEN INTO LDS,
-// not tested per read: one pass copies the staged run, converted to f32, with zeros in front of and behind it, into a second
-// LDS image that the filter alone reads.  That pass also makes the two forms, the two source formats and the seam tile one
-// case: whatever Staged::at and the conversion cost is paid once per staged sample and not once per tap.
+// staged by the clip source (clip_source_device.h) as they are (no byte outside the clip is read), and the zero extension is
+// WRITTEN INTO LDS, not tested per read: one pass copies the staged run, converted to f32, with zeros in front of and behind it,
+// into a second LDS image that the filter alone reads.  That pass also makes the two sources, the two source formats and the
+// seam tile one case: whatever the source's index functor and the conversion cost is paid once per staged sample and not once
+// per tap.
 //
 // Lane mapping: a lane computes kR = 4 consecutive outputs ("a slot": outputs 4 L .. 4 L + 3 of the tile, L = lane + 256 pass).
 // Its window is n_taps + 3 step samples.  With k = j + step m the sum splits into `step` branches, y[r] += taps[j + step m] *
@@ -34,9 +34,8 @@
 #include <hip/hip_runtime.h>
 
 #include "clip_device.h"
-#include "clip_split_device.h"
+#include "clip_source_device.h"
 #include "kernels.h"
-#include "stage_tile.h"
 
 namespace {
 
@@ -156,50 +155,32 @@ __device__ inline void fir_run(D* out, const FirTile& t, int step, int n_taps, c
 
 } // namespace
 
-template <typename D, typename S>
-__global__ __launch_bounds__(kThreads) void clip_gather_fir_kernel(ClipFirArgs a)
+template <typename D, typename S, typename B>
+__global__ __launch_bounds__(kThreads) void clip_gather_fir_kernel(ClipFirArgs<B> a)
 {
-    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
+    __shared__ __attribute__((aligned(16))) S lds[ClipSource<B>::template lds_elems<S>()];
     __shared__ float xf[kImage];
-    const FirTile t = fir_tile(a.c, a.step, a.tile_out, a.n_taps);
-    const ClipJob j = a.c.jobs[t.clip];
-    const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
-    const S* p = static_cast<const S*>(a.c.src) + j.src_off + (uint64_t)ch * a.c.lane_stride + t.lo;
-    const int shift = stage_tile(p, t.n, lds);
-    D* out = static_cast<D*>(a.c.out) + j.out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
-    fir_run<D, S>(out, t, (int)a.step, (int)a.n_taps, a.taps, lds, xf, [shift](int e) { return shift + e; });
-}
-
-template <typename D, typename S>
-__global__ __launch_bounds__(kThreads) void clip_gather_fir_split_kernel(ClipSplitFirArgs a)
-{
-    __shared__ __attribute__((aligned(16))) S lds[lds_elems<S>()];
-    __shared__ float xf[kImage];
-    const ClipArgs& c = a.s.c;
+    const ClipArgs& c = clip_args(a.s);
     const FirTile t = fir_tile(c, a.step, a.tile_out, a.n_taps);
     const uint32_t ch = (uint32_t)c.infos[t.clip].best_channel;
-    // the window is counted from the clip's first sample (lo), so the filter runs through the seam
-    const Staged st = stage_split<S>(a.s, a.s.splits[t.clip], ch, t.lo, t.n, lds);
-    D* out = static_cast<D*>(c.out) + c.jobs[t.clip].out_off + t.o0;
-    fir_run<D, S>(out, t, (int)a.step, (int)a.n_taps, a.taps, lds, xf, [st](int e) { return st.at(e); });
+    // (the job's slot is read before the staging, so that its load is not waited for behind the barrier)
+    D* out = static_cast<D*>(c.out) + c.jobs[t.clip].out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
+    // the window is counted from the clip's first sample (lo), so the filter runs through the seam of a split clip
+    const auto at = ClipSource<B>::template stage<S>(a.s, t.clip, ch, t.lo, t.n, lds);
+    fir_run<D, S>(out, t, (int)a.step, (int)a.n_taps, a.taps, lds, xf, at);
 }
 
-int fvad_launch_clip_gather_fir(const ClipFirArgs& a, hipStream_t stream)
+namespace {
+
+template <typename B>
+int launch(const ClipFirArgs<B>& a, hipStream_t stream)
 {
-    const dim3 grid(a.c.n_tiles), block(kThreads);
-    if (a.c.src_i16 && a.c.out_i16) hipLaunchKernelGGL((clip_gather_fir_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.c.src_i16) hipLaunchKernelGGL((clip_gather_fir_kernel<float, int16_t>), grid, block, 0, stream, a);
-    else if (a.c.out_i16) hipLaunchKernelGGL((clip_gather_fir_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_fir_kernel<float, float>), grid, block, 0, stream, a);
-    return (int)hipGetLastError();
+    return launch_clip_formats(clip_args(a.s), [&](auto d, auto s, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((clip_gather_fir_kernel<decltype(d), decltype(s), B>), grid, block, 0, stream, a);
+    });
 }
 
-int fvad_launch_clip_gather_fir_split(const ClipSplitFirArgs& a, hipStream_t stream)
-{
-    const dim3 grid(a.s.c.n_tiles), block(kThreads);
-    if (a.s.c.src_i16 && a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_fir_split_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.s.c.src_i16) hipLaunchKernelGGL((clip_gather_fir_split_kernel<float, int16_t>), grid, block, 0, stream, a);
-    else if (a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_fir_split_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_fir_split_kernel<float, float>), grid, block, 0, stream, a);
-    return (int)hipGetLastError();
-}
+} // namespace
+
+int fvad_launch_clip_gather_fir(const ClipFirArgs<ClipArgs>& a, hipStream_t stream) { return launch(a, stream); }
+int fvad_launch_clip_gather_fir(const ClipFirArgs<ClipSplitArgs>& a, hipStream_t stream) { return launch(a, stream); }

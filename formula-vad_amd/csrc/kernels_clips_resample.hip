@@ -3,16 +3,16 @@
 //     y[o] = sum_j taps[r + j up] * x[q - j],   P = K + o down = q up + r,  j = 0 .. (2 K - r) / up,  K = (n_taps - 1) / 2,
 // x the picked channel of the clip as f32 (PCM16: s / 32768, exact), 0 outside [0, len), one f32 fma chain from +0 in ascending
 // j, converted by Convert<D, float>.  o is counted from the CLIP's first sample: never from the lane index, the tile or the seam
-// of a split clip.  RMS and pick are kernels_clips.hip's and kernels_clips_split.hip's over EVERY sample of the UNRESAMPLED clip,
-// so the pick and both RMS values are the full-rate export's bits.
+// of a split clip.  RMS and pick are kernels_clips.hip's over EVERY sample of the UNRESAMPLED clip, so the pick and both RMS
+// values are the full-rate export's bits.
 //
 // Work unit: a tile of tile_out OUTPUT samples of one clip (resampled_tile_out of clips_resample.h: the most, in eights, whose
 // window fits kClipTile clip samples; 147/160 with 5121 taps: 7488, 147/640 with 20481 taps: 1848), found by a search of the
 // host-built prefix table.  The tile's window [ceil((o_first down - K) / up), floor((o_last down + K) / up)], clipped to
-// [0, len), is staged once by stage_tile / stage_split as they are: no byte outside the clip is read, and the seam of a split
-// clip exists in staging only (Staged::at) -- both forms run resample_run.  The zero extension is SKIPPED, not stored: the j
-// range of an output is cut to the clip.  With finite taps that gives the bits multiplying the zeros would give
-// (fma(t, 0, acc) is acc, and +0 for acc = +0).
+// [0, len), is staged once by the clip source (clip_source_device.h) as it is: no byte outside the clip is read, and the seam of
+// a split clip exists in staging only (the source's index functor) -- both sources run resample_run.  The zero extension is
+// SKIPPED, not stored: the j range of an output is cut to the clip.  With finite taps that gives the bits multiplying the zeros
+// would give (fma(t, 0, acc) is acc, and +0 for acc = +0).
 //
 // Lane mapping: consecutive lanes take consecutive outputs (the resampling ingest gives a lane 4 consecutive outputs, which puts
 // the tap reads of neighbouring lanes 4 words apart and their window reads 4 down / up samples apart).  A pass of the workgroup
@@ -36,9 +36,8 @@
 #include <hip/hip_runtime.h>
 
 #include "clip_device.h"
-#include "clip_split_device.h"
+#include "clip_source_device.h"
 #include "kernels.h"
-#include "stage_tile.h"
 
 namespace {
 
@@ -142,73 +141,46 @@ __device__ inline void resample_run(D* out, const RsTile& t, uint32_t up, uint32
 
 } // namespace
 
-template <typename D, typename S, bool TL>
-__global__ __launch_bounds__(kThreads) void clip_gather_resampled_kernel(ClipResampleArgs a)
+template <typename D, typename S, typename B, bool TL>
+__global__ __launch_bounds__(kThreads) void clip_gather_resampled_kernel(ClipResampleArgs<B> a)
 {
-    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
+    __shared__ __attribute__((aligned(16))) S lds[ClipSource<B>::template lds_elems<S>()];
     __shared__ __attribute__((aligned(16))) float ybuf[kPass];
     __shared__ float tab[TL ? kClipResampleTableLds : 1];
-    const RsTile t = rs_tile(a.c, a.up, a.down, a.tile_out, a.n_taps);
-    const ClipJob j = a.c.jobs[t.clip];
-    const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
-    const float* table = rs_table<TL>(a.table, a.up, a.n_taps, tab);
-    int shift = 0;
-    if (t.n > 0) shift = stage_tile(static_cast<const S*>(a.c.src) + j.src_off + (uint64_t)ch * a.c.lane_stride + t.lo, t.n, lds);
-    D* out = static_cast<D*>(a.c.out) + j.out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
-    resample_run<D, S>(out, t, a.up, a.down, a.n_taps, table, lds, ybuf, [shift](int e) { return shift + e; });
-}
-
-template <typename D, typename S, bool TL>
-__global__ __launch_bounds__(kThreads) void clip_gather_resampled_split_kernel(ClipSplitResampleArgs a)
-{
-    __shared__ __attribute__((aligned(16))) S lds[lds_elems<S>()];
-    __shared__ __attribute__((aligned(16))) float ybuf[kPass];
-    __shared__ float tab[TL ? kClipResampleTableLds : 1];
-    const ClipArgs& c = a.s.c;
+    const ClipArgs& c = clip_args(a.s);
     const RsTile t = rs_tile(c, a.up, a.down, a.tile_out, a.n_taps);
+    const ClipJob j = c.jobs[t.clip]; // (read before the table copy and the staging: its load is not waited for behind the barrier)
     const uint32_t ch = (uint32_t)c.infos[t.clip].best_channel;
     const float* table = rs_table<TL>(a.table, a.up, a.n_taps, tab);
-    // the window is counted from the clip's first sample (lo), so the filter runs through the seam
-    Staged st{0, 0, 0};
-    if (t.n > 0) st = stage_split<S>(a.s, a.s.splits[t.clip], ch, t.lo, t.n, lds);
-    D* out = static_cast<D*>(c.out) + c.jobs[t.clip].out_off + t.o0;
-    resample_run<D, S>(out, t, a.up, a.down, a.n_taps, table, lds, ybuf, [st](int e) { return st.at(e); });
+    // the window is counted from the clip's first sample (lo), so the filter runs through the seam of a split clip; a window of
+    // no samples is not staged
+    typename ClipSource<B>::At at{};
+    if (t.n > 0) at = ClipSource<B>::template stage<S>(a.s, t.clip, ch, t.lo, t.n, lds);
+    D* out = static_cast<D*>(c.out) + j.out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
+    // (the functor goes in behind a lambda, as each source's kernel used to pass it: handed over as it is, the compiler derives
+    // ybuf's write address from its read address and not the other way round -- one instruction more in front of the loops,
+    // which then lie 8 bytes further on in their 64-byte lines; measured 0.6 - 2 % slower with the table in LDS)
+    resample_run<D, S>(out, t, a.up, a.down, a.n_taps, table, lds, ybuf, [at](int e) { return at(e); });
 }
 
 namespace {
 
-bool table_in_lds(uint32_t up, uint32_t n_taps) { return (uint64_t)((n_taps + up - 1) / up) * up <= kClipResampleTableLds; }
-
-template <bool TL>
-void launch(const ClipResampleArgs& a, hipStream_t stream)
+template <typename B, bool TL>
+int launch(const ClipResampleArgs<B>& a, hipStream_t stream)
 {
-    const dim3 grid(a.c.n_tiles), block(kThreads);
-    if (a.c.src_i16 && a.c.out_i16) hipLaunchKernelGGL((clip_gather_resampled_kernel<int16_t, int16_t, TL>), grid, block, 0, stream, a);
-    else if (a.c.src_i16) hipLaunchKernelGGL((clip_gather_resampled_kernel<float, int16_t, TL>), grid, block, 0, stream, a);
-    else if (a.c.out_i16) hipLaunchKernelGGL((clip_gather_resampled_kernel<int16_t, float, TL>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_resampled_kernel<float, float, TL>), grid, block, 0, stream, a);
+    return launch_clip_formats(clip_args(a.s), [&](auto d, auto s, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((clip_gather_resampled_kernel<decltype(d), decltype(s), B, TL>), grid, block, 0, stream, a);
+    });
 }
 
-template <bool TL>
-void launch_split(const ClipSplitResampleArgs& a, hipStream_t stream)
+template <typename B>
+int launch(const ClipResampleArgs<B>& a, hipStream_t stream)
 {
-    const dim3 grid(a.s.c.n_tiles), block(kThreads);
-    if (a.s.c.src_i16 && a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_resampled_split_kernel<int16_t, int16_t, TL>), grid, block, 0, stream, a);
-    else if (a.s.c.src_i16) hipLaunchKernelGGL((clip_gather_resampled_split_kernel<float, int16_t, TL>), grid, block, 0, stream, a);
-    else if (a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_resampled_split_kernel<int16_t, float, TL>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_resampled_split_kernel<float, float, TL>), grid, block, 0, stream, a);
+    const bool table_in_lds = (uint64_t)((a.n_taps + a.up - 1) / a.up) * a.up <= kClipResampleTableLds;
+    return table_in_lds ? launch<B, true>(a, stream) : launch<B, false>(a, stream);
 }
 
 } // namespace
 
-int fvad_launch_clip_gather_resampled(const ClipResampleArgs& a, hipStream_t stream)
-{
-    if (table_in_lds(a.up, a.n_taps)) launch<true>(a, stream); else launch<false>(a, stream);
-    return (int)hipGetLastError();
-}
-
-int fvad_launch_clip_gather_resampled_split(const ClipSplitResampleArgs& a, hipStream_t stream)
-{
-    if (table_in_lds(a.up, a.n_taps)) launch_split<true>(a, stream); else launch_split<false>(a, stream);
-    return (int)hipGetLastError();
-}
+int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipArgs>& a, hipStream_t stream) { return launch(a, stream); }
+int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipSplitArgs>& a, hipStream_t stream) { return launch(a, stream); }

@@ -2,13 +2,13 @@
 // samples skip, skip + step, skip + 2 step, ... of the clip.  K3 brings NSNet2's 16 kHz output back to 48 kHz as [lerp, lerp,
 // sample] per 16 kHz sample (resample.zig:32-79), so a denoised lane's samples at index = 2 (mod 3) are the network's output and
 // step 3 exports exactly those; at index = 0 (mod 3) the original lane gives what downsampleAudio fed the network
-// (resample.zig:9-29).  RMS and pick are kernels_clips.hip's and kernels_clips_split.hip's over EVERY sample of the clip: only
-// the gather differs, so the pick and both RMS values are the full-rate export's bits.
+// (resample.zig:9-29).  RMS and pick are kernels_clips.hip's over EVERY sample of the clip: only the gather differs, so the pick
+// and both RMS values are the full-rate export's bits.
 //
 // Work unit: a tile of tile_out = floor(kClipTile / step) / 8 * 8 OUTPUT samples of one clip, counted from the clip's first kept
 // sample (never from the seam of a split clip); step 3: 2728 outputs, 8182 source samples staged.  A tile's first output is on a
 // 16-byte boundary of its slot, and the (n_out - 1) * step + 1 source samples from its first kept sample to its last are staged
-// by stage_tile / stage_split as they are -- nothing behind the clip's last kept sample is read.
+// by the clip source (clip_source_device.h) as they are -- nothing behind the clip's last kept sample is read.
 //
 // Lane mapping: one output per lane and pass, lane t reads element t * step of the staged tile.  Banks of the 4-byte and narrower
 // LDS reads are (byte / 4) mod 32 per 32-lane half: f32 lanes are `step` dwords apart, gcd(step, 32)-way (step 3: conflict-free,
@@ -20,9 +20,8 @@
 #include <hip/hip_runtime.h>
 
 #include "clip_device.h"
-#include "clip_split_device.h"
+#include "clip_source_device.h"
 #include "kernels.h"
-#include "stage_tile.h"
 
 namespace {
 
@@ -72,48 +71,31 @@ __device__ inline void store_strided(D* out, int n_out, int step, const S* lds, 
 
 } // namespace
 
-template <typename D, typename S>
-__global__ __launch_bounds__(kThreads) void clip_gather_strided_kernel(ClipStridedArgs a)
+template <typename D, typename S, typename B>
+__global__ __launch_bounds__(kThreads) void clip_gather_strided_kernel(ClipStridedArgs<B> a)
 {
-    __shared__ __attribute__((aligned(16))) S lds[kClipTile + 16 / sizeof(S)];
-    const StridedTile t = strided_tile(a.c, a.step, a.tile_out);
-    const ClipJob j = a.c.jobs[t.clip];
-    const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
-    const S* p = static_cast<const S*>(a.c.src) + j.src_off + (uint64_t)ch * a.c.lane_stride + t.e0;
-    const int shift = stage_tile(p, t.n, lds);
-    D* out = static_cast<D*>(a.c.out) + j.out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
-    store_strided<D, S>(out, t.n_out, (int)a.step, lds, [shift](int e) { return shift + e; });
-}
-
-template <typename D, typename S>
-__global__ __launch_bounds__(kThreads) void clip_gather_strided_split_kernel(ClipSplitStridedArgs a)
-{
-    __shared__ __attribute__((aligned(16))) S lds[lds_elems<S>()];
-    const ClipArgs& c = a.s.c;
+    __shared__ __attribute__((aligned(16))) S lds[ClipSource<B>::template lds_elems<S>()];
+    const ClipArgs& c = clip_args(a.s);
     const StridedTile t = strided_tile(c, a.step, a.tile_out);
     const uint32_t ch = (uint32_t)c.infos[t.clip].best_channel;
-    // the tile's samples are counted from the clip's first sample (e0), so the stride runs through the seam
-    const Staged st = stage_split<S>(a.s, a.s.splits[t.clip], ch, t.e0, t.n, lds);
-    D* out = static_cast<D*>(c.out) + c.jobs[t.clip].out_off + t.o0;
-    store_strided<D, S>(out, t.n_out, (int)a.step, lds, [st](int e) { return st.at(e); });
+    // (the job's slot is read before the staging, so that its load is not waited for behind the barrier)
+    D* out = static_cast<D*>(c.out) + c.jobs[t.clip].out_off + t.o0; // 16-byte aligned: the slot is, and tile_out is a multiple of 8
+    // the tile's samples are counted from the clip's first sample (e0), so the stride runs through the seam of a split clip
+    const auto at = ClipSource<B>::template stage<S>(a.s, t.clip, ch, t.e0, t.n, lds);
+    store_strided<D, S>(out, t.n_out, (int)a.step, lds, at);
 }
 
-int fvad_launch_clip_gather_strided(const ClipStridedArgs& a, hipStream_t stream)
+namespace {
+
+template <typename B>
+int launch(const ClipStridedArgs<B>& a, hipStream_t stream)
 {
-    const dim3 grid(a.c.n_tiles), block(kThreads);
-    if (a.c.src_i16 && a.c.out_i16) hipLaunchKernelGGL((clip_gather_strided_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.c.src_i16) hipLaunchKernelGGL((clip_gather_strided_kernel<float, int16_t>), grid, block, 0, stream, a);
-    else if (a.c.out_i16) hipLaunchKernelGGL((clip_gather_strided_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_strided_kernel<float, float>), grid, block, 0, stream, a);
-    return (int)hipGetLastError();
+    return launch_clip_formats(clip_args(a.s), [&](auto d, auto s, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((clip_gather_strided_kernel<decltype(d), decltype(s), B>), grid, block, 0, stream, a);
+    });
 }
 
-int fvad_launch_clip_gather_strided_split(const ClipSplitStridedArgs& a, hipStream_t stream)
-{
-    const dim3 grid(a.s.c.n_tiles), block(kThreads);
-    if (a.s.c.src_i16 && a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_strided_split_kernel<int16_t, int16_t>), grid, block, 0, stream, a);
-    else if (a.s.c.src_i16) hipLaunchKernelGGL((clip_gather_strided_split_kernel<float, int16_t>), grid, block, 0, stream, a);
-    else if (a.s.c.out_i16) hipLaunchKernelGGL((clip_gather_strided_split_kernel<int16_t, float>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((clip_gather_strided_split_kernel<float, float>), grid, block, 0, stream, a);
-    return (int)hipGetLastError();
-}
+} // namespace
+
+int fvad_launch_clip_gather_strided(const ClipStridedArgs<ClipArgs>& a, hipStream_t stream) { return launch(a, stream); }
+int fvad_launch_clip_gather_strided(const ClipStridedArgs<ClipSplitArgs>& a, hipStream_t stream) { return launch(a, stream); }

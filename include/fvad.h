@@ -840,7 +840,7 @@ int fvad_clips_export(fvad_ctx *ctx, const void *d_src, int src_format, size_t n
  * For runs sliced in time: a clip may begin in audio of earlier slices and end in the current one, so its samples are a head
  * piece in one device buffer (A: the held tail of earlier slices) followed by a body piece in another (B: the current slice's
  * lanes) -- the SplitSlice MRBRecorder reads a recording from its ring as (MRBRecorder.zig:160-192), and what fvad_fft_forward
- * takes as (first, n1, second, n2).  The kernels read the two pieces as one run (csrc/kernels_clips_split.hip).
+ * takes as (first, n1, second, n2).  The kernels read the two pieces as one run (csrc/clip_source_device.h).
  * - A split clip is a row of FVAD_CLIP_SPLIT_FIELDS uint64: n_channels, a_lane, a_from, a_len, b_lane, b_from, b_len.  Its
  *   channel c is A[a_lane + c][a_from, a_from + a_len) followed by B[b_lane + c][b_from, b_from + b_len).  Either length may be
  *   0, not both; a piece of no samples has no other rule.  d_a (d_b) may be NULL when no row takes samples from it.

@@ -212,6 +212,31 @@ def failing(got, want):
     return bad
 
 
+# ------------------------------------------------------------------ a table that stays in global memory
+# The gather keeps a [j][o mod up] table of at most TABLE_LDS entries in LDS beside the window (kClipResampleTableLds of
+# csrc/kernels.h); every table of CASES is shorter.  147/640 with half 5: 6401 taps, 44 x 147 = 6468 entries.
+TABLE_LDS = 6144
+LONG_TABLE = (147, 640, 5, "sinc")
+
+
+def long_table_case(pcm16, seed=7):
+    """the smallest shape that takes the gather with the table in global memory through a full tile, a last tile and a seam
+    inside a tile -> (src [2][n], clips [1][4], SplitLayout): two lanes, channel 1 the quieter, one clip of WINDOW + 3 samples
+    from the odd sample 1 (two gather tiles), NaN / the sentinel around it; the split form's seam at sample WINDOW + 1 of the
+    clip, which only the second tile's window holds"""
+    n = WINDOW + 3
+    rng = np.random.default_rng(seed)
+    if pcm16:
+        x = rng.integers(-15000, 15000, n + 3).astype(np.int16)
+        src = np.stack([x, np.rint(x * float(cc.SCALE)).astype(np.int16)])
+    else:
+        x = rng.uniform(-0.45, 0.45, n + 3).astype(np.float32)
+        src = np.stack([x, x * cc.SCALE])
+    clips = np.array([(0, 2, 1, 1 + n)], np.uint64)
+    src = cc.mask_outside(src, clips)
+    return src, clips, st.SplitLayout(src, clips, [(0, WINDOW + 1)])
+
+
 # ------------------------------------------------------------------ the split form
 def cuts_of(n, up, down, R, To):
     """the seams of a clip of n samples"""

@@ -46,6 +46,22 @@ def test_plan_argument_rules(fv):
     assert L.fvad_clips_plan(None, 0, 1, None, fv.C.byref(total)) == 0 and total.value == 0
 
 
+def test_plan_refuses_a_total_that_does_not_fit_64_bits(fv):
+    """a running total within 16 bytes of 2^64 is refused at the next clip, whatever its length; it must not wrap to a small total"""
+    M = 1 << 64
+    for pcm16, per16 in ((False, 4), (True, 8)):
+        near = (0, 1, 0, M - per16 - 2)            # its slot ends at M - per16: the largest total that is accepted
+        offsets, total = fv.clips_plan([near], pcm16)
+        assert total == M - per16 and list(offsets) == [0]
+        for more in ((0, 1, 0, 1), (0, 1, 0, per16), (0, 1, 0, 100)):
+            with pytest.raises(fv.FvadError) as e:
+                fv.clips_plan([near, more], pcm16)
+            assert e.value.status == INVALID
+        with pytest.raises(fv.FvadError) as e:      # one clip alone whose slot would pass 2^64
+            fv.clips_plan([(0, 1, 0, M - per16)], pcm16)
+        assert e.value.status == INVALID
+
+
 def test_from_segments_keeps_what_the_data_reaches(fv):
     segs = [(100, 5000, 0.0, 0.0), (7000, 24000, 0.0, 0.0), (30000, 48001, 0.0, 0.0)]
     # sample_to exactly at n_available is kept, one past it is not: the reference never finalises such a recording

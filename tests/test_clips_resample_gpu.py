@@ -324,6 +324,50 @@ def test_refused_calls_launch_nothing(dev):
         dev.ctx.enable_timing(False)
 
 
+@pytest.mark.parametrize("kind", ["f32", "pcm16"])
+def test_a_table_that_stays_in_global_memory(gpu_ctx, kind):
+    """clip_resample_cases.long_table_case: a table of more than TABLE_LDS entries, which no table of CASES has, through both
+    sources and all four format pairs.  The contiguous f32 output against the float64 model within the bound, PCM16 out = the f32
+    output converted, split = contiguous bit for bit with the seam inside the second tile's window."""
+    up, down, half, tk = rc.LONG_TABLE
+    taps = rc.case_taps(up, down, half, tk)
+    To = rc.tile_out(up, down, len(taps))
+    assert -(-len(taps) // up) * up > rc.TABLE_LDS
+    src, clips, lay = rc.long_table_case(kind == "pcm16")
+    n, seam = int(clips[0, 3] - clips[0, 2]), int(lay.sigma[0])
+    n_out = rc.out_len(n, up, down)
+    lo2, hi2 = rr.window(up, down, len(taps), n, To, n_out - To)
+    assert To < n_out <= 2 * To and rr.window(up, down, len(taps), n, 0, To)[1] <= seam and lo2 < seam < hi2
+    cap = n_out + 16
+    want = rc.model_export(src, clips, taps, up, down)                    # computed once, shared by the four exports below
+    bufs = [gpu_ctx.device_alloc(a.nbytes) for a in (src, lay.A, lay.B)] + [gpu_ctx.device_alloc(cap * 4)]
+    d_src, d_a, d_b, d_out = bufs
+    try:
+        for d, a in zip(bufs, (src, lay.A, lay.B)):
+            gpu_ctx.to_device(d, np.ascontiguousarray(a))
+
+        def export(split, out_pcm16):
+            dt = np.int16 if out_pcm16 else np.float32
+            gpu_ctx.to_device(d_out, np.full(cap, CANARY[out_pcm16], dt))
+            kw = dict(out_pcm16=out_pcm16, d_out=d_out, out_capacity=cap, up=up, down=down, taps=taps)
+            res = (gpu_ctx.clips_export_split(lay.a(d_a), lay.b(d_b), kind == "pcm16", lay.rows, **kw) if split else
+                   gpu_ctx.clips_export(d_src, kind == "pcm16", 2, src.shape[1], src.shape[1], clips, **kw))
+            out = gpu_ctx.to_host(np.zeros(cap, dt), d_out)
+            assert int(res["out_lens"][0]) == n_out and out[n_out:].tobytes() == np.full(cap - n_out, CANARY[out_pcm16], dt).tobytes()
+            return dict(res, samples=[out[:n_out].copy()])
+
+        got = export(False, False)
+        rc.compare(got, want, f"{up}/{down} half {half} from {kind}")
+        assert np.isfinite(got["samples"][0]).all(), "a read outside the clip reached an output"
+        p = export(False, True)
+        same_bits(p, dict(got, samples=as_pcm16(got)), "to PCM16", ("best_channel", "best_rms", "runner_up_rms"))
+        for out_pcm16, whole in ((False, got), (True, p)):
+            same_bits(export(True, out_pcm16), whole, f"split at {seam}, PCM16 out {out_pcm16}")
+    finally:
+        for d in bufs:
+            gpu_ctx.device_free(d)
+
+
 def test_the_index_width(fv, gpu_ctx):
     """o * down passes 2^32 inside one clip: PCM16 mono at 147/640, half 1; the model on the first and the last tile only"""
     up, down = 147, 640

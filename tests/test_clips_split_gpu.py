@@ -1,4 +1,4 @@
-"""The split-source Recorder on the GPU (fvad_clips_export_split_device / fvad_clips_export_split, csrc/kernels_clips_split.hip):
+"""The split-source Recorder on the GPU (fvad_clips_export_split_device / fvad_clips_export_split, csrc/clip_source_device.h):
 every clip of clip_cases.py's table cut at every seam of clip_split_cases.py, its two pieces in two separately allocated device
 buffers with their own lane counts, strides and lane order, NaN (f32) or a sentinel (PCM16) everywhere around the pieces.
 
