@@ -920,19 +920,7 @@ class Context:
         fmt = INGEST_PCM16 if out_pcm16 else INGEST_F32
         rows = sources.ctypes.data_as(C.POINTER(C.c_uint64))
         if isinstance(raw, (list, tuple)):
-            if len(raw) != n:
-                raise ValueError(f"ingest: {n} sources, {len(raw)} buffers")
-            ptrs = (vp * max(n, 1))()
-            for i, b in enumerate(raw):
-                if b is None or b.size == 0 or int(sources[i, 1]) == 0:   # no frames: no byte is read, whatever byte_offset says
-                    ptrs[i] = None
-                    continue
-                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"]:
-                    raise ValueError("ingest: a source's bytes are a C-contiguous uint8 array")
-                need = int(sources[i, 0]) + int(sources[i, 1]) * int(sources[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sources[i, 3]), 4)
-                if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_ingest", f"source {i} reads {need} bytes of a buffer of {b.size}")
-                ptrs[i] = b.ctypes.data
+            ptrs = _host_buffers("ingest", "source", "reads", sources, raw, writable=False)
             self._ck(lib().fvad_ingest(self.h, ptrs, rows, n, fmt, vp(d_lanes), n_lanes, lane_stride, n_samples), "fvad_ingest")
             return
         self._ck(lib().fvad_ingest_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, fmt, vp(d_lanes), n_lanes, lane_stride,
@@ -949,19 +937,7 @@ class Context:
         taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
         tail = (up, down, fptr(taps), taps.shape[0], vp(d_lanes), n_lanes, lane_stride, n_samples)
         if isinstance(raw, (list, tuple)):
-            if len(raw) != n:
-                raise ValueError(f"ingest_resample: {n} sources, {len(raw)} buffers")
-            ptrs = (vp * max(n, 1))()
-            for i, b in enumerate(raw):
-                if b is None or b.size == 0 or int(sources[i, 1]) == 0:   # no frames given: no byte is read
-                    ptrs[i] = None
-                    continue
-                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"]:
-                    raise ValueError("ingest_resample: a source's bytes are a C-contiguous uint8 array")
-                need = int(sources[i, 0]) + int(sources[i, 1]) * int(sources[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sources[i, 3]), 4)
-                if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_ingest_resample", f"source {i} reads {need} bytes of a buffer of {b.size}")
-                ptrs[i] = b.ctypes.data
+            ptrs = _host_buffers("ingest_resample", "source", "reads", sources, raw, writable=False)
             self._ck(lib().fvad_ingest_resample(self.h, ptrs, rows, n, *tail), "fvad_ingest_resample")
             return
         self._ck(lib().fvad_ingest_resample_device(self.h, vp(raw), int(raw_bytes or 0), rows, n, *tail), "fvad_ingest_resample_device")
@@ -977,19 +953,7 @@ class Context:
         fmt = INGEST_PCM16 if src_pcm16 else INGEST_F32
         rows = sinks.ctypes.data_as(C.POINTER(C.c_uint64))
         if isinstance(out, (list, tuple)):
-            if len(out) != n:
-                raise ValueError(f"egress: {n} sinks, {len(out)} buffers")
-            ptrs = (vp * max(n, 1))()
-            for i, b in enumerate(out):
-                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no frames: no byte is written, whatever byte_offset says
-                    ptrs[i] = None
-                    continue
-                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
-                    raise ValueError("egress: a sink's bytes are a writable C-contiguous uint8 array")
-                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
-                if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress", f"sink {i} writes {need} bytes of a buffer of {b.size}")
-                ptrs[i] = b.ctypes.data
+            ptrs = _host_buffers("egress", "sink", "writes", sinks, out, writable=True)
             self._ck(lib().fvad_egress(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, ptrs), "fvad_egress")
             return
         self._ck(lib().fvad_egress_device(self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, vp(out), int(out_bytes or 0)),
@@ -1009,19 +973,7 @@ class Context:
         head = (self.h, vp(d_orig), orig_stride, orig_samples, vp(d_den), den_stride, den_samples, INGEST_PCM16 if src_pcm16 else INGEST_F32,
                 n_lanes, float(w_orig), float(w_den), rows, n)
         if isinstance(out, (list, tuple)):
-            if len(out) != n:
-                raise ValueError(f"egress_mix: {n} sinks, {len(out)} buffers")
-            ptrs = (vp * max(n, 1))()
-            for i, b in enumerate(out):
-                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no frames: no byte is written, whatever byte_offset says
-                    ptrs[i] = None
-                    continue
-                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
-                    raise ValueError("egress_mix: a sink's bytes are a writable C-contiguous uint8 array")
-                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
-                if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, "fvad_egress_mix", f"sink {i} writes {need} bytes of a buffer of {b.size}")
-                ptrs[i] = b.ctypes.data
+            ptrs = _host_buffers("egress_mix", "sink", "writes", sinks, out, writable=True)
             self._ck(lib().fvad_egress_mix(*head, ptrs), "fvad_egress_mix")
             return
         self._ck(lib().fvad_egress_mix_device(*head, vp(out), int(out_bytes or 0)), "fvad_egress_mix_device")
@@ -1052,19 +1004,7 @@ class Context:
         taps = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
         head = (self.h, vp(d_lanes), fmt, n_lanes, lane_stride, n_samples, rows, n, up, down, fptr(taps), taps.shape[0]) + step
         if isinstance(out, (list, tuple)):
-            if len(out) != n:
-                raise ValueError(f"egress_resample: {n} rows, {len(out)} buffers")
-            ptrs = (vp * max(n, 1))()
-            for i, b in enumerate(out):
-                if b is None or b.size == 0 or int(sinks[i, 1]) == 0:   # no outputs: no byte is written, whatever byte_offset says
-                    ptrs[i] = None
-                    continue
-                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or not b.flags["WRITEABLE"]:
-                    raise ValueError("egress_resample: a row's bytes are a writable C-contiguous uint8 array")
-                need = int(sinks[i, 0]) + int(sinks[i, 1]) * int(sinks[i, 2]) * INGEST_SAMPLE_BYTES.get(int(sinks[i, 3]), 4)
-                if need > b.size:   # (the library cannot know where a host buffer ends)
-                    raise FvadError(FVAD_ERR_OUT_OF_RANGE, name, f"row {i} writes {need} bytes of a buffer of {b.size}")
-                ptrs[i] = b.ctypes.data
+            ptrs = _host_buffers("egress_resample", "row", "writes", sinks, out, writable=True, where=name)
             self._ck(getattr(lib(), name)(*head, ptrs), name)
             return
         self._ck(getattr(lib(), name + "_device")(*head, vp(out), int(out_bytes or 0)), name + "_device")
@@ -1942,6 +1882,28 @@ def _ingest_rows(sources):
 def ingest_tile_frames(n_channels, fmt):
     """frames of a source per workgroup of the ingest kernel: INGEST_TILE_BYTES rounded down to whole frames, in fours"""
     return INGEST_TILE_BYTES // (n_channels * INGEST_SAMPLE_BYTES[fmt]) // 4 * 4
+
+
+def _host_buffers(call, noun, verb, rows, bufs, writable, where=None):
+    """The per-row host buffers of a host-form call (`call`: the method's name; `where`: the C call in an FvadError, fvad_<call>
+    unless given) -> the pointer array the library takes.  A row without frames gets None: no byte of it is read or written,
+    whatever its byte_offset says.  Every other buffer is a C-contiguous uint8 array (`writable` for the calls that write) that
+    holds what the row `verb`s -- the library cannot know where a host buffer ends."""
+    n = rows.shape[0]
+    if len(bufs) != n:
+        raise ValueError(f"{call}: {n} {noun}s, {len(bufs)} buffers")
+    ptrs = (vp * max(n, 1))()
+    for i, b in enumerate(bufs):
+        if b is None or b.size == 0 or int(rows[i, 1]) == 0:
+            ptrs[i] = None
+            continue
+        if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"] or (writable and not b.flags["WRITEABLE"]):
+            raise ValueError(f"{call}: a {noun}'s bytes are a {'writable ' if writable else ''}C-contiguous uint8 array")
+        need = int(rows[i, 0]) + int(rows[i, 1]) * int(rows[i, 2]) * INGEST_SAMPLE_BYTES.get(int(rows[i, 3]), 4)
+        if need > b.size:
+            raise FvadError(FVAD_ERR_OUT_OF_RANGE, where or "fvad_" + call, f"{noun} {i} {verb} {need} bytes of a buffer of {b.size}")
+        ptrs[i] = b.ctypes.data
+    return ptrs
 
 
 def ingest_check(sources, raw_bytes, out_pcm16, n_lanes, lane_stride, n_samples):

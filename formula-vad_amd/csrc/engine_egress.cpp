@@ -5,9 +5,9 @@
 //                                  the tile is egress_resample.h's)
 //   fvad_egress_resample_strided*  the same over a stream that lies src_step apart in its lanes (host_egress_strided.cpp)
 //   fvad_egress_mix*               two sets of f32 lanes, weighted and summed (kernels_egress_mix.hip; host_egress_mix.cpp)
-// What the forms share is written once: the tables a launch searches, the device form's upload-launch-wait, and, for bytes in
-// host memory, the batches through the two-slot page-locked ring.  A form supplies its row, how a row is cut, the job of a row
-// and the launch of one file format's jobs.
+// What the forms share is written once: the tables a launch searches and the device form's upload-launch-wait (io_tables.h,
+// shared with engine_ingest.cpp) and, for bytes in host memory, the batches through the two-slot page-locked ring (host_form
+// below).  A form supplies its row, how a row is cut, the job of a row and the launch of one file format's jobs.
 // The ring is fvad_ingest's own (Workspace::IngestRing, sized by the context option ingest_ring_bytes), SHARED, not a second
 // one: every one of these calls returns only when its last batch is done, so the ring is idle whenever one starts, a slot of
 // it is what a call here needs as well -- one contiguous device image, its page-locked twin and room for a batch's tables
@@ -20,6 +20,7 @@
 #include "egress_mix.h"
 #include "egress_strided.h"
 #include "internal.h"
+#include "io_tables.h"
 
 using namespace fvad;
 
@@ -27,112 +28,12 @@ namespace {
 
 static_assert(kEgressResampleTileBytes == (uint64_t)kIngestTileBytes && kEgressResampleWindow == (uint64_t)kClipTile, "egress_resample.h restates the kernel's tile");
 
-size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
-// The rows of the three table layouts, field for field (fvad.h), so that a row is decoded by a copy.  Each begins byte_offset,
-// its count (the frames it writes), n_channels, format.
+// The rows of the three table layouts, field for field (fvad.h), so that a row is decoded by a copy (row<Row>).  Each begins
+// byte_offset, its count (the frames it writes), n_channels, format; the job of a row without frames has 0 tiles, so it gets none.
 struct Sink { uint64_t byte_offset, n_frames, n_channels, format, first_lane, src_offset; };
 struct ResampleRow { uint64_t byte_offset, n_out, n_channels, format, first_lane, src_offset, frame_base, n_frames, stream_frames, out_from; };
 struct MixSink { uint64_t byte_offset, n_frames, n_channels, format, first_lane, src_offset, orig_offset, orig_zeros; };
 static_assert(sizeof(Sink) == FVAD_EGRESS_FIELDS * 8 && sizeof(ResampleRow) == FVAD_EGRESS_RESAMPLE_FIELDS * 8 && sizeof(MixSink) == FVAD_EGRESS_MIX_FIELDS * 8, "fvad.h's rows");
-template <typename Row>
-Row row(const uint64_t* sinks, size_t i)
-{
-    Row r;
-    memcpy(&r, sinks + i * (sizeof(Row) / 8), sizeof(Row));
-    return r;
-}
-
-// The tables of one call or batch: per file format (a launch encodes one) the jobs and their unit prefix, laid out in ONE blob
-// whose parts start on 16-byte boundaries, so that one copy carries them to the device (engine_ingest.cpp's layout).
-struct Tables {
-    struct Set { size_t o_jobs = 0, o_prefix = 0; uint32_t n_jobs = 0, n_units = 0; } set[3];
-    std::vector<char> blob;
-};
-
-// as for the ingest: a launch is one workgroup of 256 lanes per unit and takes fewer than 2^24 units (about 270 GB of output)
-constexpr uint64_t kMaxUnits = (1ull << 24) - 1;
-
-// one format's jobs and the units in front of each (`prefix` gets its last entry here) appended to the blob
-template <typename Job>
-void pack(const std::vector<Job>& jobs, std::vector<uint32_t>& prefix, uint64_t units, Tables::Set& set, std::vector<char>& blob)
-{
-    set.n_jobs = (uint32_t)jobs.size();
-    set.n_units = (uint32_t)units;
-    if (jobs.empty()) return;
-    prefix.push_back((uint32_t)units);
-    set.o_jobs = blob.size();
-    set.o_prefix = set.o_jobs + up16(jobs.size() * sizeof(Job));
-    blob.resize(set.o_prefix + up16(prefix.size() * 4));
-    memcpy(blob.data() + set.o_jobs, jobs.data(), jobs.size() * sizeof(Job));
-    memcpy(blob.data() + set.o_prefix, prefix.data(), prefix.size() * 4);
-}
-
-// make(row, job) fills the job of a row that writes something and returns its tiles.  false: more than kMaxUnits units in one
-// launch.
-template <typename Job, typename Row, typename Make>
-bool build_tables(const std::vector<Row>& rows, uint64_t Row::*count, Make make, Tables& t)
-{
-    t.blob.clear();
-    for (int f = 0; f < 3; ++f) {
-        std::vector<Job> jobs;
-        std::vector<uint32_t> prefix;
-        uint64_t units = 0;
-        for (const Row& s : rows) {
-            if ((int)s.format != f || s.*count == 0) continue; // (a row without frames writes nothing)
-            Job j{};
-            const uint64_t nt = make(s, j);
-            if (nt > kMaxUnits) return false;
-            prefix.push_back((uint32_t)units);
-            jobs.push_back(j);
-            units += nt;
-            if (units > kMaxUnits) return false;
-        }
-        pack(jobs, prefix, units, t.set[f], t.blob);
-    }
-    return true;
-}
-
-// the launches of one set of tables, in the order of the formats (queued on ctx->stream): one(f, set) launches a format's jobs
-template <typename One>
-int launch_tables(const Tables& t, One one)
-{
-    for (int f = 0; f < 3; ++f) {
-        if (!t.set[f].n_units) continue;
-        const int rc = one(f, t.set[f]);
-        if (rc != FVAD_OK) return rc;
-    }
-    return FVAD_OK;
-}
-
-// The device form behind its refusals: the tables of all rows, then one allocation for the tap table (if the form has one)
-// and the tables, the copies, launch(t, d_blob, d_table) and the wait.  `what` names the allocation in its error.
-template <typename Row, typename Job, typename Make, typename Launch>
-int device_form(fvad_ctx* ctx, const std::string& who, const char* what, const uint64_t* sinks, size_t n_sinks, uint64_t Row::*count,
-                const std::vector<float>& table, Make make, Launch launch)
-{
-    std::vector<Row> all(n_sinks);
-    for (size_t i = 0; i < n_sinks; ++i) all[i] = row<Row>(sinks, i);
-    Tables t;
-    if (!build_tables<Job>(all, count, make, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": more than 2^24 tiles in one call: write in batches");
-    if (t.blob.empty()) return FVAD_OK; // nothing to write
-    const size_t o_blob = up16(table.size() * 4);
-    hipSetDevice(ctx->device);
-    char* d = nullptr; // the tap table, then the row tables
-    if (hipMalloc((void**)&d, o_blob + t.blob.size()) != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, FVAD_ERR_ALLOC_FAILED, who + ": hipMalloc of the " + what + " failed"); }
-    auto run = [&]() -> int {
-        if (!table.empty()) FVAD_HIP(ctx, hipMemcpyAsync(d, table.data(), table.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        FVAD_HIP(ctx, hipMemcpyAsync(d + o_blob, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice, ctx->stream));
-        const int rc = launch(t, d + o_blob, reinterpret_cast<const float*>(d));
-        if (rc != FVAD_OK) return rc;
-        FVAD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FVAD_OK;
-    };
-    const int rc = run();
-    if (rc != FVAD_OK) (void)hipStreamSynchronize(ctx->stream);
-    hipFree(d);
-    return rc;
-}
 
 // The rules of a host form see every row's bytes at their absolute host address: two rows of one file, or of overlapping
 // buffers, overlap there.  An address that wraps is saturated, which the range rule then refuses.
@@ -193,7 +94,7 @@ int host_form(fvad_ctx* ctx, const std::string& who, const uint64_t* sinks, size
     };
     auto flush = [&]() -> int {
         if (batch.empty()) return FVAD_OK;
-        if (!build_tables<Job>(batch, count, make, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": more than 2^24 tiles in one batch");
+        if (!build_tables<Job>(batch, make, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": more than 2^24 tiles in one batch");
         if (t.blob.size() > table_room) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, who + ": a batch's tables outgrew the ring"); // (batch_cap keeps them inside)
         // the slot is free: the batch it held was drained while the other slot's was in flight
         memcpy(ring.pin[slot] + o_tables, t.blob.data(), t.blob.size());
@@ -376,7 +277,7 @@ int resampled_device(fvad_ctx* ctx, const std::string& who, const Resampled& r, 
     const int bad = check_resampled(ctx, who, sinks, n_sinks, out_bytes, r, src_format, n_lanes, n_samples);
     if (bad != FVAD_OK) return bad;
     if (n_sinks == 0) return FVAD_OK;
-    return device_form<ResampleRow, EgressResampleJob>(ctx, who, "tables", sinks, n_sinks, &ResampleRow::n_out, resample_table(Taps{r.taps, r.n_taps}, r.q), make_resampled(r),
+    return device_form<ResampleRow, EgressResampleJob>(ctx, who, "write in batches", "tables", sinks, n_sinks, resample_table(Taps{r.taps, r.n_taps}, r.q), make_resampled(r),
                                                        [&](const Tables& t, const char* d_blob, const float* d_table) { return launch_resampled(ctx, r, t, d_blob, d_table, d_out); });
 }
 
@@ -480,7 +381,7 @@ int fvad_egress_device(fvad_ctx* ctx, const void* d_lanes, int src_format, size_
     const int bad = check_plain(ctx, "fvad_egress_device", sinks, n_sinks, out_bytes, l, n_lanes, n_samples);
     if (bad != FVAD_OK) return bad;
     if (n_sinks == 0) return FVAD_OK;
-    return device_form<Sink, EgressJob>(ctx, "fvad_egress_device", "sink tables", sinks, n_sinks, &Sink::n_frames, {}, make_plain(l),
+    return device_form<Sink, EgressJob>(ctx, "fvad_egress_device", "write in batches", "sink tables", sinks, n_sinks, {}, make_plain(l),
                                         [&](const Tables& t, const char* d_blob, const float*) { return launch_plain(ctx, l, t, d_blob, d_out); });
 }
 
@@ -537,7 +438,7 @@ int fvad_egress_mix_device(fvad_ctx* ctx, const void* d_orig, size_t orig_stride
     const int bad = check_mixed(ctx, "fvad_egress_mix_device", sinks, n_sinks, out_bytes, src_format, l);
     if (bad != FVAD_OK) return bad;
     if (n_sinks == 0) return FVAD_OK;
-    return device_form<MixSink, EgressMixJob>(ctx, "fvad_egress_mix_device", "sink tables", sinks, n_sinks, &MixSink::n_frames, {}, make_mixed(l),
+    return device_form<MixSink, EgressMixJob>(ctx, "fvad_egress_mix_device", "write in batches", "sink tables", sinks, n_sinks, {}, make_mixed(l),
                                               [&](const Tables& t, const char* d_blob, const float*) { return launch_mixed(ctx, l, t, d_blob, d_out); });
 }
 

@@ -9,6 +9,9 @@
 #include <vector>
 
 #include "../../include/fvad.h"
+#include "ingest_rules.h"
+
+using namespace fvad;
 
 namespace {
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -16,8 +19,6 @@ uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
 // n bytes at offset `at` of fp; false when the file ends before them
 bool read_at(FILE* fp, uint64_t at, void* out, size_t n) { return fseeko(fp, (off_t)at, SEEK_SET) == 0 && fread(out, 1, n, fp) == n; }
-
-struct Rect { uint64_t lane, from, to; };
 } // namespace
 
 extern "C" {
@@ -81,7 +82,8 @@ int fvad_wav_probe(const char* path, uint64_t* info)
 }
 
 // The order: arguments; then every source's own rules (format and pair, channels, fill_to); then every source's ranges (lanes,
-// fill_to against n_samples, bytes against raw_bytes); then the overlap of two sources' destinations.
+// fill_to against n_samples, bytes against raw_bytes); then the overlap of two sources' destinations -- the last two are
+// ingest_rules.h's, shared with fvad_ingest_resample_check.
 int fvad_ingest_check(const uint64_t* sources, size_t n_sources, uint64_t raw_bytes, int out_format, size_t n_lanes,
                       size_t lane_stride, size_t n_samples)
 {
@@ -98,29 +100,9 @@ int fvad_ingest_check(const uint64_t* sources, size_t n_sources, uint64_t raw_by
         if (n_channels < 1 || n_channels > 64) return FVAD_ERR_INVALID_ARGUMENT;
         if (n_frames > UINT64_MAX - dst_offset || fill_to < dst_offset + n_frames) return FVAD_ERR_INVALID_ARGUMENT;
     }
-    size_t n_rects = 0;
-    for (size_t i = 0; i < n_sources; ++i) {
-        const uint64_t* r = sources + i * FVAD_INGEST_FIELDS;
-        const uint64_t byte_offset = r[0], n_frames = r[1], n_channels = r[2], format = r[3], first_lane = r[4], fill_to = r[6];
-        if (first_lane >= n_lanes || n_channels > n_lanes - first_lane) return FVAD_ERR_OUT_OF_RANGE;
-        if (fill_to > n_samples) return FVAD_ERR_OUT_OF_RANGE;
-        const uint64_t frame_bytes = n_channels * (format == FVAD_INGEST_PCM16 ? 2u : format == FVAD_INGEST_PCM24 ? 3u : 4u);
-        if (n_frames > UINT64_MAX / frame_bytes) return FVAD_ERR_OUT_OF_RANGE;
-        if (byte_offset > raw_bytes || n_frames * frame_bytes > raw_bytes - byte_offset) return FVAD_ERR_OUT_OF_RANGE;
-        if (fill_to > r[5]) n_rects += (size_t)n_channels;
-    }
-    // two sources may not write one sample: the order of the writes would decide the result.  Per lane, the ranges sorted by
-    // their start must not reach into their successors.
-    std::vector<Rect> rects;
-    rects.reserve(n_rects);
-    for (size_t i = 0; i < n_sources; ++i) {
-        const uint64_t* r = sources + i * FVAD_INGEST_FIELDS;
-        if (r[6] <= r[5]) continue; // writes nothing
-        for (uint64_t c = 0; c < r[2]; ++c) rects.push_back({r[4] + c, r[5], r[6]});
-    }
-    std::sort(rects.begin(), rects.end(), [](const Rect& x, const Rect& y) { return x.lane != y.lane ? x.lane < y.lane : x.from < y.from; });
-    for (size_t k = 1; k < rects.size(); ++k)
-        if (rects[k].lane == rects[k - 1].lane && rects[k].from < rects[k - 1].to) return FVAD_ERR_INVALID_ARGUMENT;
+    const int rc = ingest_ranges_check(sources, n_sources, FVAD_INGEST_FIELDS, raw_bytes, n_lanes, n_samples);
+    if (rc != FVAD_OK) return rc;
+    if (!ingest_rows_disjoint(sources, n_sources, FVAD_INGEST_FIELDS)) return FVAD_ERR_INVALID_ARGUMENT;
     return FVAD_OK;
 }
 

@@ -3,6 +3,7 @@
 // calls.  Plain C++ without HIP headers (tests/sanitize/resample_san.cpp builds this file alone).
 #include <algorithm>
 
+#include "ingest_rules.h"
 #include "resample.h"
 
 using namespace fvad;
@@ -23,8 +24,6 @@ double bessel_i0(double x)
 }
 
 const double kPi = 3.14159265358979323846;
-
-struct Rect { uint64_t lane, from, to; };
 
 } // namespace
 
@@ -97,7 +96,7 @@ uint64_t fvad_ingest_resample_tile(uint32_t up, uint32_t down, uint32_t n_taps, 
 // The order: arguments (lane format, ratio, taps, sources, lane_stride); then every source's own rules (format, channels, the
 // file's length, the outputs against the file, fill_to, the given frames against the file and against the window, the tile);
 // then every source's ranges (lanes, fill_to against n_samples, bytes against raw_bytes); then the overlap of two sources'
-// destinations.
+// destinations (both ingest_rules.h's, shared with fvad_ingest_check).
 int fvad_ingest_resample_check(const uint64_t* sources, size_t n_sources, uint64_t raw_bytes, uint32_t up, uint32_t down,
                                const float* taps, uint32_t n_taps, int out_format, size_t n_lanes, size_t lane_stride, size_t n_samples)
 {
@@ -124,28 +123,9 @@ int fvad_ingest_resample_check(const uint64_t* sources, size_t n_sources, uint64
         if (hi > lo && (frame_base > lo || frame_base + n_frames < hi)) return FVAD_ERR_INVALID_ARGUMENT; // the slice would not be the file
         if (resample_tile(q, n_taps, n_channels, format) == 0) return FVAD_ERR_INVALID_ARGUMENT;         // taps too long for frames this wide
     }
-    size_t n_rects = 0;
-    for (size_t i = 0; i < n_sources; ++i) {
-        const uint64_t* r = sources + i * FVAD_RESAMPLE_FIELDS;
-        const uint64_t byte_offset = r[0], n_frames = r[1], n_channels = r[2], format = r[3], first_lane = r[4], fill_to = r[6];
-        if (first_lane >= n_lanes || n_channels > n_lanes - first_lane) return FVAD_ERR_OUT_OF_RANGE;
-        if (fill_to > n_samples) return FVAD_ERR_OUT_OF_RANGE;
-        const uint64_t frame_bytes = n_channels * sample_bytes_of(format);
-        if (n_frames > UINT64_MAX / frame_bytes) return FVAD_ERR_OUT_OF_RANGE;
-        if (byte_offset > raw_bytes || n_frames * frame_bytes > raw_bytes - byte_offset) return FVAD_ERR_OUT_OF_RANGE;
-        if (fill_to > r[5]) n_rects += (size_t)n_channels;
-    }
-    // two sources may not write one sample (fvad_ingest_check's rule)
-    std::vector<Rect> rects;
-    rects.reserve(n_rects);
-    for (size_t i = 0; i < n_sources; ++i) {
-        const uint64_t* r = sources + i * FVAD_RESAMPLE_FIELDS;
-        if (r[6] <= r[5]) continue; // writes nothing
-        for (uint64_t c = 0; c < r[2]; ++c) rects.push_back({r[4] + c, r[5], r[6]});
-    }
-    std::sort(rects.begin(), rects.end(), [](const Rect& x, const Rect& y) { return x.lane != y.lane ? x.lane < y.lane : x.from < y.from; });
-    for (size_t k = 1; k < rects.size(); ++k)
-        if (rects[k].lane == rects[k - 1].lane && rects[k].from < rects[k - 1].to) return FVAD_ERR_INVALID_ARGUMENT;
+    const int rc = ingest_ranges_check(sources, n_sources, FVAD_RESAMPLE_FIELDS, raw_bytes, n_lanes, n_samples);
+    if (rc != FVAD_OK) return rc;
+    if (!ingest_rows_disjoint(sources, n_sources, FVAD_RESAMPLE_FIELDS)) return FVAD_ERR_INVALID_ARGUMENT;
     return FVAD_OK;
 }
 

@@ -1,9 +1,13 @@
 // ingest_device.h -- device helpers shared by the ingest kernels (kernels_ingest.hip, kernels_ingest_resample.hip): the search of
-// a prefix table, the samples of the three source formats read from staged LDS bytes, and the 16-byte destination groups.
+// a prefix table, the samples of the three source formats read from staged LDS bytes, and the 16-byte destination groups; then
+// what a workgroup of either kernel begins with -- its unit, the fill tile -- and the source formats' samples as f32.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "kernels.h"    // kIngestFillTile
+#include "stage_tile.h" // kStageThreads
 
 // the job whose units [prefix[j], prefix[j + 1]) hold unit u (prefix[0] = 0, prefix[n] > u; every job has at least one unit)
 __device__ inline uint32_t find_job(const uint32_t* __restrict__ prefix, uint32_t n, uint32_t u)
@@ -63,3 +67,36 @@ __device__ inline void store_group(E* p, int n, int g, F sample)
         for (int i = max(lo, 0); i < min(hi, n); ++i) p[i] = sample(i);
     }
 }
+
+// The unit of workgroup u: the job whose units hold it (find_job), returned as a copy, and *r, its number within the job --
+// data tile r for r < n_data_tiles, else a fill tile (kernels.h).  (The job is read before the prefix entry: both scalar loads
+// are then in flight together.)
+template <typename Job>
+__device__ inline Job find_unit(const Job* __restrict__ jobs, const uint32_t* __restrict__ prefix, uint32_t n_jobs, uint32_t u, uint32_t* r)
+{
+    const uint32_t ji = find_job(prefix, n_jobs, u);
+    const Job j = jobs[ji];
+    *r = u - prefix[ji];
+    return j;
+}
+
+// Fill tile q (= r - n_data_tiles) of a job: kIngestFillTile zeros, or what is left of fill_len, of ONE lane behind the `count`
+// samples the job writes there, as store_group runs of E.  lanes: the job's sample 0 of channel 0.
+template <typename E>
+__device__ inline void fill_tile(E* lanes, uint64_t lane_stride, uint64_t count, uint64_t fill_len, uint32_t n_fill_tiles, uint32_t q)
+{
+    constexpr int G = 16 / (int)sizeof(E);
+    const uint32_t ch = q / n_fill_tiles, k = q % n_fill_tiles;
+    const uint64_t e0 = (uint64_t)k * kIngestFillTile;
+    const int n = (int)min((uint64_t)kIngestFillTile, fill_len - e0);
+    E* p = lanes + (uint64_t)ch * lane_stride + count + e0;
+    const int ng = (n + 2 * G - 2) / G; // groups a run of n can touch, whatever its alignment
+    for (int g = threadIdx.x; g < ng; g += kStageThreads) store_group(p, n, g, [](int) { return (E)0; });
+}
+
+// decode_f32<S>: a source sample's integer image (Source<S>::load) as the f32 the lanes hold: PCM16 s / 32768, PCM24
+// s / 8388608 (both exact), f32 its bits
+template <typename S> __device__ inline float decode_f32(int32_t s);
+template <> __device__ inline float decode_f32<int16_t>(int32_t s) { return (float)s * (1.0f / 32768.0f); }
+template <> __device__ inline float decode_f32<Pcm24>(int32_t s) { return (float)s * (1.0f / 8388608.0f); }
+template <> __device__ inline float decode_f32<float>(int32_t s) { return __int_as_float(s); }

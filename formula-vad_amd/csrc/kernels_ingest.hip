@@ -27,10 +27,10 @@ namespace {
 
 constexpr int kThreads = kStageThreads;
 
-// Decode<D, S>: the element stored (E) from the integer image
+// Decode<D, S>: the element stored (E) from the integer image.  Into f32 lanes decode_f32's value; the two pairs of one format
+// move bits as integers (f32: NaN payloads and -0 survive whatever the float unit would do with them).
 template <typename D, typename S> struct Decode;
-template <> struct Decode<float, int16_t> { using E = float; __device__ static E run(int32_t s) { return (float)s * (1.0f / 32768.0f); } };
-template <> struct Decode<float, Pcm24> { using E = float; __device__ static E run(int32_t s) { return (float)s * (1.0f / 8388608.0f); } };
+template <typename S> struct Decode<float, S> { using E = float; __device__ static E run(int32_t s) { return decode_f32<S>(s); } };
 template <> struct Decode<int16_t, int16_t> { using E = int16_t; __device__ static E run(int32_t s) { return (int16_t)s; } };
 template <> struct Decode<float, float> { using E = uint32_t; __device__ static E run(int32_t s) { return (uint32_t)s; } }; // the bits
 
@@ -40,22 +40,11 @@ __device__ inline void ingest_tile(const IngestArgs& a, uint8_t* lds)
     using E = typename Decode<D, S>::E;
     constexpr int G = 16 / (int)sizeof(E);
     constexpr int B = Source<S>::kBytes;
-    const uint32_t u = blockIdx.x;
-    const uint32_t ji = find_job(a.unit_prefix, a.n_jobs, u);
-    const IngestJob j = a.jobs[ji];
-    const uint32_t r = u - a.unit_prefix[ji];
+    uint32_t r;
+    const IngestJob j = find_unit(a.jobs, a.unit_prefix, a.n_jobs, blockIdx.x, &r);
     E* lanes = static_cast<E*>(a.lanes) + j.dst_off;
     const int t = threadIdx.x;
-    if (r >= j.n_data_tiles) { // zeros: one lane's fill tile
-        const uint32_t q = r - j.n_data_tiles;
-        const uint32_t ch = q / j.n_fill_tiles, k = q % j.n_fill_tiles;
-        const uint64_t e0 = (uint64_t)k * kIngestFillTile;
-        const int n = (int)min((uint64_t)kIngestFillTile, j.fill_len - e0);
-        E* p = lanes + (uint64_t)ch * a.lane_stride + j.n_frames + e0;
-        const int ng = (n + 2 * G - 2) / G; // groups a run of n can touch, whatever its alignment
-        for (int g = t; g < ng; g += kThreads) store_group(p, n, g, [](int) { return (E)0; });
-        return;
-    }
+    if (r >= j.n_data_tiles) return fill_tile(lanes, a.lane_stride, j.n_frames, j.fill_len, j.n_fill_tiles, r - j.n_data_tiles);
     const int C = (int)j.n_channels;
     const uint64_t f0 = (uint64_t)r * j.tile_frames;
     const int nfr = (int)min((uint64_t)j.tile_frames, j.n_frames - f0);

@@ -35,32 +35,16 @@ namespace {
 
 constexpr int kThreads = kStageThreads;
 
-template <typename S> __device__ inline float decode(int32_t s);
-template <> __device__ inline float decode<int16_t>(int32_t s) { return (float)s * (1.0f / 32768.0f); }
-template <> __device__ inline float decode<Pcm24>(int32_t s) { return (float)s * (1.0f / 8388608.0f); }
-template <> __device__ inline float decode<float>(int32_t s) { return __int_as_float(s); }
-
 template <typename S>
 __device__ inline void resample_tile(const IngestResampleArgs& a, uint8_t* lds)
 {
     constexpr int G = 4;
     constexpr int B = Source<S>::kBytes;
-    const uint32_t u = blockIdx.x;
-    const uint32_t ji = find_job(a.unit_prefix, a.n_jobs, u);
-    const IngestResampleJob j = a.jobs[ji];
-    const uint32_t r = u - a.unit_prefix[ji];
+    uint32_t r;
+    const IngestResampleJob j = find_unit(a.jobs, a.unit_prefix, a.n_jobs, blockIdx.x, &r);
     float* lanes = a.lanes + j.dst_off;
     const int t = threadIdx.x;
-    if (r >= j.n_data_tiles) { // zeros: one lane's fill tile
-        const uint32_t q = r - j.n_data_tiles;
-        const uint32_t ch = q / j.n_fill_tiles, k = q % j.n_fill_tiles;
-        const uint64_t e0 = (uint64_t)k * kIngestFillTile;
-        const int n = (int)min((uint64_t)kIngestFillTile, j.fill_len - e0);
-        float* p = lanes + (uint64_t)ch * a.lane_stride + j.n_out + e0;
-        const int ng = (n + 2 * G - 2) / G; // groups a run of n can touch, whatever its alignment
-        for (int g = t; g < ng; g += kThreads) store_group(p, n, g, [](int) { return 0.0f; });
-        return;
-    }
+    if (r >= j.n_data_tiles) return fill_tile(lanes, a.lane_stride, j.n_out, j.fill_len, j.n_fill_tiles, r - j.n_data_tiles);
     const int C = (int)j.n_channels, FB = C * B;
     const uint32_t up = a.up, down = a.down, taps_last = a.n_taps - 1; // taps_last = 2 K
     const uint64_t i0 = (uint64_t)r * j.tile_out;
@@ -101,7 +85,7 @@ __device__ inline void resample_tile(const IngestResampleArgs& a, uint8_t* lds)
             const int n_terms = (int)(j_last - j_first) + 1;
             const float* tp = a.table + om + (uint32_t)j_first * up;
             int b = (int)(q - j_first - lo) * FB;
-            for (int k = 0; k < n_terms; ++k, tp += up, b -= FB) acc = __builtin_fmaf(*tp, decode<S>(Source<S>::load(at, b, aligned)), acc);
+            for (int k = 0; k < n_terms; ++k, tp += up, b -= FB) acc = __builtin_fmaf(*tp, decode_f32<S>(Source<S>::load(at, b, aligned)), acc);
             return acc;
         });
     }

@@ -98,6 +98,25 @@ def test_host_form_equals_device_form_however_the_ring_cuts(dev, ring):
         ic.compare(dev.read(), dev.want, f"fvad_ingest, ring {ring}")
 
 
+def test_more_pieces_than_a_batch_holds(dev):
+    # a batch of fvad_ingest takes 4096 sources at most: the table's sources cut at seeded frame boundaries into more rows than
+    # that, so that the pump flushes for the count and not for the bytes.  A piece is a source of its own on its source's lanes,
+    # its bytes and destination moved on by the frames in front of it; only the last piece of a source keeps the fill.
+    rng = np.random.default_rng(4096)
+    src = dev.sources.astype(np.int64)
+    inner = np.concatenate([np.stack([np.full(n - 1, i), np.arange(1, n)], axis=1) for i, n in enumerate(src[:, 1]) if n > 1])
+    chosen = inner[rng.choice(len(inner), 4300, replace=False)]
+    rows = []
+    for i, (byte_offset, n, ch, fmt, first_lane, dst, fill_to) in enumerate(src.tolist()):
+        edges = [0] + sorted(chosen[chosen[:, 0] == i, 1].tolist()) + [n]
+        for a, b in zip(edges[:-1], edges[1:]):
+            rows.append((byte_offset + a * ch * ic.SAMPLE_BYTES[fmt], b - a, ch, fmt, first_lane, dst + a, fill_to if b == n else dst + b))
+    assert len(rows) == len(src) + 4300 > 4096
+    dev.fill()
+    dev.host_form(np.array(rows, np.uint64))
+    ic.compare(dev.read(), dev.want, f"fvad_ingest, {len(rows)} pieces")
+
+
 def test_order_batching_and_reruns_change_nothing(dev):
     dev.fill()
     dev.device_form(dev.sources[::-1])

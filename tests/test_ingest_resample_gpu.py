@@ -123,6 +123,24 @@ def test_host_form_equals_device_form_however_the_ring_cuts(dev, ring):
         ic.compare(dev.read(), base, f"fvad_ingest_resample, ring {ring}")
 
 
+@pytest.mark.parametrize("dev", PARAMS[:1], indirect=True, ids=["{}-{}-half{}-{}".format(*PARAMS[0])])   # (the shortest filter)
+def test_more_slices_than_a_batch_holds(dev):
+    # a batch of fvad_ingest_resample takes 2048 sources at most: the rows cut at seeded outputs into more slices than that,
+    # each given exactly its window, through the default ring -- the pump flushes for the count and not for the bytes
+    base = dev.first()
+    rng = np.random.default_rng(2048)
+    big = [i for i, row in enumerate(dev.rows) if int(row[10]) >= 8]
+    inner = np.concatenate([np.stack([np.full(int(dev.rows[i][10]) - 1, i), int(dev.rows[i][9]) + np.arange(1, int(dev.rows[i][10]))], axis=1) for i in big])
+    chosen = inner[rng.choice(len(inner), 2200, replace=False)]
+    rows = []
+    for i, row in enumerate(dev.rows):
+        rows += rc.slices(row, sorted(chosen[chosen[:, 0] == i, 1].tolist()), dev.up, dev.down, dev.n_taps)
+    assert len(rows) == len(dev.rows) + 2200 > 2048
+    dev.fill()
+    dev.host_form(rows)
+    ic.compare(dev.read(), base, f"fvad_ingest_resample, {len(rows)} slices")
+
+
 def test_order_company_and_reruns_change_nothing(dev):
     base = dev.first()
     dev.fill()

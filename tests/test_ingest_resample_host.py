@@ -300,3 +300,67 @@ def test_a_wrong_walk_fails_compare():
     for wrong in (rc.resample_model(x, taps[::-1], up, down, 0, 300)[0], np.roll(y, 1, axis=1), y + 1e-6 * B):
         with pytest.raises(AssertionError):
             rc.compare(wrong.astype(np.float32), y, B, up, taps.size)
+
+
+# ---------------------------------------------------------------- the rules fvad_ingest_check and this check share
+def _shared_rule_tables(seed, n_tables):
+    """seeded random calls -> (sources [n][7], raw_bytes, n_lanes, lane_stride, n_samples): mostly valid layouts (sources on
+    lanes of their own, inside the samples and the bytes), each field now and then replaced by a value one of the shared rules
+    refuses or that sits near a wrap"""
+    rng = np.random.default_rng(seed)
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    near_max = lambda: U64_MAX - int(rng.integers(0, 51))
+    for _ in range(n_tables):
+        n_sources = int(rng.integers(1, 4))
+        n_samples = int(rng.integers(8, 200))
+        n_lanes = int(rng.integers(1, 10))
+        lane_stride = n_samples - 1 if rng.random() < 0.04 else n_samples + int(rng.integers(0, 3))
+        raw_bytes = U64_MAX if rng.random() < 0.1 else int(rng.integers(0, 4000))
+        rows, lane, at = [], 0, 0
+        for _ in range(n_sources):
+            ch = int(rng.integers(1, 4))
+            fmt = int(rng.integers(0, 3))
+            dst = int(rng.integers(0, n_samples))
+            n = int(rng.integers(0, n_samples - dst + 1))
+            fill = int(rng.integers(0, n_samples - dst - n + 1))
+            first_lane = lane if rng.random() < 0.8 else int(rng.integers(0, n_lanes))   # (the others may overlap a neighbour)
+            lane += ch
+            byte_offset = at + int(rng.integers(0, 5))
+            at = byte_offset + n * ch * rc.SAMPLE_BYTES[fmt]
+            fill_to = dst + n + fill
+            if rng.random() < 0.05:
+                ch = pick((0, 65, 64))
+            if rng.random() < 0.04:
+                fmt = 3
+            if rng.random() < 0.05:
+                n = pick((1 << 61, int(rng.integers(1 << 32, 1 << 61)), (1 << 61) - 1))
+            if rng.random() < 0.05:
+                fill_to = (dst + n - 1) % (1 << 64)                       # short by one (n == 0 at 0: wraps)
+            if rng.random() < 0.05:
+                first_lane = pick((n_lanes, n_lanes + 1, U64_MAX, max(n_lanes - ch + 1, 0)))
+            if rng.random() < 0.04:
+                dst, fill_to = near_max(), near_max()
+            if rng.random() < 0.04:
+                byte_offset = near_max()
+            if rng.random() < 0.04:
+                fill_to = n_samples + 1
+            rows.append((byte_offset, n, ch, fmt, first_lane, dst, fill_to))
+        if rng.random() < 0.5:
+            raw_bytes = max(raw_bytes, at) - (1 if rng.random() < 0.1 else 0)
+        yield np.array(rows, np.uint64), raw_bytes, n_lanes, lane_stride, n_samples
+
+
+def test_the_shared_rules_give_both_checks_one_status(fv):
+    # up = down = 1 with the single tap 1.0, a whole-file row (frame_base 0, file_frames = n_out = n_frames, out_from 0): every
+    # rule of the resample check that fvad_ingest_check does not have passes (n_frames <= 2^61 keeps file_frames * up below
+    # 2^62), so the two checks see the same arguments, rules and order -- and must answer alike, table by table
+    seen = {OK: 0, INVALID: 0, RANGE: 0}
+    one = np.ones(1, np.float32)
+    for sources, raw_bytes, n_lanes, lane_stride, n_samples in _shared_rule_tables(20261021, 4000):
+        n = sources[:, 1:2]
+        rrows = np.concatenate([sources, np.zeros_like(n), n, np.zeros_like(n), n], axis=1)
+        plain = fv.ingest_check(sources, raw_bytes, False, n_lanes, lane_stride, n_samples)
+        resampled = fv.ingest_resample_check(rrows, raw_bytes, 1, 1, one, n_lanes, lane_stride, n_samples)
+        assert plain == resampled, (sources.tolist(), raw_bytes, n_lanes, lane_stride, n_samples, plain, resampled)
+        seen[plain] += 1
+    assert min(seen.values()) >= 20, seen
