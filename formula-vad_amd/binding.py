@@ -31,6 +31,7 @@ CLIP_STEP_MAX = 16               # the largest step of the strided clip exports
 CLIP_FIR_TAPS_MAX = 513          # the most taps of the filtered clip exports
 CLIP_MEL_NFFT_MAX = 2048         # the largest n_fft of the log-mel clip exports
 CLIP_MEL_BANDS_MAX = 128         # the most mel bands of the log-mel clip exports
+FLT_EPSILON = float(2.0 ** -23)  # Kaldi's floor of a filter-bank energy
 INGEST_F32, INGEST_PCM16, INGEST_PCM24 = 0, 1, 2   # source formats of fvad_ingest* (the first two are CLIP_*'s values)
 INGEST_FIELDS = 7                # a source: byte_offset, n_frames, n_channels, format, first_lane, dst_offset, fill_to (uint64 each)
 WAV_INFO_FIELDS = 6              # fvad_wav_probe: format, n_channels, sample_rate, data_offset, n_frames, bits
@@ -386,6 +387,21 @@ SIGNATURES = {
                                         c_float_p, c_float_p, C.POINTER(C.c_uint64),
                                                C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
                                                C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_mel_design_kaldi": (C.c_int, [C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double, c_float_p]),
+    "fvad_clips_plan_fbank": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_fbank_check": (C.c_int, [vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.c_int, C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                         C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_fbank_device": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                                 c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                                 C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                                 C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_export_fbank": (C.c_int, [vp, vp, C.c_int, sz, sz, sz, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.POINTER(C.c_int32),
+                                          c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                          C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                          C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint64), c_float_p]),
     "fvad_clips_resample_check": (C.c_int, [C.c_uint32, C.c_uint32, c_float_p, C.c_uint32]),
     "fvad_clips_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "fvad_clips_plan_resampled": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
@@ -832,6 +848,41 @@ class Context:
         out = np.zeros(max(total, 1), np.float32)
         self._ck(lib().fvad_clips_export_mel(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
                  "fvad_clips_export_mel")
+        res["out"] = out[:total]
+        return res
+
+    def clips_export_fbank(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, n_fft=512, step=1, skips=None,
+                           hop=160, scale=32768.0, preemph=0.97, remove_dc=True, floor=FLT_EPSILON, cmn=False, d_out=None, out_capacity=None):
+        """fvad_clips_export_fbank (d_out None: the features come back as a float32 array) or fvad_clips_export_fbank_device:
+        Kaldi-style filter-bank features of the clips' picked channels.  window: [win_length] float32, matrix:
+        [n_mels][n_fft / 2 + 1] float32.
+        Returns dict(best_channel, best_rms, runner_up_rms, offsets, total, n_frames, means[, out]); clip i's features are
+        out[offsets[i] : offsets[i] + n_frames[i] * n_mels].reshape(n_frames[i], n_mels), means[i] its per-band mean."""
+        clips = _clip_rows(clips)
+        n = clips.shape[0]
+        window = np.ascontiguousarray(np.asarray(window, np.float32).reshape(-1))
+        matrix = np.ascontiguousarray(np.asarray(matrix, np.float32))
+        win, n_mels = window.shape[0], matrix.shape[0]
+        if matrix.ndim != 2 or matrix.shape[1] != n_fft // 2 + 1:
+            raise ValueError("matrix must be [n_mels][n_fft / 2 + 1]")
+        skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+        frames, offsets, total = clips_plan_fbank(clips[:, 3] - clips[:, 2], skips, step, win, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
+        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
+        n_frames, means = np.zeros(n, np.uint64), np.zeros((n, n_mels), np.float32)
+        args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
+                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
+        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), win, int(n_fft), hop, fptr(window), n_mels,
+                fptr(matrix), scale, preemph, int(remove_dc), floor, int(cmn), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(means))
+        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "n_frames": n_frames,
+               "means": means}
+        if d_out is not None:
+            self._ck(lib().fvad_clips_export_fbank_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
+                     "fvad_clips_export_fbank_device")
+            return res
+        out = np.zeros(max(total, 1), np.float32)
+        self._ck(lib().fvad_clips_export_fbank(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
+                 "fvad_clips_export_fbank")
         res["out"] = out[:total]
         return res
 
@@ -1843,6 +1894,47 @@ def clips_mel_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, o
                                     None if keep[0] is None else fptr(keep[0]), int(n_mels), None if keep[1] is None else fptr(keep[1]),
                                     floor, None if keep[2] is None else fptr(keep[2]), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
                                     offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    return st, n_frames[:n], offsets[:n], int(total.value)
+
+
+def mel_design_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq):
+    """fvad_mel_design_kaldi: Kaldi's mel bank [n_mels][n_fft / 2 + 1] float32 (HTK mel, triangles in the mel domain, no
+    normalisation, a zero Nyquist column); high_freq <= 0 counts from Nyquist"""
+    matrix = np.zeros((max(int(n_mels), 1), max(int(n_fft), 0) // 2 + 1), np.float32)
+    check(lib().fvad_mel_design_kaldi(sample_rate, int(n_fft), int(n_mels), low_freq, high_freq, fptr(matrix)), "fvad_mel_design_kaldi")
+    return matrix
+
+
+def clips_plan_fbank(lens, skips, step, win_length, hop, n_mels):
+    """fvad_clips_plan_fbank: (n_frames [n] uint64, offsets [n] uint64, total), offsets and total in floats; skips None: 0"""
+    lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
+    n = lens.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
+    n_frames, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
+    check(lib().fvad_clips_plan_fbank(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(step), int(win_length),
+                                      int(hop), int(n_mels), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_fbank")
+    return n_frames, offsets, int(total.value)
+
+
+def clips_fbank_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, win_length,
+                      n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, out_format=CLIP_F32):
+    """fvad_clips_fbank_check (host only; d_src and out are addresses) -> (status, n_frames, offsets, total).  window and matrix
+    are float32 arrays or None (NULL), passed as they are"""
+    clips = None if clips is None else _clip_rows(clips)
+    n = 0 if clips is None else clips.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
+    keep = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix)]
+    n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
+    st = lib().fvad_clips_fbank_check(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
+                                      None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
+                                      out_capacity, int(device_out), int(step),
+                                      None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), int(win_length), int(n_fft),
+                                      int(hop), None if keep[0] is None else fptr(keep[0]), int(n_mels),
+                                      None if keep[1] is None else fptr(keep[1]), scale, preemph, int(remove_dc), floor, int(cmn),
+                                      n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      C.byref(total))
     return st, n_frames[:n], offsets[:n], int(total.value)
 
 

@@ -14,10 +14,14 @@
 //   (kernels_clips_fir.hip) and resampled (kernels_clips_resample.hip); the form's part is its taps as the gather walks them.
 // - fvad_clips_export_mel*: log-mel features of the picked channel's strided stream (kernels_clips_mel.hip) in place of a
 //   gather; rules in clips_mel.h, shared with the host-only fvad_clips_mel_check; parts: window, matrix and the maxima.
+// - fvad_clips_export_fbank*: Kaldi-style filter-bank features of the same stream, by the same kernel file; rules in
+//   clips_fbank.h, shared with the host-only fvad_clips_fbank_check; parts: window, matrix, the tiles' sums and the means.
+#include <algorithm>
 #include <cmath>
 #include <type_traits>
 #include <vector>
 
+#include "clips_fbank.h"
 #include "clips_mel.h"
 #include "clips_split.h"
 #include "internal.h"
@@ -381,6 +385,39 @@ struct MelCall {
     float* feat_max;
 };
 
+// the matrix as the kernels read it: [bin][band]
+std::vector<float> bands_transposed(const float* matrix, uint32_t n_mels, uint32_t n_bins)
+{
+    std::vector<float> t((size_t)n_bins * n_mels);
+    for (uint32_t b = 0; b < n_mels; ++b)
+        for (uint32_t k = 0; k < n_bins; ++k) t[(size_t)k * n_mels + b] = matrix[(size_t)b * n_bins + k];
+    return t;
+}
+
+// the tables of a feature call: one gather tile per tf frames of a clip
+bool feature_tables(const Lanes& s, const uint32_t* skips, const std::vector<uint64_t>& offsets, const std::vector<uint64_t>& frames, uint32_t tf, ClipTables& t)
+{
+    const auto desc = [&](size_t i) {
+        const ClipRow c = row(s.clips, i);
+        return ClipDesc{c.sample_to - c.sample_from, c.n_channels, c.first_lane * (uint64_t)s.lane_stride + c.sample_from, offsets[i], (frames[i] + tf - 1) / tf, skips ? skips[i] : 0, {}};
+    };
+    return build_tables(s.n_clips, false, desc, t);
+}
+
+// what both feature forms put into ClipMelArgs the same way; x[0] and x[1] are the window and the transposed matrix
+void feature_args(ClipMelArgs& a, const ClipArgs& c, const Part* x, uint32_t step, uint32_t hop, uint32_t n_mels, uint32_t tf, float floor, float log_floor)
+{
+    a.c = c;
+    a.window = reinterpret_cast<const float*>(x[0].dev);
+    a.matrix_t = reinterpret_cast<const float*>(x[1].dev);
+    a.step = step;
+    a.hop = hop;
+    a.n_mels = n_mels;
+    a.tile_frames = tf;
+    a.floor = floor;
+    a.log_floor = log_floor;
+}
+
 int mel_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
@@ -394,15 +431,8 @@ int mel_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& m
     const Mel& m = mc.m;
     const uint32_t tf = clip_mel_tile_frames(m.n_fft, m.hop), n_bins = m.n_fft / 2 + 1;
     ClipTables t;
-    const auto desc = [&](size_t i) {
-        const ClipRow c = row(s.clips, i);
-        return ClipDesc{c.sample_to - c.sample_from, c.n_channels, c.first_lane * (uint64_t)s.lane_stride + c.sample_from, offsets[i], (frames[i] + tf - 1) / tf, m.skips ? m.skips[i] : 0, {}};
-    };
-    if (!build_tables(s.n_clips, false, desc, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_mel: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
-    // the matrix as the kernels read it: [bin][band]
-    std::vector<float> matrix_t((size_t)n_bins * m.n_mels);
-    for (uint32_t b = 0; b < m.n_mels; ++b)
-        for (uint32_t k = 0; k < n_bins; ++k) matrix_t[(size_t)k * m.n_mels + b] = mc.matrix[(size_t)b * n_bins + k];
+    if (!feature_tables(s, m.skips, offsets, frames, tf, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_mel: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
+    const std::vector<float> matrix_t = bands_transposed(mc.matrix, m.n_mels, n_bins);
 
     hipSetDevice(ctx->device);
     ClipMelArgs a{};
@@ -415,17 +445,9 @@ int mel_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& m
                                      {nullptr, nullptr, t.tiles * sizeof(float), nullptr},
                                      {nullptr, fmax.data(), s.n_clips * sizeof(float), nullptr}};
     auto features = [&](const ClipArgs& c, const Part* x) -> int {
-        a.c = c;
-        a.window = reinterpret_cast<const float*>(x[kWindow].dev);
-        a.matrix_t = reinterpret_cast<const float*>(x[kMatrix].dev);
+        feature_args(a, c, x, m.step, m.hop, m.n_mels, tf, mc.floor, (float)std::log10((double)mc.floor));
         a.tile_max = reinterpret_cast<float*>(x[kTileMax].dev);
         a.feat_max = reinterpret_cast<float*>(x[kFeatMax].dev);
-        a.step = m.step;
-        a.hop = m.hop;
-        a.n_mels = m.n_mels;
-        a.tile_frames = tf;
-        a.floor = mc.floor;
-        a.log_floor = (float)std::log10((double)mc.floor);
         if (mc.norm) { a.norm_range = mc.norm[0]; a.norm_offset = mc.norm[1]; a.norm_scale = mc.norm[2]; }
         a.fft400 = m.n_fft == 400 && !ctx->tune.clip_mel_generic;
         time_begin(ctx, a.fft400 ? "clip_mel400" : "clip_mel");
@@ -462,6 +484,85 @@ int mel_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
     if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_mel: ") + why);
     return via_staging(ctx, "fvad_clips_export_mel", "fvad_clips_export_mel", o.p, (size_t)total * sizeof(float),
                        [&](void* d_out) { return mel_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, mc); });
+}
+
+// ------------------------------------------------------------------ fvad_clips_export_fbank*: Kaldi-style filter-bank features
+
+struct FbankCall {
+    Fbank f;
+    const float* window;
+    const float* matrix;
+    FbankCond c;
+    uint64_t* n_frames; // what the call reports per clip beside ClipReport; each may be NULL
+    float* means;       // [n_clips][n_mels]
+};
+
+int fbank_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FbankCall& fc)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    std::vector<uint64_t> offsets(s.n_clips), frames(s.n_clips);
+    uint64_t total = 0;
+    const char* why = "";
+    const int bad = fbank_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 1, fc.f, fc.window,
+                                fc.matrix, fc.c, frames.data(), offsets.data(), &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_fbank: ") + why);
+    const Fbank& f = fc.f;
+    const uint32_t tf = clip_mel_tile_frames(f.win_length, f.hop), n_bins = f.n_fft / 2 + 1;
+    ClipTables t;
+    if (!feature_tables(s, f.skips, offsets, frames, tf, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_fbank: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
+    const std::vector<float> matrix_t = bands_transposed(fc.matrix, f.n_mels, n_bins);
+
+    hipSetDevice(ctx->device);
+    ClipFbankArgs a{};
+    { const int rc = get_vad_plan(ctx, f.n_fft, &a.m.pl, true); if (rc != FVAD_OK) return rc; }
+    std::vector<float> means(s.n_clips * (size_t)f.n_mels);
+    enum { kWindow, kMatrix, kTileSum, kMeans };
+    const std::vector<Part> parts = {{fc.window, nullptr, f.win_length * sizeof(float), nullptr},
+                                     {matrix_t.data(), nullptr, matrix_t.size() * sizeof(float), nullptr},
+                                     {nullptr, nullptr, t.tiles * f.n_mels * sizeof(float), nullptr},
+                                     {nullptr, means.data(), means.size() * sizeof(float), nullptr}};
+    auto features = [&](const ClipArgs& c, const Part* x) -> int {
+        feature_args(a.m, c, x, f.step, f.hop, f.n_mels, tf, fc.c.floor, (float)std::log((double)fc.c.floor));
+        a.tile_sum = reinterpret_cast<float*>(x[kTileSum].dev);
+        a.means = reinterpret_cast<float*>(x[kMeans].dev);
+        a.win = f.win_length;
+        a.scale = fc.c.scale;
+        a.preemph = fc.c.preemph;
+        a.remove_dc = fc.c.remove_dc;
+        time_begin(ctx, "clip_fbank");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank(a, ctx->stream));
+        time_end(ctx);
+        time_begin(ctx, "clip_fbank_mean");
+        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank_mean(a, ctx->stream));
+        time_end(ctx);
+        if (fc.c.cmn) {
+            time_begin(ctx, "clip_fbank_sub");
+            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank_sub(a, ctx->stream));
+            time_end(ctx);
+        }
+        return FVAD_OK;
+    };
+    const int rc = run_clips(ctx, "fvad_clips_export_fbank", source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
+    if (rc != FVAD_OK) return rc;
+    for (size_t i = 0; i < s.n_clips; ++i)
+        if (fc.n_frames) fc.n_frames[i] = frames[i];
+    if (fc.means) std::copy(means.begin(), means.end(), fc.means);
+    return FVAD_OK;
+}
+
+int fbank_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FbankCall& fc)
+{
+    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
+    if (s.n_clips == 0) return FVAD_OK;
+    // every rule against the caller's own buffer first
+    uint64_t total = 0;
+    const char* why = "";
+    const int bad = fbank_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 0, fc.f, fc.window,
+                                fc.matrix, fc.c, nullptr, nullptr, &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_fbank: ") + why);
+    return via_staging(ctx, "fvad_clips_export_fbank", "fvad_clips_export_fbank", o.p, (size_t)total * sizeof(float),
+                       [&](void* d_out) { return fbank_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, fc); });
 }
 
 // the argument rules of fvad_clips_plan: the full-rate slots
@@ -709,6 +810,29 @@ int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size
     return mel_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                     ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
                     MelCall{Mel{step, skips, n_fft, hop, n_mels}, window, matrix, floor, norm, n_frames, feat_max});
+}
+
+int fvad_clips_export_fbank_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                                   const uint64_t* clips, size_t n_clips, int out_format, void* d_out, size_t out_capacity,
+                                   int32_t* best_channel, float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step,
+                                   const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window,
+                                   uint32_t n_mels, const float* matrix, float scale, float preemph, int remove_dc, float floor, int cmn,
+                                   uint64_t* n_frames, float* means)
+{
+    return fbank_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                        ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                        FbankCall{Fbank{step, skips, win_length, n_fft, hop, n_mels}, window, matrix, FbankCond{scale, preemph, remove_dc, floor, cmn}, n_frames, means});
+}
+
+int fvad_clips_export_fbank(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                            const uint64_t* clips, size_t n_clips, int out_format, void* out, size_t out_capacity, int32_t* best_channel,
+                            float* best_rms, float* runner_up_rms, uint64_t* out_offsets, uint32_t step, const uint32_t* skips,
+                            uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix,
+                            float scale, float preemph, int remove_dc, float floor, int cmn, uint64_t* n_frames, float* means)
+{
+    return fbank_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+                      ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                      FbankCall{Fbank{step, skips, win_length, n_fft, hop, n_mels}, window, matrix, FbankCond{scale, preemph, remove_dc, floor, cmn}, n_frames, means});
 }
 
 } // extern "C"

@@ -533,6 +533,23 @@ int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream);      // (aft
 int fvad_launch_clip_mel_max(const ClipMelArgs& a, hipStream_t stream);  // (after fvad_launch_clip_mel)
 int fvad_launch_clip_mel_norm(const ClipMelArgs& a, hipStream_t stream); // (after fvad_launch_clip_mel_max)
 
+// The Kaldi-style filter-bank features (kernels_clips_mel.hip, fvad_clips_export_fbank*): of the same stream times `scale` the
+// frames t < T = 1 + (L - win) / hop of `win` taps from t * hop on (snip_edges: no tap outside the stream), each with its mean
+// removed, pre-emphasised, windowed and zero-padded to m.pl.n, then power spectrum -> bands -> ln.  m is the mel export's, with
+// m.window [win], m.tile_frames = clip_mel_tile_frames(win, hop) and m.log_floor = ln(floor); m.tile_max, m.feat_max and the norm
+// are not used.
+struct ClipFbankArgs {
+    ClipMelArgs m;
+    float* tile_sum;  // [m.c.n_tiles][n_mels]: a tile's features added over ascending t, band by band
+    float* means;     // [m.c.n_clips][n_mels]: the tiles' sums added in tile order, over f32(T) (clip_fbank_mean)
+    uint32_t win;
+    float scale, preemph;
+    int remove_dc;
+};
+int fvad_launch_clip_fbank(const ClipFbankArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
+int fvad_launch_clip_fbank_mean(const ClipFbankArgs& a, hipStream_t stream); // (after fvad_launch_clip_fbank)
+int fvad_launch_clip_fbank_sub(const ClipFbankArgs& a, hipStream_t stream);  // (after fvad_launch_clip_fbank_mean)
+
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in
 // multiples of 4 (tile_frames), every channel of them -- or, after the source's n_data_tiles, kIngestFillTile zeros of one lane

@@ -31,6 +31,12 @@
 // the eight lanes of a frame hit the bank pairs {0, 18, 4, 22, 8, 26, 12, 30} + {0, 1}, the next frame the other sixteen banks
 // (400 = 16 mod 32): 32 lanes x 8 bytes in two cycles, the minimum.  Un-mixing reads, 8 bytes at dword 400 f + 2 a + 16 u and
 // its mirror: 400 = 16 mod 64, four frames x sixteen dwords: conflict-free.
+// The filter-bank export (fvad_clips_export_fbank*) is clip_mel_kernel with kFbank on: frames of `win` taps from t hop on (Kaldi's
+// snip_edges: T = 1 + (L - win) / hop, every tap inside the staged window, so no element-by-element path), the frame conditioned
+// in LDS by the workgroup (fbank_condition: scale at the frame load, the mean in a fixed order, pre-emphasis reading d[i - 1] from
+// LDS) and zero-padded to n_fft, the same generic_rfft call and projection loop, logf; lane m also adds its features over the
+// tile's frames in ascending t.  clip_fbank_mean_kernel adds the tiles' sums in tile order by one lane per (clip, band) and divides
+// by f32(T); clip_fbank_sub_kernel subtracts element-wise.  The parent's instances are kFbank off.
 // Resources (make resource-usage, gfx950): see the table in DESIGN 7.2; clip_mel400_kernel is LDS-bound at two workgroups per
 // CU (73.3 KB each: 177 VGPRs, two wavefronts per SIMD); clip_mel_kernel takes 28.0 KB at 400 / 160 (80 VGPRs, five workgroups per CU).
 #include <hip/hip_runtime.h>
@@ -52,15 +58,18 @@ struct MelTile {
     long long t0, L, w0, w1;
 };
 
-__device__ inline MelTile mel_tile(const ClipMelArgs& a, const ClipJob& j, uint32_t clip)
+// kSnip (the filter-bank export): frames of `win` taps from t hop on, T = 1 + (L - win) / hop of them, none leaving the stream
+template <bool kSnip = false>
+__device__ inline MelTile mel_tile(const ClipMelArgs& a, const ClipJob& j, uint32_t clip, uint32_t win = 0)
 {
     MelTile t;
     t.clip = clip;
     t.L = (long long)((j.len - j.skip + a.step - 1) / a.step);
-    const long long T = t.L / a.hop, pad = a.pl.n / 2;
+    const long long taps = kSnip ? (long long)win : (long long)a.pl.n;
+    const long long T = kSnip ? (t.L - taps) / a.hop + 1 : t.L / a.hop, pad = kSnip ? 0 : a.pl.n / 2;
     t.t0 = (long long)(blockIdx.x - a.c.tile_prefix[clip]) * a.tile_frames;
     t.nf = (int)min((long long)a.tile_frames, T - t.t0);
-    const long long lo = t.t0 * a.hop - pad, hi = (t.t0 + t.nf - 1) * a.hop - pad + a.pl.n;
+    const long long lo = t.t0 * a.hop - pad, hi = (t.t0 + t.nf - 1) * a.hop - pad + taps;
     t.w0 = max(lo, 0ll);
     t.w1 = min(hi, t.L); // w0 <= t0 hop < w1; w1 - w0 <= (nf - 1) hop + n_fft <= kClipTile
     return t;
@@ -99,6 +108,7 @@ __device__ inline MelSrc<S> mel_stage(const ClipMelArgs& a, const ClipJob& j, co
 }
 
 __device__ inline float mel_feat(float mel, float floor, float log_floor) { return mel > floor ? log10f(mel) : log_floor; }
+__device__ inline float fbank_feat(float mel, float floor, float log_floor) { return mel > floor ? logf(mel) : log_floor; }
 
 // a fixed tree: 64 lanes by shuffles, then the four wavefronts in order
 __device__ inline void tile_max_store(float v, float* red, float* dst)
@@ -115,17 +125,63 @@ __host__ __device__ inline uint32_t mel_stage_floats(uint32_t n_fft, uint32_t ho
     return ((tile_frames - 1) * hop + n_fft + 4 + 3) / 4 * 4;
 }
 
+// the dynamic LDS of clip_mel_kernel behind `stage` floats of the window: s_win, s_frame, bufA, bufB, s_pow
+inline size_t mel_generic_lds(uint32_t stage, uint32_t n_fft) { return (size_t)(stage + 2 * n_fft + 4 * (n_fft / 2 + 1) + (n_fft / 2 + 1)) * sizeof(float); }
+
+__device__ inline const ClipMelArgs& mel_args(const ClipMelArgs& a) { return a; }
+__device__ inline const ClipMelArgs& mel_args(const ClipFbankArgs& a) { return a.m; }
+
+// The conditioning of one filter-bank frame by the whole workgroup (fvad.h's order, every operation rounded on its own): x the
+// frame's `win` staged samples, y [n_fft] what generic_rfft windows, d [win] scratch, red one float per wavefront.
+//   x_i = x[i] * scale          -- the scale is applied HERE, at the frame load, not at staging (one rounded product either way)
+//   mean = S / f32(win)         -- with remove_dc.  THE SUM ORDER, fixed by win alone: lane l of the 256 adds x_l, x_{l + 256},
+//                                  x_{l + 512}, ... in ascending order onto 0.0f (a lane at or past win keeps 0.0f); each wavefront
+//                                  folds its 64 sums by v_l += v_{l + o} for o = 32, 16, 8, 4, 2, 1 (lane 0 holds the result);
+//                                  S = ((w_0 + w_1) + w_2) + w_3 over the four wavefronts
+//   d_i = x_i - mean            -- (x_i without remove_dc), written to LDS
+//   y_i = d_i - preemph * d_{i - 1}, d_{-1} = d_0 (Kaldi's replicated first sample); y_i = 0 for win <= i < n_fft
+// Ends with a barrier.
+__device__ inline void fbank_condition(const ClipFbankArgs& a, const float* x, float* y, float* d, float* red)
+{
+    const int tid = threadIdx.x, win = (int)a.win, n_fft = a.m.pl.n;
+    float mean = 0.0f;
+    if (a.remove_dc) {
+        float v = 0.0f;
+        for (int i = tid; i < win; i += kThreads) v += x[i] * a.scale;
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((tid & 63) == 0) red[tid >> 6] = v;
+        __syncthreads();
+        mean = (((red[0] + red[1]) + red[2]) + red[3]) / (float)win;
+    }
+    for (int i = tid; i < win; i += kThreads) {
+        const float xi = x[i] * a.scale;
+        d[i] = a.remove_dc ? xi - mean : xi;
+    }
+    __syncthreads();
+    for (int i = tid; i < n_fft; i += kThreads) y[i] = i < win ? d[i] - a.preemph * d[i > 0 ? i - 1 : 0] : 0.0f;
+    __syncthreads();
+}
+
 } // namespace
 
+// what clip_mel_kernel<S, kFbank> takes: the parent's arguments, or the filter-bank export's around them
+template <bool kFbank> struct MelKernelArgs { using type = ClipMelArgs; };
+template <> struct MelKernelArgs<true> { using type = ClipFbankArgs; };
+
 // ---------------------------------------------------------------------------- any even n_fft
-template <typename S>
-__global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipMelArgs a)
+// kFbank: the filter-bank export's frames (snip_edges, conditioned, win taps zero-padded to n_fft, natural log) and, in place of
+// the tile's maximum, the tile's sum per band over ascending t by lane m
+template <typename S, bool kFbank>
+__global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename MelKernelArgs<kFbank>::type args)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[kThreads / 64];
+    const ClipMelArgs& a = mel_args(args);
     const int n_fft = a.pl.n, M = n_fft / 2, NB = M + 1, pad = M;
+    int taps = n_fft;
+    if constexpr (kFbank) taps = (int)args.win;
     float* s_stage = sm;
-    float* s_win = s_stage + mel_stage_floats(n_fft, a.hop, a.tile_frames);
+    float* s_win = s_stage + mel_stage_floats(taps, a.hop, a.tile_frames);
     float* s_frame = s_win + n_fft;
     cpx* bufA = reinterpret_cast<cpx*>(s_frame + n_fft);
     cpx* bufB = bufA + NB;
@@ -133,15 +189,24 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipMelArgs a)
     const int tid = threadIdx.x;
     const uint32_t clip = find_clip(a.c.tile_prefix, a.c.n_clips, blockIdx.x);
     const ClipJob j = a.c.jobs[clip];
-    const MelTile t = mel_tile(a, j, clip);
-    for (int i = tid; i < n_fft; i += kThreads) s_win[i] = a.window[i];
+    const MelTile t = mel_tile<kFbank>(a, j, clip, taps);
+    if constexpr (kFbank) {
+        for (int i = tid; i < n_fft; i += kThreads) s_win[i] = i < taps ? a.window[i] : 0.0f;
+    } else {
+        for (int i = tid; i < n_fft; i += kThreads) s_win[i] = a.window[i];
+    }
     const MelSrc<S> src = mel_stage<S>(a, j, t, s_stage); // (ends with a barrier)
     float* out = static_cast<float*>(a.c.out) + j.out_off + (unsigned long long)t.t0 * a.n_mels;
-    float vmax = -__builtin_inff();
+    float vmax = -__builtin_inff(), vsum = 0.0f;
     for (int f = 0; f < t.nf; ++f) {
-        const long long j0 = (t.t0 + f) * a.hop - pad;
-        for (int i = tid; i < n_fft; i += kThreads) s_frame[i] = src.at(j0 + i);
-        __syncthreads();
+        if constexpr (kFbank) {
+            // every tap is staged: the tile's window starts at its first frame's first tap (w0 == t0 hop)
+            fbank_condition(args, src.lds + (size_t)f * a.hop, s_frame, reinterpret_cast<float*>(bufB), red);
+        } else {
+            const long long j0 = (t.t0 + f) * a.hop - pad;
+            for (int i = tid; i < n_fft; i += kThreads) s_frame[i] = src.at(j0 + i);
+            __syncthreads();
+        }
         cpx* X;
         generic_rfft(s_frame, s_win, a.pl, bufA, bufB, X); // (ends with a barrier)
         for (int k = tid; k < NB; k += kThreads) s_pow[k] = X[k].r * X[k].r + X[k].i * X[k].i;
@@ -150,13 +215,18 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipMelArgs a)
             const float* mt = a.matrix_t + tid;
             float acc = 0.0f;
             for (int k = 0; k < NB; ++k) acc += mt[(size_t)k * a.n_mels] * s_pow[k];
-            const float v = mel_feat(acc, a.floor, a.log_floor);
+            const float v = kFbank ? fbank_feat(acc, a.floor, a.log_floor) : mel_feat(acc, a.floor, a.log_floor);
             out[(size_t)f * a.n_mels + tid] = v;
-            vmax = fmaxf(vmax, v);
+            if constexpr (kFbank) vsum += v;
+            else vmax = fmaxf(vmax, v);
         }
         __syncthreads(); // the next frame overwrites s_frame and s_pow
     }
-    tile_max_store(vmax, red, a.tile_max + blockIdx.x);
+    if constexpr (kFbank) {
+        if (tid < (int)a.n_mels) args.tile_sum[(size_t)blockIdx.x * a.n_mels + tid] = vsum;
+    } else {
+        tile_max_store(vmax, red, a.tile_max + blockIdx.x);
+    }
 }
 
 // ---------------------------------------------------------------------------- n_fft == 400: eight frames per wavefront
@@ -321,6 +391,57 @@ __global__ __launch_bounds__(kThreads) void clip_mel_norm_kernel(ClipMelArgs a)
     for (int o = threadIdx.x; o < n_out; o += kThreads) out[o] = (fmaxf(out[o], lo) + a.norm_offset) * a.norm_scale;
 }
 
+// ---------------------------------------------------------------------------- the filter-bank export's means
+// one lane per (clip, band): the tiles' sums added in tile order onto 0.0f, over f32(T) -- one rounded division
+__global__ __launch_bounds__(kThreads) void clip_fbank_mean_kernel(ClipFbankArgs a)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (unsigned long long)a.m.c.n_clips * a.m.n_mels) return;
+    const uint32_t c = (uint32_t)(i / a.m.n_mels), m = (uint32_t)(i - (unsigned long long)c * a.m.n_mels);
+    const ClipJob j = a.m.c.jobs[c];
+    const long long L = (long long)((j.len - j.skip + a.m.step - 1) / a.m.step), T = (L - a.win) / a.m.hop + 1;
+    float s = 0.0f;
+    for (uint32_t g = a.m.c.tile_prefix[c]; g < a.m.c.tile_prefix[c + 1]; ++g) s += a.tile_sum[(size_t)g * a.m.n_mels + m];
+    a.means[i] = s / (float)T;
+}
+
+// feat' = feat - mean_m over a tile's cells: one rounded subtraction
+__global__ __launch_bounds__(kThreads) void clip_fbank_sub_kernel(ClipFbankArgs a)
+{
+    const uint32_t clip = find_clip(a.m.c.tile_prefix, a.m.c.n_clips, blockIdx.x);
+    const ClipJob j = a.m.c.jobs[clip];
+    const MelTile t = mel_tile<true>(a.m, j, clip, a.win);
+    float* out = static_cast<float*>(a.m.c.out) + j.out_off + (unsigned long long)t.t0 * a.m.n_mels;
+    const float* mean = a.means + (size_t)clip * a.m.n_mels;
+    const int n_out = t.nf * (int)a.m.n_mels;
+    for (int o = threadIdx.x; o < n_out; o += kThreads) out[o] = out[o] - mean[o % (int)a.m.n_mels];
+}
+
+int fvad_launch_clip_fbank(const ClipFbankArgs& a, hipStream_t stream)
+{
+    const dim3 grid(a.m.c.n_tiles), block(kThreads);
+    const size_t lds = mel_generic_lds(mel_stage_floats(a.win, a.m.hop, a.m.tile_frames), (uint32_t)a.m.pl.n); // win 400, n_fft 512, hop 160: 30.0 KB
+    const void* fn = a.m.c.src_i16 ? (const void*)clip_mel_kernel<int16_t, true> : (const void*)clip_mel_kernel<float, true>;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    if (a.m.c.src_i16) hipLaunchKernelGGL((clip_mel_kernel<int16_t, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((clip_mel_kernel<float, true>), grid, block, lds, stream, a);
+    return (int)hipGetLastError();
+}
+
+int fvad_launch_clip_fbank_mean(const ClipFbankArgs& a, hipStream_t stream)
+{
+    const unsigned long long n = (unsigned long long)a.m.c.n_clips * a.m.n_mels;
+    hipLaunchKernelGGL(clip_fbank_mean_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+int fvad_launch_clip_fbank_sub(const ClipFbankArgs& a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(clip_fbank_sub_kernel, dim3(a.m.c.n_tiles), dim3(kThreads), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
 int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream)
 {
     const dim3 grid(a.c.n_tiles), block(kThreads);
@@ -333,12 +454,12 @@ int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream)
         if (a.c.src_i16) hipLaunchKernelGGL(clip_mel400_kernel<int16_t>, grid, block, lds, stream, a);
         else hipLaunchKernelGGL(clip_mel400_kernel<float>, grid, block, lds, stream, a);
     } else {
-        const size_t lds = (size_t)(stage + 2 * n_fft + 4 * (n_fft / 2 + 1) + (n_fft / 2 + 1)) * sizeof(float); // n_fft 400, hop 160: 28.0 KB; at most 68.0 KB
-        const void* fn = a.c.src_i16 ? (const void*)clip_mel_kernel<int16_t> : (const void*)clip_mel_kernel<float>;
+        const size_t lds = mel_generic_lds(stage, n_fft); // n_fft 400, hop 160: 28.0 KB; at most 68.0 KB
+        const void* fn = a.c.src_i16 ? (const void*)clip_mel_kernel<int16_t, false> : (const void*)clip_mel_kernel<float, false>;
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
-        if (a.c.src_i16) hipLaunchKernelGGL(clip_mel_kernel<int16_t>, grid, block, lds, stream, a);
-        else hipLaunchKernelGGL(clip_mel_kernel<float>, grid, block, lds, stream, a);
+        if (a.c.src_i16) hipLaunchKernelGGL((clip_mel_kernel<int16_t, false>), grid, block, lds, stream, a);
+        else hipLaunchKernelGGL((clip_mel_kernel<float, false>), grid, block, lds, stream, a);
     }
     return (int)hipGetLastError();
 }

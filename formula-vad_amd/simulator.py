@@ -8,7 +8,8 @@ the pipeline, the Evaluator and the statistics all live behind include/fvad.h.
                                                       clips, original and denoised, cut and picked on the GPU;
                                                       --clips-denoised-rate 16000 / --clips-original-rate 16000: at NSNet2's rate;
                                                       --clips-original-filter fir: anti-aliased, also at 24000 and 8000;
-                                                      --clips-features logmel: the denoised clips' log-mel features as .npy)
+                                                      --clips-features logmel | fbank: the denoised clips' log-mel or Kaldi
+                                                      filter-bank features as .npy)
     python -m ... simulator.py -i plan.json --export-denoised DIR [--denoised-format pcm16|pcm24|f32] [--denoised-rate R|source] [--denoised-source lanes|network]   (or: run_denoise(path,
                                                       DIR): the denoised recordings as WAV files, converted and interleaved
                                                       on the GPU; --denoised-kinds denoised,original,residual,mix
@@ -561,21 +562,29 @@ def _clip_entry(path, best_channel, best_rms, runner_up_rms, rate, first_sample,
     return e
 
 
-CLIP_FEATURES = (None, "logmel")
+CLIP_FEATURES = (None, "logmel", "fbank")
 CLIP_FEATURES_NORM = {None: None, "whisper": (8.0, 4.0, 0.25)}   # (range, offset, scale), the maximum taken per clip
+CLIP_FEATURES_NORM_OF = {"logmel": (None, "whisper"), "fbank": (None, "cmn")}   # the norms each kind of features takes
 # Whisper's front end on NSNet2's own 16 kHz samples: step 3 at the denoised kind's phase, 400-point periodic Hann, hop 160,
 # 80 Slaney bands over 0 .. 8 kHz, log10(max(., 1e-10))
 LOGMEL = dict(step=3, n_fft=400, hop=160, n_mels=80, sample_rate=16000, fmin=0.0, fmax=8000.0, floor=1e-10)
+# Kaldi's fbank (compute-fbank-feats, torchaudio.compliance.kaldi.fbank) on the same samples: frames of 400 from t * 160 on
+# (snip_edges), DC removed, pre-emphasis 0.97, Povey window, 512-point transform, 80 HTK-mel triangles over 20 Hz .. Nyquist,
+# ln(max(., FLT_EPSILON)); samples scaled by 32768, Kaldi's convention
+FBANK = dict(step=3, win_length=400, n_fft=512, hop=160, n_mels=80, sample_rate=16000, low_freq=20.0, high_freq=0.0, preemph=0.97,
+             remove_dc=1, scale=32768.0, floor=fv.FLT_EPSILON)
 
 
 def _check_features(features, features_norm, slice_chunks):
     """ValueError for what run_clips does not offer with features, before any work"""
     if features not in CLIP_FEATURES:
         raise ValueError(f"features = {features!r}: one of {CLIP_FEATURES}")
-    if features_norm not in CLIP_FEATURES_NORM:
-        raise ValueError(f"features_norm = {features_norm!r}: one of {tuple(CLIP_FEATURES_NORM)}")
+    if features_norm not in CLIP_FEATURES_NORM and features_norm != "cmn":
+        raise ValueError(f"features_norm = {features_norm!r}: one of {tuple(CLIP_FEATURES_NORM) + ('cmn',)}")
     if features is None and features_norm is not None:
         raise ValueError("features_norm needs features")
+    if features is not None and features_norm not in CLIP_FEATURES_NORM_OF[features]:
+        raise ValueError(f"features_norm = {features_norm!r} with features = {features!r}: one of {CLIP_FEATURES_NORM_OF[features]}")
     if features is not None and slice_chunks is not None:
         raise ValueError("features with slice_chunks: the split-source form of fvad_clips_export_mel does not exist yet")
 
@@ -586,11 +595,18 @@ def logmel_window():
     return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)
 
 
-def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, manifests, features_norm):
-    """the features of run_clips: one fvad_clips_export_mel over the denoised lanes' clips, NAME-####-denoised.logmel.npy per
-    clip and its manifest entry under "features".  A clip too short for one reflected frame has no entry and is counted in
-    features_skipped"""
-    p = LOGMEL
+def fbank_window():
+    """Kaldi's Povey window of FBANK's win_length, evaluated in double and rounded once"""
+    n = FBANK["win_length"]
+    return ((0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))) ** 0.85).astype(np.float32)
+
+
+def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, manifests, features_norm, features="logmel"):
+    """the features of run_clips: one fvad_clips_export_mel (or fvad_clips_export_fbank) over the denoised lanes' clips,
+    NAME-####-denoised.logmel.npy (.fbank.npy) per clip and its manifest entry under "features".  A clip too short for one
+    reflected frame (for one frame of 400) has no entry and is counted in features_skipped"""
+    fbank = features == "fbank"
+    p = FBANK if fbank else LOGMEL
     rows, owner = [], []
     for i, (segs, _) in enumerate(per_inst):
         clips, _ = fv.clips_from_segments(segs, lane0[i], n_channels[i], avail[i])
@@ -601,7 +617,7 @@ def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, 
                 k += 1
             skip = int(fv.clips_phase_skips(c[2:3], p["step"], CLIP_PHASE["denoised"])[0])
             L = -(-(int(c[3] - c[2]) - skip) // p["step"])
-            if L >= p["n_fft"] // 2 + 1 and L >= p["hop"]:
+            if (L >= p["win_length"]) if fbank else (L >= p["n_fft"] // 2 + 1 and L >= p["hop"]):
                 rows.append(c)
                 owner.append((i, k))
             else:
@@ -611,6 +627,24 @@ def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, 
         return
     rows = np.array(rows, np.uint64)
     skips = fv.clips_phase_skips(rows[:, 2], p["step"], CLIP_PHASE["denoised"])
+    if fbank:
+        matrix = fv.mel_design_kaldi(p["sample_rate"], p["n_fft"], p["n_mels"], p["low_freq"], p["high_freq"])
+        res = ctx.clips_export_fbank(r.d_den, False, r.n_lanes, r.n_den, r.n_den, rows, fbank_window(), matrix, n_fft=p["n_fft"], step=p["step"],
+                                     skips=skips, hop=p["hop"], scale=p["scale"], preemph=p["preemph"], remove_dc=p["remove_dc"], floor=p["floor"],
+                                     cmn=features_norm == "cmn")
+        for j, (i, k) in enumerate(owner):
+            o, T = int(res["offsets"][j]), int(res["n_frames"][j])
+            path = os.path.join(out_dir, "{}-{:04d}-denoised.fbank.npy".format(insts[i]["name"], k))
+            np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
+            e = {"file": os.path.basename(path), "kind": "fbank", "frames": T, "n_mels": p["n_mels"], "win_length": p["win_length"],
+                 "n_fft": p["n_fft"], "hop": p["hop"], "sample_rate": p["sample_rate"], "first_sample": int(rows[j, 2]) + int(skips[j]),
+                 "best_channel": int(res["best_channel"][j]), "window": "povey", "preemph": p["preemph"], "remove_dc": bool(p["remove_dc"]),
+                 "scale": p["scale"], "snip_edges": True, "log": "ln", "floor": p["floor"], "norm": features_norm,
+                 "mel": {"design": "kaldi", "low_freq": p["low_freq"], "high_freq": p["high_freq"]}}
+            if features_norm == "cmn":
+                e["means"] = [float(v) for v in res["means"][j]]
+            manifests[i]["clips"][k]["features"] = e
+        return
     matrix = fv.mel_design(p["sample_rate"], p["n_fft"], p["n_mels"], p["fmin"], p["fmax"])
     res = ctx.clips_export_mel(r.d_den, False, r.n_lanes, r.n_den, r.n_den, rows, logmel_window(), matrix, step=p["step"], skips=skips,
                                hop=p["hop"], floor=p["floor"], norm=CLIP_FEATURES_NORM[features_norm])
@@ -682,7 +716,7 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs, features=
                                                              int(rows[j, 2]) + (0 if skips is None else int(skips[j])), n, firs[kind])
         if features is not None:
             _features_share(ctx, r, insts, per_inst, lane0, [_dims(a)[0] for a in audio], [n * chunk for n in r.n_chunks], out_dir, manifests,
-                            features_norm)
+                            features_norm, features)
         return [(segs, audit, m) for (segs, audit), m in zip(per_inst, manifests)]
     finally:
         for d in held:
@@ -739,7 +773,14 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     clip too short for one frame (under 201 samples at 16 kHz) has none and is counted in features_skipped.  features_norm
     "whisper": (max(x, max - 8) + 4) / 4 with the maximum taken per clip ("max" stays the un-normalised one).  An unknown
     features or features_norm, features_norm without features, and features with slice_chunks (the split-source form of the
-    feature export does not exist yet) raise before any work.  With features None every file and manifest is what it was."""
+    feature export does not exist yet) raise before any work.  With features None every file and manifest is what it was.
+    features "fbank": Kaldi's filter-bank features in its place -- one fvad_clips_export_fbank with FBANK's parameters: the same
+    samples (step 3, phase 2) times 32768, frames of 400 every 160 from the clip's first sample on (snip_edges), DC removed,
+    pre-emphasis 0.97, the Povey window, a 512-point transform, fvad_mel_design_kaldi(16000, 512, 80, 20, 0), ln(max(.,
+    FLT_EPSILON)).  Per clip NAME-####-denoised.fbank.npy (float32 [frames, 80], frames = 1 + (L - 400) // 160) and "features":
+    every parameter above; a clip under 400 samples at 16 kHz has none and is counted in features_skipped.  features_norm "cmn":
+    the clip's mean per band is subtracted (torchaudio's subtract_mean) and stated under "means".  "whisper" with "fbank" and
+    "cmn" with "logmel" raise before any work."""
     _check_ingest(ingest)
     _check_features(features, features_norm, slice_chunks)
     rates, firs = _clip_rates(original_rate, denoised_rate, original_filter, denoised_filter)
@@ -2715,9 +2756,12 @@ def arg_parser():
     ap.add_argument("--clips-features", default=None, metavar="KIND",
                     help="with --export-clips: logmel -- also write every denoised clip's log-mel features, computed on the GPU from the "
                          "network's own 16 kHz samples (400-point Hann, hop 160, 80 Slaney bands, log10), as NAME-####-denoised.logmel.npy; "
+                         "fbank -- Kaldi's filter-bank features of the same samples (frames of 400 every 160, DC removed, pre-emphasis 0.97, "
+                         "Povey window, 512-point transform, 80 HTK-mel bands from 20 Hz, ln), as NAME-####-denoised.fbank.npy; "
                          "not with --slice-chunks")
     ap.add_argument("--clips-features-norm", default=None, metavar="NORM",
-                    help="with --clips-features: whisper -- (max(x, max - 8) + 4) / 4, the maximum taken per clip")
+                    help="with --clips-features logmel: whisper -- (max(x, max - 8) + 4) / 4, the maximum taken per clip; "
+                         "with --clips-features fbank: cmn -- the clip's mean per band subtracted")
     ap.add_argument("--overlap", action="store_true",
                     help="with --sweep-grid and --slice-chunks (device machines and scoring): run each slice's machines beside the "
                          "next slice's denoising (a second stream and a second set of band buffers)")

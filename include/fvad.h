@@ -1150,6 +1150,80 @@ int fvad_clips_export_mel(fvad_ctx *ctx, const void *d_src, int src_format, size
                           const uint32_t *skips, uint32_t n_fft, uint32_t hop, const float *window, uint32_t n_mels,
                           const float *matrix, float floor, const float *norm, uint64_t *n_frames, float *feat_max);
 
+/* ------------------------------------------------------------------ batch Recorder with a front end: Kaldi-style filter-bank features
+ * The other input open recognisers take (k2 / icefall, WeNet, ESPnet, SpeechBrain, FunASR) is Kaldi's fbank, as
+ * compute-fbank-feats or torchaudio.compliance.kaldi.fbank make it: frames that are not centred, each with its DC removed and
+ * pre-emphasised before the window, zero-padded into a longer transform, HTK-mel triangles without area normalisation, the
+ * natural logarithm.  It cannot be made from the log-mel output above.  These calls compute it from the device-resident lanes
+ * (csrc/kernels_clips_mel.hip: the mel export's kernel with the conditioned form on).  For a clip row:
+ * - Channel, best_rms, runner_up_rms: fvad_clips_export's bits over every sample, as in the mel export.
+ * - Feature stream: s[i] = f32(clip sample skip + i * step) * scale, i < L = ceil((len - skip) / step); step, skips and PCM16
+ *   follow the mel export's rules; scale is a finite non-zero f32 and the product is rounded once (Kaldi's own convention is
+ *   32768, which only moves the exponent).
+ * - Parameters: win_length in 2..n_fft; n_fft even in 4..FVAD_CLIP_MEL_NFFT_MAX; hop in 1..win_length; n_mels in
+ *   1..FVAD_CLIP_MEL_BANDS_MAX; preemph a finite f32 in [0, 1]; remove_dc 0 or 1; the caller's window[win_length] and
+ *   matrix[n_mels][n_fft / 2 + 1]; floor finite and positive.
+ * - Frames (Kaldi's snip_edges = true): T = 1 + (L - win_length) / hop for L >= win_length; a clip with L < win_length is
+ *   refused, as the mel export refuses one too short to reflect.  Frame t is x[i] = s[t * hop + i], i < win_length.  Nothing
+ *   outside the clip is read, no sample off the stride, and there is no reflection.
+ * - Conditioning of a frame, in f32, every operation rounded on its own (fp contraction is off for the library), in this order:
+ *   1. with remove_dc, d[i] = x[i] - mean, mean = (sum of x[i]) / f32(win_length); without, d = x.  The order of the sum is
+ *      fixed for a given win_length and the same for every frame, tile and wavefront slot (the kernel's header states it).
+ *   2. y[0] = d[0] - preemph * d[0] and y[i] = d[i] - preemph * d[i - 1] (Kaldi's replicated first sample): one rounded
+ *      product and one rounded difference each.
+ *   3. z[i] = y[i] * window[i], zero for win_length <= i < n_fft.
+ * - Then as the mel export: P[k] = |rfft(z)[k]|^2; mel[m] = sum_k M[m][k] * P[k] over ascending k, one rounded product and one
+ *   rounded sum each; feat = logf(fmaxf(mel, floor)), the natural logarithm.  logf(floor) is evaluated on the host in double and
+ *   rounded once and is what every mel <= floor gives: digital silence is exactly that value in every band.
+ * - Output: per clip [T][n_mels] f32 in 16-byte-aligned slots in clip order (fvad_clips_plan_fbank); the padding is never
+ *   written by the device form and zeroed by the host form -- the mel export's rules.
+ * - Cepstral mean subtraction, cmn 0 or 1 (torchaudio's subtract_mean), in THIS order, so that numpy float32 evaluated in it is
+ *   the exact model: within a tile of min(32, (8192 - win_length) / hop + 1) consecutive frames the features of a band are
+ *   added over ascending t onto 0.0f by one lane; the tiles' sums are then added in tile order onto 0.0f by one lane per (clip,
+ *   band); mean_m = that sum / f32(T), one rounded division; with cmn, feat' = feat - mean_m, one rounded subtraction.
+ * - Reports: the four of fvad_clips_export, n_frames, and means[n_clips][n_mels] (may be NULL), filled whether or not cmn is set.
+ * - INVARIANTS, bit for bit: a frame's features before cmn depend on that frame's samples and the call's parameters alone -- not
+ *   on the other clips, their order, the tile or slot, the alignment of either side or the call form -- and repeat run after
+ *   run.  Every size runs on the generic mixed-radix transform.
+ *
+ * fvad_mel_design_kaldi (host only): matrix[n_mels][n_fft / 2 + 1] of Kaldi's bank, evaluated in double and rounded once.
+ *   mel(f) = 1127 ln(1 + f / 700); high_freq <= 0 means Nyquist + high_freq; n_mels + 2 points equally spaced in mel from
+ *   low_freq to high_freq; filter m over the bins k * sample_rate / n_fft, k < n_fft / 2, is max(0, min((mel_k - l) / (c - l),
+ *   (r - mel_k) / (r - c))) with l, c, r its three points: the triangle in the mel domain, no normalisation.  The Nyquist column
+ *   is zero.  Refusals as fvad_mel_design's (low_freq < 0, high_freq above Nyquist, low_freq >= high_freq, ...).  torchaudio was
+ *   not at hand, so the designer is checked against the formula written out independently, not against torchaudio's output.
+ * fvad_clips_plan_fbank (host only): n_frames[i], offsets[i] and *total (floats) for clips of lens[i] samples; skips NULL means
+ *   all zero.  FVAD_ERR_INVALID_ARGUMENT for a bad step, win_length (2..FVAD_CLIP_MEL_NFFT_MAX), hop or n_mels, a skip >= step,
+ *   a clip with len <= skip or L < win_length, NULLs, or a total that does not fit 64 bits.
+ * fvad_clips_fbank_check (host only; d_src and out are addresses, nothing is read through them): every argument rule of the two
+ *   exports in the one order both report them in -- the mel check's up to the rows' own rules, then step, n_fft, win_length, hop,
+ *   n_mels, per clip its skip and frames, a window or matrix value that is not finite, scale, preemph, remove_dc, floor, cmn,
+ *   then FVAD_ERR_OUT_OF_RANGE, FVAD_ERR_BUFFER_TOO_SMALL and the grids as in the mel check.
+ * fvad_clips_export_fbank_device / fvad_clips_export_fbank: the full-rate call's arguments, then step, skips, win_length, n_fft,
+ *   hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn (window, matrix: host memory) and the two reports.  Every
+ *   error comes back before any launch.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_fbank, clip_fbank_mean (always)
+ *   and, with cmn, clip_fbank_sub.  The split-source form (sliced runs) does not exist for these either. */
+int fvad_mel_design_kaldi(double sample_rate, uint32_t n_fft, uint32_t n_mels, double low_freq, double high_freq, float *matrix);
+int fvad_clips_plan_fbank(const uint64_t *lens, const uint32_t *skips, size_t n_clips, uint32_t step, uint32_t win_length,
+                          uint32_t hop, uint32_t n_mels, uint64_t *n_frames, uint64_t *offsets, uint64_t *total);
+int fvad_clips_fbank_check(const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                           const uint64_t *clips, size_t n_clips, int out_format, const void *out, size_t out_capacity,
+                           int device_out, uint32_t step, const uint32_t *skips, uint32_t win_length, uint32_t n_fft, uint32_t hop,
+                           const float *window, uint32_t n_mels, const float *matrix, float scale, float preemph, int remove_dc,
+                           float floor, int cmn, uint64_t *n_frames, uint64_t *offsets, uint64_t *total);
+int fvad_clips_export_fbank_device(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride,
+                                   size_t n_samples, const uint64_t *clips, size_t n_clips, int out_format, void *d_out,
+                                   size_t out_capacity, int32_t *best_channel, float *best_rms, float *runner_up_rms,
+                                   uint64_t *out_offsets, uint32_t step, const uint32_t *skips, uint32_t win_length, uint32_t n_fft,
+                                   uint32_t hop, const float *window, uint32_t n_mels, const float *matrix, float scale,
+                                   float preemph, int remove_dc, float floor, int cmn, uint64_t *n_frames, float *means);
+int fvad_clips_export_fbank(fvad_ctx *ctx, const void *d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
+                            const uint64_t *clips, size_t n_clips, int out_format, void *out, size_t out_capacity,
+                            int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets, uint32_t step,
+                            const uint32_t *skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float *window,
+                            uint32_t n_mels, const float *matrix, float scale, float preemph, int remove_dc, float floor, int cmn,
+                            uint64_t *n_frames, float *means);
+
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
  * hold them -- interleaved frames at the file's sample width -- and ONE kernel (csrc/kernels_ingest.hip) de-interleaves,
