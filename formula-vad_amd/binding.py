@@ -822,34 +822,12 @@ class Context:
         float32, matrix: [n_mels][n_fft / 2 + 1] float32, norm: None or (range, offset, scale).
         Returns dict(best_channel, best_rms, runner_up_rms, offsets, total, n_frames, feat_max[, out]); clip i's features are
         out[offsets[i] : offsets[i] + n_frames[i] * n_mels].reshape(n_frames[i], n_mels)."""
-        clips = _clip_rows(clips)
-        n = clips.shape[0]
-        window = np.ascontiguousarray(np.asarray(window, np.float32).reshape(-1))
-        matrix = np.ascontiguousarray(np.asarray(matrix, np.float32))
-        n_fft, n_mels = window.shape[0], matrix.shape[0]
-        if matrix.ndim != 2 or matrix.shape[1] != n_fft // 2 + 1:
-            raise ValueError("matrix must be [n_mels][n_fft / 2 + 1] for the window's n_fft")
-        skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
-        norm = None if norm is None else np.ascontiguousarray(np.asarray(norm, np.float32).reshape(3))
-        frames, offsets, total = clips_plan_mel(clips[:, 3] - clips[:, 2], skips, step, n_fft, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
-        best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
-        n_frames, feat_max = np.zeros(n, np.uint64), np.zeros(n, np.float32)
-        args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
-                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
-        info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n_fft, hop, fptr(window), n_mels, fptr(matrix),
-                floor, None if norm is None else fptr(norm), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(feat_max))
-        res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "n_frames": n_frames,
-               "feat_max": feat_max}
-        if d_out is not None:
-            self._ck(lib().fvad_clips_export_mel_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
-                     "fvad_clips_export_mel_device")
-            return res
-        out = np.zeros(max(total, 1), np.float32)
-        self._ck(lib().fvad_clips_export_mel(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
-                 "fvad_clips_export_mel")
-        res["out"] = out[:total]
-        return res
+        def params(n_fft, window, n_mels, matrix):
+            norm_ = None if norm is None else np.ascontiguousarray(np.asarray(norm, np.float32).reshape(3))
+            return (n_fft, hop, fptr(window), n_mels, fptr(matrix), floor, None if norm_ is None else fptr(norm_)), norm_
+        return self._clips_export_features("mel", (d_src, src_pcm16, n_lanes, lane_stride, n_samples), clips, window, matrix, None,
+                                           "matrix must be [n_mels][n_fft / 2 + 1] for the window's n_fft", step, skips, hop, params,
+                                           "feat_max", d_out, out_capacity)
 
     def clips_export_fbank(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, n_fft=512, step=1, skips=None,
                            hop=160, scale=32768.0, preemph=0.97, remove_dc=True, floor=FLT_EPSILON, cmn=False, d_out=None, out_capacity=None):
@@ -858,31 +836,41 @@ class Context:
         [n_mels][n_fft / 2 + 1] float32.
         Returns dict(best_channel, best_rms, runner_up_rms, offsets, total, n_frames, means[, out]); clip i's features are
         out[offsets[i] : offsets[i] + n_frames[i] * n_mels].reshape(n_frames[i], n_mels), means[i] its per-band mean."""
+        def params(win, window, n_mels, matrix):
+            return (win, int(n_fft), hop, fptr(window), n_mels, fptr(matrix), scale, preemph, int(remove_dc), floor, int(cmn)), None
+        return self._clips_export_features("fbank", (d_src, src_pcm16, n_lanes, lane_stride, n_samples), clips, window, matrix, n_fft,
+                                           "matrix must be [n_mels][n_fft / 2 + 1]", step, skips, hop, params, "means", d_out, out_capacity)
+
+    def _clips_export_features(self, family, src, clips, window, matrix, n_fft, matrix_why, step, skips, hop, params, extra, d_out, out_capacity):
+        """the two feature exports: fvad_clips_export_<family> (+ "_device" with d_out) after fvad_clips_plan_<family>.  n_fft None:
+        the window's length; params(taps, window, n_mels, matrix) -> (the family's arguments between skips and n_frames, what
+        they point into); extra: the result's own key, "feat_max" [n] or "means" [n][n_mels]"""
+        d_src, src_pcm16, n_lanes, lane_stride, n_samples = src
         clips = _clip_rows(clips)
         n = clips.shape[0]
         window = np.ascontiguousarray(np.asarray(window, np.float32).reshape(-1))
         matrix = np.ascontiguousarray(np.asarray(matrix, np.float32))
-        win, n_mels = window.shape[0], matrix.shape[0]
-        if matrix.ndim != 2 or matrix.shape[1] != n_fft // 2 + 1:
-            raise ValueError("matrix must be [n_mels][n_fft / 2 + 1]")
+        taps, n_mels = window.shape[0], matrix.shape[0]
+        if matrix.ndim != 2 or matrix.shape[1] != (taps if n_fft is None else n_fft) // 2 + 1:
+            raise ValueError(matrix_why)
         skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
-        frames, offsets, total = clips_plan_fbank(clips[:, 3] - clips[:, 2], skips, step, win, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
+        own, keep = params(taps, window, n_mels, matrix)
+        frames, offsets, total = _clips_plan_features("fvad_clips_plan_" + family, clips[:, 3] - clips[:, 2], skips, step, taps, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
-        n_frames, means = np.zeros(n, np.uint64), np.zeros((n, n_mels), np.float32)
+        n_frames, per_clip = np.zeros(n, np.uint64), np.zeros((n, n_mels) if extra == "means" else n, np.float32)
         args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
                 clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
         info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), win, int(n_fft), hop, fptr(window), n_mels,
-                fptr(matrix), scale, preemph, int(remove_dc), floor, int(cmn), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(means))
+                step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), *own,
+                n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(per_clip))
         res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "n_frames": n_frames,
-               "means": means}
+               extra: per_clip}
+        name = "fvad_clips_export_" + family
         if d_out is not None:
-            self._ck(lib().fvad_clips_export_fbank_device(*args, vp(d_out), total if out_capacity is None else out_capacity, *info),
-                     "fvad_clips_export_fbank_device")
+            self._ck(getattr(lib(), name + "_device")(*args, vp(d_out), total if out_capacity is None else out_capacity, *info), name + "_device")
             return res
         out = np.zeros(max(total, 1), np.float32)
-        self._ck(lib().fvad_clips_export_fbank(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info),
-                 "fvad_clips_export_fbank")
+        self._ck(getattr(lib(), name)(*args, out.ctypes.data, total if out_capacity is None else out_capacity, *info), name)
         res["out"] = out[:total]
         return res
 
@@ -1865,36 +1853,55 @@ def mel_design(sample_rate, n_fft, n_mels, fmin, fmax):
     return matrix
 
 
-def clips_plan_mel(lens, skips, step, n_fft, hop, n_mels):
-    """fvad_clips_plan_mel: (n_frames [n] uint64, offsets [n] uint64, total), offsets and total in floats; skips None: 0"""
+def _clips_plan_features(name, lens, skips, step, taps, hop, n_mels):
+    """fvad_clips_plan_mel / fvad_clips_plan_fbank (`name`; taps is n_fft or win_length)"""
     lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
     n = lens.shape[0]
     skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
     n_frames, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
-    check(lib().fvad_clips_plan_mel(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                    None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(step), int(n_fft),
-                                    int(hop), int(n_mels), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_mel")
+    check(getattr(lib(), name)(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(step), int(taps),
+                               int(hop), int(n_mels), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), name)
     return n_frames, offsets, int(total.value)
+
+
+def _clips_features_check(name, d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips,
+                          out_format, params):
+    """fvad_clips_mel_check / fvad_clips_fbank_check (`name`).  params(p) is the family's arguments between skips and n_frames, p
+    turning a float32 array or None into a pointer or NULL"""
+    clips = None if clips is None else _clip_rows(clips)
+    n = 0 if clips is None else clips.shape[0]
+    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
+    keep = []
+
+    def p(a):
+        if a is None:
+            return None
+        keep.append(np.ascontiguousarray(np.asarray(a, np.float32)))
+        return fptr(keep[-1])
+    n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
+    st = getattr(lib(), name)(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
+                              None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
+                              out_capacity, int(device_out), int(step),
+                              None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), *params(p),
+                              n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                              C.byref(total))
+    return st, n_frames[:n], offsets[:n], int(total.value)
+
+
+def clips_plan_mel(lens, skips, step, n_fft, hop, n_mels):
+    """fvad_clips_plan_mel: (n_frames [n] uint64, offsets [n] uint64, total), offsets and total in floats; skips None: 0"""
+    return _clips_plan_features("fvad_clips_plan_mel", lens, skips, step, n_fft, hop, n_mels)
 
 
 def clips_mel_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, n_fft, hop,
                     window, n_mels, matrix, floor, norm, out_format=CLIP_F32):
     """fvad_clips_mel_check (host only; d_src and out are addresses) -> (status, n_frames, offsets, total).  window, matrix and
     norm are float32 arrays or None (NULL), passed as they are"""
-    clips = None if clips is None else _clip_rows(clips)
-    n = 0 if clips is None else clips.shape[0]
-    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
-    keep = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix, norm)]
-    n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
-    st = lib().fvad_clips_mel_check(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
-                                    None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
-                                    out_capacity, int(device_out), int(step),
-                                    None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_fft), int(hop),
-                                    None if keep[0] is None else fptr(keep[0]), int(n_mels), None if keep[1] is None else fptr(keep[1]),
-                                    floor, None if keep[2] is None else fptr(keep[2]), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
-    return st, n_frames[:n], offsets[:n], int(total.value)
+    return _clips_features_check("fvad_clips_mel_check", d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity,
+                                 device_out, step, skips, out_format,
+                                 lambda p: (int(n_fft), int(hop), p(window), int(n_mels), p(matrix), floor, p(norm)))
 
 
 def mel_design_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq):
@@ -1907,35 +1914,17 @@ def mel_design_kaldi(sample_rate, n_fft, n_mels, low_freq, high_freq):
 
 def clips_plan_fbank(lens, skips, step, win_length, hop, n_mels):
     """fvad_clips_plan_fbank: (n_frames [n] uint64, offsets [n] uint64, total), offsets and total in floats; skips None: 0"""
-    lens = np.ascontiguousarray(np.asarray(lens, np.uint64).reshape(-1))
-    n = lens.shape[0]
-    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
-    n_frames, offsets, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(0)
-    check(lib().fvad_clips_plan_fbank(lens.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(step), int(win_length),
-                                      int(hop), int(n_mels), n_frames.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)), "fvad_clips_plan_fbank")
-    return n_frames, offsets, int(total.value)
+    return _clips_plan_features("fvad_clips_plan_fbank", lens, skips, step, win_length, hop, n_mels)
 
 
 def clips_fbank_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, win_length,
                       n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, out_format=CLIP_F32):
     """fvad_clips_fbank_check (host only; d_src and out are addresses) -> (status, n_frames, offsets, total).  window and matrix
     are float32 arrays or None (NULL), passed as they are"""
-    clips = None if clips is None else _clip_rows(clips)
-    n = 0 if clips is None else clips.shape[0]
-    skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
-    keep = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix)]
-    n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
-    st = lib().fvad_clips_fbank_check(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
-                                      None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
-                                      out_capacity, int(device_out), int(step),
-                                      None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), int(win_length), int(n_fft),
-                                      int(hop), None if keep[0] is None else fptr(keep[0]), int(n_mels),
-                                      None if keep[1] is None else fptr(keep[1]), scale, preemph, int(remove_dc), floor, int(cmn),
-                                      n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      C.byref(total))
-    return st, n_frames[:n], offsets[:n], int(total.value)
+    return _clips_features_check("fvad_clips_fbank_check", d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity,
+                                 device_out, step, skips, out_format,
+                                 lambda p: (int(win_length), int(n_fft), int(hop), p(window), int(n_mels), p(matrix), scale, preemph,
+                                            int(remove_dc), floor, int(cmn)))
 
 
 def clips_resample_check(up, down, taps):

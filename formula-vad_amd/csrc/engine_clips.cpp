@@ -12,17 +12,16 @@
 //   order (host_clips_split.cpp), reported as "<the entry point>: ..."
 //   Both in four forms (ClipForm of clips_rules.h): full rate, strided (kernels_clips_strided.hip), filtered
 //   (kernels_clips_fir.hip) and resampled (kernels_clips_resample.hip); the form's part is its taps as the gather walks them.
-// - fvad_clips_export_mel*: log-mel features of the picked channel's strided stream (kernels_clips_mel.hip) in place of a
-//   gather; rules in clips_mel.h, shared with the host-only fvad_clips_mel_check; parts: window, matrix and the maxima.
-// - fvad_clips_export_fbank*: Kaldi-style filter-bank features of the same stream, by the same kernel file; rules in
-//   clips_fbank.h, shared with the host-only fvad_clips_fbank_check; parts: window, matrix, the tiles' sums and the means.
+// - fvad_clips_export_mel* and fvad_clips_export_fbank*: log-mel or Kaldi-style filter-bank features of the picked channel's
+//   strided stream (kernels_clips_mel.hip) in place of a gather, one form over a family (features_device, features_host); rules
+//   in clips_features.h, shared with the host-only fvad_clips_mel_check and fvad_clips_fbank_check; parts: window, matrix and
+//   the family's own two (the tiles' and clips' maxima, or the tiles' sums and the means).
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 #include <vector>
 
-#include "clips_fbank.h"
-#include "clips_mel.h"
+#include "clips_features.h"
 #include "clips_split.h"
 #include "internal.h"
 
@@ -32,7 +31,6 @@ static_assert(kClipSrcTile == (uint64_t)kClipTile, "clips_rules.h and host_clips
 static_assert(kStridedSrcTile == (uint64_t)kClipTile && FVAD_CLIP_STEP_MAX == kClipStepMax, "clips_strided.h counts the kernels' tiles");
 static_assert(kFirSrcTile == (uint64_t)kClipTile && FVAD_CLIP_FIR_TAPS_MAX == kClipFirTapsMax, "clips_fir.h counts the kernels' tiles");
 static_assert(kResampledWindow == (uint64_t)kClipTile, "clips_resample.h counts the kernels' window");
-static_assert(kMelSrcTile == (uint64_t)kClipTile && kMelTileFrames == (uint64_t)kClipMelTileFrames, "clips_mel.h counts the kernels' tiles");
 static_assert(FVAD_CLIP_MEL_NFFT_MAX == kClipMelNfftMax && FVAD_CLIP_MEL_BANDS_MAX == kClipMelBandsMax, "fvad.h states the kernels' limits");
 
 namespace {
@@ -373,17 +371,27 @@ int export_split_host(fvad_ctx* ctx, const char* who, const SplitLanes& s, const
                        [&](void* d_out) { return export_split_device(ctx, who, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, form); });
 }
 
-// ------------------------------------------------------------------ fvad_clips_export_mel*: features in place of samples
+// ------------------------------------------------------------------ fvad_clips_export_mel*, fvad_clips_export_fbank*: features in place of samples
 
-struct MelCall {
-    Mel m;
+// one call of either family (f.snip: the filter-bank one)
+struct FeatCall {
+    const char* who; // the family's entry point, as error strings name it
+    Feat f;
     const float* window;
     const float* matrix;
-    float floor;
-    const float* norm;
+    FeatCond c;
     uint64_t* n_frames; // what the call reports per clip beside ClipReport; each may be NULL
-    float* feat_max;
+    float* per_clip;    // feat_max [n_clips] (log-mel) or means [n_clips][n_mels] (filter-bank)
 };
+
+// one timed launch of a family's list
+struct FeatLaunch {
+    const char* label;
+    int (*fn)(const ClipFeatArgs&, hipStream_t);
+    const char* what; // the call as FVAD_HIP would report it
+    bool on;
+};
+#define FEAT_LAUNCH(label, fn, on) FeatLaunch{label, fn, "(hipError_t)" #fn "(a, ctx->stream)", on}
 
 // the matrix as the kernels read it: [bin][band]
 std::vector<float> bands_transposed(const float* matrix, uint32_t n_mels, uint32_t n_bins)
@@ -404,165 +412,112 @@ bool feature_tables(const Lanes& s, const uint32_t* skips, const std::vector<uin
     return build_tables(s.n_clips, false, desc, t);
 }
 
-// what both feature forms put into ClipMelArgs the same way; x[0] and x[1] are the window and the transposed matrix
-void feature_args(ClipMelArgs& a, const ClipArgs& c, const Part* x, uint32_t step, uint32_t hop, uint32_t n_mels, uint32_t tf, float floor, float log_floor)
+int check_features(const Lanes& s, const ClipOut& o, int device_out, const FeatCall& fc, uint64_t* n_frames, uint64_t* offsets, uint64_t* total, const char** why)
 {
-    a.c = c;
-    a.window = reinterpret_cast<const float*>(x[0].dev);
-    a.matrix_t = reinterpret_cast<const float*>(x[1].dev);
-    a.step = step;
-    a.hop = hop;
-    a.n_mels = n_mels;
-    a.tile_frames = tf;
-    a.floor = floor;
-    a.log_floor = log_floor;
+    return feat_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, device_out, fc.f, fc.window,
+                      fc.matrix, fc.c, n_frames, offsets, total, why);
 }
 
-int mel_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
+// A family supplies its parameters (fc.f, fc.c), its two own parts -- a float per tile and per clip (the tiles' and the clips'
+// maxima) or n_mels of each (the tiles' sums and the clips' means) --, its launch list and, through the clip part, what it scatters.
+int features_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatCall& fc)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (s.n_clips == 0) return FVAD_OK;
     std::vector<uint64_t> offsets(s.n_clips), frames(s.n_clips);
     uint64_t total = 0;
     const char* why = "";
-    const int bad = mel_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 1, mc.m, mc.window,
-                              mc.matrix, mc.floor, mc.norm, frames.data(), offsets.data(), &total, &why);
-    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_mel: ") + why);
-    const Mel& m = mc.m;
-    const uint32_t tf = clip_mel_tile_frames(m.n_fft, m.hop), n_bins = m.n_fft / 2 + 1;
+    const int bad = check_features(s, o, 1, fc, frames.data(), offsets.data(), &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string(fc.who) + ": " + why);
+    const Feat& f = fc.f;
+    const uint32_t tf = feat_tile_frames(f.taps, f.hop), n_bins = f.n_fft / 2 + 1;
     ClipTables t;
-    if (!feature_tables(s, m.skips, offsets, frames, tf, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_mel: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
-    const std::vector<float> matrix_t = bands_transposed(mc.matrix, m.n_mels, n_bins);
-
-    hipSetDevice(ctx->device);
-    ClipMelArgs a{};
-    // the transform's tables (twiddles, un-mixing factors, radices), cached per context and size
-    { const int rc = get_vad_plan(ctx, m.n_fft, &a.pl, true); if (rc != FVAD_OK) return rc; }
-    std::vector<float> fmax(s.n_clips);
-    enum { kWindow, kMatrix, kTileMax, kFeatMax };
-    const std::vector<Part> parts = {{mc.window, nullptr, m.n_fft * sizeof(float), nullptr},
-                                     {matrix_t.data(), nullptr, matrix_t.size() * sizeof(float), nullptr},
-                                     {nullptr, nullptr, t.tiles * sizeof(float), nullptr},
-                                     {nullptr, fmax.data(), s.n_clips * sizeof(float), nullptr}};
-    auto features = [&](const ClipArgs& c, const Part* x) -> int {
-        feature_args(a, c, x, m.step, m.hop, m.n_mels, tf, mc.floor, (float)std::log10((double)mc.floor));
-        a.tile_max = reinterpret_cast<float*>(x[kTileMax].dev);
-        a.feat_max = reinterpret_cast<float*>(x[kFeatMax].dev);
-        if (mc.norm) { a.norm_range = mc.norm[0]; a.norm_offset = mc.norm[1]; a.norm_scale = mc.norm[2]; }
-        a.fft400 = m.n_fft == 400 && !ctx->tune.clip_mel_generic;
-        time_begin(ctx, a.fft400 ? "clip_mel400" : "clip_mel");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel(a, ctx->stream));
-        time_end(ctx);
-        time_begin(ctx, "clip_mel_max");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel_max(a, ctx->stream));
-        time_end(ctx);
-        if (mc.norm) {
-            time_begin(ctx, "clip_mel_norm");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_mel_norm(a, ctx->stream));
-            time_end(ctx);
-        }
-        return FVAD_OK;
-    };
-    const int rc = run_clips(ctx, "fvad_clips_export_mel", source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
-    if (rc != FVAD_OK) return rc;
-    for (size_t i = 0; i < s.n_clips; ++i) {
-        if (mc.n_frames) mc.n_frames[i] = frames[i];
-        if (mc.feat_max) mc.feat_max[i] = fmax[i];
-    }
-    return FVAD_OK;
-}
-
-int mel_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const MelCall& mc)
-{
-    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (s.n_clips == 0) return FVAD_OK;
-    // every rule against the caller's own buffer first
-    uint64_t total = 0;
-    const char* why = "";
-    const int bad = mel_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 0, mc.m, mc.window,
-                              mc.matrix, mc.floor, mc.norm, nullptr, nullptr, &total, &why);
-    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_mel: ") + why);
-    return via_staging(ctx, "fvad_clips_export_mel", "fvad_clips_export_mel", o.p, (size_t)total * sizeof(float),
-                       [&](void* d_out) { return mel_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, mc); });
-}
-
-// ------------------------------------------------------------------ fvad_clips_export_fbank*: Kaldi-style filter-bank features
-
-struct FbankCall {
-    Fbank f;
-    const float* window;
-    const float* matrix;
-    FbankCond c;
-    uint64_t* n_frames; // what the call reports per clip beside ClipReport; each may be NULL
-    float* means;       // [n_clips][n_mels]
-};
-
-int fbank_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FbankCall& fc)
-{
-    if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
-    if (s.n_clips == 0) return FVAD_OK;
-    std::vector<uint64_t> offsets(s.n_clips), frames(s.n_clips);
-    uint64_t total = 0;
-    const char* why = "";
-    const int bad = fbank_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 1, fc.f, fc.window,
-                                fc.matrix, fc.c, frames.data(), offsets.data(), &total, &why);
-    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_fbank: ") + why);
-    const Fbank& f = fc.f;
-    const uint32_t tf = clip_mel_tile_frames(f.win_length, f.hop), n_bins = f.n_fft / 2 + 1;
-    ClipTables t;
-    if (!feature_tables(s, f.skips, offsets, frames, tf, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, "fvad_clips_export_fbank: more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
+    if (!feature_tables(s, f.skips, offsets, frames, tf, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string(fc.who) + ": more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
     const std::vector<float> matrix_t = bands_transposed(fc.matrix, f.n_mels, n_bins);
 
     hipSetDevice(ctx->device);
-    ClipFbankArgs a{};
-    { const int rc = get_vad_plan(ctx, f.n_fft, &a.m.pl, true); if (rc != FVAD_OK) return rc; }
-    std::vector<float> means(s.n_clips * (size_t)f.n_mels);
-    enum { kWindow, kMatrix, kTileSum, kMeans };
-    const std::vector<Part> parts = {{fc.window, nullptr, f.win_length * sizeof(float), nullptr},
+    ClipFeatArgs a{};
+    // the transform's tables (twiddles, un-mixing factors, radices), cached per context and size
+    { const int rc = get_vad_plan(ctx, f.n_fft, &a.pl, true); if (rc != FVAD_OK) return rc; }
+    const size_t cells = f.snip ? f.n_mels : 1;
+    std::vector<float> per_clip(s.n_clips * cells);
+    enum { kWindow, kMatrix, kPerTile, kPerClip };
+    const std::vector<Part> parts = {{fc.window, nullptr, f.taps * sizeof(float), nullptr},
                                      {matrix_t.data(), nullptr, matrix_t.size() * sizeof(float), nullptr},
-                                     {nullptr, nullptr, t.tiles * f.n_mels * sizeof(float), nullptr},
-                                     {nullptr, means.data(), means.size() * sizeof(float), nullptr}};
+                                     {nullptr, nullptr, t.tiles * cells * sizeof(float), nullptr},
+                                     {nullptr, per_clip.data(), per_clip.size() * sizeof(float), nullptr}};
     auto features = [&](const ClipArgs& c, const Part* x) -> int {
-        feature_args(a.m, c, x, f.step, f.hop, f.n_mels, tf, fc.c.floor, (float)std::log((double)fc.c.floor));
-        a.tile_sum = reinterpret_cast<float*>(x[kTileSum].dev);
-        a.means = reinterpret_cast<float*>(x[kMeans].dev);
-        a.win = f.win_length;
-        a.scale = fc.c.scale;
-        a.preemph = fc.c.preemph;
-        a.remove_dc = fc.c.remove_dc;
-        time_begin(ctx, "clip_fbank");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank(a, ctx->stream));
-        time_end(ctx);
-        time_begin(ctx, "clip_fbank_mean");
-        FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank_mean(a, ctx->stream));
-        time_end(ctx);
-        if (fc.c.cmn) {
-            time_begin(ctx, "clip_fbank_sub");
-            FVAD_HIP(ctx, (hipError_t)fvad_launch_clip_fbank_sub(a, ctx->stream));
+        a.c = c;
+        a.window = reinterpret_cast<const float*>(x[kWindow].dev);
+        a.matrix_t = reinterpret_cast<const float*>(x[kMatrix].dev);
+        a.step = f.step;
+        a.hop = f.hop;
+        a.n_mels = f.n_mels;
+        a.tile_frames = tf;
+        a.floor = fc.c.floor;
+        float* const per_tile_dev = reinterpret_cast<float*>(x[kPerTile].dev);
+        float* const per_clip_dev = reinterpret_cast<float*>(x[kPerClip].dev);
+        if (f.snip) {
+            a.log_floor = (float)std::log((double)fc.c.floor);
+            a.tile_sum = per_tile_dev;
+            a.means = per_clip_dev;
+            a.win = f.taps;
+            a.scale = fc.c.scale;
+            a.preemph = fc.c.preemph;
+            a.remove_dc = fc.c.remove_dc;
+        } else {
+            a.log_floor = (float)std::log10((double)fc.c.floor);
+            a.tile_max = per_tile_dev;
+            a.feat_max = per_clip_dev;
+            if (fc.c.norm) { a.norm_range = fc.c.norm[0]; a.norm_offset = fc.c.norm[1]; a.norm_scale = fc.c.norm[2]; }
+            a.fft400 = f.n_fft == 400 && !ctx->tune.clip_mel_generic;
+        }
+        const FeatLaunch mel[] = {FEAT_LAUNCH(a.fft400 ? "clip_mel400" : "clip_mel", fvad_launch_clip_mel, true),
+                                  FEAT_LAUNCH("clip_mel_max", fvad_launch_clip_mel_max, true),
+                                  FEAT_LAUNCH("clip_mel_norm", fvad_launch_clip_mel_norm, fc.c.norm != nullptr)};
+        const FeatLaunch fbank[] = {FEAT_LAUNCH("clip_fbank", fvad_launch_clip_fbank, true),
+                                    FEAT_LAUNCH("clip_fbank_mean", fvad_launch_clip_fbank_mean, true),
+                                    FEAT_LAUNCH("clip_fbank_sub", fvad_launch_clip_fbank_sub, fc.c.cmn != 0)};
+        for (const FeatLaunch& l : f.snip ? fbank : mel) {
+            if (!l.on) continue;
+            time_begin(ctx, l.label);
+            const hipError_t e = (hipError_t)l.fn(a, ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, l.what);
             time_end(ctx);
         }
         return FVAD_OK;
     };
-    const int rc = run_clips(ctx, "fvad_clips_export_fbank", source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
+    const int rc = run_clips(ctx, fc.who, source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
     if (rc != FVAD_OK) return rc;
-    for (size_t i = 0; i < s.n_clips; ++i)
-        if (fc.n_frames) fc.n_frames[i] = frames[i];
-    if (fc.means) std::copy(means.begin(), means.end(), fc.means);
+    if (fc.n_frames) std::copy(frames.begin(), frames.end(), fc.n_frames);
+    if (fc.per_clip) std::copy(per_clip.begin(), per_clip.end(), fc.per_clip);
     return FVAD_OK;
 }
 
-int fbank_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FbankCall& fc)
+int features_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatCall& fc)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (s.n_clips == 0) return FVAD_OK;
     // every rule against the caller's own buffer first
     uint64_t total = 0;
     const char* why = "";
-    const int bad = fbank_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, 0, fc.f, fc.window,
-                                fc.matrix, fc.c, nullptr, nullptr, &total, &why);
-    if (bad != FVAD_OK) return set_err(ctx, bad, std::string("fvad_clips_export_fbank: ") + why);
-    return via_staging(ctx, "fvad_clips_export_fbank", "fvad_clips_export_fbank", o.p, (size_t)total * sizeof(float),
-                       [&](void* d_out) { return fbank_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, fc); });
+    const int bad = check_features(s, o, 0, fc, nullptr, nullptr, &total, &why);
+    if (bad != FVAD_OK) return set_err(ctx, bad, std::string(fc.who) + ": " + why);
+    return via_staging(ctx, fc.who, fc.who, o.p, (size_t)total * sizeof(float),
+                       [&](void* d_out) { return features_device(ctx, s, ClipOut{o.format, d_out, (size_t)total, o.rep}, fc); });
+}
+
+// the two families' calls
+FeatCall mel_call(uint32_t step, const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix, float floor,
+                  const float* norm, uint64_t* n_frames, float* feat_max)
+{
+    return FeatCall{"fvad_clips_export_mel", Feat{step, skips, n_fft, n_fft, hop, n_mels, false}, window, matrix, FeatCond{floor, norm, 0.0f, 0.0f, 0, 0}, n_frames, feat_max};
+}
+
+FeatCall fbank_call(uint32_t step, const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels,
+                    const float* matrix, float scale, float preemph, int remove_dc, float floor, int cmn, uint64_t* n_frames, float* means)
+{
+    return FeatCall{"fvad_clips_export_fbank", Feat{step, skips, win_length, n_fft, hop, n_mels, true}, window, matrix, FeatCond{floor, nullptr, scale, preemph, remove_dc, cmn}, n_frames, means};
 }
 
 // the argument rules of fvad_clips_plan: the full-rate slots
@@ -796,9 +751,9 @@ int fvad_clips_export_mel_device(fvad_ctx* ctx, const void* d_src, int src_forma
                                  const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels,
                                  const float* matrix, float floor, const float* norm, uint64_t* n_frames, float* feat_max)
 {
-    return mel_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+    return features_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                       ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                      MelCall{Mel{step, skips, n_fft, hop, n_mels}, window, matrix, floor, norm, n_frames, feat_max});
+                      mel_call(step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
 }
 
 int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -807,9 +762,9 @@ int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size
                           uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix, float floor,
                           const float* norm, uint64_t* n_frames, float* feat_max)
 {
-    return mel_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+    return features_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                     ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                    MelCall{Mel{step, skips, n_fft, hop, n_mels}, window, matrix, floor, norm, n_frames, feat_max});
+                    mel_call(step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
 }
 
 int fvad_clips_export_fbank_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -819,9 +774,9 @@ int fvad_clips_export_fbank_device(fvad_ctx* ctx, const void* d_src, int src_for
                                    uint32_t n_mels, const float* matrix, float scale, float preemph, int remove_dc, float floor, int cmn,
                                    uint64_t* n_frames, float* means)
 {
-    return fbank_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+    return features_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                        FbankCall{Fbank{step, skips, win_length, n_fft, hop, n_mels}, window, matrix, FbankCond{scale, preemph, remove_dc, floor, cmn}, n_frames, means});
+                        fbank_call(step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
 }
 
 int fvad_clips_export_fbank(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -830,9 +785,9 @@ int fvad_clips_export_fbank(fvad_ctx* ctx, const void* d_src, int src_format, si
                             uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix,
                             float scale, float preemph, int remove_dc, float floor, int cmn, uint64_t* n_frames, float* means)
 {
-    return fbank_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
+    return features_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                      FbankCall{Fbank{step, skips, win_length, n_fft, hop, n_mels}, window, matrix, FbankCond{scale, preemph, remove_dc, floor, cmn}, n_frames, means});
+                      fbank_call(step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
 }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/fvad.h"
+#include "feature_frames.h"
 
 enum { FVAD_ACT_NONE = 0, FVAD_ACT_RELU = 1, FVAD_ACT_SIGMOID = 2 };
 
@@ -504,51 +505,42 @@ template <typename B> struct ClipResampleArgs {
 int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipArgs>& a, hipStream_t stream); // (after fvad_launch_clip_pick)
 int fvad_launch_clip_gather_resampled(const ClipResampleArgs<ClipSplitArgs>& a, hipStream_t stream);
 
-// The log-mel features (kernels_clips_mel.hip, fvad_clips_export_mel*): of the picked channel's strided stream s[i] = sample
-// skip + i * step (L = ceil((len - skip) / step) of them) the frames t < T = floor(L / hop) of n_fft taps, centred with
-// reflection, as power spectrum -> mel bands -> log10.  RMS and pick are the kernels above over every sample.  A tile is
-// clip_mel_tile_frames consecutive frames of one clip; c.tile_prefix / c.n_tiles count these tiles, c.out is f32 and
-// jobs[i].out_off the clip's slot of [T][n_mels] floats.
+// The feature exports (kernels_clips_mel.hip), one argument struct for both families.  RMS and pick are the kernels above over
+// every sample.  Of the picked channel's strided stream s[i] = sample skip + i * step (L of them) the frames t < T, a tile
+// feat_tile_frames consecutive frames of one clip (feature_frames.h states L, T and the tile); c.tile_prefix / c.n_tiles count
+// these tiles, c.out is f32 and jobs[i].out_off the clip's slot of [T][n_mels] floats.
+// - log-mel (fvad_clips_export_mel*): frames of n_fft taps centred with reflection, as power spectrum -> mel bands -> log10;
+//   tile_frames = feat_tile_frames(n_fft, hop), log_floor = log10(floor).  The fields from tile_sum on are not used.
+// - Kaldi-style filter bank (fvad_clips_export_fbank*): of the stream times `scale` frames of `win` taps from t * hop on
+//   (snip_edges: no tap outside the stream), each with its mean removed, pre-emphasised, windowed and zero-padded to pl.n, then
+//   power spectrum -> bands -> ln; window [win], tile_frames = feat_tile_frames(win, hop), log_floor = ln(floor).  tile_max,
+//   feat_max, the norm and fft400 are not used.
 constexpr uint32_t kClipMelNfftMax = 2048;  // FVAD_CLIP_MEL_NFFT_MAX
 constexpr uint32_t kClipMelBandsMax = 128;  // FVAD_CLIP_MEL_BANDS_MAX
-constexpr uint32_t kClipMelTileFrames = 32; // four wavefronts of eight frames in the 400-point form
-// the frames of a tile: its window (F - 1) hop + n_fft of the stream fits kClipTile staged samples
-constexpr uint32_t clip_mel_tile_frames(uint32_t n_fft, uint32_t hop)
-{
-    return ((uint32_t)kClipTile - n_fft) / hop + 1 < kClipMelTileFrames ? ((uint32_t)kClipTile - n_fft) / hop + 1 : kClipMelTileFrames;
-}
-struct ClipMelArgs {
+static_assert(fvad::kFeatSrcTile == (uint32_t)kClipTile, "a feature tile's window is staged as a clip tile is");
+struct ClipFeatArgs {
     ClipArgs c;
     VadFftPlan pl;         // n = n_fft: tw, st and the radices of the generic transform (win and norm are not used)
-    const float* window;   // [n_fft] (device), the caller's
+    const float* window;   // [n_fft] or [win] (device), the caller's
     const float* matrix_t; // [n_fft / 2 + 1][n_mels] (device): the caller's matrix transposed, so that lanes m read neighbours
     float* tile_max;       // [c.n_tiles]: a tile's largest feature
     float* feat_max;       // [c.n_clips]: a clip's largest feature (clip_mel_max)
     uint32_t step, hop, n_mels, tile_frames;
-    float floor, log_floor; // log_floor = log10(floor), evaluated on the host in double and rounded once
+    float floor, log_floor; // the logarithm of the floor, evaluated on the host in double and rounded once
     float norm_range, norm_offset, norm_scale;
     int fft400;            // the eight-frames-per-wavefront transform (n_fft == 400 only)
-};
-int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
-int fvad_launch_clip_mel_max(const ClipMelArgs& a, hipStream_t stream);  // (after fvad_launch_clip_mel)
-int fvad_launch_clip_mel_norm(const ClipMelArgs& a, hipStream_t stream); // (after fvad_launch_clip_mel_max)
-
-// The Kaldi-style filter-bank features (kernels_clips_mel.hip, fvad_clips_export_fbank*): of the same stream times `scale` the
-// frames t < T = 1 + (L - win) / hop of `win` taps from t * hop on (snip_edges: no tap outside the stream), each with its mean
-// removed, pre-emphasised, windowed and zero-padded to m.pl.n, then power spectrum -> bands -> ln.  m is the mel export's, with
-// m.window [win], m.tile_frames = clip_mel_tile_frames(win, hop) and m.log_floor = ln(floor); m.tile_max, m.feat_max and the norm
-// are not used.
-struct ClipFbankArgs {
-    ClipMelArgs m;
-    float* tile_sum;  // [m.c.n_tiles][n_mels]: a tile's features added over ascending t, band by band
-    float* means;     // [m.c.n_clips][n_mels]: the tiles' sums added in tile order, over f32(T) (clip_fbank_mean)
+    float* tile_sum;       // [c.n_tiles][n_mels]: a tile's features added over ascending t, band by band
+    float* means;          // [c.n_clips][n_mels]: the tiles' sums added in tile order, over f32(T) (clip_fbank_mean)
     uint32_t win;
     float scale, preemph;
     int remove_dc;
 };
-int fvad_launch_clip_fbank(const ClipFbankArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
-int fvad_launch_clip_fbank_mean(const ClipFbankArgs& a, hipStream_t stream); // (after fvad_launch_clip_fbank)
-int fvad_launch_clip_fbank_sub(const ClipFbankArgs& a, hipStream_t stream);  // (after fvad_launch_clip_fbank_mean)
+int fvad_launch_clip_mel(const ClipFeatArgs& a, hipStream_t stream);        // (after fvad_launch_clip_pick)
+int fvad_launch_clip_mel_max(const ClipFeatArgs& a, hipStream_t stream);    // (after fvad_launch_clip_mel)
+int fvad_launch_clip_mel_norm(const ClipFeatArgs& a, hipStream_t stream);   // (after fvad_launch_clip_mel_max)
+int fvad_launch_clip_fbank(const ClipFeatArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
+int fvad_launch_clip_fbank_mean(const ClipFeatArgs& a, hipStream_t stream); // (after fvad_launch_clip_fbank)
+int fvad_launch_clip_fbank_sub(const ClipFeatArgs& a, hipStream_t stream);  // (after fvad_launch_clip_fbank_mean)
 
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in

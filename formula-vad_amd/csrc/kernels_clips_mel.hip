@@ -4,7 +4,7 @@
 // What a recogniser takes in, computed where the denoised lanes already are; only [T][n_mels] floats per clip leave the device.
 // RMS and pick are kernels_clips.hip's over EVERY sample of the clip.
 //
-// Work unit: a tile of clip_mel_tile_frames(n_fft, hop) <= 32 consecutive frames of one clip, found by a search of the host-built
+// Work unit: a tile of feat_tile_frames(n_fft, hop) <= 32 consecutive frames of one clip, found by a search of the host-built
 // prefix table with the block index.  The tile's window of the stream -- (F - 1) hop + n_fft samples at most, cut to the clip --
 // is staged through LDS once as f32: stage_tile (f32 lanes at step 1: 16-byte loads), stage_tile_strided (f32 lanes at a step:
 // one dword per kept sample) or one converting load per kept sample (PCM16).  Taps in front of the clip's first or behind its
@@ -36,7 +36,10 @@
 // in LDS by the workgroup (fbank_condition: scale at the frame load, the mean in a fixed order, pre-emphasis reading d[i - 1] from
 // LDS) and zero-padded to n_fft, the same generic_rfft call and projection loop, logf; lane m also adds its features over the
 // tile's frames in ascending t.  clip_fbank_mean_kernel adds the tiles' sums in tile order by one lane per (clip, band) and divides
-// by f32(T); clip_fbank_sub_kernel subtracts element-wise.  The parent's instances are kFbank off.
+// by f32(T); clip_fbank_sub_kernel subtracts element-wise.  The log-mel export's instances are kFbank off.
+// Both families take one argument struct (ClipFeatArgs of kernels.h: the filter-bank fields behind the log-mel ones), count a
+// clip's frames and a tile's by feature_frames.h's functions, which the host rules use too (clip_stream_len, mel_tile), and
+// launch their tile kernels through one ladder (launch_tiles: the dynamic-LDS attribute, then the instance of the source's format).
 // Resources (make resource-usage, gfx950): see the table in DESIGN 7.2; clip_mel400_kernel is LDS-bound at two workgroups per
 // CU (73.3 KB each: 177 VGPRs, two wavefronts per SIMD); clip_mel_kernel takes 28.0 KB at 400 / 160 (80 VGPRs, five workgroups per CU).
 #include <hip/hip_runtime.h>
@@ -58,15 +61,20 @@ struct MelTile {
     long long t0, L, w0, w1;
 };
 
-// kSnip (the filter-bank export): frames of `win` taps from t hop on, T = 1 + (L - win) / hop of them, none leaving the stream
+// job j's stream: feat_stream_len's L in the form the kernels have always had (len + step cannot wrap here: the clip lies inside
+// the lanes).  Its frames are feature_frames.h's feat_frames in the kernels' integer type, long long
+__device__ inline long long clip_stream_len(const ClipFeatArgs& a, const ClipJob& j) { return (long long)((j.len - j.skip + a.step - 1) / a.step); }
+
+// kSnip (the filter-bank export): frames of a.win taps from t hop on, none leaving the stream (L >= win: the plan); a.pl.n taps
+// centred otherwise
 template <bool kSnip = false>
-__device__ inline MelTile mel_tile(const ClipMelArgs& a, const ClipJob& j, uint32_t clip, uint32_t win = 0)
+__device__ inline MelTile mel_tile(const ClipFeatArgs& a, const ClipJob& j, uint32_t clip)
 {
     MelTile t;
     t.clip = clip;
-    t.L = (long long)((j.len - j.skip + a.step - 1) / a.step);
-    const long long taps = kSnip ? (long long)win : (long long)a.pl.n;
-    const long long T = kSnip ? (t.L - taps) / a.hop + 1 : t.L / a.hop, pad = kSnip ? 0 : a.pl.n / 2;
+    t.L = clip_stream_len(a, j);
+    const long long taps = kSnip ? (long long)a.win : (long long)a.pl.n;
+    const long long T = fvad::feat_frames<long long>(kSnip, t.L, taps, a.hop), pad = fvad::feat_pad<int>(kSnip, a.pl.n);
     t.t0 = (long long)(blockIdx.x - a.c.tile_prefix[clip]) * a.tile_frames;
     t.nf = (int)min((long long)a.tile_frames, T - t.t0);
     const long long lo = t.t0 * a.hop - pad, hi = (t.t0 + t.nf - 1) * a.hop - pad + taps;
@@ -90,7 +98,7 @@ template <typename S> struct MelSrc {
 };
 
 template <typename S>
-__device__ inline MelSrc<S> mel_stage(const ClipMelArgs& a, const ClipJob& j, const MelTile& t, float* lds)
+__device__ inline MelSrc<S> mel_stage(const ClipFeatArgs& a, const ClipJob& j, const MelTile& t, float* lds)
 {
     const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
     const S* pc = static_cast<const S*>(a.c.src) + j.src_off + (uint64_t)ch * a.c.lane_stride + j.skip;
@@ -128,9 +136,6 @@ __host__ __device__ inline uint32_t mel_stage_floats(uint32_t n_fft, uint32_t ho
 // the dynamic LDS of clip_mel_kernel behind `stage` floats of the window: s_win, s_frame, bufA, bufB, s_pow
 inline size_t mel_generic_lds(uint32_t stage, uint32_t n_fft) { return (size_t)(stage + 2 * n_fft + 4 * (n_fft / 2 + 1) + (n_fft / 2 + 1)) * sizeof(float); }
 
-__device__ inline const ClipMelArgs& mel_args(const ClipMelArgs& a) { return a; }
-__device__ inline const ClipMelArgs& mel_args(const ClipFbankArgs& a) { return a.m; }
-
 // The conditioning of one filter-bank frame by the whole workgroup (fvad.h's order, every operation rounded on its own): x the
 // frame's `win` staged samples, y [n_fft] what generic_rfft windows, d [win] scratch, red one float per wavefront.
 //   x_i = x[i] * scale          -- the scale is applied HERE, at the frame load, not at staging (one rounded product either way)
@@ -141,9 +146,9 @@ __device__ inline const ClipMelArgs& mel_args(const ClipFbankArgs& a) { return a
 //   d_i = x_i - mean            -- (x_i without remove_dc), written to LDS
 //   y_i = d_i - preemph * d_{i - 1}, d_{-1} = d_0 (Kaldi's replicated first sample); y_i = 0 for win <= i < n_fft
 // Ends with a barrier.
-__device__ inline void fbank_condition(const ClipFbankArgs& a, const float* x, float* y, float* d, float* red)
+__device__ inline void fbank_condition(const ClipFeatArgs& a, const float* x, float* y, float* d, float* red)
 {
-    const int tid = threadIdx.x, win = (int)a.win, n_fft = a.m.pl.n;
+    const int tid = threadIdx.x, win = (int)a.win, n_fft = a.pl.n;
     float mean = 0.0f;
     if (a.remove_dc) {
         float v = 0.0f;
@@ -164,22 +169,17 @@ __device__ inline void fbank_condition(const ClipFbankArgs& a, const float* x, f
 
 } // namespace
 
-// what clip_mel_kernel<S, kFbank> takes: the parent's arguments, or the filter-bank export's around them
-template <bool kFbank> struct MelKernelArgs { using type = ClipMelArgs; };
-template <> struct MelKernelArgs<true> { using type = ClipFbankArgs; };
-
 // ---------------------------------------------------------------------------- any even n_fft
 // kFbank: the filter-bank export's frames (snip_edges, conditioned, win taps zero-padded to n_fft, natural log) and, in place of
 // the tile's maximum, the tile's sum per band over ascending t by lane m
 template <typename S, bool kFbank>
-__global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename MelKernelArgs<kFbank>::type args)
+__global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipFeatArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[kThreads / 64];
-    const ClipMelArgs& a = mel_args(args);
     const int n_fft = a.pl.n, M = n_fft / 2, NB = M + 1, pad = M;
     int taps = n_fft;
-    if constexpr (kFbank) taps = (int)args.win;
+    if constexpr (kFbank) taps = (int)a.win;
     float* s_stage = sm;
     float* s_win = s_stage + mel_stage_floats(taps, a.hop, a.tile_frames);
     float* s_frame = s_win + n_fft;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename MelKernelAr
     const int tid = threadIdx.x;
     const uint32_t clip = find_clip(a.c.tile_prefix, a.c.n_clips, blockIdx.x);
     const ClipJob j = a.c.jobs[clip];
-    const MelTile t = mel_tile<kFbank>(a, j, clip, taps);
+    const MelTile t = mel_tile<kFbank>(a, j, clip);
     if constexpr (kFbank) {
         for (int i = tid; i < n_fft; i += kThreads) s_win[i] = i < taps ? a.window[i] : 0.0f;
     } else {
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename MelKernelAr
     for (int f = 0; f < t.nf; ++f) {
         if constexpr (kFbank) {
             // every tap is staged: the tile's window starts at its first frame's first tap (w0 == t0 hop)
-            fbank_condition(args, src.lds + (size_t)f * a.hop, s_frame, reinterpret_cast<float*>(bufB), red);
+            fbank_condition(a, src.lds + (size_t)f * a.hop, s_frame, reinterpret_cast<float*>(bufB), red);
         } else {
             const long long j0 = (t.t0 + f) * a.hop - pad;
             for (int i = tid; i < n_fft; i += kThreads) s_frame[i] = src.at(j0 + i);
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename MelKernelAr
         __syncthreads(); // the next frame overwrites s_frame and s_pow
     }
     if constexpr (kFbank) {
-        if (tid < (int)a.n_mels) args.tile_sum[(size_t)blockIdx.x * a.n_mels + tid] = vsum;
+        if (tid < (int)a.n_mels) a.tile_sum[(size_t)blockIdx.x * a.n_mels + tid] = vsum;
     } else {
         tile_max_store(vmax, red, a.tile_max + blockIdx.x);
     }
@@ -261,7 +261,7 @@ __device__ __forceinline__ void dft25(cpx (&v)[25], const float* __restrict__ tw
 } // namespace
 
 template <typename S>
-__global__ __launch_bounds__(kThreads) void clip_mel400_kernel(ClipMelArgs a)
+__global__ __launch_bounds__(kThreads) void clip_mel400_kernel(ClipFeatArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[kThreads / 64];
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel400_kernel(ClipMelArgs a)
 }
 
 // one lane per clip: the maximum of its tiles' maxima, in tile order (a maximum has no rounding)
-__global__ __launch_bounds__(64) void clip_mel_max_kernel(ClipMelArgs a)
+__global__ __launch_bounds__(64) void clip_mel_max_kernel(ClipFeatArgs a)
 {
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
     if (c >= a.c.n_clips) return;
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(64) void clip_mel_max_kernel(ClipMelArgs a)
 
 // feat' = (max(feat, feat_max - range) + offset) * scale over a tile's cells: one rounded subtraction, sum and product (fp
 // contraction is off for the library)
-__global__ __launch_bounds__(kThreads) void clip_mel_norm_kernel(ClipMelArgs a)
+__global__ __launch_bounds__(kThreads) void clip_mel_norm_kernel(ClipFeatArgs a)
 {
     const uint32_t clip = find_clip(a.c.tile_prefix, a.c.n_clips, blockIdx.x);
     const ClipJob j = a.c.jobs[clip];
@@ -393,84 +393,79 @@ __global__ __launch_bounds__(kThreads) void clip_mel_norm_kernel(ClipMelArgs a)
 
 // ---------------------------------------------------------------------------- the filter-bank export's means
 // one lane per (clip, band): the tiles' sums added in tile order onto 0.0f, over f32(T) -- one rounded division
-__global__ __launch_bounds__(kThreads) void clip_fbank_mean_kernel(ClipFbankArgs a)
+__global__ __launch_bounds__(kThreads) void clip_fbank_mean_kernel(ClipFeatArgs a)
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= (unsigned long long)a.m.c.n_clips * a.m.n_mels) return;
-    const uint32_t c = (uint32_t)(i / a.m.n_mels), m = (uint32_t)(i - (unsigned long long)c * a.m.n_mels);
-    const ClipJob j = a.m.c.jobs[c];
-    const long long L = (long long)((j.len - j.skip + a.m.step - 1) / a.m.step), T = (L - a.win) / a.m.hop + 1;
+    if (i >= (unsigned long long)a.c.n_clips * a.n_mels) return;
+    const uint32_t c = (uint32_t)(i / a.n_mels), m = (uint32_t)(i - (unsigned long long)c * a.n_mels);
+    const ClipJob j = a.c.jobs[c];
+    const long long T = fvad::feat_frames<long long>(true, clip_stream_len(a, j), a.win, a.hop);
     float s = 0.0f;
-    for (uint32_t g = a.m.c.tile_prefix[c]; g < a.m.c.tile_prefix[c + 1]; ++g) s += a.tile_sum[(size_t)g * a.m.n_mels + m];
+    for (uint32_t g = a.c.tile_prefix[c]; g < a.c.tile_prefix[c + 1]; ++g) s += a.tile_sum[(size_t)g * a.n_mels + m];
     a.means[i] = s / (float)T;
 }
 
 // feat' = feat - mean_m over a tile's cells: one rounded subtraction
-__global__ __launch_bounds__(kThreads) void clip_fbank_sub_kernel(ClipFbankArgs a)
+__global__ __launch_bounds__(kThreads) void clip_fbank_sub_kernel(ClipFeatArgs a)
 {
-    const uint32_t clip = find_clip(a.m.c.tile_prefix, a.m.c.n_clips, blockIdx.x);
-    const ClipJob j = a.m.c.jobs[clip];
-    const MelTile t = mel_tile<true>(a.m, j, clip, a.win);
-    float* out = static_cast<float*>(a.m.c.out) + j.out_off + (unsigned long long)t.t0 * a.m.n_mels;
-    const float* mean = a.means + (size_t)clip * a.m.n_mels;
-    const int n_out = t.nf * (int)a.m.n_mels;
-    for (int o = threadIdx.x; o < n_out; o += kThreads) out[o] = out[o] - mean[o % (int)a.m.n_mels];
+    const uint32_t clip = find_clip(a.c.tile_prefix, a.c.n_clips, blockIdx.x);
+    const ClipJob j = a.c.jobs[clip];
+    const MelTile t = mel_tile<true>(a, j, clip);
+    float* out = static_cast<float*>(a.c.out) + j.out_off + (unsigned long long)t.t0 * a.n_mels;
+    const float* mean = a.means + (size_t)clip * a.n_mels;
+    const int n_out = t.nf * (int)a.n_mels;
+    for (int o = threadIdx.x; o < n_out; o += kThreads) out[o] = out[o] - mean[o % (int)a.n_mels];
 }
 
-int fvad_launch_clip_fbank(const ClipFbankArgs& a, hipStream_t stream)
+namespace {
+
+// one workgroup per tile with `lds` bytes of dynamic LDS (which may be above the default limit), the instance by the source's format
+using FeatKernel = void (*)(ClipFeatArgs);
+int launch_tiles(FeatKernel f32, FeatKernel i16, size_t lds, const ClipFeatArgs& a, hipStream_t stream)
 {
-    const dim3 grid(a.m.c.n_tiles), block(kThreads);
-    const size_t lds = mel_generic_lds(mel_stage_floats(a.win, a.m.hop, a.m.tile_frames), (uint32_t)a.m.pl.n); // win 400, n_fft 512, hop 160: 30.0 KB
-    const void* fn = a.m.c.src_i16 ? (const void*)clip_mel_kernel<int16_t, true> : (const void*)clip_mel_kernel<float, true>;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const FeatKernel k = a.c.src_i16 ? i16 : f32;
+    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    if (a.m.c.src_i16) hipLaunchKernelGGL((clip_mel_kernel<int16_t, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((clip_mel_kernel<float, true>), grid, block, lds, stream, a);
+    hipLaunchKernelGGL(k, dim3(a.c.n_tiles), dim3(kThreads), lds, stream, a);
     return (int)hipGetLastError();
 }
 
-int fvad_launch_clip_fbank_mean(const ClipFbankArgs& a, hipStream_t stream)
+} // namespace
+
+int fvad_launch_clip_fbank(const ClipFeatArgs& a, hipStream_t stream)
 {
-    const unsigned long long n = (unsigned long long)a.m.c.n_clips * a.m.n_mels;
+    const size_t lds = mel_generic_lds(mel_stage_floats(a.win, a.hop, a.tile_frames), (uint32_t)a.pl.n); // win 400, n_fft 512, hop 160: 30.0 KB
+    return launch_tiles(clip_mel_kernel<float, true>, clip_mel_kernel<int16_t, true>, lds, a, stream);
+}
+
+int fvad_launch_clip_fbank_mean(const ClipFeatArgs& a, hipStream_t stream)
+{
+    const unsigned long long n = (unsigned long long)a.c.n_clips * a.n_mels;
     hipLaunchKernelGGL(clip_fbank_mean_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, a);
     return (int)hipGetLastError();
 }
 
-int fvad_launch_clip_fbank_sub(const ClipFbankArgs& a, hipStream_t stream)
+int fvad_launch_clip_fbank_sub(const ClipFeatArgs& a, hipStream_t stream)
 {
-    hipLaunchKernelGGL(clip_fbank_sub_kernel, dim3(a.m.c.n_tiles), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(clip_fbank_sub_kernel, dim3(a.c.n_tiles), dim3(kThreads), 0, stream, a);
     return (int)hipGetLastError();
 }
 
-int fvad_launch_clip_mel(const ClipMelArgs& a, hipStream_t stream)
+int fvad_launch_clip_mel(const ClipFeatArgs& a, hipStream_t stream)
 {
-    const dim3 grid(a.c.n_tiles), block(kThreads);
     const uint32_t n_fft = (uint32_t)a.pl.n, stage = mel_stage_floats(n_fft, a.hop, a.tile_frames);
-    if (a.fft400) {
-        const size_t lds = (size_t)(stage + n_fft + kM4 + kClipMelTileFrames * kSlab) * sizeof(float); // 73.3 KB: above the default limit
-        const void* fn = a.c.src_i16 ? (const void*)clip_mel400_kernel<int16_t> : (const void*)clip_mel400_kernel<float>;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (a.c.src_i16) hipLaunchKernelGGL(clip_mel400_kernel<int16_t>, grid, block, lds, stream, a);
-        else hipLaunchKernelGGL(clip_mel400_kernel<float>, grid, block, lds, stream, a);
-    } else {
-        const size_t lds = mel_generic_lds(stage, n_fft); // n_fft 400, hop 160: 28.0 KB; at most 68.0 KB
-        const void* fn = a.c.src_i16 ? (const void*)clip_mel_kernel<int16_t, false> : (const void*)clip_mel_kernel<float, false>;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if (a.c.src_i16) hipLaunchKernelGGL((clip_mel_kernel<int16_t, false>), grid, block, lds, stream, a);
-        else hipLaunchKernelGGL((clip_mel_kernel<float, false>), grid, block, lds, stream, a);
-    }
-    return (int)hipGetLastError();
+    // the 400-point form: 73.3 KB; the generic one: 28.0 KB at n_fft 400, hop 160, at most 68.0 KB
+    if (a.fft400) return launch_tiles(clip_mel400_kernel<float>, clip_mel400_kernel<int16_t>, (size_t)(stage + n_fft + kM4 + fvad::kFeatTileFrames * kSlab) * sizeof(float), a, stream);
+    return launch_tiles(clip_mel_kernel<float, false>, clip_mel_kernel<int16_t, false>, mel_generic_lds(stage, n_fft), a, stream);
 }
 
-int fvad_launch_clip_mel_max(const ClipMelArgs& a, hipStream_t stream)
+int fvad_launch_clip_mel_max(const ClipFeatArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(clip_mel_max_kernel, dim3((a.c.n_clips + 63) / 64), dim3(64), 0, stream, a);
     return (int)hipGetLastError();
 }
 
-int fvad_launch_clip_mel_norm(const ClipMelArgs& a, hipStream_t stream)
+int fvad_launch_clip_mel_norm(const ClipFeatArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(clip_mel_norm_kernel, dim3(a.c.n_tiles), dim3(kThreads), 0, stream, a);
     return (int)hipGetLastError();

@@ -601,12 +601,39 @@ def fbank_window():
     return ((0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))) ** 0.85).astype(np.float32)
 
 
+# what _features_share takes per kind of features: the parameters, the stream lengths L that have a frame (the skip rule), the
+# export's call with the kind's window and designer, and the manifest entry
+_FEATURES = {
+    "logmel": dict(
+        p=LOGMEL, keeps=lambda p, L: L >= p["n_fft"] // 2 + 1 and L >= p["hop"],
+        export=lambda ctx, p, src, rows, skips, norm: ctx.clips_export_mel(
+            *src, rows, logmel_window(), fv.mel_design(p["sample_rate"], p["n_fft"], p["n_mels"], p["fmin"], p["fmax"]), step=p["step"], skips=skips, hop=p["hop"], floor=p["floor"], norm=CLIP_FEATURES_NORM[norm]),
+        entry=lambda p, file, T, first, res, j, norm: {
+            "file": file, "frames": T, "n_mels": p["n_mels"], "n_fft": p["n_fft"], "hop": p["hop"],
+            "sample_rate": p["sample_rate"], "first_sample": first, "best_channel": int(res["best_channel"][j]),
+            "max": float(res["feat_max"][j]), "floor": p["floor"], "norm": norm,
+            "mel": {"design": "slaney", "fmin": p["fmin"], "fmax": p["fmax"]}}),
+    "fbank": dict(
+        p=FBANK, keeps=lambda p, L: L >= p["win_length"],
+        export=lambda ctx, p, src, rows, skips, norm: ctx.clips_export_fbank(
+            *src, rows, fbank_window(), fv.mel_design_kaldi(p["sample_rate"], p["n_fft"], p["n_mels"], p["low_freq"], p["high_freq"]), n_fft=p["n_fft"], step=p["step"], skips=skips, hop=p["hop"], scale=p["scale"], preemph=p["preemph"],
+            remove_dc=p["remove_dc"], floor=p["floor"], cmn=norm == "cmn"),
+        entry=lambda p, file, T, first, res, j, norm: dict({
+            "file": file, "kind": "fbank", "frames": T, "n_mels": p["n_mels"], "win_length": p["win_length"],
+            "n_fft": p["n_fft"], "hop": p["hop"], "sample_rate": p["sample_rate"], "first_sample": first,
+            "best_channel": int(res["best_channel"][j]), "window": "povey", "preemph": p["preemph"], "remove_dc": bool(p["remove_dc"]),
+            "scale": p["scale"], "snip_edges": True, "log": "ln", "floor": p["floor"], "norm": norm,
+            "mel": {"design": "kaldi", "low_freq": p["low_freq"], "high_freq": p["high_freq"]}},
+            **({"means": [float(v) for v in res["means"][j]]} if norm == "cmn" else {}))),
+}
+
+
 def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, manifests, features_norm, features="logmel"):
     """the features of run_clips: one fvad_clips_export_mel (or fvad_clips_export_fbank) over the denoised lanes' clips,
     NAME-####-denoised.logmel.npy (.fbank.npy) per clip and its manifest entry under "features".  A clip too short for one
     reflected frame (for one frame of 400) has no entry and is counted in features_skipped"""
-    fbank = features == "fbank"
-    p = FBANK if fbank else LOGMEL
+    fam = _FEATURES[features]
+    p = fam["p"]
     rows, owner = [], []
     for i, (segs, _) in enumerate(per_inst):
         clips, _ = fv.clips_from_segments(segs, lane0[i], n_channels[i], avail[i])
@@ -616,8 +643,7 @@ def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, 
             while (segs[k][0], segs[k][1]) != (c[2], c[3]):
                 k += 1
             skip = int(fv.clips_phase_skips(c[2:3], p["step"], CLIP_PHASE["denoised"])[0])
-            L = -(-(int(c[3] - c[2]) - skip) // p["step"])
-            if (L >= p["win_length"]) if fbank else (L >= p["n_fft"] // 2 + 1 and L >= p["hop"]):
+            if fam["keeps"](p, -(-(int(c[3] - c[2]) - skip) // p["step"])):
                 rows.append(c)
                 owner.append((i, k))
             else:
@@ -627,36 +653,12 @@ def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, 
         return
     rows = np.array(rows, np.uint64)
     skips = fv.clips_phase_skips(rows[:, 2], p["step"], CLIP_PHASE["denoised"])
-    if fbank:
-        matrix = fv.mel_design_kaldi(p["sample_rate"], p["n_fft"], p["n_mels"], p["low_freq"], p["high_freq"])
-        res = ctx.clips_export_fbank(r.d_den, False, r.n_lanes, r.n_den, r.n_den, rows, fbank_window(), matrix, n_fft=p["n_fft"], step=p["step"],
-                                     skips=skips, hop=p["hop"], scale=p["scale"], preemph=p["preemph"], remove_dc=p["remove_dc"], floor=p["floor"],
-                                     cmn=features_norm == "cmn")
-        for j, (i, k) in enumerate(owner):
-            o, T = int(res["offsets"][j]), int(res["n_frames"][j])
-            path = os.path.join(out_dir, "{}-{:04d}-denoised.fbank.npy".format(insts[i]["name"], k))
-            np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
-            e = {"file": os.path.basename(path), "kind": "fbank", "frames": T, "n_mels": p["n_mels"], "win_length": p["win_length"],
-                 "n_fft": p["n_fft"], "hop": p["hop"], "sample_rate": p["sample_rate"], "first_sample": int(rows[j, 2]) + int(skips[j]),
-                 "best_channel": int(res["best_channel"][j]), "window": "povey", "preemph": p["preemph"], "remove_dc": bool(p["remove_dc"]),
-                 "scale": p["scale"], "snip_edges": True, "log": "ln", "floor": p["floor"], "norm": features_norm,
-                 "mel": {"design": "kaldi", "low_freq": p["low_freq"], "high_freq": p["high_freq"]}}
-            if features_norm == "cmn":
-                e["means"] = [float(v) for v in res["means"][j]]
-            manifests[i]["clips"][k]["features"] = e
-        return
-    matrix = fv.mel_design(p["sample_rate"], p["n_fft"], p["n_mels"], p["fmin"], p["fmax"])
-    res = ctx.clips_export_mel(r.d_den, False, r.n_lanes, r.n_den, r.n_den, rows, logmel_window(), matrix, step=p["step"], skips=skips,
-                               hop=p["hop"], floor=p["floor"], norm=CLIP_FEATURES_NORM[features_norm])
+    res = fam["export"](ctx, p, (r.d_den, False, r.n_lanes, r.n_den, r.n_den), rows, skips, features_norm)
     for j, (i, k) in enumerate(owner):
         o, T = int(res["offsets"][j]), int(res["n_frames"][j])
-        path = os.path.join(out_dir, "{}-{:04d}-denoised.logmel.npy".format(insts[i]["name"], k))
+        path = os.path.join(out_dir, "{}-{:04d}-denoised.{}.npy".format(insts[i]["name"], k, features))
         np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
-        manifests[i]["clips"][k]["features"] = {
-            "file": os.path.basename(path), "frames": T, "n_mels": p["n_mels"], "n_fft": p["n_fft"], "hop": p["hop"],
-            "sample_rate": p["sample_rate"], "first_sample": int(rows[j, 2]) + int(skips[j]), "best_channel": int(res["best_channel"][j]),
-            "max": float(res["feat_max"][j]), "floor": p["floor"], "norm": features_norm,
-            "mel": {"design": "slaney", "fmin": p["fmin"], "fmax": p["fmax"]}}
+        manifests[i]["clips"][k]["features"] = fam["entry"](p, os.path.basename(path), T, int(rows[j, 2]) + int(skips[j]), res, j, features_norm)
 
 
 def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs, features=None, features_norm=None):

@@ -23,7 +23,7 @@ EPS = 2.0 ** -24
 FLOOR = np.float32(1e-10)
 SHAPES = [(400, 160, 80), (512, 128, 128), (8, 4, 3), (4, 1, 1), (254, 100, 5), (2048, 512, 40)]  # (n_fft, hop, n_mels)
 TABLE_SHAPES = SHAPES[:3]
-TILE, TILE_FRAMES = 8192, 32     # kClipTile, kClipMelTileFrames
+TILE, TILE_FRAMES = 8192, 32     # kClipTile (kFeatSrcTile), kFeatTileFrames
 
 # the worst distance of f32_eval from the float64 model over case_table(), in units U:
 # measured 2026-10-20 with `python tests/clip_mel_cases.py` (numpy 2.2, single-precision pocketfft)

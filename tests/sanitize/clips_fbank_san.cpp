@@ -1,4 +1,4 @@
-// clips_fbank_san.cpp -- fvad_clips_plan_fbank, fvad_clips_fbank_check and fvad_mel_design_kaldi (csrc/host_clips_fbank.cpp, host
+// clips_fbank_san.cpp -- fvad_clips_plan_fbank, fvad_clips_fbank_check and fvad_mel_design_kaldi (csrc/host_clips_features.cpp, host
 // only) under AddressSanitizer + UBSan: seeded random length / skip / frame-parameter tables with values near UINT64_MAX for the
 // overflow paths.  Whatever the plan accepts must give L = ceil((len - skip) / step) >= win_length, T = 1 + (L - win_length) / hop
 // frames, slots of T * n_mels floats that start on 16-byte boundaries in clip order without overlapping, and a total that holds

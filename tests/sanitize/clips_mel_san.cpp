@@ -1,4 +1,4 @@
-// clips_mel_san.cpp -- fvad_clips_plan_mel, fvad_clips_mel_check and fvad_mel_design (csrc/host_clips_mel.cpp, host only) under
+// clips_mel_san.cpp -- fvad_clips_plan_mel, fvad_clips_mel_check and fvad_mel_design (csrc/host_clips_features.cpp, host only) under
 // AddressSanitizer + UBSan: seeded random length / skip / frame-parameter tables with values near UINT64_MAX for the overflow
 // paths.  Whatever the plan accepts must give L = ceil((len - skip) / step) >= n_fft / 2 + 1, T = floor(L / hop) >= 1 frames,
 // slots of T * n_mels floats that start on 16-byte boundaries in clip order without overlapping, and a total that holds them all

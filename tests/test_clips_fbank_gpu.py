@@ -339,3 +339,56 @@ def test_the_mel_export_is_untouched_by_a_fbank_call(gpu_ctx, steps_case):
     after = gpu_ctx.clips_export_mel(*args, step=3, skips=ar.skips(long_enough), hop=160, norm=(8.0, 4.0, 0.25))
     for f in ("out", "feat_max", "n_frames", "offsets", "best_channel", "best_rms", "runner_up_rms"):
         assert before[f].tobytes() == after[f].tobytes(), f
+
+
+# ------------------------------------------------------------------ the two families taking turns on one context
+@pytest.mark.parametrize("mel_shape,shape", [((8, 4, 3), (6, 8, 4, 3)), ((400, 160, 80), (400, 512, 160, 80))], ids=["8", "400+512"])
+def test_the_families_take_turns_on_one_context(fv, mel_shape, shape):
+    """mel, fbank (cmn on), mel (norm on), fbank (cmn off), mel on one context -- the first pair transforms at the same n_fft and
+    shares the context's cached tables, the second is the 400-point form beside the generic 512 -- each call byte for byte the same
+    call made first on a context of its own: features, n_frames, feat_max / means and offsets.  Clips of L = win,
+    win + 5 hop + 1 and 33 frames, from f32 and from PCM16 lanes, at step 1 and step 3"""
+    win, n_fft, hop, n_mels = shape
+    assert mel_shape[1:] == (hop, n_mels)
+    wm, Mm = fc.mc.hann(mel_shape[0]), fc.mc.matrix_for(mel_shape)
+    wf, Mf = fc.window_for(shape), fc.matrix_for(shape)
+    arenas = []
+    for pcm16 in (False, True):
+        ar = FbankArena(pcm16, seed=21)
+        for k, L in enumerate((win, win + 5 * hop + 1, win + 32 * hop)):
+            ar.add(L, 1, 0, C_=1 + k % 2, pick=k % 2, align=k, signal=fc.mc.SIGNALS[k])
+            ar.add(L, 3, k % 3, C_=1, align=k + 1, signal=fc.mc.SIGNALS[k + 3])
+        arenas.append(ar.build())
+    cap = sum((it["L"] // hop + 2) * n_mels + 4 for it in arenas[0].items)
+
+    def call(kind, ctx):
+        got = []
+        for ar in arenas:
+            dev = FbankDevice(ctx, ar, cap)
+            try:
+                for idx, step in ((list(range(0, len(ar.items), 2)), 1), (list(range(1, len(ar.items), 2)), 3)):
+                    if kind.startswith("mel"):
+                        r, own = Device.export(dev, idx, step, wm, Mm, hop, norm=(8.0, 4.0, 0.25) if kind == "mel+norm" else None), "feat_max"
+                        assert [int(t) for t in r["n_frames"]] == [ar.items[i]["L"] // hop for i in idx]
+                    else:
+                        r, own = dev.export(idx, step, wf, Mf, shape, scale=32768.0, cmn=kind == "fbank+cmn"), "means"
+                        assert [int(t) for t in r["n_frames"]] == [fc.n_frames(ar.items[i]["L"], win, hop) for i in idx]
+                    got.append([f.tobytes() for f in r["feats"]] + [r[k].tobytes() for k in ("n_frames", own, "offsets")])
+            finally:
+                dev.close()
+        return got
+
+    first = {}
+    for kind in ("mel", "fbank+cmn", "mel+norm", "fbank"):
+        ctx = fv.Context(0)
+        try:
+            first[kind] = call(kind, ctx)
+        finally:
+            ctx.close()
+    assert first["mel"] != first["mel+norm"] and first["fbank"] != first["fbank+cmn"]
+    ctx = fv.Context(0)
+    try:
+        for turn, kind in enumerate(("mel", "fbank+cmn", "mel+norm", "fbank", "mel")):
+            assert call(kind, ctx) == first[kind], (turn, kind)
+    finally:
+        ctx.close()

@@ -2,6 +2,8 @@
 fvad_clips_plan_fbank's counts and slots against python integers and every refusal, every rule of fvad_clips_fbank_check in its
 order, what run_clips and main() refuse before a context exists, the committed tolerance literal against its measurement, and
 the proof that the case table bites: eight wrong versions of the float64 model."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -144,6 +146,68 @@ def test_check_rules_in_order(fv):
     huge = dict(good, clips=[[0, 1, 0, 1 << 40]], skips=None, step=1, win_length=4, n_fft=4, hop=1, n_mels=1, window=np.ones(4, np.float32),
                 matrix=np.ones((1, 3), np.float32), n_samples=1 << 40, lane_stride=1 << 40, out_capacity=1 << 62)
     assert fv.clips_fbank_check(**huge)[0] == INVALID
+
+
+def test_check_without_the_frame_arrays(fv):
+    """n_frames and offsets NULL, as the host-output export calls the rules: the status and the total of the call with them, for
+    accepted and refused inputs of test_check_rules_in_order; an accepted input's total is the plan's"""
+    w, M = fc.povey(400), fc.matrix_for(fc.SHAPES[0])
+    clips = np.array([[0, 2, 10, 10 + 3000], [1, 1, 7, 7 + 5000]], np.uint64)
+    skips = [fc.phase_skip(10, 3, 2), fc.phase_skip(7, 3, 2)]
+    good = dict(d_src=0x10000, n_lanes=2, lane_stride=6000, n_samples=6000, clips=clips, out=0x20000, out_capacity=1 << 20, device_out=True, step=3,
+                skips=skips, win_length=400, n_fft=512, hop=160, window=w, n_mels=80, matrix=M, scale=32768.0, preemph=0.97, remove_dc=1,
+                floor=2.0 ** -23, cmn=1)
+    plan = fv.clips_plan_fbank([3000, 5000], skips, 3, 400, 160, 80)[2]
+
+    def raw(null, d_src, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, win_length, n_fft, hop, window, n_mels, matrix,
+            scale, preemph, remove_dc, floor, cmn):
+        r = np.ascontiguousarray(np.asarray(clips, np.uint64).reshape(-1, 4))
+        k = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32))
+        keep = [np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix)]
+        frames, offsets, total = np.zeros(len(r), np.uint64), np.zeros(len(r), np.uint64), C.c_uint64(0)
+        st = fv.lib().fvad_clips_fbank_check(fv.vp(d_src), F32, n_lanes, lane_stride, n_samples, r.ctypes.data_as(C.POINTER(C.c_uint64)), len(r), F32, fv.vp(out),
+                                             out_capacity, int(device_out), step, None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint32)), win_length,
+                                             n_fft, hop, fv.fptr(keep[0]), n_mels, fv.fptr(keep[1]), scale, preemph, remove_dc, floor, cmn,
+                                             None if null else frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             None if null else offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+        return st, int(total.value)
+    bad_w = w.copy()
+    bad_w[399] = np.inf
+    huge = dict(clips=[[0, 1, 0, 1 << 40]], skips=None, step=1, win_length=4, n_fft=4, hop=1, n_mels=1, window=np.ones(4, np.float32),
+                matrix=np.ones((1, 3), np.float32), n_samples=1 << 40, lane_stride=1 << 40, out_capacity=1 << 62)
+    table = [(dict(), 0), (dict(out_capacity=plan), 0), (dict(cmn=0, remove_dc=0, preemph=0.0), 0), (dict(device_out=False, out=0x20004), 0),
+             (dict(step=0), INVALID), (dict(win_length=513), INVALID), (dict(hop=401), INVALID), (dict(skips=[3, 0]), INVALID),
+             (dict(clips=[[0, 2, 10, 10 + 3 * 399], [1, 1, 7, 5007]]), INVALID), (dict(window=bad_w), INVALID), (dict(scale=0.0), INVALID),
+             (dict(cmn=2), INVALID), (dict(n_samples=5006), OUT_OF_RANGE), (dict(out_capacity=plan - 1), TOO_SMALL), (huge, INVALID)]
+    for kw, want in table:
+        args = dict(good, **kw)
+        with_arrays, without = raw(False, **args), raw(True, **args)
+        assert with_arrays[0] == want and without == with_arrays, kw
+        assert fv.clips_fbank_check(src_format=F32, **args)[::3] == with_arrays, kw
+        if want == 0:
+            assert without[1] == plan, kw
+
+
+def test_public_signatures_of_the_feature_calls(fv):
+    """the Python entry points of both families, as literals: names, order and defaults"""
+    import inspect
+    want = {
+        "Context.clips_export_mel": "(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, step=1, skips=None, hop=160, "
+                                    "floor=1e-10, norm=None, d_out=None, out_capacity=None)",
+        "Context.clips_export_fbank": "(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, n_fft=512, step=1, skips=None, "
+                                      "hop=160, scale=32768.0, preemph=0.97, remove_dc=True, floor=1.1920928955078125e-07, cmn=False, d_out=None, "
+                                      "out_capacity=None)",
+        "clips_plan_mel": "(lens, skips, step, n_fft, hop, n_mels)",
+        "clips_plan_fbank": "(lens, skips, step, win_length, hop, n_mels)",
+        "clips_mel_check": "(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, n_fft, hop, window, "
+                           "n_mels, matrix, floor, norm, out_format=0)",
+        "clips_fbank_check": "(d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, win_length, n_fft, "
+                             "hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, out_format=0)"}
+    for name, sig in want.items():
+        f = fv
+        for part in name.split("."):
+            f = getattr(f, part)
+        assert str(inspect.signature(f)) == sig, name
 
 
 # ------------------------------------------------------------------ the harness's refusals

@@ -2,6 +2,8 @@
 fvad_clips_plan_mel's counts and slots against python integers and every refusal, every rule of fvad_clips_mel_check in its
 order, what run_clips and main() refuse before a context exists, the committed tolerance literal against its measurement, and
 the proof that the case table bites: six wrong versions of the float64 model."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -132,6 +134,47 @@ def test_check_rules_in_order(fv):
     huge = dict(good, clips=[[0, 1, 0, 1 << 40]], skips=None, step=1, n_fft=4, hop=1, n_mels=1, window=np.ones(4, np.float32), matrix=np.ones((1, 3), np.float32),
                 n_samples=1 << 40, lane_stride=1 << 40, out_capacity=1 << 62)
     assert fv.clips_mel_check(**huge)[0] == INVALID
+
+
+def test_check_without_the_frame_arrays(fv):
+    """n_frames and offsets NULL, as the host-output export calls the rules: the status and the total of the call with them, for
+    accepted and refused inputs of test_check_rules_in_order; an accepted input's total is the plan's"""
+    w, M = mc.hann(400), mc.matrix_for((400, 160, 80))
+    clips = np.array([[0, 2, 10, 10 + 3000], [1, 1, 7, 7 + 5000]], np.uint64)
+    skips = [mc.phase_skip(10, 3, 2), mc.phase_skip(7, 3, 2)]
+    good = dict(d_src=0x10000, n_lanes=2, lane_stride=6000, n_samples=6000, clips=clips, out=0x20000, out_capacity=1 << 20, device_out=True, step=3,
+                skips=skips, n_fft=400, hop=160, window=w, n_mels=80, matrix=M, floor=1e-10, norm=(8, 4, 0.25))
+    plan = fv.clips_plan_mel([3000, 5000], skips, 3, 400, 160, 80)[2]
+
+    def raw(null, d_src, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips, n_fft, hop, window, n_mels, matrix, floor, norm):
+        r = np.ascontiguousarray(np.asarray(clips, np.uint64).reshape(-1, 4))
+        k = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32))
+        keep = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32)) for a in (window, matrix, norm)]
+        frames, offsets, total = np.zeros(len(r), np.uint64), np.zeros(len(r), np.uint64), C.c_uint64(0)
+
+        def ptr(a):
+            return None if a is None else fv.fptr(a)
+        st = fv.lib().fvad_clips_mel_check(fv.vp(d_src), F32, n_lanes, lane_stride, n_samples, r.ctypes.data_as(C.POINTER(C.c_uint64)), len(r), F32, fv.vp(out),
+                                           out_capacity, int(device_out), step, None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint32)), n_fft, hop,
+                                           ptr(keep[0]), n_mels, ptr(keep[1]), floor, ptr(keep[2]),
+                                           None if null else frames.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           None if null else offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+        return st, int(total.value)
+    bad_w = w.copy()
+    bad_w[399] = np.inf
+    huge = dict(clips=[[0, 1, 0, 1 << 40]], skips=None, step=1, n_fft=4, hop=1, n_mels=1, window=np.ones(4, np.float32), matrix=np.ones((1, 3), np.float32),
+                n_samples=1 << 40, lane_stride=1 << 40, out_capacity=1 << 62)
+    table = [(dict(), 0), (dict(out_capacity=plan), 0), (dict(norm=None), 0), (dict(device_out=False, out=0x20004), 0),
+             (dict(step=0), INVALID), (dict(hop=401), INVALID), (dict(skips=[3, 0]), INVALID), (dict(clips=[[0, 2, 10, 10 + 600], [1, 1, 7, 5007]]), INVALID),
+             (dict(window=bad_w), INVALID), (dict(floor=0.0), INVALID), (dict(n_samples=5006), OUT_OF_RANGE), (dict(out_capacity=plan - 1), TOO_SMALL),
+             (huge, INVALID)]
+    for kw, want in table:
+        args = dict(good, **kw)
+        with_arrays, without = raw(False, **args), raw(True, **args)
+        assert with_arrays[0] == want and without == with_arrays, kw
+        assert fv.clips_mel_check(src_format=F32, **args)[::3] == with_arrays, kw
+        if want == 0:
+            assert without[1] == plan, kw
 
 
 # ------------------------------------------------------------------ the harness's refusals

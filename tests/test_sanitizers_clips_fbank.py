@@ -1,4 +1,4 @@
-"""AddressSanitizer + UBSan over fvad_clips_plan_fbank, fvad_clips_fbank_check and fvad_mel_design_kaldi (host_clips_fbank.cpp,
+"""AddressSanitizer + UBSan over fvad_clips_plan_fbank, fvad_clips_fbank_check and fvad_mel_design_kaldi (host_clips_features.cpp,
 host only): the stand-alone driver tests/sanitize/clips_fbank_san.cpp feeds them seeded random length / skip / frame-parameter
 tables with values near UINT64_MAX, and checks with 128-bit arithmetic that whatever is accepted fits its total, that the slots
 do not overlap, that no frame leaves its clip, that the check agrees with the plan and that the designer writes its matrix and
@@ -19,7 +19,7 @@ def clips_fbank_san(tmp_path_factory):
     if not cxx:
         pytest.skip("no g++ for the sanitizer build")
     out = tmp_path_factory.mktemp("san") / "clips_fbank_san"
-    srcs = [os.path.join(CSRC, "host_clips_fbank.cpp"), os.path.join(ROOT, "tests", "sanitize", "clips_fbank_san.cpp")]
+    srcs = [os.path.join(CSRC, "host_clips_features.cpp"), os.path.join(ROOT, "tests", "sanitize", "clips_fbank_san.cpp")]
     cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), *srcs, "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -1,4 +1,4 @@
-"""AddressSanitizer + UBSan over fvad_clips_plan_mel, fvad_clips_mel_check and fvad_mel_design (host_clips_mel.cpp, host only):
+"""AddressSanitizer + UBSan over fvad_clips_plan_mel, fvad_clips_mel_check and fvad_mel_design (host_clips_features.cpp, host only):
 the stand-alone driver tests/sanitize/clips_mel_san.cpp feeds them seeded random length / skip / frame-parameter tables with
 values near UINT64_MAX, and checks with 128-bit arithmetic that whatever is accepted fits its total, that the slots do not
 overlap, that the check agrees with the plan and that the designer writes its matrix and nothing else.  The driver is a plain
@@ -19,7 +19,7 @@ def clips_mel_san(tmp_path_factory):
     if not cxx:
         pytest.skip("no g++ for the sanitizer build")
     out = tmp_path_factory.mktemp("san") / "clips_mel_san"
-    srcs = [os.path.join(CSRC, "host_clips_mel.cpp"), os.path.join(ROOT, "tests", "sanitize", "clips_mel_san.cpp")]
+    srcs = [os.path.join(CSRC, "host_clips_features.cpp"), os.path.join(ROOT, "tests", "sanitize", "clips_mel_san.cpp")]
     cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), *srcs, "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
