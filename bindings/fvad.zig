@@ -474,6 +474,13 @@ pub extern "c" fn fvad_clips_plan_fbank(lens: ?[*]const u64, skips: ?[*]const u3
 pub extern "c" fn fvad_clips_fbank_check(d_src: ?*const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: ?[*]const f32, n_mels: u32, matrix: ?[*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, offsets: ?[*]u64, total: ?*u64) c_int;
 pub extern "c" fn fvad_clips_export_fbank_device(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, means: ?[*]f32) c_int;
 pub extern "c" fn fvad_clips_export_fbank(ctx: *Ctx, d_src: *const anyopaque, src_format: c_int, n_lanes: usize, lane_stride: usize, n_samples: usize, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, means: ?[*]f32) c_int;
+// the two feature exports over the split source of fvad_clips_export_split (a run sliced in time): the contiguous calls' results, bit for bit
+pub extern "c" fn fvad_clips_split_mel_check(d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: ?[*]const f32, n_mels: u32, matrix: ?[*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, offsets: ?[*]u64, total: ?*u64) c_int;
+pub extern "c" fn fvad_clips_export_split_mel_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, feat_max: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_export_split_mel(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, floor: f32, norm: ?[*]const f32, n_frames: ?[*]u64, feat_max: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_split_fbank_check(d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: ?[*]const u64, n_clips: usize, out_format: c_int, out: ?*const anyopaque, out_capacity: usize, device_out: c_int, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: ?[*]const f32, n_mels: u32, matrix: ?[*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, offsets: ?[*]u64, total: ?*u64) c_int;
+pub extern "c" fn fvad_clips_export_split_fbank_device(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, d_out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, means: ?[*]f32) c_int;
+pub extern "c" fn fvad_clips_export_split_fbank(ctx: *Ctx, d_a: ?*const anyopaque, a_lanes: usize, a_stride: usize, a_samples: usize, d_b: ?*const anyopaque, b_lanes: usize, b_stride: usize, b_samples: usize, src_format: c_int, clips: [*]const u64, n_clips: usize, out_format: c_int, out: *anyopaque, out_capacity: usize, best_channel: ?[*]i32, best_rms: ?[*]f32, runner_up_rms: ?[*]f32, out_offsets: ?[*]u64, step: u32, skips: ?[*]const u32, win_length: u32, n_fft: u32, hop: u32, window: [*]const f32, n_mels: u32, matrix: [*]const f32, scale: f32, preemph: f32, remove_dc: c_int, floor: f32, cmn: c_int, n_frames: ?[*]u64, means: ?[*]f32) c_int;
 
 // resampling ingest: files at another rate filtered and re-timed into 48 kHz f32 lanes (a rational up/down polyphase resampler)
 pub extern "c" fn fvad_resample_ratio(rate_in: u32, rate_out: u32, up: *u32, down: *u32) c_int;

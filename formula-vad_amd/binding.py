@@ -402,6 +402,31 @@ SIGNATURES = {
                                           c_float_p, c_float_p, C.POINTER(C.c_uint64),
                                           C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
                                           C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_split_mel_check": (C.c_int, [vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.c_int,
+                                             C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_split_mel_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                     C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                                     C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                                     C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_export_split_mel": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                              C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                              C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p, C.c_float, c_float_p,
+                                              C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_split_fbank_check": (C.c_int, [vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz, C.c_int,
+                                               C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                               C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fvad_clips_export_split_fbank_device": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                       C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                                       C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                                       C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                                       C.POINTER(C.c_uint64), c_float_p]),
+    "fvad_clips_export_split_fbank": (C.c_int, [vp, vp, sz, sz, sz, vp, sz, sz, sz, C.c_int, C.POINTER(C.c_uint64), sz, C.c_int, vp, sz,
+                                                C.POINTER(C.c_int32), c_float_p, c_float_p, C.POINTER(C.c_uint64),
+                                                C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, c_float_p, C.c_uint32, c_float_p,
+                                                C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                                C.POINTER(C.c_uint64), c_float_p]),
     "fvad_clips_resample_check": (C.c_int, [C.c_uint32, C.c_uint32, c_float_p, C.c_uint32]),
     "fvad_clips_resample_tile": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "fvad_clips_plan_resampled": (C.c_int, [C.POINTER(C.c_uint64), sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
@@ -829,6 +854,17 @@ class Context:
                                            "matrix must be [n_mels][n_fft / 2 + 1] for the window's n_fft", step, skips, hop, params,
                                            "feat_max", d_out, out_capacity)
 
+    def clips_export_split_mel(self, a, b, src_pcm16, clips, window, matrix, step=1, skips=None, hop=160, floor=1e-10, norm=None,
+                               d_out=None, out_capacity=None):
+        """fvad_clips_export_split_mel (d_out None) or fvad_clips_export_split_mel_device: clips_export_mel over the split source
+        of clips_export_split (a, b, [n][CLIP_SPLIT_FIELDS] rows).  Returns what clips_export_mel returns."""
+        def params(n_fft, window, n_mels, matrix):
+            norm_ = None if norm is None else np.ascontiguousarray(np.asarray(norm, np.float32).reshape(3))
+            return (n_fft, hop, fptr(window), n_mels, fptr(matrix), floor, None if norm_ is None else fptr(norm_)), norm_
+        return self._clips_export_features("mel", (a, b, src_pcm16), clips, window, matrix, None,
+                                           "matrix must be [n_mels][n_fft / 2 + 1] for the window's n_fft", step, skips, hop, params,
+                                           "feat_max", d_out, out_capacity)
+
     def clips_export_fbank(self, d_src, src_pcm16, n_lanes, lane_stride, n_samples, clips, window, matrix, n_fft=512, step=1, skips=None,
                            hop=160, scale=32768.0, preemph=0.97, remove_dc=True, floor=FLT_EPSILON, cmn=False, d_out=None, out_capacity=None):
         """fvad_clips_export_fbank (d_out None: the features come back as a float32 array) or fvad_clips_export_fbank_device:
@@ -841,12 +877,30 @@ class Context:
         return self._clips_export_features("fbank", (d_src, src_pcm16, n_lanes, lane_stride, n_samples), clips, window, matrix, n_fft,
                                            "matrix must be [n_mels][n_fft / 2 + 1]", step, skips, hop, params, "means", d_out, out_capacity)
 
+    def clips_export_split_fbank(self, a, b, src_pcm16, clips, window, matrix, n_fft=512, step=1, skips=None, hop=160, scale=32768.0,
+                                 preemph=0.97, remove_dc=True, floor=FLT_EPSILON, cmn=False, d_out=None, out_capacity=None):
+        """fvad_clips_export_split_fbank (d_out None) or fvad_clips_export_split_fbank_device: clips_export_fbank over the split
+        source of clips_export_split.  Returns what clips_export_fbank returns."""
+        def params(win, window, n_mels, matrix):
+            return (win, int(n_fft), hop, fptr(window), n_mels, fptr(matrix), scale, preemph, int(remove_dc), floor, int(cmn)), None
+        return self._clips_export_features("fbank", (a, b, src_pcm16), clips, window, matrix, n_fft,
+                                           "matrix must be [n_mels][n_fft / 2 + 1]", step, skips, hop, params, "means", d_out, out_capacity)
+
     def _clips_export_features(self, family, src, clips, window, matrix, n_fft, matrix_why, step, skips, hop, params, extra, d_out, out_capacity):
         """the two feature exports: fvad_clips_export_<family> (+ "_device" with d_out) after fvad_clips_plan_<family>.  n_fft None:
         the window's length; params(taps, window, n_mels, matrix) -> (the family's arguments between skips and n_frames, what
-        they point into); extra: the result's own key, "feat_max" [n] or "means" [n][n_mels]"""
-        d_src, src_pcm16, n_lanes, lane_stride, n_samples = src
-        clips = _clip_rows(clips)
+        they point into); extra: the result's own key, "feat_max" [n] or "means" [n][n_mels].  src: (d_src, src_pcm16, n_lanes,
+        lane_stride, n_samples), or (a, b, src_pcm16) as for clips_export_split -- fvad_clips_export_split_<family>(_device) over
+        [n][CLIP_SPLIT_FIELDS] rows"""
+        split = len(src) == 3
+        if split:
+            a, b, src_pcm16 = src
+            clips = _clip_split_rows(clips)
+            lens, src_args = clips[:, 3] + clips[:, 6], (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3], CLIP_PCM16 if src_pcm16 else CLIP_F32)
+        else:
+            d_src, src_pcm16, n_lanes, lane_stride, n_samples = src
+            clips = _clip_rows(clips)
+            lens, src_args = clips[:, 3] - clips[:, 2], (vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples)
         n = clips.shape[0]
         window = np.ascontiguousarray(np.asarray(window, np.float32).reshape(-1))
         matrix = np.ascontiguousarray(np.asarray(matrix, np.float32))
@@ -855,17 +909,16 @@ class Context:
             raise ValueError(matrix_why)
         skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(n))
         own, keep = params(taps, window, n_mels, matrix)
-        frames, offsets, total = _clips_plan_features("fvad_clips_plan_" + family, clips[:, 3] - clips[:, 2], skips, step, taps, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
+        frames, offsets, total = _clips_plan_features("fvad_clips_plan_" + family, lens, skips, step, taps, hop, n_mels) if n else (np.zeros(0, np.uint64), None, 0)
         best, rms, runner, offs = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint64)
         n_frames, per_clip = np.zeros(n, np.uint64), np.zeros((n, n_mels) if extra == "means" else n, np.float32)
-        args = (self.h, vp(d_src), CLIP_PCM16 if src_pcm16 else CLIP_F32, n_lanes, lane_stride, n_samples,
-                clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
+        args = (self.h, *src_args, clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, CLIP_F32)
         info = (best.ctypes.data_as(C.POINTER(C.c_int32)), fptr(rms), fptr(runner), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
                 step, None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), *own,
                 n_frames.ctypes.data_as(C.POINTER(C.c_uint64)), fptr(per_clip))
         res = {"best_channel": best, "best_rms": rms, "runner_up_rms": runner, "offsets": offs, "total": total, "n_frames": n_frames,
                extra: per_clip}
-        name = "fvad_clips_export_" + family
+        name = ("fvad_clips_export_split_" if split else "fvad_clips_export_") + family
         if d_out is not None:
             self._ck(getattr(lib(), name + "_device")(*args, vp(d_out), total if out_capacity is None else out_capacity, *info), name + "_device")
             return res
@@ -1867,10 +1920,11 @@ def _clips_plan_features(name, lens, skips, step, taps, hop, n_mels):
 
 
 def _clips_features_check(name, d_src, src_format, n_lanes, lane_stride, n_samples, clips, out, out_capacity, device_out, step, skips,
-                          out_format, params):
+                          out_format, params, split=None):
     """fvad_clips_mel_check / fvad_clips_fbank_check (`name`).  params(p) is the family's arguments between skips and n_frames, p
-    turning a float32 array or None into a pointer or NULL"""
-    clips = None if clips is None else _clip_rows(clips)
+    turning a float32 array or None into a pointer or NULL.  split (a, b): fvad_clips_split_mel_check / _split_fbank_check over
+    split rows; d_src, n_lanes, lane_stride and n_samples are then not used"""
+    clips = None if clips is None else (_clip_split_rows if split else _clip_rows)(clips)
     n = 0 if clips is None else clips.shape[0]
     skips = None if skips is None else np.ascontiguousarray(np.asarray(skips, np.uint32).reshape(-1))
     keep = []
@@ -1881,7 +1935,9 @@ def _clips_features_check(name, d_src, src_format, n_lanes, lane_stride, n_sampl
         keep.append(np.ascontiguousarray(np.asarray(a, np.float32)))
         return fptr(keep[-1])
     n_frames, offsets, total = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), C.c_uint64(0)
-    st = getattr(lib(), name)(vp(d_src), src_format, n_lanes, lane_stride, n_samples,
+    a, b = split if split else (None, None)
+    src_args = (vp(a[0]), a[1], a[2], a[3], vp(b[0]), b[1], b[2], b[3], src_format) if split else (vp(d_src), src_format, n_lanes, lane_stride, n_samples)
+    st = getattr(lib(), name)(*src_args,
                               None if clips is None else clips.ctypes.data_as(C.POINTER(C.c_uint64)), n, out_format, vp(out),
                               out_capacity, int(device_out), int(step),
                               None if skips is None else skips.ctypes.data_as(C.POINTER(C.c_uint32)), *params(p),
@@ -1925,6 +1981,23 @@ def clips_fbank_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips,
                                  device_out, step, skips, out_format,
                                  lambda p: (int(win_length), int(n_fft), int(hop), p(window), int(n_mels), p(matrix), scale, preemph,
                                             int(remove_dc), floor, int(cmn)))
+
+
+def clips_split_mel_check(a, b, src_format, clips, out, out_capacity, device_out, step, skips, n_fft, hop, window, n_mels, matrix, floor,
+                          norm, out_format=CLIP_F32):
+    """fvad_clips_split_mel_check (host only; a, b as for Context.clips_export_split, `out` an address) -> (status, n_frames,
+    offsets, total), as clips_mel_check"""
+    return _clips_features_check("fvad_clips_split_mel_check", None, src_format, 0, 0, 0, clips, out, out_capacity, device_out, step, skips,
+                                 out_format, lambda p: (int(n_fft), int(hop), p(window), int(n_mels), p(matrix), floor, p(norm)), split=(a, b))
+
+
+def clips_split_fbank_check(a, b, src_format, clips, out, out_capacity, device_out, step, skips, win_length, n_fft, hop, window, n_mels,
+                            matrix, scale, preemph, remove_dc, floor, cmn, out_format=CLIP_F32):
+    """fvad_clips_split_fbank_check (host only) -> (status, n_frames, offsets, total), as clips_fbank_check"""
+    return _clips_features_check("fvad_clips_split_fbank_check", None, src_format, 0, 0, 0, clips, out, out_capacity, device_out, step, skips,
+                                 out_format,
+                                 lambda p: (int(win_length), int(n_fft), int(hop), p(window), int(n_mels), p(matrix), scale, preemph,
+                                            int(remove_dc), floor, int(cmn)), split=(a, b))
 
 
 def clips_resample_check(up, down, taps):

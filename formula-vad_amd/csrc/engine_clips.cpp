@@ -13,7 +13,8 @@
 //   Both in four forms (ClipForm of clips_rules.h): full rate, strided (kernels_clips_strided.hip), filtered
 //   (kernels_clips_fir.hip) and resampled (kernels_clips_resample.hip); the form's part is its taps as the gather walks them.
 // - fvad_clips_export_mel* and fvad_clips_export_fbank*: log-mel or Kaldi-style filter-bank features of the picked channel's
-//   strided stream (kernels_clips_mel.hip) in place of a gather, one form over a family (features_device, features_host); rules
+//   strided stream (kernels_clips_mel.hip) in place of a gather, one form over a family and over either source (features_device,
+//   features_host; fvad_clips_export_split_mel*, _split_fbank*: the split source's rows, tables and ClipSplitArgs); rules
 //   in clips_features.h, shared with the host-only fvad_clips_mel_check and fvad_clips_fbank_check; parts: window, matrix and
 //   the family's own two (the tiles' and clips' maxima, or the tiles' sums and the means).
 #include <algorithm>
@@ -113,6 +114,8 @@ ClipArgs source_args(const void* src, size_t lane_stride, int src_format, int ou
 
 ClipArgs& base(ClipArgs& a) { return a; }
 ClipArgs& base(ClipSplitArgs& a) { return a.c; }
+const ClipArgs& base(const ClipArgs& a) { return a; }
+const ClipArgs& base(const ClipSplitArgs& a) { return a.c; }
 template <typename B> constexpr bool kSplit = std::is_same<B, ClipSplitArgs>::value;
 
 // The device work of a call over source B: one allocation for the tables, the partials, the infos and the form's extra parts
@@ -327,6 +330,18 @@ struct SplitLanes {
     size_t n_clips;
 };
 
+// row c's pieces as the kernels address them (a piece of no samples is never addressed)
+ClipSplit split_of(const SplitLanes& s, const SplitRow& c)
+{
+    return ClipSplit{c.a_len ? c.a_lane * (uint64_t)s.a_stride + c.a_from : 0, c.a_len, c.b_len ? c.b_lane * (uint64_t)s.b_stride + c.b_from : 0, 0};
+}
+
+// the source's share of a split call's arguments
+ClipSplitArgs split_source_args(const SplitLanes& s, int out_format, void* d_out)
+{
+    return ClipSplitArgs{source_args(s.d_a, s.a_stride, s.format, out_format, d_out), s.d_b, s.b_stride, nullptr};
+}
+
 int check_split(const fvad_ctx* ctx, const char* who, const SplitLanes& s, const ClipOut& o, bool device_out, const ClipForm& form,
                 std::vector<uint64_t>& offsets, uint64_t& total)
 {
@@ -349,14 +364,11 @@ int export_split_device(fvad_ctx* ctx, const char* who, const SplitLanes& s, con
     const auto desc = [&](size_t i) {
         const SplitRow c = split_row(s.clips, i);
         const uint64_t len = c.a_len + c.b_len;
-        // (a piece of no samples is never addressed)
-        const ClipSplit sp{c.a_len ? c.a_lane * (uint64_t)s.a_stride + c.a_from : 0, c.a_len, c.b_len ? c.b_lane * (uint64_t)s.b_stride + c.b_from : 0, 0};
-        return ClipDesc{len, c.n_channels, 0, offsets[i], form_gather_tiles(form, i, len), form_skip(form, i), sp};
+        return ClipDesc{len, c.n_channels, 0, offsets[i], form_gather_tiles(form, i, len), form_skip(form, i), split_of(s, c)};
     };
     if (!build_tables(s.n_clips, true, desc, t)) return set_err(ctx, FVAD_ERR_INVALID_ARGUMENT, std::string(who) + ": more than 2^31 tiles in one call: export in batches"); // (the check has bounded both)
     hipSetDevice(ctx->device);
-    const ClipSplitArgs src{source_args(s.d_a, s.a_stride, s.format, o.format, o.p), s.d_b, s.b_stride, nullptr};
-    return run_form(ctx, who, src, t, form, o.rep);
+    return run_form(ctx, who, split_source_args(s, o.format, o.p), t, form, o.rep);
 }
 
 int export_split_host(fvad_ctx* ctx, const char* who, const SplitLanes& s, const ClipOut& o, const ClipForm& form)
@@ -384,14 +396,20 @@ struct FeatCall {
     float* per_clip;    // feat_max [n_clips] (log-mel) or means [n_clips][n_mels] (filter-bank)
 };
 
-// one timed launch of a family's list
-struct FeatLaunch {
+// one timed launch of a family's list, over the tile kernels' arguments A of the call's source (ClipFeatOf of kernels.h)
+template <typename A> struct FeatLaunch {
     const char* label;
-    int (*fn)(const ClipFeatArgs&, hipStream_t);
+    int (*fn)(const A&, hipStream_t);
     const char* what; // the call as FVAD_HIP would report it
     bool on;
 };
-#define FEAT_LAUNCH(label, fn, on) FeatLaunch{label, fn, "(hipError_t)" #fn "(a, ctx->stream)", on}
+#define FEAT_LAUNCH(label, fn, on) {label, fn, "(hipError_t)" #fn "(a, ctx->stream)", on}
+// the launches that read tables and features only serve either source on its ClipFeatArgs
+template <int (*Fn)(const ClipFeatArgs&, hipStream_t)> int feat_plain(const ClipFeatArgs& a, hipStream_t s) { return Fn(a, s); }
+template <int (*Fn)(const ClipFeatArgs&, hipStream_t)> int feat_plain(const ClipFeatSplitArgs& a, hipStream_t s) { return Fn(a.f, s); }
+#define FEAT_PLAIN(label, fn, on) {label, feat_plain<fn>, "(hipError_t)" #fn "(a, ctx->stream)", on}
+ClipFeatArgs with_source(const ClipFeatArgs& a, const ClipArgs&) { return a; }
+ClipFeatSplitArgs with_source(const ClipFeatArgs& a, const ClipSplitArgs& s) { return ClipFeatSplitArgs{a, s.b, s.b_stride, s.splits}; }
 
 // the matrix as the kernels read it: [bin][band]
 std::vector<float> bands_transposed(const float* matrix, uint32_t n_mels, uint32_t n_bins)
@@ -412,15 +430,35 @@ bool feature_tables(const Lanes& s, const uint32_t* skips, const std::vector<uin
     return build_tables(s.n_clips, false, desc, t);
 }
 
+bool feature_tables(const SplitLanes& s, const uint32_t* skips, const std::vector<uint64_t>& offsets, const std::vector<uint64_t>& frames, uint32_t tf, ClipTables& t)
+{
+    const auto desc = [&](size_t i) {
+        const SplitRow c = split_row(s.clips, i);
+        return ClipDesc{c.a_len + c.b_len, c.n_channels, 0, offsets[i], (frames[i] + tf - 1) / tf, skips ? skips[i] : 0, split_of(s, c)};
+    };
+    return build_tables(s.n_clips, true, desc, t);
+}
+
 int check_features(const Lanes& s, const ClipOut& o, int device_out, const FeatCall& fc, uint64_t* n_frames, uint64_t* offsets, uint64_t* total, const char** why)
 {
     return feat_check(s.d_src, s.format, s.n_lanes, s.lane_stride, s.n_samples, s.clips, s.n_clips, o.format, o.p, o.capacity, device_out, fc.f, fc.window,
                       fc.matrix, fc.c, n_frames, offsets, total, why);
 }
 
+int check_features(const SplitLanes& s, const ClipOut& o, int device_out, const FeatCall& fc, uint64_t* n_frames, uint64_t* offsets, uint64_t* total, const char** why)
+{
+    return feat_split_check(s.d_a, s.a_lanes, s.a_stride, s.a_samples, s.d_b, s.b_lanes, s.b_stride, s.b_samples, s.format, s.clips, s.n_clips, o.format, o.p,
+                            o.capacity, device_out, fc.f, fc.window, fc.matrix, fc.c, n_frames, offsets, total, why);
+}
+
+ClipArgs feature_source(const Lanes& s, const ClipOut& o) { return source_args(s.d_src, s.lane_stride, s.format, o.format, o.p); }
+ClipSplitArgs feature_source(const SplitLanes& s, const ClipOut& o) { return split_source_args(s, o.format, o.p); }
+
 // A family supplies its parameters (fc.f, fc.c), its two own parts -- a float per tile and per clip (the tiles' and the clips'
 // maxima) or n_mels of each (the tiles' sums and the clips' means) --, its launch list and, through the clip part, what it scatters.
-int features_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatCall& fc)
+// One form over either source (Src: Lanes or SplitLanes), which supplies its check, its tables and its share of the arguments.
+template <typename Src>
+int features_device(fvad_ctx* ctx, const Src& s, const ClipOut& o, const FeatCall& fc)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (s.n_clips == 0) return FVAD_OK;
@@ -446,8 +484,9 @@ int features_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatC
                                      {matrix_t.data(), nullptr, matrix_t.size() * sizeof(float), nullptr},
                                      {nullptr, nullptr, t.tiles * cells * sizeof(float), nullptr},
                                      {nullptr, per_clip.data(), per_clip.size() * sizeof(float), nullptr}};
-    auto features = [&](const ClipArgs& c, const Part* x) -> int {
-        a.c = c;
+    auto features = [&](const auto& src, const Part* x) -> int {
+        using A = typename ClipFeatOf<std::decay_t<decltype(src)>>::type;
+        a.c = base(src);
         a.window = reinterpret_cast<const float*>(x[kWindow].dev);
         a.matrix_t = reinterpret_cast<const float*>(x[kMatrix].dev);
         a.step = f.step;
@@ -472,29 +511,31 @@ int features_device(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatC
             if (fc.c.norm) { a.norm_range = fc.c.norm[0]; a.norm_offset = fc.c.norm[1]; a.norm_scale = fc.c.norm[2]; }
             a.fft400 = f.n_fft == 400 && !ctx->tune.clip_mel_generic;
         }
-        const FeatLaunch mel[] = {FEAT_LAUNCH(a.fft400 ? "clip_mel400" : "clip_mel", fvad_launch_clip_mel, true),
-                                  FEAT_LAUNCH("clip_mel_max", fvad_launch_clip_mel_max, true),
-                                  FEAT_LAUNCH("clip_mel_norm", fvad_launch_clip_mel_norm, fc.c.norm != nullptr)};
-        const FeatLaunch fbank[] = {FEAT_LAUNCH("clip_fbank", fvad_launch_clip_fbank, true),
-                                    FEAT_LAUNCH("clip_fbank_mean", fvad_launch_clip_fbank_mean, true),
-                                    FEAT_LAUNCH("clip_fbank_sub", fvad_launch_clip_fbank_sub, fc.c.cmn != 0)};
-        for (const FeatLaunch& l : f.snip ? fbank : mel) {
+        const A sa = with_source(a, src);
+        const FeatLaunch<A> mel[] = {FEAT_LAUNCH(a.fft400 ? "clip_mel400" : "clip_mel", fvad_launch_clip_mel, true),
+                                     FEAT_PLAIN("clip_mel_max", fvad_launch_clip_mel_max, true),
+                                     FEAT_PLAIN("clip_mel_norm", fvad_launch_clip_mel_norm, fc.c.norm != nullptr)};
+        const FeatLaunch<A> fbank[] = {FEAT_LAUNCH("clip_fbank", fvad_launch_clip_fbank, true),
+                                       FEAT_PLAIN("clip_fbank_mean", fvad_launch_clip_fbank_mean, true),
+                                       FEAT_PLAIN("clip_fbank_sub", fvad_launch_clip_fbank_sub, fc.c.cmn != 0)};
+        for (const FeatLaunch<A>& l : f.snip ? fbank : mel) {
             if (!l.on) continue;
             time_begin(ctx, l.label);
-            const hipError_t e = (hipError_t)l.fn(a, ctx->stream);
+            const hipError_t e = (hipError_t)l.fn(sa, ctx->stream);
             if (e != hipSuccess) return hip_fail(ctx, e, l.what);
             time_end(ctx);
         }
         return FVAD_OK;
     };
-    const int rc = run_clips(ctx, fc.who, source_args(s.d_src, s.lane_stride, s.format, o.format, o.p), t, parts, features, o.rep);
+    const int rc = run_clips(ctx, fc.who, feature_source(s, o), t, parts, features, o.rep);
     if (rc != FVAD_OK) return rc;
     if (fc.n_frames) std::copy(frames.begin(), frames.end(), fc.n_frames);
     if (fc.per_clip) std::copy(per_clip.begin(), per_clip.end(), fc.per_clip);
     return FVAD_OK;
 }
 
-int features_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatCall& fc)
+template <typename Src>
+int features_host(fvad_ctx* ctx, const Src& s, const ClipOut& o, const FeatCall& fc)
 {
     if (!ctx) return FVAD_ERR_INVALID_ARGUMENT;
     if (s.n_clips == 0) return FVAD_OK;
@@ -508,16 +549,16 @@ int features_host(fvad_ctx* ctx, const Lanes& s, const ClipOut& o, const FeatCal
 }
 
 // the two families' calls
-FeatCall mel_call(uint32_t step, const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix, float floor,
-                  const float* norm, uint64_t* n_frames, float* feat_max)
+FeatCall mel_call(const char* who, uint32_t step, const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix,
+                  float floor, const float* norm, uint64_t* n_frames, float* feat_max)
 {
-    return FeatCall{"fvad_clips_export_mel", Feat{step, skips, n_fft, n_fft, hop, n_mels, false}, window, matrix, FeatCond{floor, norm, 0.0f, 0.0f, 0, 0}, n_frames, feat_max};
+    return FeatCall{who, Feat{step, skips, n_fft, n_fft, hop, n_mels, false}, window, matrix, FeatCond{floor, norm, 0.0f, 0.0f, 0, 0}, n_frames, feat_max};
 }
 
-FeatCall fbank_call(uint32_t step, const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels,
+FeatCall fbank_call(const char* who, uint32_t step, const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels,
                     const float* matrix, float scale, float preemph, int remove_dc, float floor, int cmn, uint64_t* n_frames, float* means)
 {
-    return FeatCall{"fvad_clips_export_fbank", Feat{step, skips, win_length, n_fft, hop, n_mels, true}, window, matrix, FeatCond{floor, nullptr, scale, preemph, remove_dc, cmn}, n_frames, means};
+    return FeatCall{who, Feat{step, skips, win_length, n_fft, hop, n_mels, true}, window, matrix, FeatCond{floor, nullptr, scale, preemph, remove_dc, cmn}, n_frames, means};
 }
 
 // the argument rules of fvad_clips_plan: the full-rate slots
@@ -753,7 +794,7 @@ int fvad_clips_export_mel_device(fvad_ctx* ctx, const void* d_src, int src_forma
 {
     return features_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                       ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                      mel_call(step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
+                      mel_call("fvad_clips_export_mel", step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
 }
 
 int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -764,7 +805,7 @@ int fvad_clips_export_mel(fvad_ctx* ctx, const void* d_src, int src_format, size
 {
     return features_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                     ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                    mel_call(step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
+                    mel_call("fvad_clips_export_mel", step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
 }
 
 int fvad_clips_export_fbank_device(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -776,7 +817,7 @@ int fvad_clips_export_fbank_device(fvad_ctx* ctx, const void* d_src, int src_for
 {
     return features_device(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                         ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                        fbank_call(step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
+                        fbank_call("fvad_clips_export_fbank", step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
 }
 
 int fvad_clips_export_fbank(fvad_ctx* ctx, const void* d_src, int src_format, size_t n_lanes, size_t lane_stride, size_t n_samples,
@@ -787,7 +828,53 @@ int fvad_clips_export_fbank(fvad_ctx* ctx, const void* d_src, int src_format, si
 {
     return features_host(ctx, Lanes{d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips},
                       ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
-                      fbank_call(step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
+                      fbank_call("fvad_clips_export_fbank", step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
+}
+
+int fvad_clips_export_split_mel_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                       size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                                       int out_format, void* d_out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                       uint64_t* out_offsets, uint32_t step, const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window,
+                                       uint32_t n_mels, const float* matrix, float floor, const float* norm, uint64_t* n_frames, float* feat_max)
+{
+    return features_device(ctx, SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                mel_call("fvad_clips_export_split_mel", step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
+}
+
+int fvad_clips_export_split_mel(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                                int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                uint64_t* out_offsets, uint32_t step, const uint32_t* skips, uint32_t n_fft, uint32_t hop, const float* window,
+                                uint32_t n_mels, const float* matrix, float floor, const float* norm, uint64_t* n_frames, float* feat_max)
+{
+    return features_host(ctx, SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                mel_call("fvad_clips_export_split_mel", step, skips, n_fft, hop, window, n_mels, matrix, floor, norm, n_frames, feat_max));
+}
+
+int fvad_clips_export_split_fbank_device(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                         size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                                         int out_format, void* d_out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                         uint64_t* out_offsets, uint32_t step, const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop,
+                                         const float* window, uint32_t n_mels, const float* matrix, float scale, float preemph, int remove_dc, float floor,
+                                         int cmn, uint64_t* n_frames, float* means)
+{
+    return features_device(ctx, SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                ClipOut{out_format, d_out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                fbank_call("fvad_clips_export_split_fbank", step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
+}
+
+int fvad_clips_export_split_fbank(fvad_ctx* ctx, const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b,
+                                  size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips,
+                                  int out_format, void* out, size_t out_capacity, int32_t* best_channel, float* best_rms, float* runner_up_rms,
+                                  uint64_t* out_offsets, uint32_t step, const uint32_t* skips, uint32_t win_length, uint32_t n_fft, uint32_t hop,
+                                  const float* window, uint32_t n_mels, const float* matrix, float scale, float preemph, int remove_dc, float floor,
+                                  int cmn, uint64_t* n_frames, float* means)
+{
+    return features_host(ctx, SplitLanes{d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips},
+                ClipOut{out_format, out, out_capacity, {best_channel, best_rms, runner_up_rms, out_offsets}},
+                fbank_call("fvad_clips_export_split_fbank", step, skips, win_length, n_fft, hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn, n_frames, means));
 }
 
 } // extern "C"

@@ -1,8 +1,9 @@
 // host_clips_features.cpp -- what the feature clip exports offer without a device: the two band designers (fvad_mel_design:
 // Slaney's scale, area-normalised; fvad_mel_design_kaldi: HTK's scale as Kaldi's MelBanks has it), how many frames an export
 // writes and where (fvad_clips_plan_mel, fvad_clips_plan_fbank: one loop), and every argument rule of the exports
-// (fvad_clips_mel_check, fvad_clips_fbank_check: clips_features.h's feat_check).  Plain C++: tests/sanitize/clips_mel_san.cpp
-// and clips_fbank_san.cpp build this file alone.
+// (fvad_clips_mel_check, fvad_clips_fbank_check: clips_features.h's feat_check; fvad_clips_split_mel_check,
+// fvad_clips_split_fbank_check: its feat_split_check).  Plain C++: tests/sanitize/clips_mel_san.cpp, clips_fbank_san.cpp and
+// clips_feat_split_san.cpp build this file alone.
 #include <cmath>
 #include <vector>
 
@@ -113,6 +114,27 @@ int fvad_clips_fbank_check(const void* d_src, int src_format, size_t n_lanes, si
 {
     return feat_check(d_src, src_format, n_lanes, lane_stride, n_samples, clips, n_clips, out_format, out, out_capacity, device_out,
                       Feat{step, skips, win_length, n_fft, hop, n_mels, true}, window, matrix, FeatCond{floor, nullptr, scale, preemph, remove_dc, cmn}, n_frames, offsets, total, nullptr);
+}
+
+int fvad_clips_split_mel_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
+                               size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
+                               const void* out, size_t out_capacity, int device_out, uint32_t step, const uint32_t* skips, uint32_t n_fft,
+                               uint32_t hop, const float* window, uint32_t n_mels, const float* matrix, float floor, const float* norm,
+                               uint64_t* n_frames, uint64_t* offsets, uint64_t* total)
+{
+    return feat_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips, out_format, out, out_capacity,
+                            device_out, Feat{step, skips, n_fft, n_fft, hop, n_mels, false}, window, matrix, FeatCond{floor, norm, 0.0f, 0.0f, 0, 0}, n_frames, offsets, total, nullptr);
+}
+
+int fvad_clips_split_fbank_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,
+                                 size_t b_stride, size_t b_samples, int src_format, const uint64_t* clips, size_t n_clips, int out_format,
+                                 const void* out, size_t out_capacity, int device_out, uint32_t step, const uint32_t* skips,
+                                 uint32_t win_length, uint32_t n_fft, uint32_t hop, const float* window, uint32_t n_mels, const float* matrix,
+                                 float scale, float preemph, int remove_dc, float floor, int cmn, uint64_t* n_frames, uint64_t* offsets,
+                                 uint64_t* total)
+{
+    return feat_split_check(d_a, a_lanes, a_stride, a_samples, d_b, b_lanes, b_stride, b_samples, src_format, clips, n_clips, out_format, out, out_capacity,
+                            device_out, Feat{step, skips, win_length, n_fft, hop, n_mels, true}, window, matrix, FeatCond{floor, nullptr, scale, preemph, remove_dc, cmn}, n_frames, offsets, total, nullptr);
 }
 
 } // extern "C"

@@ -3,31 +3,6 @@
 // addresses here; nothing is read through d_a, d_b or out.
 #include "clips_split.h"
 
-namespace {
-
-// the bytes [lo, hi) a buffer of n_lanes lanes covers, saturating at the top of the address space
-struct Range { uint64_t lo, hi; };
-Range buffer_range(const void* p, uint64_t n_lanes, uint64_t stride, uint64_t n_samples, uint64_t bytes)
-{
-    const uint64_t lo = (uint64_t)(uintptr_t)p;
-    if (!p || n_lanes == 0) return {lo, lo};
-    uint64_t n, b, hi;
-    if (__builtin_mul_overflow(n_lanes - 1, n_lanes > 1 ? stride : 0, &n) || __builtin_add_overflow(n, n_samples, &n) ||
-        __builtin_mul_overflow(n, bytes, &b) || __builtin_add_overflow(lo, b, &hi))
-        return {lo, UINT64_MAX};
-    return {lo, hi};
-}
-bool overlap(Range x, Range y) { return x.lo < x.hi && y.lo < y.hi && x.lo < y.hi && y.lo < x.hi; }
-
-// one piece of a row inside its buffer (a piece of no samples takes nothing and has no rule)
-bool piece_ok(uint64_t lane, uint64_t n_channels, uint64_t from, uint64_t len, uint64_t n_lanes, uint64_t n_samples)
-{
-    if (len == 0) return true;
-    return from <= n_samples && len <= n_samples - from && lane < n_lanes && n_channels <= n_lanes - lane;
-}
-
-} // namespace
-
 namespace fvad {
 
 int clips_split_check(const void* d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void* d_b, size_t b_lanes,

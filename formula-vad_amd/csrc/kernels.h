@@ -541,6 +541,21 @@ int fvad_launch_clip_mel_norm(const ClipFeatArgs& a, hipStream_t stream);   // (
 int fvad_launch_clip_fbank(const ClipFeatArgs& a, hipStream_t stream);      // (after fvad_launch_clip_pick)
 int fvad_launch_clip_fbank_mean(const ClipFeatArgs& a, hipStream_t stream); // (after fvad_launch_clip_fbank)
 int fvad_launch_clip_fbank_sub(const ClipFeatArgs& a, hipStream_t stream);  // (after fvad_launch_clip_fbank_mean)
+// The split-source form (fvad_clips_export_split_mel*, _split_fbank*): f.c is the split call's ClipArgs (piece A's src and
+// lane_stride), and stream sample i of a clip is clip sample e = skip + i * step, in piece A when e < a_len, else in piece B at
+// e - a_len: the stride is counted from the clip's first sample and runs through the seam, as do the tiles and the frames.  Only
+// the two tile kernels read samples; every other launch above serves a split call on `f` as it is.
+struct ClipFeatSplitArgs {
+    ClipFeatArgs f;
+    const void* b;
+    uint64_t b_stride;
+    const ClipSplit* splits; // [f.c.n_clips] (device)
+};
+// the tile kernels' argument by source B
+template <typename B> struct ClipFeatOf { using type = ClipFeatArgs; };
+template <> struct ClipFeatOf<ClipSplitArgs> { using type = ClipFeatSplitArgs; };
+int fvad_launch_clip_mel(const ClipFeatSplitArgs& a, hipStream_t stream);   // (after fvad_launch_clip_pick on a.f.c)
+int fvad_launch_clip_fbank(const ClipFeatSplitArgs& a, hipStream_t stream); // (after fvad_launch_clip_pick on a.f.c)
 
 // ------------------------------------------------------------------ device-side ingest (kernels_ingest.hip)
 // fvad_ingest*: a work unit is a tile of one source -- kIngestTileBytes of its interleaved bytes rounded down to whole frames in

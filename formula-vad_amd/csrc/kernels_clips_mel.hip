@@ -40,6 +40,13 @@
 // Both families take one argument struct (ClipFeatArgs of kernels.h: the filter-bank fields behind the log-mel ones), count a
 // clip's frames and a tile's by feature_frames.h's functions, which the host rules use too (clip_stream_len, mel_tile), and
 // launch their tile kernels through one ladder (launch_tiles: the dynamic-LDS attribute, then the instance of the source's format).
+// The split-source exports (fvad_clips_export_split_mel*, _split_fbank*) are the three tile kernels with the source as a template
+// parameter (B: ClipArgs, or ClipSplitArgs -- a head piece in buffer A followed by a body piece in buffer B, kernels.h).  Stream
+// sample i is clip sample e = skip + i step, in A when e < a_len, else in B at e - a_len: the stride, the tiles and the frames are
+// counted from the clip's first sample, never from the seam.  Only mel_stage and MelRun::stream (the reflected taps) know the
+// source.  A tile wholly in one piece is staged as the contiguous source stages it, from that piece's pointer; the one tile per
+// clip that holds the seam is staged element by element into the SAME contiguous image at shift 0, so every later read, the LDS
+// sizes and the bank analysis above hold for both sources.  max, norm, mean and sub read tables and features only.
 // Resources (make resource-usage, gfx950): see the table in DESIGN 7.2; clip_mel400_kernel is LDS-bound at two workgroups per
 // CU (73.3 KB each: 177 VGPRs, two wavefronts per SIMD); clip_mel_kernel takes 28.0 KB at 400 / 160 (80 VGPRs, five workgroups per CU).
 #include <hip/hip_runtime.h>
@@ -83,36 +90,88 @@ __device__ inline MelTile mel_tile(const ClipFeatArgs& a, const ClipJob& j, uint
     return t;
 }
 
+__host__ __device__ inline const ClipFeatArgs& feat_args(const ClipFeatArgs& a) { return a; }
+__host__ __device__ inline const ClipFeatArgs& feat_args(const ClipFeatSplitArgs& a) { return a.f; }
+
+// where the picked channel's stream is, by source B: stream sample r is clip sample skip + r step, of one run or of two pieces
+template <typename S, typename B> struct MelRun;
+template <typename S> struct MelRun<S, ClipArgs> {
+    const S* pc; // stream sample 0: the picked channel's first kept sample
+    uint32_t step;
+    __device__ float stream(long long r) const { return to_f32(pc[(unsigned long long)r * step]); }
+};
+template <typename S> struct MelRun<S, ClipSplitArgs> {
+    const S *pa, *pb; // the picked channel's clip sample 0 in piece A and clip sample a_len in piece B
+    uint64_t a_len;
+    uint32_t skip, step;
+    __device__ float stream(long long r) const
+    {
+        const uint64_t e = skip + (unsigned long long)r * step; // < len: the stride's phase is the clip's, on either side of the seam
+        return to_f32(*(e < a_len ? pa + e : pb + (e - a_len))); // one load from the selected address
+    }
+};
+
 // the stream as a frame reads it: staged samples from LDS, the reflected ends from the clip itself
-template <typename S> struct MelSrc {
-    const S* pc;      // stream sample 0: the picked channel's first kept sample
+template <typename S, typename B> struct MelSrc {
+    MelRun<S, B> run;
     const float* lds; // stream sample w0
     long long w0, w1, L;
-    uint32_t step;
     __device__ float at(long long j) const
     {
         if (j >= w0 && j < w1) return lds[j - w0];
         const long long r = j < 0 ? -j : (j >= L ? 2 * (L - 1) - j : j); // 0 <= r < L: L >= n_fft / 2 + 1 (the plan)
-        return to_f32(pc[(unsigned long long)r * step]);
+        return run.stream(r);
     }
 };
 
+// n stream samples p[0], p[step], ... of one run into LDS; the first of them is at the returned address.  Ends with a barrier
 template <typename S>
-__device__ inline MelSrc<S> mel_stage(const ClipFeatArgs& a, const ClipJob& j, const MelTile& t, float* lds)
+__device__ inline const float* mel_stage_run(const S* p, int n, uint32_t step, float* lds)
+{
+    if constexpr (sizeof(S) == 4) {
+        if (step == 1) return lds + stage_tile(p, n, lds);
+        stage_tile_strided(p, n, step, lds);
+    } else {
+        for (int i = threadIdx.x; i < n; i += kThreads) lds[i] = to_f32(p[(uint32_t)i * step]); // (n - 1) step < 2^17
+        __syncthreads();
+    }
+    return lds;
+}
+
+template <typename S>
+__device__ inline MelSrc<S, ClipArgs> mel_stage(const ClipFeatArgs& a, const ClipJob& j, const MelTile& t, float* lds)
 {
     const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
     const S* pc = static_cast<const S*>(a.c.src) + j.src_off + (uint64_t)ch * a.c.lane_stride + j.skip;
-    const S* p = pc + (unsigned long long)t.w0 * a.step;
+    const float* first = mel_stage_run(pc + (unsigned long long)t.w0 * a.step, (int)(t.w1 - t.w0), a.step, lds);
+    return MelSrc<S, ClipArgs>{{pc, a.step}, first, t.w0, t.w1, t.L};
+}
+
+// A tile whose kept samples lie wholly in one piece is staged from that piece as the contiguous source stages it.  The tile that
+// holds the seam (at most one per clip) is staged element by element into the same contiguous image at shift 0, one dword or one
+// converting load per kept sample, the piece picked per element -- so every later read of the window is the contiguous form's.
+// Nothing outside either piece is read, and at a step above 1 no sample off the stride.
+template <typename S>
+__device__ inline MelSrc<S, ClipSplitArgs> mel_stage(const ClipFeatSplitArgs& s, const ClipJob& j, const MelTile& t, float* lds)
+{
+    const ClipFeatArgs& a = s.f;
+    const uint32_t ch = (uint32_t)a.c.infos[t.clip].best_channel;
+    const ClipSplit sp = s.splits[t.clip];
+    const S* pa = static_cast<const S*>(a.c.src) + sp.a_off + (uint64_t)ch * a.c.lane_stride;
+    const S* pb = static_cast<const S*>(s.b) + sp.b_off + (uint64_t)ch * s.b_stride;
     const int n = (int)(t.w1 - t.w0);
+    const uint64_t e0 = j.skip + (unsigned long long)t.w0 * a.step, e1 = e0 + (uint64_t)(n - 1) * a.step; // the first and last kept sample
     const float* first = lds;
-    if constexpr (sizeof(S) == 4) {
-        if (a.step == 1) first = lds + stage_tile(p, n, lds);
-        else stage_tile_strided(p, n, a.step, lds);
-    } else {
-        for (int i = threadIdx.x; i < n; i += kThreads) lds[i] = to_f32(p[(uint32_t)i * a.step]); // (n - 1) step < 2^17
+    if (e1 < sp.a_len) first = mel_stage_run(pa + e0, n, a.step, lds);
+    else if (e0 >= sp.a_len) first = mel_stage_run(pb + (e0 - sp.a_len), n, a.step, lds);
+    else {
+        for (int i = threadIdx.x; i < n; i += kThreads) {
+            const uint64_t e = e0 + (uint32_t)i * a.step;
+            lds[i] = to_f32(*(e < sp.a_len ? pa + e : pb + (e - sp.a_len)));
+        }
         __syncthreads();
     }
-    return MelSrc<S>{pc, first, t.w0, t.w1, t.L, a.step};
+    return MelSrc<S, ClipSplitArgs>{{pa, pb, sp.a_len, j.skip, a.step}, first, t.w0, t.w1, t.L};
 }
 
 __device__ inline float mel_feat(float mel, float floor, float log_floor) { return mel > floor ? log10f(mel) : log_floor; }
@@ -172,11 +231,12 @@ __device__ inline void fbank_condition(const ClipFeatArgs& a, const float* x, fl
 // ---------------------------------------------------------------------------- any even n_fft
 // kFbank: the filter-bank export's frames (snip_edges, conditioned, win taps zero-padded to n_fft, natural log) and, in place of
 // the tile's maximum, the tile's sum per band over ascending t by lane m
-template <typename S, bool kFbank>
-__global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipFeatArgs a)
+template <typename S, bool kFbank, typename B>
+__global__ __launch_bounds__(kThreads) void clip_mel_kernel(typename ClipFeatOf<B>::type args)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[kThreads / 64];
+    const ClipFeatArgs& a = feat_args(args);
     const int n_fft = a.pl.n, M = n_fft / 2, NB = M + 1, pad = M;
     int taps = n_fft;
     if constexpr (kFbank) taps = (int)a.win;
@@ -195,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel_kernel(ClipFeatArgs a)
     } else {
         for (int i = tid; i < n_fft; i += kThreads) s_win[i] = a.window[i];
     }
-    const MelSrc<S> src = mel_stage<S>(a, j, t, s_stage); // (ends with a barrier)
+    const auto src = mel_stage<S>(args, j, t, s_stage); // (ends with a barrier)
     float* out = static_cast<float*>(a.c.out) + j.out_off + (unsigned long long)t.t0 * a.n_mels;
     float vmax = -__builtin_inff(), vsum = 0.0f;
     for (int f = 0; f < t.nf; ++f) {
@@ -260,11 +320,12 @@ __device__ __forceinline__ void dft25(cpx (&v)[25], const float* __restrict__ tw
 
 } // namespace
 
-template <typename S>
-__global__ __launch_bounds__(kThreads) void clip_mel400_kernel(ClipFeatArgs a)
+template <typename S, typename B>
+__global__ __launch_bounds__(kThreads) void clip_mel400_kernel(typename ClipFeatOf<B>::type args)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[kThreads / 64];
+    const ClipFeatArgs& a = feat_args(args);
     constexpr int n_fft = 2 * kM4, pad = kM4;
     float* s_stage = sm;
     float* s_win = s_stage + mel_stage_floats(n_fft, a.hop, a.tile_frames);
@@ -278,7 +339,7 @@ __global__ __launch_bounds__(kThreads) void clip_mel400_kernel(ClipFeatArgs a)
     const MelTile t = mel_tile(a, j, clip);
     for (int i = tid; i < n_fft; i += kThreads) s_win[i] = a.window[i];
     for (int i = tid; i < kM4; i += kThreads) s_st[i] = a.pl.st[i];
-    const MelSrc<S> src = mel_stage<S>(a, j, t, s_stage); // (ends with a barrier)
+    const auto src = mel_stage<S>(args, j, t, s_stage); // (ends with a barrier)
 
     // ---- the transform.  Slots past the tile's last frame work on that last frame again (every lane takes part in the
     // exchanges); their slab rows are never read
@@ -420,23 +481,41 @@ __global__ __launch_bounds__(kThreads) void clip_fbank_sub_kernel(ClipFeatArgs a
 namespace {
 
 // one workgroup per tile with `lds` bytes of dynamic LDS (which may be above the default limit), the instance by the source's format
-using FeatKernel = void (*)(ClipFeatArgs);
-int launch_tiles(FeatKernel f32, FeatKernel i16, size_t lds, const ClipFeatArgs& a, hipStream_t stream)
+template <typename A>
+int launch_tiles(void (*f32)(A), void (*i16)(A), size_t lds, const A& a, hipStream_t stream)
 {
-    const FeatKernel k = a.c.src_i16 ? i16 : f32;
+    const ClipArgs& c = feat_args(a).c;
+    void (*const k)(A) = c.src_i16 ? i16 : f32;
     const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3(a.c.n_tiles), dim3(kThreads), lds, stream, a);
+    hipLaunchKernelGGL(k, dim3(c.n_tiles), dim3(kThreads), lds, stream, a);
     return (int)hipGetLastError();
+}
+
+template <typename B>
+int launch_fbank(const typename ClipFeatOf<B>::type& s, hipStream_t stream)
+{
+    const ClipFeatArgs& a = feat_args(s);
+    const size_t lds = mel_generic_lds(mel_stage_floats(a.win, a.hop, a.tile_frames), (uint32_t)a.pl.n); // win 400, n_fft 512, hop 160: 30.0 KB
+    return launch_tiles(clip_mel_kernel<float, true, B>, clip_mel_kernel<int16_t, true, B>, lds, s, stream);
+}
+
+template <typename B>
+int launch_mel(const typename ClipFeatOf<B>::type& s, hipStream_t stream)
+{
+    const ClipFeatArgs& a = feat_args(s);
+    const uint32_t n_fft = (uint32_t)a.pl.n, stage = mel_stage_floats(n_fft, a.hop, a.tile_frames);
+    // the 400-point form: 73.3 KB; the generic one: 28.0 KB at n_fft 400, hop 160, at most 68.0 KB
+    if (a.fft400) return launch_tiles(clip_mel400_kernel<float, B>, clip_mel400_kernel<int16_t, B>, (size_t)(stage + n_fft + kM4 + fvad::kFeatTileFrames * kSlab) * sizeof(float), s, stream);
+    return launch_tiles(clip_mel_kernel<float, false, B>, clip_mel_kernel<int16_t, false, B>, mel_generic_lds(stage, n_fft), s, stream);
 }
 
 } // namespace
 
-int fvad_launch_clip_fbank(const ClipFeatArgs& a, hipStream_t stream)
-{
-    const size_t lds = mel_generic_lds(mel_stage_floats(a.win, a.hop, a.tile_frames), (uint32_t)a.pl.n); // win 400, n_fft 512, hop 160: 30.0 KB
-    return launch_tiles(clip_mel_kernel<float, true>, clip_mel_kernel<int16_t, true>, lds, a, stream);
-}
+int fvad_launch_clip_fbank(const ClipFeatArgs& a, hipStream_t stream) { return launch_fbank<ClipArgs>(a, stream); }
+int fvad_launch_clip_fbank(const ClipFeatSplitArgs& a, hipStream_t stream) { return launch_fbank<ClipSplitArgs>(a, stream); }
+int fvad_launch_clip_mel(const ClipFeatArgs& a, hipStream_t stream) { return launch_mel<ClipArgs>(a, stream); }
+int fvad_launch_clip_mel(const ClipFeatSplitArgs& a, hipStream_t stream) { return launch_mel<ClipSplitArgs>(a, stream); }
 
 int fvad_launch_clip_fbank_mean(const ClipFeatArgs& a, hipStream_t stream)
 {
@@ -449,14 +528,6 @@ int fvad_launch_clip_fbank_sub(const ClipFeatArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(clip_fbank_sub_kernel, dim3(a.c.n_tiles), dim3(kThreads), 0, stream, a);
     return (int)hipGetLastError();
-}
-
-int fvad_launch_clip_mel(const ClipFeatArgs& a, hipStream_t stream)
-{
-    const uint32_t n_fft = (uint32_t)a.pl.n, stage = mel_stage_floats(n_fft, a.hop, a.tile_frames);
-    // the 400-point form: 73.3 KB; the generic one: 28.0 KB at n_fft 400, hop 160, at most 68.0 KB
-    if (a.fft400) return launch_tiles(clip_mel400_kernel<float>, clip_mel400_kernel<int16_t>, (size_t)(stage + n_fft + kM4 + fvad::kFeatTileFrames * kSlab) * sizeof(float), a, stream);
-    return launch_tiles(clip_mel_kernel<float, false>, clip_mel_kernel<int16_t, false>, mel_generic_lds(stage, n_fft), a, stream);
 }
 
 int fvad_launch_clip_mel_max(const ClipFeatArgs& a, hipStream_t stream)

@@ -575,7 +575,7 @@ FBANK = dict(step=3, win_length=400, n_fft=512, hop=160, n_mels=80, sample_rate=
              remove_dc=1, scale=32768.0, floor=fv.FLT_EPSILON)
 
 
-def _check_features(features, features_norm, slice_chunks):
+def _check_features(features, features_norm, slice_chunks, features_sliced=False):
     """ValueError for what run_clips does not offer with features, before any work"""
     if features not in CLIP_FEATURES:
         raise ValueError(f"features = {features!r}: one of {CLIP_FEATURES}")
@@ -585,8 +585,12 @@ def _check_features(features, features_norm, slice_chunks):
         raise ValueError("features_norm needs features")
     if features is not None and features_norm not in CLIP_FEATURES_NORM_OF[features]:
         raise ValueError(f"features_norm = {features_norm!r} with features = {features!r}: one of {CLIP_FEATURES_NORM_OF[features]}")
-    if features is not None and slice_chunks is not None:
-        raise ValueError("features with slice_chunks: the split-source form of fvad_clips_export_mel does not exist yet")
+    if features_sliced and (features is None or slice_chunks is None):
+        raise ValueError("features_sliced (--clips-features-sliced) needs both features and slice_chunks")
+    # the gate: sliced features are opt-in, so that a run written for the refusal still gets it
+    if features is not None and slice_chunks is not None and not features_sliced:
+        raise ValueError("features with slice_chunks: the split-source form of the feature export (fvad_clips_export_split_mel / "
+                         "_split_fbank) is opt-in: pass features_sliced=True (--clips-features-sliced)")
 
 
 def logmel_window():
@@ -601,12 +605,13 @@ def fbank_window():
     return ((0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))) ** 0.85).astype(np.float32)
 
 
-# what _features_share takes per kind of features: the parameters, the stream lengths L that have a frame (the skip rule), the
-# export's call with the kind's window and designer, and the manifest entry
+# what _features_share and _features_split take per kind of features: the parameters, the stream lengths L that have a frame (the
+# skip rule), the export's call with the kind's window and designer (src: the contiguous call's source, or with split the split
+# call's (a, b, src_pcm16)), and the manifest entry
 _FEATURES = {
     "logmel": dict(
         p=LOGMEL, keeps=lambda p, L: L >= p["n_fft"] // 2 + 1 and L >= p["hop"],
-        export=lambda ctx, p, src, rows, skips, norm: ctx.clips_export_mel(
+        export=lambda ctx, p, src, rows, skips, norm, split=False: (ctx.clips_export_split_mel if split else ctx.clips_export_mel)(
             *src, rows, logmel_window(), fv.mel_design(p["sample_rate"], p["n_fft"], p["n_mels"], p["fmin"], p["fmax"]), step=p["step"], skips=skips, hop=p["hop"], floor=p["floor"], norm=CLIP_FEATURES_NORM[norm]),
         entry=lambda p, file, T, first, res, j, norm: {
             "file": file, "frames": T, "n_mels": p["n_mels"], "n_fft": p["n_fft"], "hop": p["hop"],
@@ -615,7 +620,7 @@ _FEATURES = {
             "mel": {"design": "slaney", "fmin": p["fmin"], "fmax": p["fmax"]}}),
     "fbank": dict(
         p=FBANK, keeps=lambda p, L: L >= p["win_length"],
-        export=lambda ctx, p, src, rows, skips, norm: ctx.clips_export_fbank(
+        export=lambda ctx, p, src, rows, skips, norm, split=False: (ctx.clips_export_split_fbank if split else ctx.clips_export_fbank)(
             *src, rows, fbank_window(), fv.mel_design_kaldi(p["sample_rate"], p["n_fft"], p["n_mels"], p["low_freq"], p["high_freq"]), n_fft=p["n_fft"], step=p["step"], skips=skips, hop=p["hop"], scale=p["scale"], preemph=p["preemph"],
             remove_dc=p["remove_dc"], floor=p["floor"], cmn=norm == "cmn"),
         entry=lambda p, file, T, first, res, j, norm: dict({
@@ -659,6 +664,31 @@ def _features_share(ctx, r, insts, per_inst, lane0, n_channels, avail, out_dir, 
         path = os.path.join(out_dir, "{}-{:04d}-denoised.{}.npy".format(insts[i]["name"], k, features))
         np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
         manifests[i]["clips"][k]["features"] = fam["entry"](p, os.path.basename(path), T, int(rows[j, 2]) + int(skips[j]), res, j, features_norm)
+
+
+def _features_split(ctx, a, b, rows, owner, insts, out_dir, feats, skipped, features, features_norm):
+    """the features of a sliced run_clips: one fvad_clips_export_split_mel (or _split_fbank) over the denoised kind's due clips of
+    a slice -- the split rows of its clip export over the held tail `a` and the slice's lanes `b`, owner[q] = (instance, segment,
+    absolute sample_from) --, the files and entries of _features_share: the skips from the absolute sample_from, first_sample
+    absolute.  feats[i][segment] gets the entry; a clip too short for a frame is counted in skipped[i]"""
+    fam = _FEATURES[features]
+    p = fam["p"]
+    skips = fv.clips_phase_skips([a0 for _, _, a0 in owner], p["step"], CLIP_PHASE["denoised"])
+    keep = []
+    for q, (r, (i, _, _)) in enumerate(zip(rows, owner)):
+        if fam["keeps"](p, -(-(int(r[3] + r[6]) - int(skips[q])) // p["step"])):
+            keep.append(q)
+        else:
+            skipped[i] += 1
+    if not keep:
+        return
+    res = fam["export"](ctx, p, (a, b, False), [rows[q] for q in keep], skips[keep], features_norm, split=True)
+    for u, q in enumerate(keep):
+        i, j, a0 = owner[q]
+        o, T = int(res["offsets"][u]), int(res["n_frames"][u])
+        path = os.path.join(out_dir, "{}-{:04d}-denoised.{}.npy".format(insts[i]["name"], j, features))
+        np.save(path, res["out"][o:o + T * p["n_mels"]].reshape(T, p["n_mels"]))
+        feats[i][j] = fam["entry"](p, os.path.basename(path), T, a0 + int(skips[q]), res, u, features_norm)
 
 
 def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs, features=None, features_norm=None):
@@ -726,7 +756,8 @@ def _clips_share(ctx, plan, insts, audio, out_dir, pcm16, rates, firs, features=
 
 
 def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, devices=None, ingest="host", slice_chunks=None, info=None,
-              denoised_rate=48000, original_rate=48000, original_filter="none", denoised_filter="none", features=None, features_norm=None):
+              denoised_rate=48000, original_rate=48000, original_filter="none", denoised_filter="none", features=None, features_norm=None,
+              features_sliced=False):
     """The plan's speech clips -- what main.zig writes out for the recogniser downstream: one original and one denoised
     single-channel clip per completed segment, the quietest channel over the clip (Recorder.zig:113-164), cut and picked on the
     GPU so that only the clips cross PCIe.  Per share of instances (dealt to `devices` like run_plan): the instances denoised
@@ -774,8 +805,12 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     {file, frames, n_mels, n_fft, hop, sample_rate, first_sample, best_channel, max, floor, norm, mel: {design, fmin, fmax}}; a
     clip too short for one frame (under 201 samples at 16 kHz) has none and is counted in features_skipped.  features_norm
     "whisper": (max(x, max - 8) + 4) / 4 with the maximum taken per clip ("max" stays the un-normalised one).  An unknown
-    features or features_norm, features_norm without features, and features with slice_chunks (the split-source form of the
-    feature export does not exist yet) raise before any work.  With features None every file and manifest is what it was.
+    features or features_norm, features_norm without features, and features with slice_chunks but without features_sliced (the
+    split-source form of the feature export is opt-in) raise before any work.  With features None every file and manifest is
+    what it was.
+    features_sliced True (with features and slice_chunks; without either it raises before any work): the sliced run writes the
+    features too -- per slice one fvad_clips_export_split_mel / _split_fbank over the due denoised clips' rows, the same .npy
+    files, "features" entries and features_skipped as the unsliced run, byte for byte.
     features "fbank": Kaldi's filter-bank features in its place -- one fvad_clips_export_fbank with FBANK's parameters: the same
     samples (step 3, phase 2) times 32768, frames of 400 every 160 from the clip's first sample on (snip_edges), DC removed,
     pre-emphasis 0.97, the Povey window, a 512-point transform, fvad_mel_design_kaldi(16000, 512, 80, 20, 0), ln(max(.,
@@ -784,7 +819,7 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
     the clip's mean per band is subtracted (torchaudio's subtract_mean) and stated under "means".  "whisper" with "fbank" and
     "cmn" with "logmel" raise before any work."""
     _check_ingest(ingest)
-    _check_features(features, features_norm, slice_chunks)
+    _check_features(features, features_norm, slice_chunks, features_sliced)
     rates, firs = _clip_rates(original_rate, denoised_rate, original_filter, denoised_filter)
     plan = load_plan(plan_path)
     if slice_chunks is not None:
@@ -805,7 +840,7 @@ def run_clips(plan_path, out_dir, pcm16=False, ctx=None, synth_seed=None, device
                 if slice_chunks is None:
                     done[d] = _clips_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, rates, firs, features, features_norm)
                 else:
-                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates, firs)
+                    done[d] = _clips_sliced_share(ctxs[d], plan, insts_d, audio_d, out_dir, pcm16, slice_chunks, notes[d], rates, firs, features, features_norm)
             except Exception as e:  # re-raised below, in the caller's thread
                 errs.append(e)
 
@@ -886,7 +921,7 @@ class _HeldTails:
                 b[0], b[1] = None, 0
 
 
-def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note, rates, firs):
+def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, note, rates, firs, features=None, features_norm=None):
     """run_clips(slice_chunks=N) for the instances of one context -> [(segments, audit, manifest)] in the order given.
     Channel-count group after group, each in time slices [s0, s1) of N chunks read, denoised and band-summed as a sliced grid's
     (_slice_denoise_and_bands; audio mapped or raw), one single-config host batch per instance run on part by part (_HostParts).
@@ -898,7 +933,9 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
     chunk, so that the original audio's last samples are reached.  note: "held_peak_bytes", "slices".
     rates: a kind at 16000 exports with step 3, the skips from the clips' absolute sample_from (a clip's seam has no part in
     them); firs: a filtered kind exports with its step and taps, the filter running through the seam; the carry of the held
-    tails stays a step-1 export."""
+    tails stays a step-1 export.
+    features: where a slice's due denoised clips are exported, their features are too -- one split feature call over the same
+    rows (_features_split) --, so a clip gets its features when, and only if, its denoised clip is written."""
     if not audio:
         return []
     chunk, H, N, F = 24000, SLICE_HALO_CHUNKS, slice_chunks, plan["fft_size"]
@@ -918,6 +955,7 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
     segs_of, audits = [[] for _ in audio], [None] * len(audio)
     entries = [{} for _ in audio]                   # [instance]{(segment, kind): manifest entry}
     skipped = [{"original": 0, "denoised": 0} for _ in audio]
+    feats, feats_skipped = [{} for _ in audio], [0] * len(audio)   # [instance]{segment: the "features" entry}
     note.update(held_peak_bytes=0, slices=0)
     try:
         for k, nb in own.items():
@@ -983,6 +1021,8 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
                                 _write_clip(path, res["out"][o:o + n_clip], pcm16, rates[kind])
                                 entries[i][(j, kind)] = _clip_entry(path, res["best_channel"][q], res["best_rms"][q], res["runner_up_rms"][q],
                                                                     rates[kind], a0 + (0 if skips is None else int(skips[q])), n_clip, firs[kind])
+                            if features is not None and kind == "denoised":
+                                _features_split(ctx, t.a(), b, rows, owner, insts, out_dir, feats, feats_skipped, features, features_norm)
                         t.carry(b, start * chunk, s0 * chunk, s1 * chunk, min(need) if need else None)
                     note["held_peak_bytes"] = max(note["held_peak_bytes"], sum(t.bytes() for t in tails.values()))
                 for k, i in enumerate(members):
@@ -1004,8 +1044,12 @@ def _clips_sliced_share(ctx, plan, insts, audio, out_dir, pcm16, slice_chunks, n
             for kind in ("original", "denoised"):
                 if (j, kind) in entries[i]:
                     c[kind] = entries[i][(j, kind)]
+            if j in feats[i]:
+                c["features"] = feats[i][j]
             manifest["clips"].append(c)
         manifest["original_skipped"], manifest["denoised_skipped"] = skipped[i]["original"], skipped[i]["denoised"]
+        if features is not None:
+            manifest["features_skipped"] = feats_skipped[i]
         out.append((segs_of[i], audits[i], manifest))
     return out
 
@@ -2760,7 +2804,10 @@ def arg_parser():
                          "network's own 16 kHz samples (400-point Hann, hop 160, 80 Slaney bands, log10), as NAME-####-denoised.logmel.npy; "
                          "fbank -- Kaldi's filter-bank features of the same samples (frames of 400 every 160, DC removed, pre-emphasis 0.97, "
                          "Povey window, 512-point transform, 80 HTK-mel bands from 20 Hz, ln), as NAME-####-denoised.fbank.npy; "
-                         "not with --slice-chunks")
+                         "with --slice-chunks only together with --clips-features-sliced")
+    ap.add_argument("--clips-features-sliced", action="store_true",
+                    help="with --clips-features and --slice-chunks: write the features from the sliced run too (the split-source feature "
+                         "export, one call per slice); the same files and manifests as without --slice-chunks")
     ap.add_argument("--clips-features-norm", default=None, metavar="NORM",
                     help="with --clips-features logmel: whisper -- (max(x, max - 8) + 4) / 4, the maximum taken per clip; "
                          "with --clips-features fbank: cmn -- the clip's mean per band subtracted")
@@ -2828,9 +2875,9 @@ def _parse_denoised_rate(text):
 def main(argv=None):
     a = arg_parser().parse_args(argv)
     check_modes(a)
-    if (a.clips_features is not None or a.clips_features_norm is not None) and not a.export_clips:
-        raise ValueError("--clips-features and --clips-features-norm need --export-clips")
-    _check_features(a.clips_features, a.clips_features_norm, a.slice_chunks)
+    if (a.clips_features is not None or a.clips_features_norm is not None or a.clips_features_sliced) and not a.export_clips:
+        raise ValueError("--clips-features, --clips-features-norm and --clips-features-sliced need --export-clips")
+    _check_features(a.clips_features, a.clips_features_norm, a.slice_chunks, a.clips_features_sliced)
     devices = None if a.devices is None else [int(d) for d in a.devices.split(",") if d != ""]
     if a.export_denoised:
         kinds = None if a.denoised_kinds is None else tuple(k for k in a.denoised_kinds.split(",") if k != "")
@@ -2851,7 +2898,7 @@ def main(argv=None):
         text, _ = run_clips(a.input, a.export_clips, pcm16=a.clips_pcm16, synth_seed=a.synth_seed, devices=devices, ingest=a.ingest,
                             slice_chunks=a.slice_chunks, info=info, denoised_rate=a.clips_denoised_rate, original_rate=a.clips_original_rate,
                             original_filter=a.clips_original_filter, denoised_filter=a.clips_denoised_filter, features=a.clips_features,
-                            features_norm=a.clips_features_norm)
+                            features_norm=a.clips_features_norm, features_sliced=a.clips_features_sliced)
         sys.stdout.write(text)
         if info:
             sys.stdout.write(f"\n[{info['slices']} slices; held tails: {info['held_peak_bytes'] / 2 ** 20:.1f} MiB of device memory at most]\n")

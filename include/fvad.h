@@ -1127,7 +1127,7 @@ int fvad_clips_export_split_resampled(fvad_ctx *ctx, const void *d_a, size_t a_l
  * fvad_clips_export_mel_device / fvad_clips_export_mel: the full-rate call's arguments, then step, skips, n_fft, hop, window,
  *   n_mels, matrix, floor, norm (window, matrix, norm: host memory) and the two new reports (each may be NULL).  Every error
  *   comes back before any launch.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_mel400 or clip_mel, clip_mel_max and,
- *   with norm, clip_mel_norm.  The split-source form (sliced runs) does not exist yet. */
+ *   with norm, clip_mel_norm.  The split-source form (sliced runs) is fvad_clips_export_split_mel* below. */
 #define FVAD_CLIP_MEL_NFFT_MAX 2048
 #define FVAD_CLIP_MEL_BANDS_MAX 128
 int fvad_mel_design(double sample_rate, uint32_t n_fft, uint32_t n_mels, double fmin, double fmax, float *matrix);
@@ -1202,7 +1202,7 @@ int fvad_clips_export_mel(fvad_ctx *ctx, const void *d_src, int src_format, size
  * fvad_clips_export_fbank_device / fvad_clips_export_fbank: the full-rate call's arguments, then step, skips, win_length, n_fft,
  *   hop, window, n_mels, matrix, scale, preemph, remove_dc, floor, cmn (window, matrix: host memory) and the two reports.  Every
  *   error comes back before any launch.  fvad_ctx_kernel_times names clip_rms, clip_pick, clip_fbank, clip_fbank_mean (always)
- *   and, with cmn, clip_fbank_sub.  The split-source form (sliced runs) does not exist for these either. */
+ *   and, with cmn, clip_fbank_sub.  The split-source form (sliced runs) is fvad_clips_export_split_fbank* below. */
 int fvad_mel_design_kaldi(double sample_rate, uint32_t n_fft, uint32_t n_mels, double low_freq, double high_freq, float *matrix);
 int fvad_clips_plan_fbank(const uint64_t *lens, const uint32_t *skips, size_t n_clips, uint32_t step, uint32_t win_length,
                           uint32_t hop, uint32_t n_mels, uint64_t *n_frames, uint64_t *offsets, uint64_t *total);
@@ -1223,6 +1223,73 @@ int fvad_clips_export_fbank(fvad_ctx *ctx, const void *d_src, int src_format, si
                             const uint32_t *skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float *window,
                             uint32_t n_mels, const float *matrix, float scale, float preemph, int remove_dc, float floor, int cmn,
                             uint64_t *n_frames, float *means);
+
+/* ------------------------------------------------------------------ batch Recorder with a front end: features of split clips
+ * The feature exports over the split source of fvad_clips_export_split: the features of a run sliced in time, whose clips have
+ * their head in the held tail of earlier slices (buffer A) and their body in the current slice (buffer B).  Rows are
+ * FVAD_CLIP_SPLIT_FIELDS rows and the buffers are passed as there; everything behind the rows is the contiguous call's argument
+ * list, unchanged, and so are the reports.  fvad_clips_plan_mel and fvad_clips_plan_fbank plan them with lens[i] = a_len + b_len.
+ * - The mapping: stream sample i of a clip is clip sample e = skip + i * step, read from piece A at a_from + e when e < a_len,
+ *   else from piece B at b_from + (e - a_len).  The stride is counted from the clip's first sample and runs through the seam;
+ *   frames and tiles are counted from the clip's first kept sample, never from the seam.  Nothing outside either piece is read,
+ *   and at a step above 1 no sample off the stride.
+ * - INVARIANTS, bit for bit: every result -- n_frames, offsets, best_channel, both RMS values, feat_max or means, every feature,
+ *   with or without norm / cmn -- is the contiguous call's over the same samples laid out contiguously, wherever the seam is; a
+ *   clip's results do not depend on the other rows, their order, either piece's alignment or the call form; a refused call
+ *   launches nothing and writes nothing.
+ * - The rules, in the one order all six entry points report them in:
+ *   1. fvad_clips_split_check's down to the rows' own rule (a clip with both lengths 0 or no channels); directly behind its
+ *      format rule: window or matrix NULL ("NULL argument"), then out_format other than FVAD_CLIP_F32 ("features are f32: ...");
+ *   2. the family's rules as fvad_clips_mel_check / fvad_clips_fbank_check state them from the frame parameters on: step, n_fft,
+ *      (win_length,) hop, n_mels, every clip's skip, length and slot with len = a_len + b_len, a window or matrix value that is
+ *      not finite, the family's own conditions;
+ *   3. FVAD_ERR_OUT_OF_RANGE for a piece past its buffer's samples or lanes;
+ *   4. FVAD_ERR_BUFFER_TOO_SMALL for out_capacity below the plan's total;
+ *   5. the output overlapping a source;
+ *   6. more than 2^31 - 1 RMS units or tiles of frames in one call.
+ * fvad_clips_split_mel_check / fvad_clips_split_fbank_check (host only; pointers are addresses): these rules; n_frames, offsets and
+ *   *total (each may be NULL) are filled as far as the rules held.
+ * fvad_clips_export_split_mel(_device) / fvad_clips_export_split_fbank(_device): every error comes back before any launch.
+ *   fvad_ctx_kernel_times names clip_rms_split, clip_pick and the contiguous call's feature labels. */
+int fvad_clips_split_mel_check(const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b, size_t b_lanes,
+                               size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips, size_t n_clips,
+                               int out_format, const void *out, size_t out_capacity, int device_out, uint32_t step,
+                               const uint32_t *skips, uint32_t n_fft, uint32_t hop, const float *window, uint32_t n_mels,
+                               const float *matrix, float floor, const float *norm, uint64_t *n_frames, uint64_t *offsets,
+                               uint64_t *total);
+int fvad_clips_export_split_mel_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                       const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                       const uint64_t *clips, size_t n_clips, int out_format, void *d_out, size_t out_capacity,
+                                       int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
+                                       uint32_t step, const uint32_t *skips, uint32_t n_fft, uint32_t hop, const float *window,
+                                       uint32_t n_mels, const float *matrix, float floor, const float *norm, uint64_t *n_frames,
+                                       float *feat_max);
+int fvad_clips_export_split_mel(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b,
+                                size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips,
+                                size_t n_clips, int out_format, void *out, size_t out_capacity, int32_t *best_channel,
+                                float *best_rms, float *runner_up_rms, uint64_t *out_offsets, uint32_t step, const uint32_t *skips,
+                                uint32_t n_fft, uint32_t hop, const float *window, uint32_t n_mels, const float *matrix,
+                                float floor, const float *norm, uint64_t *n_frames, float *feat_max);
+int fvad_clips_split_fbank_check(const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b, size_t b_lanes,
+                                 size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips, size_t n_clips,
+                                 int out_format, const void *out, size_t out_capacity, int device_out, uint32_t step,
+                                 const uint32_t *skips, uint32_t win_length, uint32_t n_fft, uint32_t hop, const float *window,
+                                 uint32_t n_mels, const float *matrix, float scale, float preemph, int remove_dc, float floor,
+                                 int cmn, uint64_t *n_frames, uint64_t *offsets, uint64_t *total);
+int fvad_clips_export_split_fbank_device(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples,
+                                         const void *d_b, size_t b_lanes, size_t b_stride, size_t b_samples, int src_format,
+                                         const uint64_t *clips, size_t n_clips, int out_format, void *d_out, size_t out_capacity,
+                                         int32_t *best_channel, float *best_rms, float *runner_up_rms, uint64_t *out_offsets,
+                                         uint32_t step, const uint32_t *skips, uint32_t win_length, uint32_t n_fft, uint32_t hop,
+                                         const float *window, uint32_t n_mels, const float *matrix, float scale, float preemph,
+                                         int remove_dc, float floor, int cmn, uint64_t *n_frames, float *means);
+int fvad_clips_export_split_fbank(fvad_ctx *ctx, const void *d_a, size_t a_lanes, size_t a_stride, size_t a_samples, const void *d_b,
+                                  size_t b_lanes, size_t b_stride, size_t b_samples, int src_format, const uint64_t *clips,
+                                  size_t n_clips, int out_format, void *out, size_t out_capacity, int32_t *best_channel,
+                                  float *best_rms, float *runner_up_rms, uint64_t *out_offsets, uint32_t step, const uint32_t *skips,
+                                  uint32_t win_length, uint32_t n_fft, uint32_t hop, const float *window, uint32_t n_mels,
+                                  const float *matrix, float scale, float preemph, int remove_dc, float floor, int cmn,
+                                  uint64_t *n_frames, float *means);
 
 /* ------------------------------------------------------------------ device-side ingest: a corpus's bytes into planar lanes
  * The way in for the batch paths, as fvad_clips_* is the way out: the bytes of WAV data chunks go to the device as the files
